@@ -5,8 +5,13 @@ One "step" = one pass of the hot path (pileup histogram -> gates -> per-sample g
 rule) over the synthetic "testdata"-shaped batch (BASELINE.json configs[1]: 160 BAMs x 3
 refGenomes), with the packed read columns already resident in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets the workload up (one build of the dataset), warms up, times K steps, writes the last step's outputs with --dump-outputs
+and prints the line.  --full adds everything else the benchmark measures: the median of seven builds from resident records
+(roofline_from_records), overlapped passes, the coverage / annotation / distance / host-decode legs, the CPU baseline, the end-to-end
+launcher run and, at N = 1, the one-rank point of the strong-scaling cohort (the --no-* options below still switch legs of it off).
 
 Multi-GPU: contigs shard across ranks with no data-path collective.  With the plain argv and N > 1 the line that is
 printed is the STRONG one -- one cohort (the generator of BASELINE configs[3]'s per-GPU shard, 500 samples) through the product's N-rank
@@ -189,7 +194,54 @@ def parse():
     ap.add_argument("--no-annotation", action="store_true", help="skip the --db_ann codon-annotation kernel (BASELINE configs[4]) after the timed region")
     ap.add_argument("--host-threads", type=int, default=0)
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, default) or gloo (rehearsal of the N>1 path on a box with fewer GPUs than ranks)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: seven builds (roofline_from_records), overlapped passes, coverage / annotation / distance / "
+                                                        "host-decode legs, CPU baseline, end-to-end run, the one-rank strong-scaling point")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed (rank 0's site records) as DIR/<name>.npy")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+SITE_COLUMNS = ("tid", "pos", "cov", "n0", "n1", "n2", "n3", "pop_mask", "ind_mask", "refchar", "dropped")
+PASS_COUNTS = ("n_sites", "n_called_pop", "n_called_indiv", "n_events", "n_overflow", "algorithmic_bytes")
+
+
+def dump_outputs(out_dir, sites, sample_rows, n_samples, last_pass):
+    """--dump-outputs: the site records the last timed step handed back, as .npy files a second build's run can be compared with.
+      sites.npy         float64 [k, 11]            SITE_COLUMNS of each site (tid, pos, coverage, four allele counts, masks, reference char)
+      site_samples.npy  float32 [k, n_samples, 5]  per sample: coverage and the four allele counts (zeros where a sample holds nothing)
+      site_index.npy    float64 [k]                 the rows kept: all of them, or a fixed seeded sample when the whole would pass 64 MB
+      pass_counts.npy   float64 [6]                 PASS_COUNTS of the last step's statistics
+    sample_rows(idx) returns the SAMPLE_DTYPE rows [len(idx), n_samples] of the sites idx."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n, ns = len(sites), max(1, n_samples)
+    per_site = 8 * len(SITE_COLUMNS) + 4 * 5 * ns + 8
+    keep = min(n, (DUMP_LIMIT_BYTES - 4096) // per_site)
+    idx = np.arange(n) if keep == n else np.sort(np.random.default_rng(20240601).choice(n, keep, replace=False))
+    s = sites[idx]
+    cols = np.column_stack([s["tid"], s["pos"], s["cov"], s["n"], s["pop_mask"], s["ind_mask"], s["refchar"], s["dropped"]]).astype(np.float64)
+    rows = sample_rows(idx)
+    smp = np.concatenate([rows["cov"][..., None], rows["n"]], axis=-1).astype(np.float32).reshape(len(idx), ns, 5)
+    np.save(os.path.join(out_dir, "sites.npy"), cols.reshape(len(idx), len(SITE_COLUMNS)))
+    np.save(os.path.join(out_dir, "site_samples.npy"), smp)
+    np.save(os.path.join(out_dir, "site_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "pass_counts.npy"), np.array([float(last_pass[k]) for k in PASS_COUNTS], dtype=np.float64))
+
+
+def cell_rows(n_samples, row_off, cell_sample, cells):
+    """sample_rows() of dump_outputs for the cell form (sites own cells row_off[i]:row_off[i + 1]): dense rows of the chosen sites only."""
+    import numpy as np
+    from metasnv_amd import core
+    ro = np.asarray(row_off).astype(np.int64)
+
+    def rows(idx):
+        cnt = ro[idx + 1] - ro[idx]
+        which = np.repeat(np.arange(len(idx)), cnt)
+        src = np.repeat(ro[idx], cnt) + (np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt))
+        out = np.zeros((len(idx), max(1, n_samples)), dtype=core.SAMPLE_DTYPE)
+        out[which, cell_sample[src]] = cells[src]
+        return out
+    return rows
 
 
 def cpu_baseline(sp_kwargs, n_cpu_samples):
@@ -364,12 +416,13 @@ def launcher_command(n, argv, port=None):
             "--master-port", str(port or _free_port()), os.path.abspath(__file__)] + list(argv)
 
 
-def strong_run(a, rank, world, local, dist, brief=False):
+def strong_run(a, rank, world, local, dist, brief=False, dump=None):
     """ONE fixed cohort through the product's N-rank path (parallel.resident_project_run, the function metaSNV.py runs under
     torchrun; reference: the split pool, metaSNV.py:196-215 + createOptimumSplit.py:46-62): every rank generates ("decodes") 1/N of
     the samples' record streams, the contig owners come from the first round's length x coverage, the records travel in an
     all-to-all per round, every rank packs and uploads its contigs' share and runs K timed passes (barrier + sync on both sides, max
-    over ranks), then the coverage rows and the cell-form site records are gathered to rank 0.  Returns the JSON line (rank 0)."""
+    over ranks), then the coverage rows and the cell-form site records are gathered to rank 0.  Returns the JSON line (rank 0); with
+    `dump` a directory, rank 0 writes the gathered site records of the last timed pass there (dump_outputs)."""
     import numpy as np
     from metasnv_amd import core, parallel
     sp_kwargs, wl_label = workload_params(a, 0)            # the same cohort on every rank
@@ -397,6 +450,7 @@ def strong_run(a, rank, world, local, dist, brief=False):
         timing["alg"] = sts[-1]["algorithmic_bytes"]
         timing["called"] = sts[-1]["n_called_pop"]
         timing["total_ms"] = sum(x["ms_total"] for x in sts) / len(sts)
+        timing["last"] = sts[-1]
         return sts[-1]
 
     threads = a.host_threads or max(1, min(32, (os.cpu_count() or 8) // max(1, world)))
@@ -412,11 +466,16 @@ def strong_run(a, rank, world, local, dist, brief=False):
     info = m["dataset"]
     mine = np.array([timing["dt"], float(info["n_pileup_bases"]), timing["k_ms"], float(timing["alg"]), float(timing["called"]), float(m["sites_local"]),
                      float(m["cells_local"]), m["feed_s"], m["finalize_s"], m.get("gather_coverage_s", 0.0), m["gather_sites_s"], float(info["n_positions"]),
-                     float(m.get("inflated_record_bytes") or 0), float(info["device_bytes"]), timing["total_ms"], m["coverage"]["ms_coverage"]], dtype=np.float64)
+                     float(m.get("inflated_record_bytes") or 0), float(info["device_bytes"]), timing["total_ms"], m["coverage"]["ms_coverage"],
+                     float(timing["last"]["n_sites"]), float(timing["last"]["n_called_indiv"]), float(timing["last"]["n_events"]), float(timing["last"]["n_overflow"])], dtype=np.float64)
     allr = parallel.gather_fixed(mine)
     ctx.close()
     if rank != 0:
         return None
+    if dump:
+        last = {"n_sites": sum(r[16] for r in allr), "n_called_pop": sum(r[4] for r in allr), "n_called_indiv": sum(r[17] for r in allr),
+                "n_events": sum(r[18] for r in allr), "n_overflow": sum(r[19] for r in allr), "algorithmic_bytes": sum(r[3] for r in allr)}
+        dump_outputs(dump, res["sites"], cell_rows(sp.n_samples, res["row_off"], res["cell_sample"], res["cells"]), sp.n_samples, last)
     dt_max = max(float(r[0]) for r in allr)
     bases = [float(r[1]) for r in allr]
     gbs = [float(r[3]) / (float(r[2]) * 1e-3) / 1e9 if r[2] > 0 else 0.0 for r in allr]
@@ -486,7 +545,7 @@ def main():
         raise SystemExit("bench.py: no HIP device visible; the pileup path has no CPU fallback")
     mode = a.mode or ("weak" if a.workload == "testdata" else "strong")
     if mode == "strong":
-        line = strong_run(a, rank, world, local, dist)
+        line = strong_run(a, rank, world, local, dist, dump=a.dump_outputs)
         if rank == 0:
             print(json.dumps(line))
         parallel.finalize()
@@ -501,13 +560,14 @@ def main():
     from_records = None
     if os.environ.get("MSNV_PACK", "d")[0] != "h" and not a.build_from_host and a.workload == "testdata":      # (the larger shapes make their streams group by group: they do not fit host memory at once)
         # The dataset is built from RAW RECORDS RESIDENT IN HBM (msnv_dataset_add_sample_records_resident): the streams go up first, outside
-        # every timed region; then records -> packed columns -> tile index is timed -- seven builds (the first pays the allocations, the next two still miss the allocator's cache now and then; the median is quoted), the last one is kept for the passes.
+        # every timed region; then records -> packed columns -> tile index is timed -- with --full seven builds (the first pays the allocations, the next two still miss the allocator's cache now and then; the median is quoted), the last one is kept for the passes;
+        # a plain run builds once.
         t0 = time.perf_counter()
         rr = ResidentRecords(syn, sp.n_samples, local)
         t_synth = time.perf_counter() - t0
         builds = []
         ds = None
-        for rep in range(7):
+        for rep in range(7 if a.full else 1):
             if ds is not None:
                 ds.close()
             ds, info, pack_ms, fin_ms = rr.build(core, ctx, syn)
@@ -564,11 +624,16 @@ def main():
             ms_pileup.append(st["ms_pileup"]); ms_total.append(st["ms_total"])
     barrier()
     dt = time.perf_counter() - t0
+    # N > 1 with the plain argv: the headline is the strong cohort below, which writes its own outputs
+    strong_headline = world > 1 and a.mode is None and a.workload == "testdata" and not a.no_strong_extra
+    if a.dump_outputs and rank == 0 and not strong_headline:
+        sites, samples = ds.results()             # the site records of the last timed pass
+        dump_outputs(a.dump_outputs, sites, lambda idx: samples[idx], sp.n_samples, st)
 
-    # the same K passes with the tails overlapped on a second stream (reported beside the main line, never as `value`:
+    # (--full) the same K passes with the tails overlapped on a second stream (reported beside the main line, never as `value`:
     # the roofline above is measured on kernels that have the chip to themselves)
     overlapped = None
-    if not a.sync_each_step and not a.no_overlap_extra:
+    if a.full and not a.sync_each_step and not a.no_overlap_extra:
         ds.run_many(2, overlap=True)       # untimed: allocates the second set of per-pass intermediates and the second stream
         barrier()
         t0o = time.perf_counter()
@@ -600,7 +665,7 @@ def main():
         return None
 
     cov_extra = None
-    if rank == 0:
+    if a.full and rank == 0:
         # the qaCompute half of the path on the same resident columns (msnv_coverage_tiles), outside the timed region
         ms = []
         for _ in range(5):
@@ -612,7 +677,7 @@ def main():
                                   "counters": coverage_counters(cov_ms)}}
 
     ann_extra = None
-    if not a.no_annotation and rank == 0:
+    if a.full and not a.no_annotation and rank == 0:
         # configs[4]: gene / codon annotation of the called sites on the device (outside the timed region)
         import tempfile
         with tempfile.TemporaryDirectory() as td:
@@ -627,7 +692,7 @@ def main():
                          "kernel_ms": sum(ms) / len(ms), "first_call_s_incl_parse_upload": t_first}
 
     dist_extra = None
-    if not a.no_annotation and rank == 0 and a.workload == "testdata":
+    if a.full and not a.no_annotation and rank == 0 and a.workload == "testdata":
         # metaSNV_DistDiv.py --dist on the device, on a table of the size this workload's calls give
         # (samples x called positions; random frequencies, 10 % of the cells uninformative), outside the timed region
         import random
@@ -648,7 +713,7 @@ def main():
                           "table_bytes_read_per_pair": 16 * int(npos.value)}
 
     decode_extra = None
-    if not a.no_annotation and rank == 0 and world == 1 and a.workload == "testdata":
+    if a.full and not a.no_annotation and rank == 0 and world == 1 and a.workload == "testdata":
         # the host stage in front of the kernels -- 16 of the workload's samples written as BAM files and
         # read back through msnv_dataset_add_sample_bams (read + BGZF inflate + parse + pack) with 8 host threads, the blocks inflated
         # by the host decoder and on the device (csrc/inflate_k.hip); outside the timed region
@@ -755,7 +820,7 @@ def main():
             line["roofline"]["bound"] = "valu"
             line["roofline"]["bound_note"] = ("the counters (%s) put the kernel at %.0f %% of its vector-instruction issue slots: it is VALU-issue bound, not HBM bound; achieved / peak / frac "
                                               "are still the SURVEY 8d bytes over the kernel's time against the HBM peak" % (cnt["source"], 100.0 * cnt["valu_issue_share_of_this_run"]))
-        if from_records:
+        if from_records and a.full:
             # Second roofline block: the timed region starts at RAW alignment records resident in HBM -- the SURVEY 8d bytes and then some
             # (36-byte fixed part, read name, CIGAR, 4-bit bases, one byte of quality per base) -- and ends at the calls: the per-read stage
             # (kernels of csrc/devpack.hip; WALL milliseconds of the call, host side included), finalize (the tile index; wall milliseconds,
@@ -788,17 +853,17 @@ def main():
             line["distances"] = dist_extra
         if decode_extra:
             line["host_decode"] = decode_extra
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(sp_kwargs, min(a.cpu_samples, sp.n_samples))
-        if not a.no_annotation and world == 1 and a.workload == "testdata":
+        if a.full and not a.no_annotation and world == 1 and a.workload == "testdata":
             try:
                 ds.close(); ctx.close()                       # the launcher below is a process of its own with its own context
                 line["end_to_end"] = end_to_end(sp, syn, bases, a.host_threads or min(32, os.cpu_count() or 8), line.get("cpu_baseline", {}).get("value"))
             except Exception as e:                             # the extra must never cost the bench line
                 line["end_to_end"] = {"error": repr(e)}
     strong = None
-    if (world > 1 or (a.mode is None and a.workload == "testdata")) and not a.no_strong_extra and mode == "weak":
-        # (at N = 1 with the plain argv too: the one-rank point of the cohort the N > 1 lines are about -- the base of the scaling curve)
+    if (strong_headline or (a.full and (world > 1 or (a.mode is None and a.workload == "testdata")))) and not a.no_strong_extra and mode == "weak":
+        # (at N = 1 with --full too: the one-rank point of the cohort the N > 1 lines are about -- the base of the scaling curve)
         # the product's N-rank path on ONE fixed cohort (32 species x 300 kb, 160 samples carrying six each): what the weak line above
         # cannot show -- LPT imbalance, the all-to-all of the records, the gather to rank 0
         ds.close()
@@ -811,7 +876,7 @@ def main():
             # the cohort every rank count shares: the generator of one GPU's contig shard of BASELINE configs[3] (500 samples, sparse coverage,
             # 375 species x ~2 Mbp at the default scale), dealt to the N ranks by the product's own path
             b.workload, b.scale, b.species, b.contig_len, b.mean_cov, b.samples = "config4shard", (a.scale if a.scale is not None else 0.25), None, None, None, None
-        b.steps, b.warmup = max(3, min(a.steps, 10)), 1
+        b.steps, b.warmup = (a.steps, a.warmup) if strong_headline else (max(3, min(a.steps, 10)), 1)      # (the headline takes --steps / --warmup as given)
         # the extra must never cost the bench line: not by raising, and not by one rank waiting in a collective for a rank that is gone --
         # after `limit` seconds every rank leaves, rank 0 with the line it already has
         import threading
@@ -828,7 +893,7 @@ def main():
         watchdog.daemon = True
         watchdog.start()
         try:
-            strong = strong_run(b, rank, world, local, dist, brief=False)
+            strong = strong_run(b, rank, world, local, dist, brief=False, dump=a.dump_outputs if strong_headline else None)
         except Exception as e:
             strong = {"error": repr(e)}
         watchdog.cancel()
@@ -851,6 +916,8 @@ def main():
                 print(json.dumps(line))
         parallel.finalize()
         return
+    ds.close()
+    ctx.close()
     if rank == 0:
         print(json.dumps(line))
     parallel.finalize()

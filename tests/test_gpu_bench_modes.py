@@ -57,7 +57,7 @@ def test_one_rank_strong_rate_is_the_weak_rate():
 
 def test_two_ranks_with_the_plain_argv_print_the_strong_line_and_carry_the_weak_one():
     """N > 1 without --mode: the headline is the product's N-rank path on one cohort (scaling: strong), the weak replica line rides along;
-    --mode weak keeps the weak line as the headline with the strong block inside."""
+    --mode weak --full keeps the weak line as the headline with the strong block inside."""
     common = ["--gpus", "2", "--dist-backend", "gloo", "--steps", "3", "--warmup", "1", "--samples", "24", "--contig-len", "60000", "--no-cpu-baseline", "--no-annotation",
               "--no-overlap-extra", "--strong-extra-shape", "8,40000"]
     line = _bench(common)
@@ -65,8 +65,29 @@ def test_two_ranks_with_the_plain_argv_print_the_strong_line_and_carry_the_weak_
     assert len(line["config"]["pileup_bases_per_rank"]) == 2
     w = line["weak_replicas"]
     assert w["scaling"] == "weak" and w["value"] > 0 and w["roofline"]["frac"] > 0
-    line = _bench(common + ["--mode", "weak"])
+    line = _bench(common + ["--mode", "weak", "--full"])
     assert line["scaling"] == "weak" and line["n_gpus"] == 2
     st = line["strong_scaling"]
     assert "error" not in st, st
     assert st["scaling"] == "strong" and st["n_gpus"] == 2 and len(st["config"]["pileup_bases_per_rank"]) == 2 and st["value"] > 0
+
+
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """The plain argv times exactly --steps passes and prints the headline alone; --dump-outputs writes the last step's site records
+    (float arrays, at most 64 MB) and two runs of the same arguments, whatever their step counts, write the same arrays."""
+    import numpy as np
+    small = ["--gpus", "1", "--samples", "24", "--contig-len", "60000"]
+    one = _bench(small + ["--steps", "7", "--warmup", "1", "--dump-outputs", str(tmp_path / "a")])
+    two = _bench(small + ["--steps", "3", "--warmup", "2", "--dump-outputs", str(tmp_path / "b")])
+    assert one["steps"] == 7 and one["ms_per_step"] > 0 and one["value"] > 0 and two["steps"] == 3
+    for k in ("cpu_baseline", "end_to_end", "strong_scaling", "roofline_from_records", "overlapped_passes", "coverage_pass", "annotation"):
+        assert k not in one, k
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["pass_counts.npy", "site_index.npy", "site_samples.npy", "sites.npy"] and names == sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64 << 20
+    for f in names:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and x.shape == y.shape and (x == y).all(), f
+    sites, counts = np.load(tmp_path / "a" / "sites.npy"), np.load(tmp_path / "a" / "pass_counts.npy")
+    assert len(sites) > 0 and counts[1] == one["config"]["called_SNPs_lines_per_rank"][0] > 0
+    assert np.load(tmp_path / "a" / "site_samples.npy").shape == (len(sites), 24, 5)
