@@ -189,6 +189,27 @@ int msnv_parse_float(const char *text, double *value);
 int msnv_dist_file(msnv_ctx *ctx, const char *freq_path, const char *mann_path, const char *allele_path, double threshold,
                    int32_t *n_samples, uint64_t *n_positions, double *ms_kernel);
 
+/* metaSNV_DistDiv.py --div / --divNS (computeDiv / computeDivNS, metaSNV_DistDiv.py:144-301): pairwise nucleotide
+ * diversity of one species' *.filtered.freq table on the device, bit-exact with pandas / numpy (compute_diversity for
+ * every pair of samples: single rows and multi-allelic positions, numpy's pairwise summation in 8192-element blocks,
+ * pandas' Kahan groupby sum), divided by the coverage corrections on the host.
+ *   mode MSNV_DIV:    out_a = <species>.diversity, out_b = <species>.FST
+ *   mode MSNV_DIV_NS: out_a = <species>.N_diversity, out_b = <species>.S_diversity (MSNV_EDOMAIN when the table has
+ *                     no N row or no S row, where the reference raises)
+ *   matched:          keep only the positions filt_proportion keeps (the reference's --matched)
+ *   genome_length:    sum of bed_header's column 3 over the species' contigs (L)
+ *   horizontal / vertical: the species' Percentage_1x / Average_cov per sample of the table's header, n_samples_cov of each
+ *   row_order:        the permutation sort_index applies to the rows' contig:gene:pos keys (numpy's argsort of them,
+ *                     quicksort for MSNV_DIV, stable for MSNV_DIV_NS; identity when already sorted); must sort the keys
+ * Writes the lower-triangular matrices as DataFrame.to_csv(sep='\t') does.  Out pointers may be NULL; ms_kernel is the
+ * kernels' time summed over the tables. */
+#define MSNV_DIV    0
+#define MSNV_DIV_NS 1
+int msnv_div_file(msnv_ctx *ctx, const char *freq_path, int32_t mode, int32_t matched, int64_t genome_length,
+                  const double *horizontal, const double *vertical, int32_t n_samples_cov, const int64_t *row_order,
+                  uint64_t n_rows_order, const char *out_a, const char *out_b, int32_t *n_samples, uint64_t *n_rows,
+                  double *ms_kernel);
+
 /* subpopr's raw-SNV consumers.
  *
  * msnv_genotyping_subset -- src/subpopr/inst/getGenotypingSNVSubset.py:20-48: the positions listed in every

@@ -18,6 +18,7 @@ class MsnvError(RuntimeError):
 
 
 OK, EINVAL, EIO, EFORMAT, ENODEV, EHIP, ENOMEM, EDOMAIN, ECAPACITY = range(9)
+DIV, DIV_NS = 0, 1                                             # msnv_div_file modes (include/msnv.h)
 
 
 class Params(C.Structure):
@@ -170,6 +171,8 @@ SYMBOLS = [
     ("msnv_records_contig_bases", C.c_int, [_vp, C.c_uint64, C.c_int32, P(C.c_uint64)]),
     ("msnv_parse_float", C.c_int, [C.c_char_p, P(C.c_double)]),
     ("msnv_dist_file", C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_double, P(C.c_int32), P(C.c_uint64), P(C.c_double)]),
+    ("msnv_div_file", C.c_int, [_vp, C.c_char_p, C.c_int32, C.c_int32, C.c_int64, P(C.c_double), P(C.c_double), C.c_int32, P(C.c_int64),
+                                C.c_uint64, C.c_char_p, C.c_char_p, P(C.c_int32), P(C.c_uint64), P(C.c_double)]),
     ("msnv_genotyping_subset", C.c_int, [P(C.c_char_p), C.c_int32, P(C.c_char_p), C.c_int32, C.c_char_p, P(C.c_uint64), P(C.c_uint64)]),
     ("msnv_snv_allele_freq", C.c_int, [_vp, C.c_char_p, C.c_int32, P(C.c_uint64), P(C.c_double)]),
     ("msnv_format_float", C.c_int, [C.c_double, C.c_char_p, C.c_int32]),

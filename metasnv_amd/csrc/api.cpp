@@ -1827,6 +1827,26 @@ extern "C" int msnv_dist_file(msnv_ctx *ctx, const char *freq_path, const char *
     return dist_file(ctx, freq_path, mann_path, allele_path, threshold, n_samples, n_positions, ms_kernel);
 }
 
+// ------------------------------------------------------------------------------ --div / --divNS
+namespace msnv {
+int div_file(msnv_ctx *ctx, const char *freq_path, int32_t mode, int32_t matched, int64_t genome_length, const double *h, const double *v,
+             int32_t n_cov, const int64_t *row_order, uint64_t n_order, const char *out_a, const char *out_b, int32_t *n_samples_out,
+             uint64_t *n_rows_out, double *ms_kernel);
+}
+extern "C" int msnv_div_file(msnv_ctx *ctx, const char *freq_path, int32_t mode, int32_t matched, int64_t genome_length,
+                             const double *horizontal, const double *vertical, int32_t n_samples_cov, const int64_t *row_order,
+                             uint64_t n_rows_order, const char *out_a, const char *out_b, int32_t *n_samples, uint64_t *n_rows,
+                             double *ms_kernel) {
+    clear_error();
+    if (!ctx || !freq_path || !out_a || !out_b || (n_samples_cov > 0 && (!horizontal || !vertical)) || (n_rows_order > 0 && !row_order) || n_samples_cov < 0)
+        return fail(MSNV_EINVAL, "msnv_div_file: NULL argument");
+    if (mode != MSNV_DIV && mode != MSNV_DIV_NS) return fail(MSNV_EINVAL, "msnv_div_file: mode %d", mode);
+    if (int rc = dev_set_device(ctx->device)) return rc;
+    if (ms_kernel) *ms_kernel = 0;
+    return div_file(ctx, freq_path, mode, matched, genome_length, horizontal, vertical, n_samples_cov, row_order, n_rows_order, out_a, out_b,
+                    n_samples, n_rows, ms_kernel);
+}
+
 // ------------------------------------------------------------------------------ one-call forms
 extern "C" int msnv_call(msnv_ctx *ctx, const msnv_call_args *a) {
     clear_error();

@@ -1,7 +1,8 @@
 // metasnv_amd/csrc/dist.cpp -- host side of metaSNV_DistDiv.py --dist (metaSNV_DistDiv.py:105-124): read one
 // `<species>.filtered.freq` table the way `pd.read_table(f, index_col=0, na_values=['-1']).T` does, run the pair
 // kernel (dist_k.hip), write `<species>.mann.dist` / `<species>.allele.dist` the way `DataFrame.to_csv(sep='\t')` does
-// (header = tab + sample names, floats as repr(), NaN as the empty string).
+// (header = tab + sample names, floats as repr(), NaN as the empty string).  The reader and the matrix writer serve
+// --div / --divNS too (div.cpp).
 #include <cmath>
 #include <cstring>
 
@@ -64,7 +65,7 @@ static bool is_na_token(const char *s, size_t n) {            // '-1' (na_values
     return false;
 }
 
-static int write_matrix(const char *path, const std::vector<std::string> &names, const std::vector<double> &m) {
+int write_matrix(const char *path, const std::vector<std::string> &names, const std::vector<double> &m) {
     FILE *f = fopen(path, "w");
     if (!f) return fail(MSNV_EIO, "Cannot open %s", path);
     std::string line;
@@ -86,14 +87,14 @@ static int write_matrix(const char *path, const std::vector<std::string> &names,
     return MSNV_OK;
 }
 
-int dist_file(msnv_ctx *ctx, const char *freq_path, const char *mann_path, const char *allele_path, double threshold,
-              int32_t *n_samples_out, uint64_t *n_pos_out, double *ms_kernel) {
+// one *.filtered.freq table as pd.read_table(f, index_col=0, na_values=['-1']) reads it: the sample names of the
+// header, the row labels (kept only when asked: --div / --divNS key the rows by them) and the values, row-major
+int read_freq(const char *freq_path, std::vector<std::string> &names, std::vector<std::string> *labels, std::vector<double> &rows, uint64_t &n_pos) {
     FILE *in = fopen(freq_path, "r");
     if (!in) return fail(MSNV_EIO, "Cannot open %s", freq_path);
     char *line = nullptr; size_t cap = 0; ssize_t len;
-    std::vector<std::string> names;
-    std::vector<double> rows;                                   // [pos][sample]
-    uint64_t lineno = 0, n_pos = 0;
+    uint64_t lineno = 0;
+    n_pos = 0;
     while ((len = getline(&line, &cap, in)) >= 0) {
         ++lineno;
         while (len && (line[len - 1] == '\n' || line[len - 1] == '\r')) line[--len] = 0;
@@ -113,6 +114,7 @@ int dist_file(msnv_ctx *ctx, const char *freq_path, const char *mann_path, const
         if (len == 0) continue;                                 // pandas skips blank lines
         const char *s = line, *end = line + len;
         const char *t = (const char *)memchr(s, '\t', (size_t)(end - s));
+        if (labels) labels->emplace_back(s, t ? t : end);
         size_t col = 0;
         if (t) {
             s = t + 1;
@@ -135,6 +137,15 @@ int dist_file(msnv_ctx *ctx, const char *freq_path, const char *mann_path, const
     }
     free(line);
     fclose(in);
+    return MSNV_OK;
+}
+
+int dist_file(msnv_ctx *ctx, const char *freq_path, const char *mann_path, const char *allele_path, double threshold,
+              int32_t *n_samples_out, uint64_t *n_pos_out, double *ms_kernel) {
+    std::vector<std::string> names;
+    std::vector<double> rows;                                   // [pos][sample]
+    uint64_t n_pos = 0;
+    if (int rc = read_freq(freq_path, names, nullptr, rows, n_pos)) return rc;
     const size_t S = names.size();
     std::vector<double> xt(S * n_pos);                          // sample-major for the kernel
     for (uint64_t p = 0; p < n_pos; ++p) for (size_t s = 0; s < S; ++s) xt[s * n_pos + p] = rows[p * S + s];
