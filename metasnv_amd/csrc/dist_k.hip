@@ -5,10 +5,12 @@
 //     allele = (np.abs(d1 - d2) > 0.6).mean()    NaN compares False and still counts in the denominator
 //
 // Bit-exact floating point: pandas' nanmean is `values.sum() / count` on the float64 array with NaN replaced by 0,
-// and numpy's sum of a contiguous float64 array is its PAIRWISE summation (blocks of <= 128 elements accumulated in 8
-// interleaved partial sums combined as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the tail; longer arrays split at
-// n/2 rounded down to a multiple of 8, recursively).  One thread per sample pair replays exactly that order, so the
-// printed repr() of every distance equals the reference's.  No multiplications: nothing for the compiler to contract.
+// and numpy's sum of a contiguous float64 array is 0.0 plus the PAIRWISE sum of each 8192-element block (the reduction's
+// buffer size), added one block after the other.  The pairwise sum of one block: pieces of <= 128 elements accumulated in 8
+// interleaved partial sums combined as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the tail; longer pieces split at
+// n/2 rounded down to a multiple of 8, recursively.  One wavefront per sample pair replays exactly that order for any
+// table length (div_k.hip's np_sum is the same rule, one thread per sum), so the printed repr() of every distance
+// equals the reference's.  No multiplications: nothing for the compiler to contract.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,13 +32,20 @@ __device__ __forceinline__ double absdiff0(const double *__restrict__ x, const d
     return (a != a || b != b) ? 0.0 : fabs(a - b);            // NaN -> 0 (pandas nanops: fill_value 0)
 }
 
-// numpy's pairwise summation as data: the leaves (blocks of <= 128 elements, in array order) and the order in which their sums
-// are combined (a postfix program: 0 = take the next leaf, 1 = add the two on top) -- the same for every pair of samples,
-// built once on the host from n_pos.  ONE WAVEFRONT per pair of samples: eight lanes share a leaf, lane j accumulating the
-// elements j, 8 + j, 16 + j ... exactly like numpy's r[j], so every load instruction of the wavefront reads whole 64-byte lines
+// numpy's summation as data: the leaves (pieces of <= 128 elements, in array order, none crossing an 8192-element block) and
+// the order in which their sums are combined (a postfix program run on a stack that starts as [0.0]: 0 = take the next leaf,
+// 1 = add the two on top; every block ends with the 1 that folds it into the running total) -- the same for every pair of
+// samples, built once on the host from n_pos.  The stack never holds more than 1 + 8 values (a block splits 7 times at most;
+// s_stack has 64).  ONE WAVEFRONT per pair of samples: eight lanes share a leaf, lane j accumulating the elements
+// j, 8 + j, 16 + j ... exactly like numpy's r[j], so every load instruction of the wavefront reads whole 64-byte lines
 // (the first form had one thread per pair walking two rows: lane stride n_pos x 8 bytes, nothing coalesced, device recursion).
 struct DistLeaf { long lo; int n; int pad; };
-constexpr int DIST_MAX_LEAVES_LDS = 2048;                     // leaf sums kept in LDS (n_pos <= 262144); beyond that in global scratch
+// Leaf sums are kept in LDS up to 2048 leaves, beyond that in global scratch ([pair][leaf]).  A full block is exactly 64 leaves
+// and a partial one at most 65, so the shortest table in scratch has 31 full blocks and a last block of 65 leaves: n_pos =
+// 31 * 8192 + 7689 = 261641.  From there to 32 whole blocks (n_pos = 262144, LDS) the route alternates with the last block's
+// 64 or 65 leaves, and everything longer is in scratch: the route follows the leaf count, not the length.
+constexpr long DIST_BLOCK = 8192;                             // numpy's reduction buffer, in elements
+constexpr int DIST_MAX_LEAVES_LDS = 2048;
 
 __global__ __launch_bounds__(64) void msnv_dist_pairs(const double *__restrict__ xt, int n_samples, long n_pos, double threshold,
                                                       const DistLeaf *__restrict__ leaves, int n_leaves, const unsigned char *__restrict__ prog, int n_prog,
@@ -55,7 +64,7 @@ __global__ __launch_bounds__(64) void msnv_dist_pairs(const double *__restrict__
     for (int l = grp; l < n_leaves; l += 8) {
         const DistLeaf lf = leaves[l];
         double res;
-        if (lf.n < 8) {                                          // only a table shorter than 8 positions: plain left-to-right sum
+        if (lf.n < 8) {                                          // a table or a last block shorter than 8 positions: plain left-to-right sum
             res = 0.0;
             for (int k = 0; k < lf.n; ++k) res += absdiff0(x, y, lf.lo + k);
         } else {
@@ -80,12 +89,13 @@ __global__ __launch_bounds__(64) void msnv_dist_pairs(const double *__restrict__
     for (int o = 32; o >= 1; o >>= 1) { count += __shfl_xor(count, o); above += __shfl_xor(above, o); }
     __syncthreads();
     if (lane == 0) {
-        int sp = 0, next = 0;
+        int sp = 1, next = 0;
+        s_stack[0] = 0.0;                                        // the running total numpy's reduction starts from
         for (int k = 0; k < n_prog; ++k) {
             if (prog[k] == 0) s_stack[sp++] = leaf_sum[next++];
             else { --sp; s_stack[sp - 1] = s_stack[sp - 1] + s_stack[sp]; }
         }
-        const double sum = 0.0 + (n_leaves ? s_stack[0] : 0.0);
+        const double sum = s_stack[0];
         const double nanv = nan("");
         const double m = count > 0 ? sum / (double)count : nanv;
         const double al = n_pos > 0 ? (double)above / (double)n_pos : nanv;
@@ -114,7 +124,10 @@ int dev_dist(const double *xt_host, int n_samples, long n_pos, double threshold,
     HIP_TRY(hipMalloc(&d_a.p, std::max<size_t>(mb, 16)));
     if (n_pos > 0) HIP_TRY(hipMemcpyAsync(d_x.p, xt_host, (size_t)n_samples * n_pos * sizeof(double), hipMemcpyHostToDevice, st));
     std::vector<DistLeaf> leaves; std::vector<unsigned char> prog;
-    if (n_pos > 0) pairwise_plan(0, n_pos, leaves, prog);
+    for (long lo = 0; lo < n_pos; lo += DIST_BLOCK) {           // 0.0 + pw(block 0) + pw(block 1) + ...
+        pairwise_plan(lo, std::min(DIST_BLOCK, n_pos - lo), leaves, prog);
+        prog.push_back(1);
+    }
     const long n_pairs = (long)n_samples * (n_samples + 1) / 2;
     Buf d_l, d_p, d_s;
     HIP_TRY(hipMalloc(&d_l.p, std::max<size_t>(leaves.size() * sizeof(DistLeaf), 16)));

@@ -138,3 +138,14 @@ def test_random_tables_against_the_model(tmp_path):
     species["spMid"] = (12, 9000, [rnd.choice([2, 3, 4, 12]) for _ in range(300)], [0.02] * 10 + [0.15, 0.6])
     proj = _random_project(str(tmp_path / "m"), rnd, species)
     _check_against_model(proj, ["--div", "--divNS", "--matched"])
+
+
+def test_random_table_of_70_samples_against_the_model(tmp_path):
+    """msnv_div_pairs past 24 samples: 2 485 pairs through the triangle unranking and the i * n_samples + j stores.  Few rows,
+    so that the model (one pair at a time) stays affordable; an all-NaN and two NaN-heavy samples, groups up to m = 12."""
+    rnd = random.Random(70)
+    species = {"spWide": (70, 260, [2] * 14 + [3] * 6 + [4, 5, 12], [0.05] * 66 + [0.7, 1.0, 0.02, 0.5])}
+    proj = _random_project(str(tmp_path), rnd, species)
+    assert len(open(os.path.join(proj, "filtered", "pop", "spWide.filtered.freq")).readline().split("\t")) == 71
+    _check_against_model(proj, ["--div", "--divNS"])
+    _check_against_model(proj, ["--div", "--matched"])

@@ -1138,7 +1138,7 @@ def test_distances_random_tables_against_pandas(tmp_path):
     from metasnv_amd import _lib
     ctx = core.Context(0)
     rnd = random.Random(4)
-    for n_pos, S in [(1, 3), (7, 4), (8, 4), (9, 5), (127, 6), (128, 6), (129, 6), (136, 3), (257, 5), (1000, 9), (2049, 4), (5003, 12)]:
+    for n_pos, S in [(1, 3), (7, 4), (8, 4), (9, 5), (127, 6), (128, 6), (129, 6), (136, 3), (257, 5), (1000, 9), (2049, 4), (5003, 12), (8193, 4), (16385, 5)]:
         names = ["smp%d.bam" % i for i in range(S)]
         path = str(tmp_path / ("t%d.filtered.freq" % n_pos))
         with open(path, "w") as f:
@@ -1437,6 +1437,27 @@ def test_allele_bookkeeping_follows_the_sampled_mismatch_rate(error_rate, expect
     assert prod[3]["n_events"] == 0 if expect_planes else prod[3]["n_events"] > 0
 
 
+def _filter_two_formulas(lines, names, soi_names, sp, cc, p):
+    """The rows of <sp>.filtered.freq by the reference's formulas (metaSNV_Filtering.py:183-231) evaluated in Python on the text
+    of called_SNPs: the position filter over the species' samples of interest, then count / coverage or -1 per sample."""
+    idx = [names.index(n) for n in soi_names]
+    want = ""
+    for line in lines.splitlines():
+        w = line.split()
+        if w[0].split(".")[0] != sp:
+            continue
+        c = list(map(int, w[4].split("|")))
+        good = sum(1 for i in idx if not (c[i] < cc or c[i] == 0))
+        if float(good) / len(idx) < p:
+            continue
+        for snp in w[5].split(","):
+            x = snp.split("|")
+            n = list(map(float, x[3:]))
+            fr = [n[i] / c[i] if (c[i] >= cc and c[i] != 0) else -1 for i in idx]
+            want += ":".join(w[:4]) + ">" + x[1] + ":" + x[2] + "\t" + "\t".join(str(v) for v in fr) + "\n"
+    return want
+
+
 def test_filtering_random_tables_against_python_formulas(tmp_path):
     """FILTER II on random called_SNPs-like text (zero coverages, huge coverages -> exponent-form repr, several alleles per
     line, species not of interest, thresholds on both sides of every gate) against the reference's formulas
@@ -1477,22 +1498,98 @@ def test_filtering_random_tables_against_python_formulas(tmp_path):
             if sp not in soi:
                 assert not os.path.exists(path)
                 continue
-            idx = [names.index(n) for n in soi[sp]]
-            want = ""
-            for line in lines.splitlines():
-                w = line.split()
-                if w[0].split(".")[0] != sp:
-                    continue
-                c = list(map(int, w[4].split("|")))
-                good = sum(1 for i in idx if not (c[i] < cc or c[i] == 0))
-                if float(good) / len(idx) < p:
-                    continue
-                for snp in w[5].split(","):
-                    x = snp.split("|")
-                    n = list(map(float, x[3:]))
-                    fr = [n[i] / c[i] if (c[i] >= cc and c[i] != 0) else -1 for i in idx]
-                    want += ":".join(w[:4]) + ">" + x[1] + ":" + x[2] + "\t" + "\t".join(str(v) for v in fr) + "\n"
+            want = _filter_two_formulas(lines, names, soi[sp], sp, cc, p)
             if want:
                 assert open(path).read() == "\t" + "\t".join(soi[sp]) + "\n" + want, (trial, sp)
             else:
                 assert not os.path.exists(path)
+
+
+@pytest.mark.parametrize("S", [64, 65, 130, 200])
+def test_filtering_more_samples_than_lanes_against_python_formulas(tmp_path, S):
+    """msnv_filter_freq strides its 64 lanes over a species' samples of interest and reduces `good` across the wavefront: here the
+    SoI sets have 1, 63, 64, 65, 129 and S members (second and third trips of the lane loop, a partly filled last trip), scattered
+    non-contiguously over S samples, and crafted lines put good / n_soi exactly on -p and one sample to either side of it (13 of 65
+    at -p 0.2, 32 of 64 at -p 0.5 ...).  Same Python restatement of metaSNV_Filtering.py:183-231 as the test above; the last run
+    adds --ind."""
+    import random
+    from metasnv_amd import filtering
+    rnd = random.Random(640 + S)
+    names = ["s%d.bam" % i for i in range(S)]
+    sizes = sorted({k for k in (1, 63, 64, 65, 129, S) if k <= S})
+    species = ["sp%d" % k for k in sizes]
+    members = {}
+    for k, sp in zip(sizes, species):
+        while True:
+            idx = sorted(rnd.sample(range(S), k))
+            if k in (1, S) or idx[-1] - idx[0] + 1 > k:         # holes in the index set (impossible only for 1 and for all)
+                break
+        members[sp] = idx
+    cc, ties = 5.0, 0
+    for run, p in enumerate([0.2, 0.5]):
+        proj = str(tmp_path / ("p%d" % run) / "proj")
+        os.makedirs(os.path.join(proj, "snpCaller"))
+        open(os.path.join(proj, "all_samples"), "w").write("".join("/d/%s\n" % n for n in names))
+        cov = "\t" + "\t".join(names) + "\nTaxId\t" + "\t".join(["Average_cov"] * S) + "\n"
+        per = "\t" + "\t".join(names) + "\nTaxId\t" + "\t".join(["Percentage_1x"] * S) + "\n"
+        for sp in species + ["spNone"]:                          # spNone: no sample qualifies
+            inside = set(members.get(sp, []))
+            cov += sp + "\t" + "\t".join("%f" % (rnd.choice([5.0, 20.0]) if i in inside else rnd.choice([0.0, 4.5, 20.0])) for i in range(S)) + "\n"
+            per += sp + "\t" + "\t".join("%f" % (rnd.choice([40.0, 90.0]) if i in inside else 5.0) for i in range(S)) + "\n"
+        open(os.path.join(proj, "proj.all_cov.tab"), "w").write(cov)
+        open(os.path.join(proj, "proj.all_perc.tab"), "w").write(per)
+
+        def entries(c):
+            ents = []
+            for alt in rnd.sample("ACGT", rnd.choice([1, 1, 2, 3])):
+                n = [rnd.randint(0, x) if x else 0 for x in c]
+                ents.append("%d|%s|%s|%s" % (sum(n), alt, rnd.choice([".", "S[GCT-GCC]", "N[TA-TC]"]), "|".join(map(str, n))))
+            return ",".join(ents)
+
+        def make_lines(n_random):
+            lines, pos, crafted = "", 5, {}
+            for k in range(n_random):
+                ctg = rnd.choice([sp + sfx for sp in species for sfx in (".c1", ".c2")] + ["spNone.c", "spD.z"])
+                c = [rnd.choice([0, 0, 1, 3, 4, 5, 6, 9, 40, 1000, 200003, 4000000000]) for _ in range(S)]
+                lines += "%s\t%s\t%d\t%s\t%s\t%s\n" % (ctg, rnd.choice(["-", "g%d" % k]), pos, rnd.choice("ACGTn"), "|".join(map(str, c)), entries(c))
+                pos += 2
+            for sp, k in zip(species, sizes):                    # good / n_soi on the threshold and next to it
+                t = int(p * k)
+                for good in sorted({g for g in (t - 1, t, t + 1, t + 2, 0, k) if 0 <= g <= k}):
+                    c = [rnd.choice([0, 7, 200003]) for _ in range(S)]        # outside the SoI: anything, never looked at
+                    ok = set(rnd.sample(members[sp], good))
+                    for i in members[sp]:
+                        c[i] = rnd.choice([5, 6, 40, 4000000000]) if i in ok else rnd.choice([0, 1, 4])
+                    lines += "%s.c1\t-\t%d\tA\t%s\t%s\n" % (sp, pos, "|".join(map(str, c)), entries(c))
+                    crafted[(sp, good)] = "%s.c1:-:%d:A>" % (sp, pos)
+                    pos += 2
+            return lines, crafted
+
+        lines, crafted = make_lines(150)
+        open(os.path.join(proj, "snpCaller", "called_SNPs"), "w").write(lines)
+        ind_lines, _ = make_lines(60)
+        with_ind = run == 1
+        open(os.path.join(proj, "snpCaller", "indiv_called"), "w").write(ind_lines if with_ind else "")
+        filtering.main([proj, "-b", "40", "-d", "5", "-m", "1", "-c", str(cc), "-p", str(p)] + (["--ind"] if with_ind else []))
+        soi = filtering.relevant_taxa(os.path.join(proj, "proj.all_cov.tab"), os.path.join(proj, "proj.all_perc.tab"), 40.0, 5.0, 1)["SoI"]
+        assert sorted(soi) == sorted(species)
+        assert sorted(len(v) for v in soi.values()) == sizes
+        for sp in species:
+            assert [names.index(n) for n in soi[sp]] == members[sp]
+        for sub, text in [("pop", lines)] + ([("ind", ind_lines)] if with_ind else []):
+            assert not os.path.exists(os.path.join(proj, "filtered", sub, "spNone.filtered.freq"))
+            for sp in species:
+                want = _filter_two_formulas(text, names, soi[sp], sp, cc, p)
+                assert want
+                assert open(os.path.join(proj, "filtered", sub, sp + ".filtered.freq")).read() == "\t" + "\t".join(soi[sp]) + "\n" + want, (S, p, sub, sp)
+        assert os.path.isdir(os.path.join(proj, "filtered", "ind")) == with_ind
+        # the ties landed where they were aimed: exactly on -p is kept, one good sample fewer is dropped
+        got = {sp: open(os.path.join(proj, "filtered", "pop", sp + ".filtered.freq")).read() for sp in species}
+        for sp, k in zip(species, sizes):
+            t = int(p * k)
+            if float(t) / k == p and t >= 1:
+                ties += 1
+                assert crafted[(sp, t)] in got[sp] and crafted[(sp, t - 1)] not in got[sp] and crafted[(sp, t + 1)] in got[sp], (S, p, sp)
+        if S >= 65 and p == 0.2:
+            assert crafted[("sp65", 13)] in got["sp65"] and crafted[("sp65", 12)] not in got["sp65"] and crafted[("sp65", 14)] in got["sp65"]
+    assert ties >= 1
