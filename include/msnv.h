@@ -133,7 +133,8 @@ int msnv_call(msnv_ctx *ctx, const msnv_call_args *args);
  *   out_indiv_path may be NULL (individual SNVs are then dropped, :653-660).  Of params only min_coverage, calling_threshold and
  *   min_fraction apply (the mpileup options were spent by whoever wrote the text).
  *   stats (may be NULL): [0] lines read, [1] samples, [2] called_SNPs lines, [3] indiv_called lines, [4] kernel microseconds,
- *   [5] text bytes parsed on the device, [6] base-string characters parsed, [7] reserved.
+ *   [5] text bytes parsed on the device, [6] base-string characters parsed, [7] the most lines
+ *   one wavefront of the parser handled in a launch (ceil(lines / wavefronts), the largest over the chunks of the text).
  * Input the reference crashes on (a pileup symbol outside its ten keys, e.g. '>' '<' from CIGAR N or an IUPAC letter; more samples
  * in a line than in the first) is MSNV_EDOMAIN and nothing is written. */
 typedef struct {

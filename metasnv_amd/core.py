@@ -520,7 +520,7 @@ def call_from_mpileup(ctx, called_path, indiv_path=None, text=None, mpileup_path
     st = (C.c_uint64 * 8)()
     check(lib.msnv_call_from_mpileup(ctx._h, C.byref(a), st))
     return {"lines": int(st[0]), "samples": int(st[1]), "called_lines": int(st[2]), "indiv_lines": int(st[3]), "kernel_ms": st[4] / 1000.0,
-            "text_bytes": int(st[5]), "base_chars": int(st[6])}
+            "text_bytes": int(st[5]), "base_chars": int(st[6]), "lines_per_wave": int(st[7])}
 
 
 HOST_TIMERS = ["read_s", "inflate_host_s", "inflate_device_wall_s", "pack_s", "finalize_upload_wall_s", "format_wall_s", "add_bams_wall_s", "pack_device_wall_s", "synth_wall_s"]

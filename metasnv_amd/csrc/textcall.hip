@@ -299,7 +299,7 @@ struct DevBuf { void *p = nullptr; ~DevBuf() { if (p) dev_free(p); } };
 // `samples` in line order.
 static int run_chunk(msnv_ctx *ctx, const char *text, const std::vector<uint64_t> &off, uint32_t S, const msnv_params &p,
                      std::vector<TextRec> &recs, std::vector<msnv_site_sample> &samples, double *ms_kernel, uint64_t *bases,
-                     uint32_t *err_line, uint32_t *err_code) {
+                     uint32_t *err_line, uint32_t *err_code, uint64_t *lines_per_wave) {
     hipStream_t st = (hipStream_t)ctx->stream;
     const uint32_t n_lines = (uint32_t)(off.size() - 1);
     const uint64_t n_bytes = off.back();
@@ -313,6 +313,7 @@ static int run_chunk(msnv_ctx *ctx, const char *text, const std::vector<uint64_t
     waves = (uint32_t)std::min<uint64_t>(waves, std::max<uint64_t>(256, (512ull << 20) / row_bytes));
     waves = std::max<uint32_t>(TC_NT / 64, std::min<uint32_t>(waves, (n_lines + 3u) & ~3u));
     waves = (waves + 3u) & ~3u;
+    if (lines_per_wave) *lines_per_wave = std::max<uint64_t>(*lines_per_wave, (n_lines + waves - 1u) / waves);   // round-robin: wavefront 0 takes the most
     const uint64_t cap_rec = n_lines;                                               // every line may be called
     if (int rc = dev_alloc(&d_text.p, n_bytes + 64, &acct)) return rc;
     if (int rc = dev_alloc(&d_off.p, off.size() * sizeof(uint64_t), &acct)) return rc;
@@ -376,7 +377,8 @@ static int run_chunk(msnv_ctx *ctx, const char *text, const std::vector<uint64_t
 }
 
 // snpCall over mpileup text that sits in memory.  stats (optional): [0] lines read (with the first), [1] samples, [2] called_SNPs lines,
-// [3] indiv_called lines, [4] kernel microseconds, [5] text bytes through the kernel, [6] base-string characters parsed.
+// [3] indiv_called lines, [4] kernel microseconds, [5] text bytes through the kernel, [6] base-string characters parsed,
+// [7] the most lines one wavefront handled in a launch (ceil(lines of the chunk / wavefronts of its grid), the largest over the chunks).
 int text_call(msnv_ctx *ctx, const char *text, uint64_t n_text, const msnv_params &p, const char *ref_fasta, const char *ann_path,
               const char *called_path, const char *indiv_path, uint64_t stats[8]) {
     if (int rc = dev_set_device(ctx->device)) return rc;
@@ -404,7 +406,7 @@ int text_call(msnv_ctx *ctx, const char *text, uint64_t n_text, const msnv_param
     std::vector<TextRec> recs;
     std::vector<msnv_site_sample> samples;
     std::vector<uint64_t> rec_line;                                                  // absolute line of every record
-    double ms = 0; uint64_t bases = 0;
+    double ms = 0; uint64_t bases = 0, lines_per_wave = 0;
     // ---- chunks of whole lines (<= ~256 MB of text each, MSNV_TEXT_CHUNK overrides: tests)
     uint64_t chunk_bytes = 256ull << 20;
     if (const char *e = getenv("MSNV_TEXT_CHUNK")) chunk_bytes = std::max<uint64_t>(1, (uint64_t)atoll(e));
@@ -416,7 +418,7 @@ int text_call(msnv_ctx *ctx, const char *text, uint64_t n_text, const msnv_param
         for (uint64_t i = l0; i <= l1; ++i) off[i - l0] = lines[i] - lines[l0];
         const size_t first = recs.size();
         uint32_t err_line, err_code;
-        if (int rc = run_chunk(ctx, text + lines[l0], off, S, p, recs, samples, &ms, &bases, &err_line, &err_code)) return rc;
+        if (int rc = run_chunk(ctx, text + lines[l0], off, S, p, recs, samples, &ms, &bases, &err_line, &err_code, &lines_per_wave)) return rc;
         if (err_line != UINT32_MAX) {
             const uint64_t ln = l0 + err_line;
             if ((err_code & 0xffu) == 2u)
@@ -454,7 +456,7 @@ int text_call(msnv_ctx *ctx, const char *text, uint64_t n_text, const msnv_param
     }
     uint64_t n_pop = 0, n_ind = 0;
     for (const msnv_site &o : tmp.sites) { n_pop += o.pop_mask != 0; n_ind += o.ind_mask != 0; }
-    if (stats) { stats[0] = n_lines; stats[1] = S; stats[2] = n_pop; stats[3] = n_ind; stats[4] = (uint64_t)(ms * 1000.0); stats[5] = n_lines > 1 ? n_text - lines[1] : 0; stats[6] = bases; }
+    if (stats) { stats[0] = n_lines; stats[1] = S; stats[2] = n_pop; stats[3] = n_ind; stats[4] = (uint64_t)(ms * 1000.0); stats[5] = n_lines > 1 ? n_text - lines[1] : 0; stats[6] = bases; stats[7] = lines_per_wave; }
     if (!(ann_path && ref_fasta)) return write_calls_text(tmp, called_path, indiv_path, nullptr, nullptr);     // call_vC.cpp:448
     // ---- gene / codon annotation on the device: the called positions in a linear position space of their own
     Annotation an;

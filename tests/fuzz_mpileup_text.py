@@ -1,17 +1,17 @@
 """Randomised parity sweep of the text entry (msnv_call_from_mpileup vs the oracle's snpCall restatement) over malformed and
 well-formed pileup text alike; run on the GPU box:  python3 tests/fuzz_mpileup_text.py [n_cases] [seed].
-Both sides must agree on the outputs, or both must report a domain error (an input the reference crashes on)."""
+Both sides must agree on the outputs, or both must report a domain error (an input the reference crashes on).
+The generator (make_text, cases) is shared with the suite: tests/test_textgen.py and tests/test_gpu_mpileup_text_sizes.py run it with
+fixed seeds; importing this module needs neither the product nor a device."""
 import os, random, sys, tempfile
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, _ROOT); sys.path.insert(0, os.path.join(_ROOT, "tests"))
-from metasnv_amd import core, _lib
-import orc
 
 GOOD = ".,.,.,.,..,,ACGTacgtNn*$"
+LENS = [0, 0, 1, 3, 8, 20, 60] * 40 + [1500]        # pieces of a token; the rare long one passes the 1 KB steps of the device's tab scan
 
 
 def token(rnd, bad):
-    n = rnd.choice([0, 0, 1, 3, 8, 20, 60])
+    n = rnd.choice(LENS)
     out = []
     for _ in range(n):
         u = rnd.random()
@@ -21,7 +21,7 @@ def token(rnd, bad):
             out.append("^" + rnd.choice("]I~~]]^+-. "))
         elif u < 0.93:
             k = rnd.choice([0, 1, 2, 3, 12, 150])
-            out.append(rnd.choice("+-") + (str(k) if rnd.random() < 0.9 else "") + "".join(rnd.choice("ACGTNacgtn*") for _ in range(rnd.choice([k] * 30 + [max(0, k - 1), k + 1]))))
+            out.append(rnd.choice("+-") + (str(k) if rnd.random() < 0.9 else "") + "".join(rnd.choice("ACGTNacgtn*") for _ in range(rnd.choice([k] * 3000 + [max(0, k - 1), k + 1]))))
         elif bad and u < 0.95:
             out.append(rnd.choice("<>RYKMxX#@ 0123456789"))      # symbols the reference has no key for (blanks and stray digits among them)
     t = "".join(out)
@@ -31,7 +31,7 @@ def token(rnd, bad):
 
 
 def make_text(rnd):
-    S = rnd.choice([0, 1, 2, 3, 5, 9, 70, 130])
+    S = rnd.choice([0, 1, 2, 3, 5, 9, 70, 130, 513, 700])
     bad = rnd.random() < 0.15
     n_lines = rnd.choice([0, 1, 2, 5, 30, 200])
     lines = []
@@ -40,7 +40,7 @@ def make_text(rnd):
         pos = rnd.choice([str(li + 1), str(li + 1), " 7", "", "12x", "-3"])
         refc = rnd.choice(["A", "C", "G", "T", "N", "a", "c", "g", "t", "", "AC", " T"])
         cols = [name, pos, refc]
-        s_here = max(0, S - rnd.choice([1, 2])) if rnd.random() < 0.05 else S + rnd.choice([1, 2]) if rnd.random() < 0.004 else S
+        s_here = max(0, S - rnd.choice([1, 2])) if rnd.random() < 0.05 else S + rnd.choice([1, 2]) if rnd.random() < 0.0004 else S
         for _ in range(s_here):
             t = token(rnd, bad and li > 0)
             cols += [str(len(t)), t, "I" * len(t) if rnd.random() < 0.9 else ""]
@@ -60,17 +60,25 @@ def make_text(rnd):
     return text
 
 
-def sweep(n_cases, seed):
+def cases(n_cases, seed):
+    """(text as bytes, snpCall options, MSNV_TEXT_CHUNK) of every case of a seed."""
     rnd = random.Random(seed)
+    for _ in range(n_cases):
+        text = make_text(rnd)
+        kw = dict(c=rnd.choice([1, 4, 4, 8]), t=rnd.choice([1, 2, 4, 4]), p=rnd.choice([0.01, 0.01, 0.3, 0.0]))
+        yield text.encode("latin-1"), kw, rnd.choice([1, 300, 1 << 28])
+
+
+def sweep(n_cases, seed):
+    sys.path.insert(0, _ROOT); sys.path.insert(0, os.path.join(_ROOT, "tests"))
+    from metasnv_amd import core, _lib
+    import orc
     ctx = core.Context(0)
     bad = n_err = 0
     with tempfile.TemporaryDirectory() as td:
         pp, ip = os.path.join(td, "c"), os.path.join(td, "i")
-        for case in range(n_cases):
-            text = make_text(rnd)
-            kw = dict(c=rnd.choice([1, 4, 4, 8]), t=rnd.choice([1, 2, 4, 4]), p=rnd.choice([0.01, 0.01, 0.3, 0.0]))
-            os.environ["MSNV_TEXT_CHUNK"] = str(rnd.choice([1, 300, 1 << 28]))
-            raw = text.encode("latin-1")
+        for case, (raw, kw, chunk) in enumerate(cases(n_cases, seed)):
+            os.environ["MSNV_TEXT_CHUNK"] = str(chunk)
             with tempfile.NamedTemporaryFile(dir=td, delete=False) as f:
                 f.write(raw)
             import subprocess

@@ -151,7 +151,9 @@ def qacompute(names, lengths, sample, max_cov=10, min_mapq=1):
 
 
 def snpcall_text(mpileup, fasta=None, genes=None, **kw):
-    """snpCall restatement on mpileup text.  Returns (called_SNPs, indiv_called)."""
+    """snpCall restatement on mpileup text.  Returns (exit code, called_SNPs, indiv_called, stderr).  A `str` is encoded and the
+    outputs come back as `str`; `bytes` go to the process unchanged (NUL and high bytes included) and the two outputs come back
+    as `bytes`."""
     import subprocess
     exe = os.path.join(ROOT, "oracle", "orc_snpcall")
     if not os.path.exists(exe):
@@ -165,5 +167,12 @@ def snpcall_text(mpileup, fasta=None, genes=None, **kw):
             cmd += ["-f", fasta]
         if genes:
             cmd += ["-g", genes]
+        if isinstance(mpileup, (bytes, bytearray)):
+            r = subprocess.run(cmd, input=bytes(mpileup), stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+            ind = b""
+            if os.path.exists(ip):
+                with open(ip, "rb") as f:
+                    ind = f.read()
+            return r.returncode, r.stdout, ind, r.stderr.decode("latin-1")
         r = subprocess.run(cmd, input=mpileup.encode(), stdout=subprocess.PIPE, stderr=subprocess.PIPE)
         return r.returncode, r.stdout.decode(), open(ip).read() if os.path.exists(ip) else "", r.stderr.decode()
