@@ -519,7 +519,11 @@ static int bgzf_read_files_device(msnv_ctx *ctx, const char *const *paths, int n
             uint32_t bi = 0;
             for (const BgzfBlock &bl : blocks[(size_t)k]) {
                 const uint32_t this_block = bi++;
-                if (bl.out_size == 0) continue;
+                if (bl.out_size == 0) {                              // nothing for the device to write; the payload must still be an empty stream (the EOF marker is one)
+                    if (!bgzf_inflate_block_host(in_stage + in_off[(size_t)k] + bl.in_off, bl.in_size, nullptr, 0))
+                        return fail(MSNV_EFORMAT, "%s: BGZF inflate failed (malformed DEFLATE stream or CRC-32 mismatch)", paths[f0 + k]);
+                    continue;
+                }
                 list.push_back(InfBlock{in_off[(size_t)k] + bl.in_off, ob + bl.out_off, bl.in_size, bl.out_size});
                 origin.push_back(k); blk_in_file.push_back(this_block);
             }

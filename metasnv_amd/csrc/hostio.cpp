@@ -205,7 +205,9 @@ static std::atomic<uint64_t> g_zlib_fallbacks{0};
 uint64_t inflate_zlib_fallbacks() { return g_zlib_fallbacks.load(); }
 
 static bool inflate_block(const uint8_t *src, uint32_t n_in, uint8_t *dst, uint32_t n_out) {
-    if (n_out == 0) return true;
+    // (a member of ISIZE 0 is decoded like any other: zlib, through which htslib reads, refuses one whose payload is not an empty stream)
+    uint8_t none = 0;
+    if (n_out == 0) dst = &none;                                 // (zlib wants a pointer; nothing is written)
     static const bool use_zlib = [] { const char *e = getenv("MSNV_INFLATE"); return e && e[0] == 'z'; }();     // MSNV_INFLATE=zlib: A/B of the two decoders
     static const bool bmi2 = __builtin_cpu_supports("bmi2") != 0;
     if (!use_zlib && (bmi2 ? inflate_raw_bmi2(src, n_in, dst, n_out) : inflate_raw(src, n_in, dst, n_out))) return true;

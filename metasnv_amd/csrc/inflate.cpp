@@ -23,6 +23,11 @@ constexpr int LL_BITS = 11, D_BITS = 8;
 constexpr uint32_t F_LIT = 1u << 12, F_EOB = 1u << 13, F_SUB = 1u << 14, F_BAD = 1u << 15;
 // entry: bits 0-7 code length (bits to drop), 8-11 extra bits, 12-15 flags, 16-31 literal / base value / subtable start
 
+// Room behind the main tables: a subtable of 2^k entries hangs under a prefix whose longest code has root + k bits, and in a complete code
+// (the only kind build_table lets through, the one-code sets aside: they have no subtable) the codes under that prefix are a full binary
+// tree of depth k, which has at least k + 1 leaves.  So n symbols pay for at most n * 2^k / (k + 1) entries, largest at k = 15 - root:
+// 286 * 16 / 5 = 915 for the literal/length table, 30 * 128 / 8 = 480 for the distance table (tests/deflate_craft.py: table_entries()
+// of the sets a hill-climb finds stays far below both).
 struct Tables {
     uint32_t ll[(1 << LL_BITS) + 1200];
     uint32_t d[(1 << D_BITS) + 600];
@@ -39,13 +44,16 @@ inline uint32_t rev_bits(uint32_t v, int n) {                // n <= 15
 }
 
 // Builds a decode table from canonical code lengths.  sym_entry[s] = value << 16 | extra << 8 | flags (no length yet).
-// Returns false for an over-subscribed code.  Unused slots are F_BAD.
-bool build_table(uint32_t *tab, int main_bits, int cap, const uint8_t *lens, int n_sym, const uint32_t *sym_entry) {
+// Returns false for an over-subscribed code and for an incomplete one, as zlib's inflate_table does (htslib reads through zlib: the
+// reference's tools fail on such a file) -- but for what zlib lets through where `one_code_ok` (the literal/length and the distance
+// set, not the code-length set): a single code of one bit, or no code at all.  Unused slots are F_BAD.
+bool build_table(uint32_t *tab, int main_bits, int cap, const uint8_t *lens, int n_sym, const uint32_t *sym_entry, bool one_code_ok) {
     int count[16] = {0};
     for (int s = 0; s < n_sym; ++s) count[lens[s]]++;
     count[0] = 0;
     uint32_t left = 1;
     for (int l = 1; l <= 15; ++l) { left <<= 1; if ((uint32_t)count[l] > left) return false; left -= (uint32_t)count[l]; }
+    if (left && !(one_code_ok && (left == 1u << 15 || (left == 1u << 14 && count[1] == 1)))) return false;
     uint32_t next_code[16], code = 0;
     for (int l = 1; l <= 15; ++l) { code = (code + (uint32_t)count[l - 1]) << 1; next_code[l] = code; }
     const int main_size = 1 << main_bits;
@@ -122,11 +130,11 @@ void init_static() {
     for (int s = 144; s < 256; ++s) lens[s] = 9;
     for (int s = 256; s < 280; ++s) lens[s] = 7;
     for (int s = 280; s < 288; ++s) lens[s] = 8;
-    build_table(g_fixed.ll, LL_BITS, (int)(sizeof g_fixed.ll / 4), lens, 288, g_ll_entry);
+    build_table(g_fixed.ll, LL_BITS, (int)(sizeof g_fixed.ll / 4), lens, 288, g_ll_entry, true);
     pair_literals(g_fixed.ll);
     uint8_t dl[32];
     for (int s = 0; s < 32; ++s) dl[s] = 5;
-    build_table(g_fixed.d, D_BITS, (int)(sizeof g_fixed.d / 4), dl, 32, g_d_entry);
+    build_table(g_fixed.d, D_BITS, (int)(sizeof g_fixed.d / 4), dl, 32, g_d_entry, true);
     g_init = true;
 }
 struct StaticInit { StaticInit() { init_static(); } } g_static_init;
@@ -189,7 +197,7 @@ bool MSNV_INFLATE_NAME(const uint8_t *src, uint32_t n_in, uint8_t *dst, uint32_t
                 uint32_t cl_entry[19];
                 for (int s = 0; s < 19; ++s) cl_entry[s] = (uint32_t)s << 16;
                 uint32_t cltab[1 << 7];
-                if (!build_table(cltab, 7, 1 << 7, cl, 19, cl_entry)) return false;
+                if (!build_table(cltab, 7, 1 << 7, cl, 19, cl_entry, false)) return false;
                 uint8_t lens[286 + 30 + 140];
                 int n = 0;
                 while (n < hlit + hdist) {
@@ -213,9 +221,9 @@ bool MSNV_INFLATE_NAME(const uint8_t *src, uint32_t n_in, uint8_t *dst, uint32_t
                     }
                 }
                 if (lens[256] == 0) return false;            // no end-of-block code
-                if (!build_table(dyn.ll, LL_BITS, (int)(sizeof dyn.ll / 4), lens, hlit, g_ll_entry)) return false;
+                if (!build_table(dyn.ll, LL_BITS, (int)(sizeof dyn.ll / 4), lens, hlit, g_ll_entry, true)) return false;
                 pair_literals(dyn.ll);
-                if (!build_table(dyn.d, D_BITS, (int)(sizeof dyn.d / 4), lens + hlit, hdist, g_d_entry)) return false;
+                if (!build_table(dyn.d, D_BITS, (int)(sizeof dyn.d / 4), lens + hlit, hdist, g_d_entry, true)) return false;
                 T = &dyn;
             }
             const uint32_t *const ll = T->ll, *const dt = T->d;

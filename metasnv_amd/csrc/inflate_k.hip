@@ -74,7 +74,8 @@ __device__ __forceinline__ uint32_t d_entry(const int s, const uint32_t nb) { re
 __device__ __forceinline__ uint32_t cl_entry(const int s, const uint32_t nb) { return D_SYM | nb << 2 | (uint32_t)s << 8; }
 
 // Canonical Huffman decode table from code lengths (the algorithm of csrc/inflate.cpp build_table, a symbol per lane where the work
-// has width).  kind: 0 literal/length, 1 distance, 2 code lengths.  Returns false for an over-subscribed code or a table that
+// has width).  kind: 0 literal/length, 1 distance, 2 code lengths.  Returns false for an over-subscribed code, for an incomplete one
+// (as zlib's inflate_table: all but a literal/length or distance set of a single one-bit code, or of no code at all) or a table that
 // does not fit.  Called by the whole wavefront; barriers inside.
 __device__ bool build_table(InfLds &L, uint16_t *tab, const int main_bits, const int cap, const uint8_t *lens, const int n_sym, const int kind, const int lane) {
     const uint32_t bad = kind == 0 ? LL_BAD : D_BAD;
@@ -95,6 +96,7 @@ __device__ bool build_table(InfLds &L, uint16_t *tab, const int main_bits, const
         nc[l] = code;
     }
     if (!ok) return false;
+    if (left != 0u && (kind == 2 || !(left == 1u << 15 || (left == 1u << 14 && L.count[1] == 1u)))) return false;      // (uniform)
     const int main_size = 1 << main_bits;
     // canonical codes: symbol s of length l gets next_code[l] + (number of symbols < s with the same length).  Serial over the
     // symbols (a few hundred steps), done by every lane identically; only lane 0 stores.
@@ -103,7 +105,7 @@ __device__ bool build_table(InfLds &L, uint16_t *tab, const int main_bits, const
         for (int l = 0; l < 16; ++l) nxt[l] = nc[l];
         for (int s = 0; s < n_sym; ++s) { const int l = lens[s]; if (l) L.code[s] = (uint16_t)rev_bits(nxt[l]++, l); }
     }
-    for (int i = lane; i < main_size; i += 64) { tab[i] = (uint16_t)bad; L.sub_bits[i] = 0; }      // an incomplete code leaves holes
+    for (int i = lane; i < main_size; i += 64) { tab[i] = (uint16_t)bad; L.sub_bits[i] = 0; }      // a one-code set leaves holes
     __syncthreads();
     // subtables: per root prefix the longest code that starts with it (serial: a few hundred steps)
     if (lane == 0) {
@@ -199,8 +201,9 @@ __global__ __launch_bounds__(64, MSNV_INFLATE_WAVES) void msnv_inflate_blocks(co
     // one window at a time is handled by reloading
     auto resync = [&]() {
         const uint32_t wi = (a0 + ip) >> 2;
-        // (also backwards: the stored-block path hands unread bytes of the bit buffer back; with today's refill sizes ip never falls
-        // behind the window, but readlane(win, wi - win_at) with a wrapped index would read the wrong dword without any error)
+        // (also backwards: the stored-block path hands unread bytes of the bit buffer back; ip falls behind the window only if more bytes go
+        // back than the last refill step took from the new one -- tests/deflate_craft.py: gen_stored walks LEN / NLEN across a seam behind
+        // end-of-block codes of 1, 2 and 7 bits; readlane(win, wi - win_at) with a wrapped index would read the wrong dword without any error)
         if (wi < win_at || wi >= win_at + 64u) {
             win_at = wi & ~63u;
             win = win_at + (uint32_t)lane < n_words ? wsrc[win_at + lane] : 0u;
@@ -292,7 +295,7 @@ __global__ __launch_bounds__(64, MSNV_INFLATE_WAVES) void msnv_inflate_blocks(co
                 int used = 0;
                 if ((e & 7u) == LL_SUB) { used = I_LL_BITS; e = uni((uint32_t)L.ll[(e >> 6) + (uint32_t)((bb >> I_LL_BITS) & ((2u << ((e >> 3) & 7u)) - 1u))]); }
                 const uint32_t kind = e & 7u;
-                if (kind >= LL_SUB) { fail_ = true; break; }          // (a hole of an incomplete code; a link inside a subtable cannot be)
+                if (kind >= LL_SUB) { fail_ = true; break; }          // (a hole of a one-code set; a link inside a subtable cannot be)
                 used += (int)((e >> 3) & 15u);
                 if (used > bc) { fail_ = true; break; }
                 bb >>= used; bc -= used;

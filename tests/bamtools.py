@@ -156,3 +156,39 @@ def write_bam_py(path, names, lengths, record_bytes, rnd, header_text=None):
         if rnd.random() < 0.05: out += member(b"")              # an empty member in the middle of the file
     out += member(b"")                                         # the EOF marker (an empty member)
     open(path, "wb").write(out)
+
+
+def bam_body(names, lengths, record_bytes, header_text=None):
+    """The uncompressed stream of a BAM file: magic, header text, contig table, records."""
+    text = (header_text if header_text is not None else "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % (n, l) for n, l in zip(names, lengths))).encode()
+    body = b"BAM\x01" + struct.pack("<i", len(text)) + text + struct.pack("<i", len(names))
+    for n, l in zip(names, lengths):
+        nb = n.encode() + b"\0"
+        body += struct.pack("<i", len(nb)) + nb + struct.pack("<i", l)
+    return body + bytes(record_bytes)
+
+
+def write_bam_members(path, names, lengths, record_bytes, sizes, header_text=None, level=6):
+    """A BAM whose BGZF members have GIVEN uncompressed sizes: `sizes` one after the other from the start of the stream (header included),
+    members of 0xff00 bytes behind them, the EOF marker at the end.  Returns (file offset, BSIZE, uncompressed size) of every member."""
+    import zlib
+    body = bam_body(names, lengths, record_bytes, header_text)
+    assert sum(sizes) <= len(body), "the stream is shorter than the members asked for"
+    out, members, pos = bytearray(), [], 0
+    todo = list(sizes)
+    while pos < len(body) or todo is not None:
+        if todo:
+            n = todo.pop(0)
+        elif pos < len(body):
+            n = min(0xff00, len(body) - pos)
+        else:
+            n, todo = 0, None                                  # the EOF marker
+        payload = body[pos:pos + n]; pos += n
+        c = zlib.compressobj(level, zlib.DEFLATED, -15)
+        comp = c.compress(payload) + c.flush()
+        bsize = len(comp) + 26
+        assert bsize <= 65536, "a member of %d bytes does not fit deflated" % n
+        members.append((len(out), bsize, n))
+        out += b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", bsize - 1) + comp + struct.pack("<II", zlib.crc32(payload) & 0xffffffff, n)
+    open(path, "wb").write(out)
+    return members

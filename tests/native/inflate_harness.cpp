@@ -1,6 +1,8 @@
 // tests/native/inflate_harness.cpp -- built and run by tests/test_inflate.py (CPU, with -fsanitize=address,undefined):
 // metasnv_amd/csrc/inflate.cpp against zlib on streams of every block type, and on corrupted streams (which must be refused or
 // decoded to something, but never read or write out of bounds).  argv[1] = rounds, argv[2] = "bench" for a timing line.
+// `inflate_harness corpus FILE` (tests/test_deflate_crafted.py): the hand-assembled streams of tests/deflate_craft.py, one line per case
+// and decoder: "<decoder> <name> accepted|refused match|mismatch|-" (built with -DMSNV_HARNESS_BMI2 and inflate_bmi2.cpp: both decoders).
 #include <zlib.h>
 
 #include <chrono>
@@ -10,7 +12,12 @@
 #include <cstring>
 #include <vector>
 
-namespace msnv { bool inflate_raw(const uint8_t *src, uint32_t n_in, uint8_t *dst, uint32_t n_out); }
+#include <string>
+
+namespace msnv {
+bool inflate_raw(const uint8_t *src, uint32_t n_in, uint8_t *dst, uint32_t n_out);
+bool inflate_raw_bmi2(const uint8_t *src, uint32_t n_in, uint8_t *dst, uint32_t n_out);
+}
 
 static uint64_t rng_state = 88172645463325252ull;
 static uint64_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return rng_state; }
@@ -48,7 +55,48 @@ static std::vector<uint8_t> deflate_raw(const std::vector<uint8_t> &in, int leve
     return out;
 }
 
+// The container tests/deflate_craft.py: container() writes: per case u32 name length, name, u32 valid, u32 stream length, stream, u32 output
+// length, the intended bytes.  Exact-size output buffers and 8 readable bytes behind every input, as in the rounds below.
+static int run_corpus(const char *path) {
+    FILE *f = fopen(path, "rb");
+    if (!f) { fprintf(stderr, "cannot open %s\n", path); return 2; }
+    std::vector<uint8_t> all;
+    uint8_t buf[65536];
+    for (size_t n; (n = fread(buf, 1, sizeof buf, f)) > 0;) all.insert(all.end(), buf, buf + n);
+    fclose(f);
+    size_t o = 0;
+    auto u32 = [&](uint32_t &v) -> bool { if (all.size() - o < 4) return false; memcpy(&v, all.data() + o, 4); o += 4; return true; };
+    int n_cases = 0;
+    while (o < all.size()) {
+        uint32_t n_name, valid, n_in, n_out;
+        if (!u32(n_name) || all.size() - o < n_name) return 2;
+        const std::string name((const char *)all.data() + o, n_name); o += n_name;
+        if (!u32(valid) || !u32(n_in) || all.size() - o < n_in) return 2;
+        std::vector<uint8_t> cin((size_t)n_in + 8, 0);
+        memcpy(cin.data(), all.data() + o, n_in); o += n_in;
+        if (!u32(n_out) || all.size() - o < n_out) return 2;
+        const uint8_t *want = all.data() + o; o += n_out;
+        typedef bool (*Fn)(const uint8_t *, uint32_t, uint8_t *, uint32_t);
+        struct { const char *name; Fn fn; } decoders[] = {{"inflate_raw", msnv::inflate_raw},
+#ifdef MSNV_HARNESS_BMI2
+                                                          {"inflate_raw_bmi2", msnv::inflate_raw_bmi2},
+#endif
+        };
+        for (const auto &d : decoders) {
+            uint8_t *out = new uint8_t[n_out];                  // (exactly n_out bytes, also for 0: the sanitizer sees the first byte behind them)
+            const bool ok = d.fn(cin.data(), n_in, out, n_out);
+            printf("%s %s %s %s\n", d.name, name.c_str(), ok ? "accepted" : "refused", !ok ? "-" : (n_out == 0 || memcmp(out, want, n_out) == 0) ? "match" : "mismatch");
+            delete[] out;
+        }
+        (void)valid;
+        ++n_cases;
+    }
+    printf("corpus: %d cases\n", n_cases);
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 2 && !strcmp(argv[1], "corpus")) return run_corpus(argv[2]);
     const int rounds = argc > 1 ? atoi(argv[1]) : 200;
     const bool bench = argc > 2 && !strcmp(argv[2], "bench");
     int n_ok = 0, n_refused = 0;

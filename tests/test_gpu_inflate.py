@@ -83,16 +83,7 @@ def test_file_entry_point_with_either_inflate(mode, tmp_path, monkeypatch):
 
 
 
-def _bgzf(blocks_payload):
-    """A BGZF file from (raw deflate payload, uncompressed bytes) pairs, plus the EOF block."""
-    import struct, zlib
-    out = bytearray()
-    for comp, data in blocks_payload:
-        bsize = 18 + len(comp) + 8
-        out += bytes([31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0]) + struct.pack("<H", bsize - 1)
-        out += comp + struct.pack("<II", zlib.crc32(data) & 0xffffffff, len(data))
-    out += bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
-    return bytes(out)
+from deflate_craft import bgzf as _bgzf      # (a BGZF file from (raw deflate payload, uncompressed bytes) pairs, plus the EOF block)
 
 
 def test_device_inflate_on_crafted_streams_of_every_kind(tmp_path):
