@@ -7,8 +7,10 @@ HIP device is usable every compute entry point returns MSNV_ENODEV, surfaced as 
 import ctypes as C
 import os
 
+from . import knobs
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("MSNV_LIBRARY") or os.path.join(_HERE, "csrc", "libmsnv.so")   # MSNV_LIBRARY: developer A/B of two builds
+LIB_PATH = knobs.library() or os.path.join(_HERE, "csrc", "libmsnv.so")   # MSNV_LIBRARY: developer A/B of two builds
 
 
 class MsnvError(RuntimeError):
@@ -201,7 +203,7 @@ def _load():
         raise ImportError(
             "metasnv_amd: %s is missing. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("MSNV_DIST_FORCE") == "1":
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1 or knobs.dist_force():
         # multi-rank runs exchange tables through torch.distributed: torch ships its own libamdhip64, and two HIP
         # runtimes in one process do not both see the GPU.  Importing torch first makes libmsnv.so bind to the
         # runtime torch already loaded (same SONAME).
@@ -211,7 +213,7 @@ def _load():
         try:
             fn = getattr(lib, name)      # AttributeError here = the .so does not match include/msnv.h
         except AttributeError:
-            if os.environ.get("MSNV_LIBRARY"):
+            if knobs.library():
                 continue                 # developer A/B against an older build (profiles/ab.sh): newer entry points are simply absent
             raise
         fn.restype = res

@@ -21,7 +21,7 @@ import os
 import shutil
 import sys
 
-from . import tables
+from . import knobs, tables
 
 
 def mkdir_p(d):
@@ -108,7 +108,7 @@ def _since_process_start():
 def _write_metrics(obj):
     """Kernel timings / counts of the run as JSON when MSNV_METRICS names a file (the reference has no metrics output;
     nothing is written into the project directory unless asked)."""
-    path = os.environ.get("MSNV_METRICS")
+    path = knobs.metrics_path()
     if path:
         import json
         with open(path, "a") as f:
@@ -254,11 +254,11 @@ def main(argv=None):
             # ... unless the host has few cores for the job (a container's CPU quota counts: 16 cores inflate the benchmark's 160 BAMs in 0.34 s
             # at best, the device in 0.25 s once its context stands): then the feed waits for the context and inflates on the device
             # (parallel.feed_sharded: MSNV_ONESHOT=device | host overrides)
-            how = os.environ.get("MSNV_ONESHOT", "")[:1]
+            how = knobs.oneshot()
             # ... and only when the library WILL inflate there (csrc/api.cpp: want_device_inflate -- MSNV_INFLATE=host, or fewer than 64 MB of
             # BAMs, keeps the host decoder): waiting for the context first and then inflating on the host threads anyway would lose the overlap
             def device_would_inflate():
-                e = os.environ.get("MSNV_INFLATE", "")[:1]
+                e = knobs.inflate_where()
                 if e:
                     return e == "d"
                 total = 0

@@ -201,15 +201,14 @@ static int check_open(const msnv_dataset *ds, bool staged_ok = false) {
 }
 static bool pack_on_device(const msnv_dataset *ds) {
     if (!ds->ctx) return false;
-    const char *e = getenv("MSNV_PACK");                 // (per call: tests switch it)
-    return !(e && e[0] == 'h');
+    return !knob::pack_on_host();                        // (per call: tests switch it)
 }
 // Appends n streams as n samples through the device pack, in rounds of at most MSNV_PACK_ROUND_MB (default 6144) of record bytes.
 static int add_streams_device(msnv_dataset *ds, const uint8_t *const *records, const uint64_t *n_bytes, int n, bool streams_on_device, const uint8_t *in_place_base = nullptr, uint64_t in_place_capacity = 0) {
     HostTimerScope ts(HT_PACK_DEVICE_WALL);
     fin_trace_reset();
     struct Mark { ~Mark() { fin_trace("pack: whole call"); } } mark;
-    const uint64_t round_bytes = [] { const char *e = getenv("MSNV_PACK_ROUND_MB"); const long long v = e ? atoll(e) : 6144; return (uint64_t)std::max<long long>(1, v) << 20; }();
+    const uint64_t round_bytes = knob::pack_round_bytes();
     const size_t first = ds->samples.size();
     const size_t rounds_at_entry = ds->dp.rounds.size();
     ds->samples.resize(first + (size_t)n);
@@ -361,7 +360,7 @@ struct InflatedExt { uint64_t off, size; };
 struct ResidentBatch { std::vector<BamHeader> hdr; std::vector<uint64_t> rec_off; };
 // MSNV_FEED_TRACE=1: wall milliseconds between the steps of the device feed, on stderr
 static void feed_mark(const char *what) {
-    static const bool on = [] { const char *e = getenv("MSNV_FEED_TRACE"); return e && e[0] == '1'; }();
+    const bool on = knob::feed_trace();
     if (!on) return;
     static double last = 0;
     const double now = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -391,7 +390,7 @@ static int bgzf_read_files_device(msnv_ctx *ctx, const char *const *paths, int n
     // which pins nothing: the benchmark's 160 BAMs (1.35 GB) are then ONE batch -- as two, the second one's files were read (page faults of fresh
     // buffers) while the first one's 1 GB went up from pageable memory (the runtime pinning it page by page), and the launcher waited 90 ms
     // for that read behind the first batch (MSNV_FEED_TRACE=1: round 5)
-    const uint64_t batch_in = [&] { const char *e = getenv("MSNV_INFLATE_BATCH_MB"); const long long v = e ? atoll(e) : (res ? 2048 : 1024); return (uint64_t)std::max<long long>(1, v) << 20; }();
+    const uint64_t batch_in = knob::inflate_batch_bytes(res);
     // RESIDENT form: a batch's host work -- files read into pageable memory, blocks indexed, BAM headers read from the leading blocks -- is done by
     // load_batch, and the NEXT batch is loaded (std::async) while the device inflates, checks and packs the current one
     struct Loaded {
@@ -556,11 +555,11 @@ static int bgzf_read_files_device(msnv_ctx *ctx, const char *const *paths, int n
         }
         std::vector<uint32_t> status;
         bool dev_valid = false;
-        const uint32_t check_every = inflate_check_every();       // (one reading for both decoders: msnv_internal.h)
+        const uint32_t check_every = knob::inflate_check_every();       // (one reading for both decoders)
         if (!host_batch) {
             HostTimerScope ts(HT_INFLATE_DEVICE_WALL);
             int rc = MSNV_OK;
-            if (res && getenv("MSNV_TEST_RESIDENT_FAIL")) rc = fail_quiet(MSNV_ENOMEM, "resident inflate refused (MSNV_TEST_RESIDENT_FAIL)");      // (tests: the fallback below)
+            if (res && knob::test_resident_fail()) rc = fail_quiet(MSNV_ENOMEM, "resident inflate refused (MSNV_TEST_RESIDENT_FAIL)");      // (tests: the fallback below)
             else rc = res ? dev_inflate_resident(ctx, in_stage, ib, list, blk_in_file, check_every, status, &ms) : dev_inflate(ctx, ib, list, ob, status, &ms);
             feed_mark("upload + inflate + check");
             if (rc) {
@@ -695,8 +694,7 @@ extern "C" int msnv_bgzf_inflate(msnv_ctx *ctx, const char *path, int32_t on_dev
 // MSNV_INFLATE=host | zlib keeps everything on the host, MSNV_INFLATE=device forces the device whatever the size.
 static bool want_device_inflate(msnv_ctx *ctx, const char *const *paths, int n, int threads, bool resident = false) {
     if (!ctx) return false;
-    const char *e = getenv("MSNV_INFLATE");
-    if (e) return e[0] == 'd';
+    if (const char where = knob::inflate_where()) return where == 'd';
     uint64_t bytes = 0, largest = 0;
     for (int i = 0; i < n; ++i) {
         FILE *f = fopen(paths[i], "rb");
@@ -798,7 +796,7 @@ static int add_bams_device_pack(msnv_dataset *ds, const char *const *bam_paths, 
             }
             // in HBM: the records are read where the inflate kernel wrote them (no copy into a round buffer) when the batch's buffer leaves
             // the kernels' read-ahead room behind its last stream
-            bool in_place = dev_valid && !(reinterpret_cast<uintptr_t>(base) & 15u) && !getenv("MSNV_PACK_COPY");
+            bool in_place = dev_valid && !(reinterpret_cast<uintptr_t>(base) & 15u) && !knob::pack_copy();
             for (size_t k = 0; k < ptrs.size() && in_place; ++k) {
                 if (k > 0 && ptrs[k] < ptrs[k - 1] + sizes[k - 1]) in_place = false;
                 if ((uint64_t)(ptrs[k] - base) + sizes[k] + 256 > ds->ctx->dev_out_cap) in_place = false;
@@ -859,7 +857,7 @@ extern "C" int msnv_dataset_deal_bams_device(msnv_dataset *ds, const char *const
     int nthreads = host_threads > 0 ? host_threads : (int)msnv_default_threads();
     nthreads = std::min(nthreads, std::max(1, (int)n));
     {   // one batch of the device inflate only: the parts of a call lie destination-major in `out`
-        const uint64_t batch_in = [] { const char *e = getenv("MSNV_INFLATE_BATCH_MB"); const long long v = e ? atoll(e) : 1024; return (uint64_t)std::max<long long>(1, v) << 20; }();
+        const uint64_t batch_in = knob::inflate_batch_bytes();
         uint64_t ib = 0;
         for (int i = 0; i < n; ++i) {
             FILE *f = fopen(bam_paths[i], "rb");
@@ -907,7 +905,7 @@ extern "C" int msnv_dataset_inflate_bams_device(msnv_dataset *ds, const char *co
     int nthreads = host_threads > 0 ? host_threads : (int)msnv_default_threads();
     nthreads = std::min(nthreads, std::max(1, (int)n));
     {
-        const uint64_t batch_in = [] { const char *e = getenv("MSNV_INFLATE_BATCH_MB"); const long long v = e ? atoll(e) : 1024; return (uint64_t)std::max<long long>(1, v) << 20; }();
+        const uint64_t batch_in = knob::inflate_batch_bytes();
         uint64_t ib = 0;
         for (int i = 0; i < n; ++i) {
             FILE *f = fopen(bam_paths[i], "rb");
@@ -1143,8 +1141,9 @@ extern "C" int msnv_dataset_finalize(msnv_dataset *ds) {
         std::vector<ByteBuf> bufs;
         ~FreeLater() {
             if (bufs.empty()) return;
-            if (const char *e = getenv("MSNV_STAGE_FREE")) if (e[0] == 's') { bufs.clear(); return; }
-            if (const char *e = getenv("MSNV_STAGE_FREE")) if (e[0] == 'n') { static std::vector<ByteBuf> keep; for (ByteBuf &b : bufs) keep.push_back(std::move(b)); return; }
+            const char how = knob::stage_free();
+            if (how == 's') { bufs.clear(); return; }
+            if (how == 'n') { static std::vector<ByteBuf> keep; for (ByteBuf &b : bufs) keep.push_back(std::move(b)); return; }
             const size_t nt = std::min<size_t>(bufs.size(), std::min<size_t>(16, msnv_default_threads()));
             std::vector<std::vector<ByteBuf>> share(nt);
             for (size_t i = 0; i < bufs.size(); ++i) share[i % nt].push_back(std::move(bufs[i]));

@@ -36,7 +36,7 @@ struct Init {
         __builtin_cpu_init();
         g_have_clmul = __builtin_cpu_supports("pclmul") && __builtin_cpu_supports("sse4.1");
 #endif
-        if (const char *e = getenv("MSNV_CRC")) if (e[0] == 't') g_have_clmul = false;      // MSNV_CRC=table: the other form (tests)
+        if (knob::crc_table()) g_have_clmul = false;      // MSNV_CRC=table: the other form (tests)
     }
 } g_init;
 

@@ -2364,7 +2364,7 @@ void devpack_release(msnv_dataset &ds) {
 struct BufPool {
     std::vector<std::pair<void *, uint64_t>> &slots;
     size_t next = 0; int rc = MSNV_OK;
-    bool exact = [] { const char *e = getenv("MSNV_GUARD_ALLOC"); return e && e[0] == '1'; }();
+    bool exact = knob::guard_alloc();
     void *get(uint64_t bytes) {
         if (next >= slots.size()) slots.emplace_back(nullptr, 0);
         std::pair<void *, uint64_t> &b = slots[next++];
@@ -2439,9 +2439,9 @@ static int scan_streams(hipStream_t st, const int device, BufPool &pool, const u
     if (stage_only) return MSNV_OK;
 
     // ---- record boundaries, the quick way: sub-segments walked side by side, seams checked on the device (MSNV_SCAN=segments: the careful kernel only)
-    const bool quick = [] { const char *e = getenv("MSNV_SCAN"); return !(e && e[0] == 's'); }();
+    const bool quick = !knob::scan_segments();
     if (quick && S > 0) {
-        const uint32_t sub_bytes = [] { const char *e = getenv("MSNV_SCAN_SUB"); const long long v = e ? atoll(e) : 4096; return (uint32_t)std::min<long long>(32768, std::max<long long>(64, v)); }();   // (per call: tests shrink it)
+        const uint32_t sub_bytes = knob::scan_sub_bytes(knob::SCAN_SUB_STREAMS);   // (per call: tests shrink it)
         const uint32_t cap = sub_bytes / 36u + 2u;
         std::vector<SubStream> ss(S);
         uint64_t n_sub64 = 0;
@@ -2518,7 +2518,7 @@ static int scan_streams(hipStream_t st, const int device, BufPool &pool, const u
         }
     }
     // ---- record boundaries: segments, guessed entry points, seams checked here
-    const uint64_t seg_bytes = [] { const char *e = getenv("MSNV_SCAN_SEG_KB"); const long long v = e ? atoll(e) : 256; return (uint64_t)std::max<long long>(1, v) << 10; }();   // (per call: tests shrink it)
+    const uint64_t seg_bytes = knob::scan_seg_bytes();   // (per call: tests shrink it)
     std::vector<ScanSeg> segs;
     std::vector<uint32_t> seg_lo(S + 1, 0);                       // per stream: its first segment
     uint64_t cap_total = 0;
@@ -2885,8 +2885,8 @@ int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *stre
     // learns late -- an error, a sample that needs the host pre-pass, more far-reaching reads than the list holds -- sends the round through
     // the CAREFUL route: round 5's stage-by-stage form (msnv_scan_sub / msnv_scan_segments, msnv_measure_reads, waits between the stages),
     // which also words malformed input and takes the host pre-pass's verdicts.  MSNV_SCAN=segments and MSNV_FRONT=careful force it (tests).
-    const uint32_t sub_bytes = [] { const char *e = getenv("MSNV_SCAN_SUB"); const long long v = e ? atoll(e) : 6144; return (uint32_t)std::min<long long>(32768, std::max<long long>(64, v)); }();   // (per call: tests shrink it; 6 KB: 2.36 -> 2.04 ms of scan + measure on the benchmark shape against 4 KB -- fewer entry guesses --, 8 KB the same)
-    const bool quick_wanted = [] { const char *e = getenv("MSNV_SCAN"); const char *f = getenv("MSNV_FRONT"); return !(e && e[0] == 's') && !(f && f[0] == 'c'); }();
+    const uint32_t sub_bytes = knob::scan_sub_bytes(knob::SCAN_SUB_ROUND);   // (per call: tests shrink it; 6 KB: 2.36 -> 2.04 ms of scan + measure on the benchmark shape against 4 KB -- fewer entry guesses --, 8 KB the same)
+    const bool quick_wanted = !knob::scan_segments() && !knob::front_careful();
     uint64_t n_sub64 = 0;
     std::vector<SubStream> ss(S);
     for (size_t s = 0; s < S; ++s) { ss[s] = SubStream{s_beg[s], s_end[s], (uint32_t)n_sub64, 0u}; n_sub64 += std::max<uint64_t>(1, (n_bytes[s] + sub_bytes - 1) / sub_bytes); }
@@ -3104,7 +3104,7 @@ int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *stre
             // anything is emitted -- the careful route does all of that; the quick route takes the rounds without candidates
             if (!MP.ignore_overlaps && tot.ovl >= 2) { route = 1; continue; }
             NR = tot.rec; NPC = tot.npiece; NIV = tot.niv; n_runs = tot.runs; n_groups = tot.grps; n_ovl_total = tot.ovl; seqb_total = tot.seqb;
-            in_order = tot.sort != 0 || [] { const char *e = getenv("MSNV_TILE_ORDER"); return e && e[0] == 's'; }();
+            in_order = tot.sort != 0 || knob::tile_order_sort();
             const uint64_t NRa = (uint64_t)NR + 1;
             DP_BUF(unsigned long long, d_recoff, NRa);
             DP_BUF(uint16_t, d_recsample, NRa);
@@ -3137,7 +3137,7 @@ int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *stre
             // writes the pieces' depths itself, so nothing the emit kernels read comes from it); what the host needs of it goes to the pinned
             // words behind it, with an event (evd2)
             if (!ds.ctx->stream2) { if (int rc = dev_stream_create(&ds.ctx->stream2)) return rc; }
-            static const bool depth_on_main = [] { const char *e = getenv("MSNV_DEPTH_STREAM"); return e && e[0] == 'm'; }();      // (A/B: the depth stage in front of the emit kernels, on their stream)
+            const bool depth_on_main = knob::depth_on_main();      // (A/B: the depth stage in front of the emit kernels, on their stream)
             hipStream_t st2 = depth_on_main ? st : (hipStream_t)ds.ctx->stream2;
             HIP_TRY(hipEventRecord((hipEvent_t)T.pending.evw, st));
             HIP_TRY(hipStreamWaitEvent(st2, (hipEvent_t)T.pending.evw, 0));
@@ -3224,7 +3224,7 @@ int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *stre
                     HIP_TRY(hipStreamSynchronize(st));
                     n_runs = (uint32_t)(last >> 32); n_groups = (uint32_t)last;
                 }
-                in_order = misc_h[MISC_SORT] != 0 || [] { const char *e = getenv("MSNV_TILE_ORDER"); return e && e[0] == 's'; }();      // (the tile order's route: the depth kernel writes the pieces' depths at their header slots)
+                in_order = misc_h[MISC_SORT] != 0 || knob::tile_order_sort();      // (the tile order's route: the depth kernel writes the pieces' depths at their header slots)
                 totals_h = tot;
                 HIP_TRY(hipMemcpyAsync(d_pre + NR, &totals_h, sizeof(RecCnt), hipMemcpyHostToDevice, st));
                 DP_BUF(uint32_t, c_runfirst, (uint64_t)n_runs + 1);
@@ -3255,7 +3255,7 @@ int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *stre
                 if (int rc = check_errors()) return rc;
                 // ---- overlapping mates: the candidates grouped by (sample, name); nothing is edited yet (MSNV_OVERLAP=host: the host pre-pass does it).
                 // The second pass lists them again when msnv_cap_reads has taken reads out: a dropped read is no candidate (sam.c overlap_remove)
-                const bool ovl_on_host = [] { const char *e = getenv("MSNV_OVERLAP"); return e && e[0] == 'h'; }();
+                const bool ovl_on_host = knob::overlap_on_host();
                 bool any_ovl = false;
                 for (size_t s = 0; s < S; ++s) any_ovl |= !MP.ignore_overlaps && acc[s].n_ovl >= 2;
                 if (pass == 1 && !dev_cap.empty()) { n_ovl_reads = 0; n_ovl_groups = 0; }
@@ -3309,7 +3309,7 @@ int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *stre
                 // ---- which samples need the sequential edits?  The depth cap and the token limit are kernels (msnv_cap_reads, msnv_token_cut; round 6);
                 // the host pre-pass keeps what they do not take: a template with more alignments than the overlap kernel's slots, an element longer
                 // than the tables can say, a round with far-reaching reads (the cap kernel's ring, the token kernel's window) -- and MSNV_PREPASS=host
-                const bool prepass_on_host = [] { const char *e = getenv("MSNV_PREPASS"); return e && e[0] == 'h'; }();      // (read per round: the tests switch it)
+                const bool prepass_on_host = knob::prepass_on_host();      // (read per round: the tests switch it)
                 const bool kernels_can = !prepass_on_host && misc_h[MISC_NOUT] == 0u && span_out == SPAN_OUT && misc_h[MISC_SPAN] <= CAP_RING;
                 std::vector<size_t> need;
                 for (size_t s = 0; s < S; ++s) {
@@ -3410,7 +3410,7 @@ int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *stre
         if (int rc = pin_ensure(ds, std::max<uint64_t>(o_end, S * sizeof(DpAcc)))) return rc;
         uint8_t *pinb = static_cast<uint8_t *>(T.pin) + T.pin_cap / 2;
         if (route == 0) {
-            static const bool depth_on_main = [] { const char *e = getenv("MSNV_DEPTH_STREAM"); return e && e[0] == 'm'; }();
+            const bool depth_on_main = knob::depth_on_main();
             hipStream_t st2 = depth_on_main ? st : (hipStream_t)ds.ctx->stream2;          // (behind the depth stage: its stream)
             HIP_TRY(hipMemcpy2DAsync(pinb + o_acc, sizeof(DpAcc), d_acc, sizeof(DpAcc) * ACC_COPIES, sizeof(DpAcc), S, hipMemcpyDeviceToHost, st2));
             HIP_TRY(hipMemcpyAsync(pinb + o_rb, d_recbase, b_rb, hipMemcpyDeviceToHost, st2));
@@ -3431,8 +3431,8 @@ int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *stre
             A.hdr = w_hdr; A.ptid = w_tid; A.pend = w_end; A.cov_tid = keep.cov_tid; A.cov_beg = keep.cov_beg; A.cov_end = keep.cov_end;
             A.noseq_counts = (P.c_eff == 0 && !P.all_low) ? 1u : 0u;
             A.pref4 = T.pref4; A.P = P; A.dst = d_dst; A.acc = d_acc;
-            A.slow = d_slow; A.force_slow = [] { const char *e = getenv("MSNV_EMIT"); return e && e[0] == 's'; }() ? 1u : 0u;
-            static const bool dbg = getenv("MSNV_DEBUG_SYNC") != nullptr;
+            A.slow = d_slow; A.force_slow = knob::emit_slow() ? 1u : 0u;
+            const bool dbg = knob::debug_sync();
             if (dbg) { HIP_TRY(hipStreamSynchronize(st)); fin_trace("  dbg: before emit"); }
             hipLaunchKernelGGL(msnv_emit_block, dim3((unsigned)NB), dim3(256), 0, st, A);
             if (dbg) { HIP_TRY(hipStreamSynchronize(st)); fin_trace("  dbg: emit_block"); }
@@ -3441,7 +3441,7 @@ int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *stre
             HIP_TRY(hipGetLastError());
         }
         hipLaunchKernelGGL(msnv_emit_tail, dim3((unsigned)S), dim3(64), 0, st, d_dst, d_pb, (uint32_t)S, P);
-        if (getenv("MSNV_DEBUG_SYNC")) { HIP_TRY(hipStreamSynchronize(st)); fin_trace("  dbg: emit_tail"); }
+        if (knob::debug_sync()) { HIP_TRY(hipStreamSynchronize(st)); fin_trace("  dbg: emit_tail"); }
         if (route == 0) HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)T.pending.evd2, 0));      // (the depth stage's last words into the accumulators: in front of their fold)
         hipLaunchKernelGGL(msnv_acc_fold, dim3((unsigned)S), dim3(64), 0, st, d_acc, (uint32_t)S);
         HIP_TRY(hipGetLastError());
@@ -4142,7 +4142,7 @@ int devfin_merged_headers(msnv_dataset &ds, DeviceCols &d, const std::vector<Dev
 static bool cov_dense_form(const msnv_dataset &ds, unsigned long long N) {
     const unsigned long long n_tab = (unsigned long long)ds.samples.size() * ds.n_tiles;
     bool dense_tab = n_tab <= std::max<unsigned long long>(8ull * N, 1ull << 22) && n_tab < 0xfffffff0ull;
-    if (const char *e = getenv("MSNV_COV_INDEX")) dense_tab = e[0] == 'd' ? n_tab < 0xfffffff0ull : e[0] == 's' ? false : dense_tab;
+    if (const char how = knob::cov_index()) dense_tab = how == 'd' ? n_tab < 0xfffffff0ull : false;
     return dense_tab;
 }
 int devfin_coverage_launch(msnv_dataset &ds, DeviceCols &d) {
@@ -4153,7 +4153,7 @@ int devfin_coverage_launch(msnv_dataset &ds, DeviceCols &d) {
     for (size_t s = 0; s < S; ++s) iv_start[s + 1] = iv_start[s] + ds.samples[s].n_dev_iv;
     const unsigned long long N = iv_start[S];
     const unsigned long long n_tab = (unsigned long long)S * ds.n_tiles;
-    if (N > 0xfffffff0ull || !cov_dense_form(ds, N) || n_tab > (1ull << 24) || getenv("MSNV_COV_LATE")) return MSNV_OK;
+    if (N > 0xfffffff0ull || !cov_dense_form(ds, N) || n_tab > (1ull << 24) || knob::cov_late()) return MSNV_OK;
     if (int rc = pin_ensure(ds, (2 * S + 64) * 4)) return rc;
     auto up = [](unsigned long long b) { return (b + 255ull) & ~255ull; };
     const unsigned long long b_tb = up(std::max<size_t>(1, ds.tile_base.size()) * 4), b_ivs = up((S + 1) * 8), b_cvb = up((S + 4) * 4);
@@ -4208,7 +4208,7 @@ int devfin_coverage_launch(msnv_dataset &ds, DeviceCols &d) {
     // ---- the pair tables' counts (round 6: the tables themselves are written on the device once the host has allocated them, devfin_coverage)
     T.cov_tables = nullptr;
     {
-        const bool on_host = [] { const char *e = getenv("MSNV_COV_TABLES"); return e && e[0] == 'h'; }();
+        const bool on_host = knob::cov_tables_on_host();
         const size_t NC = ds.names.size(), nt = ds.n_tiles;
         const unsigned long long n_sc = (unsigned long long)S * NC;
         if (!on_host && NC && nt && ds.tile_contig.size() >= nt) {
@@ -4232,8 +4232,8 @@ int devfin_coverage_launch(msnv_dataset &ds, DeviceCols &d) {
             HIP_TRY(hipMemcpyAsync(tcont, ds.tile_contig.data(), nt * 4, hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemsetAsync(pres, 0, c_sc, st));
             HIP_TRY(hipMemsetAsync(counts, 0, 32, st));
-            const uint32_t item_intervals = [] { const char *e = getenv("MSNV_COV_ITEM"); const long long v = e ? atoll(e) : 16384; return (uint32_t)std::min<long long>(v > 0 ? v : 16384, 0x7fffffffll); }();
-            const uint32_t narrow_max = [] { const char *e = getenv("MSNV_COV_NARROW_MAX"); const long long v = e ? atoll(e) : 32767; return (uint32_t)std::min<long long>(32767, std::max<long long>(1, v)); }();
+            const uint32_t item_intervals = knob::cov_item_intervals();
+            const uint32_t narrow_max = knob::cov_narrow_max();
             T.cov_item_intervals = item_intervals;
             hipLaunchKernelGGL(msnv_cov_flags_t, grid_for(n_tab + 1, 256), dim3(256), 0, st, hi, (uint32_t)S, ds.n_tiles, tcont, (uint32_t)NC, flag_t, pres);
             HIP_TRY(hipGetLastError());
@@ -4281,7 +4281,7 @@ int devfin_coverage(msnv_dataset &ds, DeviceCols &d, std::vector<uint64_t> &cvba
             // the pair tables on the device: their sizes came with the index's counts; the rows' (sample, contig) names come down, nothing else
             const uint32_t n_pairs = pw[S + 16], n_rows = pw[S + 17], n_work = pw[S + 18];
             const size_t NC = ds.names.size();
-            static const bool guard = [] { const char *e = getenv("MSNV_GUARD_ALLOC"); return e && e[0] == '1'; }();
+            const bool guard = knob::guard_alloc();
             const uint64_t b_p = ((uint64_t)(n_pairs + 1) * sizeof(TilePair) + 255) & ~255ull, b_w = std::max<uint64_t>(16, (uint64_t)(n_work + 1) * sizeof(WorkItem));
             if (guard) {
                 if (int rc = dev_alloc((void **)&d.cov_pairs, (uint64_t)(n_pairs + 1) * sizeof(TilePair), &d.device_bytes)) return rc;
@@ -4869,8 +4869,8 @@ int devpack_place_columns(msnv_dataset &ds, DeviceCols &d, const std::vector<uin
         }
         return sbase[R.first_sample + R.n_samples] - sbase[R.first_sample] == R.seq_total;
     };
-    const bool guard = [] { const char *e = getenv("MSNV_GUARD_ALLOC"); return e && e[0] == '1'; }();      // (guarded buffers end at the end of their mapping: no adoption of a buffer that holds two columns)
-    if (T.rounds.size() == 1 && T.rounds[0].first_sample == 0 && T.rounds[0].n_samples == S && in_place(T.rounds[0]) && !guard && !getenv("MSNV_NO_ADOPT")) {
+    const bool guard = knob::guard_alloc();      // (guarded buffers end at the end of their mapping: no adoption of a buffer that holds two columns)
+    if (T.rounds.size() == 1 && T.rounds[0].first_sample == 0 && T.rounds[0].n_samples == S && in_place(T.rounds[0]) && !guard && !knob::no_adopt()) {
         DevRound &R = T.rounds[0];
         d.seq = R.col_seq; d.qual = R.col_qual;
         d.blocks.emplace_back(R.col_buf, R.seq_total + COL_PAD + R.seq_total / 4 + 64);

@@ -25,10 +25,9 @@ namespace msnv {
 // (profiles/stage_threads.py).  Twice the quota: a thread that waits for a page fault or a read leaves its share to another.
 static double g_quota_cores = 0;       // CPU time the container is given, in cores (0: no quota)
 static std::chrono::steady_clock::time_point g_fin_trace_t;
-static bool fin_trace_on() { static const bool on = [] { const char *e = getenv("MSNV_FINALIZE_TRACE"); return e && e[0] == '1'; }(); return on; }
-void fin_trace_reset() { if (fin_trace_on()) g_fin_trace_t = std::chrono::steady_clock::now(); }
+void fin_trace_reset() { if (knob::finalize_trace()) g_fin_trace_t = std::chrono::steady_clock::now(); }
 void fin_trace(const char *what) {
-    if (!fin_trace_on()) return;
+    if (!knob::finalize_trace()) return;
     const auto now = std::chrono::steady_clock::now();
     fprintf(stderr, "[finalize] %-44s %9.3f ms\n", what, 1e3 * std::chrono::duration<double>(now - g_fin_trace_t).count());
     g_fin_trace_t = now;
@@ -66,7 +65,7 @@ void msnv_drop_pages(void *p, size_t bytes) {
 
 void msnv_advise_huge(void *p, size_t bytes) {
 #if defined(MADV_HUGEPAGE)
-    static const int mode = [] { const char *e = getenv("MSNV_HUGE"); return e ? atoi(e) : 1; }();      // 0: small pages; 2: huge pages, populated now (experiments: profiles/stage_threads.py)
+    const int mode = knob::huge_pages();      // 0: small pages; 2: huge pages, populated now (experiments: profiles/stage_threads.py)
     if (mode == 0) return;
     (void)madvise(p, bytes, MADV_HUGEPAGE);
 #if defined(MADV_POPULATE_WRITE)
@@ -208,7 +207,7 @@ static bool inflate_block(const uint8_t *src, uint32_t n_in, uint8_t *dst, uint3
     // (a member of ISIZE 0 is decoded like any other: zlib, through which htslib reads, refuses one whose payload is not an empty stream)
     uint8_t none = 0;
     if (n_out == 0) dst = &none;                                 // (zlib wants a pointer; nothing is written)
-    static const bool use_zlib = [] { const char *e = getenv("MSNV_INFLATE"); return e && e[0] == 'z'; }();     // MSNV_INFLATE=zlib: A/B of the two decoders
+    const bool use_zlib = knob::inflate_zlib();     // MSNV_INFLATE=zlib: A/B of the two decoders
     static const bool bmi2 = __builtin_cpu_supports("bmi2") != 0;
     if (!use_zlib && (bmi2 ? inflate_raw_bmi2(src, n_in, dst, n_out) : inflate_raw(src, n_in, dst, n_out))) return true;
     // zlib decides about anything the fast decoder refuses (a malformed block fails here too); counted: a well-formed file never gets here
@@ -251,7 +250,7 @@ int bgzf_read_all(const char *path, ByteBuf &out, int threads) {
     std::atomic<size_t> next{0};
     std::atomic<bool> bad{false};
     // every block's output is checked against the CRC-32 of its BGZF trailer, as htslib does (MSNV_INFLATE_CHECK=0 skips it: benchmarks)
-    const uint32_t check_every = inflate_check_every();
+    const uint32_t check_every = knob::inflate_check_every();
     auto worker = [&]() {
         HostTimerScope ts(HT_INFLATE_HOST);
         for (;;) {

@@ -344,7 +344,7 @@ __global__ __launch_bounds__(64, MSNV_INFLATE_WAVES) void msnv_inflate_blocks(co
 
 // Pinned staging of a context, grown on demand: *in holds `in_bytes` compressed bytes (the caller fills it), *out receives the output.
 int dev_inflate_staging(msnv_ctx *ctx, uint64_t in_bytes, uint64_t out_bytes, uint8_t **in, uint8_t **out) {
-    if (const char *e = getenv("MSNV_TEST_NO_STAGING")) if (e[0] == '1') return fail_quiet(MSNV_ENOMEM, "staging refused (MSNV_TEST_NO_STAGING=1)");   // tests: the host takes the batch
+    if (knob::test_no_staging()) return fail_quiet(MSNV_ENOMEM, "staging refused (MSNV_TEST_NO_STAGING=1)");   // tests: the host takes the batch
     auto grow = [](void **p, uint64_t *cap, uint64_t need, bool host) -> int {
         if (need <= *cap) return MSNV_OK;
         if (*p) { if (host) (void)hipHostFree(*p); else dev_free(*p); *p = nullptr; *cap = 0; }
@@ -445,9 +445,9 @@ __global__ __launch_bounds__(256) void msnv_crc_blocks(const uint8_t *out, const
 
 // The device halves of the staging only (compressed batch in, inflated batch out): the resident path below needs no pinned memory.
 int dev_inflate_device_buffers(msnv_ctx *ctx, uint64_t in_bytes, uint64_t out_bytes) {
-    if (const char *e = getenv("MSNV_TEST_NO_STAGING")) if (e[0] == '1') return fail_quiet(MSNV_ENOMEM, "staging refused (MSNV_TEST_NO_STAGING=1)");
+    if (knob::test_no_staging()) return fail_quiet(MSNV_ENOMEM, "staging refused (MSNV_TEST_NO_STAGING=1)");
     // (through dev_alloc: with MSNV_GUARD_ALLOC=1 the buffers are exact and end at the end of their mapping -- tests/test_gpu_guard.py)
-    const bool exact = [] { const char *e = getenv("MSNV_GUARD_ALLOC"); return e && e[0] == '1'; }();
+    const bool exact = knob::guard_alloc();
     auto grow = [&](void **p, uint64_t *cap, uint64_t need) -> int {
         if (need <= *cap && !exact) return MSNV_OK;
         if (*p) { dev_free(*p); *p = nullptr; *cap = 0; }

@@ -2304,7 +2304,7 @@ __device__ __forceinline__ void gather_merged_block(const TailArgs &a, const uin
     if (gi < a.n_merged_run) gather_merged_group<64, GMW_CELLS, GMW_PAIRS, GMW_HITS>(a, a.merged_groups[gi], s_pool + (threadIdx.x >> 6) * GMW_WORDS, threadIdx.x & 63u);
 }
 static bool merged_wave_form(const DeviceCols &d) {
-    const int forced = [] { const char *e = getenv("MSNV_MERGED_GATHER"); return !e ? 0 : e[0] == 'b' ? 1 : e[0] == 'w' ? 2 : 0; }();      // (per pass: tests switch it)
+    const int forced = knob::merged_gather();      // (per pass: tests switch it)
     return d.max_group_pairs <= GMW_PAIRS && forced != 1;
 }
 
@@ -2612,7 +2612,6 @@ int dev_set_device(int device) {
 struct GuardedAlloc { void *va; size_t reserved, mapped; hipMemGenericAllocationHandle_t handle; };
 static std::mutex g_guard_mu;
 static std::unordered_map<void *, GuardedAlloc> g_guarded;
-static bool guard_alloc_enabled() { static const bool on = [] { const char *e = getenv("MSNV_GUARD_ALLOC"); return e && e[0] == '1'; }(); return on; }
 
 // Device memory goes through a small caching allocator: a buffer that is given back keeps its mapping and serves the next request of about
 // its size.  hipFree of the rounds' work buffers and columns was a quarter of finalize's wall time (110 us a call on average, 0.7 ms for the
@@ -2628,7 +2627,7 @@ static std::vector<CacheBlock> g_cache_free;
 static std::unordered_map<void *, CacheBlock> g_cache_live;
 static uint64_t g_cache_free_bytes = 0;
 static uint64_t cache_cap_bytes(int dev) {                          // per device: the default is a share of THAT device's memory (the caller has made it current)
-    static const long long env_mb = [] { const char *e = getenv("MSNV_DEV_CACHE_MB"); return e ? std::max<long long>(0, atoll(e)) : -1ll; }();
+    const long long env_mb = knob::dev_cache_mb();
     if (env_mb >= 0) return (uint64_t)env_mb << 20;
     static std::mutex mu;
     static std::unordered_map<int, uint64_t> caps;
@@ -2654,7 +2653,7 @@ void dev_cache_trim() {
 int dev_alloc(void **p, uint64_t bytes, uint64_t *acct) {
     *p = nullptr;
     if (bytes == 0) bytes = 16;
-    if (guard_alloc_enabled()) {
+    if (knob::guard_alloc()) {
         int dev = 0;
         HIP_TRY(hipGetDevice(&dev));
         hipMemAllocationProp prop = {};
@@ -2673,8 +2672,8 @@ int dev_alloc(void **p, uint64_t bytes, uint64_t *acct) {
         HIP_TRY(hipMemSetAccess(g.va, g.mapped, &ad, 1));
         const size_t used = (size_t)((bytes + 15) & ~(uint64_t)15);  // (the buffers are read with 16-byte loads: keep that alignment)
         *p = static_cast<char *>(g.va) + (g.mapped - used);
-        if (const char *e = getenv("MSNV_GUARD_FILL")) { HIP_TRY(hipMemset(g.va, atoi(e), g.mapped)); HIP_TRY(hipStreamSynchronize(nullptr)); }      // (fresh mappings are not defined to be zero: 0 or 255 tells a read of unwritten memory)
-        if (getenv("MSNV_GUARD_LOG")) fprintf(stderr, "[guard] %p .. %p (%llu bytes; mapping %p + %zu)\n", *p, static_cast<char *>(*p) + bytes, (unsigned long long)bytes, g.va, g.mapped);
+        if (int fill = 0; knob::guard_fill(&fill)) { HIP_TRY(hipMemset(g.va, fill, g.mapped)); HIP_TRY(hipStreamSynchronize(nullptr)); }      // (fresh mappings are not defined to be zero: 0 or 255 tells a read of unwritten memory)
+        if (knob::guard_log()) fprintf(stderr, "[guard] %p .. %p (%llu bytes; mapping %p + %zu)\n", *p, static_cast<char *>(*p) + bytes, (unsigned long long)bytes, g.va, g.mapped);
         std::lock_guard<std::mutex> lk(g_guard_mu);
         g_guarded[*p] = g;
     } else {
@@ -2711,7 +2710,7 @@ int dev_alloc(void **p, uint64_t bytes, uint64_t *acct) {
 }
 void dev_free(void *p) {
     if (!p) return;
-    if (guard_alloc_enabled()) {
+    if (knob::guard_alloc()) {
         GuardedAlloc g{};
         {
             std::lock_guard<std::mutex> lk(g_guard_mu);
@@ -2757,7 +2756,7 @@ void dev_free(void *p) {
 // Many buffers of ONE owner at once (the device pack's tables and work buffers at the end of finalize): one wait for the device, not one per buffer.
 void dev_free_batch(const std::vector<void *> &ptrs) {
     if (ptrs.empty()) return;
-    if (guard_alloc_enabled()) { for (void *p : ptrs) dev_free(p); return; }
+    if (knob::guard_alloc()) { for (void *p : ptrs) dev_free(p); return; }
     (void)hipDeviceSynchronize();                                   // (the owner's device is current: devpack_finish / msnv_dataset_destroy set it)
     std::vector<CacheBlock> evict; std::vector<void *> foreign;
     {
@@ -2890,7 +2889,7 @@ static int enqueue_pass(DeviceCols &d, const msnv_params &p, hipStream_t st, hip
         if (n_narrow && d.dense) hipLaunchKernelGGL(msnv_pileup_tiles_dense, dim3(n_narrow), dim3(N_NT), 0, st, a);      // (the dense layout never merges)
         else {
             // (whole-tile items of a sparse cohort are the last items of the work list: a launch of their own since round 6, msnv_pileup_tiles_lean)
-            const bool lean_off = [] { const char *e = getenv("MSNV_LEAN"); return e && e[0] == '0'; }();      // (read per pass: the tests switch it)
+            const bool lean_off = knob::lean_off();      // (read per pass: the tests switch it)
             const uint32_t n_lean = (use_stage && !lean_off) ? d.n_work_fused : 0u, n_all = n_narrow + n_merged - n_lean;
             if (n_all && d.allele_planes) hipLaunchKernelGGL(msnv_pileup_tiles_narrow32_planes, dim3(n_all), dim3(N_NT), 0, st, a);
             else if (n_all) hipLaunchKernelGGL(msnv_pileup_tiles_narrow32, dim3(n_all), dim3(N_NT), 0, st, a);
@@ -2929,8 +2928,7 @@ static int enqueue_pass(DeviceCols &d, const msnv_params &p, hipStream_t st, hip
         g.n_active = n_dense;
         g.zero_next = 1u; g.tile_list = nullptr; g.solo_cells = 0u;
         if (n_dense) {
-            g.tiles_per_wg = n_dense >= 32768u ? 8u : n_dense >= 8192u ? 4u : 1u;
-            if (const char *e = getenv("MSNV_GATE_TILES")) g.tiles_per_wg = (uint32_t)std::min<int>((int)GATE_MAX_TILES, std::max(1, atoi(e)));
+            g.tiles_per_wg = knob::gate_tiles(n_dense >= 32768u ? 8u : n_dense >= 8192u ? 4u : 1u, (int)GATE_MAX_TILES);
             const dim3 grid((n_dense + g.tiles_per_wg - 1) / g.tiles_per_wg);
             g.aspill = d.aspill;
             if (d.allele_planes) {
@@ -2977,7 +2975,7 @@ static int enqueue_pass(DeviceCols &d, const msnv_params &p, hipStream_t st, hip
         ta.gather_split = d.gather_split;
         ta.has_wide = d.n_work > d.n_work_narrow + d.n_work_merged ? 1u : 0u;
         ta.aspill = d.allele_planes ? d.aspill : nullptr;
-        static const uint32_t tail_skip = [] { const char *e = getenv("MSNV_TAIL_SKIP"); return e ? (uint32_t)atoi(e) : 0u; }();
+        const uint32_t tail_skip = knob::tail_skip();
         ta.debug_skip = tail_skip;
         ta.n_gather_blocks = d.n_gather_tiles * d.gather_split;
         ta.tile_pair_merged = d.tile_pair_merged; ta.merged_groups = d.merged_groups; ta.chunks = d.chunks; ta.hdr8m = d.hdr8m;
@@ -2986,7 +2984,7 @@ static int enqueue_pass(DeviceCols &d, const msnv_params &p, hipStream_t st, hip
         ta.site_flags = d.site_flags; ta.site_elig = d.site_elig; ta.ind_in_gather = d.any_split ? 0u : 1u; ta.min_snvs = (uint32_t)std::max(1, p.calling_threshold);
         ta.events = d.events; ta.overflow = d.overflow; ta.counters = counters; ta.cap_list = d.cap_events / EV_LISTS; ta.cap_overflow = d.cap_overflow;
         ta.site_bits = d.site_bits; ta.site_rank = d.site_rank;
-        static const uint32_t scatter_blocks = [] { const char *e = getenv("MSNV_SCATTER_BLOCKS"); return e ? (uint32_t)std::max(1, atoi(e)) : SCATTER_BLOCKS_PER_LIST; }();
+        const uint32_t scatter_blocks = knob::scatter_blocks(SCATTER_BLOCKS_PER_LIST);
         ta.scatter_blocks = scatter_blocks;
         const dim3 grid(ta.n_gather_blocks + ta.n_merged_blocks + ta.scatter_blocks * EV_LISTS + 1u);      // + 1: the event total
         if (ta.n_merged_blocks) hipLaunchKernelGGL(msnv_gather_scatter<true>, grid, dim3(256), 0, st, ta);
@@ -3027,7 +3025,7 @@ int dev_run_pipeline(DeviceCols &d, const msnv_params &p, void *stream_, msnv_ru
     }
     // every event record costs ~6 us of stream time (the next kernel waits for the marker): the per-phase split of
     // the tail is only recorded on request (MSNV_PHASE_TIMES=1, profiles/phase_times.py)
-    static const bool phase_times = [] { const char *e = getenv("MSNV_PHASE_TIMES"); return e && e[0] == '1'; }();
+    const bool phase_times = knob::phase_times();
     if (int rc = ensure_out(d, std::max<uint64_t>(d.last_sites + d.last_sites / 2, 4096), std::max<uint64_t>(d.last_cells + d.last_cells / 2, 1u << 18))) return rc;
     uint32_t cnt[CNT_WORDS] = {0};
     if (int rc = enqueue_pass(d, p, st, ev[0], ev[1], ev[2], phase_times ? ev[3] : nullptr, phase_times ? ev[4] : nullptr, cnt)) return rc;

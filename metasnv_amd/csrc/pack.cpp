@@ -54,9 +54,7 @@ static void pack_lowq(const uint8_t *q, size_t n, int cutoff, std::vector<uint8_
 // Dense wins for short pieces (50-base reads: -18 % kernel time), loses from ~100 bases on (kernels.hip), so the
 // dataset picks it when the mean piece is shorter than 62 bases.  MSNV_LAYOUT=pieces|dense overrides.
 static bool layout_dense(uint64_t n_pieces, uint64_t n_bases) {
-    const char *e = getenv("MSNV_LAYOUT");
-    if (e && e[0] == 'p') return false;
-    if (e && e[0] == 'd') return true;
+    if (const char forced = knob::layout()) return forced == 'd';
     return n_pieces && n_bases / n_pieces < 62;      // (round 3, one bit of quality per base, eight workgroups per CU: 50-base reads 0.589 vs 0.535 ms, 75-base reads 0.476 vs 0.535 -- break-even near 62; it was 72: profiles/r03zap_layout_by_read_length.txt)
 }
 
@@ -67,18 +65,9 @@ static bool layout_dense(uint64_t n_pieces, uint64_t n_bases) {
 // (sample, tile) pair and the per-sample results are summed on the device (gather / scatter accumulate).  The pieces of a
 // group are made contiguous -- headers AND bases / qualities (MSNV_DEEP_RELOCATE=0 leaves the columns in read order: every group's
 // workgroups then fetch almost every cache line of the run).  MSNV_DEEP=wide keeps such runs whole for msnv_pileup_tiles_wide instead.
-static bool deep_runs_split() {
-    const char *e = getenv("MSNV_DEEP");                     // read per dataset (tests switch it)
-    return !(e && e[0] == 'w');
-}
-static uint32_t deep_split_at() {
-    static const uint32_t v = [] { const char *e = getenv("MSNV_SPLIT_AT"); const int x = e ? atoi(e) : 192; return (uint32_t)std::min<int>((int)NARROW_MAX_DEPTH, std::max(32, x)); }();
-    return v;
-}
-static uint32_t deep_group_depth() {
-    static const uint32_t v = [] { const char *e = getenv("MSNV_GROUP_DEPTH"); const int x = e ? atoi(e) : 128; return (uint32_t)std::min(250, std::max(16, x)); }();
-    return v;
-}
+// MSNV_SPLIT_AT and MSNV_GROUP_DEPTH move the two depths; all three are read per dataset (knobs.h).
+static bool deep_runs_split() { return !knob::deep_wide(); }
+static uint32_t deep_split_at() { return knob::split_at((int)NARROW_MAX_DEPTH); }
 static int split_deep_runs(SampleCols &sc, int device) {
     const size_t n = sc.hdr.size();
     sc.grp.assign(n, 0);
@@ -87,13 +76,13 @@ static int split_deep_runs(SampleCols &sc, int device) {
     std::vector<Ev> ev;
     std::vector<uint32_t> cur, mx, order;
     bool any_split = false;
+    const uint32_t split_at = deep_split_at(), group_depth = knob::group_depth();
     size_t i = 0;
     while (i < n) {
         size_t j = i;
         while (j < n && sc.tid[j] == sc.tid[i] && sc.hdr[j].gpos / TILE == sc.hdr[i].gpos / TILE) ++j;
         uint32_t bound = 0;
         for (size_t k = i; k < j; ++k) bound = std::max<uint32_t>(bound, sc.depth[k]);
-        const uint32_t split_at = deep_split_at();
         if (bound >= split_at) {
             const size_t m = j - i;
             auto sweep = [&](uint32_t G) -> uint32_t {            // largest per-position depth of any group
@@ -112,7 +101,6 @@ static int split_deep_runs(SampleCols &sc, int device) {
             if (exact < split_at) {
                 for (size_t k = i; k < j; ++k) sc.depth[k] = (uint16_t)exact;        // the start-time bound was pessimistic
             } else {
-                const uint32_t group_depth = deep_group_depth();
                 uint32_t G = exact / group_depth + 1;
                 while (sweep(G) >= NARROW_MAX_DEPTH) ++G;
                 std::vector<uint32_t> gmax = mx;
@@ -134,7 +122,7 @@ static int split_deep_runs(SampleCols &sc, int device) {
     // The bases and qualities follow their headers: a group's pieces were every G-th piece of the run in memory, so the workgroups
     // of the G groups -- at G different times -- each fetched (almost) every cache line of the run (one sample at 1600x: 6.2 GB of
     // HBM reads per pass for 2.2 GB of columns).  Same pieces (bases + twice as many quality bytes, alignment padding included), new order.
-    if (any_split && !(getenv("MSNV_DEEP_RELOCATE") && getenv("MSNV_DEEP_RELOCATE")[0] == '0')) {
+    if (any_split && !knob::deep_relocate_off()) {
         if (sc.on_device) {                              // (the relocation still runs on host staging: a device-packed sample comes back for it)
             if (int rc = dev_set_device(device)) return rc;
             if (int rc = devpack_sample_to_host(sc)) return rc;
@@ -803,7 +791,7 @@ struct TableArena {
     }
     int commit(DeviceCols &d) {
         if (ents.empty()) return MSNV_OK;
-        static const bool guard = [] { const char *e = getenv("MSNV_GUARD_ALLOC"); return e && e[0] == '1'; }();
+        const bool guard = knob::guard_alloc();
         if (guard) {
             for (const Ent &e : ents) {
                 if (int rc = dev_alloc(e.dst, e.bytes, &d.device_bytes)) return rc;
@@ -838,21 +826,21 @@ int finalize_dataset(msnv_dataset &ds) {
         bool any_dev = false, all_dev = true;
         for (const SampleCols &sc : ds.samples) { any_dev |= sc.dev_index; all_dev &= sc.dev_index; }
         fast = any_dev && all_dev && HDR4 && deep_runs_split();
-        if (const char *e = getenv("MSNV_FINALIZE")) if (e[0] == 'h') fast = false;
+        if (knob::finalize_on_host()) fast = false;
         if (fast) {
             uint64_t np = 0, nb = 0;
             for (const SampleCols &sc : ds.samples) { np += sc.n_dev_pieces; nb += sc.n_pileup_bases; }
-            if (layout_dense(np, nb)) if (const char *e = getenv("MSNV_DENSE_RELAYOUT")) if (e[0] == 'h') fast = false;      // (the dense re-layout on host staging: tests compare the two)
+            if (layout_dense(np, nb) && knob::dense_relayout_on_host()) fast = false;      // (the dense re-layout on host staging: tests compare the two)
             // deep (sample, tile) runs: their exact depth, and -- where a run really is that deep -- its pieces dealt into groups and the sample's
             // columns re-laid, by kernels (devpack.hip: devfin_deep_runs; MSNV_DEEP_RELOCATE=0, a host-only experiment, takes the host loops)
             const uint32_t split_at = deep_split_at();
             bool any_deep = false;
             for (const SampleCols &sc : ds.samples) for (const DevPair &p : sc.dev_pairs) if (p.maxd >= split_at) { any_deep = true; break; }
             if (fast && any_deep) {
-                if (getenv("MSNV_DEEP_RELOCATE") && getenv("MSNV_DEEP_RELOCATE")[0] == '0') fast = false;
+                if (knob::deep_relocate_off()) fast = false;
                 else {
                     bool fallback = false;
-                    if (int rc = devfin_deep_runs(ds, split_at, deep_group_depth(), &fallback)) return rc;
+                    if (int rc = devfin_deep_runs(ds, split_at, knob::group_depth(), &fallback)) return rc;
                     if (fallback) fast = false;
                 }
             }
@@ -993,7 +981,7 @@ int finalize_dataset(msnv_dataset &ds) {
         // a coverage work item = COV_ITEM_PAIRS consecutive pairs of a tile = one wavefront of msnv_coverage_tiles, which loads their
         // descriptors up front and a pair's intervals while it works on the pair before (fewer when one pair alone is deep:
         // MSNV_COV_ITEM intervals)
-        const uint64_t cov_item_intervals = [] { const char *e = getenv("MSNV_COV_ITEM"); const long long v = e ? atoll(e) : 16384; return (uint64_t)(v > 0 ? v : 16384); }();
+        const uint64_t cov_item_intervals = knob::cov_item_intervals();
         for (uint64_t t = 0; t < nt; ++t) {
             uint32_t lo = cps[t]; uint64_t acc = 0;
             for (uint32_t k = cps[t]; k < cps[t + 1]; ++k) {
@@ -1004,7 +992,7 @@ int finalize_dataset(msnv_dataset &ds) {
         // the items with a pair of more than 32 767 intervals go last: msnv_coverage_tiles<true> (one word per position) runs them,
         // the 16-bit difference array of the usual variant holds +-32 767 per position and per 16 positions of one parity
         // (MSNV_COV_NARROW_MAX is read per dataset: tests lower it to run the other variant)
-        const uint32_t cov_narrow_max = [] { const char *e = getenv("MSNV_COV_NARROW_MAX"); const long long v = e ? atoll(e) : 32767; return (uint32_t)std::min<long long>(32767, std::max<long long>(1, v)); }();
+        const uint32_t cov_narrow_max = knob::cov_narrow_max();
         auto cov_wide = [&](const WorkItem &w) { for (uint32_t k = w.pair_lo; k < w.pair_hi; ++k) if (cpairs[k].read_hi - cpairs[k].read_lo > cov_narrow_max) return true; return false; };
         bool any_wide = false;
         for (const TilePair &q : cpairs) if (q.read_hi - q.read_lo > cov_narrow_max) { any_wide = true; break; }
@@ -1042,7 +1030,7 @@ int finalize_dataset(msnv_dataset &ds) {
         int join() { if (th.joinable()) th.join(); if (rc) return fail(rc, "%s", msg.c_str()); return MSNV_OK; }
         ~CovJob() { if (th.joinable()) th.join(); }
     } cov_job;
-    if (fast && ds.dp.cov_launched && getenv("MSNV_COV_THREAD")) {
+    if (fast && ds.dp.cov_launched && knob::cov_thread()) {
         const int device = ds.ctx ? ds.ctx->device : 0;
         cov_job.th = std::thread([&cov_job, &cov_index, &cov_arena, device]() {
             (void)dev_set_device(device);
@@ -1210,7 +1198,7 @@ int finalize_dataset(msnv_dataset &ds) {
         // 24 % of the roofline) and contigs much shorter than a tile put several pairs into the same bins.
         // MSNV_SHALLOW_PIECES: number of pieces up to which a pair counts as shallow (default 48 = 3/8 of a chunk; 0 = never
         // merge); its depth bound must leave room for at least three pairs in a group, and a tile needs two such pairs.
-        const uint32_t shallow_pieces = [] { const char *e = getenv("MSNV_SHALLOW_PIECES"); const int v = e ? atoi(e) : 48; return (uint32_t)std::max(0, v); }();   // read per dataset (tests switch it)
+        const uint32_t shallow_pieces = knob::shallow_pieces();   // read per dataset (tests switch it)
         const bool can_merge = !dense && shallow_pieces > 0 && sbase[S] < ((uint64_t)SEQ_ALIGN << 37);   // merged headers hold absolute seq offsets / SEQ_ALIGN in 37 bits
         auto is_shallow = [&](const TilePair &p) { return p.read_hi - p.read_lo <= shallow_pieces && p.max_depth <= MERGE_MAX_DEPTH / 3 && !p.pad; };
         // ... and only when the shallow pairs are a real share of the dataset (>= 3 % of its pieces): a few of them -- the
@@ -1223,10 +1211,10 @@ int finalize_dataset(msnv_dataset &ds) {
         {
             uint64_t tiles_with_pairs = 0;
             for (uint64_t t = 0; t < nt; ++t) tiles_with_pairs += tps[t + 1] > tps[t];
-            const char *fe = getenv("MSNV_FUSE");
+            const char forced = knob::fuse();
             const bool sparse = tiles_with_pairs && pairs.size() < 4 * tiles_with_pairs;
-            const bool fuse_on = can_merge && !(fe && fe[0] == '0') && (sparse || (fe && fe[0] == '1'));
-            const uint32_t fuse_pieces = [] { const char *e = getenv("MSNV_FUSE_PIECES"); return (uint32_t)std::max(1, e ? atoi(e) : 256); }();
+            const bool fuse_on = can_merge && forced != '0' && (sparse || forced == '1');
+            const uint32_t fuse_pieces = knob::fuse_pieces();
             if (fuse_on) for (uint64_t t = 0; t < nt; ++t) {
                 const uint32_t n = tps[t + 1] - tps[t];
                 if (n == 0 || n > MERGE_MAX_PAIRS) continue;
@@ -1242,7 +1230,7 @@ int finalize_dataset(msnv_dataset &ds) {
                 for (uint32_t k = tps[t]; k < tps[t + 1]; ++k) { all_pieces += pairs[k].read_hi - pairs[k].read_lo; if (is_shallow(pairs[k])) { ++n_shallow; np += pairs[k].read_hi - pairs[k].read_lo; } }
                 if (n_shallow >= 2) { merge_tile[t] = 1; shallow_pieces_total += np; }
             }
-            const bool force = [] { const char *e = getenv("MSNV_MERGE_ALWAYS"); return e && e[0] == '1'; }();   // (tests)
+            const bool force = knob::merge_always();   // (tests)
             if (!force && shallow_pieces_total * 100 < all_pieces * 3) std::fill(merge_tile.begin(), merge_tile.end(), 0);
         }
         for (uint64_t t = 0; t < nt; ++t) {
@@ -1302,8 +1290,7 @@ int finalize_dataset(msnv_dataset &ds) {
         // (round 3, after the kernel had lost 9 % of its time: 1000 -> 0.5544 ms kernel / 0.6269 ms pass, 1400 -> 0.5520 / 0.6232,
         // 2000 -> 0.5510 / 0.6197, 2800 -> 0.5536 / 0.6235 over four alternations, profiles/r03k_ab_items.txt: flat in the kernel, the gate
         // kernel sums fewer partial rows)
-        uint64_t target = 2000;
-        if (const char *e = getenv("MSNV_ITEM_PIECES")) target = std::max<uint64_t>(64, (uint64_t)atoll(e));
+        uint64_t target = knob::item_pieces();
         std::vector<WorkItem> wide, merged;
         auto chunks_of = [&](const TilePair &q) -> uint64_t {
             const bool nar = q.max_depth < NARROW_MAX_DEPTH;
@@ -1315,9 +1302,9 @@ int finalize_dataset(msnv_dataset &ds) {
         // item), not fractions of the dataset: on the benchmark shape (16 M pieces) they are the last 20 / 8 / 3 %, at
         // BASELINE configs[2] scale (514 M pieces) the last 0.6 % -- tapering a fixed fraction there cost 5 %.
         // MSNV_ITEM_TAPER=0 switches it off; MSNV_TAPER_AT=u1,u2,u3 moves the thresholds.
-        const bool taper = [] { const char *e = getenv("MSNV_ITEM_TAPER"); return !(e && e[0] == '0'); }();   // read per dataset (tests switch it)
-        double u1 = 1.8, u2 = 0.73, u3 = 0.27;
-        if (const char *e = getenv("MSNV_TAPER_AT")) sscanf(e, "%lf,%lf,%lf", &u1, &u2, &u3);
+        const bool taper = knob::item_taper();   // read per dataset (tests switch it)
+        const knob::TaperAt at = knob::taper_at();
+        const double u1 = at.u1, u2 = at.u2, u3 = at.u3;
         const uint64_t base_target = target;
         const double wave_pieces = (double)dev_resident_workgroups(7) * (double)base_target;   // 7 workgroups of 256 threads per CU (kernels.hip)
         uint64_t seen = 0;
@@ -1392,7 +1379,7 @@ int finalize_dataset(msnv_dataset &ds) {
             tile_bound[work[i].tile] += bound;
             cls[i] = i >= d->n_work_narrow + d->n_work_merged ? 2 : bound < 256 ? 0 : 1;
         }
-        const uint32_t min_tot_mode = [] { const char *e = getenv("MSNV_TOT_MODE"); return e ? (uint32_t)std::min(2, std::max(0, atoi(e))) : 0u; }();
+        const uint32_t min_tot_mode = knob::tot_mode_min();
         auto tot_mode = [&](uint64_t t) { return std::max<uint32_t>(min_tot_mode, tile_bound[t] < 256 ? 0u : tile_bound[t] < 65536 ? 1u : 2u); };
         std::vector<uint32_t> fill(tss.begin(), tss.end() - 1);
         std::vector<uint8_t> slot_cls(work.size(), 0);
@@ -1438,8 +1425,7 @@ int finalize_dataset(msnv_dataset &ds) {
         for (uint32_t t : active) gts.push_back(DeviceCols::GateTileH{t, tss[t], t16[t], twide[t], tss[t + 1], vb_host[t], ve_host[t], nslots_host[t], off[tss[t]], tot_mode(t), (uint32_t)fuse_tile[t],
                                                                       tps[t], tpm[t] - tps[t], 0, 0});
         if (int rc = arena.add(&d->gate_tiles, gts, &d->device_bytes, 1)) return rc;
-        d->gather_split = (uint32_t)std::min<uint64_t>(4, std::max<uint64_t>(1, (active.empty() ? 0 : pairs.size() / active.size()) / 32));
-        if (const char *e = getenv("MSNV_GATHER_SPLIT")) d->gather_split = (uint32_t)std::max(1, atoi(e));      // (tuning experiments)
+        d->gather_split = knob::gather_split((uint32_t)std::min<uint64_t>(4, std::max<uint64_t>(1, (active.empty() ? 0 : pairs.size() / active.size()) / 32)));
         {   // whole-tile work items write their candidate records per active tile
             std::vector<uint32_t> stage_idx(nt + 1, 0xffffffffu);
             uint32_t n_fused = 0;
@@ -1516,7 +1502,7 @@ int finalize_dataset(msnv_dataset &ds) {
             for (uint32_t k = work[wi].pair_lo; k < work[wi].pair_hi; ++k) { narrow_pairs.push_back(k); chunk_cap += (pairs[k].read_hi - pairs[k].read_lo + CHUNK_READS - 1) / CHUNK_READS + 2; }
         }
         item_first.push_back((uint32_t)narrow_pairs.size());
-        if (const char *e = getenv("MSNV_CHUNK_CAP")) chunk_cap = (uint64_t)std::max<long long>(0, atoll(e));      // (tests: a table too small on purpose -> the exact, waiting form)
+        chunk_cap = knob::chunk_cap(chunk_cap);      // (tests: a table too small on purpose -> the exact, waiting form)
         if (M + chunk_cap > 0xfffffff0ull) return fail(MSNV_EDOMAIN, "more than 2^32 chunks in one shard");
     }
     else for (uint32_t wi = 0; wi < d->n_work_narrow; ++wi) {
@@ -1688,7 +1674,7 @@ int finalize_dataset(msnv_dataset &ds) {
             // is longer than its contig, where "the reference" behind the contig's last tile position differs between the two)
             bool fasta_longer = false;
             for (size_t c = 0; c < NC; ++c) if (ds.sel[c] && ds.has_seq[c] && (int64_t)ds.seqs[c].size() > maxend[c]) fasta_longer = true;
-            if (!dense && (!ds.dp.pad_in_emit || fasta_longer || getenv("MSNV_FILL_PADDING"))) if (int rc = devpack_fill_padding(*d, on_dev, ds.ctx ? ds.ctx->stream : nullptr)) return rc;
+            if (!dense && (!ds.dp.pad_in_emit || fasta_longer || knob::fill_padding())) if (int rc = devpack_fill_padding(*d, on_dev, ds.ctx ? ds.ctx->stream : nullptr)) return rc;
         }
         for (size_t s = 0; s < S; ++s) {
             const SampleCols &sc = ds.samples[s];
@@ -1729,7 +1715,7 @@ int finalize_dataset(msnv_dataset &ds) {
         const double rate = sb ? (double)sm / (double)sb : 0.0;
         est_events = rate * (double)tot_bases;
         bool planes = rate >= 0.010;
-        if (const char *e = getenv("MSNV_ALLELES")) planes = e[0] == 'p';
+        if (const char forced = knob::alleles()) planes = forced == 'p';
         if (dense || d->n_work > d->n_work_narrow + d->n_work_merged || pairs.empty()) planes = false;
         d->allele_planes = planes;
         if (planes) {
@@ -1743,8 +1729,7 @@ int finalize_dataset(msnv_dataset &ds) {
     // sparse buffers: generous first guess, grown on MSNV_ECAPACITY by the caller
     // (the event list: four times the mismatching bases the sample of every 16th piece predicts, at most one per 16 bases -- the flat
     // "one per 16 bases" of the earlier rounds was 29 GB of HBM, and 1 s of hipMalloc, for BASELINE configs[2]'s 5.8e10 bases at 0.4 % of mismatches)
-    d->cap_events = (uint32_t)std::min<uint64_t>(0x7fffffffull, std::max<uint64_t>(1u << 20, std::min<uint64_t>(tot_bases / 16, (uint64_t)(4.0 * est_events) + (1u << 20))));
-    if (const char *e = getenv("MSNV_CAP_EVENTS")) d->cap_events = (uint32_t)std::max<long long>(EV_LISTS, atoll(e));   // tests: force the grow-and-rerun path
+    d->cap_events = knob::cap_events((uint32_t)std::min<uint64_t>(0x7fffffffull, std::max<uint64_t>(1u << 20, std::min<uint64_t>(tot_bases / 16, (uint64_t)(4.0 * est_events) + (1u << 20)))), EV_LISTS);   // (tests force the grow-and-rerun path)
     d->cap_overflow = (uint32_t)std::min<uint64_t>(0x7fffffffull, std::max<uint64_t>(1u << 16, npos / 8));
     d->cap_sites = (uint32_t)std::min<uint64_t>(0x7fffffffull, std::max<uint64_t>(1u << 16, npos / 4));
     if (int rc = dev_alloc((void **)&d->events, (uint64_t)d->cap_events * sizeof(Pair32), &d->device_bytes)) return rc;

@@ -337,7 +337,7 @@ static int run_chunk(msnv_ctx *ctx, const char *text, const std::vector<uint64_t
     HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
     // MSNV_TEXT_REPEAT=n (profiles/text_bench.py): n - 1 untimed launches first, so that the timed one runs at the clocks of a busy device
     hipError_t he = hipSuccess;
-    for (int rep = getenv("MSNV_TEXT_REPEAT") ? std::max(1, atoi(getenv("MSNV_TEXT_REPEAT"))) : 1; rep > 1 && he == hipSuccess; --rep) {
+    for (int rep = knob::text_repeat(); rep > 1 && he == hipSuccess; --rep) {
         hipLaunchKernelGGL(msnv_parse_pileup_lines, dim3(waves / (TC_NT / 64)), dim3(TC_NT), 0, st, a);
         he = hipMemcpyAsync(d_cnt.p, init, sizeof init, hipMemcpyHostToDevice, st);
     }
@@ -408,8 +408,7 @@ int text_call(msnv_ctx *ctx, const char *text, uint64_t n_text, const msnv_param
     std::vector<uint64_t> rec_line;                                                  // absolute line of every record
     double ms = 0; uint64_t bases = 0, lines_per_wave = 0;
     // ---- chunks of whole lines (<= ~256 MB of text each, MSNV_TEXT_CHUNK overrides: tests)
-    uint64_t chunk_bytes = 256ull << 20;
-    if (const char *e = getenv("MSNV_TEXT_CHUNK")) chunk_bytes = std::max<uint64_t>(1, (uint64_t)atoll(e));
+    const uint64_t chunk_bytes = knob::text_chunk_bytes(256ull << 20);
     for (uint64_t l0 = 1; l0 < n_lines;) {
         uint64_t l1 = l0 + 1;
         while (l1 < n_lines && lines[l1 + 1] - lines[l0] <= chunk_bytes && l1 - l0 < (1u << 30)) ++l1;

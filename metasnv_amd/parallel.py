@@ -20,6 +20,8 @@ import sys
 
 import numpy as np
 
+from . import knobs
+
 _dist = None
 _rank, _world, _local = 0, 1, 0
 
@@ -31,11 +33,11 @@ def init_from_env(force=False):
     _rank = int(os.environ.get("RANK", "0"))
     _world = int(os.environ.get("WORLD_SIZE", "1"))
     _local = int(os.environ.get("LOCAL_RANK", "0"))
-    force = force or os.environ.get("MSNV_DIST_FORCE") == "1"
+    force = force or knobs.dist_force()
     if (_world > 1 or force) and _dist is None:
         import torch
         import torch.distributed as dist
-        if torch.cuda.is_available() and os.environ.get("MSNV_DIST_BACKEND", "nccl") == "nccl":
+        if torch.cuda.is_available() and knobs.dist_backend_nccl():
             torch.cuda.set_device(_local)
             dist.init_process_group(backend="nccl", device_id=torch.device("cuda", _local))
         else:
@@ -200,7 +202,7 @@ def _a2a_selfcheck(dev, slice_bytes):
     slices its buffers to, checked on the device.  This stack has returned wrong bytes for large exchanges (round 4: an all_to_all_single of
     more than 2^30 uint8 elements, profiles/a2a_check.py); a collective that does not deliver what was sent must stop the run, loudly."""
     global _a2a_checked
-    if _a2a_checked or os.environ.get("MSNV_A2A_SELFCHECK", "1") == "0":
+    if _a2a_checked or not knobs.a2a_selfcheck():
         return
     _a2a_checked = True
     import torch
@@ -252,11 +254,11 @@ def exchange_records(parts, status=0, keep_on_device=False):
     # behind the first ~half of the buffer on this stack (RCCL of ROCm 7.2 under torch 2.10, found in round 4 at 1.1 GB per round:
     # profiles/a2a_check.py) -- and a round of a large cohort is several GB.  Every rank walks the same number of slices (the largest part
     # anywhere, from the size exchange above).
-    slice_bytes = int(os.environ.get("MSNV_A2A_SLICE_KB", "0")) << 10 or max(1 << 20, (1 << 29) // _world)      # (MSNV_A2A_SLICE_KB: tests)
+    slice_bytes = knobs.a2a_slice_bytes() or max(1 << 20, (1 << 29) // _world)      # (MSNV_A2A_SLICE_KB: tests)
     n_slices = max(1, -(-max(rmax + [0]) // slice_bytes))
     soff = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
     roff = np.concatenate([[0], np.cumsum(rsizes)]).astype(np.int64)
-    lists = dev.type == "cuda" and os.environ.get("MSNV_A2A_FORM", "lists") == "lists"
+    lists = dev.type == "cuda" and knobs.a2a_lists()
     if lists:
         _a2a_selfcheck(dev, slice_bytes)
     for j in range(n_slices):
@@ -324,7 +326,7 @@ def _stageable(paths):
     overrides the default of a quarter of the physical memory.)"""
     try:
         total = sum(os.path.getsize(p) for p in paths) * 4
-        limit = int(os.environ.get("MSNV_STAGE_MAX_MB", "0")) << 20
+        limit = knobs.stage_max_bytes()
         if limit <= 0:
             limit = os.sysconf("SC_PAGE_SIZE") * os.sysconf("SC_PHYS_PAGES") // 4
         return total <= limit
@@ -365,7 +367,7 @@ def feed_sharded(ds, bam_paths, owner, cov_min_mapq=1, batch=1, read_records=Non
             ds.attach_context(ctx_when_ready())
             ds.add_sample_bams(bam_paths, batch)
             return np.stack([ds.sample_stats(i) for i in range(n)]) if n else np.zeros((0, len(core.STATS_FIELDS)), np.uint32)
-        if getattr(ds, "ctx", None) is None and hasattr(ds, "stage_sample_bams") and os.environ.get("MSNV_PACK", "device")[:1] != "h" and _stageable(bam_paths):
+        if getattr(ds, "ctx", None) is None and hasattr(ds, "stage_sample_bams") and not knobs.pack_on_host() and _stageable(bam_paths):
             # the device is still coming up (cli.py brings the HIP runtime up on a thread of its own): the files are read and inflated now,
             # their records are packed by kernels once the context is attached (finalize); the statistics exist then
             ds.stage_sample_bams(bam_paths, batch)
@@ -391,8 +393,8 @@ def feed_sharded(ds, bam_paths, owner, cov_min_mapq=1, batch=1, read_records=Non
 
     def device_route(need_owner=True):
         return ((owner is not None or not need_owner) and _dist is not None and getattr(ds, "ctx", None) is not None and hasattr(ds, "deal_bams_device")
-                and os.environ.get("MSNV_PACK", "device")[:1] != "h" and os.environ.get("MSNV_DEAL", "device")[:1] != "h"
-                and os.environ.get("MSNV_INFLATE", "device")[:1] == "d" and _device().type == "cuda")
+                and not knobs.pack_on_host() and not knobs.deal_on_host()
+                and knobs.inflate_where("d") == "d" and _device().type == "cuda")
 
     def deal_files_on_device(paths):
         import torch
@@ -514,7 +516,7 @@ def feed_sharded(ds, bam_paths, owner, cov_min_mapq=1, batch=1, read_records=Non
                 failure, dev_send = e, None
             decoded = []
         deal_on_device = (dev_send is None and failure is None and len(decoded) > 0 and _dist is not None and getattr(ds, "ctx", None) is not None and hasattr(ds, "add_samples_records_device")
-                          and os.environ.get("MSNV_PACK", "device")[:1] != "h" and os.environ.get("MSNV_DEAL", "device")[:1] != "h" and _device().type == "cuda")
+                          and not knobs.pack_on_host() and not knobs.deal_on_host() and _device().type == "cuda")
         if deal_on_device:
             try:
                 import torch
@@ -557,7 +559,7 @@ def feed_sharded(ds, bam_paths, owner, cov_min_mapq=1, batch=1, read_records=Non
             send.append(np.concatenate([hdr] + per_dest[q]) if per_dest[q] else np.zeros(0, np.uint8))
         # over RCCL the received streams stay in HBM and are parsed / filtered / packed there (csrc/devpack.hip): no copy to the host, no host
         # pack, no second upload (MSNV_PACK=host keeps the round trip)
-        on_device = getattr(ds, "ctx", None) is not None and hasattr(ds, "add_samples_records_device") and os.environ.get("MSNV_PACK", "device")[:1] != "h"
+        on_device = getattr(ds, "ctx", None) is not None and hasattr(ds, "add_samples_records_device") and not knobs.pack_on_host()
         try:
             got = exchange_records(dev_send if dev_send is not None else send, status=0 if failure is None else int(getattr(failure, "code", 0)) or 99, keep_on_device=on_device)
         except RankError:
@@ -603,12 +605,12 @@ def feed_sharded(ds, bam_paths, owner, cov_min_mapq=1, batch=1, read_records=Non
     # in one launch of one wavefront per BGZF block, and seven files are ~3 000 blocks for 5 000 wavefront slots: as many files as fit three
     # quarters of a batch of the device inflate (the feed of the benchmark's 160 BAMs: 0.65 s at 7 files a round, 0.43 s at 32; round 6).
     # Every rank computes the same number from the same list.  MSNV_FEED_BATCH overrides.
-    if os.environ.get("MSNV_FEED_BATCH"):
-        batch = max(1, int(os.environ["MSNV_FEED_BATCH"]))
+    if knobs.feed_batch():
+        batch = knobs.feed_batch()
     elif read_many is not None and device_route(need_owner=False):
         try:
             largest = max(os.path.getsize(p) for p in bam_paths) if bam_paths else 0
-            room = (int(os.environ.get("MSNV_INFLATE_BATCH_MB", "1024")) << 20) * 3 // 4
+            room = (knobs.inflate_batch_mb() << 20) * 3 // 4
             batch = max(batch, min(64, max(1, room // max(1, largest + 32))))
         except OSError:
             pass
@@ -642,7 +644,7 @@ def feed_sharded(ds, bam_paths, owner, cov_min_mapq=1, batch=1, read_records=Non
         # ranks) and dealt once the owners are known; whatever follows streams through.  A small cohort is planned on all of its reads.
         names, lengths = plan
         local = np.zeros(len(names), dtype=np.uint64)
-        budget = int(os.environ.get("MSNV_PLAN_MB", "0")) << 20
+        budget = knobs.plan_bytes()
         if budget <= 0:
             try:
                 budget = os.sysconf("SC_PAGE_SIZE") * os.sysconf("SC_PHYS_PAGES") // 4 // max(1, _world)
@@ -704,8 +706,8 @@ def feed_sharded(ds, bam_paths, owner, cov_min_mapq=1, batch=1, read_records=Non
                     os.close(fd)
             except (OSError, AttributeError):
                 pass
-    host_decoder = read_records is not None or os.environ.get("MSNV_INFLATE", "device")[:1] == "h"
-    want_overlap = feed_overlap if feed_overlap is not None else os.environ.get("MSNV_FEED_OVERLAP", "1") != "0"      # (an argument of the run; the environment is the default)
+    host_decoder = read_records is not None or knobs.inflate_where("d") == "h"
+    want_overlap = feed_overlap if feed_overlap is not None else knobs.feed_overlap()      # (an argument of the run; the environment is the default)
     overlap = host_decoder and want_overlap and len(rounds) - k > 1
     # ... and on the DEVICE route (round 6): the upload, inflate, CRC check and dealing of round k + 1 run on a second context of the device
     # (core.Dataset.set_feed_context: its own stream, staging buffers and pinned words) from a thread of its own, under the exchange and the

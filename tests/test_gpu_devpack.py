@@ -105,6 +105,18 @@ def _same_dataset(names, lengths, seqs, samples, bed=None, params=None, many=Fal
         dh.close(); dd.close(); ch.close(); cd.close()
 
 
+def _deep_runs_split(syn, samples):
+    """Deep (sample, tile) runs that the device-packed build of the cohort dealt into groups, under the environment of the caller."""
+    with _env(MSNV_PACK="device"):
+        ctx = core.Context(0)
+        ds = core.Dataset(ctx, syn.names, syn.lengths, syn.seqs)
+        ds.add_samples_records(samples)
+        ds.finalize()
+        n = ds.pack_stats()["deep_runs_split"]
+        ds.close(); ctx.close()
+    return n
+
+
 def test_synthetic_cohort_same_columns():
     syn, samples = synth_case(n_species=3, contig_len=9000, n_samples=10, mean_cov=12.0, snv_density=0.02, error_rate=0.004, lowercase_ref=1, seed=21)
     info = _same_dataset(syn.names, syn.lengths, syn.seqs, samples)
@@ -137,6 +149,9 @@ def test_deep_runs_are_dealt_into_groups_and_short_reads_into_block_streams_on_t
     with _env(MSNV_SPLIT_AT="40", MSNV_GROUP_DEPTH="24"):                                                        # (many groups per run; some runs only look deep)
         syn2, samples2 = synth_case(n_species=2, contig_len=5000, n_samples=4, mean_cov=45.0, sigma_cov=0.6, snv_density=0.02, seed=29)
         _same_dataset(syn2.names, syn2.lengths, syn2.seqs, samples2)
+        split = _deep_runs_split(syn2, samples2)
+    with _env(MSNV_SPLIT_AT=None, MSNV_GROUP_DEPTH=None):                                                        # (the two knobs are read per dataset: more runs were dealt than without them)
+        assert split > _deep_runs_split(syn2, samples2)
     # short reads: dense block layout (odd and even lengths, indels cut the reads into pieces of every length)
     for read_len, seed, kw in ((36, 28, {}), (35, 30, dict(min_baseq=0)), (51, 31, dict(min_baseq=30)), (20, 32, {})):
         syn, samples = synth_case(n_species=2, contig_len=5000, n_samples=4, mean_cov=12.0, read_len=read_len, snv_density=0.02, frac_indel_reads=0.3, seed=seed)
@@ -151,6 +166,9 @@ def test_deep_runs_are_dealt_into_groups_and_short_reads_into_block_streams_on_t
     with _env(MSNV_SPLIT_AT="40", MSNV_GROUP_DEPTH="24"):                                                        # deep runs of short reads: dealt first, then laid out
         syn3, samples3 = synth_case(n_species=1, contig_len=4000, n_samples=3, mean_cov=60.0, read_len=40, sigma_cov=0.4, snv_density=0.02, seed=33)
         _same_dataset(syn3.names, syn3.lengths, syn3.seqs, samples3)
+        split = _deep_runs_split(syn3, samples3)
+    with _env(MSNV_SPLIT_AT=None, MSNV_GROUP_DEPTH=None):
+        assert split > _deep_runs_split(syn3, samples3)
     with _env(MSNV_LAYOUT="dense"):                                                                              # long reads forced into blocks: pieces of up to four blocks
         syn4, samples4 = synth_case(n_species=2, contig_len=6000, n_samples=3, mean_cov=15.0, snv_density=0.02, seed=34)
         _same_dataset(syn4.names, syn4.lengths, syn4.seqs, samples4)
