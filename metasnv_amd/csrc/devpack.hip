@@ -7,7 +7,9 @@
 // (M/=/X) segments, '=' -> reference base, and the -Q test of every base.  pack.cpp is the same stage on host threads (MSNV_PACK=host);
 // the two produce the same columns byte for byte (tests/test_gpu_devpack.py).
 //
-// Stages of one round of samples (round 6; DESIGN.md section 3 has the table with the kernels' times).  The QUICK route, the default:
+// Stages of one round of samples (round 6; DESIGN.md section 3 has the table with the kernels' times), the function of each beside it
+// (members of `Round`; devpack_add_round is their driver).  Round::stage (stage_streams) puts the streams in place.  The QUICK route, the
+// default -- Round::front_quick, then launch_emit and collect:
 //   msnv_scan_sub2        one LANE per sub-segment of a few kilobytes of a stream: guesses where the block_size chain enters its bytes, walks the
 //                         records that start there and MEASURES each as it goes (header, CIGAR geometry, the read filters of both tools,
 //                         qaCompute's statistics, the pieces / seq bytes / M intervals the record will emit) into a 32-byte slot
@@ -19,7 +21,11 @@
 //   msnv_emit_block       a workgroup per 256 records, their bytes staged in LDS: piece headers, qaCompute's intervals, bases (nibble swap,
 //                         '=' -> reference code), "quality below the -Q cutoff" flags, mismatch sampling of every 16th piece, in TILE order
 //                         (the pieces a read leaves in the next tile are placed by counting); msnv_emit_block_slow takes what it lists
-// The CAREFUL route (msnv_scan_sub / msnv_scan_segments, msnv_measure_reads, msnv_tables_from_measure, a wait between the stages) takes the
+//                         -- Round::launch_emit, both routes; Round::collect waits for the small results and can hand the round to the careful route
+//   the (sample, tile) pairs (Round::tile_pairs: by counting over the groups, or the rocPRIM sort) and the samples' host fields (Round::publish)
+// The CAREFUL route -- Round::front_careful: scan_records (scan_sub_walk: msnv_scan_sub; scan_segments: msnv_scan_segments), then per pass
+// measure (msnv_measure_reads), tables_and_depth (msnv_tables_from_measure, msnv_depth2), list_overlaps, sequential_edits (the host pre-pass:
+// host_prepass_samples), a wait between the stages; then Round::edit_qualities (msnv_ovl_groups, msnv_token_*) -- takes the
 // rounds the quick one leaves: paired reads, chains that break, the general tile-order sort -- and the three SEQUENTIAL edits of the host
 // stage, all kernels now: the overlapping-mate quality tweak (msnv_ovl_*, round 4), mpileup's depth cap (msnv_cap_reads) and snpCall's token
 // limit (msnv_token_clamp, msnv_token_cut; round 6).  Which samples' records can trigger one is decided on the device (a read starts above
@@ -2360,14 +2366,15 @@ void devpack_release(msnv_dataset &ds) {
     }
 }
 
-// Work buffers taken from a grow-only list in call order (a dataset's pool, or a caller's own list).
+// Work buffers taken from a grow-only list in call order (a dataset's pool, or a caller's own list).  A failed allocation sticks: every
+// later take() returns NULL and `rc` says why, so a batch of takes is followed by ONE `if (pool.rc) return pool.rc;`.
 struct BufPool {
     std::vector<std::pair<void *, uint64_t>> &slots;
     size_t next = 0; int rc = MSNV_OK;
     bool exact = knob::guard_alloc();
-    void *get(uint64_t bytes) {
-        if (next >= slots.size()) slots.emplace_back(nullptr, 0);
-        std::pair<void *, uint64_t> &b = slots[next++];
+    void *at(size_t i, uint64_t bytes) {                          // slot i, holding at least `bytes` (guarded allocations: exactly, and fresh)
+        if (rc) return nullptr;
+        std::pair<void *, uint64_t> &b = slots[i];
         bytes = std::max<uint64_t>(bytes, 16);
         if (b.second < bytes || (exact && b.second != bytes)) {
             if (b.first) dev_free(b.first);
@@ -2378,10 +2385,68 @@ struct BufPool {
         }
         return b.first;
     }
+    void *get(uint64_t bytes) {
+        if (next >= slots.size()) slots.emplace_back(nullptr, 0);
+        return at(next++, bytes);
+    }
+    template <typename T> T *take(uint64_t count) { return static_cast<T *>(get(count * sizeof(T))); }
+    // the slots taken since mark() are handed out again after rewind(mark): in the same order, to the same uses
+    size_t mark() const { return next; }
+    void rewind(size_t m) { next = m; }
 };
-#define DP_BUF(type, name, count)                                                      \
-    type *name = static_cast<type *>(pool.get((uint64_t)(count) * sizeof(type)));      \
-    if (!name) return pool.rc
+
+// rocPRIM calls with grow-only temporary storage: a buffer of its own (finalize), or after bind() ONE slot of a BufPool (the per-read stage:
+// the slot keeps its index, so a dataset's second round allocates nothing).  Every call is rocPRIM's two -- the size query, room(), the
+// launch; with `ask` it is the query alone (*ask = the larger of the two), for callers that grow the storage ONCE for several calls before
+// they queue anything: a grow frees, and a free waits for the device.
+struct Prim {
+    hipStream_t st; DevBuf own; void *buf = nullptr; size_t cap = 0;
+    BufPool *pool = nullptr; size_t slot = 0;
+    explicit Prim(hipStream_t s) : st(s) {}
+    int bind(BufPool &p, uint64_t bytes) {                        // the pool's next slot, `bytes` to begin with
+        pool = &p; slot = p.next;
+        buf = p.get(bytes);
+        if (!buf) return p.rc;
+        cap = (size_t)p.slots[slot].second;
+        return MSNV_OK;
+    }
+    int room(size_t need) {
+        if (need <= cap) return MSNV_OK;
+        if (pool) { buf = pool->at(slot, need); if (!buf) return pool->rc; cap = (size_t)pool->slots[slot].second; }
+        else { if (int rc = own.alloc(need)) return rc; buf = own.p; cap = need; }
+        return MSNV_OK;
+    }
+    template <typename In, typename Out, typename Op> int inclusive(In in, Out out, size_t n, Op op, size_t *ask = nullptr) {
+        size_t need = 0;
+        HIP_TRY(rocprim::inclusive_scan(nullptr, need, in, out, n, op, st));
+        if (ask) { *ask = std::max(*ask, need); return MSNV_OK; }
+        if (int rc = room(need)) return rc;
+        HIP_TRY(rocprim::inclusive_scan(buf, need, in, out, n, op, st));
+        return MSNV_OK;
+    }
+    template <typename In, typename Out, typename Init, typename Op> int exclusive(In in, Out out, Init init, size_t n, Op op, size_t *ask = nullptr) {
+        size_t need = 0;
+        HIP_TRY(rocprim::exclusive_scan(nullptr, need, in, out, init, n, op, st));
+        if (ask) { *ask = std::max(*ask, need); return MSNV_OK; }
+        if (int rc = room(need)) return rc;
+        HIP_TRY(rocprim::exclusive_scan(buf, need, in, out, init, n, op, st));
+        return MSNV_OK;
+    }
+    template <typename K, typename V> int sort_pairs(K *kin, K *kout, V *vin, V *vout, size_t n, unsigned end_bit, size_t *ask = nullptr) {
+        size_t need = 0;
+        HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, kin, kout, vin, vout, n, 0u, end_bit, st));
+        if (ask) { *ask = std::max(*ask, need); return MSNV_OK; }
+        if (int rc = room(need)) return rc;
+        HIP_TRY(rocprim::radix_sort_pairs(buf, need, kin, kout, vin, vout, n, 0u, end_bit, st));
+        return MSNV_OK;
+    }
+    // The forms most callers use.  Defined further down, not here: rocPRIM's kernels enter the code object in the order in which the compiler
+    // meets their first use, and these definitions stand where the per-read stage and finalize have always had theirs.
+    int scan32(const uint32_t *in, uint32_t *out, size_t n, bool inclusive_);
+    int sort64(unsigned long long *kin, unsigned long long *kout, uint32_t *vin, uint32_t *vout, size_t n, unsigned end_bit);
+    int scan64(const uint32_t *in, unsigned long long *out, size_t n);
+    int reserve_scan32(size_t n);           // room for scans of up to n words before the first launch
+};
 
 // Record streams (host or device memory) side by side in one device buffer and the offsets of their records: what the device pack
 // (devpack_add_round) and the device dealer (msnv_records_deal_device) start from.
@@ -2393,131 +2458,130 @@ struct ScanResult {
     uint32_t *d_recbase = nullptr; unsigned long long *d_send = nullptr, *d_recoff = nullptr; uint16_t *d_recsample = nullptr;
     double wall_upload_s = 0, ms_scan = 0; uint64_t n_redone = 0;
 };
-// stage_only: the streams are put in place and nothing is scanned; a later call with the same ScanResult (raw set) scans what is there.
-static int scan_streams(hipStream_t st, const int device, BufPool &pool, const uint8_t *const *streams, const uint64_t *n_bytes, const size_t S, const bool on_device, const int NC_, ScanResult &R,
-                        const uint8_t *in_place_base = nullptr, uint64_t in_place_capacity = 0, bool stage_only = false) {
-    const size_t NC = (size_t)NC_;
-    Timer tm(st);
-    // ---- the round's streams side by side in one buffer: every stream starts on 16 bytes, readable bytes behind the last
-    std::vector<unsigned long long> &s_beg = R.s_beg, &s_end = R.s_end;
-    uint64_t raw_bytes = R.raw_bytes;
-    uint8_t *raw = R.raw;
-    if (!R.raw) {
-    s_beg.assign(S, 0); s_end.assign(S, 0);
+// The round's streams side by side in one buffer: every stream starts on 16 bytes, readable bytes behind the last.  Nothing is scanned.
+static int stage_streams(hipStream_t st, const int device, BufPool &pool, const uint8_t *const *streams, const uint64_t *n_bytes, const size_t S, const bool on_device, ScanResult &R,
+                         const uint8_t *in_place_base = nullptr) {
+    R.s_beg.assign(S, 0); R.s_end.assign(S, 0);
     if (in_place_base) {
         // the streams where they lie: offsets into the caller's buffer (api.cpp has checked order, alignment of the base and the bytes behind the last)
-        for (size_t s = 0; s < S; ++s) { s_beg[s] = (unsigned long long)(streams[s] - in_place_base); s_end[s] = s_beg[s] + n_bytes[s]; }
-        raw = const_cast<uint8_t *>(in_place_base);
-        for (size_t s = 0; s < S; ++s) raw_bytes += n_bytes[s];     // (accounting: the records' bytes)
+        for (size_t s = 0; s < S; ++s) { R.s_beg[s] = (unsigned long long)(streams[s] - in_place_base); R.s_end[s] = R.s_beg[s] + n_bytes[s]; }
+        R.raw = const_cast<uint8_t *>(in_place_base);
+        for (size_t s = 0; s < S; ++s) R.raw_bytes += n_bytes[s];     // (accounting: the records' bytes)
+        return MSNV_OK;
+    }
+    for (size_t s = 0; s < S; ++s) { R.s_beg[s] = R.raw_bytes; R.s_end[s] = R.raw_bytes + n_bytes[s]; R.raw_bytes += (n_bytes[s] + 15 + 16) & ~15ull; }
+    uint8_t *const raw = pool.take<uint8_t>(R.raw_bytes + 256);
+    if (pool.rc) return pool.rc;
+    const double t0 = now_s();
+    if (on_device) {
+        for (size_t s = 0; s < S; ++s) if (n_bytes[s]) HIP_TRY(hipMemcpyAsync(raw + R.s_beg[s], streams[s], n_bytes[s], hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
     } else {
-    for (size_t s = 0; s < S; ++s) { s_beg[s] = raw_bytes; s_end[s] = raw_bytes + n_bytes[s]; raw_bytes += (n_bytes[s] + 15 + 16) & ~15ull; }
-    DP_BUF(uint8_t, raw_, raw_bytes + 256);
-    raw = raw_;
-    {
-        const double t0 = now_s();
-        if (on_device) {
-            for (size_t s = 0; s < S; ++s) if (n_bytes[s]) HIP_TRY(hipMemcpyAsync(raw + s_beg[s], streams[s], n_bytes[s], hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        } else {
-            // pageable host memory: a few copies in flight keep the link busy (the runtime stages them)
-            std::atomic<size_t> next{0}; std::atomic<int> bad{0};
-            
-            auto w = [&]() {
-                (void)hipSetDevice(device);
-                for (;;) { const size_t s = next.fetch_add(1); if (s >= S) break; if (n_bytes[s] && hipMemcpy(raw + s_beg[s], streams[s], n_bytes[s], hipMemcpyHostToDevice) != hipSuccess) bad.store(1); }
-            };
-            std::vector<std::thread> th;
-            for (size_t k = 0; k < std::min<size_t>(S, 6); ++k) th.emplace_back(w);
-            for (auto &x : th) x.join();
-            if (bad.load()) return fail(MSNV_EHIP, "upload of the record streams failed: %s", hipGetErrorString(hipGetLastError()));
-        }
-        R.wall_upload_s += now_s() - t0;
+        // pageable host memory: a few copies in flight keep the link busy (the runtime stages them)
+        std::atomic<size_t> next{0}; std::atomic<int> bad{0};
+        auto w = [&]() {
+            (void)hipSetDevice(device);
+            for (;;) { const size_t s = next.fetch_add(1); if (s >= S) break; if (n_bytes[s] && hipMemcpy(raw + R.s_beg[s], streams[s], n_bytes[s], hipMemcpyHostToDevice) != hipSuccess) bad.store(1); }
+        };
+        std::vector<std::thread> th;
+        for (size_t k = 0; k < std::min<size_t>(S, 6); ++k) th.emplace_back(w);
+        for (auto &x : th) x.join();
+        if (bad.load()) return fail(MSNV_EHIP, "upload of the record streams failed: %s", hipGetErrorString(hipGetLastError()));
     }
-    }
-    R.raw = raw; R.raw_bytes = raw_bytes;
-    }
-    if (stage_only) return MSNV_OK;
+    R.wall_upload_s += now_s() - t0;
+    R.raw = raw;
+    return MSNV_OK;
+}
 
-    // ---- record boundaries, the quick way: sub-segments walked side by side, seams checked on the device (MSNV_SCAN=segments: the careful kernel only)
-    const bool quick = !knob::scan_segments();
-    if (quick && S > 0) {
-        const uint32_t sub_bytes = knob::scan_sub_bytes(knob::SCAN_SUB_STREAMS);   // (per call: tests shrink it)
-        const uint32_t cap = sub_bytes / 36u + 2u;
-        std::vector<SubStream> ss(S);
-        uint64_t n_sub64 = 0;
-        for (size_t s = 0; s < S; ++s) { ss[s] = SubStream{s_beg[s], s_end[s], (uint32_t)n_sub64, 0u}; n_sub64 += std::max<uint64_t>(1, (n_bytes[s] + sub_bytes - 1) / sub_bytes); }
-        if (n_sub64 < 0x7ffffff0ull) {
-            const uint32_t n_sub = (uint32_t)n_sub64;
-            const size_t pool_from = pool.next;
-            DP_BUF(SubStream, d_ss, S);
-            DP_BUF(unsigned long long, d_first, (uint64_t)n_sub + 1);
-            DP_BUF(unsigned long long, d_stop, (uint64_t)n_sub + 1);
-            DP_BUF(unsigned long long, d_stopmax, (uint64_t)n_sub + 1);
-            DP_BUF(uint32_t, d_cnt, (uint64_t)n_sub + 1);
-            DP_BUF(uint32_t, d_base, (uint64_t)n_sub + 1);
-            DP_BUF(uint16_t, d_delta, (uint64_t)n_sub * cap + 8);
-            DP_BUF(uint32_t, d_fl, 4);
-            DP_BUF(uint32_t, d_recbase, S + 1);
-            DP_BUF(unsigned long long, d_send, S);
-            DP_BUF(uint8_t, d_tmp, 1u << 20);
-            size_t tmp_cap = (size_t)pool.slots[pool.next - 1].second;
-            tm.start();
-            HIP_TRY(hipMemcpyAsync(d_ss, ss.data(), S * sizeof(SubStream), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_send, s_end.data(), S * 8, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemsetAsync(d_fl, 0, 16, st));
-            hipLaunchKernelGGL(msnv_scan_sub, grid_for(n_sub, 256), dim3(256), 0, st, raw, d_ss, (uint32_t)S, n_sub, sub_bytes, cap, (int)NC, d_first, d_stop, d_cnt, d_delta, d_fl);
-            HIP_TRY(hipGetLastError());
-            size_t need = 0, need2 = 0;
-            HIP_TRY(rocprim::inclusive_scan(nullptr, need, d_stop, d_stopmax, (size_t)n_sub, U64Max(), st));
-            HIP_TRY(rocprim::exclusive_scan(nullptr, need2, d_cnt, d_base, 0u, (size_t)n_sub + 1, rocprim::plus<uint32_t>(), st));
-            need = std::max(need, need2);
-            if (need > tmp_cap) { pool.next -= 1; d_tmp = static_cast<uint8_t *>(pool.get(need)); if (!d_tmp) return pool.rc; }
-            uint32_t fl_tot[2] = {0, 0};
-            DP_BUF(uint32_t, d_firstbad, S);
-            HIP_TRY(hipMemsetAsync(d_firstbad, 0xff, S * 4, st));
-            for (int pass = 0;; ++pass) {
-                // seams: checked, every stream's first sub-segment that guessed wrong walked again, until none is left (usually the first look)
-                HIP_TRY(rocprim::inclusive_scan(d_tmp, need, d_stop, d_stopmax, (size_t)n_sub, U64Max(), st));
-                hipLaunchKernelGGL(msnv_scan_check, grid_for((uint64_t)n_sub + 1, 256), dim3(256), 0, st, d_ss, (uint32_t)S, n_sub, sub_bytes, d_first, d_stopmax, d_cnt, d_firstbad);
-                hipLaunchKernelGGL(msnv_scan_fix, grid_for(S, 64), dim3(64), 0, st, raw, d_ss, (uint32_t)S, sub_bytes, cap, d_first, d_stop, d_stopmax, d_cnt, d_delta, d_firstbad, d_fl);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipMemcpyAsync(&fl_tot[0], d_fl, 4, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                if (!(fl_tot[0] & 2u) || (fl_tot[0] & 5u) || pass >= 4096) break;
-                R.n_redone += 1;                                  // (counted: a repair pass)
-                HIP_TRY(hipMemsetAsync(d_fl, 0, 4, st));
-            }
-            if (!fl_tot[0]) {
-                HIP_TRY(rocprim::exclusive_scan(d_tmp, need, d_cnt, d_base, 0u, (size_t)n_sub + 1, rocprim::plus<uint32_t>(), st));
-                HIP_TRY(hipMemcpyAsync(&fl_tot[1], d_base + n_sub, 4, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-            }
-            if (!fl_tot[0]) {
-                // (a 32-bit count that wrapped would show as a total below the sub-segments' sum; 2^32 records need 150 GB of stream in one round -- refused by size)
-                if (raw_bytes / 36 > 0xfffffff0ull) return fail(MSNV_EDOMAIN, "more than 2^32 records in one round of the device pack");
-                const uint32_t NR = fl_tot[1];
-                const uint64_t NRa = (uint64_t)NR + 1;
-                DP_BUF(unsigned long long, d_recoff, NRa);
-                DP_BUF(uint16_t, d_recsample, NRa);
-                hipLaunchKernelGGL(msnv_scan_write, grid_for(n_sub, 256), dim3(256), 0, st, d_ss, (uint32_t)S, n_sub, sub_bytes, cap, d_cnt, d_base, d_delta, d_recoff, d_recsample, d_recbase);
-                HIP_TRY(hipGetLastError());
-                std::vector<uint32_t> &rec_base = R.rec_base; rec_base.assign(S + 1, 0);
-                HIP_TRY(hipMemcpyAsync(d_recbase + S, &NR, 4, hipMemcpyHostToDevice, st));
-                HIP_TRY(hipMemcpyAsync(rec_base.data(), d_recbase, S * 4, hipMemcpyDeviceToHost, st));
-                R.ms_scan += tm.stop();
-                rec_base[S] = NR;
-                R.n_rec.assign(S, 0); R.bad_off.assign(S, ~0ull);
-                for (size_t s = 0; s < S; ++s) R.n_rec[s] = rec_base[s + 1] - rec_base[s];
-                R.NR = NR;
-                R.d_recbase = d_recbase; R.d_send = d_send; R.d_recoff = d_recoff; R.d_recsample = d_recsample;
-                return MSNV_OK;
-            }
-            R.ms_scan += tm.stop();
-            R.n_redone += 1;                                      // (counted: the round went through the careful kernel)
-            pool.next = pool_from;
-        }
+// Record boundaries of staged streams, the quick way: sub-segments walked side by side, seams checked on the device.  `found` says whether
+// the walk stands; a chain that breaks or a sub-segment with more records than its slots leaves the round to scan_segments (counted).
+static int scan_sub_walk(hipStream_t st, BufPool &pool, const uint64_t *n_bytes, const size_t S, const size_t NC, ScanResult &R, bool &found) {
+    found = false;
+    const uint32_t sub_bytes = knob::scan_sub_bytes(knob::SCAN_SUB_STREAMS);   // (per call: tests shrink it)
+    const uint32_t cap = sub_bytes / 36u + 2u;
+    std::vector<SubStream> ss(S);
+    uint64_t n_sub64 = 0;
+    for (size_t s = 0; s < S; ++s) { ss[s] = SubStream{R.s_beg[s], R.s_end[s], (uint32_t)n_sub64, 0u}; n_sub64 += std::max<uint64_t>(1, (n_bytes[s] + sub_bytes - 1) / sub_bytes); }
+    if (n_sub64 >= 0x7ffffff0ull) return MSNV_OK;
+    const uint32_t n_sub = (uint32_t)n_sub64;
+    uint8_t *const raw = R.raw;
+    Timer tm(st);
+    Prim prim(st);
+    const size_t pool_from = pool.mark();
+    auto *d_ss = pool.take<SubStream>(S);
+    auto *d_first = pool.take<unsigned long long>((uint64_t)n_sub + 1);
+    auto *d_stop = pool.take<unsigned long long>((uint64_t)n_sub + 1);
+    auto *d_stopmax = pool.take<unsigned long long>((uint64_t)n_sub + 1);
+    auto *d_cnt = pool.take<uint32_t>((uint64_t)n_sub + 1);
+    auto *d_base = pool.take<uint32_t>((uint64_t)n_sub + 1);
+    auto *d_delta = pool.take<uint16_t>((uint64_t)n_sub * cap + 8);
+    auto *d_fl = pool.take<uint32_t>(4);
+    auto *d_recbase = pool.take<uint32_t>(S + 1);
+    auto *d_send = pool.take<unsigned long long>(S);
+    if (pool.rc) return pool.rc;
+    if (int rc = prim.bind(pool, 1u << 20)) return rc;
+    tm.start();
+    HIP_TRY(hipMemcpyAsync(d_ss, ss.data(), S * sizeof(SubStream), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_send, R.s_end.data(), S * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_fl, 0, 16, st));
+    hipLaunchKernelGGL(msnv_scan_sub, grid_for(n_sub, 256), dim3(256), 0, st, raw, d_ss, (uint32_t)S, n_sub, sub_bytes, cap, (int)NC, d_first, d_stop, d_cnt, d_delta, d_fl);
+    HIP_TRY(hipGetLastError());
+    size_t need = 0;                                              // both scans' storage before either is queued
+    if (int rc = prim.inclusive(d_stop, d_stopmax, (size_t)n_sub, U64Max(), &need)) return rc;
+    if (int rc = prim.exclusive(d_cnt, d_base, 0u, (size_t)n_sub + 1, rocprim::plus<uint32_t>(), &need)) return rc;
+    if (int rc = prim.room(need)) return rc;
+    uint32_t fl = 0;
+    auto *d_firstbad = pool.take<uint32_t>(S);
+    if (pool.rc) return pool.rc;
+    HIP_TRY(hipMemsetAsync(d_firstbad, 0xff, S * 4, st));
+    // (the seam loop is written twice, here and in Round::front_quick: the two differ in the fix kernel and in what is queued behind it before
+    // the one wait, and a shared form would need both as callbacks whose signatures are longer than the loop)
+    for (int pass = 0;; ++pass) {
+        // seams: checked, every stream's first sub-segment that guessed wrong walked again, until none is left (usually the first look)
+        if (int rc = prim.inclusive(d_stop, d_stopmax, (size_t)n_sub, U64Max())) return rc;
+        hipLaunchKernelGGL(msnv_scan_check, grid_for((uint64_t)n_sub + 1, 256), dim3(256), 0, st, d_ss, (uint32_t)S, n_sub, sub_bytes, d_first, d_stopmax, d_cnt, d_firstbad);
+        hipLaunchKernelGGL(msnv_scan_fix, grid_for(S, 64), dim3(64), 0, st, raw, d_ss, (uint32_t)S, sub_bytes, cap, d_first, d_stop, d_stopmax, d_cnt, d_delta, d_firstbad, d_fl);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&fl, d_fl, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (!(fl & 2u) || (fl & 5u) || pass >= 4096) break;
+        R.n_redone += 1;                                  // (counted: a repair pass)
+        HIP_TRY(hipMemsetAsync(d_fl, 0, 4, st));
     }
-    // ---- record boundaries: segments, guessed entry points, seams checked here
+    if (fl) {
+        R.ms_scan += tm.stop();
+        R.n_redone += 1;                                          // (counted: the round goes through the careful kernel)
+        pool.rewind(pool_from);
+        return MSNV_OK;
+    }
+    if (int rc = prim.exclusive(d_cnt, d_base, 0u, (size_t)n_sub + 1, rocprim::plus<uint32_t>())) return rc;
+    HIP_TRY(hipMemcpyAsync(&R.NR, d_base + n_sub, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    // (a 32-bit count that wrapped would show as a total below the sub-segments' sum; 2^32 records need 150 GB of stream in one round -- refused by size)
+    if (R.raw_bytes / 36 > 0xfffffff0ull) return fail(MSNV_EDOMAIN, "more than 2^32 records in one round of the device pack");
+    const uint32_t NR = R.NR;
+    auto *d_recoff = pool.take<unsigned long long>((uint64_t)NR + 1);
+    auto *d_recsample = pool.take<uint16_t>((uint64_t)NR + 1);
+    if (pool.rc) return pool.rc;
+    hipLaunchKernelGGL(msnv_scan_write, grid_for(n_sub, 256), dim3(256), 0, st, d_ss, (uint32_t)S, n_sub, sub_bytes, cap, d_cnt, d_base, d_delta, d_recoff, d_recsample, d_recbase);
+    HIP_TRY(hipGetLastError());
+    R.rec_base.assign(S + 1, 0);
+    HIP_TRY(hipMemcpyAsync(d_recbase + S, &R.NR, 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(R.rec_base.data(), d_recbase, S * 4, hipMemcpyDeviceToHost, st));
+    R.ms_scan += tm.stop();                                       // (waits: both copies are done)
+    R.rec_base[S] = NR;
+    R.n_rec.assign(S, 0); R.bad_off.assign(S, ~0ull);
+    for (size_t s = 0; s < S; ++s) R.n_rec[s] = R.rec_base[s + 1] - R.rec_base[s];
+    R.d_recbase = d_recbase; R.d_send = d_send; R.d_recoff = d_recoff; R.d_recsample = d_recsample;
+    found = true;
+    return MSNV_OK;
+}
+
+// Record boundaries of staged streams, the careful way: segments, guessed entry points, seams checked on the host; words malformed input.
+static int scan_segments(hipStream_t st, BufPool &pool, const size_t S, const size_t NC, ScanResult &R) {
+    const std::vector<unsigned long long> &s_beg = R.s_beg, &s_end = R.s_end;
+    uint8_t *const raw = R.raw;
+    Timer tm(st);
     const uint64_t seg_bytes = knob::scan_seg_bytes();   // (per call: tests shrink it)
     std::vector<ScanSeg> segs;
     std::vector<uint32_t> seg_lo(S + 1, 0);                       // per stream: its first segment
@@ -2533,9 +2597,10 @@ static int scan_streams(hipStream_t st, const int device, BufPool &pool, const u
     seg_lo[S] = (uint32_t)segs.size();
     const size_t NSEG = segs.size();
     if (NSEG > 0x7fffffffull) return fail(MSNV_EDOMAIN, "too many scan segments in one round");
-    DP_BUF(ScanSeg, d_segs, NSEG + 1);
-    DP_BUF(ScanOut, d_outs, NSEG + 1);
-    DP_BUF(unsigned long long, d_tmpoff, cap_total + 64);
+    auto *d_segs = pool.take<ScanSeg>(NSEG + 1);
+    auto *d_outs = pool.take<ScanOut>(NSEG + 1);
+    auto *d_tmpoff = pool.take<unsigned long long>(cap_total + 64);
+    if (pool.rc) return pool.rc;
     std::vector<ScanOut> outs(NSEG);
     std::vector<uint32_t> &n_rec = R.n_rec; n_rec.assign(S, 0); std::vector<uint32_t> acc_cnt(NSEG, 0);
     std::vector<unsigned long long> &bad_off = R.bad_off; bad_off.assign(S, ~0ull);
@@ -2550,6 +2615,7 @@ static int scan_streams(hipStream_t st, const int device, BufPool &pool, const u
         std::vector<unsigned long long> cur(S);
         std::vector<uint32_t> at(S);                             // next segment to look at, per stream
         for (size_t s = 0; s < S; ++s) { cur[s] = s_beg[s]; at[s] = seg_lo[s]; }
+        const size_t repair_lists = pool.mark();                  // (the two lists below are reused by every repair round)
         for (int round_no = 0;; ++round_no) {
             std::vector<uint32_t> redo;
             for (size_t s = 0; s < S; ++s) {
@@ -2568,8 +2634,9 @@ static int scan_streams(hipStream_t st, const int device, BufPool &pool, const u
             // walk the segments that guessed wrong again, from the true entry point (one launch over just those)
             std::vector<ScanSeg> again;
             for (uint32_t k : redo) again.push_back(segs[k]);
-            DP_BUF(ScanSeg, d_again, again.size());
-            DP_BUF(ScanOut, d_aout, again.size());
+            auto *d_again = pool.take<ScanSeg>(again.size());
+            auto *d_aout = pool.take<ScanOut>(again.size());
+            if (pool.rc) return pool.rc;
             std::vector<ScanOut> aout(again.size());
             HIP_TRY(hipMemcpyAsync(d_again, again.data(), again.size() * sizeof(ScanSeg), hipMemcpyHostToDevice, st));
             hipLaunchKernelGGL(msnv_scan_segments, dim3((unsigned)again.size()), dim3(64), 0, st, raw, d_again, (uint32_t)again.size(), (int)NC, d_tmpoff, d_aout);
@@ -2578,7 +2645,7 @@ static int scan_streams(hipStream_t st, const int device, BufPool &pool, const u
             HIP_TRY(hipStreamSynchronize(st));
             for (size_t j = 0; j < redo.size(); ++j) outs[redo[j]] = aout[j];
             R.n_redone += redo.size();
-            pool.next -= 2;                                        // (the two lists are reused by the next repair round)
+            pool.rewind(repair_lists);
         }
     }
     R.ms_scan += tm.stop();                                       // (the lists below are allocated outside the timed region)
@@ -2597,28 +2664,34 @@ static int scan_streams(hipStream_t st, const int device, BufPool &pool, const u
         }
         rec_base[S] = (uint32_t)total;
     }
-    const uint32_t NR = rec_base[S];
-    const uint64_t NRa = (uint64_t)NR + 1;
-    DP_BUF(uint32_t, d_recbase, S + 1);
-    DP_BUF(unsigned long long, d_send, S);
-    DP_BUF(unsigned long long, d_recoff, NRa);
-    DP_BUF(uint16_t, d_recsample, NRa);
-    DP_BUF(CompactSeg, d_csegs, csegs.size() + 1);
+    R.NR = rec_base[S];
+    const uint64_t NRa = (uint64_t)R.NR + 1;
+    R.d_recbase = pool.take<uint32_t>(S + 1);
+    R.d_send = pool.take<unsigned long long>(S);
+    R.d_recoff = pool.take<unsigned long long>(NRa);
+    R.d_recsample = pool.take<uint16_t>(NRa);
+    auto *d_csegs = pool.take<CompactSeg>(csegs.size() + 1);
+    if (pool.rc) return pool.rc;
     tm.start();
-    HIP_TRY(hipMemcpyAsync(d_recbase, rec_base.data(), (S + 1) * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_send, s_end.data(), S * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(R.d_recbase, rec_base.data(), (S + 1) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(R.d_send, s_end.data(), S * 8, hipMemcpyHostToDevice, st));
     if (!csegs.empty()) {
         HIP_TRY(hipMemcpyAsync(d_csegs, csegs.data(), csegs.size() * sizeof(CompactSeg), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(msnv_compact_offsets, dim3((unsigned)csegs.size()), dim3(256), 0, st, d_tmpoff, d_csegs, d_recoff, d_recsample);
+        hipLaunchKernelGGL(msnv_compact_offsets, dim3((unsigned)csegs.size()), dim3(256), 0, st, d_tmpoff, d_csegs, R.d_recoff, R.d_recsample);
         HIP_TRY(hipGetLastError());
     }
-    R.ms_scan += tm.stop();
-
-    R.NR = NR;
-    R.d_recbase = d_recbase; R.d_send = d_send; R.d_recoff = d_recoff; R.d_recsample = d_recsample;
+    R.ms_scan += tm.stop();                                       // (waits: csegs' bytes are up)
     return MSNV_OK;
 }
-#undef DP_BUF
+// Where the records of staged streams begin: the sub-segment walk, and the segment scan for what it leaves (and under MSNV_SCAN=segments).
+static int scan_records(hipStream_t st, BufPool &pool, const uint64_t *n_bytes, const size_t S, const size_t NC, ScanResult &R) {
+    if (!knob::scan_segments() && S > 0) {
+        bool found = false;
+        if (int rc = scan_sub_walk(st, pool, n_bytes, S, NC, R, found)) return rc;
+        if (found) return MSNV_OK;
+    }
+    return scan_segments(st, pool, S, NC, R);
+}
 
 
 // ------------------------------------------------------------------------------------------ records dealt to their owners, on the device
@@ -2749,11 +2822,9 @@ int records_deal_device(msnv_ctx *ctx, const uint8_t *const *streams, const uint
     std::vector<std::pair<void *, uint64_t>> slots;                // this call's work buffers
     struct FreeSlots { std::vector<std::pair<void *, uint64_t>> &v; ~FreeSlots() { for (auto &b : v) if (b.first) dev_free(b.first); } } free_slots{slots};
     BufPool pool{slots};
-#define DP_BUF(type, name, count)                                                      \
-    type *name = static_cast<type *>(pool.get((uint64_t)(count) * sizeof(type)));      \
-    if (!name) return pool.rc
     ScanResult SR;
-    if (int rc = scan_streams(st, ctx->device, pool, streams, n_bytes, S, on_device, n_contigs, SR)) return rc;
+    if (int rc = stage_streams(st, ctx->device, pool, streams, n_bytes, S, on_device, SR)) return rc;
+    if (int rc = scan_records(st, pool, n_bytes, S, (size_t)n_contigs, SR)) return rc;
     for (size_t s = 0; s < S; ++s) if (SR.bad_off[s] != ~0ull) return fail(MSNV_EFORMAT, "malformed BAM record at byte %llu of stream %zu", (unsigned long long)SR.bad_off[s], s);
     const uint32_t NR = SR.NR;
     const bool measure_only = out == nullptr;                      // statistics and aligned bases only (the split planner's pass over held streams)
@@ -2763,17 +2834,18 @@ int records_deal_device(msnv_ctx *ctx, const uint8_t *const *streams, const uint
     for (size_t i = 0; i < S * (size_t)n_parts; ++i) part_bytes[i] = 0;
     for (size_t s = 0; s < S; ++s) stats[s] = msnv_sample_stats{};
     if (!NR) return MSNV_OK;
-    DP_BUF(int32_t, d_owner, std::max(1, n_contigs));
-    DP_BUF(uint32_t, d_key, (uint64_t)NR + 1);
-    DP_BUF(uint32_t, d_size, (uint64_t)NR + 1);
-    DP_BUF(uint32_t, d_idx, (uint64_t)NR + 1);
-    DP_BUF(uint32_t, d_skey, (uint64_t)NR + 1);
-    DP_BUF(uint32_t, d_order, (uint64_t)NR + 1);
-    DP_BUF(uint32_t, d_ssize, (uint64_t)NR + 1);
-    DP_BUF(unsigned long long, d_pos, (uint64_t)NR + 1);
-    DP_BUF(DealAcc, d_acc, S * DEAL_COPIES);
-    DP_BUF(unsigned long long, d_pb, (uint64_t)DEAL_COPIES * S * (uint64_t)n_parts + 1);
-    DP_BUF(unsigned long long, d_cb, std::max(1, n_contigs));
+    auto *d_owner = pool.take<int32_t>(std::max(1, n_contigs));
+    auto *d_key = pool.take<uint32_t>((uint64_t)NR + 1);
+    auto *d_size = pool.take<uint32_t>((uint64_t)NR + 1);
+    auto *d_idx = pool.take<uint32_t>((uint64_t)NR + 1);
+    auto *d_skey = pool.take<uint32_t>((uint64_t)NR + 1);
+    auto *d_order = pool.take<uint32_t>((uint64_t)NR + 1);
+    auto *d_ssize = pool.take<uint32_t>((uint64_t)NR + 1);
+    auto *d_pos = pool.take<unsigned long long>((uint64_t)NR + 1);
+    auto *d_acc = pool.take<DealAcc>(S * DEAL_COPIES);
+    auto *d_pb = pool.take<unsigned long long>((uint64_t)DEAL_COPIES * S * (uint64_t)n_parts + 1);
+    auto *d_cb = pool.take<unsigned long long>(std::max(1, n_contigs));
+    if (pool.rc) return pool.rc;
     // (per-(stream, part) byte counts: copy c of stream s, part k at ((c * S) + s) * n_parts + k -- indexed below with the same formula)
     const uint64_t pb_words = (uint64_t)DEAL_COPIES * S * (uint64_t)n_parts;
     HIP_TRY(hipMemcpyAsync(d_owner, owner, (size_t)n_contigs * 4, hipMemcpyHostToDevice, st));
@@ -2786,16 +2858,15 @@ int records_deal_device(msnv_ctx *ctx, const uint8_t *const *streams, const uint
     if (!measure_only) {   // stable sort by owner (8 bits), then the places: exclusive scan of the sizes in that order
         hipLaunchKernelGGL(msnv_deal_iota, grid_for(NR, 256), dim3(256), 0, st, d_idx, NR);
         HIP_TRY(hipGetLastError());
-        size_t tmp = 0;
-        HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, d_key, d_skey, d_idx, d_order, (size_t)NR, 0u, 8u, st));
-        DP_BUF(uint8_t, d_tmp, tmp + 16);
-        HIP_TRY(rocprim::radix_sort_pairs(d_tmp, tmp, d_key, d_skey, d_idx, d_order, (size_t)NR, 0u, 8u, st));
+        Prim prim(st);
+        size_t tmp_need = 0;                                       // the sort's and the scan's storage before either is queued
+        if (int rc = prim.sort_pairs(d_key, d_skey, d_idx, d_order, (size_t)NR, 8u, &tmp_need)) return rc;
+        if (int rc = prim.exclusive(d_ssize, d_pos, 0ull, (size_t)NR, rocprim::plus<unsigned long long>(), &tmp_need)) return rc;
+        if (int rc = prim.bind(pool, tmp_need + 16)) return rc;
+        if (int rc = prim.sort_pairs(d_key, d_skey, d_idx, d_order, (size_t)NR, 8u)) return rc;
         hipLaunchKernelGGL(msnv_deal_sizes, grid_for(NR, 256), dim3(256), 0, st, d_order, d_size, NR, d_ssize);
         HIP_TRY(hipGetLastError());
-        size_t tmp2 = 0;
-        HIP_TRY(rocprim::exclusive_scan(nullptr, tmp2, d_ssize, d_pos, 0ull, (size_t)NR, rocprim::plus<unsigned long long>(), st));
-        DP_BUF(uint8_t, d_tmp2, tmp2 + 16);
-        HIP_TRY(rocprim::exclusive_scan(d_tmp2, tmp2, d_ssize, d_pos, 0ull, (size_t)NR, rocprim::plus<unsigned long long>(), st));
+        if (int rc = prim.exclusive(d_ssize, d_pos, 0ull, (size_t)NR, rocprim::plus<unsigned long long>())) return rc;
     }
     if (!measure_only) hipLaunchKernelGGL(msnv_deal_copy, grid_for((uint64_t)NR * 16, 256), dim3(256), 0, st, SR.raw, SR.d_recoff, SR.d_recsample, d_order, d_skey, d_ssize, d_pos, NR, (uint32_t)n_parts, (uint32_t)S,
                        (unsigned long long)gap, out, d_pb);
@@ -2823,555 +2894,563 @@ int records_deal_device(msnv_ctx *ctx, const uint8_t *const *streams, const uint
         part_bytes[s * (size_t)n_parts + (size_t)k] += pb[((size_t)c * S + s) * (size_t)n_parts + (size_t)k];
     if (contig_bases) for (int c = 0; c < n_contigs; ++c) contig_bases[c] += cb[(size_t)c];
     return MSNV_OK;
-#undef DP_BUF
 }
 
-int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *streams, const uint64_t *n_bytes, int n, bool on_device, const uint8_t *in_place_base, uint64_t in_place_capacity) {
-    if (n <= 0) return MSNV_OK;
-    if (n > 2048) return fail(MSNV_EINVAL, "internal: a device-pack round holds at most 2048 samples");
-    if (!ds.ctx) return fail(MSNV_ENODEV, "the device pack needs a device context");
-    if (int rc = dev_set_device(ds.ctx->device)) return rc;
-    hipStream_t st = (hipStream_t)ds.ctx->stream;
-    fin_trace_reset();
-    if (int rc = devpack_sync_pending(ds)) return rc;              // (the round before may still be writing: its work buffers are this round's)
-    DevPackTables &T = ds.dp;
-    fin_trace("  pack: enter");
-    if (int rc = build_contigs(ds)) return rc;
-    fin_trace("  pack: contigs");
-    // the packed FASTA of the selected contigs is built by the first round, on a thread of its own BESIDE the round's first kernels, which
-    // do not read it (round 5: 0.4 ms in front of them); the emit kernels do
-    struct TablesJob {
-        std::thread th; int rc = MSNV_OK; std::string msg;
-        int join() { if (th.joinable()) th.join(); if (rc) return fail(rc, "%s", msg.c_str()); return MSNV_OK; }
-        ~TablesJob() { if (th.joinable()) th.join(); }
-    } tables;
-    if (!T.ready) {
-        const int device = ds.ctx->device;
-        tables.th = std::thread([&ds, &tables, device]() {
-            (void)hipSetDevice(device);
-            try { tables.rc = build_tables(ds); } catch (const std::exception &e) { tables.rc = fail_quiet(MSNV_ENOMEM, "device pack tables: %s", e.what()); }
-            if (tables.rc) tables.msg = msnv_last_error();
-        });
-    }
-    const size_t S = (size_t)n, NC = ds.names.size();
-    const msnv_params &MP = ds.params;
-    DpParams P{};
-    P.flag_filter = MP.flag_filter; P.min_mapq = MP.min_mapq; P.count_orphans = MP.count_orphans; P.cov_min_mapq = MP.cov_min_mapq;
-    P.max_depth = MP.max_depth; P.token_limit = MP.token_limit; P.ignore_overlaps = MP.ignore_overlaps;
-    P.c_eff = std::min(std::max(MP.min_baseq, -127), 127); P.all_low = MP.min_baseq > 127;
-    P.n_contigs = (int)NC; P.has_bed = ds.has_bed ? 1 : 0;
-    Timer tm(st);
+int Prim::scan32(const uint32_t *in, uint32_t *out, size_t n, bool inclusive_) {
+    return inclusive_ ? inclusive(in, out, n, rocprim::plus<uint32_t>()) : exclusive(in, out, 0u, n, rocprim::plus<uint32_t>());
+}
+int Prim::sort64(unsigned long long *kin, unsigned long long *kout, uint32_t *vin, uint32_t *vout, size_t n, unsigned end_bit) { return sort_pairs(kin, kout, vin, vout, n, end_bit); }
+
+// ------------------------------------------------------------------------------------------ one round of samples through the per-read stage
+namespace {
+constexpr int TO_CAREFUL = -1;      // a stage's verdict beside MSNV_OK and the error codes: the careful route has to take this round
+
+// the packed FASTA of the selected contigs is built by the first round, on a thread of its own BESIDE the round's first kernels, which
+// do not read it (round 5: 0.4 ms in front of them); the emit kernels do
+struct TablesJob {
+    std::thread th; int rc = MSNV_OK; std::string msg;
+    int join() { if (th.joinable()) th.join(); if (rc) return fail(rc, "%s", msg.c_str()); return MSNV_OK; }
+    ~TablesJob() { if (th.joinable()) th.join(); }
+};
+
+// Everything one call of devpack_add_round works on.  The stages are member functions; each says what it takes and what it leaves.  Host
+// words that an asynchronous copy reads or writes are members here (or lie in the dataset's pinned block) unless the function that queues
+// the copy also waits for it: no stage leaves a copy in flight into its own frame.
+struct Round {
+    // ---- the inputs, and what every stage reads
+    msnv_dataset &ds; DevPackTables &T; const msnv_params &MP;
+    const size_t first; const uint8_t *const *const streams; const uint64_t *const n_bytes; const size_t S, NC; const bool on_device; const uint8_t *const in_place_base;
+    const hipStream_t st; DpParams P{}; const DpContig *ctg = nullptr;
+    Timer tm; TablesJob tables;
     // work buffers of the round: taken from the dataset's pool in call order (BufPool: grow-only, so a dataset's second round allocates nothing;
-    // with guarded allocations -- MSNV_GUARD_ALLOC=1 -- every buffer is exact and fresh)
-    BufPool pool{T.scratch};
-#define DP_BUF(type, name, count)                                                      \
-    type *name = static_cast<type *>(pool.get((uint64_t)(count) * sizeof(type)));      \
-    if (!name) return pool.rc
+    // with guarded allocations -- MSNV_GUARD_ALLOC=1 -- every buffer is exact and fresh); rocPRIM's storage is one slot of it
+    BufPool pool; Prim prim; size_t pool_staged = 0;
+    // ---- stage(): the streams in place, the quick walk's sub-segments
+    ScanResult SR; uint8_t *raw = nullptr; unsigned long long end_all = 0;
+    std::vector<SubStream> ss; uint64_t n_sub64 = 0; uint32_t sub_bytes = 0, cap2 = 0; bool quick_possible = false;
+    // ---- a front: the records' tables, the round's totals and lasting buffers, the depth stage launched
+    bool quick = false;                                          // the route that runs
+    uint32_t NR = 0, NPC = 0, NIV = 0, n_runs = 0, n_groups = 0, span_out = SPAN_OUT; uint64_t seqb_total = 0, seq_bound = 0, qual_bound = 0; bool in_order = false;
+    DpAcc *d_acc = nullptr; uint32_t *d_misc = nullptr, *d_outl = nullptr; uint8_t *d_cut = nullptr;
+    RdTables TB{}; uint32_t *d_recbase = nullptr; unsigned long long *d_send = nullptr;
+    uint32_t *d_runfirst = nullptr, *d_runf1 = nullptr, *d_grpfirst = nullptr, *d_grpmd = nullptr; DpRun *d_runs = nullptr; uint2 *d_grppre = nullptr; DevGroupRec *d_groups = nullptr;
+    uint32_t fl_h = 0; SubCnt tot_q{}; RecCnt tot_c{}, totals_h{}; uint32_t misc_h[MISC_WORDS] = {0, 0, 0, 0};      // (words of asynchronous copies)
+    struct Held {                                                // the round's lasting buffers, the round's until it is known to stand
+        void *round_buf = nullptr, *keep_buf = nullptr;
+        void drop() { if (round_buf) dev_free(round_buf); if (keep_buf) dev_free(keep_buf); round_buf = keep_buf = nullptr; }
+        ~Held() { drop(); }
+    } held;
+    DevRound keep; uint8_t *r_seq = nullptr, *r_qual = nullptr;
+    ReadHdr *w_hdr = nullptr; int32_t *w_tid = nullptr, *w_end = nullptr; uint16_t *w_depth = nullptr;      // where the emit kernels write the headers (keep's, or work buffers first)
+    DpSampleSum2 *d_sum = nullptr; unsigned long long *d_ss0 = nullptr, *d_pb = nullptr; uint32_t *d_slow = nullptr; DpSampleDst *d_dst = nullptr;
+    // ---- the careful front's work columns and what its sequential edits need
+    uint8_t *c_flags0 = nullptr; unsigned long long *c_key = nullptr, *c_sf = nullptr; uint32_t *c_end = nullptr, *c_maxc = nullptr; RecCnt *c_cnt = nullptr, *c_blkcnt = nullptr, *c_blkpre = nullptr;
+    uint32_t *d_ovr = nullptr; bool have_ovr = false;
+    uint32_t *d_depth0 = nullptr, *d_hot = nullptr, *d_hotn = nullptr, *d_capfail = nullptr;      // (msnv_cap_reads / msnv_token_cut)
+    std::vector<uint32_t> dev_cap, dev_tok;                      // samples whose depth cap / token limit the kernels take
+    DevBuf o_flag, o_rank, o_skip, o_keys, o_skeys, o_vals, o_svals, o_starts;      // overlapping mates (paired reads only: not from the pool)
+    uint32_t n_ovl_reads = 0, n_ovl_groups = 0;
+    // ---- the host's side of the round
+    std::vector<DpAcc> acc; std::vector<uint8_t> cut_marks, host_sample; std::vector<DpRun> runs; std::vector<DevGroupRec> groups;
+    std::vector<DpSampleSum2> sum; std::vector<unsigned long long> piece_bytes; std::vector<uint32_t> rec_base_h;
+    uint8_t *pinb = nullptr; uint64_t o_acc = 0, o_sum = 0, o_pb = 0, o_rb = 0, o_misc = 0, o_runs = 0, o_grp = 0;      // the pinned words launch_emit() fills and collect() reads
+    std::vector<DevPairRec> prec; uint32_t uns_h = 0, n_pairs_h = 0;
 
-    // ---- the round's streams side by side in one buffer (or where they lie, in HBM)
-    ScanResult SR;
-    if (int rc = scan_streams(st, ds.ctx->device, pool, streams, n_bytes, S, on_device, (int)NC, SR, in_place_base, in_place_capacity, true)) return rc;
-    T.wall_upload_s += SR.wall_upload_s; T.raw_bytes += SR.raw_bytes;
-    SR.wall_upload_s = 0;
-    uint8_t *const raw = SR.raw;
-    const std::vector<unsigned long long> &s_beg = SR.s_beg, &s_end = SR.s_end;
-    fin_trace("  pack: staged");
-    const size_t pool_staged = pool.next;
-    const DpContig *ctg = static_cast<const DpContig *>(T.contigs);
-    const unsigned long long end_all = S ? s_end[S - 1] : 0ull;
-
-    // Two routes to the records' tables.  QUICK (round 6): record boundaries and everything a record decides by itself in ONE walk
-    // (msnv_scan_sub2), one wait for the round's totals, then every kernel up to msnv_emit_block launched back to back; what the host
-    // learns late -- an error, a sample that needs the host pre-pass, more far-reaching reads than the list holds -- sends the round through
-    // the CAREFUL route: round 5's stage-by-stage form (msnv_scan_sub / msnv_scan_segments, msnv_measure_reads, waits between the stages),
-    // which also words malformed input and takes the host pre-pass's verdicts.  MSNV_SCAN=segments and MSNV_FRONT=careful force it (tests).
-    const uint32_t sub_bytes = knob::scan_sub_bytes(knob::SCAN_SUB_ROUND);   // (per call: tests shrink it; 6 KB: 2.36 -> 2.04 ms of scan + measure on the benchmark shape against 4 KB -- fewer entry guesses --, 8 KB the same)
-    const bool quick_wanted = !knob::scan_segments() && !knob::front_careful();
-    uint64_t n_sub64 = 0;
-    std::vector<SubStream> ss(S);
-    for (size_t s = 0; s < S; ++s) { ss[s] = SubStream{s_beg[s], s_end[s], (uint32_t)n_sub64, 0u}; n_sub64 += std::max<uint64_t>(1, (n_bytes[s] + sub_bytes - 1) / sub_bytes); }
-    const uint32_t cap2 = sub_bytes / 48u + 2u;                   // slots per sub-segment (a sub-segment of more, shorter records takes the careful route)
-    int route = (quick_wanted && S > 0 && sub_bytes <= 8192 && n_sub64 < 0x7ffffff0ull && n_sub64 * cap2 < 0xfffffff0ull) ? 0 : 1;
-
-    std::vector<DpAcc> acc(S);
-    std::vector<uint8_t> cut_marks(S, 0), host_sample(S, 0);
-    std::vector<DpRun> runs;
-    std::vector<DevGroupRec> groups;
-    std::vector<DpSampleSum2> sum(S + 1);
-    std::vector<unsigned long long> piece_bytes(S);
-    uint32_t NR = 0, NPC = 0, NIV = 0;
-    bool in_order = false;
-    DevRound keep;
-    uint8_t *r_seq = nullptr, *r_qual = nullptr;
-    std::vector<uint32_t> rec_base_h;
-    RecCnt totals_h{};
-    ReadHdr *w_hdr = nullptr; int32_t *w_tid = nullptr, *w_end = nullptr; uint16_t *w_depth = nullptr;
-    DpSampleDst *d_dst = nullptr;
-
-    if (!T.pending.ev0) {
-        hipEvent_t a = nullptr, b = nullptr, c = nullptr, d = nullptr, e = nullptr, f = nullptr;
-        HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b)); HIP_TRY(hipEventCreate(&c)); HIP_TRY(hipEventCreate(&d)); HIP_TRY(hipEventCreate(&e)); HIP_TRY(hipEventCreate(&f));
-        T.pending.ev0 = a; T.pending.ev1 = b; T.pending.evh = c; T.pending.evd = d; T.pending.evd2 = e; T.pending.evw = f;
+    Round(msnv_dataset &ds_, size_t first_, const uint8_t *const *streams_, const uint64_t *n_bytes_, int n, bool on_device_, const uint8_t *in_place_base_)
+        : ds(ds_), T(ds_.dp), MP(ds_.params), first(first_), streams(streams_), n_bytes(n_bytes_), S((size_t)n), NC(ds_.names.size()), on_device(on_device_), in_place_base(in_place_base_),
+          st((hipStream_t)ds_.ctx->stream), tm(st), pool{T.scratch}, prim(st), ss(S), acc(S), cut_marks(S, 0), host_sample(S, 0), sum(S + 1), piece_bytes(S) {
+        if (!T.ready) {
+            const int device = ds.ctx->device;
+            msnv_dataset *d = &ds; TablesJob *job = &tables;
+            tables.th = std::thread([d, job, device]() {
+                (void)hipSetDevice(device);
+                try { job->rc = build_tables(*d); } catch (const std::exception &e) { job->rc = fail_quiet(MSNV_ENOMEM, "device pack tables: %s", e.what()); }
+                if (job->rc) job->msg = msnv_last_error();
+            });
+        }
+        P.flag_filter = MP.flag_filter; P.min_mapq = MP.min_mapq; P.count_orphans = MP.count_orphans; P.cov_min_mapq = MP.cov_min_mapq;
+        P.max_depth = MP.max_depth; P.token_limit = MP.token_limit; P.ignore_overlaps = MP.ignore_overlaps;
+        P.c_eff = std::min(std::max(MP.min_baseq, -127), 127); P.all_low = MP.min_baseq > 127;
+        P.n_contigs = (int)NC; P.has_bed = ds.has_bed ? 1 : 0;
     }
-    for (;;) {
-        pool.next = pool_staged;
+
+    // Takes: the caller's streams.  Leaves: them side by side in one buffer (or where they lie, in HBM), the quick walk's sub-segments, whether
+    // the quick route may try, the round's events.  The pool stands at `pool_staged`: everything behind it is a route's.
+    int stage() {
+        if (int rc = stage_streams(st, ds.ctx->device, pool, streams, n_bytes, S, on_device, SR, in_place_base)) return rc;
+        T.wall_upload_s += SR.wall_upload_s; T.raw_bytes += SR.raw_bytes;
+        SR.wall_upload_s = 0;
+        raw = SR.raw;
+        fin_trace("  pack: staged");
+        pool_staged = pool.mark();
+        ctg = static_cast<const DpContig *>(T.contigs);
+        end_all = S ? SR.s_end[S - 1] : 0ull;
+        // Two routes to the records' tables.  QUICK (round 6): record boundaries and everything a record decides by itself in ONE walk
+        // (msnv_scan_sub2), one wait for the round's totals, then every kernel up to msnv_emit_block launched back to back; what the host
+        // learns late -- an error, a sample that needs the host pre-pass, more far-reaching reads than the list holds -- sends the round through
+        // the CAREFUL route: round 5's stage-by-stage form (msnv_scan_sub / msnv_scan_segments, msnv_measure_reads, waits between the stages),
+        // which also words malformed input and takes the host pre-pass's verdicts.  MSNV_SCAN=segments and MSNV_FRONT=careful force it (tests).
+        sub_bytes = knob::scan_sub_bytes(knob::SCAN_SUB_ROUND);   // (per call: tests shrink it; 6 KB: 2.36 -> 2.04 ms of scan + measure on the benchmark shape against 4 KB -- fewer entry guesses --, 8 KB the same)
+        const bool quick_wanted = !knob::scan_segments() && !knob::front_careful();
+        for (size_t s = 0; s < S; ++s) { ss[s] = SubStream{SR.s_beg[s], SR.s_end[s], (uint32_t)n_sub64, 0u}; n_sub64 += std::max<uint64_t>(1, (n_bytes[s] + sub_bytes - 1) / sub_bytes); }
+        cap2 = sub_bytes / 48u + 2u;                              // slots per sub-segment (a sub-segment of more, shorter records takes the careful route)
+        quick_possible = quick_wanted && S > 0 && sub_bytes <= 8192 && n_sub64 < 0x7ffffff0ull && n_sub64 * cap2 < 0xfffffff0ull;
+        if (!T.pending.ev0) {
+            hipEvent_t a = nullptr, b = nullptr, c = nullptr, d = nullptr, e = nullptr, f = nullptr;
+            HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b)); HIP_TRY(hipEventCreate(&c)); HIP_TRY(hipEventCreate(&d)); HIP_TRY(hipEventCreate(&e)); HIP_TRY(hipEventCreate(&f));
+            T.pending.ev0 = a; T.pending.ev1 = b; T.pending.evh = c; T.pending.evd = d; T.pending.evd2 = e; T.pending.evw = f;
+        }
+        return MSNV_OK;
+    }
+
+    // A route begins: whatever a route before it held goes back (its kernels have been waited for: collect()), the pool stands at
+    // `pool_staged` again, the accumulators are cleared.
+    int begin_route(bool quick_route) {
+        quick = quick_route;
+        held.drop();
+        pool.rewind(pool_staged);
         T.pending.has_evd = false;
-        DP_BUF(DpAcc, d_acc, S * ACC_COPIES);
-        DP_BUF(uint32_t, d_misc, MISC_WORDS);
-        DP_BUF(uint32_t, d_outl, CAP_OUT);
-        DP_BUF(uint8_t, d_cut, S);
-        DP_BUF(uint8_t, d_tmp, 1u << 20);                             // rocPRIM's temporary storage (grown below when a call asks for more)
-        size_t tmp_cap = (size_t)T.scratch[pool.next - 1].second;
-        const size_t tmp_slot = pool.next - 1;
-        auto tmp_for = [&](size_t need) -> int {
-            if (need <= tmp_cap) return MSNV_OK;
-            const size_t keep_next = pool.next;
-            pool.next = tmp_slot;
-            d_tmp = static_cast<uint8_t *>(pool.get(need));
-            pool.next = keep_next;
-            if (!d_tmp) return pool.rc;
-            tmp_cap = (size_t)T.scratch[tmp_slot].second;
-            return MSNV_OK;
-        };
-        auto scan32 = [&](const uint32_t *in, uint32_t *out, size_t cnt, bool inclusive) -> int {
-            size_t need = 0;
-            if (inclusive) HIP_TRY(rocprim::inclusive_scan(nullptr, need, in, out, cnt, rocprim::plus<uint32_t>(), st));
-            else HIP_TRY(rocprim::exclusive_scan(nullptr, need, in, out, 0u, cnt, rocprim::plus<uint32_t>(), st));
-            if (int rc = tmp_for(need)) return rc;
-            if (inclusive) HIP_TRY(rocprim::inclusive_scan(d_tmp, need, in, out, cnt, rocprim::plus<uint32_t>(), st));
-            else HIP_TRY(rocprim::exclusive_scan(d_tmp, need, in, out, 0u, cnt, rocprim::plus<uint32_t>(), st));
-            return MSNV_OK;
-        };
-        auto sort64 = [&](unsigned long long *kin, unsigned long long *kout, uint32_t *vin, uint32_t *vout, size_t cnt, unsigned end_bit) -> int {
-            size_t need = 0;
-            HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, kin, kout, vin, vout, cnt, 0u, end_bit, st));
-            if (int rc = tmp_for(need)) return rc;
-            HIP_TRY(rocprim::radix_sort_pairs(d_tmp, need, kin, kout, vin, vout, cnt, 0u, end_bit, st));
-            return MSNV_OK;
-        };
+        d_acc = pool.take<DpAcc>(S * ACC_COPIES);
+        d_misc = pool.take<uint32_t>(MISC_WORDS);
+        d_outl = pool.take<uint32_t>(CAP_OUT);
+        d_cut = pool.take<uint8_t>(S);
+        if (pool.rc) return pool.rc;
+        if (int rc = prim.bind(pool, 1u << 20)) return rc;        // rocPRIM's temporary storage (grown when a call asks for more)
         hipLaunchKernelGGL(msnv_acc_init, grid_for(S * ACC_COPIES, 256), dim3(256), 0, st, d_acc, (uint32_t)(S * ACC_COPIES));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemsetAsync(d_misc, 0, MISC_WORDS * 4, st));
-        uint32_t span_out = SPAN_OUT, n_runs = 0, n_groups = 0, n_ovl_total = 0;
-        uint64_t seqb_total = 0;
-        (void)n_ovl_total;
-        uint32_t misc_h[MISC_WORDS] = {0, 0, 0, 0};
-        RdTables TB{};
-        uint32_t *d_recbase = nullptr; unsigned long long *d_send = nullptr;
-        uint32_t *d_ovr = nullptr;
-        bool have_ovr = false;
-        uint32_t *d_depth0 = nullptr, *d_hot = nullptr, *d_hotn = nullptr, *d_capfail = nullptr;      // (careful route: msnv_cap_reads / msnv_token_cut)
-        std::vector<uint32_t> dev_cap, dev_tok;                      // samples whose depth cap / token limit the kernels take
-        DpSampleSum2 *d_sum = nullptr; unsigned long long *d_ss0 = nullptr, *d_pb = nullptr; uint32_t *d_slow = nullptr;
-        uint64_t seq_bound = 0, qual_bound = 0;
-        struct Held {                                                // the round's lasting buffers, this function's until the round is known to stand
-            void *round_buf = nullptr, *keep_buf = nullptr;
-            void drop() { if (round_buf) dev_free(round_buf); if (keep_buf) dev_free(keep_buf); round_buf = keep_buf = nullptr; }
-            ~Held() { drop(); }
-        } held;
-        DevBuf o_flag, o_rank, o_skip, o_keys, o_skeys, o_vals, o_svals, o_starts;      // overlapping mates (paired reads only: not from the pool)
-        uint32_t n_ovl_reads = 0, n_ovl_groups = 0;
-        uint32_t *d_runfirst = nullptr, *d_runf1 = nullptr, *d_grpfirst = nullptr, *d_grpmd = nullptr; DpRun *d_runs = nullptr; uint2 *d_grppre = nullptr; DevGroupRec *d_groups = nullptr;
+        span_out = SPAN_OUT; n_runs = n_groups = 0; seqb_total = 0; TB = RdTables{};
+        d_ovr = d_depth0 = d_hot = d_hotn = d_capfail = nullptr; have_ovr = false;
+        std::fill(misc_h, misc_h + MISC_WORDS, 0u);
         std::fill(host_sample.begin(), host_sample.end(), 0); std::fill(cut_marks.begin(), cut_marks.end(), 0);
+        return MSNV_OK;
+    }
 
-        // depth at every read start, the run and group tables: launched, not waited for
-        // The round's lasting buffers and the layout's small tables, once the round's totals are known (NPC, NIV, seqb_total, in_order).  The
-        // round's columns: per sample its pieces + 32 tail bytes, starting on 16 bytes, and one flag bit per nibble of them; the samples' shares
-        // are laid out on the device (msnv_sample_layout), the buffer is sized by the round's seq bytes + the most the tails and the rounding add.
-        auto alloc_round_buffers = [&]() -> int {
-            held.drop();
-            seq_bound = (seqb_total + (uint64_t)S * 48ull + 15ull) & ~15ull; qual_bound = seq_bound / 4;
-            const uint64_t NPCa = (uint64_t)NPC + 1, NB_ = ((uint64_t)NR + PB - 1) / PB;
-            if (int rc = dev_alloc(&held.round_buf, seq_bound + COL_PAD + qual_bound + 64, nullptr)) return rc;
-            r_seq = static_cast<uint8_t *>(held.round_buf); r_qual = r_seq + seq_bound + COL_PAD;
-            {
-                const uint64_t lo = seqb_total & ~15ull;              // (from the lowest place the columns can end to the flags: N -- the exact end is the device's)
-                HIP_TRY(hipMemsetAsync(r_seq + lo, 0xff, seq_bound + COL_PAD - lo, st));
-                HIP_TRY(hipMemsetAsync(r_qual, 0, qual_bound + 64, st));
+    // The round's lasting buffers and the layout's small tables, once the round's totals are known (NPC, NIV, seqb_total, in_order).  The
+    // round's columns: per sample its pieces + 32 tail bytes, starting on 16 bytes, and one flag bit per nibble of them; the samples' shares
+    // are laid out on the device (msnv_sample_layout), the buffer is sized by the round's seq bytes + the most the tails and the rounding add.
+    int alloc_round_buffers() {
+        held.drop();
+        seq_bound = (seqb_total + (uint64_t)S * 48ull + 15ull) & ~15ull; qual_bound = seq_bound / 4;
+        const uint64_t NPCa = (uint64_t)NPC + 1, NB_ = ((uint64_t)NR + PB - 1) / PB;
+        if (int rc = dev_alloc(&held.round_buf, seq_bound + COL_PAD + qual_bound + 64, nullptr)) return rc;
+        r_seq = static_cast<uint8_t *>(held.round_buf); r_qual = r_seq + seq_bound + COL_PAD;
+        {
+            const uint64_t lo = seqb_total & ~15ull;              // (from the lowest place the columns can end to the flags: N -- the exact end is the device's)
+            HIP_TRY(hipMemsetAsync(r_seq + lo, 0xff, seq_bound + COL_PAD - lo, st));
+            HIP_TRY(hipMemsetAsync(r_qual, 0, qual_bound + 64, st));
+        }
+        keep = DevRound{};
+        {   // what stays in HBM of the round besides the columns: headers (tile order) and intervals, for finalize -- written where they stay
+            const uint64_t b_hdr = (uint64_t)NPC * sizeof(ReadHdr), b_4 = (((uint64_t)NPC * 4) + 15) & ~15ull, b_2 = (((uint64_t)NPC * 2) + 15) & ~15ull, b_iv = (((uint64_t)NIV * 4) + 15) & ~15ull;
+            if (int rc = dev_alloc(&held.keep_buf, b_hdr + 2 * b_4 + b_2 + 3 * b_iv + 64, nullptr)) return rc;
+            uint8_t *q = static_cast<uint8_t *>(held.keep_buf);
+            keep.buf = held.keep_buf;
+            keep.hdr = reinterpret_cast<ReadHdr *>(q); q += b_hdr;
+            keep.tid = reinterpret_cast<int32_t *>(q); q += b_4;
+            keep.end = reinterpret_cast<int32_t *>(q); q += b_4;
+            keep.depth = reinterpret_cast<uint16_t *>(q); q += b_2;
+            keep.cov_tid = reinterpret_cast<int32_t *>(q); q += b_iv;
+            keep.cov_beg = reinterpret_cast<int32_t *>(q); q += b_iv;
+            keep.cov_end = reinterpret_cast<int32_t *>(q);
+            keep.n_pieces = NPC; keep.n_iv = NIV; keep.first_sample = first;
+            keep.col_buf = held.round_buf; keep.col_seq = r_seq; keep.col_qual = r_qual; keep.seq_total = 0; keep.n_samples = S;
+        }
+        d_sum = pool.take<DpSampleSum2>(S + 1);
+        d_ss0 = pool.take<unsigned long long>(S + 1);
+        d_dst = pool.take<DpSampleDst>(S);
+        d_pb = pool.take<unsigned long long>(S);
+        d_slow = pool.take<uint32_t>(NB_ + 2);
+        // (the general route keeps the headers in file order first: work buffers, sorted into `keep` by tile_pairs())
+        w_hdr = keep.hdr; w_tid = keep.tid; w_end = keep.end; w_depth = keep.depth;
+        if (in_order) {
+            w_hdr = pool.take<ReadHdr>(NPCa);
+            w_tid = pool.take<int32_t>(NPCa);
+            w_end = pool.take<int32_t>(NPCa);
+            w_depth = pool.take<uint16_t>(NPCa);
+        }
+        return pool.rc;
+    }
+    // the run and group tables' buffers, once their counts are known
+    int take_run_group_tables() {
+        d_runfirst = pool.take<uint32_t>((uint64_t)n_runs + 1);
+        d_runf1 = pool.take<uint32_t>((uint64_t)n_runs + 1);
+        d_runs = pool.take<DpRun>((uint64_t)n_runs + 1);
+        d_grpfirst = pool.take<uint32_t>((uint64_t)n_groups + 2);
+        d_grpmd = pool.take<uint32_t>(2 * ((uint64_t)n_groups + 1));
+        d_grppre = pool.take<uint2>((uint64_t)n_groups + 2);
+        d_groups = pool.take<DevGroupRec>((uint64_t)n_groups + 1);
+        return pool.rc;
+    }
+    // depth at every read start (written to the pieces' header slots), the run and group tables: launched on `sx`, not waited for.  Needs
+    // the groups' places (msnv_group_pre2) and the round's buffers.
+    int launch_depth_stage(hipStream_t sx) {
+        HIP_TRY(hipMemsetAsync(d_runf1, 0xff, ((uint64_t)n_runs + 1) * 4, sx));
+        HIP_TRY(hipMemsetAsync(d_grpmd, 0, 2 * ((uint64_t)n_groups + 1) * 4, sx));
+        if (d_hotn) HIP_TRY(hipMemsetAsync(d_hotn, 0, 4, sx));
+        if (NR) hipLaunchKernelGGL(msnv_depth2, grid_for(NR, 256), dim3(256), 0, sx, NR, TB.rd, TB.r_flags, TB.r_rg, TB.r_pre, TB.r_ftile, have_ovr ? d_ovr : nullptr, P, d_misc + MISC_SPAN, d_outl,
+                                   d_misc + MISC_NOUT, w_depth, d_grppre, in_order ? 1u : 0u, d_runfirst, d_runf1, d_grpfirst, d_grpmd, d_acc, d_depth0, d_hot, d_hotn);
+        if (n_runs) hipLaunchKernelGGL(msnv_run_table2, grid_for(n_runs, 256), dim3(256), 0, sx, n_runs, d_runfirst, d_runf1, TB.rd, d_runs);
+        hipLaunchKernelGGL(msnv_group_table2, grid_for((uint64_t)n_groups + 1, 256), dim3(256), 0, sx, n_groups, NR, d_grpfirst, TB.r_pre, TB.rd, TB.r_ftile, d_grpmd, (uint2 *)nullptr, d_groups);
+        HIP_TRY(hipGetLastError());
+        return MSNV_OK;
+    }
+    // errors, in record order (what the host stage's sequential walk would have met first)
+    int check_errors() const {
+        for (size_t s = 0; s < S; ++s) {
+            const unsigned long long e = acc[s].err;
+            if (e != ~0ull) {
+                const uint32_t kind = (uint32_t)(e & 7u); const unsigned long long idx = (e >> 3) - rec_base_h[s];
+                return fail(MSNV_EFORMAT, "%s (sample %zu of the batch, record %llu)", err_text(kind), s, idx);
             }
-            keep = DevRound{};
-            {   // what stays in HBM of the round besides the columns: headers (tile order) and intervals, for finalize -- written where they stay
-                const uint64_t b_hdr = (uint64_t)NPC * sizeof(ReadHdr), b_4 = (((uint64_t)NPC * 4) + 15) & ~15ull, b_2 = (((uint64_t)NPC * 2) + 15) & ~15ull, b_iv = (((uint64_t)NIV * 4) + 15) & ~15ull;
-                if (int rc = dev_alloc(&held.keep_buf, b_hdr + 2 * b_4 + b_2 + 3 * b_iv + 64, nullptr)) return rc;
-                uint8_t *q = static_cast<uint8_t *>(held.keep_buf);
-                keep.buf = held.keep_buf;
-                keep.hdr = reinterpret_cast<ReadHdr *>(q); q += b_hdr;
-                keep.tid = reinterpret_cast<int32_t *>(q); q += b_4;
-                keep.end = reinterpret_cast<int32_t *>(q); q += b_4;
-                keep.depth = reinterpret_cast<uint16_t *>(q); q += b_2;
-                keep.cov_tid = reinterpret_cast<int32_t *>(q); q += b_iv;
-                keep.cov_beg = reinterpret_cast<int32_t *>(q); q += b_iv;
-                keep.cov_end = reinterpret_cast<int32_t *>(q);
-                keep.n_pieces = NPC; keep.n_iv = NIV; keep.first_sample = first;
-                keep.col_buf = held.round_buf; keep.col_seq = r_seq; keep.col_qual = r_qual; keep.seq_total = 0; keep.n_samples = S;
-            }
-            DP_BUF(DpSampleSum2, d_sum_, S + 1);
-            DP_BUF(unsigned long long, d_ss0_, S + 1);
-            DP_BUF(DpSampleDst, d_dst_, S);
-            DP_BUF(unsigned long long, d_pb_, S);
-            DP_BUF(uint32_t, d_slow_, NB_ + 2);
-            d_sum = d_sum_; d_ss0 = d_ss0_; d_dst = d_dst_; d_pb = d_pb_; d_slow = d_slow_;
-            // (the general route keeps the headers in file order first: work buffers, sorted into `keep` below)
-            w_hdr = keep.hdr; w_tid = keep.tid; w_end = keep.end; w_depth = keep.depth;
-            if (in_order) {
-                DP_BUF(ReadHdr, d_hdr, NPCa);
-                DP_BUF(int32_t, d_ptid, NPCa);
-                DP_BUF(int32_t, d_pend, NPCa);
-                DP_BUF(uint16_t, d_pdepth, NPCa);
-                w_hdr = d_hdr; w_tid = d_ptid; w_end = d_pend; w_depth = d_pdepth;
-            }
-            return MSNV_OK;
-        };
-        // depth at every read start (written to the pieces' header slots), the run and group tables: launched on `sx`, not waited for.  Needs
-        // the groups' places (msnv_group_pre2) and the round's buffers.
-        auto launch_depth_stage = [&](hipStream_t sx) -> int {
-            HIP_TRY(hipMemsetAsync(d_runf1, 0xff, ((uint64_t)n_runs + 1) * 4, sx));
-            HIP_TRY(hipMemsetAsync(d_grpmd, 0, 2 * ((uint64_t)n_groups + 1) * 4, sx));
-            if (d_hotn) HIP_TRY(hipMemsetAsync(d_hotn, 0, 4, sx));
-            if (NR) hipLaunchKernelGGL(msnv_depth2, grid_for(NR, 256), dim3(256), 0, sx, NR, TB.rd, TB.r_flags, TB.r_rg, TB.r_pre, TB.r_ftile, have_ovr ? d_ovr : nullptr, P, d_misc + MISC_SPAN, d_outl,
-                                       d_misc + MISC_NOUT, w_depth, d_grppre, in_order ? 1u : 0u, d_runfirst, d_runf1, d_grpfirst, d_grpmd, d_acc, d_depth0, d_hot, d_hotn);
-            if (n_runs) hipLaunchKernelGGL(msnv_run_table2, grid_for(n_runs, 256), dim3(256), 0, sx, n_runs, d_runfirst, d_runf1, TB.rd, d_runs);
-            hipLaunchKernelGGL(msnv_group_table2, grid_for((uint64_t)n_groups + 1, 256), dim3(256), 0, sx, n_groups, NR, d_grpfirst, TB.r_pre, TB.rd, TB.r_ftile, d_grpmd, (uint2 *)nullptr, d_groups);
-            HIP_TRY(hipGetLastError());
-            return MSNV_OK;
-        };
-        // errors, in record order (what the host stage's sequential walk would have met first)
-        auto check_errors = [&]() -> int {
-            for (size_t s = 0; s < S; ++s) {
-                const unsigned long long e = acc[s].err;
-                if (e != ~0ull) {
-                    const uint32_t kind = (uint32_t)(e & 7u); const unsigned long long idx = (e >> 3) - rec_base_h[s];
-                    return fail(MSNV_EFORMAT, "%s (sample %zu of the batch, record %llu)", err_text(kind), s, idx);
-                }
-                if (!SR.bad_off.empty() && SR.bad_off[s] != ~0ull) return fail(MSNV_EFORMAT, "malformed BAM record at byte %llu", SR.bad_off[s]);
-            }
-            return MSNV_OK;
-        };
+            if (!SR.bad_off.empty() && SR.bad_off[s] != ~0ull) return fail(MSNV_EFORMAT, "malformed BAM record at byte %llu", SR.bad_off[s]);
+        }
+        return MSNV_OK;
+    }
 
-        if (route == 0) {
-            // ================================================================ QUICK: one walk, one wait
-            const uint32_t n_sub = (uint32_t)n_sub64;
-            DP_BUF(SubStream, d_ss, S);
-            DP_BUF(unsigned long long, d_first, (uint64_t)n_sub + 1);
-            DP_BUF(unsigned long long, d_stop, (uint64_t)n_sub + 1);
-            DP_BUF(unsigned long long, d_stopmax, (uint64_t)n_sub + 1);
-            DP_BUF(uint32_t, d_cnt, (uint64_t)n_sub + 1);
-            DP_BUF(uint16_t, d_delta, (uint64_t)n_sub * cap2 + 8);
-            DP_BUF(Slot, d_slots, (uint64_t)n_sub * cap2 + 1);
-            DP_BUF(SubInfo, d_info, (uint64_t)n_sub + 1);
-            DP_BUF(SubCnt, d_subcnt, (uint64_t)n_sub + 1);
-            DP_BUF(SubCnt, d_subbase, (uint64_t)n_sub + 1);
-            DP_BUF(uint8_t, d_bflag, (uint64_t)n_sub + 1);
-            DP_BUF(uint32_t, d_fl, 4);
-            DP_BUF(uint32_t, d_firstbad, S);
-            DP_BUF(uint32_t, d_recbase_, S + 1);
-            DP_BUF(unsigned long long, d_send_, S);
-            d_recbase = d_recbase_; d_send = d_send_;
-            fin_trace("  pack: quick buffers");
-            tm.start();
-            HIP_TRY(hipMemcpyAsync(d_ss, ss.data(), S * sizeof(SubStream), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_send, s_end.data(), S * 8, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemsetAsync(d_fl, 0, 16, st));
-            HIP_TRY(hipMemsetAsync(d_firstbad, 0xff, S * 4, st));
-            hipLaunchKernelGGL(msnv_scan_sub2, grid_for(n_sub, 256), dim3(256), 0, st, raw, d_ss, (uint32_t)S, n_sub, sub_bytes, cap2, (int)NC, ctg, P, d_first, d_stop, d_cnt, d_delta, d_slots, d_info, d_fl);
+    // ================================================================ QUICK: one walk, one wait
+    // Takes: the staged streams.  Leaves: the records' tables (TB), the round's totals and buffers, msnv_scan_write2 .. msnv_acc_fold queued on
+    // the stream and the depth stage on the second -- or TO_CAREFUL, with nothing of the round allocated yet.
+    int front_quick() {
+        if (int rc = begin_route(true)) return rc;
+        const uint32_t n_sub = (uint32_t)n_sub64;
+        auto *d_ss = pool.take<SubStream>(S);
+        auto *d_first = pool.take<unsigned long long>((uint64_t)n_sub + 1);
+        auto *d_stop = pool.take<unsigned long long>((uint64_t)n_sub + 1);
+        auto *d_stopmax = pool.take<unsigned long long>((uint64_t)n_sub + 1);
+        auto *d_cnt = pool.take<uint32_t>((uint64_t)n_sub + 1);
+        auto *d_delta = pool.take<uint16_t>((uint64_t)n_sub * cap2 + 8);
+        auto *d_slots = pool.take<Slot>((uint64_t)n_sub * cap2 + 1);
+        auto *d_info = pool.take<SubInfo>((uint64_t)n_sub + 1);
+        auto *d_subcnt = pool.take<SubCnt>((uint64_t)n_sub + 1);
+        auto *d_subbase = pool.take<SubCnt>((uint64_t)n_sub + 1);
+        auto *d_bflag = pool.take<uint8_t>((uint64_t)n_sub + 1);
+        auto *d_fl = pool.take<uint32_t>(4);
+        auto *d_firstbad = pool.take<uint32_t>(S);
+        d_recbase = pool.take<uint32_t>(S + 1);
+        d_send = pool.take<unsigned long long>(S);
+        if (pool.rc) return pool.rc;
+        fin_trace("  pack: quick buffers");
+        tm.start();
+        HIP_TRY(hipMemcpyAsync(d_ss, ss.data(), S * sizeof(SubStream), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_send, SR.s_end.data(), S * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(d_fl, 0, 16, st));
+        HIP_TRY(hipMemsetAsync(d_firstbad, 0xff, S * 4, st));
+        hipLaunchKernelGGL(msnv_scan_sub2, grid_for(n_sub, 256), dim3(256), 0, st, raw, d_ss, (uint32_t)S, n_sub, sub_bytes, cap2, (int)NC, ctg, P, d_first, d_stop, d_cnt, d_delta, d_slots, d_info, d_fl);
+        HIP_TRY(hipGetLastError());
+        size_t need = 0;                                          // both scans' storage before either is queued
+        if (int rc = prim.inclusive(d_stop, d_stopmax, (size_t)n_sub, U64Max(), &need)) return rc;
+        if (int rc = prim.exclusive(d_subcnt, d_subbase, SubCnt{}, (size_t)n_sub + 1, SubCntSum(), &need)) return rc;
+        if (int rc = prim.room(need)) return rc;
+        for (int pass = 0;; ++pass) {
+            // seams checked, every stream's first sub-segment that guessed wrong walked again (until none is left: usually the first look), then
+            // the boundaries, and the scan whose last entry holds the round's totals -- all of it queued, ONE wait  (scan_sub_walk has this loop's twin)
+            if (int rc = prim.inclusive(d_stop, d_stopmax, (size_t)n_sub, U64Max())) return rc;
+            hipLaunchKernelGGL(msnv_scan_check, grid_for((uint64_t)n_sub + 1, 256), dim3(256), 0, st, d_ss, (uint32_t)S, n_sub, sub_bytes, d_first, d_stopmax, d_cnt, d_firstbad);
+            hipLaunchKernelGGL(msnv_scan_fix2, grid_for(S, 64), dim3(64), 0, st, raw, d_ss, (uint32_t)S, sub_bytes, cap2, ctg, P, d_first, d_stop, d_stopmax, d_cnt, d_delta, d_slots, d_info, d_firstbad, d_fl);
+            hipLaunchKernelGGL(msnv_sub_bounds, grid_for((uint64_t)n_sub + 1, 256), dim3(256), 0, st, d_ss, (uint32_t)S, n_sub, d_cnt, d_info, d_subcnt, d_bflag);
             HIP_TRY(hipGetLastError());
-            size_t need_max = 0, need_sub = 0;
-            HIP_TRY(rocprim::inclusive_scan(nullptr, need_max, d_stop, d_stopmax, (size_t)n_sub, U64Max(), st));
-            HIP_TRY(rocprim::exclusive_scan(nullptr, need_sub, d_subcnt, d_subbase, SubCnt{}, (size_t)n_sub + 1, SubCntSum(), st));
-            if (int rc = tmp_for(std::max(need_max, need_sub))) return rc;
-            uint32_t fl = 0; SubCnt tot{};
-            for (int pass = 0;; ++pass) {
-                // seams checked, every stream's first sub-segment that guessed wrong walked again (until none is left: usually the first look), then
-                // the boundaries, and the scan whose last entry holds the round's totals -- all of it queued, ONE wait
-                HIP_TRY(rocprim::inclusive_scan(d_tmp, need_max, d_stop, d_stopmax, (size_t)n_sub, U64Max(), st));
-                hipLaunchKernelGGL(msnv_scan_check, grid_for((uint64_t)n_sub + 1, 256), dim3(256), 0, st, d_ss, (uint32_t)S, n_sub, sub_bytes, d_first, d_stopmax, d_cnt, d_firstbad);
-                hipLaunchKernelGGL(msnv_scan_fix2, grid_for(S, 64), dim3(64), 0, st, raw, d_ss, (uint32_t)S, sub_bytes, cap2, ctg, P, d_first, d_stop, d_stopmax, d_cnt, d_delta, d_slots, d_info, d_firstbad, d_fl);
-                hipLaunchKernelGGL(msnv_sub_bounds, grid_for((uint64_t)n_sub + 1, 256), dim3(256), 0, st, d_ss, (uint32_t)S, n_sub, d_cnt, d_info, d_subcnt, d_bflag);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(rocprim::exclusive_scan(d_tmp, need_sub, d_subcnt, d_subbase, SubCnt{}, (size_t)n_sub + 1, SubCntSum(), st));
-                HIP_TRY(hipMemcpyAsync(&fl, d_fl, 4, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipMemcpyAsync(&tot, d_subbase + n_sub, sizeof(SubCnt), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                if (!(fl & 2u) || (fl & 5u) || pass >= 4096) break;
-                T.n_scan_redone += 1;                             // (counted: a repair pass)
-                HIP_TRY(hipMemsetAsync(d_fl, 0, 4, st));
+            if (int rc = prim.exclusive(d_subcnt, d_subbase, SubCnt{}, (size_t)n_sub + 1, SubCntSum())) return rc;
+            HIP_TRY(hipMemcpyAsync(&fl_h, d_fl, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(&tot_q, d_subbase + n_sub, sizeof(SubCnt), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (!(fl_h & 2u) || (fl_h & 5u) || pass >= 4096) break;
+            T.n_scan_redone += 1;                             // (counted: a repair pass)
+            HIP_TRY(hipMemsetAsync(d_fl, 0, 4, st));
+        }
+        T.ms_scan += tm.stop();
+        fin_trace("  pack: scan + measure, totals (wait)");
+        const SubCnt &tot = tot_q;
+        if (fl_h || tot.odd) { T.n_scan_redone += 1; return TO_CAREFUL; }      // a chain that breaks, a sub-segment the slots cannot hold: the careful route takes (and words) it
+        if (SR.raw_bytes / 36 > 0xfffffff0ull) return fail(MSNV_EDOMAIN, "more than 2^32 records in one round of the device pack");
+        // paired reads: the candidates of the overlapping-mate tweak are grouped, and the samples that need the host pre-pass known, before
+        // anything is emitted -- the careful route does all of that; the quick route takes the rounds without candidates
+        if (!MP.ignore_overlaps && tot.ovl >= 2) return TO_CAREFUL;
+        NR = tot.rec; NPC = tot.npiece; NIV = tot.niv; n_runs = tot.runs; n_groups = tot.grps; seqb_total = tot.seqb;
+        in_order = tot.sort != 0 || knob::tile_order_sort();
+        const uint64_t NRa = (uint64_t)NR + 1;
+        auto *d_recoff = pool.take<unsigned long long>(NRa);
+        auto *d_recsample = pool.take<uint16_t>(NRa);
+        auto *d_rd = pool.take<uint4>(NRa);
+        auto *d_pre = pool.take<RecCnt>(NRa);
+        auto *d_ftile = pool.take<uint32_t>(NRa);
+        auto *d_flags = pool.take<uint8_t>(NRa);
+        auto *d_rg = pool.take<unsigned long long>(NRa);
+        if (int rc = take_run_group_tables()) return rc;
+        if (int rc = alloc_round_buffers()) return rc;
+        TB = RdTables{d_recoff, d_recsample, d_recbase, d_rd, d_pre, d_ftile, d_flags, d_rg, d_runfirst, d_grpfirst};
+        if (n_sub) hipLaunchKernelGGL(msnv_scan_write2, grid_for(n_sub, 256), dim3(256), 0, st, d_ss, (uint32_t)S, n_sub, sub_bytes, cap2, d_cnt, d_subbase, d_bflag, d_delta, d_slots, d_info, TB, d_acc, d_misc,
+                                      d_outl, span_out, T.overhang, P);
+        HIP_TRY(hipGetLastError());
+        totals_h = RecCnt{tot.pile, tot.npiece, tot.niv, tot.spill, tot.seqb};
+        HIP_TRY(hipMemcpyAsync(d_pre + NR, &totals_h, sizeof(RecCnt), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_recoff + NR, &end_all, 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_recbase + S, &NR, 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(msnv_group_pre2, grid_for((uint64_t)n_groups + 1, 256), dim3(256), 0, st, n_groups, NR, d_grpfirst, TB.r_pre, d_grppre);
+        hipLaunchKernelGGL(msnv_acc_fold, dim3((unsigned)S), dim3(64), 0, st, d_acc, (uint32_t)S);
+        HIP_TRY(hipGetLastError());
+        // ---- the depth stage on the context's SECOND stream, beside the layout and the emit kernels on the first (round 6: msnv_depth2
+        // writes the pieces' depths itself, so nothing the emit kernels read comes from it); what the host needs of it goes to the pinned
+        // words behind it, with an event (evd2)
+        if (!ds.ctx->stream2) { if (int rc = dev_stream_create(&ds.ctx->stream2)) return rc; }
+        const bool depth_on_main = knob::depth_on_main();      // (A/B: the depth stage in front of the emit kernels, on their stream)
+        hipStream_t st2 = depth_on_main ? st : (hipStream_t)ds.ctx->stream2;
+        HIP_TRY(hipEventRecord((hipEvent_t)T.pending.evw, st));
+        HIP_TRY(hipStreamWaitEvent(st2, (hipEvent_t)T.pending.evw, 0));
+        HIP_TRY(hipEventRecord((hipEvent_t)T.pending.evd, st2)); T.pending.has_evd = true;
+        return launch_depth_stage(st2);
+    }
+
+    // ================================================================ CAREFUL: stage by stage
+    // Takes: the staged streams.  Leaves: what front_quick() leaves, everything waited for and looked at (errors reported), and what
+    // edit_qualities() needs: the overlapping mates' groups (o_*), the samples of the kernels' edits (dev_tok), the host pre-pass's verdicts
+    // (d_ovr, cut_marks, host_sample).  Two passes at the most: the second measures again behind the pre-pass and msnv_cap_reads.
+    int front_careful() {
+        if (int rc = begin_route(false)) return rc;
+        SR.ms_scan = 0; SR.n_redone = 0;
+        if (int rc = scan_records(st, pool, n_bytes, S, NC, SR)) return rc;
+        T.ms_scan += SR.ms_scan; T.n_scan_redone += SR.n_redone;
+        NR = SR.NR;
+        const uint64_t NRa = (uint64_t)NR + 1, NBa = ((uint64_t)NR + PB - 1) / PB + 1;   // blocks of PB records: their sums and bases (entry NB of the bases = the round's totals)
+        d_recbase = SR.d_recbase; d_send = SR.d_send;
+        fin_trace("  pack: scan done");
+        c_flags0 = pool.take<uint8_t>(NRa);
+        c_key = pool.take<unsigned long long>(NRa);
+        c_end = pool.take<uint32_t>(NRa);
+        c_maxc = pool.take<uint32_t>(NRa);
+        auto *d_ftile = pool.take<uint32_t>(NRa);
+        c_cnt = pool.take<RecCnt>(NRa);
+        c_blkcnt = pool.take<RecCnt>(NBa);
+        c_blkpre = pool.take<RecCnt>(NBa);
+        d_ovr = pool.take<uint32_t>(NRa);
+        auto *d_rd = pool.take<uint4>(NRa);
+        auto *d_pre = pool.take<RecCnt>(NRa);
+        auto *d_flags = pool.take<uint8_t>(NRa);
+        auto *d_rg = pool.take<unsigned long long>(NRa);
+        c_sf = pool.take<unsigned long long>(NRa);
+        d_depth0 = pool.take<uint32_t>(NRa);
+        d_hot = pool.take<uint32_t>(NRa);
+        d_hotn = pool.take<uint32_t>(2);
+        if (pool.rc) return pool.rc;
+        d_capfail = d_hotn + 1;
+        HIP_TRY(hipMemsetAsync(d_hotn, 0, 8, st));
+        TB = RdTables{SR.d_recoff, SR.d_recsample, d_recbase, d_rd, d_pre, d_ftile, d_flags, d_rg, nullptr, nullptr};
+        HIP_TRY(hipMemcpyAsync(SR.d_recoff + NR, &end_all, 8, hipMemcpyHostToDevice, st));
+        const size_t depth_bufs_from = pool.mark();
+        for (int pass = 0; pass < 2; ++pass) {
+            pool.rewind(depth_bufs_from);
+            if (int rc = measure()) return rc;
+            if (int rc = tables_and_depth()) return rc;
+            const bool ovl_on_host = knob::overlap_on_host();      // (read per pass, like MSNV_PREPASS below: the tests switch them)
+            if (int rc = list_overlaps(pass, ovl_on_host)) return rc;
+            if (pass == 1) {
+                if (!dev_cap.empty()) {
+                    uint32_t cap_fail = 0;
+                    HIP_TRY(hipMemcpy(&cap_fail, d_capfail, 4, hipMemcpyDeviceToHost));
+                    if (cap_fail) return fail(MSNV_EINVAL, "internal: the depth-cap kernel met a read that spans more than its ring holds");
+                }
+                break;
             }
-            T.ms_scan += tm.stop();
-            fin_trace("  pack: scan + measure, totals (wait)");
-            if (fl || tot.odd) { route = 1; T.n_scan_redone += 1; continue; }      // a chain that breaks, a sub-segment the slots cannot hold: the careful route takes (and words) it
-            if (SR.raw_bytes / 36 > 0xfffffff0ull) return fail(MSNV_EDOMAIN, "more than 2^32 records in one round of the device pack");
-            // paired reads: the candidates of the overlapping-mate tweak are grouped, and the samples that need the host pre-pass known, before
-            // anything is emitted -- the careful route does all of that; the quick route takes the rounds without candidates
-            if (!MP.ignore_overlaps && tot.ovl >= 2) { route = 1; continue; }
-            NR = tot.rec; NPC = tot.npiece; NIV = tot.niv; n_runs = tot.runs; n_groups = tot.grps; n_ovl_total = tot.ovl; seqb_total = tot.seqb;
-            in_order = tot.sort != 0 || knob::tile_order_sort();
-            const uint64_t NRa = (uint64_t)NR + 1;
-            DP_BUF(unsigned long long, d_recoff, NRa);
-            DP_BUF(uint16_t, d_recsample, NRa);
-            DP_BUF(uint4, d_rd, NRa);
-            DP_BUF(RecCnt, d_pre, NRa);
-            DP_BUF(uint32_t, d_ftile, NRa);
-            DP_BUF(uint8_t, d_flags, NRa);
-            DP_BUF(unsigned long long, d_rg, NRa);
-            DP_BUF(uint32_t, q_runfirst, (uint64_t)n_runs + 1);
-            DP_BUF(uint32_t, q_runf1, (uint64_t)n_runs + 1);
-            DP_BUF(DpRun, q_runs, (uint64_t)n_runs + 1);
-            DP_BUF(uint32_t, q_grpfirst, (uint64_t)n_groups + 2);
-            DP_BUF(uint32_t, q_grpmd, 2 * ((uint64_t)n_groups + 1));
-            DP_BUF(uint2, q_grppre, (uint64_t)n_groups + 2);
-            DP_BUF(DevGroupRec, q_groups, (uint64_t)n_groups + 1);
-            d_runfirst = q_runfirst; d_runf1 = q_runf1; d_runs = q_runs; d_grpfirst = q_grpfirst; d_grpmd = q_grpmd; d_grppre = q_grppre; d_groups = q_groups;
-            if (int rc = alloc_round_buffers()) return rc;
-            TB = RdTables{d_recoff, d_recsample, d_recbase, d_rd, d_pre, d_ftile, d_flags, d_rg, d_runfirst, d_grpfirst};
-            if (n_sub) hipLaunchKernelGGL(msnv_scan_write2, grid_for(n_sub, 256), dim3(256), 0, st, d_ss, (uint32_t)S, n_sub, sub_bytes, cap2, d_cnt, d_subbase, d_bflag, d_delta, d_slots, d_info, TB, d_acc, d_misc,
-                                          d_outl, span_out, T.overhang, P);
+            bool second_pass = false;
+            if (int rc = sequential_edits(ovl_on_host, second_pass)) return rc;
+            if (!second_pass) break;
+        }
+        return MSNV_OK;
+    }
+    // msnv_measure_reads and the scan of its blocks' sums; again with a wider window when more far-reaching reads turn up than the list holds.
+    // Leaves: the round's totals (tot_c, NPC, NIV, seqb_total), misc_h.  One wait per turn.
+    int measure() {
+        const uint64_t NB = ((uint64_t)NR + PB - 1) / PB;
+        hipLaunchKernelGGL(msnv_acc_init, grid_for(S * ACC_COPIES, 256), dim3(256), 0, st, d_acc, (uint32_t)(S * ACC_COPIES));
+        HIP_TRY(hipGetLastError());
+        tm.start();
+        for (;;) {
+            HIP_TRY(hipMemsetAsync(d_misc, 0, MISC_WORDS * 4, st));
+            HIP_TRY(hipMemsetAsync(c_blkcnt + NB, 0, sizeof(RecCnt), st));
+            if (NR) {
+                hipLaunchKernelGGL(msnv_measure_reads, grid_for(NR, 256), dim3(256), 0, st, raw, TB.rec_off, TB.rec_sample, d_recbase, d_send, NR, ctg, P, have_ovr ? d_ovr : nullptr, c_flags0,
+                                   c_key, c_end, c_maxc, c_cnt, TB.r_ftile, c_blkcnt, d_acc, d_misc, d_outl, span_out, T.overhang);
+                HIP_TRY(hipGetLastError());
+            }
+            // every block's base: rank among the pileup reads, first piece, first interval, next-tile pieces before it, first seq byte
+            if (int rc = prim.exclusive(c_blkcnt, c_blkpre, RecCnt{}, (size_t)(NB + 1), RecCntSum())) return rc;
+            HIP_TRY(hipMemcpyAsync(&tot_c, c_blkpre + NB, sizeof(RecCnt), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(misc_h, d_misc, MISC_WORDS * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (misc_h[MISC_NOUT] <= CAP_OUT || span_out >= 0x40000000u) break;
+            // more far-reaching reads than the list holds (long reads): they are the ordinary reads of this round -- a wider window, again
+            span_out = span_out < 0x04000000u ? span_out * 16u : 0x7fffffffu;
+            hipLaunchKernelGGL(msnv_acc_init, grid_for(S * ACC_COPIES, 256), dim3(256), 0, st, d_acc, (uint32_t)(S * ACC_COPIES));
             HIP_TRY(hipGetLastError());
-            totals_h = RecCnt{tot.pile, tot.npiece, tot.niv, tot.spill, tot.seqb};      // (function scope: the copy below may read it later)
-            HIP_TRY(hipMemcpyAsync(d_pre + NR, &totals_h, sizeof(RecCnt), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_recoff + NR, &end_all, 8, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_recbase + S, &NR, 4, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(msnv_group_pre2, grid_for((uint64_t)n_groups + 1, 256), dim3(256), 0, st, n_groups, NR, d_grpfirst, TB.r_pre, d_grppre);
-            hipLaunchKernelGGL(msnv_acc_fold, dim3((unsigned)S), dim3(64), 0, st, d_acc, (uint32_t)S);
+        }
+        T.ms_measure += tm.stop();
+        fin_trace("  pack: measure + block scan (sync)");
+        NPC = tot_c.npiece; NIV = tot_c.niv; seqb_total = tot_c.seqb;
+        return MSNV_OK;
+    }
+    // The records' tables in the quick route's form (run and group numbers by a scan of their start flags), the round's buffers, the depth
+    // stage -- on the round's own stream, waited for; then the errors.  Leaves: TB filled, runs / groups / acc / misc_h on the host.
+    int tables_and_depth() {
+        tm.start();
+        n_runs = 0; n_groups = 0;
+        if (NR) {
+            hipLaunchKernelGGL(msnv_tables_from_measure, grid_for(NR, 256), dim3(256), 0, st, NR, TB.rec_sample, c_flags0, c_key, c_end, c_maxc, c_cnt, c_blkpre, TB.r_ftile, span_out, P, TB, c_sf, d_acc, d_misc);
             HIP_TRY(hipGetLastError());
-            // ---- the depth stage on the context's SECOND stream, beside the layout and the emit kernels on the first (round 6: msnv_depth2
-            // writes the pieces' depths itself, so nothing the emit kernels read comes from it); what the host needs of it goes to the pinned
-            // words behind it, with an event (evd2)
-            if (!ds.ctx->stream2) { if (int rc = dev_stream_create(&ds.ctx->stream2)) return rc; }
-            const bool depth_on_main = knob::depth_on_main();      // (A/B: the depth stage in front of the emit kernels, on their stream)
-            hipStream_t st2 = depth_on_main ? st : (hipStream_t)ds.ctx->stream2;
-            HIP_TRY(hipEventRecord((hipEvent_t)T.pending.evw, st));
-            HIP_TRY(hipStreamWaitEvent(st2, (hipEvent_t)T.pending.evw, 0));
-            HIP_TRY(hipEventRecord((hipEvent_t)T.pending.evd, st2)); T.pending.has_evd = true;
-            if (int rc = launch_depth_stage(st2)) return rc;
-        } else {
-            // ================================================================ CAREFUL: stage by stage
-            SR.ms_scan = 0; SR.n_redone = 0;
-            if (int rc = scan_streams(st, ds.ctx->device, pool, streams, n_bytes, S, on_device, (int)NC, SR, in_place_base, in_place_capacity)) return rc;
-            T.ms_scan += SR.ms_scan; T.n_scan_redone += SR.n_redone;
-            NR = SR.NR;
-            const uint64_t NRa = (uint64_t)NR + 1;
-            d_recbase = SR.d_recbase; d_send = SR.d_send;
-            fin_trace("  pack: scan done");
-            DP_BUF(uint8_t, d_flags0, NRa);
-            DP_BUF(unsigned long long, d_key, NRa);
-            DP_BUF(uint32_t, d_end, NRa);
-            DP_BUF(uint32_t, d_maxc, NRa);
-            DP_BUF(uint32_t, d_ftile, NRa);
-            DP_BUF(RecCnt, d_cnt, NRa);
-            const uint64_t NB = ((uint64_t)NR + PB - 1) / PB, NBa = NB + 1;   // blocks of PB records: their sums and bases (entry NB of the bases = the round's totals)
-            DP_BUF(RecCnt, d_blkcnt, NBa);
-            DP_BUF(RecCnt, d_blkpre, NBa);
-            DP_BUF(uint32_t, d_ovr_, NRa);
-            DP_BUF(uint4, d_rd, NRa);
-            DP_BUF(RecCnt, d_pre, NRa);
-            DP_BUF(uint8_t, d_flags, NRa);
-            DP_BUF(unsigned long long, d_rg, NRa);
-            DP_BUF(unsigned long long, d_sf, NRa);
-            d_ovr = d_ovr_;
-            DP_BUF(uint32_t, d_depth0_, NRa);
-            DP_BUF(uint32_t, d_hot_, NRa);
-            DP_BUF(uint32_t, d_hotn_, 2);
-            d_depth0 = d_depth0_; d_hot = d_hot_; d_hotn = d_hotn_; d_capfail = d_hotn_ + 1;
-            HIP_TRY(hipMemsetAsync(d_hotn_, 0, 8, st));
-            TB = RdTables{SR.d_recoff, SR.d_recsample, d_recbase, d_rd, d_pre, d_ftile, d_flags, d_rg, nullptr, nullptr};
-            HIP_TRY(hipMemcpyAsync(SR.d_recoff + NR, &end_all, 8, hipMemcpyHostToDevice, st));
-            const size_t depth_bufs_from = pool.next;
-            RecCnt tot{};
-            for (int pass = 0; pass < 2; ++pass) {
-                pool.next = depth_bufs_from;
-                hipLaunchKernelGGL(msnv_acc_init, grid_for(S * ACC_COPIES, 256), dim3(256), 0, st, d_acc, (uint32_t)(S * ACC_COPIES));
-                HIP_TRY(hipGetLastError());
-                tm.start();
-                for (;;) {
-                    HIP_TRY(hipMemsetAsync(d_misc, 0, MISC_WORDS * 4, st));
-                    HIP_TRY(hipMemsetAsync(d_blkcnt + NB, 0, sizeof(RecCnt), st));
-                    if (NR) {
-                        hipLaunchKernelGGL(msnv_measure_reads, grid_for(NR, 256), dim3(256), 0, st, raw, SR.d_recoff, SR.d_recsample, d_recbase, d_send, NR, ctg, P, have_ovr ? d_ovr : nullptr, d_flags0,
-                                           d_key, d_end, d_maxc, d_cnt, d_ftile, d_blkcnt, d_acc, d_misc, d_outl, span_out, T.overhang);
-                        HIP_TRY(hipGetLastError());
-                    }
-                    {   // every block's base: rank among the pileup reads, first piece, first interval, next-tile pieces before it, first seq byte
-                        size_t need = 0;
-                        HIP_TRY(rocprim::exclusive_scan(nullptr, need, d_blkcnt, d_blkpre, RecCnt{}, (size_t)NBa, RecCntSum(), st));
-                        if (int rc = tmp_for(need)) return rc;
-                        HIP_TRY(rocprim::exclusive_scan(d_tmp, need, d_blkcnt, d_blkpre, RecCnt{}, (size_t)NBa, RecCntSum(), st));
-                    }
-                    HIP_TRY(hipMemcpyAsync(&tot, d_blkpre + NB, sizeof(RecCnt), hipMemcpyDeviceToHost, st));
-                    HIP_TRY(hipMemcpyAsync(misc_h, d_misc, MISC_WORDS * 4, hipMemcpyDeviceToHost, st));
-                    HIP_TRY(hipStreamSynchronize(st));
-                    if (misc_h[MISC_NOUT] <= CAP_OUT || span_out >= 0x40000000u) break;
-                    // more far-reaching reads than the list holds (long reads): they are the ordinary reads of this round -- a wider window, again
-                    span_out = span_out < 0x04000000u ? span_out * 16u : 0x7fffffffu;
-                    hipLaunchKernelGGL(msnv_acc_init, grid_for(S * ACC_COPIES, 256), dim3(256), 0, st, d_acc, (uint32_t)(S * ACC_COPIES));
-                    HIP_TRY(hipGetLastError());
-                }
-                T.ms_measure += tm.stop();
-                fin_trace("  pack: measure + block scan (sync)");
-                NPC = tot.npiece; NIV = tot.niv; seqb_total = tot.seqb;
-                // ---- the records' tables in the quick route's form; run and group numbers by a scan of their start flags
-                tm.start();
-                n_runs = 0; n_groups = 0;
-                if (NR) {
-                    hipLaunchKernelGGL(msnv_tables_from_measure, grid_for(NR, 256), dim3(256), 0, st, NR, SR.d_recsample, d_flags0, d_key, d_end, d_maxc, d_cnt, d_blkpre, d_ftile, span_out, P, TB, d_sf, d_acc, d_misc);
-                    HIP_TRY(hipGetLastError());
-                    size_t need = 0;
-                    HIP_TRY(rocprim::inclusive_scan(nullptr, need, d_sf, d_rg, (size_t)NR, rocprim::plus<unsigned long long>(), st));
-                    if (int rc = tmp_for(need)) return rc;
-                    HIP_TRY(rocprim::inclusive_scan(d_tmp, need, d_sf, d_rg, (size_t)NR, rocprim::plus<unsigned long long>(), st));
-                    unsigned long long last = 0;
-                    HIP_TRY(hipMemcpyAsync(&last, d_rg + (NR - 1), 8, hipMemcpyDeviceToHost, st));
-                    HIP_TRY(hipMemcpyAsync(misc_h, d_misc, MISC_WORDS * 4, hipMemcpyDeviceToHost, st));
-                    HIP_TRY(hipStreamSynchronize(st));
-                    n_runs = (uint32_t)(last >> 32); n_groups = (uint32_t)last;
-                }
-                in_order = misc_h[MISC_SORT] != 0 || knob::tile_order_sort();      // (the tile order's route: the depth kernel writes the pieces' depths at their header slots)
-                totals_h = tot;
-                HIP_TRY(hipMemcpyAsync(d_pre + NR, &totals_h, sizeof(RecCnt), hipMemcpyHostToDevice, st));
-                DP_BUF(uint32_t, c_runfirst, (uint64_t)n_runs + 1);
-                DP_BUF(uint32_t, c_runf1, (uint64_t)n_runs + 1);
-                DP_BUF(DpRun, c_runs, (uint64_t)n_runs + 1);
-                DP_BUF(uint32_t, c_grpfirst, (uint64_t)n_groups + 2);
-                DP_BUF(uint32_t, c_grpmd, 2 * ((uint64_t)n_groups + 1));
-                DP_BUF(uint2, c_grppre, (uint64_t)n_groups + 2);
-                DP_BUF(DevGroupRec, c_groups, (uint64_t)n_groups + 1);
-                d_runfirst = c_runfirst; d_runf1 = c_runf1; d_runs = c_runs; d_grpfirst = c_grpfirst; d_grpmd = c_grpmd; d_grppre = c_grppre; d_groups = c_groups;
-                if (int rc = alloc_round_buffers()) return rc;
-                // (the groups' first records: this route has no table of them yet -- the depth kernel writes it, the places follow, then the depths)
-                hipLaunchKernelGGL(msnv_group_firsts, grid_for(NR, 256), dim3(256), 0, st, NR, TB.r_flags, TB.r_rg, d_runfirst, d_grpfirst);
-                hipLaunchKernelGGL(msnv_group_pre2, grid_for((uint64_t)n_groups + 1, 256), dim3(256), 0, st, n_groups, NR, d_grpfirst, TB.r_pre, d_grppre);
-                HIP_TRY(hipGetLastError());
-                if (int rc = launch_depth_stage(st)) return rc;
-                hipLaunchKernelGGL(msnv_acc_fold, dim3((unsigned)S), dim3(64), 0, st, d_acc, (uint32_t)S);
-                HIP_TRY(hipGetLastError());
-                runs.resize(n_runs); groups.resize(n_groups);
-                HIP_TRY(hipMemcpyAsync(runs.data(), d_runs, (size_t)n_runs * sizeof(DpRun), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipMemcpyAsync(groups.data(), d_groups, (size_t)n_groups * sizeof(DevGroupRec), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipMemcpy2DAsync(acc.data(), sizeof(DpAcc), d_acc, sizeof(DpAcc) * ACC_COPIES, sizeof(DpAcc), S, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipMemcpyAsync(misc_h, d_misc, MISC_WORDS * 4, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                T.ms_depth += tm.stop();
-                fin_trace("  pack: depth stage (sync)");
-                rec_base_h = SR.rec_base;
-                if (int rc = check_errors()) return rc;
-                // ---- overlapping mates: the candidates grouped by (sample, name); nothing is edited yet (MSNV_OVERLAP=host: the host pre-pass does it).
-                // The second pass lists them again when msnv_cap_reads has taken reads out: a dropped read is no candidate (sam.c overlap_remove)
-                const bool ovl_on_host = knob::overlap_on_host();
-                bool any_ovl = false;
-                for (size_t s = 0; s < S; ++s) any_ovl |= !MP.ignore_overlaps && acc[s].n_ovl >= 2;
-                if (pass == 1 && !dev_cap.empty()) { n_ovl_reads = 0; n_ovl_groups = 0; }
-                if (any_ovl && !ovl_on_host && (pass == 0 || !dev_cap.empty())) {
-                    tm.start();
-                    if (int rc = o_flag.alloc(NRa * 4)) return rc;
-                    if (int rc = o_rank.alloc(NRa * 4)) return rc;
-                    if (int rc = o_skip.alloc(S)) return rc;
-                    HIP_TRY(hipMemsetAsync(o_skip.p, 0, S, st));
-                    hipLaunchKernelGGL(msnv_ovl_mark, grid_for(NRa, 256), dim3(256), 0, st, TB.r_flags, NR, TB.rec_sample, o_skip.as<uint8_t>(), o_flag.as<uint32_t>());
-                    HIP_TRY(hipGetLastError());
-                    if (int rc = scan32(o_flag.as<uint32_t>(), o_rank.as<uint32_t>(), NRa, false)) return rc;
-                    HIP_TRY(hipMemcpyAsync(&n_ovl_reads, o_rank.as<uint32_t>() + NR, 4, hipMemcpyDeviceToHost, st));
-                    HIP_TRY(hipStreamSynchronize(st));
-                    if (n_ovl_reads >= 2) {
-                        const uint64_t NOa = (uint64_t)n_ovl_reads + 1;
-                        if (int rc = o_keys.alloc(NOa * 8)) return rc;
-                        if (int rc = o_skeys.alloc(NOa * 8)) return rc;
-                        if (int rc = o_vals.alloc(NOa * 4)) return rc;
-                        if (int rc = o_svals.alloc(NOa * 4)) return rc;
-                        hipLaunchKernelGGL(msnv_ovl_list, grid_for(NR, 256), dim3(256), 0, st, TB.r_flags, o_rank.as<uint32_t>(), NR, raw, TB.rec_off, TB.rec_sample, o_skip.as<uint8_t>(),
-                                           o_keys.as<unsigned long long>(), o_vals.as<uint32_t>());
-                        HIP_TRY(hipGetLastError());
-                        if (int rc = sort64(o_keys.as<unsigned long long>(), o_skeys.as<unsigned long long>(), o_vals.as<uint32_t>(), o_svals.as<uint32_t>(), n_ovl_reads, 64u)) return rc;
-                        // groups of equal keys: flags and their scan in the unsorted arrays' memory
-                        uint32_t *gflag = o_vals.as<uint32_t>(), *gid = reinterpret_cast<uint32_t *>(o_keys.p);
-                        hipLaunchKernelGGL(msnv_pair_flags, grid_for(n_ovl_reads, 256), dim3(256), 0, st, o_skeys.as<unsigned long long>(), n_ovl_reads, gflag);
-                        HIP_TRY(hipGetLastError());
-                        if (int rc = scan32(gflag, gid, n_ovl_reads, true)) return rc;
-                        HIP_TRY(hipMemcpyAsync(&n_ovl_groups, gid + (n_ovl_reads - 1), 4, hipMemcpyDeviceToHost, st));
-                        HIP_TRY(hipStreamSynchronize(st));
-                        if (int rc = o_starts.alloc(((uint64_t)n_ovl_groups + 1) * 4)) return rc;
-                        hipLaunchKernelGGL(msnv_ovl_group_starts, grid_for(n_ovl_reads, 256), dim3(256), 0, st, gflag, gid, n_ovl_reads, o_starts.as<uint32_t>());
-                        hipLaunchKernelGGL(msnv_ovl_check, grid_for(n_ovl_groups, 256), dim3(256), 0, st, o_starts.as<uint32_t>(), n_ovl_groups, n_ovl_reads, o_svals.as<uint32_t>(), TB.rec_sample, d_acc);
-                        HIP_TRY(hipGetLastError());
-                        std::vector<DpAcc> again(S);
-                        HIP_TRY(hipMemcpy2DAsync(again.data(), sizeof(DpAcc), d_acc, sizeof(DpAcc) * ACC_COPIES, sizeof(DpAcc), S, hipMemcpyDeviceToHost, st));
-                        HIP_TRY(hipStreamSynchronize(st));
-                        for (size_t s = 0; s < S; ++s) acc[s].need_host = again[s].need_host;
-                    }
-                    T.ms_depth += tm.stop();
-                }
-                if (pass == 1) {
-                    if (!dev_cap.empty()) {
-                        uint32_t cap_fail = 0;
-                        HIP_TRY(hipMemcpy(&cap_fail, d_capfail, 4, hipMemcpyDeviceToHost));
-                        if (cap_fail) return fail(MSNV_EINVAL, "internal: the depth-cap kernel met a read that spans more than its ring holds");
-                    }
-                    break;
-                }
-                // ---- which samples need the sequential edits?  The depth cap and the token limit are kernels (msnv_cap_reads, msnv_token_cut; round 6);
-                // the host pre-pass keeps what they do not take: a template with more alignments than the overlap kernel's slots, an element longer
-                // than the tables can say, a round with far-reaching reads (the cap kernel's ring, the token kernel's window) -- and MSNV_PREPASS=host
-                const bool prepass_on_host = knob::prepass_on_host();      // (read per round: the tests switch it)
-                const bool kernels_can = !prepass_on_host && misc_h[MISC_NOUT] == 0u && span_out == SPAN_OUT && misc_h[MISC_SPAN] <= CAP_RING;
-                std::vector<size_t> need;
-                for (size_t s = 0; s < S; ++s) {
-                    const uint32_t nh = acc[s].need_host;
-                    if ((nh & (NEED_OVL | NEED_BIGC)) || (nh && !kernels_can) || (ovl_on_host && !MP.ignore_overlaps && acc[s].n_ovl >= 2)) need.push_back(s);
-                    else {
-                        if (nh & NEED_CAP) dev_cap.push_back((uint32_t)s);
-                        if (nh & NEED_TOKEN) dev_tok.push_back((uint32_t)s);
-                    }
-                }
-                for (size_t s : need) host_sample[s] = 1;
-                T.n_device_edit_samples += dev_tok.size();
-                for (uint32_t s : dev_cap) if (!(acc[s].need_host & NEED_TOKEN)) T.n_device_edit_samples += 1;
-                if (need.empty() && dev_cap.empty()) break;                // (the token limit alone: the reads msnv_depth2 has listed stand)
-                const double t0 = now_s();
-                T.n_prepass_samples += need.size();
-                std::vector<uint32_t> ovr_all((size_t)NR + 1, 0u);
-                std::vector<std::vector<uint8_t>> host_copy(need.size()), patched(need.size());
-                std::vector<int> rcs(need.size(), 0); std::vector<std::string> msgs(need.size());
-                for (size_t k = 0; k < need.size(); ++k) if (on_device) {
-                    host_copy[k].resize(n_bytes[need[k]]);
-                    if (n_bytes[need[k]]) HIP_TRY(hipMemcpy(host_copy[k].data(), raw + s_beg[need[k]], n_bytes[need[k]], hipMemcpyDeviceToHost));
-                }
-                {
-                    std::atomic<size_t> next{0};
-                    auto w = [&]() {
-                        for (;;) {
-                            const size_t k = next.fetch_add(1);
-                            if (k >= need.size()) break;
-                            const size_t s = need[k];
-                            const uint8_t *rec = on_device ? host_copy[k].data() : streams[s];
-                            std::vector<uint32_t> ov; bool cm = false;
-                            int rc;
-                            try { rc = host_prepass(ds, rec, n_bytes[s], ov, patched[k], cm); } catch (const std::exception &e) { rc = fail_quiet(MSNV_ENOMEM, "host pre-pass: %s", e.what()); }
-                            if (!rc && ov.size() != SR.n_rec[s]) rc = fail_quiet(MSNV_EINVAL, "internal: the host pre-pass saw %zu records, the device scan %u", ov.size(), SR.n_rec[s]);
-                            if (rc) { rcs[k] = rc; msgs[k] = msnv_last_error(); continue; }
-                            std::copy(ov.begin(), ov.end(), ovr_all.begin() + SR.rec_base[s]);
-                            cut_marks[s] = cm ? 1 : 0;
-                        }
-                    };
-                    std::vector<std::thread> th;
-                    const size_t nt = std::min<size_t>(need.size(), msnv_default_threads());
-                    for (size_t k = 0; k < nt; ++k) th.emplace_back(w);
-                    for (auto &x : th) x.join();
-                }
-                for (size_t k = 0; k < need.size(); ++k) if (rcs[k]) return fail(rcs[k], "%s", msgs[k].c_str());
-                for (size_t k = 0; k < need.size(); ++k) if (!patched[k].empty()) HIP_TRY(hipMemcpy(raw + s_beg[need[k]], patched[k].data(), patched[k].size(), hipMemcpyHostToDevice));
-                HIP_TRY(hipMemcpy(d_ovr, ovr_all.data(), ((uint64_t)NR + 1) * 4, hipMemcpyHostToDevice));
-                have_ovr = true;
-                if (!need.empty()) T.wall_prepass_s += now_s() - t0;
-                if (!dev_cap.empty()) {                                    // who enters the pileup of these samples: a wavefront each (into d_ovr, behind the host's verdicts)
-                    DP_BUF(uint32_t, d_caplist, dev_cap.size());
-                    HIP_TRY(hipMemcpyAsync(d_caplist, dev_cap.data(), dev_cap.size() * 4, hipMemcpyHostToDevice, st));
-                    hipLaunchKernelGGL(msnv_cap_reads, dim3((unsigned)dev_cap.size()), dim3(64), 0, st, d_caplist, d_recbase, TB.rd, TB.r_flags, d_depth0, MP.max_depth, d_ovr, d_capfail);
-                    HIP_TRY(hipGetLastError());
-                    HIP_TRY(hipStreamSynchronize(st));                     // (dev_cap's bytes; the second pass takes the pool's buffers back)
-                }
+            if (int rc = prim.inclusive(c_sf, TB.r_rg, (size_t)NR, rocprim::plus<unsigned long long>())) return rc;
+            unsigned long long last = 0;
+            HIP_TRY(hipMemcpyAsync(&last, TB.r_rg + (NR - 1), 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(misc_h, d_misc, MISC_WORDS * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            n_runs = (uint32_t)(last >> 32); n_groups = (uint32_t)last;
+        }
+        in_order = misc_h[MISC_SORT] != 0 || knob::tile_order_sort();      // (the tile order's route: the depth kernel writes the pieces' depths at their header slots)
+        totals_h = tot_c;
+        HIP_TRY(hipMemcpyAsync(TB.r_pre + NR, &totals_h, sizeof(RecCnt), hipMemcpyHostToDevice, st));
+        if (int rc = take_run_group_tables()) return rc;
+        if (int rc = alloc_round_buffers()) return rc;
+        // (the groups' first records: this route has no table of them yet -- the depth kernel writes it, the places follow, then the depths)
+        hipLaunchKernelGGL(msnv_group_firsts, grid_for(NR, 256), dim3(256), 0, st, NR, TB.r_flags, TB.r_rg, d_runfirst, d_grpfirst);
+        hipLaunchKernelGGL(msnv_group_pre2, grid_for((uint64_t)n_groups + 1, 256), dim3(256), 0, st, n_groups, NR, d_grpfirst, TB.r_pre, d_grppre);
+        HIP_TRY(hipGetLastError());
+        if (int rc = launch_depth_stage(st)) return rc;
+        hipLaunchKernelGGL(msnv_acc_fold, dim3((unsigned)S), dim3(64), 0, st, d_acc, (uint32_t)S);
+        HIP_TRY(hipGetLastError());
+        runs.resize(n_runs); groups.resize(n_groups);
+        HIP_TRY(hipMemcpyAsync(runs.data(), d_runs, (size_t)n_runs * sizeof(DpRun), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(groups.data(), d_groups, (size_t)n_groups * sizeof(DevGroupRec), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpy2DAsync(acc.data(), sizeof(DpAcc), d_acc, sizeof(DpAcc) * ACC_COPIES, sizeof(DpAcc), S, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(misc_h, d_misc, MISC_WORDS * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        T.ms_depth += tm.stop();
+        fin_trace("  pack: depth stage (sync)");
+        rec_base_h = SR.rec_base;
+        return check_errors();
+    }
+    // ---- overlapping mates: the candidates grouped by (sample, name); nothing is edited yet (MSNV_OVERLAP=host: the host pre-pass does it).
+    // The second pass lists them again when msnv_cap_reads has taken reads out: a dropped read is no candidate (sam.c overlap_remove).
+    // Leaves: n_ovl_reads, n_ovl_groups, o_starts / o_svals (the groups), o_skip; need_host of samples whose templates overflow the slots.
+    int list_overlaps(int pass, bool ovl_on_host) {
+        const uint64_t NRa = (uint64_t)NR + 1;
+        bool any_ovl = false;
+        for (size_t s = 0; s < S; ++s) any_ovl |= !MP.ignore_overlaps && acc[s].n_ovl >= 2;
+        if (pass == 1 && !dev_cap.empty()) { n_ovl_reads = 0; n_ovl_groups = 0; }
+        if (!any_ovl || ovl_on_host || (pass == 1 && dev_cap.empty())) return MSNV_OK;
+        tm.start();
+        if (int rc = o_flag.alloc(NRa * 4)) return rc;
+        if (int rc = o_rank.alloc(NRa * 4)) return rc;
+        if (int rc = o_skip.alloc(S)) return rc;
+        HIP_TRY(hipMemsetAsync(o_skip.p, 0, S, st));
+        hipLaunchKernelGGL(msnv_ovl_mark, grid_for(NRa, 256), dim3(256), 0, st, TB.r_flags, NR, TB.rec_sample, o_skip.as<uint8_t>(), o_flag.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        if (int rc = prim.scan32(o_flag.as<uint32_t>(), o_rank.as<uint32_t>(), NRa, false)) return rc;
+        HIP_TRY(hipMemcpyAsync(&n_ovl_reads, o_rank.as<uint32_t>() + NR, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (n_ovl_reads >= 2) {
+            const uint64_t NOa = (uint64_t)n_ovl_reads + 1;
+            if (int rc = o_keys.alloc(NOa * 8)) return rc;
+            if (int rc = o_skeys.alloc(NOa * 8)) return rc;
+            if (int rc = o_vals.alloc(NOa * 4)) return rc;
+            if (int rc = o_svals.alloc(NOa * 4)) return rc;
+            hipLaunchKernelGGL(msnv_ovl_list, grid_for(NR, 256), dim3(256), 0, st, TB.r_flags, o_rank.as<uint32_t>(), NR, raw, TB.rec_off, TB.rec_sample, o_skip.as<uint8_t>(),
+                               o_keys.as<unsigned long long>(), o_vals.as<uint32_t>());
+            HIP_TRY(hipGetLastError());
+            if (int rc = prim.sort64(o_keys.as<unsigned long long>(), o_skeys.as<unsigned long long>(), o_vals.as<uint32_t>(), o_svals.as<uint32_t>(), n_ovl_reads, 64u)) return rc;
+            // groups of equal keys: flags and their scan in the unsorted arrays' memory
+            uint32_t *gflag = o_vals.as<uint32_t>(), *gid = reinterpret_cast<uint32_t *>(o_keys.p);
+            hipLaunchKernelGGL(msnv_pair_flags, grid_for(n_ovl_reads, 256), dim3(256), 0, st, o_skeys.as<unsigned long long>(), n_ovl_reads, gflag);
+            HIP_TRY(hipGetLastError());
+            if (int rc = prim.scan32(gflag, gid, n_ovl_reads, true)) return rc;
+            HIP_TRY(hipMemcpyAsync(&n_ovl_groups, gid + (n_ovl_reads - 1), 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (int rc = o_starts.alloc(((uint64_t)n_ovl_groups + 1) * 4)) return rc;
+            hipLaunchKernelGGL(msnv_ovl_group_starts, grid_for(n_ovl_reads, 256), dim3(256), 0, st, gflag, gid, n_ovl_reads, o_starts.as<uint32_t>());
+            hipLaunchKernelGGL(msnv_ovl_check, grid_for(n_ovl_groups, 256), dim3(256), 0, st, o_starts.as<uint32_t>(), n_ovl_groups, n_ovl_reads, o_svals.as<uint32_t>(), TB.rec_sample, d_acc);
+            HIP_TRY(hipGetLastError());
+            std::vector<DpAcc> again(S);
+            HIP_TRY(hipMemcpy2DAsync(again.data(), sizeof(DpAcc), d_acc, sizeof(DpAcc) * ACC_COPIES, sizeof(DpAcc), S, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            for (size_t s = 0; s < S; ++s) acc[s].need_host = again[s].need_host;
+        }
+        T.ms_depth += tm.stop();
+        return MSNV_OK;
+    }
+    // ---- which samples need the sequential edits?  The depth cap and the token limit are kernels (msnv_cap_reads, msnv_token_cut; round 6);
+    // the host pre-pass keeps what they do not take: a template with more alignments than the overlap kernel's slots, an element longer
+    // than the tables can say, a round with far-reaching reads (the cap kernel's ring, the token kernel's window) -- and MSNV_PREPASS=host.
+    // Leaves: dev_cap, dev_tok, host_sample; `second_pass` when a verdict changes who enters the pileup (d_ovr then holds the verdicts).
+    int sequential_edits(bool ovl_on_host, bool &second_pass) {
+        const bool prepass_on_host = knob::prepass_on_host();      // (read per round: the tests switch it)
+        const bool kernels_can = !prepass_on_host && misc_h[MISC_NOUT] == 0u && span_out == SPAN_OUT && misc_h[MISC_SPAN] <= CAP_RING;
+        std::vector<size_t> need;
+        for (size_t s = 0; s < S; ++s) {
+            const uint32_t nh = acc[s].need_host;
+            if ((nh & (NEED_OVL | NEED_BIGC)) || (nh && !kernels_can) || (ovl_on_host && !MP.ignore_overlaps && acc[s].n_ovl >= 2)) need.push_back(s);
+            else {
+                if (nh & NEED_CAP) dev_cap.push_back((uint32_t)s);
+                if (nh & NEED_TOKEN) dev_tok.push_back((uint32_t)s);
             }
         }
-        const uint64_t NB = ((uint64_t)NR + PB - 1) / PB;
+        for (size_t s : need) host_sample[s] = 1;
+        T.n_device_edit_samples += dev_tok.size();
+        for (uint32_t s : dev_cap) if (!(acc[s].need_host & NEED_TOKEN)) T.n_device_edit_samples += 1;
+        second_pass = !need.empty() || !dev_cap.empty();           // (the token limit alone: the reads msnv_depth2 has listed stand)
+        if (!second_pass) return MSNV_OK;
+        if (int rc = host_prepass_samples(need)) return rc;
+        if (!dev_cap.empty()) {                                    // who enters the pileup of these samples: a wavefront each (into d_ovr, behind the host's verdicts)
+            auto *d_caplist = pool.take<uint32_t>(dev_cap.size());
+            if (pool.rc) return pool.rc;
+            HIP_TRY(hipMemcpyAsync(d_caplist, dev_cap.data(), dev_cap.size() * 4, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(msnv_cap_reads, dim3((unsigned)dev_cap.size()), dim3(64), 0, st, d_caplist, d_recbase, TB.rd, TB.r_flags, d_depth0, MP.max_depth, d_ovr, d_capfail);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(st));                     // (dev_cap's bytes; the second pass takes the pool's buffers back)
+        }
+        return MSNV_OK;
+    }
+    // pack.cpp: host_prepass over the samples of `need`, on host threads; its verdicts per record go up into d_ovr (zeros for everyone else),
+    // the records it patched back into the streams.  Blocking copies only.
+    int host_prepass_samples(const std::vector<size_t> &need) {
+        const double t0 = now_s();
+        T.n_prepass_samples += need.size();
+        std::vector<uint32_t> ovr_all((size_t)NR + 1, 0u);
+        std::vector<std::vector<uint8_t>> host_copy(need.size()), patched(need.size());
+        std::vector<int> rcs(need.size(), 0); std::vector<std::string> msgs(need.size());
+        for (size_t k = 0; k < need.size(); ++k) if (on_device) {
+            host_copy[k].resize(n_bytes[need[k]]);
+            if (n_bytes[need[k]]) HIP_TRY(hipMemcpy(host_copy[k].data(), raw + SR.s_beg[need[k]], n_bytes[need[k]], hipMemcpyDeviceToHost));
+        }
+        {
+            std::atomic<size_t> next{0};
+            auto w = [&]() {
+                for (;;) {
+                    const size_t k = next.fetch_add(1);
+                    if (k >= need.size()) break;
+                    const size_t s = need[k];
+                    const uint8_t *rec = on_device ? host_copy[k].data() : streams[s];
+                    std::vector<uint32_t> ov; bool cm = false;
+                    int rc;
+                    try { rc = host_prepass(ds, rec, n_bytes[s], ov, patched[k], cm); } catch (const std::exception &e) { rc = fail_quiet(MSNV_ENOMEM, "host pre-pass: %s", e.what()); }
+                    if (!rc && ov.size() != SR.n_rec[s]) rc = fail_quiet(MSNV_EINVAL, "internal: the host pre-pass saw %zu records, the device scan %u", ov.size(), SR.n_rec[s]);
+                    if (rc) { rcs[k] = rc; msgs[k] = msnv_last_error(); continue; }
+                    std::copy(ov.begin(), ov.end(), ovr_all.begin() + SR.rec_base[s]);
+                    cut_marks[s] = cm ? 1 : 0;
+                }
+            };
+            std::vector<std::thread> th;
+            const size_t nt = std::min<size_t>(need.size(), msnv_default_threads());
+            for (size_t k = 0; k < nt; ++k) th.emplace_back(w);
+            for (auto &x : th) x.join();
+        }
+        for (size_t k = 0; k < need.size(); ++k) if (rcs[k]) return fail(rcs[k], "%s", msgs[k].c_str());
+        for (size_t k = 0; k < need.size(); ++k) if (!patched[k].empty()) HIP_TRY(hipMemcpy(raw + SR.s_beg[need[k]], patched[k].data(), patched[k].size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_ovr, ovr_all.data(), ((uint64_t)NR + 1) * 4, hipMemcpyHostToDevice));
+        have_ovr = true;
+        if (!need.empty()) T.wall_prepass_s += now_s() - t0;
+        return MSNV_OK;
+    }
 
-        // ================================================================ overlapping mates: the qualities of the pairs are edited where they lie
+    // Takes: the careful front's groups and lists.  Leaves: the qualities of overlapping mates edited where they lie (msnv_ovl_groups), then
+    // snpCall's token limit: the bases behind the cut get their mark (behind the mates' edits: the -Q test sees them).
+    int edit_qualities() {
         if (n_ovl_groups) {
             tm.start();
             HIP_TRY(hipMemcpyAsync(o_skip.p, host_sample.data(), S, hipMemcpyHostToDevice, st));
@@ -3380,12 +3459,12 @@ int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *stre
             HIP_TRY(hipGetLastError());
             T.ms_depth += tm.stop();
         }
-        // ================================================================ snpCall's token limit: the bases behind the cut get their mark (behind the mates' edits: the -Q test sees them)
         if (!dev_tok.empty()) {
             tm.start();
             std::vector<uint8_t> tk(S, 0);
             for (uint32_t s : dev_tok) { tk[s] = 1; cut_marks[s] = 1; }
-            DP_BUF(uint8_t, d_tok, S);
+            auto *d_tok = pool.take<uint8_t>(S);
+            if (pool.rc) return pool.rc;
             HIP_TRY(hipMemcpyAsync(d_tok, tk.data(), S, hipMemcpyHostToDevice, st));
             hipLaunchKernelGGL(msnv_token_clamp, grid_for((uint64_t)NR * 64u, 256), dim3(256), 0, st, d_tok, TB.rec_sample, TB.r_flags, NR, raw, TB.rec_off);
             hipLaunchKernelGGL(msnv_token_cut, dim3(4096), dim3(256), 0, st, d_hot, d_hotn, d_tok, d_recbase, TB.rd, TB.r_flags, raw, TB.rec_off, d_misc + MISC_SPAN, P);
@@ -3393,23 +3472,27 @@ int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *stre
             HIP_TRY(hipStreamSynchronize(st));                             // (tk's bytes)
             T.ms_depth += tm.stop();
         }
-        if (route == 1) fin_trace("  pack: checks, overlaps");
+        fin_trace("  pack: checks, overlaps");
+        return MSNV_OK;
+    }
 
-        // ================================================================ layout + emit (both routes)
-        const uint64_t NPCa = (uint64_t)NPC + 1;
+    // ================================================================ layout + emit (both routes)
+    // Takes: a front's tables and buffers.  Leaves: msnv_sample_layout, the emit kernels and the fold RUNNING (T.pending), and on their way
+    // into the dataset's pinned words what the host needs of the stages so far, with an event behind the copies (evh; the quick route's depth
+    // stage: evd2).  The emit kernels are launched first, THEN collect() waits for the events.  Does not wait (but for the FASTA thread).
+    int launch_emit() {
+        const uint64_t NB = ((uint64_t)NR + PB - 1) / PB;
         HIP_TRY(hipMemcpyAsync(d_cut, cut_marks.data(), S, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemsetAsync(d_slow, 0, 4, st));
         hipLaunchKernelGGL(msnv_sample_layout, dim3(1), dim3(256), 0, st, d_recbase, (uint32_t)S, TB.r_pre, d_acc, TB.rd, r_seq, r_qual, d_cut, d_sum, d_ss0, d_dst, d_pb);
         HIP_TRY(hipGetLastError());
-        // ---- what the host needs of the stages so far, through the dataset's pinned words, with an event behind the copies: the emit kernels
-        // are launched first, THEN the host waits for the event -- and builds its tables beside them
         const uint64_t b_acc = S * sizeof(DpAcc), b_sum = (S + 1) * sizeof(DpSampleSum2), b_pb = S * 8, b_rb = (S + 1) * 4, b_runs = (uint64_t)n_runs * sizeof(DpRun), b_grp = (uint64_t)n_groups * sizeof(DevGroupRec);
         auto up8 = [](uint64_t v) { return (v + 15) & ~15ull; };
-        const uint64_t o_acc = up8(((uint64_t)ds.samples.size() + 16) * 4), o_sum = o_acc + up8(b_acc), o_pb = o_sum + up8(b_sum), o_rb = o_pb + up8(b_pb), o_misc = o_rb + up8(b_rb), o_runs = o_misc + 16, o_grp = o_runs + up8(b_runs),
-                       o_end = o_grp + up8(b_grp);
+        o_acc = up8(((uint64_t)ds.samples.size() + 16) * 4); o_sum = o_acc + up8(b_acc); o_pb = o_sum + up8(b_sum); o_rb = o_pb + up8(b_pb); o_misc = o_rb + up8(b_rb); o_runs = o_misc + 16; o_grp = o_runs + up8(b_runs);
+        const uint64_t o_end = o_grp + up8(b_grp);
         if (int rc = pin_ensure(ds, std::max<uint64_t>(o_end, S * sizeof(DpAcc)))) return rc;
-        uint8_t *pinb = static_cast<uint8_t *>(T.pin) + T.pin_cap / 2;
-        if (route == 0) {
+        pinb = static_cast<uint8_t *>(T.pin) + T.pin_cap / 2;
+        if (quick) {
             const bool depth_on_main = knob::depth_on_main();
             hipStream_t st2 = depth_on_main ? st : (hipStream_t)ds.ctx->stream2;          // (behind the depth stage: its stream)
             HIP_TRY(hipMemcpy2DAsync(pinb + o_acc, sizeof(DpAcc), d_acc, sizeof(DpAcc) * ACC_COPIES, sizeof(DpAcc), S, hipMemcpyDeviceToHost, st2));
@@ -3442,7 +3525,7 @@ int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *stre
         }
         hipLaunchKernelGGL(msnv_emit_tail, dim3((unsigned)S), dim3(64), 0, st, d_dst, d_pb, (uint32_t)S, P);
         if (knob::debug_sync()) { HIP_TRY(hipStreamSynchronize(st)); fin_trace("  dbg: emit_tail"); }
-        if (route == 0) HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)T.pending.evd2, 0));      // (the depth stage's last words into the accumulators: in front of their fold)
+        if (quick) HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)T.pending.evd2, 0));      // (the depth stage's last words into the accumulators: in front of their fold)
         hipLaunchKernelGGL(msnv_acc_fold, dim3((unsigned)S), dim3(64), 0, st, d_acc, (uint32_t)S);
         HIP_TRY(hipGetLastError());
         // The round's last kernels are left RUNNING: nothing the host still has to do for this round -- its (sample, tile) pairs, its tables --
@@ -3451,66 +3534,78 @@ int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *stre
         HIP_TRY(hipMemcpy2DAsync(T.pin, sizeof(DpAcc), d_acc, sizeof(DpAcc) * ACC_COPIES, sizeof(DpAcc), S, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipEventRecord((hipEvent_t)T.pending.ev1, st));
         T.pending.active = true; T.pending.first = first; T.pending.n = S;
+        return MSNV_OK;
+    }
 
-        // ---- the host's share: wait for the small results (not for the emit kernels), look at them
+    // the round is not to be: nothing stays pending, and its kernels have run before anyone frees what they write into
+    int withdraw() { T.pending.active = false; HIP_TRY(hipStreamSynchronize(st)); return MSNV_OK; }
+
+    // ---- the host's share.  Takes: the pinned words.  Waits for the small results (evh, evd2), not for the emit kernels, and looks at them.
+    // Leaves: sum, piece_bytes (quick: acc, rec_base_h, misc_h, runs, groups too) on the host; the round's buffers the dataset's.  Or
+    // TO_CAREFUL (quick route only): the round withdrawn, `held` still holding its buffers for the next route to drop.
+    int collect() {
         HIP_TRY(hipEventSynchronize((hipEvent_t)T.pending.evh));
-        if (route == 0) HIP_TRY(hipEventSynchronize((hipEvent_t)T.pending.evd2));
+        if (quick) HIP_TRY(hipEventSynchronize((hipEvent_t)T.pending.evd2));
         fin_trace("  pack: depth stage, layout (wait)");
-        memcpy(sum.data(), pinb + o_sum, b_sum);
-        memcpy(piece_bytes.data(), pinb + o_pb, b_pb);
-        if (route == 0) {
-            memcpy(acc.data(), pinb + o_acc, b_acc);
-            rec_base_h.assign(S + 1, 0); memcpy(rec_base_h.data(), pinb + o_rb, b_rb);
+        memcpy(sum.data(), pinb + o_sum, (S + 1) * sizeof(DpSampleSum2));
+        memcpy(piece_bytes.data(), pinb + o_pb, S * 8);
+        if (quick) {
+            memcpy(acc.data(), pinb + o_acc, S * sizeof(DpAcc));
+            rec_base_h.assign(S + 1, 0); memcpy(rec_base_h.data(), pinb + o_rb, (S + 1) * 4);
             memcpy(misc_h, pinb + o_misc, MISC_WORDS * 4);
             runs.resize(n_runs); groups.resize(n_groups);
-            if (n_runs) memcpy(runs.data(), pinb + o_runs, b_runs);
-            if (n_groups) memcpy(groups.data(), pinb + o_grp, b_grp);
+            if (n_runs) memcpy(runs.data(), pinb + o_runs, (size_t)n_runs * sizeof(DpRun));
+            if (n_groups) memcpy(groups.data(), pinb + o_grp, (size_t)n_groups * sizeof(DevGroupRec));
             // what the quick route could not know when it launched the emit kernels: an error (reported), or something only the careful route
             // handles -- a sample that needs the host pre-pass (depth cap, token limit), more far-reaching reads than the list holds, two
             // overhanging contigs in one sub-segment.  The round is taken back (the kernels that still write into its buffers are waited for)
             bool again = misc_h[MISC_NOUT] > CAP_OUT || misc_h[MISC_OVERHANG] == 2u;
             for (size_t s = 0; s < S; ++s) again |= acc[s].need_host != 0;
-            int rc_err = check_errors();
+            const int rc_err = check_errors();
             if (rc_err || again) {
-                T.pending.active = false;
-                HIP_TRY(hipStreamSynchronize(st));
+                if (int rc = withdraw()) return rc;
                 if (rc_err) return rc_err;
-                route = 1; T.n_quick_redone += 1;
-                continue;                                              // (`held` gives the buffers back)
+                T.n_quick_redone += 1;
+                return TO_CAREFUL;
             }
         }
         if (misc_h[MISC_OVERHANG]) T.any_overhang_h = true;
         for (size_t s = 0; s < S; ++s)
-            if (piece_bytes[s] > 0xffffff00ull) { T.pending.active = false; HIP_TRY(hipStreamSynchronize(st)); return fail(MSNV_EDOMAIN, "one sample holds more than 8.5 G aligned bases in this shard: shard the contigs further"); }
+            if (piece_bytes[s] > 0xffffff00ull) { if (int rc = withdraw()) return rc; return fail(MSNV_EDOMAIN, "one sample holds more than 8.5 G aligned bases in this shard: shard the contigs further"); }
         keep.seq_total = sum[S].seq_off;
         T.n_pieces += NPC; T.n_records += NR;
         T.pad_in_emit = true;                                          // (msnv_emit_block* leave the alignment nibbles behind every piece as finalize wants them)
         T.round_bufs.push_back(held.round_buf); held.round_buf = nullptr;
         held.keep_buf = nullptr;                                       // (the dataset's from here on)
         T.rounds.push_back(keep);
-        if (in_order) if (int rc = devpack_sync_pending(ds)) return rc;      // (the general tile-order route below waits for its sort anyway)
+        if (in_order) if (int rc = devpack_sync_pending(ds)) return rc;      // (the general tile-order route of tile_pairs() waits for its sort anyway)
         fin_trace("  pack: emit launched, results in");
+        return MSNV_OK;
+    }
 
-        // ---- the (sample, contig, tile) runs of pieces = the pairs of the tile index
+    // ---- the (sample, contig, tile) runs of pieces = the pairs of the tile index.  Takes: the headers (in_order: work buffers, emitted) or the
+    // groups on the host.  Leaves: `prec` -- the sort route's still on its way down (publish() waits), the headers in tile order in `keep`.
+    int tile_pairs() {
         if (in_order) tm.start();
-        std::vector<DevPairRec> prec;
         if (NPC >= 1 && in_order) {
             // the general route: stable sort of the headers by (sample, contig, tile), runs of equal keys
-            DP_BUF(unsigned long long, d_tk, NPCa);
-            DP_BUF(uint32_t, d_ix, NPCa);
-            DP_BUF(uint32_t, d_uns, 4);
+            const uint64_t NPCa = (uint64_t)NPC + 1;
+            auto *d_tk = pool.take<unsigned long long>(NPCa);
+            auto *d_ix = pool.take<uint32_t>(NPCa);
+            auto *d_uns = pool.take<uint32_t>(4);
+            if (pool.rc) return pool.rc;
             HIP_TRY(hipMemsetAsync(d_uns, 0, 4, st));
             const unsigned tid_bits = std::max(1u, bit_width_u64(NC ? NC - 1 : 0));
             hipLaunchKernelGGL(msnv_tile_keys, grid_for(NPC, 256), dim3(256), 0, st, w_hdr, w_tid, d_dst, (uint32_t)S, NPC, tid_bits, d_tk, d_ix, d_uns);
             HIP_TRY(hipGetLastError());
-            uint32_t uns = 0;
-            HIP_TRY(hipMemcpyAsync(&uns, d_uns, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(&uns_h, d_uns, 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             const unsigned long long *skeys = d_tk;
-            DP_BUF(unsigned long long, d_tk2, NPCa);
-            DP_BUF(uint32_t, d_ix2, NPCa);
-            if (uns) {
-                if (int rc = sort64(d_tk, d_tk2, d_ix, d_ix2, NPC, 21u + tid_bits + std::max(1u, bit_width_u64(S - 1)))) return rc;
+            auto *d_tk2 = pool.take<unsigned long long>(NPCa);
+            auto *d_ix2 = pool.take<uint32_t>(NPCa);
+            if (pool.rc) return pool.rc;
+            if (uns_h) {
+                if (int rc = prim.sort64(d_tk, d_tk2, d_ix, d_ix2, NPC, 21u + tid_bits + std::max(1u, bit_width_u64(S - 1)))) return rc;
                 hipLaunchKernelGGL(msnv_gather_pieces, grid_for(NPC, 256), dim3(256), 0, st, d_ix2, NPC, w_hdr, w_tid, w_end, w_depth, keep.hdr, keep.tid, keep.end, keep.depth);
                 HIP_TRY(hipGetLastError());
                 skeys = d_tk2;
@@ -3521,13 +3616,14 @@ int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *stre
                 HIP_TRY(hipMemcpyAsync(keep.depth, w_depth, (size_t)NPC * 2, hipMemcpyDeviceToDevice, st));
             }
             // runs of equal keys (d_ix / d_ix2 are free again: flags and their scan)
-            uint32_t n_pairs = 0;
             hipLaunchKernelGGL(msnv_pair_flags, grid_for(NPC, 256), dim3(256), 0, st, skeys, NPC, d_ix);
             HIP_TRY(hipGetLastError());
-            if (int rc = scan32(d_ix, d_ix2, NPC, true)) return rc;
-            HIP_TRY(hipMemcpyAsync(&n_pairs, d_ix2 + (NPC - 1), 4, hipMemcpyDeviceToHost, st));
+            if (int rc = prim.scan32(d_ix, d_ix2, NPC, true)) return rc;
+            HIP_TRY(hipMemcpyAsync(&n_pairs_h, d_ix2 + (NPC - 1), 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-            DP_BUF(DevPairRec, d_prec, (uint64_t)n_pairs + 1);
+            const uint32_t n_pairs = n_pairs_h;
+            auto *d_prec = pool.take<DevPairRec>((uint64_t)n_pairs + 1);
+            if (pool.rc) return pool.rc;
             hipLaunchKernelGGL(msnv_pair_starts, grid_for(NPC, 256), dim3(256), 0, st, skeys, d_ix, d_ix2, NPC, tid_bits, d_prec);
             hipLaunchKernelGGL(msnv_pair_maxd, grid_for(n_pairs, 64), dim3(64), 0, st, d_prec, n_pairs, NPC, keep.depth);
             HIP_TRY(hipGetLastError());
@@ -3545,9 +3641,12 @@ int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *stre
             }
         }
         if (in_order) T.ms_sort += tm.stop();                          // (the counting route is host work on the groups: nothing to wait for)
-
         fin_trace("  pack: pairs");
-        // ---- what the host keeps of a sample: its summaries and its (contig, tile) runs
+        return MSNV_OK;
+    }
+
+    // ---- what the host keeps of a sample: its summaries and its (contig, tile) runs.  Takes: acc, sum, piece_bytes, prec, runs.
+    int publish() {
         const double t_dl = now_s();
         const int32_t round_no = (int32_t)T.rounds.size() - 1;
         for (size_t s = 0; s < S; ++s) {
@@ -3594,10 +3693,41 @@ int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *stre
         }
         T.wall_download_s += now_s() - t_dl;
         fin_trace("  pack: host tables");
-        break;
+        return MSNV_OK;
     }
-#undef DP_BUF
-    return MSNV_OK;
+};
+}  // namespace
+
+// The driver of a round: the quick route when it may try, the careful route for what it hands back (or for everything), the common tail.
+// Which work is queued before which wait is each stage's header comment; a stage that answers TO_CAREFUL has left nothing running.
+int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *streams, const uint64_t *n_bytes, int n, bool on_device, const uint8_t *in_place_base, uint64_t in_place_capacity) {
+    (void)in_place_capacity;                                       // (api.cpp has checked the streams against it)
+    if (n <= 0) return MSNV_OK;
+    if (n > 2048) return fail(MSNV_EINVAL, "internal: a device-pack round holds at most 2048 samples");
+    if (!ds.ctx) return fail(MSNV_ENODEV, "the device pack needs a device context");
+    if (int rc = dev_set_device(ds.ctx->device)) return rc;
+    fin_trace_reset();
+    if (int rc = devpack_sync_pending(ds)) return rc;              // (the round before may still be writing: its work buffers are this round's)
+    fin_trace("  pack: enter");
+    if (int rc = build_contigs(ds)) return rc;
+    fin_trace("  pack: contigs");
+    Round R(ds, first, streams, n_bytes, n, on_device, in_place_base);
+    if (int rc = R.stage()) return rc;
+    int rc = TO_CAREFUL;
+    if (R.quick_possible) {
+        rc = R.front_quick();
+        if (!rc) rc = R.launch_emit();
+        if (!rc) rc = R.collect();
+    }
+    if (rc == TO_CAREFUL) {
+        rc = R.front_careful();
+        if (!rc) rc = R.edit_qualities();
+        if (!rc) rc = R.launch_emit();
+        if (!rc) rc = R.collect();
+    }
+    if (!rc) rc = R.tile_pairs();
+    if (!rc) rc = R.publish();
+    return rc;
 }
 
 // The headers and intervals of the device-packed samples as host staging (SampleCols::hdr / tid / end / depth / cov_*): what the host
@@ -3657,40 +3787,13 @@ int devpack_copy_columns(const SampleCols &sc, uint8_t *dst_seq, uint8_t *dst_qu
 // The per-piece and per-interval parts of finalize_dataset (pack.cpp) for a dataset whose samples were all packed here: the headers and
 // intervals never leave HBM; the host works on (sample, tile) pairs only.  Every function mirrors the host loop named beside it and
 // produces the same bytes (tests/test_gpu_devpack.py compares every table of the two builds).
+int Prim::scan64(const uint32_t *in, unsigned long long *out, size_t n) { return exclusive(in, out, 0ull, n, rocprim::plus<unsigned long long>()); }
+int Prim::reserve_scan32(size_t n) {
+    size_t need = 0;
+    if (int rc = exclusive((const uint32_t *)nullptr, (uint32_t *)nullptr, 0u, n, rocprim::plus<uint32_t>(), &need)) return rc;
+    return room(need + 256);
+}
 namespace {
-struct Prim {                        // rocPRIM calls with a grow-only temporary buffer
-    hipStream_t st; DevBuf tmp; size_t cap = 0;
-    explicit Prim(hipStream_t s) : st(s) {}
-    int room(size_t need) { if (need > cap) { if (int rc = tmp.alloc(need)) return rc; cap = need; } return MSNV_OK; }
-    int reserve_scan32(size_t n) {          // room for scans of up to n words before the first launch: growing later frees, and a free waits for the device
-        size_t need = 0;
-        HIP_TRY(rocprim::exclusive_scan(nullptr, need, (const uint32_t *)nullptr, (uint32_t *)nullptr, 0u, n, rocprim::plus<uint32_t>(), st));
-        return room(need + 256);
-    }
-    int scan32(const uint32_t *in, uint32_t *out, size_t n, bool inclusive) {
-        size_t need = 0;
-        if (inclusive) HIP_TRY(rocprim::inclusive_scan(nullptr, need, in, out, n, rocprim::plus<uint32_t>(), st));
-        else HIP_TRY(rocprim::exclusive_scan(nullptr, need, in, out, 0u, n, rocprim::plus<uint32_t>(), st));
-        if (int rc = room(need)) return rc;
-        if (inclusive) HIP_TRY(rocprim::inclusive_scan(tmp.p, need, in, out, n, rocprim::plus<uint32_t>(), st));
-        else HIP_TRY(rocprim::exclusive_scan(tmp.p, need, in, out, 0u, n, rocprim::plus<uint32_t>(), st));
-        return MSNV_OK;
-    }
-    int scan64(const uint32_t *in, unsigned long long *out, size_t n) {
-        size_t need = 0;
-        HIP_TRY(rocprim::exclusive_scan(nullptr, need, in, out, 0ull, n, rocprim::plus<unsigned long long>(), st));
-        if (int rc = room(need)) return rc;
-        HIP_TRY(rocprim::exclusive_scan(tmp.p, need, in, out, 0ull, n, rocprim::plus<unsigned long long>(), st));
-        return MSNV_OK;
-    }
-    int sort64(unsigned long long *kin, unsigned long long *kout, uint32_t *vin, uint32_t *vout, size_t n, unsigned end_bit) {
-        size_t need = 0;
-        HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, kin, kout, vin, vout, n, 0u, end_bit, st));
-        if (int rc = room(need)) return rc;
-        HIP_TRY(rocprim::radix_sort_pairs(tmp.p, need, kin, kout, vin, vout, n, 0u, end_bit, st));
-        return MSNV_OK;
-    }
-};
 
 __global__ void msnv_fin_headers(const ReadHdr *src, const int32_t *tid, unsigned long long n, const uint32_t *tile_base, ReadHdr *dst) {
     const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -4041,12 +4144,10 @@ int devfin_chunks_launch(msnv_dataset &ds, DeviceCols &d, const std::vector<uint
     HIP_TRY(hipGetLastError());
     {
         // (rocPRIM's temporary storage outlives this call: the scan is only queued)
-        size_t need = 0;
-        HIP_TRY(rocprim::exclusive_scan(nullptr, need, cnt, scan, 0u, n + 1, rocprim::plus<uint32_t>(), st));
-        void *tmp = nullptr;
-        if (int rc = dev_alloc(&tmp, need + 256, nullptr)) return rc;
-        T.fin_keep.push_back(tmp);
-        HIP_TRY(rocprim::exclusive_scan(tmp, need, cnt, scan, 0u, n + 1, rocprim::plus<uint32_t>(), st));
+        Prim pr(st);
+        const int rc = pr.exclusive(cnt, scan, 0u, n + 1, rocprim::plus<uint32_t>());
+        if (pr.own.p) T.fin_keep.push_back(pr.own.release());
+        if (rc) return rc;
     }
     hipLaunchKernelGGL(msnv_fin_chunks<true>, grid_for(n * 64, 256), dim3(256), 0, st, d.pairs, list, (uint32_t)n, s_hdr, (const unsigned long long *)d.s_read_base,
                        (const unsigned long long *)d.s_seq_base, nullptr, scan, d.chunks + base, d.hdr4, (uint32_t)std::min<uint64_t>(cap, 0xffffffffull));
@@ -4253,7 +4354,7 @@ int devfin_coverage_launch(msnv_dataset &ds, DeviceCols &d) {
     // behind these run while the host builds the coverage pair tables (round 6)
     if (!T.cov_event) { hipEvent_t e = nullptr; HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); T.cov_event = e; }
     HIP_TRY(hipEventRecord((hipEvent_t)T.cov_event, st));
-    T.cov_tmp = pr.tmp.release();                                  // (rocPRIM's work memory: in use until the kernels above have run)
+    T.cov_tmp = pr.own.release();                                  // (rocPRIM's work memory: in use until the kernels above have run)
     T.cov_launched = true;
     return MSNV_OK;
 }
@@ -4406,7 +4507,7 @@ int devfin_coverage(msnv_dataset &ds, DeviceCols &d, std::vector<uint64_t> &cvba
         size_t need = 0;
         HIP_TRY(rocprim::reduce(nullptr, need, ntile, tot.as<unsigned long long>(), 0ull, (size_t)N, rocprim::plus<unsigned long long>(), st));
         if (int rc = pr.room(need)) return rc;
-        HIP_TRY(rocprim::reduce(pr.tmp.p, need, ntile, tot.as<unsigned long long>(), 0ull, (size_t)N, rocprim::plus<unsigned long long>(), st));
+        HIP_TRY(rocprim::reduce(pr.buf, need, ntile, tot.as<unsigned long long>(), 0ull, (size_t)N, rocprim::plus<unsigned long long>(), st));
         HIP_TRY(hipMemcpyAsync(&n_ent64, tot.p, 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }

@@ -70,7 +70,7 @@ inline bool scan_segments() { return first("MSNV_SCAN") == 's'; }
 // MSNV_FRONT=careful: a round takes the stage-by-stage route, not the one-walk route.  Per call (tests/test_gpu_devpack.py).
 inline bool front_careful() { return first("MSNV_FRONT") == 'c'; }
 // MSNV_SCAN_SUB (64 .. 32768): bytes of a sub-segment of the boundary walk.  Its default belongs to the route that asks: 4096 in
-// scan_streams (the deal, the careful route), 6144 in a round's one-walk route (2.36 -> 2.04 ms of scan + measure on the benchmark shape
+// scan_sub_walk (the deal, the careful route), 6144 in a round's one-walk route (2.36 -> 2.04 ms of scan + measure on the benchmark shape
 // against 4 KB, 8 KB the same).  Per call (tests/test_gpu_devpack.py shrinks it).
 constexpr long long SCAN_SUB_STREAMS = 4096, SCAN_SUB_ROUND = 6144;
 inline uint32_t scan_sub_bytes(long long route_default) { return (uint32_t)std::min<long long>(32768, std::max<long long>(64, i64_or("MSNV_SCAN_SUB", route_default))); }

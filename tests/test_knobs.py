@@ -158,7 +158,7 @@ PARSING = {
     "cov_item_intervals": ("MSNV_COV_ITEM", ["16384", "16384", "16384", "1", "16384", "16384", "2147483647"], {"64": "64"}),
     # v = e ? atoll(e) : 32767; min(32767, max(1, v))
     "cov_narrow_max": ("MSNV_COV_NARROW_MAX", ["32767", "1", "1", "1", "1", "1", "32767"], {"100": "100"}),
-    # v = e ? atoll(e) : 4096 (scan_streams) / 6144 (a round's one walk); min(32768, max(64, v))
+    # v = e ? atoll(e) : 4096 (scan_sub_walk) / 6144 (a round's one walk); min(32768, max(64, v))
     "scan_sub_bytes_streams": ("MSNV_SCAN_SUB", ["4096"] + ["64"] * 5 + ["32768"], {"256": "256"}),
     "scan_sub_bytes_round": ("MSNV_SCAN_SUB", ["6144"] + ["64"] * 5 + ["32768"], {"256": "256"}),
     # v = e ? atoll(e) : 256; max(1, v) << 10
