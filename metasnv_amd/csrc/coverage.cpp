@@ -17,6 +17,17 @@ int coverage_run(msnv_dataset &ds, msnv_run_stats *stats) {
     ds.cov_acc.assign(n, 0);                                 // tile t added to copy t % cov_copies (device.h)
     for (uint32_t k = 0; k < d.cov_copies; ++k)
         for (size_t i = 0; i < n; ++i) ds.cov_acc[i] += copies[(size_t)k * n + i];
+    // bin 0 (printed nowhere: OUT.detail is cumulative from bin 1): the kernel counts the zero-depth positions of the tiles a sample has
+    // intervals in; a tile without any has no work item and is depth 0 throughout -- its positions are added here
+    if (!ds.cov_row_scanned_ok) {
+        ds.cov_row_scanned.assign((size_t)d.n_cov_rows, 0);
+        if (int rc = dev_coverage_scanned(d, ds.ctx->stream, ds.cov_row_scanned.data())) return rc;
+        ds.cov_row_scanned_ok = true;
+    }
+    for (size_t r = 0; r < (size_t)d.n_cov_rows; ++r) {
+        const unsigned long long L = (unsigned long long)ds.lengths[ds.cov_row_contig[r]];
+        if (L > ds.cov_row_scanned[r]) ds.cov_acc[r * (1 + COV_BINS) + 1] += L - ds.cov_row_scanned[r];
+    }
     ds.have_coverage = true;
     if (stats) stats->ms_coverage = st.ms_coverage;
     return MSNV_OK;

@@ -251,6 +251,8 @@ struct msnv_dataset {
     std::vector<uint32_t> cov_row_sample, cov_row_contig;
     std::vector<uint64_t> cov_row_start;       // per sample: its first row (n_samples + 1)
     std::vector<unsigned long long> cov_acc;   // [row][1 + COV_BINS] of the last coverage run
+    std::vector<unsigned long long> cov_row_scanned;   // per row: positions of its contig in the tiles the sample has a pair in (what the kernel scans; the rest is depth 0)
+    bool cov_row_scanned_ok = false;           // (counted once per finalize, by the first coverage run)
 };
 
 inline const msnv_site_sample *msnv::SiteRowView::row(const msnv_dataset &ds, size_t i, size_t S) {

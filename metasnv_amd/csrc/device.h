@@ -186,6 +186,7 @@ void dev_stream_destroy(void *stream);
 // One pass of the pipeline (pileup -> gate -> gather -> decide) on `stream`.
 constexpr int COV_BINS = 16;            // histogram bins kept on the device (qaCompute -c <= 15)
 int  dev_run_coverage(DeviceCols &d, int max_cov, void *stream, msnv_run_stats *stats);
+int  dev_coverage_scanned(DeviceCols &d, void *stream, unsigned long long *scanned);      // scanned[n_cov_rows]: positions msnv_coverage_tiles scans per accumulator row
 int  dev_run_pipeline(DeviceCols &d, const msnv_params &p, void *stream, msnv_run_stats *stats, RunCounts *counts);
 int  dev_run_pipeline_many(DeviceCols &d, const msnv_params &p, void *stream, int n, bool overlap, msnv_run_stats *stats, RunCounts *counts);
 void dev_free_all(DeviceCols &d);

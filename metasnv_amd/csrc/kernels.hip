@@ -3204,6 +3204,38 @@ int dev_run_coverage(DeviceCols &d, int max_cov, void *stream_, msnv_run_stats *
     return MSNV_OK;
 }
 
+// Positions that msnv_coverage_tiles scans per accumulator row: the lengths of the tiles the row's sample has a pair in.  A tile without a
+// pair has no work item -- depth 0 throughout, which no printed number needs (the detail row starts at bin 1) but bin 0 does: the host
+// adds contig length - scanned to it (coverage.cpp).  One thread per work item; the index does not change between runs, so this runs once.
+__global__ void msnv_coverage_scanned(const TilePair *pairs, const WorkItem *work, const uint32_t *tile_len, const uint32_t n_work, const uint32_t n_pairs,
+                                      const uint32_t n_rows, unsigned long long *scanned) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_work) return;
+    const WorkItem w = work[i];
+    const unsigned long long tl = tile_len[w.tile];
+    for (uint32_t k = w.pair_lo; k < w.pair_hi && k < n_pairs; ++k) {
+        const uint32_t row = pairs[k].max_depth;
+        if (row < n_rows) atomicAdd(&scanned[row], tl);
+    }
+}
+int dev_coverage_scanned(DeviceCols &d, void *stream_, unsigned long long *scanned) {
+    hipStream_t st = (hipStream_t)stream_;
+    if (!d.n_cov_rows) return MSNV_OK;
+    unsigned long long *buf = nullptr;
+    if (int rc = dev_alloc((void **)&buf, d.n_cov_rows * sizeof(unsigned long long), nullptr)) return rc;
+    hipError_t e = hipMemsetAsync(buf, 0, d.n_cov_rows * sizeof(unsigned long long), st);
+    if (e == hipSuccess && d.n_cov_work) {
+        hipLaunchKernelGGL(msnv_coverage_scanned, dim3((d.n_cov_work + 255u) / 256u), dim3(256), 0, st, d.cov_pairs, d.cov_work, d.tile_len, d.n_cov_work,
+                           d.n_cov_pairs, (uint32_t)d.n_cov_rows, buf);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(scanned, buf, d.n_cov_rows * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    dev_free(buf);
+    if (e != hipSuccess) return fail(MSNV_EHIP, "coverage: counting the scanned positions failed: %s", hipGetErrorString(e));
+    return MSNV_OK;
+}
+
 // The runtime loads a translation unit's code object when its first kernel is launched (~10 ms): msnv_ctx_create does that here, on the
 // thread that brings the context up, instead of inside the first timed stage.
 __global__ void msnv_warm_kernels() {}

@@ -1769,6 +1769,7 @@ int finalize_dataset(msnv_dataset &ds) {
     lap("    cov tables: up");
     {   // accumulator copies: as many as fit 64 MB, at most 8 (many contigs = few tiles per contig = little contention anyway)
         d->n_cov_rows = ds.cov_row_sample.size();
+        ds.cov_row_scanned_ok = false;
         const uint64_t acc_bytes = std::max<uint64_t>(1, d->n_cov_rows) * (1 + COV_BINS) * sizeof(unsigned long long);
         d->cov_copies = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(8, (64ull << 20) / std::max<uint64_t>(1, acc_bytes)));
         if (int rc = dev_alloc((void **)&d->cov_acc, d->cov_copies * acc_bytes, &d->device_bytes)) return rc;
