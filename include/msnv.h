@@ -374,6 +374,62 @@ int  msnv_fused_run(msnv_dataset *ds, msnv_run_stats *pileup_stats, msnv_run_sta
 /* Writes OUT / OUT.detail for sample `sample_idx` from the last msnv_coverage_run. */
 int  msnv_write_coverage(msnv_dataset *ds, int32_t sample_idx, const char *cov_path, const char *detail_path);
 
+/* ------------------------------------------------------------------------------------
+ * qaCompute's -m, -p W and -x FILE from the resident dataset (csrc/covext_k.hip): the median of the per-position depth, the window
+ * profile and the mean depth of named regions, for every sample in one pass over the coverage index -- replaces one single-threaded
+ * `qaCompute -m -p W -x FILE` per BAM (qaCompute.cpp:100-123,173-190,215).  Runs after msnv_dataset_finalize, before or after
+ * msnv_coverage_run; asking for none of the three launches nothing.  Regions are (header contig index, start, end), both ends inclusive,
+ * in the index space of qaCompute.cpp:114-116 (index = 1-based position); a region with start > end or end >= contig length is
+ * MSNV_EDOMAIN (the reference reads past its prefix sums there).
+ * ------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t        want_median;     /* -m                                                   */
+    int32_t        window;          /* -p W; 0 = no profile                                 */
+    uint32_t       n_regions;       /* -x: entries of the three arrays below; 0 = none      */
+    uint32_t       reserved;
+    const int32_t *region_contig;
+    const int32_t *region_start;
+    const int32_t *region_end;
+} msnv_cov_extras;
+int  msnv_coverage_extras_run(msnv_dataset *ds, const msnv_cov_extras *what);
+/* Results of the last msnv_coverage_extras_run.
+ *   medians      int32[n_samples][n_contigs]: data[L / 2] of the depths sorted as radix.h sorts them (unsigned: a negative depth, which only a contig's
+ *                last position can hold, orders last); 0 where the sample has no coverage on the contig; all 0 without want_median.
+ *   window sums  of ONE sample, uint64, contig-major in header order: contig c holds (L - 1) / W windows of the loop of
+ *                qaCompute.cpp:175-182 (window 0 = indices 0 .. W, window k = k W + 1 .. (k + 1) W) plus, when (L - 1) % W != 0, the
+ *                trailing one of :183-185; none for L == 1.  A sum is taken modulo 2^64 like the reference's wSum.
+ *                msnv_coverage_window_count gives the number of entries (0 without a window).
+ *   region sums  uint64[n_samples][n_regions], the sum of the depth over [start, end].
+ * msnv_coverage_extras_launches: kernel launches the run took (0 when nothing was asked for; at most 3 per batch of rows). */
+int  msnv_coverage_medians(msnv_dataset *ds, int32_t *out, uint64_t capacity);
+int  msnv_coverage_window_count(const msnv_dataset *ds, uint64_t *n_windows);
+int  msnv_coverage_window_sums(msnv_dataset *ds, int32_t sample_idx, uint64_t *out, uint64_t capacity);
+int  msnv_coverage_region_sums(msnv_dataset *ds, uint64_t *out, uint64_t capacity);
+int  msnv_coverage_extras_launches(const msnv_dataset *ds, uint32_t *n_launches);
+/* One line of a -x file (qaCompute.cpp:344): contig name (need not be in the header), start, end, alias. */
+typedef struct { const char *contig; int32_t start, end; const char *alias; } msnv_cov_region;
+/* msnv_write_coverage plus the files of the last msnv_coverage_extras_run: OUT takes the Median_Cov column (qaCompute.cpp:215,237,437)
+ * when that run computed medians; profile_path (NULL: not written) is OUT.profile (:173-186,249-260), specific_path (NULL: not
+ * written) OUT.specific (:100-123,604-615) for the lines `regions` of the -x file -- those that name a header contig must be, in
+ * order, the regions of the run.  DESIGN.md section 7 lists the one divergence (a contig whose reads are all filtered). */
+int  msnv_write_coverage_ex(msnv_dataset *ds, int32_t sample_idx, const char *cov_path, const char *detail_path, const char *profile_path,
+                            const char *specific_path, const msnv_cov_region *regions, uint32_t n_regions);
+/* msnv_coverage with -m, -p W and -x FILE: the one-BAM form behind the msnv_qacompute drop-in.  A regions file whose field
+ * count is no multiple of four, or with an interval outside its contig, is MSNV_EDOMAIN. */
+typedef struct {
+    const char *bam_path;
+    int32_t     max_cov;            /* -c                                  */
+    int32_t     min_mapq;           /* -q, default 1                       */
+    const char *out_cov_path;       /* OUT                                 */
+    const char *out_detail_path;    /* OUT.detail (-d)                     */
+    int32_t     want_median;        /* -m                                  */
+    int32_t     window;             /* -p W; 0 = no OUT.profile            */
+    const char *out_profile_path;   /* OUT.profile; needed when window > 0 */
+    const char *regions_path;       /* -x FILE; NULL = no OUT.specific     */
+    const char *out_specific_path;  /* OUT.specific; needed with -x        */
+} msnv_cov_ex_args;
+int  msnv_coverage_ex(msnv_ctx *ctx, const msnv_cov_ex_args *args);
+
 /* Formats the last run as called_SNPs / indiv_called (call_vC.cpp:641-667).
  * ann_path / fasta_path feed the codon annotation (call_vC.cpp:604-633) and may be NULL. */
 int  msnv_write_calls(msnv_dataset *ds, const char *called_path, const char *indiv_path,

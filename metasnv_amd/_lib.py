@@ -35,6 +35,21 @@ class CovArgs(C.Structure):
                 ("out_cov_path", C.c_char_p), ("out_detail_path", C.c_char_p)]
 
 
+class CovExtras(C.Structure):
+    _fields_ = [("want_median", C.c_int32), ("window", C.c_int32), ("n_regions", C.c_uint32), ("reserved", C.c_uint32),
+                ("region_contig", C.POINTER(C.c_int32)), ("region_start", C.POINTER(C.c_int32)), ("region_end", C.POINTER(C.c_int32))]
+
+
+class CovRegion(C.Structure):
+    _fields_ = [("contig", C.c_char_p), ("start", C.c_int32), ("end", C.c_int32), ("alias", C.c_char_p)]
+
+
+class CovExArgs(C.Structure):
+    _fields_ = [("bam_path", C.c_char_p), ("max_cov", C.c_int32), ("min_mapq", C.c_int32),
+                ("out_cov_path", C.c_char_p), ("out_detail_path", C.c_char_p), ("want_median", C.c_int32), ("window", C.c_int32),
+                ("out_profile_path", C.c_char_p), ("regions_path", C.c_char_p), ("out_specific_path", C.c_char_p)]
+
+
 class CallArgs(C.Structure):
     _fields_ = [("bam_paths", C.POINTER(C.c_char_p)), ("n_bams", C.c_int32), ("ref_fasta", C.c_char_p),
                 ("ann_path", C.c_char_p), ("bed_split_path", C.c_char_p), ("out_called_path", C.c_char_p),
@@ -152,6 +167,14 @@ SYMBOLS = [
     ("msnv_coverage_run", C.c_int, [_vp, P(RunStats)]),
     ("msnv_fused_run", C.c_int, [_vp, P(RunStats), P(RunStats)]),
     ("msnv_write_coverage", C.c_int, [_vp, C.c_int32, C.c_char_p, C.c_char_p]),
+    ("msnv_coverage_extras_run", C.c_int, [_vp, P(CovExtras)]),
+    ("msnv_coverage_medians", C.c_int, [_vp, P(C.c_int32), C.c_uint64]),
+    ("msnv_coverage_window_count", C.c_int, [_vp, P(C.c_uint64)]),
+    ("msnv_coverage_window_sums", C.c_int, [_vp, C.c_int32, P(C.c_uint64), C.c_uint64]),
+    ("msnv_coverage_region_sums", C.c_int, [_vp, P(C.c_uint64), C.c_uint64]),
+    ("msnv_coverage_extras_launches", C.c_int, [_vp, P(C.c_uint32)]),
+    ("msnv_write_coverage_ex", C.c_int, [_vp, C.c_int32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, P(CovRegion), C.c_uint32]),
+    ("msnv_coverage_ex", C.c_int, [_vp, P(CovExArgs)]),
     ("msnv_write_calls", C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]),
     ("msnv_dataset_first_line", C.c_int, [_vp, P(C.c_int32), P(C.c_int32)]),
     ("msnv_dataset_first_lines", C.c_int, [_vp, P(C.c_int32), P(C.c_int32), C.c_int32]),

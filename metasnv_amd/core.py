@@ -299,8 +299,44 @@ class Dataset:
         check(lib.msnv_dataset_sample_stats(self._h, sample_idx, C.byref(st)))
         return np.array([getattr(st, k) for k in STATS_FIELDS], dtype=np.uint32)
 
-    def write_coverage(self, sample_idx, cov_path, detail_path):
-        check(lib.msnv_write_coverage(self._h, sample_idx, cov_path.encode(), detail_path.encode()))
+    def write_coverage(self, sample_idx, cov_path, detail_path, profile_path=None, specific_path=None, regions=None):
+        """OUT / OUT.detail of one sample.  With profile_path, specific_path or after a coverage_extras(median=True) run the
+        files take qaCompute's -m / -p / -x forms (msnv_write_coverage_ex); regions = the lines of the -x file as
+        (contig name, start, end, alias), see read_regions()."""
+        if profile_path is None and specific_path is None and not getattr(self, "_extras_median", False):
+            check(lib.msnv_write_coverage(self._h, sample_idx, cov_path.encode(), detail_path.encode()))
+            return
+        regions = list(regions or [])
+        arr = (_lib.CovRegion * max(1, len(regions)))()
+        for i, (name, start, end, alias) in enumerate(regions):
+            arr[i] = _lib.CovRegion(name.encode(), int(start), int(end), alias.encode())
+        check(lib.msnv_write_coverage_ex(self._h, sample_idx, cov_path.encode(), detail_path.encode(),
+                                         profile_path.encode() if profile_path is not None else None,
+                                         specific_path.encode() if specific_path is not None else None, arr, len(regions)))
+
+    def coverage_extras(self, median=False, window=0, regions=None):
+        """qaCompute's -m, -p W and -x over every sample of the resident dataset (msnv_coverage_extras_run).  regions: (contig, start,
+        end) triples, contig a header index or name, both ends inclusive.  Returns a dict: "medians" int32[n_samples][n_contigs],
+        "window_sums" uint64[n_samples][n_windows] (contig-major, see include/msnv.h), "region_sums" uint64[n_samples][n_regions],
+        "launches" -- the parts that were not asked for are empty or zero."""
+        regions = [(self.names.index(c) if isinstance(c, str) else int(c), int(s), int(e)) for c, s, e in (regions or [])]
+        cols = [np.ascontiguousarray([r[k] for r in regions], dtype=np.int32) for k in range(3)]
+        what = _lib.CovExtras(1 if median else 0, int(window), len(regions), 0, *[c.ctypes.data_as(C.POINTER(C.c_int32)) for c in cols])
+        check(lib.msnv_coverage_extras_run(self._h, C.byref(what)))
+        self._extras_median = bool(median)
+        S = max(1, self.n_samples)
+        med = np.zeros((S, len(self.names)), dtype=np.int32)
+        check(lib.msnv_coverage_medians(self._h, med.ctypes.data_as(C.POINTER(C.c_int32)), med.size))
+        n = C.c_uint64()
+        check(lib.msnv_coverage_window_count(self._h, C.byref(n)))
+        win = np.zeros((S, n.value), dtype=np.uint64)
+        for s in range(self.n_samples):
+            check(lib.msnv_coverage_window_sums(self._h, s, win[s].ctypes.data_as(C.POINTER(C.c_uint64)), n.value))
+        reg = np.zeros((S, len(regions)), dtype=np.uint64)
+        check(lib.msnv_coverage_region_sums(self._h, reg.ctypes.data_as(C.POINTER(C.c_uint64)), reg.size))
+        k = C.c_uint32()
+        check(lib.msnv_coverage_extras_launches(self._h, C.byref(k)))
+        return {"medians": med, "window_sums": win, "region_sums": reg, "launches": k.value}
 
     def results(self):
         n = C.c_uint64()
@@ -460,6 +496,15 @@ def contig_bases(records, n_contigs, into=None):
     out = into if into is not None else np.zeros(n_contigs, dtype=np.uint64)
     check(lib.msnv_records_contig_bases(rec.ctypes.data, rec.size, n_contigs, out.ctypes.data_as(C.POINTER(C.c_uint64))))
     return out
+
+
+def read_regions(path):
+    """The lines of a qaCompute -x file as (contig name, start, end, alias): whitespace-separated quadruples, as the
+    reference's fscanf reads them (qaCompute.cpp:344)."""
+    tok = open(path).read().split()
+    if len(tok) % 4:
+        raise ValueError("%s: %d fields, not a multiple of four" % (path, len(tok)))
+    return [(tok[i], int(tok[i + 1]), int(tok[i + 2]), tok[i + 3]) for i in range(0, len(tok), 4)]
 
 
 def write_coverage_records(names, lengths, max_cov, stats, acc, cov_path, detail_path):

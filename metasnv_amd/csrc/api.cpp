@@ -1636,9 +1636,85 @@ namespace msnv {
 int records_partition(const uint8_t *rec, uint64_t n_bytes, const int32_t *owner, int n_contigs, int n_parts, int cov_min_mapq,
                       uint8_t *out, uint64_t *part_bytes, msnv_sample_stats &st);
 int coverage_write_rows(const std::vector<std::string> &names, const std::vector<int64_t> &lengths, int max_cov, const msnv_sample_stats &sc,
-                        const unsigned long long *acc, const char *cov_path, const char *detail_path, int sample);
+                        const unsigned long long *acc, const char *cov_path, const char *detail_path, int sample, const int32_t *median);
+int coverage_extras_run(msnv_dataset &ds, const msnv_cov_extras &what);
+int coverage_window_count(const msnv_dataset &ds, uint64_t *n);
+int coverage_window_sums(const msnv_dataset &ds, int sample, uint64_t *out);
+int coverage_write_ex(msnv_dataset &ds, int sample, const char *cov_path, const char *detail_path, const char *profile_path, const char *specific_path,
+                      const msnv_cov_region *regions, uint32_t n_regions);
+int coverage_regions_parse(const char *path, std::vector<std::string> &names, std::vector<int32_t> &starts, std::vector<int32_t> &ends, std::vector<std::string> &aliases);
 }
 static_assert(MSNV_COV_WORDS == 1 + COV_BINS, "msnv.h and device.h disagree on the accumulator width");
+
+// ------------------------------------------------------------------------------ qaCompute -m / -p / -x (covext.cpp, covext_k.hip)
+extern "C" int msnv_coverage_extras_run(msnv_dataset *ds, const msnv_cov_extras *what) {
+    clear_error();
+    if (!ds || !what || !ds->finalized) return fail(MSNV_EINVAL, "msnv_coverage_extras_run: dataset is not finalized");
+    if (int rc = dev_set_device(ds->ctx->device)) return rc;
+    try { return coverage_extras_run(*ds, *what); }
+    catch (const std::exception &e) { return fail(MSNV_ENOMEM, "msnv_coverage_extras_run: %s", e.what()); }
+}
+
+static int need_extras(const msnv_dataset *ds, const char *who) {
+    if (!ds) return fail(MSNV_EINVAL, "%s: NULL argument", who);
+    if (!ds->covx.valid) return fail(MSNV_EINVAL, "no coverage extras: call msnv_coverage_extras_run first");
+    return MSNV_OK;
+}
+
+extern "C" int msnv_coverage_medians(msnv_dataset *ds, int32_t *out, uint64_t capacity) {
+    clear_error();
+    if (int rc = need_extras(ds, "msnv_coverage_medians")) return rc;
+    const uint64_t n = (uint64_t)ds->samples.size() * ds->names.size();
+    if (capacity < n) return fail(MSNV_ECAPACITY, "capacity %llu < %llu medians", (unsigned long long)capacity, (unsigned long long)n);
+    if (n && !out) return fail(MSNV_EINVAL, "msnv_coverage_medians: NULL argument");
+    for (uint64_t i = 0; i < n; ++i) out[i] = 0;
+    for (size_t r = 0; r < ds->cov_row_sample.size(); ++r) out[(uint64_t)ds->cov_row_sample[r] * ds->names.size() + ds->cov_row_contig[r]] = ds->covx.row_median[r];
+    return MSNV_OK;
+}
+
+extern "C" int msnv_coverage_window_count(const msnv_dataset *ds, uint64_t *n_windows) {
+    clear_error();
+    if (int rc = need_extras(ds, "msnv_coverage_window_count")) return rc;
+    if (!n_windows) return fail(MSNV_EINVAL, "msnv_coverage_window_count: NULL argument");
+    return coverage_window_count(*ds, n_windows);
+}
+
+extern "C" int msnv_coverage_window_sums(msnv_dataset *ds, int32_t sample_idx, uint64_t *out, uint64_t capacity) {
+    clear_error();
+    if (int rc = need_extras(ds, "msnv_coverage_window_sums")) return rc;
+    if (sample_idx < 0 || (size_t)sample_idx >= ds->samples.size()) return fail(MSNV_EINVAL, "sample index %d out of range", sample_idx);
+    uint64_t n = 0;
+    coverage_window_count(*ds, &n);
+    if (capacity < n) return fail(MSNV_ECAPACITY, "capacity %llu < %llu window sums", (unsigned long long)capacity, (unsigned long long)n);
+    if (n && !out) return fail(MSNV_EINVAL, "msnv_coverage_window_sums: NULL argument");
+    return coverage_window_sums(*ds, sample_idx, out);
+}
+
+extern "C" int msnv_coverage_region_sums(msnv_dataset *ds, uint64_t *out, uint64_t capacity) {
+    clear_error();
+    if (int rc = need_extras(ds, "msnv_coverage_region_sums")) return rc;
+    const uint64_t n = ds->covx.reg_sum.size();
+    if (capacity < n) return fail(MSNV_ECAPACITY, "capacity %llu < %llu region sums", (unsigned long long)capacity, (unsigned long long)n);
+    if (n && !out) return fail(MSNV_EINVAL, "msnv_coverage_region_sums: NULL argument");
+    if (n) memcpy(out, ds->covx.reg_sum.data(), n * sizeof(uint64_t));
+    return MSNV_OK;
+}
+
+extern "C" int msnv_coverage_extras_launches(const msnv_dataset *ds, uint32_t *n_launches) {
+    clear_error();
+    if (int rc = need_extras(ds, "msnv_coverage_extras_launches")) return rc;
+    if (!n_launches) return fail(MSNV_EINVAL, "msnv_coverage_extras_launches: NULL argument");
+    *n_launches = ds->covx.n_launches;
+    return MSNV_OK;
+}
+
+extern "C" int msnv_write_coverage_ex(msnv_dataset *ds, int32_t sample_idx, const char *cov_path, const char *detail_path, const char *profile_path,
+                                      const char *specific_path, const msnv_cov_region *regions, uint32_t n_regions) {
+    clear_error();
+    if (!ds || !cov_path || !detail_path) return fail(MSNV_EINVAL, "msnv_write_coverage_ex: NULL argument");
+    try { return coverage_write_ex(*ds, sample_idx, cov_path, detail_path, profile_path, specific_path, regions, n_regions); }
+    catch (const std::exception &e) { return fail(MSNV_ENOMEM, "msnv_write_coverage_ex: %s", e.what()); }
+}
 
 extern "C" int msnv_records_partition(const uint8_t *records, uint64_t n_bytes, const int32_t *contig_owner, int32_t n_contigs,
                                       int32_t n_parts, int32_t cov_min_mapq, uint8_t *out, uint64_t *part_bytes, msnv_sample_stats *stats) {
@@ -1730,7 +1806,7 @@ extern "C" int msnv_write_coverage_records(const msnv_ref_desc *ref, int32_t max
         return fail(MSNV_EINVAL, "msnv_write_coverage_records: bad argument");
     std::vector<std::string> names; std::vector<int64_t> lens;
     for (int i = 0; i < ref->n_contigs; ++i) { names.emplace_back(ref->names[i]); lens.push_back(ref->lengths[i]); }
-    return coverage_write_rows(names, lens, max_cov, *stats, reinterpret_cast<const unsigned long long *>(acc), cov_path, detail_path, 0);
+    return coverage_write_rows(names, lens, max_cov, *stats, reinterpret_cast<const unsigned long long *>(acc), cov_path, detail_path, 0, nullptr);
 }
 
 // ------------------------------------------------------------------------------ filter_two (section 8 f1)
@@ -1866,6 +1942,44 @@ extern "C" int msnv_call(msnv_ctx *ctx, const msnv_call_args *a) {
     if (!rc) rc = msnv_write_calls(ds, a->out_called_path, a->out_indiv_path, a->ann_path, a->ref_fasta);
     msnv_dataset_destroy(ds);
     return rc;
+}
+
+extern "C" int msnv_coverage_ex(msnv_ctx *ctx, const msnv_cov_ex_args *a) {
+    clear_error();
+    if (!ctx || !a || !a->bam_path || !a->out_cov_path || !a->out_detail_path) return fail(MSNV_EINVAL, "msnv_coverage_ex: NULL argument");
+    if (a->window < 0 || (a->window > 0 && !a->out_profile_path) || (a->regions_path && !a->out_specific_path)) return fail(MSNV_EINVAL, "msnv_coverage_ex: bad argument");
+    msnv_params p;
+    msnv_params_default(&p);
+    p.cov_max = a->max_cov > 0 ? a->max_cov : 10;
+    p.cov_min_mapq = a->min_mapq;
+    try {
+        std::vector<std::string> names, aliases;
+        std::vector<int32_t> starts, ends;
+        if (a->regions_path) if (int rc = coverage_regions_parse(a->regions_path, names, starts, ends, aliases)) return rc;
+        msnv_dataset *ds = nullptr;
+        int rc = msnv_dataset_create_from_files(ctx, a->bam_path, nullptr, &p, &ds);
+        if (rc) return rc;
+        // the lines that name a header contig are what the device sums; the others print as zeros
+        std::vector<msnv_cov_region> lines;
+        std::vector<int32_t> rc_contig, rc_start, rc_end;
+        for (size_t i = 0; i < names.size(); ++i) {
+            lines.push_back(msnv_cov_region{names[i].c_str(), starts[i], ends[i], aliases[i].c_str()});
+            const auto it = std::find(ds->names.begin(), ds->names.end(), names[i]);
+            if (it == ds->names.end()) continue;
+            rc_contig.push_back((int32_t)(it - ds->names.begin())); rc_start.push_back(starts[i]); rc_end.push_back(ends[i]);
+        }
+        msnv_cov_extras what{};
+        what.want_median = a->want_median; what.window = a->window; what.n_regions = (uint32_t)rc_contig.size();
+        what.region_contig = rc_contig.data(); what.region_start = rc_start.data(); what.region_end = rc_end.data();
+        rc = msnv_dataset_add_sample_bam(ds, a->bam_path);
+        if (!rc) rc = msnv_dataset_finalize(ds);
+        if (!rc) rc = msnv_coverage_run(ds, nullptr);
+        if (!rc) rc = msnv_coverage_extras_run(ds, &what);
+        if (!rc) rc = msnv_write_coverage_ex(ds, 0, a->out_cov_path, a->out_detail_path, a->window > 0 ? a->out_profile_path : nullptr,
+                                             a->regions_path ? a->out_specific_path : nullptr, lines.data(), (uint32_t)lines.size());
+        msnv_dataset_destroy(ds);
+        return rc;
+    } catch (const std::exception &e) { return fail(MSNV_ENOMEM, "msnv_coverage_ex: %s", e.what()); }
 }
 
 extern "C" int msnv_coverage(msnv_ctx *ctx, const msnv_cov_args *a) {

@@ -33,9 +33,10 @@ int coverage_run(msnv_dataset &ds, msnv_run_stats *stats) {
     return MSNV_OK;
 }
 
-// OUT / OUT.detail of one sample from its accumulator rows acc[contig][1 + COV_BINS] and its read statistics.
+// OUT / OUT.detail of one sample from its accumulator rows acc[contig][1 + COV_BINS] and its read statistics; with median[contig]
+// (qaCompute -m) OUT takes the Median_Cov column.
 int coverage_write_rows(const std::vector<std::string> &names, const std::vector<int64_t> &lengths, int max_cov, const msnv_sample_stats &sc,
-                        const unsigned long long *acc, const char *cov_path, const char *detail_path, int sample) {
+                        const unsigned long long *acc, const char *cov_path, const char *detail_path, int sample, const int32_t *median) {
     if (max_cov < 1 || max_cov >= COV_BINS) return fail(MSNV_EINVAL, "coverage histogram cutoff must be in [1, %d]", COV_BINS - 1);
     // a BAM without mapped reads makes qaCompute read target_name[-1] (qaCompute.cpp:596)
     if (!sc.any_mapped) return fail(MSNV_EDOMAIN, "sample %d has no mapped reads (qaCompute: undefined behaviour, README.md:59)", sample);
@@ -46,7 +47,8 @@ int coverage_write_rows(const std::vector<std::string> &names, const std::vector
     const size_t NC = names.size();
     std::vector<unsigned long long> global_hist((size_t)max_cov + 1, 0);
     unsigned long long total_len = 0;
-    fprintf(out, "Chromosome\tSeq_lem\tAvg_Cov\n");                                  // qaCompute.cpp:439
+    if (median) fprintf(out, "Chromosome\tSeq_len\tAvg_Cov\tMedian_Cov\n");                // qaCompute.cpp:437
+    else fprintf(out, "Chromosome\tSeq_lem\tAvg_Cov\n");                             // :439
     for (size_t c = 0; c < NC; ++c) {
         total_len += (unsigned long long)lengths[c];                                    // :425-427
         // contigs without reads print zeros through printSkipped (:226-263); contigs with reads through
@@ -60,7 +62,8 @@ int coverage_write_rows(const std::vector<std::string> &names, const std::vector
             fprintf(det, "%d\t", (int)cum);
         }
         fprintf(det, "\n");
-        fprintf(out, "%s\t%d\t%3.5f\n", names[c].c_str(), L, L ? (double)a[0] / L : 0.0);
+        if (median) fprintf(out, "%s\t%d\t%3.5f\t%d\n", names[c].c_str(), L, L ? (double)a[0] / L : 0.0, median[c]);      // :215,237
+        else fprintf(out, "%s\t%d\t%3.5f\n", names[c].c_str(), L, L ? (double)a[0] / L : 0.0);
         for (int x = 1; x <= max_cov; ++x) global_hist[(size_t)x] += a[1 + x];
     }
     fprintf(out, "\nCov*X\tPercentage\tNr. of bases\n");                                // :623-640
@@ -92,7 +95,7 @@ int coverage_write(msnv_dataset &ds, int sample, const char *cov_path, const cha
     std::vector<unsigned long long> dense(ds.names.size() * (1 + COV_BINS), 0ull);
     for (uint64_t r = ds.cov_row_start[(size_t)sample]; r < ds.cov_row_start[(size_t)sample + 1]; ++r)
         memcpy(&dense[(size_t)ds.cov_row_contig[(size_t)r] * (1 + COV_BINS)], &ds.cov_acc[(size_t)r * (1 + COV_BINS)], (1 + COV_BINS) * sizeof(unsigned long long));
-    return coverage_write_rows(ds.names, ds.lengths, ds.params.cov_max, ds.samples[(size_t)sample].st, dense.data(), cov_path, detail_path, sample);
+    return coverage_write_rows(ds.names, ds.lengths, ds.params.cov_max, ds.samples[(size_t)sample].st, dense.data(), cov_path, detail_path, sample, nullptr);
 }
 
 }  // namespace msnv

@@ -253,6 +253,15 @@ struct msnv_dataset {
     std::vector<unsigned long long> cov_acc;   // [row][1 + COV_BINS] of the last coverage run
     std::vector<unsigned long long> cov_row_scanned;   // per row: positions of its contig in the tiles the sample has a pair in (what the kernel scans; the rest is depth 0)
     bool cov_row_scanned_ok = false;           // (counted once per finalize, by the first coverage run)
+    // results of the last msnv_coverage_extras_run (covext.cpp), per accumulator row where they are per (sample, contig)
+    struct CovExtras {
+        bool valid = false, have_median = false;
+        uint32_t window = 0, n_launches = 0;
+        std::vector<int32_t>  row_median;
+        std::vector<uint64_t> row_win_off, win;                     // first window sum of every row (n_rows + 1); the sums
+        std::vector<int32_t>  reg_contig, reg_start, reg_end;       // the regions as they were handed over
+        std::vector<uint64_t> reg_sum;                              // [sample][region]
+    } covx;
 };
 
 inline const msnv_site_sample *msnv::SiteRowView::row(const msnv_dataset &ds, size_t i, size_t S) {

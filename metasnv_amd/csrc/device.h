@@ -187,6 +187,21 @@ void dev_stream_destroy(void *stream);
 constexpr int COV_BINS = 16;            // histogram bins kept on the device (qaCompute -c <= 15)
 int  dev_run_coverage(DeviceCols &d, int max_cov, void *stream, msnv_run_stats *stats);
 int  dev_coverage_scanned(DeviceCols &d, void *stream, unsigned long long *scanned);      // scanned[n_cov_rows]: positions msnv_coverage_tiles scans per accumulator row
+// qaCompute -m / -p / -x from the same index (covext_k.hip).  Rows are the accumulator rows of dataset.h; the host hands over what the kernel
+// cannot know (contig lengths, the first tile of every contig, the windows of every row) and takes the medians, window sums and region sums.
+constexpr uint32_t CX_BINS = 2048, CX_ROW_WORDS = CX_BINS + 2;      // histogram window of one row + its positions at a negative depth: their number, their sum
+struct CovxRegion { uint32_t start, end, max_end, id; };            // per contig sorted by start; max_end: largest end up to here; id: the caller's index
+struct CovxJob {
+    bool want_median = false; uint32_t window = 0, n_samples = 0;
+    std::vector<uint32_t> contig_tile_base;                          // per contig
+    std::vector<uint32_t> row_contig;
+    std::vector<uint64_t> row_len, row_scanned, row_win_off;          // per row: contig length, positions in tiles with a work item; first window (n_rows + 1)
+    std::vector<CovxRegion> regs; std::vector<uint32_t> reg_off;     // regions contig by contig (n_contigs + 1 offsets)
+    // results
+    std::vector<int32_t> row_median; std::vector<uint64_t> win, reg_sum;      // reg_sum[sample][region id]
+    uint32_t n_launches = 0;
+};
+int  dev_run_coverage_extras(DeviceCols &d, CovxJob &job, void *stream);
 int  dev_run_pipeline(DeviceCols &d, const msnv_params &p, void *stream, msnv_run_stats *stats, RunCounts *counts);
 int  dev_run_pipeline_many(DeviceCols &d, const msnv_params &p, void *stream, int n, bool overlap, msnv_run_stats *stats, RunCounts *counts);
 void dev_free_all(DeviceCols &d);

@@ -1,8 +1,9 @@
-// msnv_qacompute -- process-level drop-in for `qaCompute [-c INT] [-q INT] -d -i <in.bam> <out>` as metaSNV.py:63-65
-// invokes it (argv: src/qaTools/qaCompute.cpp:312-359; outputs OUT and OUT.detail; "Printing details in ..." on
-// stdout :387; exit status 1 for usage / unopenable files :356-359,376-379, 0 on success :680).
-// A thin main over the C ABI (include/msnv.h): all arithmetic runs on the GPU.  Options of qaCompute that
-// metaSNV never passes (-m -p -s -x -a -h) are rejected instead of being silently ignored.
+// msnv_qacompute -- process-level drop-in for `qaCompute [-c INT] [-q INT] [-m] [-p INT] [-x FILE] -d -i <in.bam> <out>`:
+// metaSNV.py:63-65 invokes it with -c 10 -d -i (argv: src/qaTools/qaCompute.cpp:312-359; outputs OUT and OUT.detail,
+// OUT.profile with -p and OUT.specific with -x :380-405; "Printing details in ..." on stdout :387; exit status 1 for
+// usage / unopenable files :356-359,376-379, 0 on success :680).
+// A thin main over the C ABI (include/msnv.h): all arithmetic runs on the GPU.  The options of qaCompute that are
+// not built (-s -a -h) are rejected instead of being silently ignored.
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -11,34 +12,54 @@
 #include "../../../include/msnv.h"
 
 static void usage() {
-    fprintf(stderr, "Usage: msnv_qacompute [-c INT] [-q INT] -d [-i] <in.bam> <output.out>\n"
+    fprintf(stderr, "Usage: msnv_qacompute [-c INT] [-q INT] [-m] [-p INT] [-x FILE] -d [-i] <in.bam> <output.out>\n"
                     "  -c INT  maximum coverage of the breadth histogram (1..15, default 10 as metaSNV passes it)\n"
                     "  -q INT  minimum mapping quality (default 1)\n"
                     "  -d      write <output.out>.detail (always written; metaSNV.py always passes -d)\n"
-                    "  -i      silent\n");
+                    "  -i      silent\n"
+                    "  -m      add the Median_Cov column to <output.out>\n"
+                    "  -p INT  write the coverage profile of windows of INT bases to <output.out>.profile (INT >= 1)\n"
+                    "  -x FILE write the mean coverage of the regions in FILE (name start end alias) to <output.out>.specific\n"
+                    "  -s INT, -a FLOAT, -h FILE of qaCompute are not supported\n");
 }
 
 int main(int argc, char **argv) {
-    int max_cov = 10, min_mapq = 1, arg;
+    int max_cov = 10, min_mapq = 1, arg, median = 0, window = 0;
+    bool profile = false;
+    const char *regions = nullptr;
     while ((arg = getopt(argc, argv, "mdip:s:q:c:h:x:a:")) >= 0) {
         switch (arg) {
         case 'd': case 'i': break;
         case 'q': min_mapq = atoi(optarg); break;
         case 'c': max_cov = atoi(optarg); break;
+        case 'm': median = 1; break;
+        case 'p': window = atoi(optarg); profile = true; break;
+        case 'x': regions = optarg; break;
         default:
             fprintf(stderr, "msnv_qacompute: option -%c of qaCompute is not supported (metaSNV.py never passes it)\n", arg);
             return 1;
         }
     }
-    if (argc - optind != 2) { usage(); return 1; }
-    const std::string out = argv[optind + 1], detail = out + ".detail";
+    if (argc - optind != 2 || (profile && window < 1)) { usage(); return 1; }
+    const std::string out = argv[optind + 1], detail = out + ".detail", prof = out + ".profile", spec = out + ".specific";
     msnv_ctx *ctx = nullptr;
     if (msnv_ctx_create(0, &ctx)) { fprintf(stderr, "msnv_qacompute: %s\n", msnv_last_error()); return 1; }
-    msnv_cov_args a{};
-    a.bam_path = argv[optind]; a.max_cov = max_cov; a.min_mapq = min_mapq;
-    a.out_cov_path = out.c_str(); a.out_detail_path = detail.c_str();
     fprintf(stdout, "Printing details in %s!\n", detail.c_str());
-    const int rc = msnv_coverage(ctx, &a);
+    int rc;
+    if (!median && !profile && !regions) {                 // the argv of metaSNV.py: the path it has always taken
+        msnv_cov_args a{};
+        a.bam_path = argv[optind]; a.max_cov = max_cov; a.min_mapq = min_mapq;
+        a.out_cov_path = out.c_str(); a.out_detail_path = detail.c_str();
+        rc = msnv_coverage(ctx, &a);
+    }
+    else {
+        msnv_cov_ex_args a{};
+        a.bam_path = argv[optind]; a.max_cov = max_cov; a.min_mapq = min_mapq;
+        a.out_cov_path = out.c_str(); a.out_detail_path = detail.c_str();
+        a.want_median = median; a.window = window; a.out_profile_path = prof.c_str();
+        a.regions_path = regions; a.out_specific_path = spec.c_str();
+        rc = msnv_coverage_ex(ctx, &a);
+    }
     if (rc) fprintf(stderr, "msnv_qacompute: %s\n", msnv_last_error());
     msnv_ctx_destroy(ctx);
     return rc ? 1 : 0;
