@@ -247,7 +247,7 @@ def main(argv=None):
         from . import core
         no_device = "\nERROR:  no HIP device is available\n\nSOLUTION: run on a node with an AMD Instinct GPU (there is no CPU fallback)\n\n"
         if world == 1 and args.threads >= 8:
-            # one process, many host threads: the BAMs are inflated by the host decoder (csrc/api.cpp: want_device_inflate), so the device
+            # one process, many host threads: the BAMs are inflated by the host decoder (csrc/bamfeed.cpp: want_device_inflate), so the device
             # is first needed when the packed columns go up -- the runtime (counting the devices alone takes 0.1 s) and the context come
             # up on a thread of their own meanwhile; a node without a GPU is reported when that thread is asked for the context
             from concurrent.futures import ThreadPoolExecutor
@@ -255,7 +255,7 @@ def main(argv=None):
             # at best, the device in 0.25 s once its context stands): then the feed waits for the context and inflates on the device
             # (parallel.feed_sharded: MSNV_ONESHOT=device | host overrides)
             how = knobs.oneshot()
-            # ... and only when the library WILL inflate there (csrc/api.cpp: want_device_inflate -- MSNV_INFLATE=host, or fewer than 64 MB of
+            # ... and only when the library WILL inflate there (csrc/bamfeed.cpp: want_device_inflate -- MSNV_INFLATE=host, or fewer than 64 MB of
             # BAMs, keeps the host decoder): waiting for the context first and then inflating on the host threads anyway would lose the overlap
             def device_would_inflate():
                 e = knobs.inflate_where()

@@ -1,10 +1,6 @@
 // metasnv_amd/csrc/api.cpp -- C ABI of libmsnv.so (include/msnv.h): contexts, datasets, the
 // pipeline driver, result mapping and the reference-format text writers.
 #include <algorithm>
-#include <sys/stat.h>
-
-#include <atomic>
-#include <future>
 #include <chrono>
 #include <climits>
 #include <cstring>
@@ -12,21 +8,9 @@
 #include <thread>
 #include <unordered_map>
 
-#include "device.h"
+#include "bamfeed.h"
 #include "devpack.h"
 #include "filter.h"
-
-namespace msnv {
-int pack_sample(const msnv_dataset &ds, const uint8_t *rec, uint64_t n_bytes, SampleCols &sc);
-int pileup_qualities(const msnv_dataset &ds, const uint8_t *rec, uint64_t n_bytes, uint8_t *out);
-int finalize_dataset(msnv_dataset &ds);
-int write_calls_text(msnv_dataset &ds, const char *called_path, const char *indiv_path,
-                     const msnv_site_ann *ann, const std::vector<std::string> *gene_names);
-int coverage_run(msnv_dataset &ds, msnv_run_stats *stats);
-int coverage_write(msnv_dataset &ds, int sample, const char *cov_path, const char *detail_path);
-std::vector<std::string> synth_contigs(const msnv_synth_params &p);
-void synth_sample_records(const msnv_synth_params &p, int sample, const std::vector<std::string> &contigs, std::vector<uint8_t> &out);
-}  // namespace msnv
 
 using namespace msnv;
 
@@ -42,7 +26,6 @@ extern "C" void msnv_params_default(msnv_params *p) {
     p->token_limit = 10000;                                                       // call_vC.cpp:481-483
 }
 
-namespace msnv { void warm_devpack(void *), warm_kernels(void *), warm_textcall(void *), warm_annotate(void *); }
 extern "C" int msnv_ctx_create(int device_id, msnv_ctx **out) {
     clear_error();
     if (!out) return fail(MSNV_EINVAL, "msnv_ctx_create: NULL out");
@@ -56,7 +39,6 @@ extern "C" int msnv_ctx_create(int device_id, msnv_ctx **out) {
     return MSNV_OK;
 }
 
-namespace msnv { void dev_inflate_release(msnv_ctx *ctx); }
 extern "C" void msnv_ctx_destroy(msnv_ctx *ctx) {
     if (!ctx) return;
     dev_inflate_release(ctx);
@@ -203,41 +185,6 @@ static bool pack_on_device(const msnv_dataset *ds) {
     if (!ds->ctx) return false;
     return !knob::pack_on_host();                        // (per call: tests switch it)
 }
-// Appends n streams as n samples through the device pack, in rounds of at most MSNV_PACK_ROUND_MB (default 6144) of record bytes.
-static int add_streams_device(msnv_dataset *ds, const uint8_t *const *records, const uint64_t *n_bytes, int n, bool streams_on_device, const uint8_t *in_place_base = nullptr, uint64_t in_place_capacity = 0) {
-    HostTimerScope ts(HT_PACK_DEVICE_WALL);
-    fin_trace_reset();
-    struct Mark { ~Mark() { fin_trace("pack: whole call"); } } mark;
-    const uint64_t round_bytes = knob::pack_round_bytes();
-    const size_t first = ds->samples.size();
-    const size_t rounds_at_entry = ds->dp.rounds.size();
-    ds->samples.resize(first + (size_t)n);
-    int rc = MSNV_OK;
-    try {
-        for (int i0 = 0; i0 < n && !rc;) {
-            int i1 = i0; uint64_t b = 0;
-            while (i1 < n && i1 - i0 < 2048 && (i1 == i0 || b + n_bytes[i1] <= round_bytes)) { b += n_bytes[i1]; ++i1; }
-            rc = devpack_add_round(*ds, first + (size_t)i0, records + i0, n_bytes + i0, i1 - i0, streams_on_device, in_place_base, in_place_capacity);
-            i0 = i1;
-        }
-    } catch (const std::exception &e) { rc = fail(MSNV_ENOMEM, "packing on the device failed: %s", e.what()); }
-    if (rc) {
-        ds->samples.resize(first);
-        // rounds of this call that went through left their tables behind (dp.rounds, first_sample): finalize would index with them
-        if (ds->dp.rounds.size() != rounds_at_entry) ds->poisoned = true;
-    }
-    return rc;
-}
-
-// A call that appends its samples in SEVERAL add_streams_device calls (groups of files, batches of the device inflate, groups of synthetic
-// samples) and fails in a later one: the samples of the calls that went through are dropped with the rest (msnv.h: a failed add_* call adds
-// nothing), and since their rounds' tables stay behind in dp.rounds the dataset is poisoned like in add_streams_device itself.
-static int fail_multi_add(msnv_dataset *ds, size_t first, size_t rounds_at_entry, int rc) {
-    ds->samples.resize(first);
-    if (ds->dp.rounds.size() != rounds_at_entry) ds->poisoned = true;
-    return rc;
-}
-
 extern "C" int msnv_dataset_add_sample_records_device(msnv_dataset *ds, const void *const *dev_records, const uint64_t *n_bytes, int32_t n) {
     clear_error();
     if (!ds || n < 0 || (n && (!dev_records || !n_bytes))) return fail(MSNV_EINVAL, "msnv_dataset_add_sample_records_device: bad argument");
@@ -283,45 +230,19 @@ extern "C" int msnv_dataset_add_sample_records_many(msnv_dataset *ds, const uint
     if (int rc = check_open(ds)) return rc;
     for (int i = 0; i < n; ++i) if (n_bytes[i] && !records[i]) return fail(MSNV_EINVAL, "msnv_dataset_add_sample_records_many: stream %d is NULL", i);
     if (pack_on_device(ds)) return add_streams_device(ds, records, n_bytes, n, false);
-    int nthreads = host_threads > 0 ? host_threads : (int)msnv_default_threads();
-    nthreads = std::min(nthreads, std::max(1, (int)n));
     const size_t first = ds->samples.size();
     ds->samples.resize(first + (size_t)n);
-    std::atomic<int> next{0}, err{0};
-    std::vector<std::string> msgs((size_t)n);
-    auto worker = [&]() {
-        for (;;) {
-            const int i = next.fetch_add(1);
-            if (i >= n || err.load()) break;
-            int rc;
-            try { rc = pack_sample(*ds, records[i], n_bytes[i], ds->samples[first + (size_t)i]); }
-            catch (const std::exception &e) { rc = fail(MSNV_ENOMEM, "packing sample %d failed: %s", i, e.what()); }
-            if (rc) { msgs[(size_t)i] = msnv_last_error(); err.store(rc); }
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 0; t < nthreads; ++t) th.emplace_back(worker);
-    for (auto &t : th) t.join();
-    if (err.load()) {
-        ds->samples.resize(first);
-        for (const std::string &m : msgs) if (!m.empty()) return fail(err.load(), "%s", m.c_str());
-        return fail(err.load(), "packing failed");
-    }
-    return MSNV_OK;
+    const int rc = for_each_index(0, (size_t)n, pool_threads(host_threads, n), 1,
+                                  [&](size_t i) { return pack_sample(*ds, records[i], n_bytes[i], ds->samples[first + i]); },
+                                  [](size_t i) { return "packing sample " + std::to_string(i) + " failed"; });
+    if (rc) ds->samples.resize(first);
+    return rc;
 }
 
 extern "C" int msnv_dataset_pileup_qualities(const msnv_dataset *ds, const uint8_t *records, uint64_t n_bytes, uint8_t *out) {
     clear_error();
     if (!ds || (n_bytes && (!records || !out))) return fail(MSNV_EINVAL, "msnv_dataset_pileup_qualities: NULL argument");
     return pileup_qualities(*ds, records, n_bytes, out);
-}
-
-static int check_header(const msnv_dataset &ds, const BamHeader &h, const char *path) {
-    // metaSNV assumes every BAM shares the header of the first (metaSNV.py:82-83)
-    if (h.names.size() != ds.names.size()) return fail(MSNV_EFORMAT, "%s: header has %zu contigs, expected %zu", path, h.names.size(), ds.names.size());
-    for (size_t i = 0; i < h.names.size(); ++i)
-        if (h.names[i] != ds.names[i] || h.lengths[i] != ds.lengths[i]) return fail(MSNV_EFORMAT, "%s: contig %zu differs from the first BAM's header", path, i);
-    return MSNV_OK;
 }
 
 extern "C" int msnv_dataset_add_sample_bam(msnv_dataset *ds, const char *bam_path) {
@@ -331,333 +252,6 @@ extern "C" int msnv_dataset_add_sample_bam(msnv_dataset *ds, const char *bam_pat
     if (int rc = bam_read(bam_path, h, buf, rec_off, 4)) return rc;
     if (int rc = check_header(*ds, h, bam_path)) return rc;
     return msnv_dataset_add_sample_records(ds, buf.data() + rec_off, buf.size() - rec_off);      // (device pack when the dataset has a context)
-}
-
-namespace msnv {
-struct InfBlock { unsigned long long in_off, out_off; uint32_t in_size, out_size; };
-int dev_inflate_staging(msnv_ctx *ctx, uint64_t in_bytes, uint64_t out_bytes, uint8_t **in, uint8_t **out);
-void dev_inflate_release(msnv_ctx *ctx);
-void dev_inflate_release_device(msnv_ctx *ctx);
-int dev_inflate(msnv_ctx *ctx, uint64_t comp_bytes, const std::vector<InfBlock> &blocks, uint64_t out_bytes, std::vector<uint32_t> &status, double *ms_kernel);
-int dev_inflate_device_buffers(msnv_ctx *ctx, uint64_t in_bytes, uint64_t out_bytes);
-int dev_inflate_resident(msnv_ctx *ctx, const uint8_t *host_in, uint64_t comp_bytes, const std::vector<InfBlock> &blocks, const std::vector<uint32_t> &blk_in_file,
-                         uint32_t check_every, std::vector<uint32_t> &status, double *ms_kernel);
-int dev_inflate_patch(msnv_ctx *ctx, uint64_t out_off, const uint8_t *data, uint32_t n);
-}
-
-// BGZF files inflated on the device (inflate_k.hip).  The files of a batch are read by `threads` host threads straight into the
-// context's pinned staging buffer (no copy of the compressed bytes), their blocks are indexed there, the device inflates all blocks of
-// the batch into the pinned output buffer, and `consume(f0, f1, out, ext)` parses files [f0, f1) in place (no copy of the inflated
-// bytes either; the buffer is reused by the next batch).  Blocks the device refuses are inflated by the host decoder, which words
-// the error of a malformed file.  ext[k]: offset and size of file f0 + k in `out`.
-// counters (optional): [0] blocks, [1] blocks inflated on the host after all, [2] kernel microseconds, [3] inflated bytes.
-struct InflatedExt { uint64_t off, size; };
-// RESIDENT form (res != nullptr; the device pack's: add_bams_device_pack): the inflated bytes never leave HBM.  The files are read into
-// pageable memory (no pinning: a context's first gigabyte of pinned staging costs 0.25 s), the batch goes up as it is, every block's CRC-32
-// is checked by a kernel (inflate_k.hip: msnv_crc_blocks), only the status words come back; the BAM headers are read from the leading
-// blocks of every file by the host decoder (res->hdr / res->rec_off, per file of the batch); a block the device refused or that did not
-// check is inflated by the host decoder and patched into the device buffer.  consume() then gets out = nullptr and dev_valid = true.
-struct ResidentBatch { std::vector<BamHeader> hdr; std::vector<uint64_t> rec_off; };
-// MSNV_FEED_TRACE=1: wall milliseconds between the steps of the device feed, on stderr
-static void feed_mark(const char *what) {
-    const bool on = knob::feed_trace();
-    if (!on) return;
-    static double last = 0;
-    const double now = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    fprintf(stderr, "[feed] %-44s %8.3f ms\n", what, last ? (now - last) * 1e3 : 0.0);
-    last = now;
-}
-template <typename Consume>
-static int bgzf_read_files_device(msnv_ctx *ctx, const char *const *paths, int n, int threads, Consume consume, uint64_t counters[4], ResidentBatch *res = nullptr) {
-    feed_mark("enter");
-    if (int rc = dev_set_device(ctx->device)) return rc;
-    std::vector<uint64_t> fsize((size_t)n, 0);
-    for (int i = 0; i < n; ++i) {
-        FILE *f = fopen(paths[i], "rb");
-        if (!f) return fail(MSNV_EIO, "cannot open %s", paths[i]);
-        fseek(f, 0, SEEK_END);
-        const long sz = ftell(f);
-        fclose(f);
-        if (sz < 0) return fail(MSNV_EIO, "cannot stat %s", paths[i]);
-        fsize[(size_t)i] = (uint64_t)sz;
-    }
-    double ms = 0;
-    uint64_t n_blocks = 0, n_host = 0, n_bytes = 0;
-    // the batch buffers in HBM go back on EVERY way out (a caller that falls back to the host path after an error must not find up to ~4.6 GB
-    // of staging still attached to the context); the pinned half stays for the next call
-    struct ReleaseDevice { msnv_ctx *c; ~ReleaseDevice() { dev_inflate_release_device(c); } } release_device{ctx};
-    // compressed bytes per batch (tests shrink it).  1 GB (~3.6 GB inflated) where the batch goes through pinned staging; 2 GB for the resident form,
-    // which pins nothing: the benchmark's 160 BAMs (1.35 GB) are then ONE batch -- as two, the second one's files were read (page faults of fresh
-    // buffers) while the first one's 1 GB went up from pageable memory (the runtime pinning it page by page), and the launcher waited 90 ms
-    // for that read behind the first batch (MSNV_FEED_TRACE=1: round 5)
-    const uint64_t batch_in = knob::inflate_batch_bytes(res);
-    // RESIDENT form: a batch's host work -- files read into pageable memory, blocks indexed, BAM headers read from the leading blocks -- is done by
-    // load_batch, and the NEXT batch is loaded (std::async) while the device inflates, checks and packs the current one
-    struct Loaded {
-        int f0 = 0, f1 = 0; uint64_t ib = 0;
-        std::vector<uint64_t> in_off; ByteBuf host_in;
-        std::vector<std::vector<BgzfBlock>> blocks; std::vector<uint64_t> total;
-        std::vector<BamHeader> hdr; std::vector<uint64_t> rec_off;
-        int rc = MSNV_OK; std::string msg;
-    };
-    auto batch_extent = [&](int f0, std::vector<uint64_t> &in_off, uint64_t &ib) -> int {
-        int f1 = f0; ib = 0; in_off.clear();
-        while (f1 < n && (f1 == f0 || ib + fsize[(size_t)f1] <= batch_in)) { in_off.push_back(ib); ib += (fsize[(size_t)f1] + 31) & ~15ull; ++f1; }   // 16 bytes of slack behind every file
-        return f1;
-    };
-    auto load_batch = [&](int f0) -> std::unique_ptr<Loaded> {
-        std::unique_ptr<Loaded> L(new Loaded());
-        L->f0 = f0; L->f1 = batch_extent(f0, L->in_off, L->ib);
-        const int nf = L->f1 - f0;
-        auto failed = [&](int rc) { L->rc = rc; L->msg = msnv_last_error(); return std::move(L); };
-        try {
-            if (!L->host_in.alloc(L->ib + 64)) return failed(fail(MSNV_ENOMEM, "out of memory for %llu compressed bytes", (unsigned long long)L->ib));
-            L->blocks.resize((size_t)nf); L->total.assign((size_t)nf, 0); L->hdr.assign((size_t)nf, BamHeader()); L->rec_off.assign((size_t)nf, 0);
-            std::atomic<int> next{0}, err{0};
-            std::vector<std::string> msgs((size_t)nf);
-            auto w = [&]() {
-                for (;;) {
-                    const int k = next.fetch_add(1);
-                    if (k >= nf || err.load()) break;
-                    const char *path = paths[f0 + k];
-                    int rc = MSNV_OK;
-                    try {
-                        uint8_t *dst = L->host_in.data() + L->in_off[(size_t)k];
-                        const uint64_t sz = fsize[(size_t)(f0 + k)];
-                        {
-                            HostTimerScope ts(HT_READ);
-                            FILE *f = fopen(path, "rb");
-                            if (!f) rc = fail(MSNV_EIO, "cannot open %s", path);
-                            else {
-                                if (sz && fread(dst, 1, sz, f) != sz) rc = fail(MSNV_EIO, "short read on %s", path);
-                                fclose(f);
-                            }
-                        }
-                        if (!rc) { memset(dst + sz, 0, 16); rc = bgzf_index_bytes(dst, sz, path, L->blocks[(size_t)k], L->total[(size_t)k]); }
-                        if (!rc) rc = bam_header_from_blocks(dst, L->blocks[(size_t)k], path, L->hdr[(size_t)k], L->rec_off[(size_t)k]);      // (leading blocks, host decoder)
-                    } catch (const std::exception &e) { rc = fail(MSNV_ENOMEM, "%s: %s", path, e.what()); }
-                    if (rc) { msgs[(size_t)k] = msnv_last_error(); err.store(rc); }
-                }
-            };
-            std::vector<std::thread> th;
-            for (int t = 0; t < std::max(1, std::min(threads, nf)); ++t) th.emplace_back(w);
-            for (auto &t : th) t.join();
-            if (err.load()) { L->rc = err.load(); for (const std::string &m : msgs) if (!m.empty()) { L->msg = m; break; } if (L->msg.empty()) L->msg = "BGZF read failed"; }
-        } catch (const std::exception &e) { L->rc = MSNV_ENOMEM; L->msg = e.what(); }
-        return L;
-    };
-    std::future<std::unique_ptr<Loaded>> ahead;
-    struct WaitAhead { std::future<std::unique_ptr<Loaded>> &f; ~WaitAhead() { if (f.valid()) f.wait(); } } wait_ahead{ahead};      // (the loader reads this frame's variables: never leave it running)
-    for (int f0 = 0; f0 < n;) {
-        int f1 = f0; uint64_t ib = 0;
-        std::vector<uint64_t> in_off;
-        std::unique_ptr<Loaded> loaded;
-        if (res) {
-            loaded = ahead.valid() ? ahead.get() : load_batch(f0);
-            feed_mark("batch loaded (files read, blocks indexed)");
-            if (loaded->rc) return fail(loaded->rc, "%s", loaded->msg.c_str());
-            f1 = loaded->f1; ib = loaded->ib; in_off = loaded->in_off;
-            if (f1 < n) ahead = std::async(std::launch::async, load_batch, f1);
-        } else f1 = batch_extent(f0, in_off, ib);
-        uint8_t *in_stage = nullptr, *out = nullptr;
-        // A batch whose staging cannot be had (pinned host memory or HBM: MSNV_ENOMEM) or whose launch fails is inflated by the host
-        // decoder instead -- the call must not fail where the host path would have worked (a multi-GB BAM sizes the staging to itself)
-        bool host_batch = false;
-        ByteBuf host_in, host_out;
-        if (res) {
-            host_in = std::move(loaded->host_in);
-            in_stage = host_in.data();
-        } else if (int rc = dev_inflate_staging(ctx, ib, 0, &in_stage, &out)) {
-            if (rc != MSNV_ENOMEM) return rc;
-            fprintf(stderr, "libmsnv: no staging for the device inflate (%s); this batch is inflated on the host\n", msnv_last_error());
-            clear_error();
-            host_batch = true;
-            if (!host_in.alloc(ib + 64)) return fail(MSNV_ENOMEM, "out of memory for %llu compressed bytes", (unsigned long long)ib);
-            in_stage = host_in.data();
-        }
-        const int nf = f1 - f0;
-        std::vector<std::vector<BgzfBlock>> blocks((size_t)nf);
-        std::vector<uint64_t> total((size_t)nf, 0);
-        if (res) { blocks = std::move(loaded->blocks); total = std::move(loaded->total); }
-        std::atomic<int> next{0}, err{0};
-        std::vector<std::string> msgs((size_t)nf);
-        auto loader = [&]() {
-            for (;;) {
-                const int k = next.fetch_add(1);
-                if (k >= nf || err.load()) break;
-                const char *path = paths[f0 + k];
-                int rc = MSNV_OK;
-                try {
-                    HostTimerScope ts(HT_READ);
-                    uint8_t *dst = in_stage + in_off[(size_t)k];
-                    const uint64_t sz = fsize[(size_t)(f0 + k)];
-                    FILE *f = fopen(path, "rb");
-                    if (!f) rc = fail(MSNV_EIO, "cannot open %s", path);
-                    else {
-                        if (sz && fread(dst, 1, sz, f) != sz) rc = fail(MSNV_EIO, "short read on %s", path);
-                        fclose(f);
-                    }
-                    if (!rc) { memset(dst + sz, 0, 16); rc = bgzf_index_bytes(dst, sz, path, blocks[(size_t)k], total[(size_t)k]); }
-                } catch (const std::exception &e) { rc = fail(MSNV_ENOMEM, "%s: %s", path, e.what()); }
-                if (rc) { msgs[(size_t)k] = msnv_last_error(); err.store(rc); }
-            }
-        };
-        if (!res) {
-            std::vector<std::thread> th;
-            for (int t = 0; t < std::max(1, std::min(threads, nf)); ++t) th.emplace_back(loader);
-            for (auto &t : th) t.join();
-        }
-        if (err.load()) { for (const std::string &m : msgs) if (!m.empty()) return fail(err.load(), "%s", m.c_str()); return fail(err.load(), "BGZF read failed"); }
-        uint64_t ob = 0;
-        std::vector<InfBlock> list;
-        std::vector<int> origin;                                     // file (of the batch) of every entry
-        std::vector<uint32_t> blk_in_file;                           // ... and its index among the file's blocks (MSNV_INFLATE_CHECK counts per file)
-        std::vector<InflatedExt> ext((size_t)nf);
-        for (int k = 0; k < nf; ++k) {
-            ext[(size_t)k] = InflatedExt{ob, total[(size_t)k]};
-            uint32_t bi = 0;
-            for (const BgzfBlock &bl : blocks[(size_t)k]) {
-                const uint32_t this_block = bi++;
-                if (bl.out_size == 0) {                              // nothing for the device to write; the payload must still be an empty stream (the EOF marker is one)
-                    if (!bgzf_inflate_block_host(in_stage + in_off[(size_t)k] + bl.in_off, bl.in_size, nullptr, 0))
-                        return fail(MSNV_EFORMAT, "%s: BGZF inflate failed (malformed DEFLATE stream or CRC-32 mismatch)", paths[f0 + k]);
-                    continue;
-                }
-                list.push_back(InfBlock{in_off[(size_t)k] + bl.in_off, ob + bl.out_off, bl.in_size, bl.out_size});
-                origin.push_back(k); blk_in_file.push_back(this_block);
-            }
-            ob += (total[(size_t)k] + 15) & ~15ull;
-            n_bytes += total[(size_t)k];
-        }
-        if (res) {
-            res->hdr = std::move(loaded->hdr); res->rec_off = std::move(loaded->rec_off);      // (read by load_batch)
-            feed_mark("block list");
-            const int rc_buf = dev_inflate_device_buffers(ctx, ib, ob);
-            feed_mark("device buffers");
-            if (int rc = rc_buf) {
-                if (rc != MSNV_ENOMEM) return rc;
-                fprintf(stderr, "libmsnv: no staging for the device inflate (%s); this batch is inflated on the host\n", msnv_last_error());
-                clear_error();
-                host_batch = true;
-            }
-        } else if (!host_batch) {
-            uint8_t *same_in = nullptr;
-            if (int rc = dev_inflate_staging(ctx, ib, ob, &same_in, &out)) {      // (the input staging does not move: it only grows when ib does)
-                if (rc != MSNV_ENOMEM) return rc;
-                fprintf(stderr, "libmsnv: no staging for the device inflate (%s); this batch is inflated on the host\n", msnv_last_error());
-                clear_error();
-                host_batch = true;
-            }
-        }
-        if (host_batch) {
-            if (!host_out.alloc(ob + 64)) return fail(MSNV_ENOMEM, "out of memory for %llu inflated bytes", (unsigned long long)ob);
-            out = host_out.data();
-        }
-        std::vector<uint32_t> status;
-        bool dev_valid = false;
-        const uint32_t check_every = knob::inflate_check_every();       // (one reading for both decoders)
-        if (!host_batch) {
-            HostTimerScope ts(HT_INFLATE_DEVICE_WALL);
-            int rc = MSNV_OK;
-            if (res && knob::test_resident_fail()) rc = fail_quiet(MSNV_ENOMEM, "resident inflate refused (MSNV_TEST_RESIDENT_FAIL)");      // (tests: the fallback below)
-            else rc = res ? dev_inflate_resident(ctx, in_stage, ib, list, blk_in_file, check_every, status, &ms) : dev_inflate(ctx, ib, list, ob, status, &ms);
-            feed_mark("upload + inflate + check");
-            if (rc) {
-                if (rc != MSNV_ENOMEM && rc != MSNV_EHIP) return rc;
-                fprintf(stderr, "libmsnv: the device inflate failed (%s); this batch is inflated on the host\n", msnv_last_error());
-                clear_error();
-                host_batch = true;
-                // (a resident batch has no host copy of its output yet: the host decoder needs one -- round 4 wrote through a NULL pointer here)
-                if (res) {
-                    if (host_out.size() < ob + 64) { if (!host_out.alloc(ob + 64)) return fail(MSNV_ENOMEM, "out of memory for %llu inflated bytes", (unsigned long long)ob); }
-                    out = host_out.data();
-                }
-            }
-        }
-        if (host_batch) status.assign(list.size(), 1u);
-        // Every block's output is checked against the CRC-32 of its BGZF trailer, as htslib does for the reference's tools (a block that
-        // does not check is handed to the host decoder like one the device refused); the host threads share the blocks.
-        // MSNV_INFLATE_CHECK=n: every n-th block only (0 = none: benchmarks).
-        if (check_every && !(res && !host_batch)) {                // (resident batches were checked by msnv_crc_blocks)
-            std::atomic<size_t> nxt{0};
-            auto checker = [&]() {
-                HostTimerScope ts(HT_INFLATE_HOST);
-                for (;;) {
-                    const size_t e0 = nxt.fetch_add(64);
-                    if (e0 >= list.size()) break;
-                    for (size_t e = e0; e < std::min(list.size(), e0 + 64); ++e) {
-                        if (status[e] || blk_in_file[e] % check_every) continue;
-                        const uint8_t *trailer = in_stage + list[e].in_off + list[e].in_size;
-                        const uint32_t want = (uint32_t)trailer[0] | (uint32_t)trailer[1] << 8 | (uint32_t)trailer[2] << 16 | (uint32_t)trailer[3] << 24;
-                        if (bgzf_crc32(out + list[e].out_off, list[e].out_size) != want) status[e] = 2u;
-                    }
-                }
-            };
-            std::vector<std::thread> th;
-            for (int t = 0; t < std::max(1, std::min<int>(threads, (int)(list.size() / 64) + 1)); ++t) th.emplace_back(checker);
-            for (auto &t : th) t.join();
-        }
-        if (res && !host_batch) {
-            // resident batch: the few blocks the device refused or that did not check are inflated by the host decoder and patched into HBM
-            std::vector<uint8_t> tmp;
-            uint64_t done = 0;
-            for (size_t e = 0; e < list.size(); ++e) {
-                if (!status[e]) continue;
-                HostTimerScope ts(HT_INFLATE_HOST);
-                ++done;
-                tmp.resize((size_t)list[e].out_size + 64);
-                bool ok = bgzf_inflate_block_host(in_stage + list[e].in_off, list[e].in_size, tmp.data(), list[e].out_size);
-                if (ok && check_every) {
-                    const uint8_t *trailer = in_stage + list[e].in_off + list[e].in_size;
-                    const uint32_t want = (uint32_t)trailer[0] | (uint32_t)trailer[1] << 8 | (uint32_t)trailer[2] << 16 | (uint32_t)trailer[3] << 24;
-                    ok = bgzf_crc32(tmp.data(), list[e].out_size) == want;
-                }
-                if (!ok) return fail(MSNV_EFORMAT, "%s: BGZF inflate failed (malformed DEFLATE stream or CRC-32 mismatch)", paths[f0 + origin[e]]);
-                if (int rc = dev_inflate_patch(ctx, list[e].out_off, tmp.data(), list[e].out_size)) return rc;
-            }
-            n_host += done;
-            dev_valid = true;
-        } else {   // blocks the device refused (or all of them, for a host batch): the host decoder, shared by the host threads
-            std::atomic<size_t> nxt{0};
-            std::atomic<int> bad{-1};
-            std::atomic<uint64_t> done{0};
-            auto redo = [&]() {
-                HostTimerScope ts(HT_INFLATE_HOST);
-                for (;;) {
-                    const size_t e0 = nxt.fetch_add(16);
-                    if (e0 >= list.size() || bad.load() >= 0) break;
-                    for (size_t e = e0; e < std::min(list.size(), e0 + 16); ++e) {
-                        if (!status[e]) continue;
-                        done.fetch_add(1);
-                        bool ok = bgzf_inflate_block_host(in_stage + list[e].in_off, list[e].in_size, out + list[e].out_off, list[e].out_size);
-                        if (ok && check_every) {                     // the host decoder's bytes answer to the same trailer
-                            const uint8_t *trailer = in_stage + list[e].in_off + list[e].in_size;
-                            const uint32_t want = (uint32_t)trailer[0] | (uint32_t)trailer[1] << 8 | (uint32_t)trailer[2] << 16 | (uint32_t)trailer[3] << 24;
-                            ok = bgzf_crc32(out + list[e].out_off, list[e].out_size) == want;
-                        }
-                        if (!ok) { int expect = -1; bad.compare_exchange_strong(expect, origin[e]); }
-                    }
-                }
-            };
-            bool any = host_batch;
-            for (size_t e = 0; e < list.size() && !any; ++e) any = status[e] != 0u;
-            if (any) {
-                std::vector<std::thread> th;
-                for (int t = 0; t < std::max(1, host_batch ? threads : std::min(threads, 4)); ++t) th.emplace_back(redo);
-                for (auto &t : th) t.join();
-            }
-            n_host += done.load();
-            if (bad.load() >= 0) return fail(MSNV_EFORMAT, "%s: BGZF inflate failed (malformed DEFLATE stream or CRC-32 mismatch)", paths[f0 + bad.load()]);
-            dev_valid = !host_batch && done.load() == 0;               // every block of the batch as the device wrote it: ctx->dev_out holds the same bytes as `out`
-        }
-        n_blocks += list.size();
-        feed_mark("blocks settled");
-        if (int rc = consume(f0, f1, (const uint8_t *)out, ext, dev_valid)) return rc;
-        feed_mark("batch consumed (statistics, pack)");
-        f0 = f1;
-    }
-    if (counters) { counters[0] = n_blocks; counters[1] = n_host; counters[2] = (uint64_t)(ms * 1000.0); counters[3] = n_bytes; }
-    return MSNV_OK;
 }
 
 // Test / measurement hook: the inflated bytes of one BGZF file, through the device (on_device != 0; needs ctx) or the host decoder.
@@ -686,34 +280,6 @@ extern "C" int msnv_bgzf_inflate(msnv_ctx *ctx, const char *path, int32_t on_dev
     } catch (const std::exception &e) { return fail(MSNV_ENOMEM, "msnv_bgzf_inflate: %s", e.what()); }
 }
 
-// Where the BGZF blocks of a call's files are inflated: on the device when that is the faster way for THIS call.  The device path
-// needs pinned staging for a batch (up to 1 GB compressed + its inflated bytes), and pinning costs ~0.25 s per GB the first time a
-// context does it -- more than 32 host threads need for the whole job of the benchmark shape (160 BAMs, 1.35 GB: device path cold
-// 1.5 s, host decoder 0.4 s; profiles/r03d end-to-end).  So: device when the estimated host time (compressed bytes / threads x
-// ~90 MB/s per thread) exceeds the estimated device time (staging still to pin + both transfers at ~25 GB/s + a launch).
-// MSNV_INFLATE=host | zlib keeps everything on the host, MSNV_INFLATE=device forces the device whatever the size.
-static bool want_device_inflate(msnv_ctx *ctx, const char *const *paths, int n, int threads, bool resident = false) {
-    if (!ctx) return false;
-    if (const char where = knob::inflate_where()) return where == 'd';
-    uint64_t bytes = 0, largest = 0;
-    for (int i = 0; i < n; ++i) {
-        FILE *f = fopen(paths[i], "rb");
-        if (!f) continue;
-        fseek(f, 0, SEEK_END);
-        const long z = ftell(f);
-        fclose(f);
-        if (z > 0) { bytes += (uint64_t)z; largest = std::max<uint64_t>(largest, (uint64_t)z); }
-    }
-    if (bytes < (64ull << 20)) return false;                       // the host decoder is done before the staging is set up
-    const double batch_in = (double)std::max<uint64_t>(std::min<uint64_t>(bytes, 1024ull << 20), largest), batch_out = 3.6 * batch_in;
-    const double to_pin = std::max(0.0, batch_in - (double)ctx->pin_in_cap) + std::max(0.0, batch_out - (double)ctx->pin_out_cap);
-    // (resident: add_bams_device_pack -- nothing is pinned, the compressed bytes go up from pageable memory at ~40 GB/s, the inflated bytes stay
-    // in HBM and are checked there; the kernel writes ~21 GB/s of output on a 160-BAM job: profiles/r04e_inflate_*)
-    const double est_dev = resident ? (double)bytes / 40e9 + 3.6 * (double)bytes / 21e9 + 0.03 : to_pin * 0.25e-9 + (double)bytes * (1.0 + 3.6) / 25e9 + 0.02;
-    const double est_host = (double)bytes / ((double)std::max(1, threads) * 90e6);
-    return est_dev < est_host;
-}
-
 // The record streams of several BAM files (the N-rank driver deals them to the ranks that own their contigs): through the device
 // inflate when a context is given and the files are large enough (the rule of msnv_dataset_add_sample_bams), else one host thread
 // per file.  records[i] (released with msnv_free) holds n_bytes[i] bytes: the alignment records behind the header of bam_paths[i].
@@ -721,12 +287,9 @@ extern "C" int msnv_bam_records_many(msnv_ctx *ctx, const char *const *bam_paths
     clear_error();
     if (n < 0 || (n && (!bam_paths || !records || !n_bytes))) return fail(MSNV_EINVAL, "msnv_bam_records_many: bad argument");
     for (int i = 0; i < n; ++i) { records[i] = nullptr; n_bytes[i] = 0; }
-    int nthreads = host_threads > 0 ? host_threads : (int)msnv_default_threads();
-    nthreads = std::min(nthreads, std::max(1, (int)n));
-    const bool on_device = want_device_inflate(ctx, bam_paths, n, nthreads);
-    std::atomic<int> err{0};
-    std::vector<std::string> msgs((size_t)std::max(n, 0));
-    auto keep = [&](int i, const uint8_t *data, uint64_t size) -> int {      // header parsed, records copied out
+    const int nthreads = pool_threads(host_threads, n);
+    auto name_of = [&](size_t i) { return std::string(bam_paths[i]); };
+    auto keep = [&](size_t i, const uint8_t *data, uint64_t size) -> int {      // header parsed, records copied out
         BamHeader h; uint64_t rec_off = 0;
         if (int rc = bam_parse_header_bytes(data, size, bam_paths[i], h, rec_off)) return rc;
         const uint64_t nb = size - rec_off;
@@ -736,112 +299,22 @@ extern "C" int msnv_bam_records_many(msnv_ctx *ctx, const char *const *bam_paths
         records[i] = p; n_bytes[i] = nb;
         return MSNV_OK;
     };
-    auto run_threads = [&](int lo, int hi, auto body) {
-        std::atomic<int> nxt{lo};
-        auto w = [&]() {
-            for (;;) {
-                const int i = nxt.fetch_add(1);
-                if (i >= hi || err.load()) break;
-                int rc;
-                try { rc = body(i); } catch (const std::exception &e) { rc = fail(MSNV_ENOMEM, "%s: %s", bam_paths[i], e.what()); }
-                if (rc) { msgs[(size_t)i] = msnv_last_error(); err.store(rc); }
-            }
-        };
-        std::vector<std::thread> th;
-        for (int t = 0; t < std::max(1, std::min(nthreads, hi - lo)); ++t) th.emplace_back(w);
-        for (auto &t : th) t.join();
-    };
     int rc = MSNV_OK;
     try {
-        if (on_device) {
+        if (want_device_inflate(ctx, bam_paths, n, nthreads)) {
             auto consume = [&](int f0, int f1, const uint8_t *out, const std::vector<InflatedExt> &ext, bool) -> int {
-                run_threads(f0, f1, [&](int i) { return keep(i, out + ext[(size_t)(i - f0)].off, ext[(size_t)(i - f0)].size); });
-                return err.load();
+                return for_each_index((size_t)f0, (size_t)f1, nthreads, 1, [&](size_t i) { return keep(i, out + ext[i - (size_t)f0].off, ext[i - (size_t)f0].size); }, name_of);
             };
             uint64_t cnt[4];
             rc = bgzf_read_files_device(ctx, bam_paths, n, nthreads, consume, cnt);
-        } else {
-            run_threads(0, n, [&](int i) { ByteBuf buf; if (int r = bgzf_read_all(bam_paths[i], buf, 1)) return r; return keep(i, buf.data(), buf.size()); });
-            rc = err.load();
-        }
+        } else rc = for_each_index(0, (size_t)n, nthreads, 1, [&](size_t i) -> int {
+            ByteBuf buf;
+            if (int r = bgzf_read_all(bam_paths[i], buf, 1)) return r;
+            return keep(i, buf.data(), buf.size());
+        }, name_of);
     } catch (const std::exception &e) { rc = fail(MSNV_ENOMEM, "msnv_bam_records_many: %s", e.what()); }
-    if (rc) {
-        for (int i = 0; i < n; ++i) { free(records[i]); records[i] = nullptr; n_bytes[i] = 0; }
-        for (const std::string &m : msgs) if (!m.empty()) return fail(rc, "%s", m.c_str());
-        return rc;
-    }
-    return MSNV_OK;
-}
-
-// BAM files -> samples with the per-read stage on the device: the files are read and inflated group by group (host threads, or the device
-// inflate when the rule of want_device_inflate picks it), the record streams of a group go to HBM and are packed there (devpack.hip).
-static int add_bams_device_pack(msnv_dataset *ds, const char *const *bam_paths, int n, int nthreads) {
-    const bool inflate_on_device = want_device_inflate(ds->ctx, bam_paths, n, nthreads, true);
-    if (inflate_on_device) {
-        // the inflated bytes of a batch are in the context's device buffer (and, for the CRC check and the header parse, in its pinned
-        // twin): the record streams are handed over where they lie in HBM
-        // (resident form of bgzf_read_files_device: the batch's bytes exist in HBM only, its headers were read from the files' leading blocks)
-        ResidentBatch rb;
-        const size_t first = ds->samples.size(), rounds_at_entry = ds->dp.rounds.size();
-        auto consume = [&](int f0, int f1, const uint8_t *out, const std::vector<InflatedExt> &ext, bool dev_valid) -> int {
-            std::vector<const uint8_t *> ptrs; std::vector<uint64_t> sizes;
-            // (a batch the host decoder had to take -- no room for it in HBM -- is in host memory: it goes up from there)
-            const uint8_t *base = dev_valid ? static_cast<const uint8_t *>(ds->ctx->dev_out) : out;
-            for (int i = f0; i < f1; ++i) {
-                const uint64_t size = ext[(size_t)(i - f0)].size, rec_off = rb.rec_off[(size_t)(i - f0)];
-                if (int rc = check_header(*ds, rb.hdr[(size_t)(i - f0)], bam_paths[i])) return rc;
-                if (rec_off > size) return fail(MSNV_EFORMAT, "%s: truncated BAM header", bam_paths[i]);
-                ptrs.push_back(base + ext[(size_t)(i - f0)].off + rec_off);
-                sizes.push_back(size - rec_off);
-            }
-            // in HBM: the records are read where the inflate kernel wrote them (no copy into a round buffer) when the batch's buffer leaves
-            // the kernels' read-ahead room behind its last stream
-            bool in_place = dev_valid && !(reinterpret_cast<uintptr_t>(base) & 15u) && !knob::pack_copy();
-            for (size_t k = 0; k < ptrs.size() && in_place; ++k) {
-                if (k > 0 && ptrs[k] < ptrs[k - 1] + sizes[k - 1]) in_place = false;
-                if ((uint64_t)(ptrs[k] - base) + sizes[k] + 256 > ds->ctx->dev_out_cap) in_place = false;
-            }
-            return add_streams_device(ds, ptrs.data(), sizes.data(), f1 - f0, dev_valid, in_place ? base : nullptr, in_place ? ds->ctx->dev_out_cap : 0);
-        };
-        int rc;
-        try { uint64_t cnt[4]; rc = bgzf_read_files_device(ds->ctx, bam_paths, n, nthreads, consume, cnt, &rb); }
-        catch (const std::exception &e) { rc = fail(MSNV_ENOMEM, "device inflate: %s", e.what()); }
-        return rc ? fail_multi_add(ds, first, rounds_at_entry, rc) : MSNV_OK;      // (a later batch failed: the earlier batches' samples go too)
-    }
-    const size_t first = ds->samples.size(), rounds_at_entry = ds->dp.rounds.size();
-    const int group = std::max(nthreads, 16);
-    for (int g0 = 0; g0 < n; g0 += group) {
-        const int g1 = std::min(n, g0 + group);
-        std::vector<ByteBuf> bufs((size_t)(g1 - g0));
-        std::vector<uint64_t> rec_off((size_t)(g1 - g0), 0);
-        std::atomic<int> next{g0}, err{0};
-        std::vector<std::string> msgs((size_t)(g1 - g0));
-        auto worker = [&]() {
-            for (;;) {
-                const int i = next.fetch_add(1);
-                if (i >= g1 || err.load()) break;
-                int rc;
-                try {
-                    BamHeader h;
-                    rc = bam_read(bam_paths[i], h, bufs[(size_t)(i - g0)], rec_off[(size_t)(i - g0)], 1);
-                    if (!rc) rc = check_header(*ds, h, bam_paths[i]);
-                } catch (const std::exception &e) { rc = fail(MSNV_ENOMEM, "%s: %s", bam_paths[i], e.what()); }
-                if (rc) { msgs[(size_t)(i - g0)] = msnv_last_error(); err.store(rc); }
-            }
-        };
-        std::vector<std::thread> th;
-        for (int t = 0; t < std::min(nthreads, g1 - g0); ++t) th.emplace_back(worker);
-        for (auto &t : th) t.join();
-        int rc = err.load();
-        if (rc) { for (const std::string &m : msgs) if (!m.empty()) { fail(rc, "%s", m.c_str()); break; } }
-        if (!rc) {
-            std::vector<const uint8_t *> ptrs; std::vector<uint64_t> sizes;
-            for (int i = g0; i < g1; ++i) { ptrs.push_back(bufs[(size_t)(i - g0)].data() + rec_off[(size_t)(i - g0)]); sizes.push_back(bufs[(size_t)(i - g0)].size() - rec_off[(size_t)(i - g0)]); }
-            rc = add_streams_device(ds, ptrs.data(), sizes.data(), g1 - g0, false);
-        }
-        if (rc) return fail_multi_add(ds, first, rounds_at_entry, rc);
-    }
-    return MSNV_OK;
+    if (rc) for (int i = 0; i < n; ++i) { free(records[i]); records[i] = nullptr; n_bytes[i] = 0; }
+    return rc;
 }
 
 // The N-rank feed's decode + deal step without a host copy of the inflated bytes: the files' BGZF blocks are inflated and checked on the device
@@ -854,22 +327,9 @@ extern "C" int msnv_dataset_deal_bams_device(msnv_dataset *ds, const char *const
     if (n == 0) return MSNV_OK;
     msnv_ctx *const fc = ds->feed_ctx ? ds->feed_ctx : ds->ctx;      // (msnv_dataset_set_feed_ctx: a round ahead of the dataset's own context)
     if (int rc = dev_set_device(fc->device)) return rc;
-    int nthreads = host_threads > 0 ? host_threads : (int)msnv_default_threads();
-    nthreads = std::min(nthreads, std::max(1, (int)n));
-    {   // one batch of the device inflate only: the parts of a call lie destination-major in `out`
-        const uint64_t batch_in = knob::inflate_batch_bytes();
-        uint64_t ib = 0;
-        for (int i = 0; i < n; ++i) {
-            FILE *f = fopen(bam_paths[i], "rb");
-            if (!f) return fail(MSNV_EIO, "cannot open %s", bam_paths[i]);
-            fseek(f, 0, SEEK_END);
-            const long z = ftell(f);
-            fclose(f);
-            if (z < 0) return fail(MSNV_EIO, "cannot stat %s", bam_paths[i]);
-            ib += ((uint64_t)z + 31) & ~15ull;
-        }
-        if (n > 1 && ib > batch_in) return fail_quiet(MSNV_EDOMAIN, "msnv_dataset_deal_bams_device: the files of the call do not fit one batch of the device inflate (%llu bytes)", (unsigned long long)ib);
-    }
+    const int nthreads = pool_threads(host_threads, n);
+    // one batch of the device inflate only: the parts of a call lie destination-major in `out`
+    if (int rc = fits_one_batch("msnv_dataset_deal_bams_device", bam_paths, n)) return rc;
     const int NC = (int)ds->names.size();
     ResidentBatch rb;
     int calls = 0;
@@ -877,14 +337,8 @@ extern "C" int msnv_dataset_deal_bams_device(msnv_dataset *ds, const char *const
         if (calls++ || f0 != 0 || f1 != n) return fail(MSNV_EINVAL, "internal: msnv_dataset_deal_bams_device expects one batch");
         std::vector<const uint8_t *> ptrs; std::vector<uint64_t> sizes;
         const uint8_t *base = dev_valid ? static_cast<const uint8_t *>(fc->dev_out) : host_out;      // (a batch the host decoder had to take lies in host memory)
-        for (int i = 0; i < n; ++i) {
-            const uint64_t size = ext[(size_t)i].size, rec_off = rb.rec_off[(size_t)i];
-            if (int rc = check_header(*ds, rb.hdr[(size_t)i], bam_paths[i])) return rc;
-            if (rec_off > size) return fail(MSNV_EFORMAT, "%s: truncated BAM header", bam_paths[i]);
-            ptrs.push_back(base + ext[(size_t)i].off + rec_off);
-            sizes.push_back(size - rec_off);
-            record_bytes[i] = size - rec_off;
-        }
+        if (int rc = resident_streams(*ds, bam_paths, 0, n, rb, ext, base, ptrs, sizes)) return rc;
+        std::copy(sizes.begin(), sizes.end(), record_bytes);
         return records_deal_device(fc, ptrs.data(), sizes.data(), n, dev_valid, contig_owner, NC, n_parts, cov_min_mapq, out, capacity, gap, part_bytes, stats, nullptr);
     };
     try { uint64_t cnt[4]; return bgzf_read_files_device(fc, bam_paths, n, nthreads, consume, cnt, &rb); }
@@ -902,39 +356,24 @@ extern "C" int msnv_dataset_inflate_bams_device(msnv_dataset *ds, const char *co
     if (n == 0) return MSNV_OK;
     msnv_ctx *const fc = ds->feed_ctx ? ds->feed_ctx : ds->ctx;
     if (int rc = dev_set_device(fc->device)) return rc;
-    int nthreads = host_threads > 0 ? host_threads : (int)msnv_default_threads();
-    nthreads = std::min(nthreads, std::max(1, (int)n));
-    {
-        const uint64_t batch_in = knob::inflate_batch_bytes();
-        uint64_t ib = 0;
-        for (int i = 0; i < n; ++i) {
-            FILE *f = fopen(bam_paths[i], "rb");
-            if (!f) return fail(MSNV_EIO, "cannot open %s", bam_paths[i]);
-            fseek(f, 0, SEEK_END);
-            const long z = ftell(f);
-            fclose(f);
-            if (z < 0) return fail(MSNV_EIO, "cannot stat %s", bam_paths[i]);
-            ib += ((uint64_t)z + 31) & ~15ull;
-        }
-        if (n > 1 && ib > batch_in) return fail_quiet(MSNV_EDOMAIN, "msnv_dataset_inflate_bams_device: the files of the call do not fit one batch of the device inflate (%llu bytes)", (unsigned long long)ib);
-    }
+    const int nthreads = pool_threads(host_threads, n);
+    if (int rc = fits_one_batch("msnv_dataset_inflate_bams_device", bam_paths, n)) return rc;
     const int NC = (int)ds->names.size();
     ResidentBatch rb;
     int calls = 0;
     auto consume = [&](int f0, int f1, const uint8_t *host_out, const std::vector<InflatedExt> &ext, bool dev_valid) -> int {
         if (calls++ || f0 != 0 || f1 != n) return fail(MSNV_EINVAL, "internal: msnv_dataset_inflate_bams_device expects one batch");
-        std::vector<const uint8_t *> ptrs; std::vector<uint64_t> sizes;
+        std::vector<const uint8_t *> src, ptrs; std::vector<uint64_t> sizes;
         const uint8_t *base = dev_valid ? static_cast<const uint8_t *>(fc->dev_out) : host_out;
+        if (int rc = resident_streams(*ds, bam_paths, 0, n, rb, ext, base, src, sizes)) return rc;
         uint64_t o = 0;
         for (int i = 0; i < n; ++i) {
-            const uint64_t size = ext[(size_t)i].size, ro = rb.rec_off[(size_t)i];
-            if (int rc = check_header(*ds, rb.hdr[(size_t)i], bam_paths[i])) return rc;
-            if (ro > size) return fail(MSNV_EFORMAT, "%s: truncated BAM header", bam_paths[i]);
-            rec_off[i] = o; rec_bytes[i] = size - ro;
-            if (o + (size - ro) + 32 > capacity) return fail_quiet(MSNV_ECAPACITY, "msnv_dataset_inflate_bams_device: the output holds %llu bytes, more are needed", (unsigned long long)capacity);
-            if (size - ro) if (int rc = dev_copy_bytes(out + o, base + ext[(size_t)i].off + ro, size - ro, dev_valid, fc->stream)) return rc;
-            ptrs.push_back(out + o); sizes.push_back(size - ro);
-            o += (size - ro + 31) & ~15ull;                       // (16 readable bytes behind every stream)
+            const uint64_t sz = sizes[(size_t)i];
+            rec_off[i] = o; rec_bytes[i] = sz;
+            if (o + sz + 32 > capacity) return fail_quiet(MSNV_ECAPACITY, "msnv_dataset_inflate_bams_device: the output holds %llu bytes, more are needed", (unsigned long long)capacity);
+            if (sz) if (int rc = dev_copy_bytes(out + o, src[(size_t)i], sz, dev_valid, fc->stream)) return rc;
+            ptrs.push_back(out + o);
+            o += (sz + 31) & ~15ull;                              // (16 readable bytes behind every stream)
         }
         std::vector<int32_t> nobody((size_t)std::max(1, NC), -1);
         std::vector<uint64_t> pb((size_t)n, 0);
@@ -949,74 +388,36 @@ extern "C" int msnv_dataset_add_sample_bams(msnv_dataset *ds, const char *const 
     HostTimerScope ts_all(HT_ADD_WALL);
     if (!ds || (n && !bam_paths)) return fail(MSNV_EINVAL, "msnv_dataset_add_sample_bams: NULL argument");
     if (int rc = check_open(ds)) return rc;
-    int nthreads = host_threads > 0 ? host_threads : (int)msnv_default_threads();
-    nthreads = std::min(nthreads, std::max(1, (int)n));
+    const int nthreads = pool_threads(host_threads, n);
     if (pack_on_device(ds)) return add_bams_device_pack(ds, bam_paths, n, nthreads);
     const size_t first = ds->samples.size();
     ds->samples.resize(first + (size_t)n);
-    std::atomic<int> next{0}, err{0};
-    std::vector<std::string> msgs((size_t)n);
-    // MSNV_INFLATE=device: the BGZF blocks of the files are inflated on the device (inflate_k.hip: a wavefront per block, thousands of
-    // blocks at a time), batch by batch; the host threads read the files in front of it and parse / pack the batch's bytes in place
-    bool on_device = want_device_inflate(ds->ctx, bam_paths, n, nthreads);
-    auto pack_one = [&](int i, const uint8_t *data, uint64_t size, BamHeader &h, uint64_t rec_off) -> int {
+    auto name_of = [&](size_t i) { return std::string(bam_paths[i]); };
+    auto pack_one = [&](size_t i, const uint8_t *data, uint64_t size, const BamHeader &h, uint64_t rec_off) -> int {
         if (int rc = check_header(*ds, h, bam_paths[i])) return rc;
-        return pack_sample(*ds, data + rec_off, size - rec_off, ds->samples[first + (size_t)i]);
+        return pack_sample(*ds, data + rec_off, size - rec_off, ds->samples[first + i]);
     };
-    if (on_device) {
+    int rc;
+    if (want_device_inflate(ds->ctx, bam_paths, n, nthreads)) {
+        // MSNV_INFLATE=device: the BGZF blocks of the files are inflated on the device (inflate_k.hip: a wavefront per block, thousands of
+        // blocks at a time), batch by batch; the host threads read the files in front of it and parse / pack the batch's bytes in place
         auto consume = [&](int f0, int f1, const uint8_t *out, const std::vector<InflatedExt> &ext, bool) -> int {
-            std::atomic<int> nxt{f0};
-            auto w = [&]() {
-                for (;;) {
-                    const int i = nxt.fetch_add(1);
-                    if (i >= f1 || err.load()) break;
-                    int rc;
-                    try {
-                        BamHeader h; uint64_t rec_off = 0;
-                        const uint8_t *data = out + ext[(size_t)(i - f0)].off; const uint64_t size = ext[(size_t)(i - f0)].size;
-                        rc = bam_parse_header_bytes(data, size, bam_paths[i], h, rec_off);
-                        if (!rc) rc = pack_one(i, data, size, h, rec_off);
-                    } catch (const std::exception &e) { rc = fail(MSNV_ENOMEM, "%s: %s", bam_paths[i], e.what()); }
-                    if (rc) { msgs[(size_t)i] = msnv_last_error(); err.store(rc); }
-                }
-            };
-            std::vector<std::thread> th;
-            for (int t = 0; t < std::max(1, std::min(nthreads, f1 - f0)); ++t) th.emplace_back(w);
-            for (auto &t : th) t.join();
-            return err.load();
+            return for_each_index((size_t)f0, (size_t)f1, nthreads, 1, [&](size_t i) -> int {
+                BamHeader h; uint64_t rec_off = 0;
+                const uint8_t *data = out + ext[i - (size_t)f0].off; const uint64_t size = ext[i - (size_t)f0].size;
+                if (int r = bam_parse_header_bytes(data, size, bam_paths[i], h, rec_off)) return r;
+                return pack_one(i, data, size, h, rec_off);
+            }, name_of);
         };
-        int rc;
         try { uint64_t cnt[4]; rc = bgzf_read_files_device(ds->ctx, bam_paths, n, nthreads, consume, cnt); }
         catch (const std::exception &e) { rc = fail(MSNV_ENOMEM, "device inflate: %s", e.what()); }
-        if (rc) {
-            ds->samples.resize(first);
-            for (const std::string &m : msgs) if (!m.empty()) return fail(rc, "%s", m.c_str());
-            return rc;
-        }
-        return MSNV_OK;
-    }
-    auto worker = [&]() {
-        for (;;) {
-            int i = next.fetch_add(1);
-            if (i >= n || err.load()) break;
-            int rc;
-            try {                                              // an exception in a worker thread would be std::terminate
-                BamHeader h; ByteBuf buf; uint64_t rec_off = 0;
-                rc = bam_read(bam_paths[i], h, buf, rec_off, 1);
-                if (!rc) rc = pack_one(i, buf.data(), buf.size(), h, rec_off);
-            } catch (const std::exception &e) { rc = fail(MSNV_ENOMEM, "%s: %s", bam_paths[i], e.what()); }
-            if (rc) { msgs[(size_t)i] = msnv_last_error(); err.store(rc); }
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 0; t < nthreads; ++t) th.emplace_back(worker);
-    for (auto &t : th) t.join();
-    if (err.load()) {
-        ds->samples.resize(first);
-        for (const std::string &m : msgs) if (!m.empty()) return fail(err.load(), "%s", m.c_str());
-        return fail(err.load(), "BAM decode failed");
-    }
-    return MSNV_OK;
+    } else rc = for_each_index(0, (size_t)n, nthreads, 1, [&](size_t i) -> int {
+        BamHeader h; ByteBuf buf; uint64_t rec_off = 0;
+        if (int r = bam_read(bam_paths[i], h, buf, rec_off, 1)) return r;
+        return pack_one(i, buf.data(), buf.size(), h, rec_off);
+    }, name_of);
+    if (rc) ds->samples.resize(first);
+    return rc;
 }
 
 // BAM files read, inflated and header-checked by the host threads, their record streams KEPT as they are: msnv_dataset_finalize packs them,
@@ -1028,43 +429,25 @@ extern "C" int msnv_dataset_stage_sample_bams(msnv_dataset *ds, const char *cons
     if (!ds || n < 0 || (n && !bam_paths)) return fail(MSNV_EINVAL, "msnv_dataset_stage_sample_bams: bad argument");
     if (int rc = check_open(ds, true)) return rc;
     if (!ds->samples.empty()) return fail(MSNV_EINVAL, "msnv_dataset_stage_sample_bams: the dataset already holds packed samples (staged streams are packed last)");
-    int nthreads = host_threads > 0 ? host_threads : (int)msnv_default_threads();
-    nthreads = std::min(nthreads, std::max(1, (int)n));
+    const int nthreads = pool_threads(host_threads, n);
     const size_t first = ds->staged.size();
     ds->staged.resize(first + (size_t)n); ds->staged_off.resize(first + (size_t)n, 0);
-    std::atomic<int> next{0}, err{0};
-    std::vector<std::string> msgs((size_t)n);
     // largest files first: the threads take files from one queue, so the last ones to be started are the small ones and no thread is left
     // alone with a large file at the end (160 files on 32 threads: the tail was a file's ~60 ms)
     std::vector<int> order((size_t)n);
     {
-        std::vector<long> fsz((size_t)n, 0);
-        for (int i = 0; i < n; ++i) { order[(size_t)i] = i; struct stat sb; if (stat(bam_paths[i], &sb) == 0) fsz[(size_t)i] = (long)sb.st_size; }
+        std::vector<uint64_t> fsz((size_t)n, 0);
+        for (int i = 0; i < n; ++i) { order[(size_t)i] = i; (void)file_size(bam_paths[i], &fsz[(size_t)i]); }      // (a file that cannot be sized: bam_read words that)
         std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return fsz[(size_t)a] > fsz[(size_t)b]; });
     }
-    auto worker = [&]() {
-        for (;;) {
-            const int k = next.fetch_add(1);
-            if (k >= n || err.load()) break;
-            const int i = order[(size_t)k];
-            int rc;
-            try {
-                BamHeader h;
-                rc = bam_read(bam_paths[i], h, ds->staged[first + (size_t)i], ds->staged_off[first + (size_t)i], 1);
-                if (!rc) rc = check_header(*ds, h, bam_paths[i]);
-            } catch (const std::exception &e) { rc = fail(MSNV_ENOMEM, "%s: %s", bam_paths[i], e.what()); }
-            if (rc) { msgs[(size_t)i] = msnv_last_error(); err.store(rc); }
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 0; t < nthreads; ++t) th.emplace_back(worker);
-    for (auto &t : th) t.join();
-    if (err.load()) {
-        ds->staged.resize(first); ds->staged_off.resize(first);
-        for (const std::string &m : msgs) if (!m.empty()) return fail(err.load(), "%s", m.c_str());
-        return fail(err.load(), "BAM decode failed");
-    }
-    return MSNV_OK;
+    const int rc = for_each_index(0, (size_t)n, nthreads, 1, [&](size_t k) -> int {
+        const size_t i = (size_t)order[k];
+        BamHeader h;
+        if (int r = bam_read(bam_paths[i], h, ds->staged[first + i], ds->staged_off[first + i], 1)) return r;
+        return check_header(*ds, h, bam_paths[i]);
+    }, [&](size_t k) { return std::string(bam_paths[order[k]]); });
+    if (rc) { ds->staged.resize(first); ds->staged_off.resize(first); }
+    return rc;
 }
 
 extern "C" int msnv_dataset_add_synth_samples(msnv_dataset *ds, const msnv_synth_params *p, int32_t first, int32_t count, int32_t host_threads) {
@@ -1072,9 +455,9 @@ extern "C" int msnv_dataset_add_synth_samples(msnv_dataset *ds, const msnv_synth
     if (!ds || !p || count < 0) return fail(MSNV_EINVAL, "msnv_dataset_add_synth_samples: bad argument");
     if (int rc = check_open(ds)) return rc;
     if ((size_t)msnv_synth_contig_count(p) != ds->names.size()) return fail(MSNV_EINVAL, "synthetic parameters describe %d contigs, dataset has %zu", msnv_synth_contig_count(p), ds->names.size());
-    int nthreads = host_threads > 0 ? host_threads : (int)msnv_default_threads();
-    nthreads = std::min(nthreads, std::max(1, (int)count));
+    const int nthreads = pool_threads(host_threads, count);
     const std::vector<std::string> contigs = synth_contigs(*p);
+    auto name_of = [&](size_t i) { return "synthetic sample " + std::to_string(first + (int)i); };
     if (pack_on_device(ds)) {
         // record streams are made by the host threads, group by group, and packed in HBM
         const size_t base0 = ds->samples.size(), rounds_at_entry = ds->dp.rounds.size();
@@ -1082,19 +465,9 @@ extern "C" int msnv_dataset_add_synth_samples(msnv_dataset *ds, const msnv_synth
         for (int g0 = 0; g0 < count; g0 += group) {
             const int g1 = std::min<int>(count, g0 + group);
             std::vector<std::vector<uint8_t>> recs((size_t)(g1 - g0));
-            std::atomic<int> nxt{g0}, bad{0};
             const auto t_synth = std::chrono::steady_clock::now();     // (wall seconds of MAKING the group's streams: the generator, not the product)
-            auto w = [&]() {
-                for (;;) {
-                    const int i = nxt.fetch_add(1);
-                    if (i >= g1) break;
-                    try { synth_sample_records(*p, first + i, contigs, recs[(size_t)(i - g0)]); } catch (const std::exception &) { bad.store(1); }
-                }
-            };
-            std::vector<std::thread> th;
-            for (int t = 0; t < std::min(nthreads, g1 - g0); ++t) th.emplace_back(w);
-            for (auto &t : th) t.join();
-            if (bad.load()) return fail_multi_add(ds, base0, rounds_at_entry, fail(MSNV_ENOMEM, "making a synthetic sample failed"));
+            if (for_each_index((size_t)g0, (size_t)g1, nthreads, 1, [&](size_t i) { synth_sample_records(*p, first + (int)i, contigs, recs[i - (size_t)g0]); return (int)MSNV_OK; }, name_of))
+                return fail_multi_add(ds, base0, rounds_at_entry, fail(MSNV_ENOMEM, "making a synthetic sample failed"));
             host_timer_add(HT_SYNTH_WALL, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_synth).count());
             std::vector<const uint8_t *> ptrs; std::vector<uint64_t> sizes;
             for (auto &r : recs) { ptrs.push_back(r.data()); sizes.push_back(r.size()); }
@@ -1104,25 +477,12 @@ extern "C" int msnv_dataset_add_synth_samples(msnv_dataset *ds, const msnv_synth
     }
     const size_t base = ds->samples.size();
     ds->samples.resize(base + (size_t)count);
-    std::atomic<int> next{0}, err{0};
-    std::string msg;
-    auto worker = [&]() {
-        std::vector<uint8_t> rec;
-        for (;;) {
-            int i = next.fetch_add(1);
-            if (i >= count || err.load()) break;
-            int rc;
-            try {
-                synth_sample_records(*p, first + i, contigs, rec);
-                rc = pack_sample(*ds, rec.data(), rec.size(), ds->samples[base + (size_t)i]);
-            } catch (const std::exception &) { rc = MSNV_ENOMEM; }
-            if (rc) { err.store(rc); }
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 0; t < nthreads; ++t) th.emplace_back(worker);
-    for (auto &t : th) t.join();
-    if (err.load()) { ds->samples.resize(base); return fail(err.load(), "packing a synthetic sample failed"); }
+    const int rc = for_each_index(0, (size_t)count, nthreads, 1, [&](size_t i) -> int {
+        thread_local std::vector<uint8_t> rec;                       // (a worker's buffer, reused from sample to sample)
+        synth_sample_records(*p, first + (int)i, contigs, rec);
+        return pack_sample(*ds, rec.data(), rec.size(), ds->samples[base + i]);
+    }, name_of);
+    if (rc) { ds->samples.resize(base); return fail(rc, "packing a synthetic sample failed"); }
     return MSNV_OK;
 }
 
@@ -1226,7 +586,6 @@ extern "C" int msnv_dataset_info_get(const msnv_dataset *ds, msnv_dataset_info *
 }
 
 // ------------------------------------------------------------------------------ pipeline
-namespace msnv { int dev_reserve_passes(DeviceCols &d, int n); }
 extern "C" int msnv_pileup_reserve(msnv_dataset *ds, int32_t n) {
     clear_error();
     if (!ds || !ds->finalized || n <= 0) return fail(MSNV_EINVAL, "msnv_pileup_reserve: dataset is not finalized or n <= 0");
@@ -1568,11 +927,6 @@ extern "C" int msnv_write_calls_cells(const msnv_ref_desc *ref, int32_t n_sample
     return write_gathered(tmp, ref, n_sites, called_path, indiv_path, ann_path, fasta_path, ann);
 }
 
-namespace msnv {
-int text_call(msnv_ctx *ctx, const char *text, uint64_t n_text, const msnv_params &p, const char *ref_fasta, const char *ann_path,
-              const char *called_path, const char *indiv_path, uint64_t stats[8]);
-}
-
 extern "C" int msnv_call_from_mpileup(msnv_ctx *ctx, const msnv_mpileup_args *a, uint64_t stats[8]) {
     clear_error();
     if (!ctx || !a || !a->out_called_path) return fail(MSNV_EINVAL, "msnv_call_from_mpileup: NULL argument");
@@ -1632,18 +986,6 @@ extern "C" int msnv_write_coverage(msnv_dataset *ds, int32_t sample_idx, const c
 }
 
 // ------------------------------------------------------------------------------ multi-GPU: decode sharding + gathered coverage
-namespace msnv {
-int records_partition(const uint8_t *rec, uint64_t n_bytes, const int32_t *owner, int n_contigs, int n_parts, int cov_min_mapq,
-                      uint8_t *out, uint64_t *part_bytes, msnv_sample_stats &st);
-int coverage_write_rows(const std::vector<std::string> &names, const std::vector<int64_t> &lengths, int max_cov, const msnv_sample_stats &sc,
-                        const unsigned long long *acc, const char *cov_path, const char *detail_path, int sample, const int32_t *median);
-int coverage_extras_run(msnv_dataset &ds, const msnv_cov_extras &what);
-int coverage_window_count(const msnv_dataset &ds, uint64_t *n);
-int coverage_window_sums(const msnv_dataset &ds, int sample, uint64_t *out);
-int coverage_write_ex(msnv_dataset &ds, int sample, const char *cov_path, const char *detail_path, const char *profile_path, const char *specific_path,
-                      const msnv_cov_region *regions, uint32_t n_regions);
-int coverage_regions_parse(const char *path, std::vector<std::string> &names, std::vector<int32_t> &starts, std::vector<int32_t> &ends, std::vector<std::string> &aliases);
-}
 static_assert(MSNV_COV_WORDS == 1 + COV_BINS, "msnv.h and device.h disagree on the accumulator width");
 
 // ------------------------------------------------------------------------------ qaCompute -m / -p / -x (covext.cpp, covext_k.hip)
@@ -1810,11 +1152,6 @@ extern "C" int msnv_write_coverage_records(const msnv_ref_desc *ref, int32_t max
 }
 
 // ------------------------------------------------------------------------------ filter_two (section 8 f1)
-namespace msnv {
-int filter_files(msnv_ctx *ctx, const char *const *paths, int n_paths, uint32_t n_samples, const FilterSpecies &sp,
-                 double min_cov, double min_prop, const char *out_dir, uint64_t *n_lines_kept, double *ms_kernel);
-}
-namespace msnv { void py_repr(double x, std::string &out); }
 static int make_filter_species(const msnv_filter_species *species, int32_t n_species, int32_t n_samples, FilterSpecies &sp, const char *who);
 extern "C" int msnv_format_float(double x, char *buf, int32_t cap) {
     std::string s;
@@ -1839,10 +1176,6 @@ extern "C" int msnv_filter_files(msnv_ctx *ctx, const char *const *snp_paths, in
     return filter_files(ctx, snp_paths, n_paths, (uint32_t)n_samples, sp, min_cov_c, min_prop_p, out_dir, n_positions_kept, ms_kernel);
 }
 
-namespace msnv {
-int filter_resident(msnv_dataset &ds, int which, const FilterSpecies &sp, double min_cov, double min_prop, const char *out_dir,
-                    const msnv_site_ann *ann, const std::vector<std::string> *gene_names, uint64_t *n_lines_kept, double *ms_kernel);
-}
 static int make_filter_species(const msnv_filter_species *species, int32_t n_species, int32_t n_samples, FilterSpecies &sp, const char *who) {
     sp.soi_off.push_back(0);
     for (int i = 0; i < n_species; ++i) {
@@ -1885,11 +1218,6 @@ extern "C" int msnv_filter_resident(msnv_dataset *ds, int32_t which, const msnv_
 }
 
 // ------------------------------------------------------------------------------ --dist (section 8 f3)
-namespace msnv {
-int dist_file(msnv_ctx *ctx, const char *freq_path, const char *mann_path, const char *allele_path, double threshold,
-              int32_t *n_samples_out, uint64_t *n_pos_out, double *ms_kernel);
-}
-namespace msnv { bool pandas_strtod(const char *s, const char *end, double &out); }
 extern "C" int msnv_parse_float(const char *text, double *value) {
     clear_error();
     if (!text || !value) return fail(MSNV_EINVAL, "msnv_parse_float: NULL argument");
@@ -1907,11 +1235,6 @@ extern "C" int msnv_dist_file(msnv_ctx *ctx, const char *freq_path, const char *
 }
 
 // ------------------------------------------------------------------------------ --div / --divNS
-namespace msnv {
-int div_file(msnv_ctx *ctx, const char *freq_path, int32_t mode, int32_t matched, int64_t genome_length, const double *h, const double *v,
-             int32_t n_cov, const int64_t *row_order, uint64_t n_order, const char *out_a, const char *out_b, int32_t *n_samples_out,
-             uint64_t *n_rows_out, double *ms_kernel);
-}
 extern "C" int msnv_div_file(msnv_ctx *ctx, const char *freq_path, int32_t mode, int32_t matched, int64_t genome_length,
                              const double *horizontal, const double *vertical, int32_t n_samples_cov, const int64_t *row_order,
                              uint64_t n_rows_order, const char *out_a, const char *out_b, int32_t *n_samples, uint64_t *n_rows,

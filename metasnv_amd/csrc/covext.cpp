@@ -11,9 +11,6 @@
 
 namespace msnv {
 
-int coverage_write_rows(const std::vector<std::string> &names, const std::vector<int64_t> &lengths, int max_cov, const msnv_sample_stats &sc,
-                        const unsigned long long *acc, const char *cov_path, const char *detail_path, int sample, const int32_t *median);
-
 // windows of a contig of L indices: the loop of qaCompute.cpp:175-182 prints one at every i = W, 2 W, ... < L, the trailing line (:183)
 // exists unless (L - 1) % W == 0 -- none at all for L == 1
 static uint64_t window_count(int64_t L, uint32_t W) {

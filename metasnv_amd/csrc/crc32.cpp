@@ -16,8 +16,6 @@
 
 namespace msnv {
 
-uint32_t crc32_pclmul_fold(uint32_t state, const uint8_t *p, size_t n);      // crc32_pclmul.cpp: n >= 64, a multiple of 16; state = ~crc in, ~crc out
-
 namespace {
 
 uint32_t g_tab[8][256];

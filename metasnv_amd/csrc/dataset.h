@@ -179,6 +179,27 @@ struct DevPackTables {
 }  // namespace msnv
 struct msnv_dataset;
 namespace msnv {
+// ---- the host stages over a dataset
+// pack.cpp: the per-read stage on host threads, the qualities as the pileup engine sees them, the tile index + upload, a stream dealt by contig owner
+int pack_sample(const msnv_dataset &ds, const uint8_t *rec, uint64_t n_bytes, SampleCols &sc);
+int pileup_qualities(const msnv_dataset &ds, const uint8_t *rec, uint64_t n_bytes, uint8_t *out);
+int finalize_dataset(msnv_dataset &ds);
+int records_partition(const uint8_t *rec, uint64_t n_bytes, const int32_t *owner, int n_contigs, int n_parts, int cov_min_mapq,
+                      uint8_t *out, uint64_t *part_bytes, msnv_sample_stats &st);
+// format.cpp: called_SNPs / indiv_called of the fetched sites
+int write_calls_text(msnv_dataset &ds, const char *called_path, const char *indiv_path, const msnv_site_ann *ann, const std::vector<std::string> *gene_names);
+// coverage.cpp, covext.cpp: qaCompute's pass, its output files, its -m / -p / -x extras
+int coverage_run(msnv_dataset &ds, msnv_run_stats *stats);
+int coverage_write(msnv_dataset &ds, int sample, const char *cov_path, const char *detail_path);
+int coverage_write_rows(const std::vector<std::string> &names, const std::vector<int64_t> &lengths, int max_cov, const msnv_sample_stats &sc,
+                        const unsigned long long *acc, const char *cov_path, const char *detail_path, int sample, const int32_t *median);
+int coverage_extras_run(msnv_dataset &ds, const msnv_cov_extras &what);
+int coverage_window_count(const msnv_dataset &ds, uint64_t *n);
+int coverage_window_sums(const msnv_dataset &ds, int sample, uint64_t *out);
+int coverage_write_ex(msnv_dataset &ds, int sample, const char *cov_path, const char *detail_path, const char *profile_path, const char *specific_path,
+                      const msnv_cov_region *regions, uint32_t n_regions);
+int coverage_regions_parse(const char *path, std::vector<std::string> &names, std::vector<int32_t> &starts, std::vector<int32_t> &ends, std::vector<std::string> &aliases);
+
 // The per-sample records of fetched site i, one entry per sample: a pointer into the dense form when the dataset holds it, else the
 // site's cells expanded into `scratch` (S entries, all zero between calls: the entries a call touches are zeroed again by the next).
 struct SiteRowView {
@@ -217,7 +238,7 @@ struct msnv_dataset {
     // samples
     std::vector<msnv::SampleCols> samples;
     bool finalized = false;
-    bool poisoned = false;          // an add_* call failed AFTER rounds of the device pack had been appended (api.cpp: add_streams_device): nothing more is added or finalized
+    bool poisoned = false;          // an add_* call failed AFTER rounds of the device pack had been appended (bamfeed.cpp: add_streams_device): nothing more is added or finalized
     // layout
     std::vector<uint32_t> tile_base;       // per contig (selected only; others = UINT32_MAX)
     std::vector<uint32_t> tile_contig;     // per tile

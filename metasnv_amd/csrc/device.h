@@ -205,5 +205,33 @@ int  dev_run_coverage_extras(DeviceCols &d, CovxJob &job, void *stream);
 int  dev_run_pipeline(DeviceCols &d, const msnv_params &p, void *stream, msnv_run_stats *stats, RunCounts *counts);
 int  dev_run_pipeline_many(DeviceCols &d, const msnv_params &p, void *stream, int n, bool overlap, msnv_run_stats *stats, RunCounts *counts);
 void dev_free_all(DeviceCols &d);
+int  dev_reserve_passes(DeviceCols &d, int n);
+// one tiny launch per translation unit with kernels: its code object is loaded when the context is made, not inside the first stage that needs it
+void warm_devpack(void *stream), warm_kernels(void *stream), warm_textcall(void *stream), warm_annotate(void *stream);
+
+// ---- BGZF blocks inflated on the device (inflate_k.hip; bamfeed.cpp drives it)
+struct InfBlock { unsigned long long in_off, out_off; uint32_t in_size, out_size; };      // offsets into the batch's compressed / inflated bytes
+int  dev_inflate_staging(msnv_ctx *ctx, uint64_t in_bytes, uint64_t out_bytes, uint8_t **in, uint8_t **out);
+void dev_inflate_release(msnv_ctx *ctx);
+void dev_inflate_release_device(msnv_ctx *ctx);
+int  dev_inflate(msnv_ctx *ctx, uint64_t comp_bytes, const std::vector<InfBlock> &blocks, uint64_t out_bytes, std::vector<uint32_t> &status, double *ms_kernel);
+int  dev_inflate_device_buffers(msnv_ctx *ctx, uint64_t in_bytes, uint64_t out_bytes);
+int  dev_inflate_resident(msnv_ctx *ctx, const uint8_t *host_in, uint64_t comp_bytes, const std::vector<InfBlock> &blocks, const std::vector<uint32_t> &blk_in_file,
+                          uint32_t check_every, std::vector<uint32_t> &status, double *ms_kernel);
+int  dev_inflate_patch(msnv_ctx *ctx, uint64_t out_off, const uint8_t *data, uint32_t n);
+
+// ---- the stages that work on files (textcall.hip; dist.cpp + dist_k.hip; div.cpp + div_k.hip; subpopr.cpp + subpopr_k.hip)
+int  text_call(msnv_ctx *ctx, const char *text, uint64_t n_text, const msnv_params &p, const char *ref_fasta, const char *ann_path,
+               const char *called_path, const char *indiv_path, uint64_t stats[8]);
+int  dist_file(msnv_ctx *ctx, const char *freq_path, const char *mann_path, const char *allele_path, double threshold,
+               int32_t *n_samples_out, uint64_t *n_pos_out, double *ms_kernel);
+int  div_file(msnv_ctx *ctx, const char *freq_path, int32_t mode, int32_t matched, int64_t genome_length, const double *h, const double *v,
+              int32_t n_cov, const int64_t *row_order, uint64_t n_order, const char *out_a, const char *out_b, int32_t *n_samples_out,
+              uint64_t *n_rows_out, double *ms_kernel);
+int dev_dist(const double *xt_host, int n_samples, long n_pos, double threshold, void *stream, double *mann, double *allele, double *ms_kernel);
+int dev_div(const double *xs, const uint64_t *bits, long n_single, long n_words, const double *xg, const long *goff, long n_groups, long n_grouped,
+            int n_samples, void *stream, double *out, double *ms_kernel);
+int dev_allele_freq(const std::vector<uint32_t> &cov, const std::vector<uint32_t> &cnt, const std::vector<uint32_t> &row_line,
+                    uint32_t n_samples, long long min_depth, void *stream, std::vector<double> &freq, double *ms_kernel);
 
 }  // namespace msnv

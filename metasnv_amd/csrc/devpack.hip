@@ -2463,7 +2463,7 @@ static int stage_streams(hipStream_t st, const int device, BufPool &pool, const 
                          const uint8_t *in_place_base = nullptr) {
     R.s_beg.assign(S, 0); R.s_end.assign(S, 0);
     if (in_place_base) {
-        // the streams where they lie: offsets into the caller's buffer (api.cpp has checked order, alignment of the base and the bytes behind the last)
+        // the streams where they lie: offsets into the caller's buffer (api.cpp / bamfeed.cpp have checked order, alignment of the base and the bytes behind the last)
         for (size_t s = 0; s < S; ++s) { R.s_beg[s] = (unsigned long long)(streams[s] - in_place_base); R.s_end[s] = R.s_beg[s] + n_bytes[s]; }
         R.raw = const_cast<uint8_t *>(in_place_base);
         for (size_t s = 0; s < S; ++s) R.raw_bytes += n_bytes[s];     // (accounting: the records' bytes)
@@ -3701,7 +3701,7 @@ struct Round {
 // The driver of a round: the quick route when it may try, the careful route for what it hands back (or for everything), the common tail.
 // Which work is queued before which wait is each stage's header comment; a stage that answers TO_CAREFUL has left nothing running.
 int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *streams, const uint64_t *n_bytes, int n, bool on_device, const uint8_t *in_place_base, uint64_t in_place_capacity) {
-    (void)in_place_capacity;                                       // (api.cpp has checked the streams against it)
+    (void)in_place_capacity;                                       // (api.cpp / bamfeed.cpp have checked the streams against it)
     if (n <= 0) return MSNV_OK;
     if (n > 2048) return fail(MSNV_EINVAL, "internal: a device-pack round holds at most 2048 samples");
     if (!ds.ctx) return fail(MSNV_ENODEV, "the device pack needs a device context");

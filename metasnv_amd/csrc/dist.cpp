@@ -7,11 +7,9 @@
 #include <cstring>
 
 #include "dataset.h"
+#include "device.h"
 
 namespace msnv {
-
-void py_repr(double x, std::string &out);
-int dev_dist(const double *xt_host, int n_samples, long n_pos, double threshold, void *stream, double *mann, double *allele, double *ms_kernel);
 
 // pandas' default float converter (read_table(float_precision=None) -> precise_xstrtod, pandas/_libs/src/parser/
 // tokenizer.c; pandas is a dependency of the reference, version unpinned -- restated from pandas 2.x and pinned by

@@ -7,13 +7,9 @@
 #include <cstring>
 
 #include "dataset.h"
+#include "device.h"
 
 namespace msnv {
-
-int read_freq(const char *freq_path, std::vector<std::string> &names, std::vector<std::string> *labels, std::vector<double> &rows, uint64_t &n_pos);
-int write_matrix(const char *path, const std::vector<std::string> &names, const std::vector<double> &m);
-int dev_div(const double *xs, const uint64_t *bits, long n_single, long n_words, const double *xg, const long *goff, long n_groups, long n_grouped,
-            int n_samples, void *stream, double *out, double *ms_kernel);
 
 namespace {
 

@@ -5,6 +5,8 @@
 #include <string>
 #include <vector>
 
+#include "dataset.h"
+
 namespace msnv {
 
 // samples of interest of every species of interest (metaSNV_Filtering.py:111-145), flattened
@@ -26,6 +28,10 @@ struct FilterBatch {
     void clear() { cov.clear(); cnt.clear(); row_line.clear(); line_species.clear(); row_out.clear(); row_id.clear(); n_out = 0; }
 };
 
+int filter_files(msnv_ctx *ctx, const char *const *paths, int n_paths, uint32_t n_samples, const FilterSpecies &sp,
+                 double min_cov, double min_prop, const char *out_dir, uint64_t *n_lines_kept, double *ms_kernel);
+int filter_resident(msnv_dataset &ds, int which, const FilterSpecies &sp, double min_cov, double min_prop, const char *out_dir,
+                    const msnv_site_ann *ann, const std::vector<std::string> *gene_names, uint64_t *n_lines_kept, double *ms_kernel);
 int dev_filter_batch(const FilterBatch &b, const FilterSpecies &sp, double min_cov, double min_prop, void *stream,
                      std::vector<double> &freq, std::vector<uint8_t> &line_pass, double *ms_kernel);
 

@@ -100,7 +100,6 @@ void clear_error() { t_err[0] = 0; }
 }  // namespace msnv
 
 extern "C" const char *msnv_last_error(void) { return msnv::t_err; }
-namespace msnv { uint64_t inflate_zlib_fallbacks(); }
 extern "C" int msnv_host_stats(uint64_t *zlib_fallbacks) { if (zlib_fallbacks) *zlib_fallbacks = msnv::inflate_zlib_fallbacks(); return MSNV_OK; }
 
 namespace msnv {
@@ -198,8 +197,6 @@ static int bgzf_index(const ConstBytes in, const char *path, std::vector<BlockRe
     return MSNV_OK;
 }
 
-bool inflate_raw(const uint8_t *src, uint32_t n_in, uint8_t *dst, uint32_t n_out);          // inflate.cpp
-bool inflate_raw_bmi2(const uint8_t *src, uint32_t n_in, uint8_t *dst, uint32_t n_out);     // the same, compiled with -mbmi2
 static std::atomic<uint64_t> g_zlib_fallbacks{0};
 uint64_t inflate_zlib_fallbacks() { return g_zlib_fallbacks.load(); }
 
@@ -222,7 +219,7 @@ static bool inflate_block(const uint8_t *src, uint32_t n_in, uint8_t *dst, uint3
     return rc == Z_STREAM_END && zs.avail_out == 0;
 }
 
-// The two halves of bgzf_read_all for callers that inflate elsewhere (the device: api.cpp / inflate_k.hip)
+// The two halves of bgzf_read_all for callers that inflate elsewhere (the device: bamfeed.cpp / inflate_k.hip)
 int bgzf_load(const char *path, ByteBuf &comp, size_t &n_in, std::vector<BgzfBlock> &blocks, uint64_t &total_out) {
     if (int rc = read_file(path, comp, n_in)) return rc;
     blocks.clear();

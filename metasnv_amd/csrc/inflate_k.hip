@@ -26,8 +26,6 @@ namespace msnv {
         if (e_ != hipSuccess) return fail(MSNV_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-struct InfBlock { unsigned long long in_off, out_off; uint32_t in_size, out_size; };
-
 namespace {
 
 #if !defined(MSNV_INFLATE_WAVES)

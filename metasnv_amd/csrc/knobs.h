@@ -27,13 +27,13 @@ inline bool i64_of(const char *name, long long *v) { const char *e = getenv(name
 inline int       int_or(const char *name, int dflt) { int_of(name, &dflt); return dflt; }
 inline long long i64_or(const char *name, long long dflt) { i64_of(name, &dflt); return dflt; }
 
-// ---------------------------------------------------------------------------------- host IO and inflate (hostio.cpp, crc32.cpp, api.cpp, inflate_k.hip)
+// ---------------------------------------------------------------------------------- host IO and inflate (hostio.cpp, crc32.cpp, bamfeed.cpp, inflate_k.hip)
 // MSNV_INFLATE_CHECK=n: block i of a file is checked against the CRC-32 of its BGZF trailer when i % n == 0 (default 1: every block, as
 // htslib does; 0 or negative: none -- benchmarks).  ONE reading for the host decoder and the device inflate.  Per call (tests/test_crc32.py,
 // test_hostio.py, test_gpu_inflate*.py switch it).
 inline uint32_t inflate_check_every() { const int v = int_or("MSNV_INFLATE_CHECK", 1); return (uint32_t)(v < 0 ? 0 : v); }
 // MSNV_INFLATE=device|host|zlib has TWO readings.  (1) Where a call's BGZF blocks are inflated: 'd' the device whatever the size, any other
-// value ('h') the host, '\0' unset = api.cpp estimates.  Per call (tests/test_gpu_inflate.py and bench.py switch device / host in process).
+// value ('h') the host, '\0' unset = bamfeed.cpp estimates.  Per call (tests/test_gpu_inflate.py and bench.py switch device / host in process).
 constexpr const char *INFLATE = "MSNV_INFLATE";
 inline char inflate_where() { const char *e = getenv(INFLATE); return !e ? '\0' : e[0] == 'd' ? 'd' : 'h'; }
 // (2) 'z': the host decoder hands every block to zlib (A/B of the two decoders).  Once: asked per BGZF block by many threads; set for a
@@ -58,7 +58,7 @@ inline bool feed_trace() { static const bool on = first("MSNV_FEED_TRACE") == '1
 // Per call.  Profiling only.
 inline char stage_free() { const char c = first("MSNV_STAGE_FREE"); return c == 's' || c == 'n' ? c : '\0'; }
 
-// ---------------------------------------------------------------------------------- the per-read stage (api.cpp, devpack.hip)
+// ---------------------------------------------------------------------------------- the per-read stage (api.cpp, bamfeed.cpp, devpack.hip)
 // MSNV_PACK=host: BAM records are packed by the host stage (pack.cpp) although the dataset has a context.  Per call (tests/test_gpu_devpack.py, bench.py).
 inline bool pack_on_host() { return first("MSNV_PACK") == 'h'; }
 // MSNV_PACK_ROUND_MB (6144, at least 1): record megabytes per round of the device pack.  Per call (tests/test_gpu_devpack.py).

@@ -84,6 +84,11 @@ int bgzf_index_bytes(const uint8_t *data, size_t n, const char *path, std::vecto
 int bam_parse_header_bytes(const uint8_t *data, size_t n, const char *path, BamHeader &hdr, uint64_t &rec_off);
 int bam_header_from_blocks(const uint8_t *file_bytes, const std::vector<BgzfBlock> &blocks, const char *path, BamHeader &hdr, uint64_t &rec_off);   // leading blocks inflated on the host
 int bgzf_write_all(const char *path, const uint8_t *data, uint64_t n, int level);
+// the host decoder of one raw DEFLATE stream (inflate.cpp; the same compiled with -mbmi2: inflate_bmi2.cpp), the blocks it left to zlib so far
+bool inflate_raw(const uint8_t *src, uint32_t n_in, uint8_t *dst, uint32_t n_out);
+bool inflate_raw_bmi2(const uint8_t *src, uint32_t n_in, uint8_t *dst, uint32_t n_out);
+uint64_t inflate_zlib_fallbacks();
+uint32_t crc32_pclmul_fold(uint32_t state, const uint8_t *p, size_t n);      // crc32_pclmul.cpp: n >= 64, a multiple of 16; state = ~crc in, ~crc out
 
 // BAM = BGZF(magic, header text, contig table, records...)
 // The records start at buf.data() + rec_off (the header sits in front of them in the same buffer: no second copy).
@@ -99,6 +104,16 @@ int fasta_read(const char *path, std::vector<FastaSeq> &out);
 // 3-column BED as written by metaSNV.py:92 (`name\t1\tLEN`): 0-based half-open regions.
 struct BedRegion { std::string name; int64_t beg, end; };
 int bed_read(const char *path, std::vector<BedRegion> &out);
+
+// ---------------------------------------------------------------------------------- numbers and tables as Python writes and reads them
+void py_repr(double x, std::string &out);                                   // filter.cpp: repr(float)
+bool pandas_strtod(const char *s, const char *end, double &out);            // dist.cpp: pandas' default float converter
+int read_freq(const char *freq_path, std::vector<std::string> &names, std::vector<std::string> *labels, std::vector<double> &rows, uint64_t &n_pos);   // dist.cpp: a *.filtered.freq table
+int write_matrix(const char *path, const std::vector<std::string> &names, const std::vector<double> &m);
+
+// ---------------------------------------------------------------------------------- synthetic workload (synth.cpp)
+std::vector<std::string> synth_contigs(const msnv_synth_params &p);
+void synth_sample_records(const msnv_synth_params &p, int sample, const std::vector<std::string> &contigs, std::vector<uint8_t> &out);
 
 // ---------------------------------------------------------------------------------- gene annotation (parsing only)
 // --db_ann rows as snpCall keeps them (call_vC.cpp:116-199,205-284): per contig in file order, start<=end only,

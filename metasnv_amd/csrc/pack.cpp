@@ -207,8 +207,6 @@ static void relayout_dense(SampleCols &sc) {
     sc.seq.swap(nseq); sc.qual.swap(nqual);
 }
 
-std::vector<std::string> synth_contigs(const msnv_synth_params &p);
-void synth_sample_records(const msnv_synth_params &p, int sample, const std::vector<std::string> &contigs, std::vector<uint8_t> &out);
 
 static inline bool consumes_ref(uint32_t t) { return t == C_M || t == C_D || t == C_N || t == C_EQ || t == C_X; }
 static inline bool consumes_query(uint32_t t) { return t == C_M || t == C_I || t == C_S || t == C_EQ || t == C_X; }

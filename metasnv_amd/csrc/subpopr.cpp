@@ -20,10 +20,6 @@
 
 namespace msnv {
 
-void py_repr(double x, std::string &out);
-int dev_allele_freq(const std::vector<uint32_t> &cov, const std::vector<uint32_t> &cnt, const std::vector<uint32_t> &row_line,
-                    uint32_t n_samples, long long min_depth, void *stream, std::vector<double> &freq, double *ms_kernel);
-
 namespace {
 
 int read_file(const char *path, std::string &out) {

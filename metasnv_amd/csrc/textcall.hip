@@ -35,7 +35,6 @@ namespace msnv {
         if (e_ != hipSuccess) return fail(MSNV_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-int write_calls_text(msnv_dataset &ds, const char *called_path, const char *indiv_path, const msnv_site_ann *ann, const std::vector<std::string> *gene_names);
 
 constexpr uint32_t TOK_CAP = 10000;            // call_vC.cpp:482: characters of a token that toksplit keeps
 constexpr uint32_t CLS_IGNORE = 5, CLS_CARET = 6, CLS_INDEL = 7, CLS_BAD = 8;   // classes of a base-string character next to 0 (match) and 1-4 (A C G T)
