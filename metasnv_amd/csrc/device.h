@@ -11,6 +11,9 @@
 namespace msnv {
 
 struct Pair32 { uint32_t x, y; };
+// DeviceCols::tile_nslots[] on the device: cells per site row of the tile (<= 16 384 + padding) and, in the top bit, "some sample of the tile
+// was split into several pairs": only there can two allele events meet in one cell (pack.cpp sets it, the scatter half of the tail reads it)
+constexpr uint32_t NSLOTS_SPLIT = 1u << 31, NSLOTS_MASK = NSLOTS_SPLIT - 1u;
 struct MergedGroupDev { uint64_t hdr_base; uint32_t tile, pair_lo, n_pairs, n_pieces; };   // one merged group of shallow pairs (gather_merged_block): its
                                                                                         // headers in hdr8m, its pairs
 
@@ -109,7 +112,7 @@ struct DeviceCols {
     uint32_t  cap_events = 0, cap_overflow = 0, cap_sites = 0;
     SiteRec  *sites = nullptr;
     uint32_t *tile_site_base = nullptr, *tile_site_cnt = nullptr;
-    uint32_t *tile_nslots = nullptr; // per tile: samples that have reads in it = cells per site of that tile (kernels.hip: CellMap)
+    uint32_t *tile_nslots = nullptr; // per tile: samples that have reads in it = cells per site of that tile (kernels.hip: CellMap) | NSLOTS_SPLIT
     unsigned long long *tile_cell_base = nullptr;   // per tile and pass: first cell of its sites' rows (gate kernel)
     uint64_t  cap_cells = 0, last_cells = 0;
     uint16_t *ncol = nullptr;        // [4][cap_cells]: mismatching A, C, G, T counts per (site, slot), one column per allele

@@ -77,10 +77,6 @@ __device__ __forceinline__ uint32_t allele_index(uint32_t code) {
 __device__ __forceinline__ uint32_t nz_bytes(uint32_t x) {         // bit 8j+7 set iff byte j != 0
     return (((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u;
 }
-__device__ __forceinline__ uint32_t count_nz_bytes(const uint4 a, const uint4 b) {
-    return (uint32_t)__popc(nz_bytes(a.x) | nz_bytes(a.y) >> 1 | nz_bytes(a.z) >> 2 | nz_bytes(a.w) >> 3 |
-                            nz_bytes(b.x) >> 4 | nz_bytes(b.y) >> 5 | nz_bytes(b.z) >> 6 | nz_bytes(b.w) >> 7);
-}
 __device__ __forceinline__ uint32_t nz_nibbles(uint32_t x) {       // bit 4j+3 set iff nibble j != 0
     return (((x & 0x77777777u) + 0x77777777u) | x) & 0x88888888u;
 }
@@ -484,8 +480,12 @@ __device__ __forceinline__ void narrow_pass(LDS &L, const PileupArgs &a, uint32_
         const uint4 a1 = *reinterpret_cast<uint4 *>(&L.al[N_PPT * tid + 4]);
         const uint32_t alw[N_PPT] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
 #pragma unroll
-        for (int j = 0; j < N_PPT; ++j) pm |= (alw[j] ? 1u : 0u) << j;
-        myev = count_nz_bytes(a0, a1);
+        for (int j = 0; j < N_PPT; ++j) pm |= min(alw[j], 1u) << j;
+        // events = non-zero allele bytes: the masked SAD adds |(w + 1) - w| = 1 for every byte of w that is not zero (bins are < 255 -- host
+        // bound -- so the + 1 carries into no neighbour): one instruction per word where the SWAR test took three and a final popcount
+        myev = 0;
+#pragma unroll
+        for (int j = 0; j < N_PPT; ++j) myev = __builtin_amdgcn_msad_u8(alw[j] + 0x01010101u, alw[j], myev);
     }
     if (!__any(pm != 0u)) return;                            // no mismatching allele in this wavefront's 512 positions
     dirty |= pm != 0u;                                       // my 8 positions lie in one 64-position block (store_part_row tells the gate kernel)
@@ -1281,7 +1281,7 @@ static_assert(GATE_PPT == 8, "the gate kernel is written for 8 positions per thr
 struct CellMap { const uint32_t *tile_site_base; const unsigned long long *tile_cell_base; const uint32_t *tile_nslots; unsigned long long cap_cells;
                  const unsigned long long *block_row; };     // per 64 positions: first cell of the first site in them (gate kernel)
 __device__ __forceinline__ uint64_t cell_of(const CellMap &m, const uint32_t tile, const uint32_t site, const uint32_t slot) {
-    return m.tile_cell_base[tile] + (uint64_t)(site - m.tile_site_base[tile]) * m.tile_nslots[tile] + slot;
+    return m.tile_cell_base[tile] + (uint64_t)(site - m.tile_site_base[tile]) * (m.tile_nslots[tile] & NSLOTS_MASK) + slot;
 }
 
 // Zeroes n bytes at p (2-byte aligned, n even) with the NT threads of the caller: halfword stores up to the first 16-byte boundary
@@ -2039,7 +2039,7 @@ __device__ __forceinline__ void gather_cov_block(const TailArgs &a, const uint32
     if (n <= part) return;
     const uint32_t base = a.tile_site_base[tile];
     if (base + n > a.cap_out) return;                   // the host sees the site count and retries with a larger buffer
-    const uint32_t n_slots = a.cells.tile_nslots[tile];
+    const uint32_t n_slots = a.cells.tile_nslots[tile] & NSLOTS_MASK;
     const unsigned long long cell0 = a.cells.tile_cell_base[tile];
     if (cell0 + (unsigned long long)n * n_slots > a.cells.cap_cells) return;
     const uint32_t ps = a.tile_pair_start[tile], np = a.tile_pair_merged[tile] - ps;      // the merged pairs (behind the others) spill nothing
@@ -2105,58 +2105,86 @@ __device__ __forceinline__ void gather_cov_block(const TailArgs &a, const uint32
         }
         return;
     }
-    const uint64_t work = (uint64_t)mine * np;
-    for (uint64_t i = threadIdx.x; i < work; i += blockDim.x) {
-        const uint32_t j = part + (uint32_t)(i / np) * GATHER_SPLIT, kk = (uint32_t)(i % np);
-        const uint32_t off = a.sites[base + j].gpos - t0;
-        const uint32_t pad = a.pairs[ps + kk].pad;          // kind | slot << 8
-        const uint32_t cov = a.spill[(uint64_t)(ps + kk) * TILE + off];
-        uint16_t *dst = &a.cov_col[cell0 + (uint64_t)j * n_slots + (pad >> 8)];
-        if (pad & 0xffu) add_u16(dst, cov);                 // one of several pairs of this sample: the groups add up
-        else if (cov != 255u && cov) *dst = (uint16_t)cov;  // (zero: what the gate kernel left there) 255 (wide kernel only): the overflow list holds the value, the scatter half writes it
-        if (arows) put_allele_word(a, arows[(uint64_t)kk * TILE + off], cell0 + (uint64_t)j * n_slots + (pad >> 8), (pad & 0xffu) != 0u);
+    // FEW sites (< GD_MIN_SITES for this workgroup): one cell per thread and trip, no division.  The 256 threads are dealt as P pair lanes x S
+    // site lanes, P the power of two that holds the tile's pairs (<= 256): a wavefront is consecutive pairs at one site -- its cells are
+    // consecutive slots, a line or two per store -- and a thread stays in one spill row.  The site offsets wait in LDS, the pair's slot
+    // in a register, so a trip is four independent one-byte loads and then their stores (the form before: a 64-bit divide and two
+    // dependent global loads -- site, then byte -- per cell).
+    uint32_t *const s_off = s_pool;                                  // [GD_MIN_SITES]
+    static_assert(GD_MIN_SITES <= TAIL_POOL_WORDS, "the site offsets of the few-site gather live in the launch's LDS pool");
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lg = np > 1u ? min(8u, 32u - (uint32_t)__clz((int)(np - 1u))) : 0u, P = 1u << lg, S = 256u >> lg;
+    const uint32_t kk0 = tid & (P - 1u), s0 = tid >> lg;
+    const uint32_t pad0 = kk0 < np ? a.pairs[ps + kk0].pad : 0u;     // (in flight with the site records)
+    if (tid < mine) s_off[tid] = a.sites[base + part + tid * GATHER_SPLIT].gpos - t0;      // (mine <= share < GD_MIN_SITES)
+    __syncthreads();
+    for (uint32_t kk = kk0; kk < np; kk += P) {
+        const uint32_t pad = kk == kk0 ? pad0 : a.pairs[ps + kk].pad;          // kind | slot << 8
+        const bool add = (pad & 0xffu) != 0u;                        // one of several pairs of this sample: the groups add up
+        const uint8_t *row = a.spill + (uint64_t)(ps + kk) * TILE;
+        for (uint32_t jj = s0; jj < mine; jj += 4u * S) {
+            uint32_t off[4], cov[4], aw[4];
+#pragma unroll
+            for (uint32_t u = 0; u < 4u; ++u) {
+                off[u] = s_off[min(jj + u * S, mine - 1u)];
+                cov[u] = row[off[u]];
+                aw[u] = arows ? arows[(uint64_t)kk * TILE + off[u]] : 0u;
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < 4u; ++u) {
+                if (jj + u * S >= mine) continue;
+                const unsigned long long cell = cell0 + (unsigned long long)(part + (jj + u * S) * GATHER_SPLIT) * n_slots + (pad >> 8);
+                if (add) { if (cov[u]) add_u16(&a.cov_col[cell], cov[u]); }
+                else if (cov[u] != 255u && cov[u]) a.cov_col[cell] = (uint16_t)cov[u];   // (zero: what the gate kernel left there) 255 (wide kernel only): the overflow list holds the value, the scatter half writes it
+                if (arows) put_allele_word(a, aw[u], cell, add);
+            }
+        }
     }
 }
 
 __device__ __forceinline__ void scatter_events_block(const TailArgs &a, const uint32_t bx, const uint32_t k) {
     if (a.counters[2] > a.cap_out || *reinterpret_cast<const unsigned long long *>(&a.counters[CNT_CELLS]) > a.cells.cap_cells) return;
     // an event finds its cell from three INDEPENDENT lookups by position -- site bitmap word, first cell of the 64-position
-    // block's first site, slots of the tile -- so the loop is two levels of dependent loads deep (event -> tables -> atomic)
-    auto apply = [&](const Pair32 e, const bool allele) {
-        const unsigned long long w = a.site_bits[e.x >> 6], bit = 1ull << (e.x & 63u);
-        const unsigned long long row0 = a.cells.block_row[e.x >> 6];
-        const uint32_t ns = a.cells.tile_nslots[e.x / TILE];
-        if (!(w & bit)) return;                    // most events are sequencing errors at positions that are not sites
-        const unsigned long long row = row0 + (unsigned long long)__popcll(w & (bit - 1ull)) * ns;
-        // events carry the SLOT of their sample in the tile (pack.cpp)
-        if (allele) add_u16(&a.ncol[ncol_base((e.y >> 16) & 3u, a.cells.cap_cells) + row + (e.y >> 18)], e.y & 0xffffu);   // one event per (site, pair, allele)
-        else a.cov_col[row + (e.y >> 16)] = (uint16_t)(e.y & 0xffffu);
+    // block's first site, slots of the tile -- so the loop is two levels of dependent loads deep (event -> tables -> write).
+    // cell_at: the first cell of the event's site, or false (most events are sequencing errors at positions that are not sites)
+    auto cell_at = [](const uint32_t gpos, const unsigned long long w, const unsigned long long row0, const uint32_t ns, unsigned long long &row) {
+        const unsigned long long bit = 1ull << (gpos & 63u);
+        row = row0 + (unsigned long long)__popcll(w & (bit - 1ull)) * (ns & NSLOTS_MASK);
+        return (w & bit) != 0ull;
     };
     const uint32_t n_k = min(a.counters[16u + k * EV_CNT_STRIDE], a.cap_list);
     const Pair32 *list = a.events + (uint64_t)k * a.cap_list;
-    {   // four events per trip: their loads, then their table loads, are in flight together
+    {   // four events per trip: their loads, then their table loads, are in flight together; then the writes.  The last trip of a thread is
+        // the same trip with fewer live events (they re-read the thread's first one), not a chain of dependent loads per event.
         constexpr uint32_t U = 4;
         const uint32_t stride = a.scatter_blocks * blockDim.x;
-        uint32_t i = bx * blockDim.x + threadIdx.x;
-        for (; i + (U - 1u) * stride < n_k; i += U * stride) {
+        for (uint32_t i = bx * blockDim.x + threadIdx.x; i < n_k; i += U * stride) {
             Pair32 e[U]; unsigned long long w[U], row0[U]; uint32_t ns[U];
 #pragma unroll
-            for (uint32_t u = 0; u < U; ++u) e[u] = list[i + u * stride];
+            for (uint32_t u = 0; u < U; ++u) e[u] = list[i + u * stride < n_k ? i + u * stride : i];
 #pragma unroll
             for (uint32_t u = 0; u < U; ++u) { w[u] = a.site_bits[e[u].x >> 6]; row0[u] = a.cells.block_row[e[u].x >> 6]; ns[u] = a.cells.tile_nslots[e[u].x / TILE]; }
 #pragma unroll
             for (uint32_t u = 0; u < U; ++u) {
-                const unsigned long long bit = 1ull << (e[u].x & 63u);
-                if (!(w[u] & bit)) continue;
-                const unsigned long long row = row0[u] + (unsigned long long)__popcll(w[u] & (bit - 1ull)) * ns[u];
-                add_u16(&a.ncol[ncol_base((e[u].y >> 16) & 3u, a.cells.cap_cells) + row + (e[u].y >> 18)], e[u].y & 0xffffu);
+                unsigned long long row;
+                if ((u && i + u * stride >= n_k) || !cell_at(e[u].x, w[u], row0[u], ns[u], row)) continue;
+                // events carry the SLOT of their sample in the tile (pack.cpp), one event per (site, pair, allele).  Only the pairs of a SPLIT
+                // sample meet in a cell: their tile (NSLOTS_SPLIT) adds with memory-side atomics.  In every other tile the cell -- zero since
+                // the gate kernel -- has this one writer: a plain two-byte store, nothing for the memory side to read, modify and write
+                uint16_t *dst = &a.ncol[ncol_base((e[u].y >> 16) & 3u, a.cells.cap_cells) + row + (e[u].y >> 18)];
+                if (ns[u] & NSLOTS_SPLIT) add_u16(dst, e[u].y & 0xffffu);
+                else *dst = (uint16_t)(e[u].y & 0xffffu);
             }
         }
-        for (; i < n_k; i += stride) apply(list[i], true);
     }
+    // coverages >= 255 of the wide kernel: the gather half leaves those cells (byte 255) to this store
+    auto apply_cov = [&](const Pair32 e) {
+        unsigned long long row;
+        if (cell_at(e.x, a.site_bits[e.x >> 6], a.cells.block_row[e.x >> 6], a.cells.tile_nslots[e.x / TILE], row)) a.cov_col[row + (e.y >> 16)] = (uint16_t)(e.y & 0xffffu);
+    };
     const uint32_t n_overflow = min(a.counters[1], a.cap_overflow);
     for (uint32_t i = (k * a.scatter_blocks + bx) * blockDim.x + threadIdx.x; i < n_overflow; i += a.scatter_blocks * EV_LISTS * blockDim.x)
-        apply(a.overflow[i], false);
+        apply_cov(a.overflow[i]);
 }
 
 // Per-sample coverage of the called positions for the pairs of MERGED groups (no spill row exists for them): one workgroup
@@ -2194,7 +2222,7 @@ __device__ __forceinline__ void gather_merged_group(const TailArgs &a, const Mer
     // everything that hangs on the descriptor alone is requested together -- the tile's site tables, its bitmap and ranks, the first
     // round(s) of piece headers, the pairs' slots: the group is a chain of dependent loads (one group of a sparse cohort is ~250 pieces), not arithmetic
     const uint32_t tile = w.tile, t0 = tile * TILE;
-    const uint32_t n = a.tile_site_cnt[tile], base = a.tile_site_base[tile], n_slots = a.cells.tile_nslots[tile];
+    const uint32_t n = a.tile_site_cnt[tile], base = a.tile_site_base[tile], n_slots = a.cells.tile_nslots[tile] & NSLOTS_MASK;
     const unsigned long long cell0 = a.cells.tile_cell_base[tile];
     unsigned long long my_bits = 0; uint32_t my_rank = 0;
     if (tid < TILE / 64) { my_bits = a.site_bits[(t0 >> 6) + tid]; my_rank = a.site_rank[(t0 >> 6) + tid]; }
@@ -2368,7 +2396,7 @@ __global__ __launch_bounds__(256) void msnv_decide_sites(const SiteRec *sites, c
                 if ((int)nx < min_snvs) continue;           // neither rule can fire
                 if ((double)nx >= (double)(int)s.cov * min_frac) { pop |= 1u << x; continue; }
                 bool any = false;
-                const uint32_t tile = s.gpos / TILE, n_slots = cells.tile_nslots[tile];
+                const uint32_t tile = s.gpos / TILE, n_slots = cells.tile_nslots[tile] & NSLOTS_MASK;
                 const uint64_t row = cell_of(cells, tile, site, 0u);
                 for (uint32_t i = lane; i < n_slots; i += 64)
                     any |= (int)ncol[(uint64_t)x * cells.cap_cells + row + i] >= min_snvs;

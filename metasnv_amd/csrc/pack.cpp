@@ -1265,6 +1265,10 @@ int finalize_dataset(msnv_dataset &ds) {
         }
         ds.tile_slot_stride = nslots;
         ds.tile_slot_base[nt] = (uint64_t)ds.slot_sample.size();
+        // the device's copy also says whether some sample of the tile was split into several pairs (device.h: NSLOTS_SPLIT): several
+        // allele events may then meet in one cell and are added; in every other tile a cell has one writer (kernels.hip: scatter_events_block)
+        for (uint64_t t = 0; t < nt; ++t)
+            for (uint32_t k = tps[t]; k < tps[t + 1]; ++k) if ((pairs[k].pad & 0xffu) == 1u) { nslots[t] |= NSLOTS_SPLIT; break; }
         if (int rc = arena.add(&d->tile_nslots, nslots, &d->device_bytes)) return rc;
         if (int rc = dev_alloc((void **)&d->tile_cell_base, (nt + 1) * sizeof(unsigned long long), &d->device_bytes)) return rc;
         if (int rc = dev_memset_async(d->tile_cell_base, 0, (nt + 1) * sizeof(unsigned long long), ds.ctx ? ds.ctx->stream : nullptr)) return rc;
