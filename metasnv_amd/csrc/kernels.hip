@@ -385,7 +385,7 @@ constexpr int N_EVCAP = MSNV_N_EVCAP;
 static_assert(N_PPT == 8, "narrow per-sample pass is written for 8 positions per thread");
 
 struct alignas(16) NarrowLds {
-    uint32_t start[TILE / 4 + 4];
+    uint32_t start[TILE / 4];                  // (no piece starts at the tile end: the four words that padded this row are wsum below)
     uint32_t end[TILE / 4 + 4];
     unsigned long long exc[TILE / 8 + 4];      // byte bins, updated 8 positions at a time with 64-bit LDS atomics
     uint32_t al[TILE];
@@ -393,6 +393,7 @@ struct alignas(16) NarrowLds {
     uint2    hdr[2][N_HCAP];
     Pair32   ev[N_EVCAP];
     ChunkDesc desc[MAX_CHUNKS_PER_ITEM];
+    uint32_t wsum[N_NT / 64];                  // flush_alleles: the events each wavefront's staged records expand to (read as one 16-byte word)
     uint32_t carry[N_NT / 64 + 1];             // depth at the left edge of each wavefront's quarter of the tile ([4]: scratch for pieces that end at the tile end)
     uint32_t evn, ev_base;
     uint32_t emask[SEQ_ALIGN_LOG2 < 3 ? 33 : 1];   // pieces closer than 16 bases apart: mismatch flags of a lane's first n bases (narrow_classify32's flag order)
@@ -412,7 +413,11 @@ struct alignas(16) NarrowLds {
 // calling rule then reads the summed per-sample records), and leaves every bin zero.
 // DA ("dense alleles", pack.cpp: allele planes): the pair's mismatch counts leave as four byte planes -- plain stores next to the coverage
 // bytes -- instead of one total atomic + one event per (position, allele): what a pass costs no longer depends on how noisy the reads are.
-template <typename LDS, int EXC_PAD, bool MERGED = false, bool FUSED = false, bool DA = false>
+// LATE (msnv_pileup_tiles_narrow32's ordinary items): the pass stages a position's allele WORD -- one 8-byte record {tile position | split << 11 |
+// sample << 12, word} per position that holds an allele -- and flush_alleles, where the workgroup meets with all 256 lanes anyway, makes the
+// total atomics, the individual rule's marks and the events of it.  What left the pass: the event count, the walk over a word's alleles and
+// two to three global atomics per allele, at ~7 active lanes of 64 between barriers (B) and (A).
+template <typename LDS, int EXC_PAD, bool MERGED = false, bool FUSED = false, bool DA = false, bool LATE = false>
 __device__ __forceinline__ void narrow_pass(LDS &L, const PileupArgs &a, uint32_t (&tc)[N_PPT / 2], bool &dirty, const uint32_t t0,
                                             const int tid, const int lane, const int wave, const uint32_t sample, const uint32_t k,
                                             const uint32_t split, const uint32_t tmode) {
@@ -474,18 +479,25 @@ __device__ __forceinline__ void narrow_pass(LDS &L, const PileupArgs &a, uint32_
         }
         return;
     }
-    uint32_t pm = 0, myev;
+    uint32_t pm = 0, myev = 0;
     {
         const uint4 a0 = *reinterpret_cast<uint4 *>(&L.al[N_PPT * tid]);
         const uint4 a1 = *reinterpret_cast<uint4 *>(&L.al[N_PPT * tid + 4]);
         const uint32_t alw[N_PPT] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
 #pragma unroll
-        for (int j = 0; j < N_PPT; ++j) pm |= min(alw[j], 1u) << j;
+        for (int j = 0; j < N_PPT; ++j) {
+            if constexpr (LATE) {                                // min(w, 1) folded by shift-or: 15 instructions where the compiler's compare / select pairs and their hazard waits took 20
+                uint32_t one;
+                asm("v_min_u32 %0, 1, %1" : "=v"(one) : "v"(alw[j]));
+                pm |= one << j;
+            } else pm |= min(alw[j], 1u) << j;
+        }
         // events = non-zero allele bytes: the masked SAD adds |(w + 1) - w| = 1 for every byte of w that is not zero (bins are < 255 -- host
         // bound -- so the + 1 carries into no neighbour): one instruction per word where the SWAR test took three and a final popcount
-        myev = 0;
+        if constexpr (!LATE) {
 #pragma unroll
-        for (int j = 0; j < N_PPT; ++j) myev = __builtin_amdgcn_msad_u8(alw[j] + 0x01010101u, alw[j], myev);
+            for (int j = 0; j < N_PPT; ++j) myev = __builtin_amdgcn_msad_u8(alw[j] + 0x01010101u, alw[j], myev);
+        }
     }
     if (!__any(pm != 0u)) return;                            // no mismatching allele in this wavefront's 512 positions
     dirty |= pm != 0u;                                       // my 8 positions lie in one 64-position block (store_part_row tells the gate kernel)
@@ -505,6 +517,62 @@ __device__ __forceinline__ void narrow_pass(LDS &L, const PileupArgs &a, uint32_
         }
         return;
     }
+    // the alleles of my positions in `pm`, each to the tile's totals, the individual rule's marks and one event at `slot` on (the staging buffer, or the list itself)
+    auto expand = [&](uint32_t pm, uint32_t slot, const bool direct) {
+        while (pm) {
+            const uint32_t j = (uint32_t)__builtin_ctz(pm);
+            pm &= pm - 1u;
+            const uint32_t word = L.al[N_PPT * tid + j];
+            L.al[N_PPT * tid + j] = 0u;
+            const uint32_t gpos = t0 + N_PPT * tid + j;
+            // (a position with mismatches nearly always holds ONE allele: a walk over the non-zero bytes instead of four unrolled tests, each of
+            // which the wavefront issues in full as soon as one of its lanes holds that allele -- round 4)
+            for (uint32_t m = nz_bytes(word); m; m &= m - 1u) {
+                const uint32_t x = (uint32_t)__builtin_ctz(m) >> 3;
+                const uint32_t n = (word >> (8u * x)) & 0xffu;
+                tot_add_one(a.tot + 4ull * t0, tmode, N_PPT * tid + j, x, n);
+                // the individual rule's "some sample holds >= t reads of x"; a sample that was split into several pairs may reach
+                // the threshold only in sum: those positions are marked and decided from the per-sample records (msnv_decide_sites)
+                if (n >= a.min_snvs) atomicOr(&a.ind4[gpos >> 3], 1u << (4u * (gpos & 7u) + x));
+                else if (split) atomicOr(&a.unc_bits[gpos >> 5], 1u << (gpos & 31u));
+                const Pair32 e{gpos, sample << 18 | x << 16 | n};
+                if (direct) { if (slot < a.cap_events) a.events[slot] = e; }
+                else L.ev[slot] = e;
+                ++slot;
+            }
+        }
+    };
+    if constexpr (LATE) {
+        // slots for the wavefront's POSITIONS, taken or not taken (the compare-and-swap of the form below, and why it is one)
+        const uint32_t np = (uint32_t)__builtin_popcount(pm);
+        uint32_t pi = (uint32_t)wave_inclusive_scan((int)np);
+        asm volatile("" : "+v"(pi));                         // (kept whole: summed back from the scan's six shifted terms, `pi - np` below costs each of its steps a zero fill and a move)
+        uint32_t got = 0;
+        if (lane == 63) {
+            uint32_t cur = atomicAdd(&L.evn, 0u);
+            for (;;) {
+                if (cur + pi > (uint32_t)N_EVCAP) { got = 0x80000000u; break; }      // staging full (noisy pair): this wavefront expands its alleles itself, below
+                const uint32_t seen = atomicCAS(&L.evn, cur, cur + pi);
+                if (seen == cur) { got = cur; break; }
+                cur = seen;
+            }
+        }
+        got = (uint32_t)__builtin_amdgcn_readlane((int)got, 63);
+        if (!(got & 0x80000000u)) {
+            uint32_t slot = got + pi - np;
+            const uint32_t tag = (split ? 1u << 11 : 0u) | sample << 12;
+            while (pm) {
+                const uint32_t j = (uint32_t)__builtin_ctz(pm);
+                pm &= pm - 1u;
+                const uint32_t word = L.al[N_PPT * tid + j];
+                L.al[N_PPT * tid + j] = 0u;
+                L.ev[slot++] = Pair32{(uint32_t)(N_PPT * tid) + j | tag, word};
+            }
+            return;
+        }
+        // staging full: the wavefront's alleles go straight into the list, the way the other form does it below (its event count from the bins: rare)
+        for (uint32_t q = pm; q; q &= q - 1u) myev += (uint32_t)__builtin_popcount(nz_bytes(L.al[N_PPT * tid + (uint32_t)__builtin_ctz(q)]));
+    }
     const uint32_t ei = (uint32_t)wave_inclusive_scan((int)myev);   // exclusive prefix of the lanes' event counts = their slots
     uint32_t res = 0;
     if (lane == 63 && ei) {
@@ -515,7 +583,7 @@ __device__ __forceinline__ void narrow_pass(LDS &L, const PileupArgs &a, uint32_
         // fuzz cases once the buffer held 224 events instead of 256; profiles/stress_case.py shows it in seconds.)
         uint32_t cur = atomicAdd(&L.evn, 0u);
         for (;;) {
-            if (cur + ei > (uint32_t)N_EVCAP) { res = 0x80000000u | atomicAdd(a.ev_count, ei); break; }   // straight into the list
+            if (LATE || cur + ei > (uint32_t)N_EVCAP) { res = 0x80000000u | atomicAdd(a.ev_count, ei); break; }   // straight into the list (LATE: the staging buffer holds records, not events)
             const uint32_t seen = atomicCAS(&L.evn, cur, cur + ei);
             if (seen == cur) { res = cur; break; }                                 // staged: flushed behind a later barrier (A)
             cur = seen;
@@ -524,28 +592,38 @@ __device__ __forceinline__ void narrow_pass(LDS &L, const PileupArgs &a, uint32_
     res = (uint32_t)__builtin_amdgcn_readlane((int)res, 63);
     const bool direct = (res & 0x80000000u) != 0u;
     uint32_t slot = (res & 0x7fffffffu) + ei - myev;
-    while (pm) {
-        const uint32_t j = (uint32_t)__builtin_ctz(pm);
-        pm &= pm - 1u;
-        const uint32_t word = L.al[N_PPT * tid + j];
-        L.al[N_PPT * tid + j] = 0u;
-        const uint32_t gpos = t0 + N_PPT * tid + j;
-        // (a position with mismatches nearly always holds ONE allele: a walk over the non-zero bytes instead of four unrolled tests, each of
-        // which the wavefront issues in full as soon as one of its lanes holds that allele -- round 4)
-        for (uint32_t m = nz_bytes(word); m; m &= m - 1u) {
-            const uint32_t x = (uint32_t)__builtin_ctz(m) >> 3;
-            const uint32_t n = (word >> (8u * x)) & 0xffu;
-            tot_add_one(a.tot + 4ull * t0, tmode, N_PPT * tid + j, x, n);
-            // the individual rule's "some sample holds >= t reads of x"; a sample that was split into several pairs may reach
-            // the threshold only in sum: those positions are marked and decided from the per-sample records (msnv_decide_sites)
-            if (n >= a.min_snvs) atomicOr(&a.ind4[gpos >> 3], 1u << (4u * (gpos & 7u) + x));
-            else if (split) atomicOr(&a.unc_bits[gpos >> 5], 1u << (gpos & 31u));
-            const Pair32 e{gpos, sample << 18 | x << 16 | n};
-            if (direct) { if (slot < a.cap_events) a.events[slot] = e; }
-            else L.ev[slot] = e;
-            ++slot;
-        }
+    expand(pm, slot, direct);
+}
+
+// The flush of the staged allele records (narrow_pass<LATE>): called by all threads between barriers, like flush_events.  A thread takes ONE
+// record (N_EVCAP <= 256: one trip), the workgroup's prefix over the records' allele counts turns into slots behind one returning atomic, and
+// every allele of a record -- usually one -- gets what the pass used to give it: its add to the tile's totals, the individual rule's
+// mark (>= min_snvs reads in this sample; a sample split into several pairs may reach the threshold only in sum: msnv_decide_sites) and its event.
+__device__ __forceinline__ void flush_alleles(NarrowLds &L, const PileupArgs &a, const int tid, const int lane, const int wave, const uint32_t t0, const uint32_t tmode) {
+    static_assert(N_EVCAP <= N_NT && offsetof(NarrowLds, wsum) % 16 == 0 && N_NT / 64 == 4, "one staged record per thread; four wavefront sums in one word");
+    const uint32_t n = min(L.evn, (uint32_t)N_EVCAP);
+    Pair32 r{0u, 0u};
+    if ((uint32_t)tid < n) r = L.ev[tid];
+    const uint32_t cnt = (uint32_t)__builtin_popcount(nz_bytes(r.y));
+    const uint32_t incl = (uint32_t)wave_inclusive_scan((int)cnt);
+    if (lane == 63) L.wsum[wave] = incl;
+    __syncthreads();
+    const uint4 ws = *reinterpret_cast<const uint4 *>(L.wsum);
+    if (tid == 0) { const uint32_t total = ws.x + ws.y + ws.z + ws.w; L.ev_base = total ? atomicAdd(a.ev_count, total) : 0u; }
+    uint32_t slot = incl - cnt + (wave > 0 ? ws.x : 0u) + (wave > 1 ? ws.y : 0u) + (wave > 2 ? ws.z : 0u);
+    __syncthreads();
+    slot += L.ev_base;
+    const uint32_t p = r.x & (TILE - 1u), gpos = t0 + p, split = r.x & (1u << 11), sample = r.x >> 12;
+    for (uint32_t m = nz_bytes(r.y); m; m &= m - 1u) {
+        const uint32_t x = (uint32_t)__builtin_ctz(m) >> 3;
+        const uint32_t nn = (r.y >> (8u * x)) & 0xffu;
+        tot_add_one(a.tot + 4ull * t0, tmode, p, x, nn);
+        if (nn >= a.min_snvs) atomicOr(&a.ind4[gpos >> 3], 1u << (4u * (gpos & 7u) + x));
+        else if (split) atomicOr(&a.unc_bits[gpos >> 5], 1u << (gpos & 31u));
+        if (slot < a.cap_events) a.events[slot] = Pair32{gpos, sample << 18 | x << 16 | nn};
+        ++slot;
     }
+    if (tid == 0) L.evn = 0;
 }
 
 // This item's coverage partial: 8 positions per thread, u8 when the host bounded the item's summed depth below 256 (bit 0 of
@@ -862,7 +940,7 @@ __device__ __forceinline__ void pileup_tiles_narrow32_body(PileupArgs a, NarrowL
         const bool last_chunk = (cd.nrd_flags >> 16) != 0u;
         if (prev_last) __syncthreads();                              // (A): the pass of the previous pair left every bin zero
         desc_refill(L.desc, a.chunks + w.chunk_lo, c, nch, tid);
-        if (!MERGED && !DA && L.evn >= (uint32_t)(N_EVCAP / 2)) flush_events<NarrowLds, N_NT, N_EVCAP>(L, a, tid);
+        if (!MERGED && !DA && L.evn >= (uint32_t)(N_EVCAP / 2)) flush_alleles(L, a, tid, lane, wave, t0, tot_mode_of(w));
         if (tid < N_HCAP) {
             const uint32_t hx = get_hdr(c & 1u, (uint32_t)tid).x;
             const uint32_t s = hx & (TILE - 1u), sb = s + ((hx >> 11) & 0xffu);
@@ -881,7 +959,7 @@ __device__ __forceinline__ void pileup_tiles_narrow32_body(PileupArgs a, NarrowL
         hreg = load_hdr(c + 2u);
         __syncthreads();                                            // (B): this chunk is in the bins; the next chunk's headers are visible
         if (c + 1u < nch) issue_loads(c + 1u);                       // in flight under the per-sample pass
-        if (last_chunk) narrow_pass<NarrowLds, 0, MERGED, fused, DA>(L, a, tc, dirty, t0, tid, lane, wave, cd.sample, cd.pair, cd.pad, tot_mode_of(w));
+        if (last_chunk) narrow_pass<NarrowLds, 0, MERGED, fused, DA, !MERGED && !DA>(L, a, tc, dirty, t0, tid, lane, wave, cd.sample, cd.pair, cd.pad, tot_mode_of(w));
         prev_last = last_chunk;
     }
     __syncthreads();
@@ -894,7 +972,7 @@ __device__ __forceinline__ void pileup_tiles_narrow32_body(PileupArgs a, NarrowL
         }
         return;
     }
-    if (!MERGED && !DA) flush_events<NarrowLds, N_NT, N_EVCAP>(L, a, tid);
+    if (!MERGED && !DA) flush_alleles(L, a, tid, lane, wave, t0, tot_mode_of(w));
     store_part_row(a.part, w, tc, tid);
     store_item_dirty(a.slot_dirty, w, dirty, tid);
 }
