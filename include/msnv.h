@@ -252,6 +252,37 @@ int  msnv_dataset_create_from_files(msnv_ctx *ctx, const char *bam_path, const c
 int  msnv_dataset_attach_ctx(msnv_dataset *ds, msnv_ctx *ctx);
 void msnv_dataset_destroy(msnv_dataset *ds);
 
+/* msnv_mpileup_text  <-  samtools mpileup -f ref_fasta [-l bed_split_path] -B -b <bam list> [-q -Q -A -x -d --ff] > out_path
+ * (metaSNV.py:160-165, the left half of its pipe): the pileup TEXT itself, the reference's process boundary between samtools and
+ * snpCall, formatted on the device (csrc/mptext_k.hip) -- one line `name \t pos \t REF { \t cnt \t bases \t quals }` per position
+ * that a read passing the filters covers, samples in bam_paths order, elements in file order ([^ mapq] base | * | > < [+n ins | -n del]
+ * [$]; bam_plcmd.c pileup_seq [EXT]).  -B is implied: base qualities are never recomputed (no BAQ).
+ *   out_path NULL or "-": stdout.  Of params only the mpileup fields are read (min_baseq -Q, flag_filter --ff, count_orphans -A,
+ *   max_depth -d, min_mapq -q, ignore_overlaps -x).
+ *   stats (may be NULL): [0] lines, [1] samples, [2] text bytes, [3] pileup elements printed, [4] measure-pass kernel ms,
+ *   [5] write-pass kernel ms, [6] batches of text that left the device (MSNV_MPTEXT_BATCH bytes each at most, whole tiles),
+ *   [7] rounds of samples that went up (MSNV_MPTEXT_ROUND each).
+ * DESIGN.md section 7 lists the one divergence from samtools' text (the quality character of a deletion / ref-skip element of the
+ * first mate in front of an overlap). */
+typedef struct {
+    const char *const *bam_paths;
+    int32_t     n_bams;
+    const char *ref_fasta;        /* -f; NULL: every reference character is N              */
+    const char *bed_split_path;   /* -l or NULL                                            */
+    const char *out_path;         /* stdout of samtools                                    */
+    int32_t     host_threads;     /* BAM decode / pre-pass threads, 0 = auto               */
+    msnv_params params;
+} msnv_mpileup_text_args;
+int msnv_mpileup_text(msnv_ctx *ctx, const msnv_mpileup_text_args *args, uint64_t stats[8]);
+/* The same text from record streams in memory (what sam_read1() yields, one stream per sample; the reference as msnv_ref_desc,
+ * the -l regions as for msnv_dataset_set_bed: at most one per contig, n_bed = 0 for none).  *text is released with msnv_free;
+ * the text is not NUL-terminated.  What the tests and the Python layer use. */
+int msnv_mpileup_text_records(msnv_ctx *ctx, const msnv_ref_desc *ref, const msnv_params *params, int32_t n_bed, const int32_t *bed_tid,
+                              const int64_t *bed_beg, const int64_t *bed_end, const uint8_t *const *records, const uint64_t *n_bytes,
+                              int32_t n, char **text, uint64_t *text_bytes, uint64_t stats[8]);
+/* The sizes at which the kernels' forms change (tests): positions per tile, read descriptors taken through LDS at a time. */
+void msnv_mpileup_text_geometry(int32_t *tile_positions, int32_t *lds_reads);
+
 /* Restrict the shard: BED regions (mpileup -l; 0-based half-open, at most one region per
  * contig) and/or a contig mask.  Must precede the first add_sample call. */
 int  msnv_dataset_set_bed(msnv_dataset *ds, int32_t n, const int32_t *tid, const int64_t *beg, const int64_t *end);

@@ -62,6 +62,11 @@ class MpileupArgs(C.Structure):
                 ("ann_path", C.c_char_p), ("out_called_path", C.c_char_p), ("out_indiv_path", C.c_char_p), ("params", Params)]
 
 
+class MpileupTextArgs(C.Structure):
+    _fields_ = [("bam_paths", C.POINTER(C.c_char_p)), ("n_bams", C.c_int32), ("ref_fasta", C.c_char_p), ("bed_split_path", C.c_char_p),
+                ("out_path", C.c_char_p), ("host_threads", C.c_int32), ("params", Params)]
+
+
 class RefDesc(C.Structure):
     _fields_ = [("n_contigs", C.c_int32), ("names", C.POINTER(C.c_char_p)), ("lengths", C.POINTER(C.c_int64)),
                 ("seqs", C.POINTER(C.c_char_p)), ("seq_lens", C.POINTER(C.c_int64))]
@@ -133,6 +138,10 @@ SYMBOLS = [
     ("msnv_coverage", C.c_int, [_vp, P(CovArgs)]),
     ("msnv_call", C.c_int, [_vp, P(CallArgs)]),
     ("msnv_call_from_mpileup", C.c_int, [_vp, P(MpileupArgs), P(C.c_uint64)]),
+    ("msnv_mpileup_text", C.c_int, [_vp, P(MpileupTextArgs), P(C.c_uint64)]),
+    ("msnv_mpileup_text_records", C.c_int, [_vp, P(RefDesc), P(Params), C.c_int32, P(C.c_int32), P(C.c_int64), P(C.c_int64), P(_vp), P(C.c_uint64), C.c_int32,
+                                            P(P(C.c_char)), P(C.c_uint64), P(C.c_uint64)]),
+    ("msnv_mpileup_text_geometry", None, [P(C.c_int32), P(C.c_int32)]),
     ("msnv_bam_records_many", C.c_int, [_vp, P(C.c_char_p), C.c_int32, C.c_int32, P(P(C.c_uint8)), P(C.c_uint64)]),
     ("msnv_bgzf_inflate", C.c_int, [_vp, C.c_char_p, C.c_int32, P(P(C.c_uint8)), P(C.c_uint64), P(C.c_uint64)]),
     ("msnv_dataset_create", C.c_int, [_vp, P(RefDesc), P(Params), P(_vp)]),

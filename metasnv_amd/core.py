@@ -46,6 +46,55 @@ class Context:
             lib.msnv_ctx_destroy(self._h)
             self._h = C.c_void_p()
 
+    def mpileup_text(self, names, lengths, seqs, samples, bed=None, **params):
+        """The text of `samtools mpileup -f REF [-l BED] -B -b LIST` for record streams in memory (msnv_mpileup_text_records), formatted on
+        the device.  samples: one stream of raw BAM records (bytes / numpy uint8) per sample; seqs: FASTA characters per contig, None for a
+        contig the FASTA lacks, or None for no reference at all; bed: (tid, beg, end) regions, 0-based half-open, at most one per contig;
+        params: the mpileup fields of msnv_params (min_baseq, flag_filter, count_orphans, max_depth, min_mapq, ignore_overlaps).
+        Returns the text as bytes; self.mpileup_stats holds the call's statistics."""
+        n = len(names)
+        c_names = _cstr_array(names)
+        c_lengths = (C.c_int64 * n)(*[int(x) for x in lengths])
+        keep = [None if s is None else (s if isinstance(s, bytes) else s.encode()) for s in (seqs if seqs is not None else [None] * n)]
+        c_seqs = (C.c_char_p * n)(*keep)
+        c_seq_lens = (C.c_int64 * n)(*[0 if s is None else len(s) for s in keep])
+        rd = RefDesc(n, c_names, c_lengths, c_seqs if seqs is not None else None, c_seq_lens if seqs is not None else None)
+        p = default_params(**params)
+        bufs = [np.ascontiguousarray(np.frombuffer(r, dtype=np.uint8) if isinstance(r, (bytes, bytearray)) else r, dtype=np.uint8) for r in samples]
+        m = len(bufs)
+        ptrs = (C.c_void_p * m)(*[b.ctypes.data if b.size else None for b in bufs])
+        sizes = (C.c_uint64 * m)(*[b.size for b in bufs])
+        bed = list(bed or [])
+        bt = (C.c_int32 * len(bed))(*[r[0] for r in bed])
+        bb = (C.c_int64 * len(bed))(*[r[1] for r in bed])
+        be = (C.c_int64 * len(bed))(*[r[2] for r in bed])
+        text = C.POINTER(C.c_char)()
+        nb = C.c_uint64()
+        st = (C.c_uint64 * 8)()
+        check(lib.msnv_mpileup_text_records(self._h, C.byref(rd), C.byref(p), len(bed), bt, bb, be, ptrs, sizes, m, C.byref(text), C.byref(nb), st))
+        try:
+            out = C.string_at(text, nb.value)
+        finally:
+            lib.msnv_free(text)
+        self.mpileup_stats = _mpileup_stats(st)
+        return out
+
+    def mpileup_files(self, bams, fasta, out, bed=None, host_threads=0, **params):
+        """`samtools mpileup -f fasta [-l bed] -B -b <bams> > out` (msnv_mpileup_text); out None or "-": stdout; bed: the path of a BED
+        file.  Returns the call's statistics."""
+        a = _lib.MpileupTextArgs()
+        paths = _cstr_array(list(bams))
+        a.bam_paths = paths; a.n_bams = len(bams)
+        a.ref_fasta = fasta.encode() if fasta else None
+        a.bed_split_path = bed.encode() if bed else None
+        a.out_path = out.encode() if out else None
+        a.host_threads = host_threads
+        a.params = default_params(**params)
+        st = (C.c_uint64 * 8)()
+        check(lib.msnv_mpileup_text(self._h, C.byref(a), st))
+        self.mpileup_stats = _mpileup_stats(st)
+        return self.mpileup_stats
+
     def __enter__(self):
         return self
 
@@ -57,6 +106,18 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+def mpileup_text_geometry():
+    """(positions per tile, read descriptors taken through LDS at a time) of the mpileup-text kernels (csrc/mptext.h)."""
+    t, b = C.c_int32(), C.c_int32()
+    lib.msnv_mpileup_text_geometry(C.byref(t), C.byref(b))
+    return t.value, b.value
+
+
+def _mpileup_stats(st):
+    return {"lines": int(st[0]), "samples": int(st[1]), "text_bytes": int(st[2]), "elements": int(st[3]), "measure_ms": int(st[4]),
+            "write_ms": int(st[5]), "batches": int(st[6]), "rounds": int(st[7])}
 
 
 def _cstr_array(strings):

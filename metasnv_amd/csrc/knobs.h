@@ -194,5 +194,12 @@ inline uint64_t text_chunk_bytes(uint64_t default_bytes) { long long v = 0; retu
 // MSNV_TEXT_REPEAT (1, at least 1): n - 1 untimed launches before the timed one.  Per call.  Profiling only (profiles/text_bench.py).
 inline int text_repeat() { return std::max(1, int_or("MSNV_TEXT_REPEAT", 1)); }
 
+// ---------------------------------------------------------------------------------- the mpileup-text writer (mptext.cpp)
+// MSNV_MPTEXT_BATCH (64 MB; at least 1): bytes of text per batch that leaves the device (whole tiles; a tile that is longer is a batch
+// of its own).  Per call (tests/test_gpu_mpileup_write.py sets a few bytes and a few kilobytes).
+inline uint64_t mptext_batch_bytes() { return (uint64_t)std::max<long long>(1, i64_or("MSNV_MPTEXT_BATCH", 64ll << 20)); }
+// MSNV_MPTEXT_ROUND (64, at least 1): samples per round -- pre-pass on the host threads, one upload.  Per call (tests/test_gpu_mpileup_write.py).
+inline int mptext_round_samples() { return std::max(1, int_or("MSNV_MPTEXT_ROUND", 64)); }
+
 }  // namespace knob
 }  // namespace msnv
