@@ -13,7 +13,7 @@
 //   msnv_scan_sub2        one LANE per sub-segment of a few kilobytes of a stream: guesses where the block_size chain enters its bytes, walks the
 //                         records that start there and MEASURES each as it goes (header, CIGAR geometry, the read filters of both tools,
 //                         qaCompute's statistics, the pieces / seq bytes / M intervals the record will emit) into a 32-byte slot
-//   msnv_scan_check / _fix2 / msnv_sub_bounds + ONE scan of the sub-segments' sums: the seams, what crosses them, the round's totals
+//   msnv_scan_check / _fix2 / msnv_sub_bounds + ONE scan of the sub-segments' sums: the seams (SubWalk::settle), what crosses them, the round's totals
 //                         -- the stage's one wait: the host sizes every buffer from them
 //   msnv_scan_write2      the records' tables in record order: offsets, {position, end, contig, sample}, places before every record
 //   msnv_depth2           pileup reads alive at every read start (mpileup -d, the depth bound of the tile index, the upper bound of a
@@ -32,6 +32,9 @@
 // the cap; two or more reads pass htslib's overlap_push precondition; the upper bound of a base string reaches the limit).  The host
 // pre-pass (pack.cpp: host_prepass) keeps three corner cases (a template with more alignments than the overlap kernel's slots, reads that
 // span more than 16 384 reference positions, an indel of half a million bases) and MSNV_PREPASS=host.
+// The sub-segment walk is written once for both routes and the dealer: sub_of / sub_at, guess_entry, scan_sub_body<Walk> and
+// scan_fix_body<Walk> over WalkPlain (offsets) or WalkMeasure (slots and sums), wave_records for the two write kernels; SubWalk on the host
+// (the walk's buffers, the seam loop).  AccAdd is what a record or a sub-segment adds to its sample's accumulators.
 #include <algorithm>
 #include <chrono>
 #include <cstdint>
@@ -177,6 +180,39 @@ __device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {
     for (int o = 32; o > 0; o >>= 1) { const unsigned long long w = __shfl_down(v, o); v = w < v ? w : v; }
     return v;
 }
+// What some records add to their sample's DpAcc: one record's (a lane of msnv_measure_reads), one sub-segment's (a lane of msnv_scan_write2),
+// or -- acc_wave, in lane 0 -- a wavefront's, when all of it is one sample's.  The caller picks the copy (ACC_COPIES) that acc_add adds to.
+struct AccAdd {
+    uint32_t total = 0, unmapped = 0, zeroq = 0, proper = 0, dup = 0, any_mapped = 0, n_pile_reads = 0, n_ovl = 0;
+    unsigned long long n_bases = 0, alg8d = 0, alg_cigar = 0, alg_seq = 0, alg_qual = 0;
+    unsigned long long err = ~0ull, first_pile = ~0ull, beyond = ~0ull;        // minima (~0: none)
+};
+__device__ __forceinline__ AccAdd acc_wave(const AccAdd &x) {
+    AccAdd t;
+    t.total = wave_sum(x.total); t.unmapped = wave_sum(x.unmapped); t.zeroq = wave_sum(x.zeroq); t.proper = wave_sum(x.proper); t.dup = wave_sum(x.dup);
+    t.any_mapped = wave_sum(x.any_mapped); t.n_pile_reads = wave_sum(x.n_pile_reads); t.n_ovl = wave_sum(x.n_ovl);
+    t.n_bases = wave_sum(x.n_bases); t.alg8d = wave_sum(x.alg8d); t.alg_cigar = wave_sum(x.alg_cigar); t.alg_seq = wave_sum(x.alg_seq); t.alg_qual = wave_sum(x.alg_qual);
+    t.err = wave_min(x.err); t.first_pile = wave_min(x.first_pile); t.beyond = wave_min(x.beyond);
+    return t;
+}
+__device__ __forceinline__ void acc_add(DpAcc &a, const AccAdd &x) {       // (an atomic only where there is something to add: most counters of most wavefronts are zero)
+    if (x.total) atomicAdd(&a.total, x.total);
+    if (x.unmapped) atomicAdd(&a.unmapped, x.unmapped);
+    if (x.zeroq) atomicAdd(&a.zeroq, x.zeroq);
+    if (x.proper) atomicAdd(&a.proper, x.proper);
+    if (x.dup) atomicAdd(&a.dup, x.dup);
+    if (x.any_mapped) atomicOr(&a.any_mapped, 1u);
+    if (x.n_pile_reads) atomicAdd(&a.n_pile_reads, x.n_pile_reads);
+    if (x.n_ovl) atomicAdd(&a.n_ovl, x.n_ovl);
+    if (x.n_bases) atomicAdd(&a.n_bases, x.n_bases);
+    if (x.alg8d) atomicAdd(&a.alg8d, x.alg8d);
+    if (x.alg_cigar) atomicAdd(&a.alg_cigar, x.alg_cigar);
+    if (x.alg_seq) atomicAdd(&a.alg_seq, x.alg_seq);
+    if (x.alg_qual) atomicAdd(&a.alg_qual, x.alg_qual);
+    if (x.err != ~0ull) atomicMin(&a.err, x.err);
+    if (x.first_pile != ~0ull) atomicMin(&a.first_pile, x.first_pile);
+    if (x.beyond != ~0ull) atomicMin(&a.beyond, x.beyond);
+}
 
 // ------------------------------------------------------------------------------------------ record boundaries
 // The records of a BAM are a chain: the next one starts block_size + 4 bytes behind this one (qaCompute.cpp:441 reads them with sam_read1
@@ -292,7 +328,9 @@ __global__ __launch_bounds__(64) void msnv_scan_segments(const uint8_t *raw, con
 // seam on the device -- a sub-segment's walk must have begun exactly where the chain stood after the sub-segments before it (running maximum
 // of the walks' ends) --, a scan of the accepted counts gives every sub-segment its first record, a third kernel writes the offsets out.
 // One wait, for the record count.  A seam that does not hold (a wrong guess: a record longer than a sub-segment with something
-// header-like inside) or a malformed chain sends the round through msnv_scan_segments above, which repairs and reports.
+// header-like inside) is repaired on the device: msnv_scan_check finds every stream's first such sub-segment, msnv_scan_fix walks it again
+// from the true entry (below).  Only a chain that breaks from its true entry, or a sub-segment with more records than slots, sends the round
+// through msnv_scan_segments above, which words the error.
 struct SubStream { unsigned long long beg, end; uint32_t sub0, pad; };        // bytes [beg, end) of the round buffer, first sub-segment
 __device__ __forceinline__ bool hdr_plausible(const uint8_t *raw, unsigned long long o, unsigned long long s_end, int n_contigs, uint32_t &bs_out) {
     if (s_end - o < 36) return false;
@@ -320,54 +358,90 @@ __device__ __forceinline__ uint32_t sub_stream_of(const SubStream *ss, uint32_t 
     while (b - a > 1) { const uint32_t m = (a + b) / 2; if (ss[m].sub0 <= g) a = m; else b = m; }
     return a;
 }
-__global__ __launch_bounds__(256) void msnv_scan_sub(const uint8_t *raw, const SubStream *ss, uint32_t n_streams, uint32_t n_sub, uint32_t sub_bytes, uint32_t cap, int n_contigs,
-                                                     unsigned long long *first, unsigned long long *stop, uint32_t *cnt, uint16_t *delta, uint32_t *flags) {
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_sub) return;
-    const SubStream S = ss[sub_stream_of(ss, n_streams, g)];
-    const unsigned long long b = S.beg + (unsigned long long)(g - S.sub0) * sub_bytes, e = b + sub_bytes < S.end ? b + sub_bytes : S.end;
+// Sub-segment g: its stream (si, S) and its bytes [b, e) of the round buffer.  sub_at when the stream is known, sub_of finds it.
+struct Sub { SubStream S; uint32_t si; unsigned long long b, e; };
+__device__ __forceinline__ Sub sub_at(const SubStream *ss, uint32_t si, uint32_t g, uint32_t sub_bytes) {
+    Sub u; u.S = ss[si]; u.si = si;
+    u.b = u.S.beg + (unsigned long long)(g - u.S.sub0) * sub_bytes; u.e = u.b + sub_bytes < u.S.end ? u.b + sub_bytes : u.S.end;
+    return u;
+}
+__device__ __forceinline__ Sub sub_of(const SubStream *ss, uint32_t n_streams, uint32_t g, uint32_t sub_bytes) { return sub_at(ss, sub_stream_of(ss, n_streams, g), g, sub_bytes); }
+// Where the chain enters [b, e), guessed: the first offset that is plausible with its two successors (~0: none)
+__device__ __forceinline__ unsigned long long guess_entry(const uint8_t *raw, const SubStream &S, unsigned long long b, unsigned long long e, int n_contigs) {
+    // sixteen offsets a step from 32 bytes in registers (a load per offset made the kernel L2-bound: every lane steps through its own
+    // cache lines); block_size and refID of a candidate are looked at first -- almost nothing else passes them
     unsigned long long f = ~0ull;
-    if (g == S.sub0) f = S.beg;
-    else {
-        // sixteen offsets a step from 32 bytes in registers (a load per offset made the kernel L2-bound: every lane steps through its own
-        // cache lines); block_size and refID of a candidate are looked at first -- almost nothing else passes them
-        const unsigned long long a0 = b & ~15ull;                  // (aligned 16-byte pieces; the buffer is readable 256 bytes past the last stream)
-        uint4 lo4 = *reinterpret_cast<const uint4 *>(raw + a0);
-        for (unsigned long long base16 = a0; base16 < e && f == ~0ull; base16 += 16) {
-            const uint4 hi4 = *reinterpret_cast<const uint4 *>(raw + base16 + 16);
-            const uint32_t w[7] = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z};
+    const unsigned long long a0 = b & ~15ull;                  // (aligned 16-byte pieces; the buffer is readable 256 bytes past the last stream)
+    uint4 lo4 = *reinterpret_cast<const uint4 *>(raw + a0);
+    for (unsigned long long base16 = a0; base16 < e && f == ~0ull; base16 += 16) {
+        const uint4 hi4 = *reinterpret_cast<const uint4 *>(raw + base16 + 16);
+        const uint32_t w[7] = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z};
 #pragma unroll
-            for (uint32_t k = 0; k < 16u; ++k) {
-                const uint32_t bs = __builtin_amdgcn_alignbyte(w[(k >> 2) + 1], w[k >> 2], k & 3u);
-                const int32_t tid = (int32_t)__builtin_amdgcn_alignbyte(w[(k >> 2) + 2], w[(k >> 2) + 1], k & 3u);
-                const unsigned long long o = base16 + k;
-                if ((int32_t)bs < 32 || bs >= (1u << 28) || tid < -1 || tid >= n_contigs || o < b || o >= e || f != ~0ull) continue;
-                uint32_t bs1 = 0;
-                if (!hdr_plausible(raw, o, S.end, n_contigs, bs1)) continue;
-                bool ok = true;
-                unsigned long long o2 = o + 4ull + bs1;
-                for (int d = 0; d < 2 && ok && o2 < S.end; ++d) { uint32_t b2 = 0; ok = hdr_plausible(raw, o2, S.end, n_contigs, b2); o2 += 4ull + b2; }
-                if (ok) f = o;
-            }
-            lo4 = hi4;
+        for (uint32_t k = 0; k < 16u; ++k) {
+            const uint32_t bs = __builtin_amdgcn_alignbyte(w[(k >> 2) + 1], w[k >> 2], k & 3u);
+            const int32_t tid = (int32_t)__builtin_amdgcn_alignbyte(w[(k >> 2) + 2], w[(k >> 2) + 1], k & 3u);
+            const unsigned long long o = base16 + k;
+            if ((int32_t)bs < 32 || bs >= (1u << 28) || tid < -1 || tid >= n_contigs || o < b || o >= e || f != ~0ull) continue;
+            uint32_t bs1 = 0;
+            if (!hdr_plausible(raw, o, S.end, n_contigs, bs1)) continue;
+            bool ok = true;
+            unsigned long long o2 = o + 4ull + bs1;
+            for (int d = 0; d < 2 && ok && o2 < S.end; ++d) { uint32_t b2 = 0; ok = hdr_plausible(raw, o2, S.end, n_contigs, b2); o2 += 4ull + b2; }
+            if (ok) f = o;
         }
+        lo4 = hi4;
     }
-    uint32_t n = 0; unsigned long long off = f;
-    bool bad = false;
-    if (f != ~0ull) {
+    return f;
+}
+// A Walk goes over one sub-segment's records.  Two exist: WalkPlain here (the offsets: the careful route, the dealer) and WalkMeasure
+// further down (the slots and the sub-segment's SubInfo: the quick route).  What the scan and the fix body ask of one:
+//   walk(g, entry, b, e, s_end, cap, sums, n, off)   from `entry`, the records that start in [b, e): the first `cap` into sub-segment g's
+//                                                    slots; leaves their number in n, the chain's next offset in off, and adds what it
+//                                                    sums to `sums`; returns whether the chain held
+//   Sums, none()                                     what a walk sums, and its empty value (WalkPlain: nothing)
+//   keep(g, sums)                                    stores the sums of an ACCEPTED walk -- info[g] is written by the measuring walk only
+struct WalkPlain {
+    struct Sums {};
+    const uint8_t *raw; uint16_t *delta;
+    static __device__ __forceinline__ Sums none() { return Sums{}; }
+    __device__ __forceinline__ bool walk(uint32_t g, unsigned long long entry, unsigned long long b, unsigned long long e, unsigned long long s_end, uint32_t cap, Sums &,
+                                         uint32_t &n, unsigned long long &off) const {
         uint16_t *dl = delta + (size_t)g * cap;
+        n = 0; off = entry;
         while (off < e) {
-            if (S.end - off < 36) { bad = true; break; }
+            if (s_end - off < 36) return false;
             const uint32_t bs = ld32(raw + off);
-            if ((int32_t)bs < 32 || (unsigned long long)bs + 4 > S.end - off) { bad = true; break; }
+            if ((int32_t)bs < 32 || (unsigned long long)bs + 4 > s_end - off) return false;
             if (n < cap) dl[n] = (uint16_t)(off - b);
             ++n;
             off += 4ull + bs;
         }
+        return true;
     }
-    if ((bad || n > cap) && g != S.sub0) { first[g] = ~0ull - 1ull; stop[g] = 0ull; cnt[g] = 0u; return; }      // a walk from a GUESSED entry that breaks: a wrong guess (msnv_scan_repair walks again from the true one)
+    __device__ __forceinline__ void keep(uint32_t, const Sums &) const {}
+};
+// One lane per sub-segment: the entry (the stream's first byte, or a guess), the walk from it, the verdict.
+template <typename Walk>
+__device__ __forceinline__ void scan_sub_body(const uint8_t *raw, const SubStream *ss, uint32_t n_streams, uint32_t n_sub, uint32_t sub_bytes, uint32_t cap, int n_contigs,
+                                              unsigned long long *first, unsigned long long *stop, uint32_t *cnt, uint32_t *flags, const Walk &wk) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_sub) return;
+    const Sub u = sub_of(ss, n_streams, g, sub_bytes);
+    const bool guessed = g != u.S.sub0;
+    const unsigned long long f = guessed ? guess_entry(raw, u.S, u.b, u.e, n_contigs) : u.S.beg;
+    uint32_t n = 0; unsigned long long off = f;
+    bool ok = true;
+    typename Walk::Sums sums = Walk::none();
+    if (f != ~0ull) ok = wk.walk(g, f, u.b, u.e, u.S.end, cap, sums, n, off);
+    ok = ok && n <= cap;
+    if (!ok && guessed) { first[g] = ~0ull - 1ull; stop[g] = 0ull; cnt[g] = 0u; return; }      // a walk from a GUESSED entry that breaks: a wrong guess (the fix kernel walks again from the true one)
     first[g] = f; stop[g] = f != ~0ull ? off : 0ull; cnt[g] = n;
-    if (bad || n > cap) atomicOr(flags, 1u);                        // a malformed chain from the stream's first byte (or an impossible count): the careful kernel reports it
+    wk.keep(g, sums);
+    if (!ok) atomicOr(flags, 1u);                                   // a malformed chain from the stream's first byte (or more records than slots): the careful kernel / route reports or takes it
+}
+__global__ __launch_bounds__(256) void msnv_scan_sub(const uint8_t *raw, const SubStream *ss, uint32_t n_streams, uint32_t n_sub, uint32_t sub_bytes, uint32_t cap, int n_contigs,
+                                                     unsigned long long *first, unsigned long long *stop, uint32_t *cnt, uint16_t *delta, uint32_t *flags) {
+    scan_sub_body(raw, ss, n_streams, n_sub, sub_bytes, cap, n_contigs, first, stop, cnt, flags, WalkPlain{raw, delta});
 }
 // seams: cur = where the chain stands in front of sub-segment g = the largest end of a walk before it (the stream's first byte for its first
 // sub-segment: ends of earlier streams lie before it)
@@ -378,77 +452,81 @@ __global__ __launch_bounds__(256) void msnv_scan_sub(const uint8_t *raw, const S
 // it may lie a whole stream further on -- makes the ones behind it LOOK wrong): msnv_scan_check finds it, msnv_scan_fix walks it again from the
 // true entry, the host scans the ends again and asks once more -- as many passes as the worst stream has wrong guesses (usually none).
 // Flags: 2 = a sub-segment was fixed, 4 = the chain breaks from its TRUE entry (malformed input: the careful kernel words the error).
+__device__ __forceinline__ unsigned long long chain_before(const Sub &u, const unsigned long long *stop_max, uint32_t g) {      // (g is not its stream's first sub-segment)
+    const unsigned long long cur = stop_max[g - 1];
+    return cur > u.S.beg ? cur : u.S.beg;
+}
 __global__ void msnv_scan_check(const SubStream *ss, uint32_t n_streams, uint32_t n_sub, uint32_t sub_bytes, const unsigned long long *first, const unsigned long long *stop_max, uint32_t *cnt, uint32_t *first_bad) {
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_sub) { if (g == n_sub) cnt[g] = 0; return; }
-    const uint32_t si = sub_stream_of(ss, n_streams, g);
-    const SubStream S = ss[si];
-    if (g == S.sub0) return;                                        // (entered at the stream's first byte)
-    const unsigned long long b = S.beg + (unsigned long long)(g - S.sub0) * sub_bytes, e = b + sub_bytes < S.end ? b + sub_bytes : S.end;
-    unsigned long long cur = stop_max[g - 1];
-    cur = cur > S.beg ? cur : S.beg;
-    const unsigned long long want = cur >= e ? ~0ull : cur;         // cur >= e: a record runs across the whole sub-segment, nothing starts here
-    if (first[g] != want) atomicMin(&first_bad[si], g);
+    const Sub u = sub_of(ss, n_streams, g, sub_bytes);
+    if (g == u.S.sub0) return;                                      // (entered at the stream's first byte)
+    const unsigned long long cur = chain_before(u, stop_max, g);
+    const unsigned long long want = cur >= u.e ? ~0ull : cur;       // cur >= e: a record runs across the whole sub-segment, nothing starts here
+    if (first[g] != want) atomicMin(&first_bad[u.si], g);
 }
-__global__ void msnv_scan_fix(const uint8_t *raw, const SubStream *ss, uint32_t n_streams, uint32_t sub_bytes, uint32_t cap, unsigned long long *first, unsigned long long *stop,
-                              const unsigned long long *stop_max, uint32_t *cnt, uint16_t *delta, uint32_t *first_bad, uint32_t *flags) {
+// One lane per stream: its first sub-segment that guessed wrong, walked again from where the chain stands.
+template <typename Walk>
+__device__ __forceinline__ void scan_fix_body(const SubStream *ss, uint32_t n_streams, uint32_t sub_bytes, uint32_t cap, unsigned long long *first, unsigned long long *stop,
+                                              const unsigned long long *stop_max, uint32_t *cnt, uint32_t *first_bad, uint32_t *flags, const Walk &wk) {
     const uint32_t si = blockIdx.x * blockDim.x + threadIdx.x;
     if (si >= n_streams) return;
     const uint32_t g = first_bad[si];
     first_bad[si] = 0xffffffffu;                                    // (for the next pass)
     if (g == 0xffffffffu) return;
-    const SubStream S = ss[si];
-    const unsigned long long b = S.beg + (unsigned long long)(g - S.sub0) * sub_bytes, e = b + sub_bytes < S.end ? b + sub_bytes : S.end;
-    unsigned long long cur = stop_max[g - 1];
-    cur = cur > S.beg ? cur : S.beg;
+    const Sub u = sub_at(ss, si, g, sub_bytes);
+    const unsigned long long cur = chain_before(u, stop_max, g);
     atomicOr(flags, 2u);
-    if (cur >= e) { first[g] = ~0ull; stop[g] = 0ull; cnt[g] = 0u; return; }
+    typename Walk::Sums sums = Walk::none();
+    if (cur >= u.e) { first[g] = ~0ull; stop[g] = 0ull; cnt[g] = 0u; wk.keep(g, sums); return; }
     uint32_t n = 0; unsigned long long off = cur;
-    bool bad = false;
-    uint16_t *dl = delta + (size_t)g * cap;
-    while (off < e) {
-        if (S.end - off < 36) { bad = true; break; }
-        const uint32_t bs = ld32(raw + off);
-        if ((int32_t)bs < 32 || (unsigned long long)bs + 4 > S.end - off) { bad = true; break; }
-        if (n < cap) dl[n] = (uint16_t)(off - b);
-        ++n;
-        off += 4ull + bs;
-    }
-    if (bad || n > cap) { atomicOr(flags, 4u); return; }
+    if (!wk.walk(g, cur, u.b, u.e, u.S.end, cap, sums, n, off) || n > cap) { atomicOr(flags, 4u); return; }
     first[g] = cur; stop[g] = off; cnt[g] = n;
+    wk.keep(g, sums);
+}
+__global__ void msnv_scan_fix(const uint8_t *raw, const SubStream *ss, uint32_t n_streams, uint32_t sub_bytes, uint32_t cap, unsigned long long *first, unsigned long long *stop,
+                              const unsigned long long *stop_max, uint32_t *cnt, uint16_t *delta, uint32_t *first_bad, uint32_t *flags) {
+    scan_fix_body(ss, n_streams, sub_bytes, cap, first, stop, stop_max, cnt, first_bad, flags, WalkPlain{raw, delta});
 }
 struct U64Max { __device__ __host__ unsigned long long operator()(unsigned long long a, unsigned long long b) const { return a > b ? a : b; } };
-// the offsets out: a wavefront takes 64 consecutive sub-segments, whose records are consecutive in the list, and writes them 64 at a time
-// (every record finds its sub-segment among the wavefront's 64 by bisection over the lanes' first records)
-__global__ __launch_bounds__(256) void msnv_scan_write(const SubStream *ss, uint32_t n_streams, uint32_t n_sub, uint32_t sub_bytes, uint32_t cap, const uint32_t *cnt, const uint32_t *base,
-                                                       const uint16_t *delta, unsigned long long *rec_off, uint16_t *rec_sample, uint32_t *rec_base) {
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63u, g0 = g - lane;
-    if (g0 >= n_sub) return;
-    const bool have = g < n_sub;
-    uint32_t si = 0, w = 0xffffffffu; unsigned long long b = 0;
-    if (have) {
-        si = sub_stream_of(ss, n_streams, g);
-        const SubStream S = ss[si];
-        b = S.beg + (unsigned long long)(g - S.sub0) * sub_bytes;
-        w = base[g];
-        if (g == S.sub0) rec_base[si] = w;
-    }
-    const uint32_t n_here = (n_sub - g0 < 64u ? n_sub - g0 : 64u);
-    const uint32_t j_lo = __shfl(w, 0), j_hi = base[g0 + n_here];   // (base has n_sub + 1 entries)
+// The records in record order: a wavefront takes 64 consecutive sub-segments (n_here of them exist), whose records [w of lane 0, j_hi) are
+// consecutive in the list, 64 a step; record j finds its sub-segment among the wavefront's by bisection over the lanes' first records (w).
+// EVERY lane calls per_record(j, owner lane) in EVERY step -- it may shuffle the owner's values to itself, and a shuffle needs all lanes --,
+// so per_record guards its own stores with j < j_hi.
+template <typename PerRecord>
+__device__ __forceinline__ void wave_records(uint32_t w, uint32_t n_here, uint32_t j_hi, PerRecord &&per_record) {
+    const uint32_t lane = threadIdx.x & 63u, j_lo = __shfl(w, 0);
     for (uint32_t j0 = j_lo; j0 < j_hi; j0 += 64u) {
         const uint32_t j = j0 + lane;
-        // last lane t (< n_here) whose first record is at or before j
-        uint32_t lo = 0, hi = n_here;
+        uint32_t lo = 0, hi = n_here;                              // last lane t (< n_here) whose first record is at or before j
 #pragma unroll
         for (int it = 0; it < 6; ++it) {                           // (six halvings of at most 64 lanes; every lane takes every step: the shuffles need all lanes)
             const uint32_t m = (lo + hi) / 2;
             const uint32_t bm = __shfl(w, (int)m);
             if (hi - lo > 1) { if (bm <= j) lo = m; else hi = m; }
         }
+        per_record(j, lo);
+    }
+}
+// the offsets out
+__global__ __launch_bounds__(256) void msnv_scan_write(const SubStream *ss, uint32_t n_streams, uint32_t n_sub, uint32_t sub_bytes, uint32_t cap, const uint32_t *cnt, const uint32_t *base,
+                                                       const uint16_t *delta, unsigned long long *rec_off, uint16_t *rec_sample, uint32_t *rec_base) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63u, g0 = g - lane;
+    if (g0 >= n_sub) return;
+    uint32_t si = 0, w = 0xffffffffu; unsigned long long b = 0;
+    if (g < n_sub) {
+        const Sub u = sub_of(ss, n_streams, g, sub_bytes);
+        si = u.si; b = u.b;
+        w = base[g];
+        if (g == u.S.sub0) rec_base[si] = w;
+    }
+    const uint32_t n_here = (n_sub - g0 < 64u ? n_sub - g0 : 64u);
+    const uint32_t j_hi = base[g0 + n_here];                        // (base has n_sub + 1 entries)
+    wave_records(w, n_here, j_hi, [&](uint32_t j, uint32_t lo) {
         const uint32_t wt = __shfl(w, (int)lo), st = __shfl(si, (int)lo);
         const unsigned long long bt = __shfl(b, (int)lo);
         if (j < j_hi) { rec_off[j] = bt + delta[(size_t)(g0 + lo) * cap + (j - wt)]; rec_sample[j] = (uint16_t)st; }
-    }
+    });
 }
 
 struct CompactSeg { unsigned long long src; uint32_t dst, cnt, sample, pad; };
@@ -591,28 +669,26 @@ __global__ __launch_bounds__(256) void msnv_measure_reads(const uint8_t *raw, co
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = i < n_rec;
     const uint32_t s = valid ? rec_sample[i] : 0xffffffffu;
-    uint32_t st_total = 0, st_unmapped = 0, st_zeroq = 0, st_proper = 0, st_dup = 0, st_any = 0, n_pile = 0, n_ovl = 0;
-    unsigned long long m_pile = 0, alg8d = 0, alg_cigar = 0, alg_seq = 0, alg_qual = 0;
-    unsigned long long err = ~0ull, first_pile = ~0ull, beyond_at = ~0ull;
+    AccAdd c;                                                       // what this record adds to its sample's accumulators
     uint8_t flags = 0; unsigned long long key = 0; uint32_t o_end = 0, o_maxc = 0, o_np = 0, o_sb = 0, o_niv = 0, o_ftile = 0, o_spill = 0;
     bool need_sort = false, order_me = false;
     if (valid) {
         const uint8_t *p = raw + rec_off[i];
         const Rec r = rec_load(p, s_end[s] - rec_off[i]);
         const RecMeasure m = measure_one(r, ctg, P, ovr ? ovr[i] : 0u);
-        st_total = 1;
-        if (m.err) err = (unsigned long long)i << 3 | m.err;
-        st_unmapped = (m.st & ST_UNMAPPED) ? 1u : 0u; st_zeroq = (m.st & ST_ZEROQ) ? 1u : 0u; st_proper = (m.st & ST_PROPER) ? 1u : 0u; st_dup = (m.st & ST_DUP) ? 1u : 0u;
-        st_any = (m.st & ST_ANY) ? 1u : 0u; n_ovl = (m.st & ST_OVL) ? 1u : 0u;
+        c.total = 1;
+        if (m.err) c.err = (unsigned long long)i << 3 | m.err;
+        c.unmapped = (m.st & ST_UNMAPPED) ? 1u : 0u; c.zeroq = (m.st & ST_ZEROQ) ? 1u : 0u; c.proper = (m.st & ST_PROPER) ? 1u : 0u; c.dup = (m.st & ST_DUP) ? 1u : 0u;
+        c.any_mapped = (m.st & ST_ANY) ? 1u : 0u; c.n_ovl = (m.st & ST_OVL) ? 1u : 0u;
         flags = (uint8_t)m.flags; key = m.key; order_me = (m.st & ST_ORDER) != 0u;
         o_end = m.end; o_maxc = m.maxc; o_niv = m.niv; o_ftile = m.ftile; o_spill = m.spill; o_np = m.np; o_sb = m.sb;
-        if (m.st & ST_BEYOND) beyond_at = i;
+        if (m.st & ST_BEYOND) c.beyond = i;
         if (m.flags & RF_PILE) {
-            n_pile = 1; first_pile = i;
-            m_pile = m.m_bases;
-            alg8d = 16ull + 4ull * m.n_cigar + ((unsigned long long)m.m_bases + 1) / 2 + (unsigned long long)m.m_bases;
-            alg_cigar = 4ull * m.n_cigar;
-            if (m.st & ST_SHIPS) { alg_seq = m.a_seq; alg_qual = m.m_bases; }
+            c.n_pile_reads = 1; c.first_pile = i;
+            c.n_bases = m.m_bases;
+            c.alg8d = 16ull + 4ull * m.n_cigar + ((unsigned long long)m.m_bases + 1) / 2 + (unsigned long long)m.m_bases;
+            c.alg_cigar = 4ull * m.n_cigar;
+            if (m.st & ST_SHIPS) { c.alg_seq = m.a_seq; c.alg_qual = m.m_bases; }
             if (m.st & ST_OVERHANG) { atomicMax(&overhang[m.over_tid], m.over_end); misc[MISC_OVERHANG] = 1u; }
             need_sort = (m.st & ST_SORT) != 0u;
         }
@@ -644,7 +720,7 @@ __global__ __launch_bounds__(256) void msnv_measure_reads(const uint8_t *raw, co
             }
             if (have) {
                 const int32_t tj = (int32_t)(prev_key >> 32), pj = (int32_t)(uint32_t)prev_key, ti = (int32_t)(key >> 32), pi = (int32_t)(uint32_t)key;
-                if (ti < tj || (ti == tj && pi < pj)) { const unsigned long long e = (unsigned long long)i << 3 | ERR_UNSORTED; err = e < err ? e : err; }
+                if (ti < tj || (ti == tj && pi < pj)) { const unsigned long long e = (unsigned long long)i << 3 | ERR_UNSORTED; c.err = e < c.err ? e : c.err; }
             }
         }
     }
@@ -664,48 +740,9 @@ __global__ __launch_bounds__(256) void msnv_measure_reads(const uint8_t *raw, co
     const uint32_t s0 = __shfl(s, 0);
     const bool uniform = __all(s == s0 || !valid) && s0 != 0xffffffffu;
     if (uniform) {
-        const uint32_t t0 = wave_sum(st_total), t1 = wave_sum(st_unmapped), t2 = wave_sum(st_zeroq), t3 = wave_sum(st_proper), t4 = wave_sum(st_dup), t5 = wave_sum(st_any),
-                       t6 = wave_sum(n_pile), t7 = wave_sum(n_ovl);
-        const unsigned long long u0 = wave_sum(m_pile), u1 = wave_sum(alg8d), u2 = wave_sum(alg_cigar), u3 = wave_sum(alg_seq), u4 = wave_sum(alg_qual);
-        const unsigned long long e0 = wave_min(err), e1 = wave_min(first_pile), e2 = wave_min(beyond_at);
-        if ((threadIdx.x & 63u) == 0) {
-            DpAcc &a = acc[(size_t)s0 * ACC_COPIES + (blockIdx.x % ACC_COPIES)];
-            if (t0) atomicAdd(&a.total, t0);
-            if (t1) atomicAdd(&a.unmapped, t1);
-            if (t2) atomicAdd(&a.zeroq, t2);
-            if (t3) atomicAdd(&a.proper, t3);
-            if (t4) atomicAdd(&a.dup, t4);
-            if (t5) atomicOr(&a.any_mapped, 1u);
-            if (t6) atomicAdd(&a.n_pile_reads, t6);
-            if (t7) atomicAdd(&a.n_ovl, t7);
-            if (u0) atomicAdd(&a.n_bases, u0);
-            if (u1) atomicAdd(&a.alg8d, u1);
-            if (u2) atomicAdd(&a.alg_cigar, u2);
-            if (u3) atomicAdd(&a.alg_seq, u3);
-            if (u4) atomicAdd(&a.alg_qual, u4);
-            if (e0 != ~0ull) atomicMin(&a.err, e0);
-            if (e1 != ~0ull) atomicMin(&a.first_pile, e1);
-            if (e2 != ~0ull) atomicMin(&a.beyond, e2);
-        }
-    } else if (valid) {
-        DpAcc &a = acc[(size_t)s * ACC_COPIES + (blockIdx.x % ACC_COPIES)];
-        atomicAdd(&a.total, st_total);
-        if (st_unmapped) atomicAdd(&a.unmapped, 1u);
-        if (st_zeroq) atomicAdd(&a.zeroq, 1u);
-        if (st_proper) atomicAdd(&a.proper, 1u);
-        if (st_dup) atomicAdd(&a.dup, 1u);
-        if (st_any) atomicOr(&a.any_mapped, 1u);
-        if (n_pile) atomicAdd(&a.n_pile_reads, 1u);
-        if (n_ovl) atomicAdd(&a.n_ovl, 1u);
-        if (m_pile) atomicAdd(&a.n_bases, m_pile);
-        if (alg8d) atomicAdd(&a.alg8d, alg8d);
-        if (alg_cigar) atomicAdd(&a.alg_cigar, alg_cigar);
-        if (alg_seq) atomicAdd(&a.alg_seq, alg_seq);
-        if (alg_qual) atomicAdd(&a.alg_qual, alg_qual);
-        if (err != ~0ull) atomicMin(&a.err, err);
-        if (first_pile != ~0ull) atomicMin(&a.first_pile, first_pile);
-        if (beyond_at != ~0ull) atomicMin(&a.beyond, beyond_at);
-    }
+        const AccAdd t = acc_wave(c);
+        if ((threadIdx.x & 63u) == 0) acc_add(acc[(size_t)s0 * ACC_COPIES + (blockIdx.x % ACC_COPIES)], t);
+    } else if (valid) acc_add(acc[(size_t)s * ACC_COPIES + (blockIdx.x % ACC_COPIES)], c);
 }
 
 // ------------------------------------------------------------------------------------------ depth at every read start
@@ -756,150 +793,94 @@ struct SubInfo {
     uint32_t maxc_big;                                // some pileup read's longest element does not fit the slot's 19 bits
 };
 constexpr uint32_t MAXC_SAT = 0x7ffffu;
-// One sub-segment's records from `entry`: the chain, the slots, the sums.  Returns false when the chain breaks.
-// st: this lane's column of the workgroup's statistics words in LDS (WALK_STATS rows of blockDim.x words: eleven sums a lane would otherwise
-// keep in registers through the walk -- the kernel sits at the register step of its occupancy)
-constexpr uint32_t WALK_STATS = 11;
-__device__ __forceinline__ bool walk_sub2(const uint8_t *raw, unsigned long long s_end, unsigned long long b, unsigned long long e, unsigned long long entry, uint32_t cap,
-                                          const DpContig *ctg, const DpParams &P, uint16_t *dl, Slot *slots, SubInfo &I, uint32_t &n_out, unsigned long long &off_out, uint32_t *st, uint32_t st_stride) {
-    for (uint32_t k = 0; k < WALK_STATS; ++k) st[k * st_stride] = 0u;
-    DpContig c_cache{}; int32_t c_tid = -2;
-    SubInfo s{};
-    s.fp_slot = s.fm_slot = s.err = s.beyond_slot = 0xffffffffu;
-    uint32_t n = 0; unsigned long long off = entry;
-    bool bad = false;
-    unsigned long long prev_key = 0; bool have_prev = false;                  // last mapped record of this walk
-    uint32_t lp_sample_tid = 0, lp_ft = 0; bool have_lp = false;              // last pileup read of this walk
-    while (off < e) {
-        if (s_end - off < 36) { bad = true; break; }
-        const Rec r = rec_load(raw + off, s_end - off);
-        if ((int32_t)r.bs < 32 || (unsigned long long)r.bs + 4 > s_end - off) { bad = true; break; }
-        if (n < cap) {
-            const RecMeasure m = measure_one(r, ctg, P, 0u, &c_cache, &c_tid);
-            uint32_t err = m.err;
-            if (m.st & ST_ORDER) {                                             // coordinate order inside the walk (across sub-segments: msnv_sub_bounds)
-                if (have_prev) {
-                    const int32_t tj = (int32_t)(prev_key >> 32), pj = (int32_t)(uint32_t)prev_key, ti = (int32_t)(m.key >> 32), pi = (int32_t)(uint32_t)m.key;
-                    if ((ti < tj || (ti == tj && pi < pj)) && !err) err = ERR_UNSORTED;
+// The measuring Walk: the chain, the slots, the sums.  The sums go straight into the SubInfo and live in registers through the walk:
+// msnv_scan_sub2 takes 122 VGPRs, no scratch, no LDS, 4 waves per SIMD (MEASURED.md has the table).
+struct WalkMeasure {
+    typedef SubInfo Sums;
+    const uint8_t *raw; const DpContig *ctg; const DpParams &P; uint16_t *delta; Slot *slots; SubInfo *info;
+    static __device__ __forceinline__ SubInfo none() { SubInfo s{}; s.fp_slot = s.fm_slot = s.err = s.beyond_slot = 0xffffffffu; return s; }
+    __device__ __forceinline__ bool walk(uint32_t g, unsigned long long entry, unsigned long long b, unsigned long long e, unsigned long long s_end, uint32_t cap, SubInfo &s,
+                                         uint32_t &n, unsigned long long &off) const {
+        uint16_t *dl = delta + (size_t)g * cap; Slot *sl = slots + (size_t)g * cap;
+        DpContig c_cache{}; int32_t c_tid = -2;
+        n = 0; off = entry;
+        unsigned long long prev_key = 0; bool have_prev = false;                  // last mapped record of this walk
+        uint32_t lp_sample_tid = 0, lp_ft = 0; bool have_lp = false;              // last pileup read of this walk
+        while (off < e) {
+            if (s_end - off < 36) return false;
+            const Rec r = rec_load(raw + off, s_end - off);
+            if ((int32_t)r.bs < 32 || (unsigned long long)r.bs + 4 > s_end - off) return false;
+            if (n < cap) {
+                const RecMeasure m = measure_one(r, ctg, P, 0u, &c_cache, &c_tid);
+                uint32_t err = m.err;
+                if (m.st & ST_ORDER) {                                             // coordinate order inside the walk (across sub-segments: msnv_sub_bounds)
+                    if (have_prev) {
+                        const int32_t tj = (int32_t)(prev_key >> 32), pj = (int32_t)(uint32_t)prev_key, ti = (int32_t)(m.key >> 32), pi = (int32_t)(uint32_t)m.key;
+                        if ((ti < tj || (ti == tj && pi < pj)) && !err) err = ERR_UNSORTED;
+                    }
                 }
-            }
-            if (m.flags & RF_MAPPED) {
-                if (s.fm_slot == 0xffffffffu) { s.fm_slot = n; s.fm_key = m.key; }
-                s.lm_key = m.key; prev_key = m.key; have_prev = true;
-            }
-            uint32_t run_start = 0, grp_start = 0;
-            if (m.flags & RF_PILE) {
-                const uint32_t t = (uint32_t)(m.key >> 32);
-                if (!have_lp) { s.fp_slot = n; s.fp_tid = t; s.fp_ftile = m.ftile; }
-                else {
-                    run_start = t != lp_sample_tid ? 1u : 0u;
-                    grp_start = (run_start || m.ftile != lp_ft) ? 1u : 0u;
-                    if (!run_start && lp_ft > m.ftile) s.flags |= 1u;           // (a read whose first aligned base lies in an earlier tile than its predecessor's: leading deletions)
+                if (m.flags & RF_MAPPED) {
+                    if (s.fm_slot == 0xffffffffu) { s.fm_slot = n; s.fm_key = m.key; }
+                    s.lm_key = m.key; prev_key = m.key; have_prev = true;
                 }
-                lp_sample_tid = t; lp_ft = m.ftile; have_lp = true;
-                s.lp_tid = t; s.lp_ftile = m.ftile;
-                s.runs += run_start; s.grps += grp_start;
+                uint32_t run_start = 0, grp_start = 0;
+                if (m.flags & RF_PILE) {
+                    const uint32_t t = (uint32_t)(m.key >> 32);
+                    if (!have_lp) { s.fp_slot = n; s.fp_tid = t; s.fp_ftile = m.ftile; }
+                    else {
+                        run_start = t != lp_sample_tid ? 1u : 0u;
+                        grp_start = (run_start || m.ftile != lp_ft) ? 1u : 0u;
+                        if (!run_start && lp_ft > m.ftile) s.flags |= 1u;           // (a read whose first aligned base lies in an earlier tile than its predecessor's: leading deletions)
+                    }
+                    lp_sample_tid = t; lp_ft = m.ftile; have_lp = true;
+                    s.lp_tid = t; s.lp_ftile = m.ftile;
+                    s.runs += run_start; s.grps += grp_start;
+                }
+                if (err && s.err == 0xffffffffu) s.err = n << 3 | err;
+                if ((m.st & ST_BEYOND) && s.beyond_slot == 0xffffffffu) s.beyond_slot = n;
+                if (m.st & ST_SORT) s.flags |= 1u;
+                if (m.st & ST_OVERHANG) {
+                    if ((s.flags & 2u) && s.over_tid != m.over_tid) s.flags |= 4u;
+                    if (!(s.flags & 2u) || m.over_end > s.over_end) { s.over_tid = m.over_tid; s.over_end = m.over_end; }
+                    s.flags |= 2u;
+                }
+                const uint32_t mc = m.maxc < MAXC_SAT ? m.maxc : MAXC_SAT;
+                if ((m.flags & RF_PILE) && m.maxc >= MAXC_SAT) s.maxc_big = 1u;
+                Slot q;
+                q.a = make_uint4((uint32_t)m.key, m.end, (uint32_t)(m.key >> 32), mc << 13 | grp_start << 8 | run_start << 7 | (err & 7u) << 4 | (m.flags & 15u));
+                q.b = make_uint4(m.ftile, s.seqb | s.npiece << 16, s.niv | s.spill << 16, s.pile | s.runs << 8 | s.grps << 16);
+                sl[n] = q;
+                dl[n] = (uint16_t)(off - b);
+                // ---- the sub-segment's sums
+                if (m.st & ST_UNMAPPED) s.st_unmapped += 1u;
+                if (m.st & ST_ZEROQ) s.st_zeroq += 1u;
+                if (m.st & ST_PROPER) s.st_proper += 1u;
+                if (m.st & ST_DUP) s.st_dup += 1u;
+                if (m.st & ST_ANY) s.st_any += 1u;
+                if (m.st & ST_OVL) s.st_ovl += 1u;
+                if (m.flags & RF_PILE) {
+                    s.pile += 1u; s.m_pile += m.m_bases;
+                    s.alg8d += 16u + 4u * m.n_cigar + (m.m_bases + 1u) / 2u + m.m_bases; s.alg_cigar += 4u * m.n_cigar;
+                    if (m.st & ST_SHIPS) { s.alg_seq += m.a_seq; s.alg_qual += m.m_bases; }
+                }
+                s.npiece += m.np; s.niv += m.niv; s.spill += m.spill; s.seqb += m.sb;
+                if ((s.npiece | s.niv | s.spill | s.seqb) > 0xffffu || s.pile > 0xffu) s.flags |= 8u;      // (a SEQ-less read with a CIGAR of thousands of bases, sub-segments of many kilobytes: the careful route's)
             }
-            if (err && s.err == 0xffffffffu) s.err = n << 3 | err;
-            if ((m.st & ST_BEYOND) && s.beyond_slot == 0xffffffffu) s.beyond_slot = n;
-            if (m.st & ST_SORT) s.flags |= 1u;
-            if (m.st & ST_OVERHANG) {
-                if ((s.flags & 2u) && s.over_tid != m.over_tid) s.flags |= 4u;
-                if (!(s.flags & 2u) || m.over_end > s.over_end) { s.over_tid = m.over_tid; s.over_end = m.over_end; }
-                s.flags |= 2u;
-            }
-            const uint32_t mc = m.maxc < MAXC_SAT ? m.maxc : MAXC_SAT;
-            if ((m.flags & RF_PILE) && m.maxc >= MAXC_SAT) s.maxc_big = 1u;
-            Slot q;
-            q.a = make_uint4((uint32_t)m.key, m.end, (uint32_t)(m.key >> 32), mc << 13 | grp_start << 8 | run_start << 7 | (err & 7u) << 4 | (m.flags & 15u));
-            q.b = make_uint4(m.ftile, s.seqb | s.npiece << 16, s.niv | s.spill << 16, s.pile | s.runs << 8 | s.grps << 16);
-            slots[n] = q;
-            dl[n] = (uint16_t)(off - b);
-            // ---- the sub-segment's sums
-            if (m.st & ST_UNMAPPED) st[0] += 1u;
-            if (m.st & ST_ZEROQ) st[1 * st_stride] += 1u;
-            if (m.st & ST_PROPER) st[2 * st_stride] += 1u;
-            if (m.st & ST_DUP) st[3 * st_stride] += 1u;
-            if (m.st & ST_ANY) st[4 * st_stride] += 1u;
-            if (m.st & ST_OVL) st[5 * st_stride] += 1u;
-            if (m.flags & RF_PILE) {
-                s.pile += 1u; st[6 * st_stride] += m.m_bases;
-                st[7 * st_stride] += 16u + 4u * m.n_cigar + (m.m_bases + 1u) / 2u + m.m_bases; st[8 * st_stride] += 4u * m.n_cigar;
-                if (m.st & ST_SHIPS) { st[9 * st_stride] += m.a_seq; st[10 * st_stride] += m.m_bases; }
-            }
-            s.npiece += m.np; s.niv += m.niv; s.spill += m.spill; s.seqb += m.sb;
-            if ((s.npiece | s.niv | s.spill | s.seqb) > 0xffffu || s.pile > 0xffu) s.flags |= 8u;      // (a SEQ-less read with a CIGAR of thousands of bases, sub-segments of many kilobytes: the careful route's)
+            ++n;
+            off += 4ull + r.bs;
         }
-        ++n;
-        off += 4ull + r.bs;
+        return true;
     }
-    s.st_unmapped = st[0]; s.st_zeroq = st[1 * st_stride]; s.st_proper = st[2 * st_stride]; s.st_dup = st[3 * st_stride]; s.st_any = st[4 * st_stride]; s.st_ovl = st[5 * st_stride];
-    s.m_pile = st[6 * st_stride]; s.alg8d = st[7 * st_stride]; s.alg_cigar = st[8 * st_stride]; s.alg_seq = st[9 * st_stride]; s.alg_qual = st[10 * st_stride];
-    I = s; n_out = n; off_out = off;
-    return !bad;
-}
+    __device__ __forceinline__ void keep(uint32_t g, const SubInfo &s) const { info[g] = s; }
+};
 __global__ __launch_bounds__(256) void msnv_scan_sub2(const uint8_t *raw, const SubStream *ss, uint32_t n_streams, uint32_t n_sub, uint32_t sub_bytes, uint32_t cap, int n_contigs,
                                                       const DpContig *ctg, DpParams P, unsigned long long *first, unsigned long long *stop, uint32_t *cnt, uint16_t *delta, Slot *slots, SubInfo *info,
                                                       uint32_t *flags) {
-    __shared__ uint32_t s_stat[WALK_STATS * 256];
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_sub) return;
-    const SubStream S = ss[sub_stream_of(ss, n_streams, g)];
-    const unsigned long long b = S.beg + (unsigned long long)(g - S.sub0) * sub_bytes, e = b + sub_bytes < S.end ? b + sub_bytes : S.end;
-    unsigned long long f = ~0ull;
-    if (g == S.sub0) f = S.beg;
-    else {
-        const unsigned long long a0 = b & ~15ull;                  // (the entry guess of msnv_scan_sub, to the letter)
-        uint4 lo4 = *reinterpret_cast<const uint4 *>(raw + a0);
-        for (unsigned long long base16 = a0; base16 < e && f == ~0ull; base16 += 16) {
-            const uint4 hi4 = *reinterpret_cast<const uint4 *>(raw + base16 + 16);
-            const uint32_t w[7] = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z};
-#pragma unroll
-            for (uint32_t k = 0; k < 16u; ++k) {
-                const uint32_t bs = __builtin_amdgcn_alignbyte(w[(k >> 2) + 1], w[k >> 2], k & 3u);
-                const int32_t tid = (int32_t)__builtin_amdgcn_alignbyte(w[(k >> 2) + 2], w[(k >> 2) + 1], k & 3u);
-                const unsigned long long o = base16 + k;
-                if ((int32_t)bs < 32 || bs >= (1u << 28) || tid < -1 || tid >= n_contigs || o < b || o >= e || f != ~0ull) continue;
-                uint32_t bs1 = 0;
-                if (!hdr_plausible(raw, o, S.end, n_contigs, bs1)) continue;
-                bool ok = true;
-                unsigned long long o2 = o + 4ull + bs1;
-                for (int d = 0; d < 2 && ok && o2 < S.end; ++d) { uint32_t b2 = 0; ok = hdr_plausible(raw, o2, S.end, n_contigs, b2); o2 += 4ull + b2; }
-                if (ok) f = o;
-            }
-            lo4 = hi4;
-        }
-    }
-    uint32_t n = 0; unsigned long long off = f;
-    bool ok = true;
-    SubInfo I{};
-    I.fp_slot = I.fm_slot = I.err = I.beyond_slot = 0xffffffffu;
-    if (f != ~0ull) ok = walk_sub2(raw, S.end, b, e, f, cap, ctg, P, delta + (size_t)g * cap, slots + (size_t)g * cap, I, n, off, &s_stat[threadIdx.x], 256u);
-    if ((!ok || n > cap) && g != S.sub0) { first[g] = ~0ull - 1ull; stop[g] = 0ull; cnt[g] = 0u; return; }      // a walk from a GUESSED entry that breaks: a wrong guess (msnv_scan_fix2 walks again from the true one)
-    first[g] = f; stop[g] = f != ~0ull ? off : 0ull; cnt[g] = n;
-    info[g] = I;
-    if (!ok || n > cap) atomicOr(flags, 1u);                        // a malformed chain from the stream's first byte (or more records than slots): the careful route reports / takes it
+    scan_sub_body(raw, ss, n_streams, n_sub, sub_bytes, cap, n_contigs, first, stop, cnt, flags, WalkMeasure{raw, ctg, P, delta, slots, info});
 }
 __global__ void msnv_scan_fix2(const uint8_t *raw, const SubStream *ss, uint32_t n_streams, uint32_t sub_bytes, uint32_t cap, const DpContig *ctg, DpParams P, unsigned long long *first,
                                unsigned long long *stop, const unsigned long long *stop_max, uint32_t *cnt, uint16_t *delta, Slot *slots, SubInfo *info, uint32_t *first_bad, uint32_t *flags) {
-    __shared__ uint32_t s_stat[WALK_STATS * 64];
-    const uint32_t si = blockIdx.x * blockDim.x + threadIdx.x;
-    if (si >= n_streams) return;
-    const uint32_t g = first_bad[si];
-    first_bad[si] = 0xffffffffu;                                    // (for the next pass)
-    if (g == 0xffffffffu) return;
-    const SubStream S = ss[si];
-    const unsigned long long b = S.beg + (unsigned long long)(g - S.sub0) * sub_bytes, e = b + sub_bytes < S.end ? b + sub_bytes : S.end;
-    unsigned long long cur = stop_max[g - 1];
-    cur = cur > S.beg ? cur : S.beg;
-    atomicOr(flags, 2u);
-    SubInfo I{};
-    I.fp_slot = I.fm_slot = I.err = I.beyond_slot = 0xffffffffu;
-    if (cur >= e) { first[g] = ~0ull; stop[g] = 0ull; cnt[g] = 0u; info[g] = I; return; }
-    uint32_t n = 0; unsigned long long off = cur;
-    const bool ok = walk_sub2(raw, S.end, b, e, cur, cap, ctg, P, delta + (size_t)g * cap, slots + (size_t)g * cap, I, n, off, &s_stat[threadIdx.x], 64u);
-    if (!ok || n > cap) { atomicOr(flags, 4u); return; }
-    first[g] = cur; stop[g] = off; cnt[g] = n; info[g] = I;
+    scan_fix_body(ss, n_streams, sub_bytes, cap, first, stop, stop_max, cnt, first_bad, flags, WalkMeasure{raw, ctg, P, delta, slots, info});
 }
 // What crosses a sub-segment's front boundary, once every seam holds: does its first pileup read start a run / a group (against the last
 // pileup read of the nearest sub-segment of its stream in front of it that has one)?  is its first mapped record in coordinate order behind
@@ -913,7 +894,7 @@ __global__ __launch_bounds__(256) void msnv_sub_bounds(const SubStream *ss, uint
     uint32_t bf = 0;
     if (n) {
         SubInfo I = info[g];
-        const SubStream S = ss[sub_stream_of(ss, n_streams, g)];
+        const SubStream S = ss[sub_stream_of(ss, n_streams, g)];    // (the stream alone: no bytes are looked at here)
         if (I.fp_slot != 0xffffffffu) {
             bool have = false; uint32_t pt = 0, pf = 0;
             for (uint32_t k = g; k > S.sub0 && !have;) { --k; if (cnt[k] && info[k].fp_slot != 0xffffffffu) { have = true; pt = info[k].lp_tid; pf = info[k].lp_ftile; } }
@@ -935,7 +916,7 @@ __global__ __launch_bounds__(256) void msnv_sub_bounds(const SubStream *ss, uint
     }
     out[g] = c; bflag[g] = (uint8_t)bf;
 }
-// The records in record order, a wavefront per 64 consecutive sub-segments (msnv_scan_write's walk): offsets, samples, and from the slots +
+// The records in record order, a wavefront per 64 consecutive sub-segments (wave_records): offsets, samples, and from the slots +
 // the sub-segments' bases every record's row of the per-record tables.  The lane that holds a sub-segment adds its statistics to its
 // sample's accumulators first (one atomic per counter and wavefront when the 64 sub-segments are one stream's, as nearly always).
 struct RdTables {
@@ -956,22 +937,20 @@ __global__ __launch_bounds__(256) void msnv_scan_write2(const SubStream *ss, uin
     SubCnt B{}; uint32_t bf = 0, fp_slot = 0xffffffffu;
     {
         // ---- this lane's sub-segment: base, statistics, first error
-        uint32_t t_total = 0, t_unm = 0, t_zq = 0, t_pp = 0, t_dup = 0, t_any = 0, t_pile = 0, t_ovl = 0, need = 0;
-        unsigned long long u_bases = 0, u_8d = 0, u_cig = 0, u_seq = 0, u_qual = 0, e_err = ~0ull, e_first = ~0ull, e_beyond = ~0ull;
+        AccAdd c; uint32_t need = 0;
         if (have) {
-            si = sub_stream_of(ss, n_streams, g);
-            const SubStream S = ss[si];
-            b = S.beg + (unsigned long long)(g - S.sub0) * sub_bytes;
+            const Sub u = sub_of(ss, n_streams, g, sub_bytes);
+            si = u.si; b = u.b;
             B = base[g]; w = B.rec; bf = bflag[g];
-            if (g == S.sub0) T.rec_base[si] = w;
+            if (g == u.S.sub0) T.rec_base[si] = w;
             if (cnt[g]) {
                 const SubInfo I = info[g];
                 fp_slot = I.fp_slot;
-                t_total = cnt[g]; t_unm = I.st_unmapped; t_zq = I.st_zeroq; t_pp = I.st_proper; t_dup = I.st_dup; t_any = I.st_any; t_pile = I.pile; t_ovl = I.st_ovl;
-                u_bases = I.m_pile; u_8d = I.alg8d; u_cig = I.alg_cigar; u_seq = I.alg_seq; u_qual = I.alg_qual;
-                if (I.err != 0xffffffffu) e_err = (unsigned long long)(w + (I.err >> 3)) << 3 | (I.err & 7u);
-                if (I.fp_slot != 0xffffffffu) e_first = w + I.fp_slot;
-                if (I.beyond_slot != 0xffffffffu) e_beyond = w + I.beyond_slot;
+                c.total = cnt[g]; c.unmapped = I.st_unmapped; c.zeroq = I.st_zeroq; c.proper = I.st_proper; c.dup = I.st_dup; c.any_mapped = I.st_any; c.n_pile_reads = I.pile; c.n_ovl = I.st_ovl;
+                c.n_bases = I.m_pile; c.alg8d = I.alg8d; c.alg_cigar = I.alg_cigar; c.alg_seq = I.alg_seq; c.alg_qual = I.alg_qual;
+                if (I.err != 0xffffffffu) c.err = (unsigned long long)(w + (I.err >> 3)) << 3 | (I.err & 7u);
+                if (I.fp_slot != 0xffffffffu) c.first_pile = w + I.fp_slot;
+                if (I.beyond_slot != 0xffffffffu) c.beyond = w + I.beyond_slot;
                 if ((I.flags & 1u) || (bf & 4u)) atomicOr(&misc[MISC_SORT], 1u);
                 if (I.flags & 2u) { atomicMax(&overhang[I.over_tid], I.over_end); misc[MISC_OVERHANG] = 1u; }
                 if (I.flags & 4u) misc[MISC_OVERHANG] = 2u;             // (two contigs' worth in one sub-segment: the host takes the careful route)
@@ -980,64 +959,22 @@ __global__ __launch_bounds__(256) void msnv_scan_write2(const SubStream *ss, uin
         }
         const uint32_t s0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)si);
         if (__all(si == s0 || !have) && s0 != 0xffffffffu) {
-            const uint32_t a0 = wave_sum(t_total), a1 = wave_sum(t_unm), a2 = wave_sum(t_zq), a3 = wave_sum(t_pp), a4 = wave_sum(t_dup), a5 = wave_sum(t_any), a6 = wave_sum(t_pile), a7 = wave_sum(t_ovl);
-            const unsigned long long v0 = wave_sum(u_bases), v1 = wave_sum(u_8d), v2 = wave_sum(u_cig), v3 = wave_sum(u_seq), v4 = wave_sum(u_qual);
-            const unsigned long long m0 = wave_min(e_err), m1 = wave_min(e_first), m2 = wave_min(e_beyond);
+            const AccAdd t = acc_wave(c);
             uint32_t nd = need; for (int o = 32; o > 0; o >>= 1) nd |= __shfl_down(nd, o);
             if (lane == 0) {
-                DpAcc &a = acc[(size_t)s0 * ACC_COPIES + ((blockIdx.x * 4u + (threadIdx.x >> 6)) % ACC_COPIES)];
-                if (a0) atomicAdd(&a.total, a0);
-                if (a1) atomicAdd(&a.unmapped, a1);
-                if (a2) atomicAdd(&a.zeroq, a2);
-                if (a3) atomicAdd(&a.proper, a3);
-                if (a4) atomicAdd(&a.dup, a4);
-                if (a5) atomicOr(&a.any_mapped, 1u);
-                if (a6) atomicAdd(&a.n_pile_reads, a6);
-                if (a7) atomicAdd(&a.n_ovl, a7);
-                if (v0) atomicAdd(&a.n_bases, v0);
-                if (v1) atomicAdd(&a.alg8d, v1);
-                if (v2) atomicAdd(&a.alg_cigar, v2);
-                if (v3) atomicAdd(&a.alg_seq, v3);
-                if (v4) atomicAdd(&a.alg_qual, v4);
-                if (m0 != ~0ull) atomicMin(&a.err, m0);
-                if (m1 != ~0ull) atomicMin(&a.first_pile, m1);
-                if (m2 != ~0ull) atomicMin(&a.beyond, m2);
+                acc_add(acc[(size_t)s0 * ACC_COPIES + ((blockIdx.x * 4u + (threadIdx.x >> 6)) % ACC_COPIES)], t);
                 if (nd) atomicOr(&acc[(size_t)s0 * ACC_COPIES].need_host, nd);
             }
-        } else if (have && t_total) {
-            DpAcc &a = acc[(size_t)si * ACC_COPIES + (blockIdx.x % ACC_COPIES)];
-            atomicAdd(&a.total, t_total);
-            if (t_unm) atomicAdd(&a.unmapped, t_unm);
-            if (t_zq) atomicAdd(&a.zeroq, t_zq);
-            if (t_pp) atomicAdd(&a.proper, t_pp);
-            if (t_dup) atomicAdd(&a.dup, t_dup);
-            if (t_any) atomicOr(&a.any_mapped, 1u);
-            if (t_pile) atomicAdd(&a.n_pile_reads, t_pile);
-            if (t_ovl) atomicAdd(&a.n_ovl, t_ovl);
-            if (u_bases) atomicAdd(&a.n_bases, u_bases);
-            if (u_8d) atomicAdd(&a.alg8d, u_8d);
-            if (u_cig) atomicAdd(&a.alg_cigar, u_cig);
-            if (u_seq) atomicAdd(&a.alg_seq, u_seq);
-            if (u_qual) atomicAdd(&a.alg_qual, u_qual);
-            if (e_err != ~0ull) atomicMin(&a.err, e_err);
-            if (e_first != ~0ull) atomicMin(&a.first_pile, e_first);
-            if (e_beyond != ~0ull) atomicMin(&a.beyond, e_beyond);
+        } else if (have && c.total) {
+            acc_add(acc[(size_t)si * ACC_COPIES + (blockIdx.x % ACC_COPIES)], c);
             if (need) atomicOr(&acc[(size_t)si * ACC_COPIES].need_host, need);
         }
     }
     // ---- the records of the wavefront's sub-segments, 64 at a time
     const uint32_t n_here = (n_sub - g0 < 64u ? n_sub - g0 : 64u);
-    const uint32_t j_lo = __shfl(w, 0), j_hi = base[g0 + n_here].rec;   // (base has n_sub + 1 entries)
+    const uint32_t j_hi = base[g0 + n_here].rec;                    // (base has n_sub + 1 entries)
     uint32_t span_max = 0;
-    for (uint32_t j0 = j_lo; j0 < j_hi; j0 += 64u) {
-        const uint32_t j = j0 + lane;
-        uint32_t lo = 0, hi = n_here;                              // last lane t (< n_here) whose first record is at or before j
-#pragma unroll
-        for (int it = 0; it < 6; ++it) {
-            const uint32_t m = (lo + hi) / 2;
-            const uint32_t bm = __shfl(w, (int)m);
-            if (hi - lo > 1) { if (bm <= j) lo = m; else hi = m; }
-        }
+    wave_records(w, n_here, j_hi, [&](uint32_t j, uint32_t lo) {
         const uint32_t wt = __shfl(w, (int)lo), st = __shfl(si, (int)lo), bft = __shfl(bf, (int)lo), fpt = __shfl(fp_slot, (int)lo);
         const unsigned long long bt = __shfl(b, (int)lo);
         const uint32_t p_pile = __shfl(B.pile, (int)lo), p_np = __shfl(B.npiece, (int)lo), p_niv = __shfl(B.niv, (int)lo), p_sp = __shfl(B.spill, (int)lo), p_runs = __shfl(B.runs, (int)lo), p_grps = __shfl(B.grps, (int)lo);
@@ -1070,7 +1007,7 @@ __global__ __launch_bounds__(256) void msnv_scan_write2(const SubStream *ss, uin
             T.r_pre[j] = pre;
             T.r_ftile[j] = q.b.x; T.r_flags[j] = fl;
         }
-    }
+    });
     for (int o = 32; o > 0; o >>= 1) { const uint32_t x = __shfl_xor(span_max, o); span_max = x > span_max ? x : span_max; }
     if (lane == 0 && span_max > *(volatile uint32_t *)&misc[MISC_SPAN]) atomicMax(&misc[MISC_SPAN], span_max);
     // (entry n_rec of r_pre / rec_off: the round's totals and end -- written by the host's launch sequence)
@@ -2493,68 +2430,92 @@ static int stage_streams(hipStream_t st, const int device, BufPool &pool, const 
     return MSNV_OK;
 }
 
+// What the sub-segment walk of either route works on: the sub-segments' entries, ends, counts and offsets, the seam check's words.  A route
+// adds its own buffers and kernels: the walk and the fix kernel, and what it queues behind the repair before the one wait.
+struct SubWalk {
+    uint32_t n_sub = 0, sub_bytes = 0, cap = 0; size_t S = 0;
+    SubStream *d_ss = nullptr; unsigned long long *d_first = nullptr, *d_stop = nullptr, *d_stopmax = nullptr; uint32_t *d_cnt = nullptr; uint16_t *d_delta = nullptr;
+    uint32_t *d_fl = nullptr, *d_firstbad = nullptr;
+    SubWalk(size_t n_streams, uint32_t n_sub_, uint32_t sub_bytes_, uint32_t cap_) : n_sub(n_sub_), sub_bytes(sub_bytes_), cap(cap_), S(n_streams) {}
+    void take(BufPool &pool) {                                    // (the caller looks at pool.rc after its own takes)
+        d_ss = pool.take<SubStream>(S);
+        d_first = pool.take<unsigned long long>((uint64_t)n_sub + 1);
+        d_stop = pool.take<unsigned long long>((uint64_t)n_sub + 1);
+        d_stopmax = pool.take<unsigned long long>((uint64_t)n_sub + 1);
+        d_cnt = pool.take<uint32_t>((uint64_t)n_sub + 1);
+        d_delta = pool.take<uint16_t>((uint64_t)n_sub * cap + 8);
+        d_fl = pool.take<uint32_t>(4);
+        d_firstbad = pool.take<uint32_t>(S);
+    }
+    // the streams' sub-segments and ends up (d_send: the route's own copy of the ends), the flags cleared
+    int upload(hipStream_t st, const std::vector<SubStream> &ss, const std::vector<unsigned long long> &s_end, unsigned long long *d_send) {
+        HIP_TRY(hipMemcpyAsync(d_ss, ss.data(), S * sizeof(SubStream), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_send, s_end.data(), S * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(d_fl, 0, 16, st));
+        HIP_TRY(hipMemsetAsync(d_firstbad, 0xff, S * 4, st));
+        return MSNV_OK;
+    }
+    // The seams, behind the walk kernel: checked, every stream's first sub-segment that guessed wrong walked again -- fix() launches the route's
+    // fix kernel --, until none is left (usually the first look).  after() queues what the route wants behind the repair, so that every pass
+    // has ONE wait.  Leaves the flag word in `fl` (0: every seam holds; else the walk does not stand) and counts the repair passes.
+    template <typename Fix, typename After>
+    int settle(hipStream_t st, Prim &prim, Fix fix, After after, uint32_t &fl, uint64_t &n_redone) {
+        for (int pass = 0;; ++pass) {
+            if (int rc = prim.inclusive(d_stop, d_stopmax, (size_t)n_sub, U64Max())) return rc;
+            hipLaunchKernelGGL(msnv_scan_check, grid_for((uint64_t)n_sub + 1, 256), dim3(256), 0, st, d_ss, (uint32_t)S, n_sub, sub_bytes, d_first, d_stopmax, d_cnt, d_firstbad);
+            fix();
+            HIP_TRY(hipGetLastError());
+            if (int rc = after()) return rc;
+            HIP_TRY(hipMemcpyAsync(&fl, d_fl, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (!(fl & 2u) || (fl & 5u) || pass >= 4096) return MSNV_OK;
+            n_redone += 1;                                        // (counted: a repair pass)
+            HIP_TRY(hipMemsetAsync(d_fl, 0, 4, st));
+        }
+    }
+};
+
 // Record boundaries of staged streams, the quick way: sub-segments walked side by side, seams checked on the device.  `found` says whether
 // the walk stands; a chain that breaks or a sub-segment with more records than its slots leaves the round to scan_segments (counted).
 static int scan_sub_walk(hipStream_t st, BufPool &pool, const uint64_t *n_bytes, const size_t S, const size_t NC, ScanResult &R, bool &found) {
     found = false;
     const uint32_t sub_bytes = knob::scan_sub_bytes(knob::SCAN_SUB_STREAMS);   // (per call: tests shrink it)
-    const uint32_t cap = sub_bytes / 36u + 2u;
     std::vector<SubStream> ss(S);
     uint64_t n_sub64 = 0;
     for (size_t s = 0; s < S; ++s) { ss[s] = SubStream{R.s_beg[s], R.s_end[s], (uint32_t)n_sub64, 0u}; n_sub64 += std::max<uint64_t>(1, (n_bytes[s] + sub_bytes - 1) / sub_bytes); }
     if (n_sub64 >= 0x7ffffff0ull) return MSNV_OK;
-    const uint32_t n_sub = (uint32_t)n_sub64;
+    SubWalk W(S, (uint32_t)n_sub64, sub_bytes, sub_bytes / 36u + 2u);
+    const uint32_t n_sub = W.n_sub;
     uint8_t *const raw = R.raw;
     Timer tm(st);
     Prim prim(st);
     const size_t pool_from = pool.mark();
-    auto *d_ss = pool.take<SubStream>(S);
-    auto *d_first = pool.take<unsigned long long>((uint64_t)n_sub + 1);
-    auto *d_stop = pool.take<unsigned long long>((uint64_t)n_sub + 1);
-    auto *d_stopmax = pool.take<unsigned long long>((uint64_t)n_sub + 1);
-    auto *d_cnt = pool.take<uint32_t>((uint64_t)n_sub + 1);
+    W.take(pool);
     auto *d_base = pool.take<uint32_t>((uint64_t)n_sub + 1);
-    auto *d_delta = pool.take<uint16_t>((uint64_t)n_sub * cap + 8);
-    auto *d_fl = pool.take<uint32_t>(4);
     auto *d_recbase = pool.take<uint32_t>(S + 1);
     auto *d_send = pool.take<unsigned long long>(S);
     if (pool.rc) return pool.rc;
     if (int rc = prim.bind(pool, 1u << 20)) return rc;
     tm.start();
-    HIP_TRY(hipMemcpyAsync(d_ss, ss.data(), S * sizeof(SubStream), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_send, R.s_end.data(), S * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(d_fl, 0, 16, st));
-    hipLaunchKernelGGL(msnv_scan_sub, grid_for(n_sub, 256), dim3(256), 0, st, raw, d_ss, (uint32_t)S, n_sub, sub_bytes, cap, (int)NC, d_first, d_stop, d_cnt, d_delta, d_fl);
+    if (int rc = W.upload(st, ss, R.s_end, d_send)) return rc;
+    hipLaunchKernelGGL(msnv_scan_sub, grid_for(n_sub, 256), dim3(256), 0, st, raw, W.d_ss, (uint32_t)S, n_sub, sub_bytes, W.cap, (int)NC, W.d_first, W.d_stop, W.d_cnt, W.d_delta, W.d_fl);
     HIP_TRY(hipGetLastError());
     size_t need = 0;                                              // both scans' storage before either is queued
-    if (int rc = prim.inclusive(d_stop, d_stopmax, (size_t)n_sub, U64Max(), &need)) return rc;
-    if (int rc = prim.exclusive(d_cnt, d_base, 0u, (size_t)n_sub + 1, rocprim::plus<uint32_t>(), &need)) return rc;
+    if (int rc = prim.inclusive(W.d_stop, W.d_stopmax, (size_t)n_sub, U64Max(), &need)) return rc;
+    if (int rc = prim.exclusive(W.d_cnt, d_base, 0u, (size_t)n_sub + 1, rocprim::plus<uint32_t>(), &need)) return rc;
     if (int rc = prim.room(need)) return rc;
     uint32_t fl = 0;
-    auto *d_firstbad = pool.take<uint32_t>(S);
-    if (pool.rc) return pool.rc;
-    HIP_TRY(hipMemsetAsync(d_firstbad, 0xff, S * 4, st));
-    // (the seam loop is written twice, here and in Round::front_quick: the two differ in the fix kernel and in what is queued behind it before
-    // the one wait, and a shared form would need both as callbacks whose signatures are longer than the loop)
-    for (int pass = 0;; ++pass) {
-        // seams: checked, every stream's first sub-segment that guessed wrong walked again, until none is left (usually the first look)
-        if (int rc = prim.inclusive(d_stop, d_stopmax, (size_t)n_sub, U64Max())) return rc;
-        hipLaunchKernelGGL(msnv_scan_check, grid_for((uint64_t)n_sub + 1, 256), dim3(256), 0, st, d_ss, (uint32_t)S, n_sub, sub_bytes, d_first, d_stopmax, d_cnt, d_firstbad);
-        hipLaunchKernelGGL(msnv_scan_fix, grid_for(S, 64), dim3(64), 0, st, raw, d_ss, (uint32_t)S, sub_bytes, cap, d_first, d_stop, d_stopmax, d_cnt, d_delta, d_firstbad, d_fl);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&fl, d_fl, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (!(fl & 2u) || (fl & 5u) || pass >= 4096) break;
-        R.n_redone += 1;                                  // (counted: a repair pass)
-        HIP_TRY(hipMemsetAsync(d_fl, 0, 4, st));
-    }
+    auto fix = [&]() {
+        hipLaunchKernelGGL(msnv_scan_fix, grid_for(S, 64), dim3(64), 0, st, raw, W.d_ss, (uint32_t)S, sub_bytes, W.cap, W.d_first, W.d_stop, W.d_stopmax, W.d_cnt, W.d_delta, W.d_firstbad, W.d_fl);
+    };
+    if (int rc = W.settle(st, prim, fix, []() { return MSNV_OK; }, fl, R.n_redone)) return rc;
     if (fl) {
         R.ms_scan += tm.stop();
         R.n_redone += 1;                                          // (counted: the round goes through the careful kernel)
         pool.rewind(pool_from);
         return MSNV_OK;
     }
-    if (int rc = prim.exclusive(d_cnt, d_base, 0u, (size_t)n_sub + 1, rocprim::plus<uint32_t>())) return rc;
+    if (int rc = prim.exclusive(W.d_cnt, d_base, 0u, (size_t)n_sub + 1, rocprim::plus<uint32_t>())) return rc;
     HIP_TRY(hipMemcpyAsync(&R.NR, d_base + n_sub, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     // (a 32-bit count that wrapped would show as a total below the sub-segments' sum; 2^32 records need 150 GB of stream in one round -- refused by size)
@@ -2563,7 +2524,7 @@ static int scan_sub_walk(hipStream_t st, BufPool &pool, const uint64_t *n_bytes,
     auto *d_recoff = pool.take<unsigned long long>((uint64_t)NR + 1);
     auto *d_recsample = pool.take<uint16_t>((uint64_t)NR + 1);
     if (pool.rc) return pool.rc;
-    hipLaunchKernelGGL(msnv_scan_write, grid_for(n_sub, 256), dim3(256), 0, st, d_ss, (uint32_t)S, n_sub, sub_bytes, cap, d_cnt, d_base, d_delta, d_recoff, d_recsample, d_recbase);
+    hipLaunchKernelGGL(msnv_scan_write, grid_for(n_sub, 256), dim3(256), 0, st, W.d_ss, (uint32_t)S, n_sub, sub_bytes, W.cap, W.d_cnt, d_base, W.d_delta, d_recoff, d_recsample, d_recbase);
     HIP_TRY(hipGetLastError());
     R.rec_base.assign(S + 1, 0);
     HIP_TRY(hipMemcpyAsync(d_recbase + S, &R.NR, 4, hipMemcpyHostToDevice, st));
@@ -3113,51 +3074,38 @@ struct Round {
     // the stream and the depth stage on the second -- or TO_CAREFUL, with nothing of the round allocated yet.
     int front_quick() {
         if (int rc = begin_route(true)) return rc;
-        const uint32_t n_sub = (uint32_t)n_sub64;
-        auto *d_ss = pool.take<SubStream>(S);
-        auto *d_first = pool.take<unsigned long long>((uint64_t)n_sub + 1);
-        auto *d_stop = pool.take<unsigned long long>((uint64_t)n_sub + 1);
-        auto *d_stopmax = pool.take<unsigned long long>((uint64_t)n_sub + 1);
-        auto *d_cnt = pool.take<uint32_t>((uint64_t)n_sub + 1);
-        auto *d_delta = pool.take<uint16_t>((uint64_t)n_sub * cap2 + 8);
+        SubWalk W(S, (uint32_t)n_sub64, sub_bytes, cap2);
+        const uint32_t n_sub = W.n_sub;
+        W.take(pool);
         auto *d_slots = pool.take<Slot>((uint64_t)n_sub * cap2 + 1);
         auto *d_info = pool.take<SubInfo>((uint64_t)n_sub + 1);
         auto *d_subcnt = pool.take<SubCnt>((uint64_t)n_sub + 1);
         auto *d_subbase = pool.take<SubCnt>((uint64_t)n_sub + 1);
         auto *d_bflag = pool.take<uint8_t>((uint64_t)n_sub + 1);
-        auto *d_fl = pool.take<uint32_t>(4);
-        auto *d_firstbad = pool.take<uint32_t>(S);
         d_recbase = pool.take<uint32_t>(S + 1);
         d_send = pool.take<unsigned long long>(S);
         if (pool.rc) return pool.rc;
         fin_trace("  pack: quick buffers");
         tm.start();
-        HIP_TRY(hipMemcpyAsync(d_ss, ss.data(), S * sizeof(SubStream), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_send, SR.s_end.data(), S * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(d_fl, 0, 16, st));
-        HIP_TRY(hipMemsetAsync(d_firstbad, 0xff, S * 4, st));
-        hipLaunchKernelGGL(msnv_scan_sub2, grid_for(n_sub, 256), dim3(256), 0, st, raw, d_ss, (uint32_t)S, n_sub, sub_bytes, cap2, (int)NC, ctg, P, d_first, d_stop, d_cnt, d_delta, d_slots, d_info, d_fl);
+        if (int rc = W.upload(st, ss, SR.s_end, d_send)) return rc;
+        hipLaunchKernelGGL(msnv_scan_sub2, grid_for(n_sub, 256), dim3(256), 0, st, raw, W.d_ss, (uint32_t)S, n_sub, sub_bytes, cap2, (int)NC, ctg, P, W.d_first, W.d_stop, W.d_cnt, W.d_delta, d_slots, d_info, W.d_fl);
         HIP_TRY(hipGetLastError());
         size_t need = 0;                                          // both scans' storage before either is queued
-        if (int rc = prim.inclusive(d_stop, d_stopmax, (size_t)n_sub, U64Max(), &need)) return rc;
+        if (int rc = prim.inclusive(W.d_stop, W.d_stopmax, (size_t)n_sub, U64Max(), &need)) return rc;
         if (int rc = prim.exclusive(d_subcnt, d_subbase, SubCnt{}, (size_t)n_sub + 1, SubCntSum(), &need)) return rc;
         if (int rc = prim.room(need)) return rc;
-        for (int pass = 0;; ++pass) {
-            // seams checked, every stream's first sub-segment that guessed wrong walked again (until none is left: usually the first look), then
-            // the boundaries, and the scan whose last entry holds the round's totals -- all of it queued, ONE wait  (scan_sub_walk has this loop's twin)
-            if (int rc = prim.inclusive(d_stop, d_stopmax, (size_t)n_sub, U64Max())) return rc;
-            hipLaunchKernelGGL(msnv_scan_check, grid_for((uint64_t)n_sub + 1, 256), dim3(256), 0, st, d_ss, (uint32_t)S, n_sub, sub_bytes, d_first, d_stopmax, d_cnt, d_firstbad);
-            hipLaunchKernelGGL(msnv_scan_fix2, grid_for(S, 64), dim3(64), 0, st, raw, d_ss, (uint32_t)S, sub_bytes, cap2, ctg, P, d_first, d_stop, d_stopmax, d_cnt, d_delta, d_slots, d_info, d_firstbad, d_fl);
-            hipLaunchKernelGGL(msnv_sub_bounds, grid_for((uint64_t)n_sub + 1, 256), dim3(256), 0, st, d_ss, (uint32_t)S, n_sub, d_cnt, d_info, d_subcnt, d_bflag);
+        auto fix = [&]() {
+            hipLaunchKernelGGL(msnv_scan_fix2, grid_for(S, 64), dim3(64), 0, st, raw, W.d_ss, (uint32_t)S, sub_bytes, cap2, ctg, P, W.d_first, W.d_stop, W.d_stopmax, W.d_cnt, W.d_delta, d_slots, d_info, W.d_firstbad, W.d_fl);
+        };
+        // behind the repair: the boundaries, and the scan whose last entry holds the round's totals -- all of it queued before the pass's ONE wait
+        auto after = [&]() -> int {
+            hipLaunchKernelGGL(msnv_sub_bounds, grid_for((uint64_t)n_sub + 1, 256), dim3(256), 0, st, W.d_ss, (uint32_t)S, n_sub, W.d_cnt, d_info, d_subcnt, d_bflag);
             HIP_TRY(hipGetLastError());
             if (int rc = prim.exclusive(d_subcnt, d_subbase, SubCnt{}, (size_t)n_sub + 1, SubCntSum())) return rc;
-            HIP_TRY(hipMemcpyAsync(&fl_h, d_fl, 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(&tot_q, d_subbase + n_sub, sizeof(SubCnt), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            if (!(fl_h & 2u) || (fl_h & 5u) || pass >= 4096) break;
-            T.n_scan_redone += 1;                             // (counted: a repair pass)
-            HIP_TRY(hipMemsetAsync(d_fl, 0, 4, st));
-        }
+            return MSNV_OK;
+        };
+        if (int rc = W.settle(st, prim, fix, after, fl_h, T.n_scan_redone)) return rc;
         T.ms_scan += tm.stop();
         fin_trace("  pack: scan + measure, totals (wait)");
         const SubCnt &tot = tot_q;
@@ -3179,7 +3127,7 @@ struct Round {
         if (int rc = take_run_group_tables()) return rc;
         if (int rc = alloc_round_buffers()) return rc;
         TB = RdTables{d_recoff, d_recsample, d_recbase, d_rd, d_pre, d_ftile, d_flags, d_rg, d_runfirst, d_grpfirst};
-        if (n_sub) hipLaunchKernelGGL(msnv_scan_write2, grid_for(n_sub, 256), dim3(256), 0, st, d_ss, (uint32_t)S, n_sub, sub_bytes, cap2, d_cnt, d_subbase, d_bflag, d_delta, d_slots, d_info, TB, d_acc, d_misc,
+        if (n_sub) hipLaunchKernelGGL(msnv_scan_write2, grid_for(n_sub, 256), dim3(256), 0, st, W.d_ss, (uint32_t)S, n_sub, sub_bytes, cap2, W.d_cnt, d_subbase, d_bflag, W.d_delta, d_slots, d_info, TB, d_acc, d_misc,
                                       d_outl, span_out, T.overhang, P);
         HIP_TRY(hipGetLastError());
         totals_h = RecCnt{tot.pile, tot.npiece, tot.niv, tot.spill, tot.seqb};

@@ -361,19 +361,9 @@ def test_errors_carry_the_host_stage_codes():
         ctx.close()
 
 
-def test_record_scan_across_segment_seams():
-    """The record chain is walked piecewise with GUESSED entry points checked at every seam -- round 5: a lane per sub-segment, seams checked
-    on the device, wrong guesses walked again there (devpack.hip: msnv_scan_sub / msnv_scan_repair; MSNV_SCAN_SUB bytes); the careful form (msnv_scan_segments, MSNV_SCAN=segments,
-    MSNV_SCAN_SEG_KB) repairs wrong guesses on the host and takes over when the quick form meets a chain that breaks.  Tiny pieces put a seam into almost
-    every record (and records longer than a sub-segment next to it); a read name that holds plausible record headers makes guesses go wrong."""
-    syn, samples = synth_case(n_species=2, contig_len=6000, n_samples=4, mean_cov=9.0, snv_density=0.02, seed=25)
-    for sub in ("64", "100", "333", "4096"):
-        with _env(MSNV_SCAN_SUB=sub):
-            _same_dataset(syn.names, syn.lengths, syn.seqs, samples, check_oracle=(sub == "100"))
-    for kb in ("1", "2", "64"):
-        with _env(MSNV_SCAN_SEG_KB=kb, MSNV_SCAN="segments"):
-            _same_dataset(syn.names, syn.lengths, syn.seqs, samples, check_oracle=(kb == "1"))
-    # a decoy: inside a long read name, the bytes of three consecutive plausible record headers
+def _decoy_stream():
+    """40 records of 50 bases on a 6000-base contig; every third carries, in an aux field, the bytes of plausible record headers 40 bytes
+    apart: a walk that enters there on a guess ends cleanly at the wrong place, and only the seam check can tell.  Returns (ref, stream)."""
     import struct
     ref = "ACGT" * 1500
 
@@ -383,21 +373,42 @@ def test_record_scan_across_segment_seams():
     recs = []
     for k in range(40):
         recs.append(bt.make_record(0, 10 + 20 * k, "50M", ref[10 + 20 * k:60 + 20 * k], name="r%d" % k, aux=b"ZZZ" + decoy[:200] if k % 3 == 0 else b""))
-    stream = bt.records(*recs)
+    return ref, bt.records(*recs)
+
+
+def test_record_scan_across_segment_seams():
+    """The record chain is walked piecewise with GUESSED entry points checked at every seam -- round 5: a lane per sub-segment, seams checked
+    on the device, wrong guesses walked again there (devpack.hip: msnv_scan_sub2 / msnv_scan_fix2, and msnv_scan_sub / msnv_scan_fix under MSNV_FRONT=careful; MSNV_SCAN_SUB bytes); the careful form (msnv_scan_segments, MSNV_SCAN=segments,
+    MSNV_SCAN_SEG_KB) repairs wrong guesses on the host and takes over when the quick form meets a chain that breaks.  Tiny pieces put a seam into almost
+    every record (and records longer than a sub-segment next to it); a read name that holds plausible record headers makes guesses go wrong."""
+    syn, samples = synth_case(n_species=2, contig_len=6000, n_samples=4, mean_cov=9.0, snv_density=0.02, seed=25)
+    for sub in ("64", "100", "333", "4096"):
+        with _env(MSNV_SCAN_SUB=sub):
+            _same_dataset(syn.names, syn.lengths, syn.seqs, samples, check_oracle=(sub == "100"))
+    for sub in ("64", "333"):                                        # the careful front's walk (msnv_scan_sub) on the same pieces
+        with _env(MSNV_FRONT="careful", MSNV_SCAN_SUB=sub):
+            _same_dataset(syn.names, syn.lengths, syn.seqs, samples, check_oracle=False)
+    for kb in ("1", "2", "64"):
+        with _env(MSNV_SCAN_SEG_KB=kb, MSNV_SCAN="segments"):
+            _same_dataset(syn.names, syn.lengths, syn.seqs, samples, check_oracle=(kb == "1"))
+    # a decoy: inside a long aux field, the bytes of consecutive plausible record headers
+    ref, stream = _decoy_stream()
     ctx = core.Context(0)
     try:
-        for env in (dict(MSNV_SCAN_SEG_KB="1", MSNV_SCAN="segments"), dict(MSNV_SCAN_SEG_KB="256", MSNV_SCAN="segments"), dict(MSNV_SCAN_SUB="64"), dict(MSNV_SCAN_SUB="128"), dict(MSNV_SCAN_SUB="4096")):
+        for env in (dict(MSNV_SCAN_SEG_KB="1", MSNV_SCAN="segments"), dict(MSNV_SCAN_SEG_KB="256", MSNV_SCAN="segments"), dict(MSNV_SCAN_SUB="64"), dict(MSNV_SCAN_SUB="128"), dict(MSNV_SCAN_SUB="4096"),
+                    dict(MSNV_FRONT="careful", MSNV_SCAN_SUB="64"), dict(MSNV_FRONT="careful", MSNV_SCAN_SUB="128")):
             with _env(MSNV_PACK="device", **env):
                 ds = core.Dataset(ctx, ["c"], [6000], [ref])
                 ds.add_sample_records(stream)
                 ds.finalize()
                 assert ds.info()["n_reads_pileup"] == 40
                 if env.get("MSNV_SCAN_SUB") in ("64", "128"):
-                    # the quick form fell for the decoy and walked those sub-segments again from the true entry (msnv_scan_repair), on the device
+                    # the walk fell for the decoy and went over those sub-segments again from the true entry (msnv_scan_fix2; msnv_scan_fix under the careful front), on the device
                     assert ds.pack_stats()["scan_segments_redone"] >= 1
                 ds.close()
-        for sub in ("64", "128"):                                    # ... and what it builds is the host pack's dataset, byte for byte
-            with _env(MSNV_SCAN_SUB=sub):
+        for env in (dict(MSNV_SCAN_SUB="64"), dict(MSNV_SCAN_SUB="128"),      # ... and what it builds is the host pack's dataset, byte for byte
+                    dict(MSNV_FRONT="careful", MSNV_SCAN_SUB="64"), dict(MSNV_FRONT="careful", MSNV_SCAN_SUB="128")):
+            with _env(**env):
                 _same_dataset(["c"], [6000], [ref], [stream])
     finally:
         ctx.close()
@@ -428,14 +439,18 @@ def test_aux_fields_and_cigars_in_the_cg_field():
 def test_records_dealt_on_the_device_equal_the_host_partition():
     """msnv_records_deal_device (the N-rank feed's dealing step as kernels) against msnv_records_partition / msnv_records_contig_bases on host
     threads: the bytes of every (stream, part), their sizes, qaCompute's statistics and the aligned bases per contig -- paired reads, unmapped
-    records, aux tags, SEQ `*`, contigs owned by nobody, empty streams, one-kilobyte scan segments, a gap in front of every part."""
+    records, aux tags, SEQ `*`, contigs owned by nobody, empty streams, a stream whose aux fields hold plausible record headers (walked in
+    64-byte sub-segments: the dealer's msnv_scan_fix repairs the wrong guesses -- the dealer reports no count of repairs, so a silent fall-back
+    to the segment scan would pass here too; test_record_scan_across_segment_seams asserts the repair on the same walk under MSNV_FRONT=careful),
+    one-kilobyte scan segments, a gap in front of every part."""
     hip = C.CDLL("libamdhip64.so")
     syn, samples = synth_case(n_species=5, contig_len=6000, n_samples=9, mean_cov=9.0, frac_paired=0.4, frac_aux=0.4, frac_noseq=0.05, frac_absent=0.3, seed=41)
     unm = bt.records(bt.make_record(-1, -1, "*", "ACGT", name="u1", flag=4), bt.make_record(-1, -1, "*", "ACGTAC", name="u2", flag=4))
     samples = [np.concatenate([s, np.frombuffer(unm.tobytes(), np.uint8)]) if i % 3 == 0 else s for i, s in enumerate(samples)] + [np.zeros(0, np.uint8)]
+    samples.append(np.frombuffer(_decoy_stream()[1].tobytes(), np.uint8))
     nc = len(syn.names)
     ctx = core.Context(0)
-    for n_parts, seg_kb, gap in ((1, None, 0), (3, "1", 72), (8, None, 16)):
+    for n_parts, seg_kb, gap, scan_sub in ((1, None, 0, None), (3, "1", 72, "64"), (8, None, 16, None)):
         owner = np.array([(c * 7 + 1) % n_parts if c % 4 != 3 else -1 for c in range(nc)], dtype=np.int32)
         want_parts, want_stats, want_cb = [], [], np.zeros(nc, np.uint64)
         for s in samples:
@@ -446,7 +461,7 @@ def test_records_dealt_on_the_device_equal_the_host_partition():
         assert hip.hipMalloc(C.byref(p), C.c_size_t(max(16, cap))) == 0
         assert hip.hipMemset(p, 0xEE, C.c_size_t(max(16, cap))) == 0
         cb = np.zeros(nc, np.uint64)
-        with _env(MSNV_SCAN_SEG_KB=seg_kb):
+        with _env(MSNV_SCAN_SEG_KB=seg_kb, MSNV_SCAN_SUB=scan_sub):
             pb, stats = core.deal_records_device(ctx, samples, owner, n_parts, p.value, cap, gap=gap, contig_bases=cb)
         got = np.zeros(max(16, cap), np.uint8)
         assert hip.hipMemcpy(C.c_void_p(got.ctypes.data), p, C.c_size_t(max(16, cap)), 2) == 0
