@@ -816,7 +816,7 @@ struct WalkMeasure {
                 if (m.st & ST_ORDER) {                                             // coordinate order inside the walk (across sub-segments: msnv_sub_bounds)
                     if (have_prev) {
                         const int32_t tj = (int32_t)(prev_key >> 32), pj = (int32_t)(uint32_t)prev_key, ti = (int32_t)(m.key >> 32), pi = (int32_t)(uint32_t)m.key;
-                        if ((ti < tj || (ti == tj && pi < pj)) && !err) err = ERR_UNSORTED;
+                        if ((ti < tj || (ti == tj && pi < pj)) && (!err || err > ERR_UNSORTED)) err = ERR_UNSORTED;      // (pack.cpp looks at the order before CIGAR against SEQ: the lower kind, as at a seam and in msnv_measure_reads)
                     }
                 }
                 if (m.flags & RF_MAPPED) {
@@ -3109,7 +3109,8 @@ struct Round {
         T.ms_scan += tm.stop();
         fin_trace("  pack: scan + measure, totals (wait)");
         const SubCnt &tot = tot_q;
-        if (fl_h || tot.odd) { T.n_scan_redone += 1; return TO_CAREFUL; }      // a chain that breaks, a sub-segment the slots cannot hold: the careful route takes (and words) it
+        if (fl_h) { T.n_scan_redone += 1; return TO_CAREFUL; }       // a chain that breaks, a sub-segment with more records than slots: the careful route takes (and words) it
+        if (tot.odd) { T.n_quick_redone += 1; return TO_CAREFUL; }   // the walk stands, but a place does not fit its slot field or two contigs overhang in one sub-segment: a round the quick route hands back
         if (SR.raw_bytes / 36 > 0xfffffff0ull) return fail(MSNV_EDOMAIN, "more than 2^32 records in one round of the device pack");
         // paired reads: the candidates of the overlapping-mate tweak are grouped, and the samples that need the host pre-pass known, before
         // anything is emitted -- the careful route does all of that; the quick route takes the rounds without candidates
@@ -3526,7 +3527,12 @@ struct Round {
         T.round_bufs.push_back(held.round_buf); held.round_buf = nullptr;
         held.keep_buf = nullptr;                                       // (the dataset's from here on)
         T.rounds.push_back(keep);
-        if (in_order) if (int rc = devpack_sync_pending(ds)) return rc;      // (the general tile-order route of tile_pairs() waits for its sort anyway)
+        if (in_order) {                                                // (the general tile-order route of tile_pairs() waits for its sort anyway)
+            if (int rc = devpack_sync_pending(ds)) return rc;
+            // (the round's samples are not the dataset's yet: publish() takes the mismatch sample from `acc`, so the emit kernels' counts go there)
+            const DpAcc *a = static_cast<const DpAcc *>(T.pin);
+            for (size_t s = 0; s < S; ++s) { acc[s].mm_bases = a[s].mm_bases; acc[s].mm = a[s].mm; }
+        }
         fin_trace("  pack: emit launched, results in");
         return MSNV_OK;
     }

@@ -65,13 +65,13 @@ inline bool pack_on_host() { return first("MSNV_PACK") == 'h'; }
 inline uint64_t pack_round_bytes() { return (uint64_t)std::max<long long>(1, i64_or("MSNV_PACK_ROUND_MB", 6144)) << 20; }
 // MSNV_PACK_COPY (present): record streams that are already in HBM are copied into the round's buffer, not packed in place.  Per call.  Profiling only.
 inline bool pack_copy() { return present("MSNV_PACK_COPY"); }
-// MSNV_SCAN=segments: record boundaries by the careful kernel only, no sub-segment walk.  Per call (tests/test_gpu_devpack.py, fuzz_parity.py).
+// MSNV_SCAN=segments: record boundaries by the careful kernel only, no sub-segment walk.  Per call (tests/test_gpu_devpack.py, test_gpu_record_walk.py, fuzz_parity.py).
 inline bool scan_segments() { return first("MSNV_SCAN") == 's'; }
-// MSNV_FRONT=careful: a round takes the stage-by-stage route, not the one-walk route.  Per call (tests/test_gpu_devpack.py).
+// MSNV_FRONT=careful: a round takes the stage-by-stage route, not the one-walk route.  Per call (tests/test_gpu_devpack.py, test_gpu_record_walk.py).
 inline bool front_careful() { return first("MSNV_FRONT") == 'c'; }
 // MSNV_SCAN_SUB (64 .. 32768): bytes of a sub-segment of the boundary walk.  Its default belongs to the route that asks: 4096 in
 // scan_sub_walk (the deal, the careful route), 6144 in a round's one-walk route (2.36 -> 2.04 ms of scan + measure on the benchmark shape
-// against 4 KB, 8 KB the same).  Per call (tests/test_gpu_devpack.py shrinks it).
+// against 4 KB, 8 KB the same).  Per call (tests/test_gpu_devpack.py and test_gpu_record_walk.py set it).
 constexpr long long SCAN_SUB_STREAMS = 4096, SCAN_SUB_ROUND = 6144;
 inline uint32_t scan_sub_bytes(long long route_default) { return (uint32_t)std::min<long long>(32768, std::max<long long>(64, i64_or("MSNV_SCAN_SUB", route_default))); }
 // MSNV_SCAN_SEG_KB (256, at least 1): kilobytes of a segment of the careful boundary scan.  Per call (tests/test_gpu_devpack.py shrinks it).
