@@ -626,20 +626,7 @@ extern "C" int msnv_pileup_run(msnv_dataset *ds, msnv_run_stats *stats) {
     int rc = dev_run_pipeline(d, ds->params, ds->ctx->stream, &st, &c);
     for (int attempt = 0; rc == MSNV_ECAPACITY && attempt < 3; ++attempt) {      // (sparse buffers; whole-tile items sent back to the unfused path)
         // grow the sparse buffers to what the failed pass asked for and run again
-        auto grow = [&](void **p, uint32_t &cap, uint32_t need, size_t elem) -> int {
-            if (need <= cap) return MSNV_OK;
-            dev_free(*p); *p = nullptr;
-            cap = (uint32_t)std::min<uint64_t>(0x7fffffffull, (uint64_t)need + need / 4 + 1024);
-            return dev_alloc(p, (uint64_t)cap * elem, &d.device_bytes);
-        };
-        if (int r2 = grow((void **)&d.events, d.cap_events, c.n_events, sizeof(Pair32))) return r2;
-        if (int r2 = grow((void **)&d.overflow, d.cap_overflow, c.n_overflow, sizeof(Pair32))) return r2;
-        const uint32_t old_cap_sites = d.cap_sites;
-        if (int r2 = grow((void **)&d.sites, d.cap_sites, c.n_sites, sizeof(SiteRec))) return r2;
-        if (d.cap_sites != old_cap_sites) {                 // the list of sites msnv_decide_sites looks at is sized like the sites
-            dev_free(d.unc_sites); d.unc_sites = nullptr;
-            if (int r2 = dev_alloc((void **)&d.unc_sites, (uint64_t)d.cap_sites * sizeof(uint32_t), &d.device_bytes)) return r2;
-        }
+        if (int r2 = passbufs_grow(d, d, c)) return r2;
         clear_error();
         rc = dev_run_pipeline(d, ds->params, ds->ctx->stream, &st, &c);
     }

@@ -44,7 +44,48 @@ int  dev_ann_upload(DeviceCols &d, const AnnHost &h);
 // Annotates the d.last_sites device site records; err_gpos[k] = UINT32_MAX when error kind k did not occur.
 int  dev_annotate(DeviceCols &d, uint32_t n_sites, uint32_t drop_gpos, void *stream, double *ms, uint32_t err_gpos[2]);
 
-struct DeviceCols {
+// One descriptor per active tile for the gate kernels: everything they look up about their tile in one 64-byte load (pack.cpp builds them).
+// staged: a whole-tile work item leaves the tile's candidates in a record list (then row0 = index of that list); pair_lo / n_plane_pairs:
+// the tile's pairs that write allele planes
+struct GateTile { uint32_t tile, slot_lo, slot_16, slot_w, slot_hi, vbeg, vend, n_slots; uint64_t row0; uint32_t tot_mode, staged, pair_lo, n_plane_pairs, pad0, pad1; };
+static_assert(sizeof(GateTile) == 64, "gate tile descriptor");
+
+// What one pass writes and a pass in flight beside it must not share.  A dataset holds two of these (DeviceCols itself and DeviceCols::alt):
+// msnv_pileup_run_many alternates overlapped passes between them.  Allocated, grown, freed and swapped as a whole (kernels.hip: passbufs_*).
+struct PassBufs {
+    uint32_t *tot = nullptr;         // [4][n_tiles*TILE]: mismatching A, C, G, T summed over samples
+    uint8_t  *part = nullptr;        // coverage partial row of every work item (tile-major; u16 per position for narrow items, u32 for wide)
+    uint8_t  *spill = nullptr;       // [n_pairs][TILE] per-sample coverage, saturating at 255
+    uint8_t  *aspill = nullptr;      // [n_pairs][4][TILE] per-sample mismatching A, C, G, T counts (allele planes: noisy reads, pack.cpp); else NULL
+    Pair32   *events = nullptr;      // {gpos, sample<<18 | allele<<16 | count}
+    Pair32   *overflow = nullptr;    // {gpos, sample<<16 | cov}
+    uint32_t *counters = nullptr;    // two blocks of CNT_WORDS ([0] events [1] overflow [2] sites [4] pop lines [5] indiv lines, then the event
+                                     // sub-list counters): consecutive passes alternate, the gate kernel of a pass zeroes the other block
+    uint32_t  cnt_parity = 0;        // block the NEXT pass uses
+    uint32_t *ind4 = nullptr;        // 4 bits per position: some sample holds >= calling_threshold reads of mismatching A / C / G / T
+    uint32_t *unc_bits = nullptr;    // 1 bit per position: a sample split into several pairs holds a mismatching allele (follows ind4 in its allocation)
+    uint32_t *tile_dirty = nullptr;  // per work item (by the slot of its coverage row), 1 bit per 64 positions of the tile: the item added to the allele totals there
+                                     // (set by the pileup kernels, consumed and cleared by the gate)
+    uint32_t *unc_sites = nullptr;   // [cap_sites]: sites whose call depends on a split / merged sample's summed counts (msnv_decide_sites)
+    unsigned long long *site_row = nullptr;   // per 64 positions: first cell of the first site in them (gate kernel; what an event finds its cell with)
+    unsigned long long *site_bits = nullptr;  // 1 bit per position: is a site (written by the gate kernel for every tile)
+    uint32_t *site_rank = nullptr;   // per 64 positions: index of their first site (tiles with sites only)
+    SiteRec  *sites = nullptr;
+    uint32_t *tile_site_base = nullptr, *tile_site_cnt = nullptr;
+    unsigned long long *tile_cell_base = nullptr;   // per tile and pass: first cell of its sites' rows (gate kernel)
+    uint16_t *ncol = nullptr;        // [4][cap_cells]: mismatching A, C, G, T counts per (site, slot), one column per allele
+    uint16_t *cov_col = nullptr;     // [cap_cells]: per-sample coverage.  Structure of arrays: a site's row of cells is contiguous in every column,
+                                     // so rows can be zeroed and written 16 bytes at a time; the host zips the five columns into msnv_site_sample records
+    uint8_t  *site_flags = nullptr;  // pop_mask | ind_mask << 4
+    uint8_t  *site_elig = nullptr;   // alleles still open to the individual rule when the gate kernel has decided what it can (merged gather)
+    TileStage *tile_stage = nullptr; // per active tile (index of its GateTile): candidate records of whole-tile work items; behind them, in the same
+                                     // allocation, the list of tiles whose candidates did not fit (kernels.hip: stage_ovf_list)
+    uint32_t  cap_events = 0, cap_overflow = 0, cap_sites = 0;
+    uint64_t  cap_out_sites = 0, cap_cells = 0;
+    uint64_t  bytes = 0;             // what the set's buffers hold of DeviceCols::device_bytes
+};
+
+struct DeviceCols : PassBufs {
     // ---- inputs (uploaded once by finalize)
     ReadHdr  *hdr = nullptr;         // 16-byte piece headers (wide kernel)
     PieceHdr *hdr8 = nullptr;        // 8-byte tile-local piece headers (narrow32 kernel, MSNV_LAYOUT=pieces; MSNV_HDR4=0 builds)
@@ -68,33 +109,17 @@ struct DeviceCols {
     uint32_t  n_tiles = 0, n_pairs = 0, n_work = 0, n_work_narrow = 0, n_samples = 0;   // work[0..n_work_narrow) = narrow items
     uint64_t  n_reads = 0, n_seq_bytes = 0, n_chunks = 0, n_hdr8m = 0, n_blk = 0;
     // ---- intermediates
-    uint32_t *tot = nullptr;         // [4][n_tiles*TILE]: mismatching A, C, G, T summed over samples
     uint32_t *active_tiles = nullptr; // tiles that hold work items (gate / gather run over these only)
     uint32_t  n_active_tiles = 0;
-    uint8_t  *part = nullptr;        // coverage partial row of every work item (tile-major; u16 per position for narrow items, u32 for wide)
     uint64_t *slot_off = nullptr;    // byte offset of every row; n_work + 1
     uint32_t *tile_slot_u16 = nullptr;    // first u16 row of every tile (u8 rows come first)
     uint32_t *tile_slot_wide = nullptr;   // first wide (u32) row of every tile
     uint64_t  part_bytes = 0;
     uint32_t *tile_slot_start = nullptr;   // n_tiles + 1
-    uint8_t  *spill = nullptr;       // [n_pairs][TILE] per-sample coverage, saturating at 255
-    uint8_t  *aspill = nullptr;      // [n_pairs][4][TILE] per-sample mismatching A, C, G, T counts (allele planes: noisy reads, pack.cpp); else NULL
     bool      allele_planes = false;
-    Pair32   *events = nullptr;      // {gpos, sample<<18 | allele<<16 | count}
-    Pair32   *overflow = nullptr;    // {gpos, sample<<16 | cov}
-    uint32_t *counters = nullptr;    // two blocks of CNT_WORDS ([0] events [1] overflow [2] sites [4] pop lines [5] indiv lines, then the event
-                                     // sub-list counters): consecutive passes alternate, the gate kernel of a pass zeroes the other block
-    uint32_t  cnt_parity = 0;        // block the NEXT pass uses
-    uint32_t *ind4 = nullptr;        // 4 bits per position: some sample holds >= calling_threshold reads of mismatching A / C / G / T
-    uint32_t *unc_bits = nullptr;    // 1 bit per position: a sample split into several pairs holds a mismatching allele (follows ind4 in its allocation)
-    uint32_t *tile_dirty = nullptr;  // per work item (by the slot of its coverage row), 1 bit per 64 positions of the tile: the item added to the allele totals there
-                                     // (set by the pileup kernels, consumed and cleared by the gate)
-    uint32_t *unc_sites = nullptr;   // [cap_sites]: sites whose call depends on a split / merged sample's summed counts (msnv_decide_sites)
-    struct GateTileH { uint32_t tile, slot_lo, slot_16, slot_w, slot_hi, vbeg, vend, n_slots; uint64_t row0; uint32_t tot_mode, staged, pair_lo, n_plane_pairs, pad0, pad1; } *gate_tiles = nullptr;   // per active tile (kernels.hip: GateTile)
-    unsigned long long *site_row = nullptr;   // per 64 positions: first cell of the first site in them (gate kernel; what an event finds its cell with)
-    GateTileH *gate_tiles_dense = nullptr, *gate_tiles_staged = nullptr;   // gate_tiles without / only the tiles of whole-tile work items (staged: row0 = index of the record list)
+    GateTile *gate_tiles = nullptr;  // per active tile
+    GateTile *gate_tiles_dense = nullptr, *gate_tiles_staged = nullptr;   // gate_tiles without / only the tiles of whole-tile work items (staged: row0 = index of the record list)
     uint32_t *gather_tiles = nullptr; uint32_t n_gather_tiles = 0;   // active tiles that hold pairs outside merged groups (spill gather)
-    TileStage *tile_stage = nullptr;   // per active tile (index of its GateTile): candidate records of whole-tile work items
     uint32_t *tile_stage_idx = nullptr;   // per tile: that index
     uint32_t  max_group_pairs = 0;   // most pairs a merged group holds (<= GMW_PAIRS: the merged gather runs a wavefront per group, kernels.hip)
     uint32_t  n_groups_solo = 0;     // the last n_groups_solo merged groups are whole-tile groups of ONE pair (no gather needed when the pass is fused)
@@ -107,20 +132,8 @@ struct DeviceCols {
     bool      use_dirty = false;     // sparse cohort (few work items per tile): the gate kernel consults tile_dirty before it reads the allele totals
     uint32_t  gather_split = 4;      // workgroups per tile in the spill gather (fewer for sparse cohorts: a pair or two per tile)
     bool      any_split = false;     // some (sample, tile) run was dealt into several pairs: the calling rule then needs the summed per-sample records
-    unsigned long long *site_bits = nullptr;   // 1 bit per position: is a site (written by the gate kernel for every tile)
-    uint32_t *site_rank = nullptr;   // per 64 positions: index of their first site (tiles with sites only)
-    uint32_t  cap_events = 0, cap_overflow = 0, cap_sites = 0;
-    SiteRec  *sites = nullptr;
-    uint32_t *tile_site_base = nullptr, *tile_site_cnt = nullptr;
     uint32_t *tile_nslots = nullptr; // per tile: samples that have reads in it = cells per site of that tile (kernels.hip: CellMap) | NSLOTS_SPLIT
-    unsigned long long *tile_cell_base = nullptr;   // per tile and pass: first cell of its sites' rows (gate kernel)
-    uint64_t  cap_cells = 0, last_cells = 0;
-    uint16_t *ncol = nullptr;        // [4][cap_cells]: mismatching A, C, G, T counts per (site, slot), one column per allele
-    uint16_t *cov_col = nullptr;     // [cap_cells]: per-sample coverage.  Structure of arrays: a site's row of cells is contiguous in every column,
-                                     // so rows can be zeroed and written 16 bytes at a time; the host zips the five columns into msnv_site_sample records
-    uint8_t  *site_flags = nullptr;  // pop_mask | ind_mask << 4
-    uint8_t  *site_elig = nullptr;   // alleles still open to the individual rule when the gate kernel has decided what it can (merged gather)
-    uint64_t  cap_out_sites = 0, last_sites = 0;
+    uint64_t  last_cells = 0, last_sites = 0;
     // ---- genome coverage (qaCompute path)
     Pair32   *cov_iv = nullptr;          // {gbeg, gend}: +1 at gbeg, -1 at gend (index space of qaCompute.cpp:530-552)
     uint64_t *s_cov_base = nullptr;      // per sample
@@ -139,15 +152,9 @@ struct DeviceCols {
     // into one of them are not freed by themselves (dev_free_all)
     std::vector<std::pair<void *, uint64_t>> blocks;
     AnnDev    ann;
-    // second set of per-pass intermediates + second stream: msnv_pileup_run_many alternates passes between the two sets so
+    // second set of per-pass buffers + second stream: msnv_pileup_run_many alternates passes between the two sets so
     // that the small tail kernels of pass i overlap with the pileup kernel of pass i+1 (allocated on first use)
-    struct AltBufs {
-        uint32_t *tot = nullptr; uint8_t *part = nullptr; uint8_t *spill = nullptr, *aspill = nullptr; Pair32 *events = nullptr, *overflow = nullptr;
-        TileStage *tile_stage = nullptr;
-        uint32_t *counters = nullptr; SiteRec *sites = nullptr; uint32_t *tile_site_base = nullptr, *tile_site_cnt = nullptr; unsigned long long *tile_cell_base = nullptr;
-        uint16_t *ncol = nullptr; uint16_t *cov_col = nullptr; uint8_t *site_flags = nullptr, *site_elig = nullptr; uint32_t *ind4 = nullptr, *unc_bits = nullptr, *tile_dirty = nullptr, *unc_sites = nullptr; unsigned long long *site_row = nullptr; unsigned long long *site_bits = nullptr; uint32_t *site_rank = nullptr;
-        uint32_t cap_events = 0, cap_overflow = 0, cap_sites = 0, cnt_parity = 0; uint64_t cap_out_sites = 0, cap_cells = 0;
-    } alt;
+    PassBufs  alt;
     void     *stream2 = nullptr;
     std::vector<void *> event_pool;          // hipEvent_t of msnv_pileup_run_many
     uint32_t *pinned_cnt = nullptr; size_t pinned_cnt_cap = 0;   // pinned host blocks for the per-pass counters
@@ -208,6 +215,12 @@ int  dev_run_coverage_extras(DeviceCols &d, CovxJob &job, void *stream);
 int  dev_run_pipeline(DeviceCols &d, const msnv_params &p, void *stream, msnv_run_stats *stats, RunCounts *counts);
 int  dev_run_pipeline_many(DeviceCols &d, const msnv_params &p, void *stream, int n, bool overlap, msnv_run_stats *stats, RunCounts *counts);
 void dev_free_all(DeviceCols &d);
+// A set of per-pass buffers (kernels.hip).  alloc: every buffer of an EMPTY set from the dataset's shape (d's counts; part_bytes, n_active_tiles,
+// n_fused_tiles, allele_planes) and the capacities `caps`, the fills queued on `stream`; grow: events, overflow and sites (with unc_sites) to
+// what a failed pass asked for; free: everything, and the set's bytes leave d.device_bytes with it.
+int  passbufs_alloc(DeviceCols &d, PassBufs &b, const PassBufs &caps, void *stream);
+int  passbufs_grow(DeviceCols &d, PassBufs &b, const RunCounts &need);
+void passbufs_free(DeviceCols &d, PassBufs &b);
 int  dev_reserve_passes(DeviceCols &d, int n);
 // one tiny launch per translation unit with kernels: its code object is loaded when the context is made, not inside the first stage that needs it
 void warm_devpack(void *stream), warm_kernels(void *stream), warm_textcall(void *stream), warm_annotate(void *stream), warm_mptext(void *stream);

@@ -1393,8 +1393,6 @@ __device__ __forceinline__ void zero_cells(uint16_t *ncol, uint16_t *cov_col, co
     zero_span<NT>(reinterpret_cast<uint8_t *>(cov_col + first), n * sizeof(uint16_t), tid);      // samples without reads at a position keep coverage 0
 }
 
-struct GateTile { uint32_t tile, slot_lo, slot_16, slot_w, slot_hi, vbeg, vend, n_slots; uint64_t row0; uint32_t tot_mode, staged, pair_lo, n_plane_pairs, pad0, pad1; };   // 64 B (pack.cpp); staged: a whole-tile work item leaves the tile's candidates in a record list; pair_lo / n_plane_pairs: the tile's pairs that write allele planes
-
 struct GateArgs {
     uint32_t *tot; const uint8_t *part; const uint64_t *slot_off; const uint32_t *tile_slot_start, *tile_slot_u16, *tile_slot_wide; uint64_t npos;
     const uint32_t *tile_vbeg, *tile_vend; int min_cov, min_snvs; double min_frac;
@@ -2919,48 +2917,125 @@ int dev_stream_wait(void *stream) { HIP_TRY(hipStreamSynchronize((hipStream_t)st
 int dev_stream_create(void **stream) { hipStream_t s; HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); *stream = s; return MSNV_OK; }
 void dev_stream_destroy(void *stream) { if (stream) (void)hipStreamDestroy((hipStream_t)stream); }
 
+// (a pointer into one of the dataset's shared allocations is not freed by itself: DeviceCols::blocks)
+static bool dev_in_block(const DeviceCols &d, const void *p) {
+    for (const auto &b : d.blocks) if ((const char *)p >= (const char *)b.first && (const char *)p < (const char *)b.first + b.second) return true;
+    return false;
+}
+
+// ---- a set of per-pass buffers (device.h: PassBufs): the four functions below are the only place that knows its sizes and its members
+// A set's bytes are part of the dataset's count for as long as the set holds them: out while one of the functions remakes buffers, back in when it leaves.
+struct SetBytes { DeviceCols &d; PassBufs &b; SetBytes(DeviceCols &d_, PassBufs &b_) : d(d_), b(b_) { d.device_bytes -= b.bytes; } ~SetBytes() { d.device_bytes += b.bytes; } };
+// one buffer of `elems` elements (and `tail` bytes); a buffer that is there already goes back first, with the `old_elems` it held
+template <typename T> static int set_buf(PassBufs &b, T *&p, uint64_t old_elems, uint64_t elems, uint64_t tail = 0) {
+    if (p) { dev_free(p); p = nullptr; b.bytes -= old_elems * sizeof(T) + tail; }
+    return dev_alloc((void **)&p, elems * sizeof(T) + tail, &b.bytes);
+}
+// the output columns at exactly these capacities (0: none yet -- the first pass sizes them, ensure_out)
+static int set_out_caps(PassBufs &b, uint64_t cap_sites, uint64_t cap_cells) {
+    if (cap_sites != b.cap_out_sites) {
+        if (int rc = set_buf(b, b.site_flags, b.cap_out_sites, cap_sites, 4)) return rc;      // (+4: 32-bit atomics on the byte's aligned word)
+        if (int rc = set_buf(b, b.site_elig, b.cap_out_sites, cap_sites, 4)) return rc;
+        b.cap_out_sites = cap_sites;
+    }
+    if (cap_cells != b.cap_cells) {
+        if (int rc = set_buf(b, b.ncol, 4 * b.cap_cells, 4 * cap_cells, 16)) return rc;
+        if (int rc = set_buf(b, b.cov_col, b.cap_cells, cap_cells, 16)) return rc;
+        b.cap_cells = cap_cells;
+    }
+    return MSNV_OK;
+}
+int passbufs_alloc(DeviceCols &d, PassBufs &b, const PassBufs &caps, void *stream) {
+    SetBytes count(d, b);
+    const uint64_t npos = (uint64_t)d.n_tiles * TILE, nt1 = (uint64_t)d.n_tiles + 1, per64 = npos / 64 + 1;
+    // what starts zeroed stays zeroed between passes: the gate kernel clears the allele totals, the individual-rule bits and the dirty
+    // words it consumes, and the counter blocks alternate (the gate kernel of a pass zeroes the next one), so no pass begins with a memset
+    auto zeroed = [&](auto *&p, uint64_t elems) -> int {
+        if (int rc = set_buf(b, p, 0, elems)) return rc;
+        return dev_memset_async(p, 0, elems * sizeof(*p), stream);
+    };
+    if (int rc = zeroed(b.tot, std::max<uint64_t>(1, 4 * npos))) return rc;
+    if (int rc = set_buf(b, b.part, 0, d.part_bytes)) return rc;
+    if (int rc = set_buf(b, b.spill, 0, std::max<uint64_t>(1, d.n_pairs) * TILE)) return rc;
+    if (d.allele_planes) if (int rc = zeroed(b.aspill, (uint64_t)d.n_pairs * 4 * TILE)) return rc;      // (rows of merged pairs are never written and never read)
+    b.cap_events = caps.cap_events; b.cap_overflow = caps.cap_overflow; b.cap_sites = caps.cap_sites;
+    if (int rc = set_buf(b, b.events, 0, b.cap_events)) return rc;
+    if (int rc = set_buf(b, b.overflow, 0, b.cap_overflow)) return rc;
+    if (int rc = set_buf(b, b.sites, 0, b.cap_sites)) return rc;
+    if (int rc = set_buf(b, b.unc_sites, 0, b.cap_sites)) return rc;      // the list of sites msnv_decide_sites looks at is sized like the sites
+    if (int rc = set_buf(b, b.site_row, 0, per64)) return rc;             // per 64 positions (CellMap::block_row)
+    if (int rc = zeroed(b.tile_dirty, (uint64_t)d.n_work + 1)) return rc;      // one word per work item (by slot)
+    if (int rc = zeroed(b.counters, 2 * CNT_WORDS)) return rc;
+    b.cnt_parity = 0;
+    if (int rc = zeroed(b.ind4, npos / 8 + npos / 32 + 2)) return rc;
+    b.unc_bits = b.ind4 + npos / 8 + 1;
+    if (int rc = set_buf(b, b.site_bits, 0, per64)) return rc;
+    if (int rc = set_buf(b, b.site_rank, 0, per64)) return rc;
+    if (int rc = zeroed(b.tile_site_base, nt1)) return rc;
+    if (int rc = zeroed(b.tile_site_cnt, nt1)) return rc;
+    if (int rc = zeroed(b.tile_cell_base, nt1)) return rc;
+    // whole-tile work items write their candidate records per active tile (+ one index per whole-tile item behind the lists: the tiles
+    // whose candidates do not fit a list -- stage_ovf_list)
+    if (d.n_fused_tiles) {
+        if (int rc = dev_alloc((void **)&b.tile_stage, (uint64_t)d.n_active_tiles * sizeof(TileStage) + (uint64_t)d.n_fused_tiles * sizeof(uint32_t), &b.bytes)) return rc;
+        if (int rc = dev_memset_async(b.tile_stage, 0, (uint64_t)d.n_active_tiles * sizeof(TileStage), stream)) return rc;
+    }
+    return set_out_caps(b, caps.cap_out_sites, caps.cap_cells);
+}
+int passbufs_grow(DeviceCols &d, PassBufs &b, const RunCounts &need) {
+    SetBytes count(d, b);
+    auto grown = [](uint32_t cap, uint32_t n) { return n <= cap ? cap : (uint32_t)std::min<uint64_t>(0x7fffffffull, (uint64_t)n + n / 4 + 1024); };
+    const uint32_t ev = grown(b.cap_events, need.n_events), ov = grown(b.cap_overflow, need.n_overflow), si = grown(b.cap_sites, need.n_sites);
+    if (ev != b.cap_events) { if (int rc = set_buf(b, b.events, b.cap_events, ev)) return rc; b.cap_events = ev; }
+    if (ov != b.cap_overflow) { if (int rc = set_buf(b, b.overflow, b.cap_overflow, ov)) return rc; b.cap_overflow = ov; }
+    if (si != b.cap_sites) {
+        if (int rc = set_buf(b, b.sites, b.cap_sites, si)) return rc;
+        if (int rc = set_buf(b, b.unc_sites, b.cap_sites, si)) return rc;
+        b.cap_sites = si;
+    }
+    return MSNV_OK;
+}
+void passbufs_free(DeviceCols &d, PassBufs &b) {
+    SetBytes count(d, b);
+    void *ptrs[] = {b.tot, b.part, b.spill, b.aspill, b.events, b.overflow, b.counters, b.ind4, b.tile_dirty, b.unc_sites, b.site_row, b.site_bits, b.site_rank, b.sites,
+                    b.tile_site_base, b.tile_site_cnt, b.tile_cell_base, b.ncol, b.cov_col, b.site_flags, b.site_elig, b.tile_stage};      // (unc_bits: inside ind4)
+    for (void *p : ptrs) if (p && !dev_in_block(d, p)) dev_free(p);
+    b = PassBufs{};
+}
+
 void dev_free_all(DeviceCols &d) {
+    passbufs_free(d, d); passbufs_free(d, d.alt);
     void *ptrs[] = {d.hdr, d.hdr8, d.hdr4, d.hdr8m, d.merged_groups, d.tile_pair_merged, d.blk, d.seq, d.qual, d.s_read_base, d.s_seq_base, d.ref4, d.ref_lc, d.pairs,
-                    d.tile_pair_start, d.work, d.chunks, d.tile_vbeg, d.tile_vend, d.tot, d.part, d.tile_slot_start, d.tile_slot_u16, d.tile_slot_wide, d.slot_off, d.spill, d.events, d.overflow, d.counters, d.ind4, d.tile_dirty, d.unc_sites, d.site_row, d.gate_tiles,
-                    d.sites, d.tile_site_base, d.tile_site_cnt, d.tile_cell_base, d.tile_nslots, d.ncol, d.cov_col, d.site_flags, d.site_elig,
-                    d.cov_iv, d.s_cov_base, d.cov_pairs, d.cov_work, d.tile_len, d.tile_contig_dev, d.cov_acc, d.tile_stage, d.tile_stage_idx, d.alt.tile_stage, d.gate_tiles_dense, d.gate_tiles_staged, d.gather_tiles};
-    auto in_block = [&](void *p) { for (const auto &b : d.blocks) if ((char *)p >= (char *)b.first && (char *)p < (char *)b.first + b.second) return true; return false; };
-    for (void *p : ptrs) if (p && !in_block(p)) dev_free(p);
+                    d.tile_pair_start, d.work, d.chunks, d.tile_vbeg, d.tile_vend, d.tile_slot_start, d.tile_slot_u16, d.tile_slot_wide, d.slot_off, d.gate_tiles, d.tile_nslots,
+                    d.cov_iv, d.s_cov_base, d.cov_pairs, d.cov_work, d.tile_len, d.tile_contig_dev, d.cov_acc, d.tile_stage_idx, d.gate_tiles_dense, d.gate_tiles_staged, d.gather_tiles, d.active_tiles};
+    for (void *p : ptrs) if (p && !dev_in_block(d, p)) dev_free(p);
     void *aptrs[] = {d.ann.seg_beg, d.ann.seg_end, d.ann.seg_gene, d.ann.genes, d.ann.contigs, d.ann.codons, d.ann.out, d.ann.err};
     for (void *p : aptrs) dev_free(p);
     for (void *e : d.timing_events) if (e) (void)hipEventDestroy((hipEvent_t)e);
     for (void *e : d.event_pool) (void)hipEventDestroy((hipEvent_t)e);
     if (d.pinned_cnt) (void)hipHostFree(d.pinned_cnt);
-    void *alts[] = {d.aspill, d.alt.aspill, d.alt.tot, d.alt.part, d.alt.spill, d.alt.events, d.alt.overflow, d.alt.counters, d.alt.ind4, d.alt.tile_dirty, d.alt.unc_sites, d.alt.site_row, d.alt.sites, d.alt.tile_site_base,
-                    d.alt.tile_site_cnt, d.alt.tile_cell_base, d.alt.ncol, d.alt.cov_col, d.alt.site_flags, d.alt.site_elig, d.alt.site_bits, d.site_bits, d.alt.site_rank, d.site_rank, d.active_tiles};
-    for (void *p : alts) if (p && !in_block(p)) dev_free(p);
     for (const auto &b : d.blocks) dev_free(b.first);
     if (d.stream2) (void)hipStreamDestroy((hipStream_t)d.stream2);
     d = DeviceCols{};
 }
 
-static int ensure_out(DeviceCols &d, uint64_t n_sites, uint64_t n_cells) {
-    if (n_sites > d.cap_out_sites) {
-        dev_free(d.site_flags); d.site_flags = nullptr;
-        dev_free(d.site_elig); d.site_elig = nullptr;
-        const uint64_t cap = std::max<uint64_t>(n_sites + n_sites / 4, 1024);
-        if (int rc = dev_alloc((void **)&d.site_flags, cap + 4, &d.device_bytes)) return rc;      // (+4: 32-bit atomics on the byte's aligned word)
-        if (int rc = dev_alloc((void **)&d.site_elig, cap + 4, &d.device_bytes)) return rc;
-        d.cap_out_sites = cap;
-    }
-    if (n_cells > d.cap_cells) {
-        dev_free(d.ncol); dev_free(d.cov_col);
-        d.ncol = nullptr; d.cov_col = nullptr;
-        const uint64_t cap = (std::max<uint64_t>(n_cells + n_cells / 4, 1u << 16) + 7) & ~7ull;      // (a multiple of 8: every column starts on 16 bytes)
-        if (int rc = dev_alloc((void **)&d.ncol, 4 * cap * sizeof(uint16_t) + 16, &d.device_bytes)) return rc;
-        if (int rc = dev_alloc((void **)&d.cov_col, cap * sizeof(uint16_t) + 16, &d.device_bytes)) return rc;
-        d.cap_cells = cap;
-    }
-    return MSNV_OK;
+// the output columns of a set hold at least n_sites / n_cells (with a quarter to spare when they have to grow)
+static int ensure_out(DeviceCols &d, PassBufs &b, uint64_t n_sites, uint64_t n_cells) {
+    SetBytes count(d, b);
+    return set_out_caps(b, n_sites > b.cap_out_sites ? std::max<uint64_t>(n_sites + n_sites / 4, 1024) : b.cap_out_sites,
+                        n_cells > b.cap_cells ? (std::max<uint64_t>(n_cells + n_cells / 4, 1u << 16) + 7) & ~7ull : b.cap_cells);      // (a multiple of 8: every column starts on 16 bytes)
 }
 
 // (the list lives behind the record lists, in the same allocation: the two sets of intermediates swap it with them)
 static inline uint32_t *stage_ovf_list(const DeviceCols &d) { return d.tile_stage ? reinterpret_cast<uint32_t *>(d.tile_stage + d.n_active_tiles) : nullptr; }
+
+// msnv_gate_sites for (several tiles per workgroup or a tile list, 32-bit allele totals, allele planes)
+static void launch_gate_sites(bool multi, bool wide_tot, bool planes, dim3 grid, hipStream_t st, const GateArgs &g) {
+    void (*const k)(GateArgs) =
+        planes ? (!multi ? (wide_tot ? msnv_gate_sites<false, true, true> : msnv_gate_sites<false, false, true>) : (wide_tot ? msnv_gate_sites<true, true, true> : msnv_gate_sites<true, false, true>))
+               : (!multi ? (wide_tot ? msnv_gate_sites<false, true> : msnv_gate_sites<false, false>) : (wide_tot ? msnv_gate_sites<true, true> : msnv_gate_sites<true, false>));
+    hipLaunchKernelGGL(k, grid, dim3(GATE_NT), 0, st, g);
+}
 
 // Enqueues one pass (kernels + readback of the pass' counter block into host_cnt[CNT_WORDS]) without waiting for it.
 // ev_begin / ev_pile0 / ev_pile1 are recorded before the pass, before and after the pileup kernel(s); ev3 / ev4 (optional)
@@ -3021,53 +3096,32 @@ static int enqueue_pass(DeviceCols &d, const msnv_params &p, hipStream_t st, hip
         g.site_bits = d.site_bits; g.site_rank = d.site_rank; g.sites = d.sites; g.cap_sites = d.cap_sites; g.counters = counters; g.counters_next = counters_next;
         g.tile_site_base = d.tile_site_base; g.tile_site_cnt = d.tile_site_cnt; g.active_tiles = d.active_tiles;
         g.ncol = d.ncol; g.cov_col = d.cov_col; g.site_flags = d.site_flags; g.cap_out = cap_out;
-        g.gate_tiles = reinterpret_cast<const GateTile *>(d.gate_tiles); g.tile_dirty = d.tile_dirty; g.unc_sites = d.unc_sites;
+        g.gate_tiles = d.gate_tiles; g.tile_dirty = d.tile_dirty; g.unc_sites = d.unc_sites;
         g.use_dirty = d.use_dirty ? 1u : 0u; g.block_row = d.site_row; g.site_elig = d.site_elig; g.any_split = d.any_split ? 1u : 0u;
-        static_assert(sizeof(GateTile) == sizeof(DeviceCols::GateTileH) && sizeof(GateTile) == 64, "gate tile descriptor");
         g.tile_nslots = d.tile_nslots; g.tile_cell_base = d.tile_cell_base; g.cap_cells = d.cap_cells;
         // several tiles per workgroup once the tiles outnumber what the device holds at a time several times over (one reservation of
         // site slots per workgroup: msnv_gate_sites); MSNV_GATE_TILES overrides (tests run every size)
         g.tile_stage = d.tile_stage; g.tiles_per_wg = 1u;
         // whole-tile work items left record lists: their tiles go through msnv_gate_staged, the others through msnv_gate_sites
         const uint32_t n_staged = use_stage ? d.n_fused_tiles : 0u, n_dense = d.n_active_tiles - n_staged;
-        if (use_stage) g.gate_tiles = reinterpret_cast<const GateTile *>(d.gate_tiles_dense);
+        if (use_stage) g.gate_tiles = d.gate_tiles_dense;
         g.n_active = n_dense;
         g.zero_next = 1u; g.tile_list = nullptr; g.solo_cells = 0u;
         if (n_dense) {
             g.tiles_per_wg = knob::gate_tiles(n_dense >= 32768u ? 8u : n_dense >= 8192u ? 4u : 1u, (int)GATE_MAX_TILES);
             const dim3 grid((n_dense + g.tiles_per_wg - 1) / g.tiles_per_wg);
             g.aspill = d.aspill;
-            if (d.allele_planes) {
-                if (g.tiles_per_wg == 1u) {
-                    if (d.wide_tot) hipLaunchKernelGGL((msnv_gate_sites<false, true, true>), grid, dim3(GATE_NT), 0, st, g);
-                    else hipLaunchKernelGGL((msnv_gate_sites<false, false, true>), grid, dim3(GATE_NT), 0, st, g);
-                } else {
-                    if (d.wide_tot) hipLaunchKernelGGL((msnv_gate_sites<true, true, true>), grid, dim3(GATE_NT), 0, st, g);
-                    else hipLaunchKernelGGL((msnv_gate_sites<true, false, true>), grid, dim3(GATE_NT), 0, st, g);
-                }
-            } else if (g.tiles_per_wg == 1u) {
-                if (d.wide_tot) hipLaunchKernelGGL((msnv_gate_sites<false, true>), grid, dim3(GATE_NT), 0, st, g);
-                else hipLaunchKernelGGL((msnv_gate_sites<false, false>), grid, dim3(GATE_NT), 0, st, g);
-            } else {
-                if (d.wide_tot) hipLaunchKernelGGL((msnv_gate_sites<true, true>), grid, dim3(GATE_NT), 0, st, g);
-                else hipLaunchKernelGGL((msnv_gate_sites<true, false>), grid, dim3(GATE_NT), 0, st, g);
-            }
+            launch_gate_sites(g.tiles_per_wg != 1u, d.wide_tot, d.allele_planes, grid, st, g);
             g.zero_next = 0u;
         }
         if (n_staged) {
-            hipLaunchKernelGGL(msnv_gate_staged, dim3((n_staged + GS_WAVES * GS_TILES - 1) / (GS_WAVES * GS_TILES)), dim3(64 * GS_WAVES), 0, st, g, reinterpret_cast<const GateTile *>(d.gate_tiles_staged), n_staged);
+            hipLaunchKernelGGL(msnv_gate_staged, dim3((n_staged + GS_WAVES * GS_TILES - 1) / (GS_WAVES * GS_TILES)), dim3(64 * GS_WAVES), 0, st, g, d.gate_tiles_staged, n_staged);
             // the tiles whose candidates did not fit their record list (counted and listed on the device: fused_tile_gate) through the ordinary
             // gate; the workgroups stride over the list -- as many as the previous pass would have kept busy, a handful when it listed none
-            g.gate_tiles = reinterpret_cast<const GateTile *>(d.gate_tiles); g.tile_list = stage_ovf_list(d); g.n_active = n_staged; g.solo_cells = 1u;
+            g.gate_tiles = d.gate_tiles; g.tile_list = stage_ovf_list(d); g.n_active = n_staged; g.solo_cells = 1u;
             g.tiles_per_wg = 1u; g.zero_next = 0u; g.aspill = d.aspill;
             const dim3 grid(std::min<uint32_t>(n_staged, std::max<uint32_t>(64u, std::min<uint32_t>(4096u, d.last_ovf_tiles))));
-            if (d.allele_planes) {
-                if (d.wide_tot) hipLaunchKernelGGL((msnv_gate_sites<true, true, true>), grid, dim3(GATE_NT), 0, st, g);
-                else hipLaunchKernelGGL((msnv_gate_sites<true, false, true>), grid, dim3(GATE_NT), 0, st, g);
-            } else {
-                if (d.wide_tot) hipLaunchKernelGGL((msnv_gate_sites<true, true>), grid, dim3(GATE_NT), 0, st, g);
-                else hipLaunchKernelGGL((msnv_gate_sites<true, false>), grid, dim3(GATE_NT), 0, st, g);
-            }
+            launch_gate_sites(true, d.wide_tot, d.allele_planes, grid, st, g);
         }
         HIP_TRY(hipGetLastError());
     } else HIP_TRY(hipMemsetAsync(counters_next, 0, CNT_WORDS * sizeof(uint32_t), st));   // nobody else would
@@ -3132,7 +3186,7 @@ int dev_run_pipeline(DeviceCols &d, const msnv_params &p, void *stream_, msnv_ru
     // every event record costs ~6 us of stream time (the next kernel waits for the marker): the per-phase split of
     // the tail is only recorded on request (MSNV_PHASE_TIMES=1, profiles/phase_times.py)
     const bool phase_times = knob::phase_times();
-    if (int rc = ensure_out(d, std::max<uint64_t>(d.last_sites + d.last_sites / 2, 4096), std::max<uint64_t>(d.last_cells + d.last_cells / 2, 1u << 18))) return rc;
+    if (int rc = ensure_out(d, d, std::max<uint64_t>(d.last_sites + d.last_sites / 2, 4096), std::max<uint64_t>(d.last_cells + d.last_cells / 2, 1u << 18))) return rc;
     uint32_t cnt[CNT_WORDS] = {0};
     if (int rc = enqueue_pass(d, p, st, ev[0], ev[1], ev[2], phase_times ? ev[3] : nullptr, phase_times ? ev[4] : nullptr, cnt)) return rc;
     HIP_TRY(hipEventRecord(ev[5], st));
@@ -3154,62 +3208,17 @@ int dev_run_pipeline(DeviceCols &d, const msnv_params &p, void *stream_, msnv_ru
     return MSNV_OK;
 }
 
-// Second set of per-pass intermediates, sized like the first (re-made when the first set was grown).
-static int ensure_alt(DeviceCols &d) {
-    DeviceCols::AltBufs &a = d.alt;
-    const uint64_t npos = (uint64_t)d.n_tiles * TILE;
+// Second set of per-pass buffers, sized like the first (re-made when the first set was grown).  Its fills are queued on `stream` and waited
+// for: the passes run on two streams that nothing else orders behind them.
+static int ensure_alt(DeviceCols &d, void *stream) {
+    PassBufs &a = d.alt;
     if (a.tot && a.cap_events == d.cap_events && a.cap_overflow == d.cap_overflow && a.cap_sites == d.cap_sites && a.cap_out_sites == d.cap_out_sites && a.cap_cells == d.cap_cells) return MSNV_OK;
-    void *old[] = {a.aspill, a.tot, a.part, a.spill, a.events, a.overflow, a.counters, a.ind4, a.tile_dirty, a.unc_sites, a.site_row, a.sites, a.tile_site_base, a.tile_site_cnt, a.tile_cell_base, a.ncol, a.cov_col, a.site_flags, a.site_elig, a.site_bits, a.site_rank, a.tile_stage};
-    for (void *p : old) dev_free(p);
-    a = DeviceCols::AltBufs{};
-    if (int rc = dev_alloc((void **)&a.tot, std::max<uint64_t>(1, 4 * npos) * sizeof(uint32_t), &d.device_bytes)) return rc;
-    if (int rc = dev_memset(a.tot, 0, std::max<uint64_t>(1, 4 * npos) * sizeof(uint32_t))) return rc;
-    if (int rc = dev_alloc((void **)&a.part, d.part_bytes, &d.device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&a.spill, std::max<uint64_t>(1, d.n_pairs) * TILE, &d.device_bytes)) return rc;
-    if (d.allele_planes) {
-        if (int rc = dev_alloc((void **)&a.aspill, (uint64_t)d.n_pairs * 4 * TILE, &d.device_bytes)) return rc;
-        if (int rc = dev_memset(a.aspill, 0, (uint64_t)d.n_pairs * 4 * TILE)) return rc;
-    }
-    if (int rc = dev_alloc((void **)&a.events, (uint64_t)d.cap_events * sizeof(Pair32), &d.device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&a.overflow, (uint64_t)d.cap_overflow * sizeof(Pair32), &d.device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&a.sites, (uint64_t)d.cap_sites * sizeof(SiteRec), &d.device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&a.unc_sites, (uint64_t)d.cap_sites * sizeof(uint32_t), &d.device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&a.site_row, (npos / 64 + 1) * sizeof(unsigned long long), &d.device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&a.tile_dirty, ((uint64_t)d.n_work + 1) * sizeof(uint32_t), &d.device_bytes)) return rc;
-    if (int rc = dev_memset(a.tile_dirty, 0, ((uint64_t)d.n_work + 1) * sizeof(uint32_t))) return rc;
-    if (int rc = dev_alloc((void **)&a.counters, 2 * CNT_WORDS * sizeof(uint32_t), &d.device_bytes)) return rc;
-    if (int rc = dev_memset(a.counters, 0, 2 * CNT_WORDS * sizeof(uint32_t))) return rc;
-    if (int rc = dev_alloc((void **)&a.ind4, (npos / 8 + npos / 32 + 2) * sizeof(uint32_t), &d.device_bytes)) return rc;
-    if (int rc = dev_memset(a.ind4, 0, (npos / 8 + npos / 32 + 2) * sizeof(uint32_t))) return rc;
-    a.unc_bits = a.ind4 + npos / 8 + 1; a.cnt_parity = 0;
-    if (int rc = dev_alloc((void **)&a.site_bits, (npos / 64 + 1) * sizeof(unsigned long long), &d.device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&a.site_rank, (npos / 64 + 1) * sizeof(uint32_t), &d.device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&a.tile_site_base, ((uint64_t)d.n_tiles + 1) * sizeof(uint32_t), &d.device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&a.tile_site_cnt, ((uint64_t)d.n_tiles + 1) * sizeof(uint32_t), &d.device_bytes)) return rc;
-    if (int rc = dev_memset(a.tile_site_cnt, 0, ((uint64_t)d.n_tiles + 1) * sizeof(uint32_t))) return rc;
-    if (int rc = dev_memset(a.tile_site_base, 0, ((uint64_t)d.n_tiles + 1) * sizeof(uint32_t))) return rc;
-    if (int rc = dev_alloc((void **)&a.tile_cell_base, ((uint64_t)d.n_tiles + 1) * sizeof(unsigned long long), &d.device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&a.ncol, 4 * d.cap_cells * sizeof(uint16_t) + 16, &d.device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&a.cov_col, d.cap_cells * sizeof(uint16_t) + 16, &d.device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&a.site_flags, d.cap_out_sites + 4, &d.device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&a.site_elig, d.cap_out_sites + 4, &d.device_bytes)) return rc;
-    if (d.n_fused_tiles && !a.tile_stage) {
-        if (int rc = dev_alloc((void **)&a.tile_stage, (uint64_t)d.n_active_tiles * sizeof(TileStage) + (uint64_t)d.n_fused_tiles * sizeof(uint32_t), &d.device_bytes)) return rc;   // (+ the overflow list: stage_ovf_list)
-        if (int rc = dev_memset(a.tile_stage, 0, (uint64_t)d.n_active_tiles * sizeof(TileStage))) return rc;
-    }
-    a.cap_events = d.cap_events; a.cap_overflow = d.cap_overflow; a.cap_sites = d.cap_sites; a.cap_out_sites = d.cap_out_sites; a.cap_cells = d.cap_cells;
-    return MSNV_OK;
+    passbufs_free(d, a);
+    if (int rc = passbufs_alloc(d, a, d, stream)) return rc;
+    return dev_stream_wait(stream);
 }
-static void swap_sets(DeviceCols &d) {
-    DeviceCols::AltBufs &a = d.alt;
-    std::swap(d.tot, a.tot); std::swap(d.part, a.part); std::swap(d.spill, a.spill); std::swap(d.events, a.events);
-    if (a.aspill) std::swap(d.aspill, a.aspill);
-    std::swap(d.overflow, a.overflow); std::swap(d.counters, a.counters); std::swap(d.sites, a.sites);
-    std::swap(d.tile_site_base, a.tile_site_base); std::swap(d.tile_site_cnt, a.tile_site_cnt); std::swap(d.tile_cell_base, a.tile_cell_base); std::swap(d.ncol, a.ncol); std::swap(d.cov_col, a.cov_col);
-    std::swap(d.site_flags, a.site_flags); std::swap(d.site_elig, a.site_elig); std::swap(d.ind4, a.ind4); std::swap(d.unc_bits, a.unc_bits); std::swap(d.cnt_parity, a.cnt_parity);
-    if (a.tile_stage) std::swap(d.tile_stage, a.tile_stage);
-    std::swap(d.tile_dirty, a.tile_dirty); std::swap(d.unc_sites, a.unc_sites); std::swap(d.site_row, a.site_row); std::swap(d.site_bits, a.site_bits); std::swap(d.site_rank, a.site_rank);
-}
+// (both sets hold aspill under allele_planes and tile_stage under n_fused_tiles: a null swaps with a null)
+static void swap_sets(DeviceCols &d) { std::swap(static_cast<PassBufs &>(d), d.alt); }
 
 // n passes, ONE host synchronisation at the end; with `overlap` they are in flight on two streams (a queue of shards / repeated passes keeps the
 // GPU busy: the host round trip of the single-pass form costs ~40 us of idle GPU per pass).  Consecutive passes use
@@ -3236,11 +3245,11 @@ int dev_reserve_passes(DeviceCols &d, int n) {
 int dev_run_pipeline_many(DeviceCols &d, const msnv_params &p, void *stream_, int n, bool overlap, msnv_run_stats *stats, RunCounts *counts) {
     if (n <= 0) return MSNV_OK;
     hipStream_t s0 = (hipStream_t)stream_, s1 = s0;
-    if (int rc = ensure_out(d, std::max<uint64_t>(d.last_sites + d.last_sites / 2, 4096), std::max<uint64_t>(d.last_cells + d.last_cells / 2, 1u << 18))) return rc;
+    if (int rc = ensure_out(d, d, std::max<uint64_t>(d.last_sites + d.last_sites / 2, 4096), std::max<uint64_t>(d.last_cells + d.last_cells / 2, 1u << 18))) return rc;
     if (overlap && n > 1) {
         if (!d.stream2) { hipStream_t s; HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); d.stream2 = s; }
         s1 = (hipStream_t)d.stream2;
-        if (int rc = ensure_alt(d)) return rc;
+        if (int rc = ensure_alt(d, s0)) return rc;
     }
     const bool two = s1 != s0;
     if (int rc = dev_reserve_passes(d, n)) return rc;

@@ -1270,8 +1270,6 @@ int finalize_dataset(msnv_dataset &ds) {
         for (uint64_t t = 0; t < nt; ++t)
             for (uint32_t k = tps[t]; k < tps[t + 1]; ++k) if ((pairs[k].pad & 0xffu) == 1u) { nslots[t] |= NSLOTS_SPLIT; break; }
         if (int rc = arena.add(&d->tile_nslots, nslots, &d->device_bytes)) return rc;
-        if (int rc = dev_alloc((void **)&d->tile_cell_base, (nt + 1) * sizeof(unsigned long long), &d->device_bytes)) return rc;
-        if (int rc = dev_memset_async(d->tile_cell_base, 0, (nt + 1) * sizeof(unsigned long long), ds.ctx ? ds.ctx->stream : nullptr)) return rc;
     }
     lap("slots");
     // ---- work list: split each tile's pairs so that work items carry similar read counts
@@ -1418,13 +1416,12 @@ int finalize_dataset(msnv_dataset &ds) {
         if (int rc = arena.add(&d->tile_slot_u16, t16, &d->device_bytes)) return rc;
         if (int rc = arena.add(&d->tile_slot_wide, twide, &d->device_bytes)) return rc;
         if (int rc = arena.add(&d->slot_off, off, &d->device_bytes)) return rc;
-        if (int rc = dev_alloc((void **)&d->part, d->part_bytes, &d->device_bytes)) return rc;
         // one descriptor per active tile for the gate kernel: everything it looks up about its tile in one load
         std::vector<uint32_t> nslots_host(nt + 1, 0);
         for (uint64_t t = 0; t < nt; ++t) nslots_host[t] = ds.tile_slot_stride[t];
-        std::vector<DeviceCols::GateTileH> gts;
+        std::vector<GateTile> gts;
         gts.reserve(active.size());
-        for (uint32_t t : active) gts.push_back(DeviceCols::GateTileH{t, tss[t], t16[t], twide[t], tss[t + 1], vb_host[t], ve_host[t], nslots_host[t], off[tss[t]], tot_mode(t), (uint32_t)fuse_tile[t],
+        for (uint32_t t : active) gts.push_back(GateTile{t, tss[t], t16[t], twide[t], tss[t + 1], vb_host[t], ve_host[t], nslots_host[t], off[tss[t]], tot_mode(t), (uint32_t)fuse_tile[t],
                                                                       tps[t], tpm[t] - tps[t], 0, 0});
         if (int rc = arena.add(&d->gate_tiles, gts, &d->device_bytes, 1)) return rc;
         d->gather_split = knob::gather_split((uint32_t)std::min<uint64_t>(4, std::max<uint64_t>(1, (active.empty() ? 0 : pairs.size() / active.size()) / 32)));
@@ -1434,19 +1431,16 @@ int finalize_dataset(msnv_dataset &ds) {
             for (size_t i = 0; i < active.size(); ++i) { stage_idx[active[i]] = (uint32_t)i; n_fused += fuse_tile[active[i]] != 0; }
             d->n_fused_tiles = n_fused;
             if (n_fused) {
-                std::vector<DeviceCols::GateTileH> dense_l, staged_l;
+                std::vector<GateTile> dense_l, staged_l;
                 for (size_t i = 0; i < gts.size(); ++i) {
                     if (!gts[i].staged) { dense_l.push_back(gts[i]); continue; }
-                    DeviceCols::GateTileH g = gts[i];
+                    GateTile g = gts[i];
                     g.row0 = (uint64_t)i;                              // (a whole-tile item writes no partial row: the field carries the index of its record list)
                     staged_l.push_back(g);
                 }
                 if (int rc = arena.add(&d->gate_tiles_dense, dense_l, &d->device_bytes, 1)) return rc;
                 if (int rc = arena.add(&d->gate_tiles_staged, staged_l, &d->device_bytes, 1)) return rc;
                 if (int rc = arena.add(&d->tile_stage_idx, stage_idx, &d->device_bytes)) return rc;
-                // (+ one index per whole-tile item behind the lists: the tiles whose candidates do not fit a list -- kernels.hip: stage_ovf_list)
-                if (int rc = dev_alloc((void **)&d->tile_stage, (uint64_t)active.size() * sizeof(TileStage) + (uint64_t)n_fused * sizeof(uint32_t), &d->device_bytes)) return rc;
-                if (int rc = dev_memset_async(d->tile_stage, 0, (uint64_t)active.size() * sizeof(TileStage), ds.ctx ? ds.ctx->stream : nullptr)) return rc;
             }
         }
         d->wide_tot = false;
@@ -1693,9 +1687,6 @@ int finalize_dataset(msnv_dataset &ds) {
     // ---- intermediates (before the coverage index: their allocations and fills -- queued on the context's stream, in front of the first
     // pass -- run while the device still works on the index; the coverage index below holds finalize's last wait)
     void *const fin_stream = ds.ctx ? ds.ctx->stream : nullptr;
-    if (int rc = dev_alloc((void **)&d->tot, std::max<uint64_t>(1, 4 * npos) * sizeof(uint32_t), &d->device_bytes)) return rc;
-    if (int rc = dev_memset_async(d->tot, 0, std::max<uint64_t>(1, 4 * npos) * sizeof(uint32_t), fin_stream)) return rc;   // the gate kernel keeps it zero between passes
-    if (int rc = dev_alloc((void **)&d->spill, std::max<uint64_t>(1, (uint64_t)pairs.size()) * TILE, &d->device_bytes)) return rc;
     double est_events = 0.0;                                        // mismatching bases the sampled rate predicts: what the event list is sized by
     {
         // Allele bookkeeping of the narrow work items.  Clean reads (the benchmark's 0.1 % errors): a mismatching base is an EVENT -- one
@@ -1720,11 +1711,6 @@ int finalize_dataset(msnv_dataset &ds) {
         if (const char forced = knob::alleles()) planes = forced == 'p';
         if (dense || d->n_work > d->n_work_narrow + d->n_work_merged || pairs.empty()) planes = false;
         d->allele_planes = planes;
-        if (planes) {
-            const uint64_t bytes = (uint64_t)pairs.size() * 4 * TILE;
-            if (int rc = dev_alloc((void **)&d->aspill, bytes, &d->device_bytes)) return rc;
-            if (int rc = dev_memset_async(d->aspill, 0, bytes, fin_stream)) return rc;      // (rows of merged pairs are never written and never read)
-        }
         ds.info.allele_planes = planes ? 1 : 0;
         ds.info.sampled_mismatch_ppm = (uint64_t)(rate * 1e6);
     }
@@ -1734,27 +1720,8 @@ int finalize_dataset(msnv_dataset &ds) {
     d->cap_events = knob::cap_events((uint32_t)std::min<uint64_t>(0x7fffffffull, std::max<uint64_t>(1u << 20, std::min<uint64_t>(tot_bases / 16, (uint64_t)(4.0 * est_events) + (1u << 20)))), EV_LISTS);   // (tests force the grow-and-rerun path)
     d->cap_overflow = (uint32_t)std::min<uint64_t>(0x7fffffffull, std::max<uint64_t>(1u << 16, npos / 8));
     d->cap_sites = (uint32_t)std::min<uint64_t>(0x7fffffffull, std::max<uint64_t>(1u << 16, npos / 4));
-    if (int rc = dev_alloc((void **)&d->events, (uint64_t)d->cap_events * sizeof(Pair32), &d->device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&d->overflow, (uint64_t)d->cap_overflow * sizeof(Pair32), &d->device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&d->sites, (uint64_t)d->cap_sites * sizeof(SiteRec), &d->device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&d->unc_sites, (uint64_t)d->cap_sites * sizeof(uint32_t), &d->device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&d->site_row, (npos / 64 + 1) * sizeof(unsigned long long), &d->device_bytes)) return rc;   // per 64 positions (kernels.hip: CellMap::block_row)
-    if (int rc = dev_alloc((void **)&d->tile_dirty, ((uint64_t)work.size() + 1) * sizeof(uint32_t), &d->device_bytes)) return rc;    // one word per work item (by slot)
-    if (int rc = dev_memset_async(d->tile_dirty, 0, ((uint64_t)work.size() + 1) * sizeof(uint32_t), fin_stream)) return rc;
-    // no memset per pass: the counter blocks alternate (the gate kernel zeroes the next one) and the gate kernel leaves the
-    // individual-rule bits it consumes zero, like the allele totals
-    if (int rc = dev_alloc((void **)&d->counters, 2 * CNT_WORDS * sizeof(uint32_t), &d->device_bytes)) return rc;
-    if (int rc = dev_memset_async(d->counters, 0, 2 * CNT_WORDS * sizeof(uint32_t), fin_stream)) return rc;
-    if (int rc = dev_alloc((void **)&d->ind4, (npos / 8 + npos / 32 + 2) * sizeof(uint32_t), &d->device_bytes)) return rc;
-    if (int rc = dev_memset_async(d->ind4, 0, (npos / 8 + npos / 32 + 2) * sizeof(uint32_t), fin_stream)) return rc;
-    d->unc_bits = d->ind4 + npos / 8 + 1;
     for (const TilePair &tp : pairs) if ((tp.pad & 0xffu) == 1) { d->any_split = true; break; }
-    if (int rc = dev_alloc((void **)&d->site_bits, (npos / 64 + 1) * sizeof(unsigned long long), &d->device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&d->site_rank, (npos / 64 + 1) * sizeof(uint32_t), &d->device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&d->tile_site_base, (nt + 1) * sizeof(uint32_t), &d->device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&d->tile_site_cnt, (nt + 1) * sizeof(uint32_t), &d->device_bytes)) return rc;
-    if (int rc = dev_memset_async(d->tile_site_cnt, 0, (nt + 1) * sizeof(uint32_t), fin_stream)) return rc;
-    if (int rc = dev_memset_async(d->tile_site_base, 0, (nt + 1) * sizeof(uint32_t), fin_stream)) return rc;
+    if (int rc = passbufs_alloc(*d, *d, *d, fin_stream)) return rc;      // (the output columns come with the first pass: their capacities are still 0)
 
     ds.info.n_samples = S; ds.info.n_contigs = 0; ds.info.n_positions = 0;
     for (size_t c = 0; c < NC; ++c) if (ds.sel[c]) { ds.info.n_contigs++; ds.info.n_positions += (uint64_t)ds.lengths[c]; }

@@ -526,6 +526,34 @@ def test_event_list_grows_when_a_sub_list_overflows(monkeypatch):
     assert prod[3]["n_events"] == ref_run[3]["n_events"] > 4096
 
 
+def test_second_set_follows_a_grown_first_set(monkeypatch):
+    """The overlapped batch keeps a second set of per-pass buffers at the first set's capacities (kernels.hip: ensure_alt).  A dataset
+    whose event list starts at 1024 grows its first set in run(); the overlapped batches behind that build the second set at the grown
+    capacities, end on either set, and the single-pass form runs on whichever set is primary -- the same bytes and the same event count
+    as a dataset that never grew, after every step.  The second sequence makes its first overlapped batch right behind the grow and
+    runs the single-pass form between two batches: a dataset-level grow there (capacities that differ from the second set's) sends
+    ensure_alt through its rebuild.  The passes of one dataset ask for the same capacities every time, so this cohort settles after
+    the first grow; the sequence stays for the case that does not."""
+    syn, samples = synth_case(n_species=2, contig_len=7000, n_samples=8, mean_cov=14.0, snv_density=0.03, error_rate=0.01, seed=909)
+    monkeypatch.setenv("MSNV_ALLELES", "events")
+    *_, ref_st, ref_ds, ref_ctx = run_product(syn.names, syn.lengths, syn.seqs, samples, return_ds=True)
+    ref = tuple(x.tobytes() for x in ref_ds.results())
+    ref_ds.close(); ref_ctx.close()
+    assert ref_st["n_events"] > 4096
+    monkeypatch.setenv("MSNV_CAP_EVENTS", "1024")                    # 32 events per sub-list: every list overflows
+
+    def same(ds, stats, step):
+        assert tuple(x.tobytes() for x in ds.results()) == ref, step
+        assert all(s["n_events"] == ref_st["n_events"] for s in stats), step
+
+    for steps in (((3, True), (2, True), None), ((2, True), None, (2, True))):
+        *_, st, ds, ctx = run_product(syn.names, syn.lengths, syn.seqs, samples, return_ds=True)      # (its run() grows the first set)
+        same(ds, [st], "run")
+        for i, step in enumerate(steps):
+            same(ds, [ds.run()] if step is None else ds.run_many(*step), (steps, i))
+        ds.close(); ctx.close()
+
+
 @pytest.mark.parametrize("knobs", [dict(MSNV_ITEM_PIECES="64"), dict(MSNV_ITEM_PIECES="300", MSNV_ITEM_TAPER="0"),
                                    dict(MSNV_ITEM_PIECES="5000"), dict(MSNV_TAPER_AT="900,300,100"), dict(MSNV_COV_ITEM="7")])
 def test_results_do_not_depend_on_the_work_decomposition(knobs, monkeypatch, tmp_path):
