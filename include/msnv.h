@@ -368,7 +368,11 @@ int  msnv_dataset_info_get(const msnv_dataset *ds, msnv_dataset_info *out);
 #define MSNV_PACK_STATS 18
 int  msnv_dataset_pack_stats(const msnv_dataset *ds, double *out, int32_t n);
 /* Inspection hook: the bytes of one device column / index table of a finalized dataset ("hdr", "hdr4", "hdr8m", "blk", "seq", "qual",
- * "s_read_base", "s_seq_base", "ref4", "pairs", "work", "chunks", "cov_iv", "cov_pairs", "cov_work").  out = NULL: size query.  The tests
+ * "s_read_base", "s_seq_base", "ref4", "pairs", "work", "chunks", "cov_iv", "cov_pairs", "cov_work"; the other tables of the tile index:
+ * "ref_lc", "tile_vbeg", "tile_vend", "tile_nslots", "active_tiles", "gather_tiles", "tile_slot_start", "tile_slot_u16", "tile_slot_wide",
+ * "slot_off", "gate_tiles", "gate_tiles_dense", "gate_tiles_staged", "tile_stage_idx", "merged_groups", "tile_pair_start",
+ * "tile_pair_merged", "s_cov_base", "tile_len", "tile_contig_dev"; a table the dataset's layout does not allocate holds 0 bytes).
+ * out = NULL: size query.  The tests
  * use it to show that the device pack (csrc/devpack.hip) and the host pack (csrc/pack.cpp) build the same dataset byte for byte. */
 int  msnv_dataset_fetch_column(msnv_dataset *ds, const char *name, uint8_t *out, uint64_t capacity, uint64_t *n_bytes);
 

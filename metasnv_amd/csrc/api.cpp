@@ -569,6 +569,27 @@ extern "C" int msnv_dataset_fetch_column(msnv_dataset *ds, const char *name, uin
     else if (k == "cov_iv") { p = d.cov_iv; n = d.n_cov_iv * sizeof(Pair32); }
     else if (k == "cov_pairs") { p = d.cov_pairs; n = (uint64_t)d.n_cov_pairs * sizeof(TilePair); }
     else if (k == "cov_work") { p = d.cov_work; n = (uint64_t)d.n_cov_work * sizeof(WorkItem); }
+    // the rest of what finalize.cpp uploads: per-tile tables hold n_tiles + 1 words, a table the layout does not allocate holds nothing
+    else if (k == "ref_lc") { p = d.ref_lc; n = (nt * TILE / 32 + 1) * 4; }
+    else if (k == "tile_vbeg") { p = d.tile_vbeg; n = (nt + 1) * 4; }
+    else if (k == "tile_vend") { p = d.tile_vend; n = (nt + 1) * 4; }
+    else if (k == "tile_nslots") { p = d.tile_nslots; n = (nt + 1) * 4; }
+    else if (k == "tile_slot_start") { p = d.tile_slot_start; n = (nt + 1) * 4; }
+    else if (k == "tile_slot_u16") { p = d.tile_slot_u16; n = (nt + 1) * 4; }
+    else if (k == "tile_slot_wide") { p = d.tile_slot_wide; n = (nt + 1) * 4; }
+    else if (k == "tile_pair_start") { p = d.tile_pair_start; n = (nt + 1) * 4; }
+    else if (k == "tile_pair_merged") { p = d.tile_pair_merged; n = (nt + 1) * 4; }
+    else if (k == "tile_len") { p = d.tile_len; n = (nt + 1) * 4; }
+    else if (k == "tile_contig_dev") { p = d.tile_contig_dev; n = (nt + 1) * 4; }
+    else if (k == "tile_stage_idx") { p = d.tile_stage_idx; n = d.tile_stage_idx ? (nt + 1) * 4 : 0; }      // (datasets with whole-tile work items only)
+    else if (k == "active_tiles") { p = d.active_tiles; n = (uint64_t)d.n_active_tiles * 4; }
+    else if (k == "gather_tiles") { p = d.gather_tiles; n = (uint64_t)d.n_gather_tiles * 4; }
+    else if (k == "slot_off") { p = d.slot_off; n = ((uint64_t)d.n_work + 1) * 8; }
+    else if (k == "gate_tiles") { p = d.gate_tiles; n = (uint64_t)d.n_active_tiles * sizeof(GateTile); }
+    else if (k == "gate_tiles_dense") { p = d.gate_tiles_dense; n = d.gate_tiles_dense ? (uint64_t)(d.n_active_tiles - d.n_fused_tiles) * sizeof(GateTile) : 0; }
+    else if (k == "gate_tiles_staged") { p = d.gate_tiles_staged; n = d.gate_tiles_staged ? (uint64_t)d.n_fused_tiles * sizeof(GateTile) : 0; }
+    else if (k == "merged_groups") { p = d.merged_groups; n = (uint64_t)d.n_merged_groups * sizeof(MergedGroupDev); }
+    else if (k == "s_cov_base") { p = d.s_cov_base; n = (S + 1) * 8; }
     else return fail(MSNV_EINVAL, "msnv_dataset_fetch_column: no column named %s", name);
     *n_bytes = n;
     if (!out) return MSNV_OK;                                      // size query
@@ -690,7 +711,7 @@ static int fetch_results(msnv_dataset *ds) {
             ds->site_dev_index.push_back(i);
             const uint64_t cell0 = tcell[t] + (uint64_t)j * ds->tile_slot_stride[t];
             if (cell0 + n_slots > n_cells) return fail(MSNV_EHIP, "internal: the device reported %llu cells but tile %u needs cell %llu", (unsigned long long)n_cells, t, (unsigned long long)(cell0 + n_slots));
-            // the site's row of cells: the tile's slots in SAMPLE order (pack.cpp sorts a tile's pairs by kind, so the slots are not),
+            // the site's row of cells: the tile's slots in SAMPLE order (finalize.cpp sorts a tile's pairs by kind, so the slots are not),
             // without the samples that hold nothing at this position
             const size_t c_lo = ds->site_cells.size();
             for (uint64_t c = 0; c < n_slots; ++c) {

@@ -38,7 +38,7 @@ constexpr uint32_t SEQ_ALIGN_LOG2 = MSNV_SEQ_ALIGN_LOG2;
 constexpr uint32_t SEQ_ALIGN = 1u << SEQ_ALIGN_LOG2;
 static_assert(SEQ_ALIGN_LOG2 >= 1 && SEQ_ALIGN_LOG2 <= 3, "piece starts on 2, 4 or 8 bytes of the seq column");
 // Piece headers of the ordinary narrow work items: 4 bytes -- start in the tile (11 bits) | length (8) | seq offset relative to the
-// CHUNK's first byte in SEQ_ALIGN units (13 bits: a chunk spans < 16 KB of the seq column, pack.cpp closes it early otherwise); the
+// CHUNK's first byte in SEQ_ALIGN units (13 bits: a chunk spans < 16 KB of the seq column, finalize.cpp closes it early otherwise); the
 // chunk descriptor carries the absolute base (uniform per chunk: scalar registers, the loads take base + 32-bit lane offset).
 // MSNV_HDR4=0 (build-time) keeps the 8-byte form {start | length << 11, offset in the sample / SEQ_ALIGN} for A/B runs.
 #ifndef MSNV_HDR4
@@ -66,7 +66,7 @@ struct TilePair { uint32_t sample, read_lo, read_hi, max_depth, blk_lo, nblk, se
                                                                         // max_depth = upper bound of the per-position depth
 // One chunk = up to CHUNK_READS consecutive reads of one (tile, sample) pair, with everything the
 // kernel needs to start loading (no dependent scalar loads on the critical path).
-// Whole-tile work items (sparse cohorts, pack.cpp): ONE merged group holds every pair of the tile, so the workgroup that piles it up
+// Whole-tile work items (sparse cohorts, finalize.cpp: pair_classes): ONE merged group holds every pair of the tile, so the workgroup that piles it up
 // has the tile's coverage and allele totals in its LDS bins and applies snpCall's gates and calling rule itself (kernels.hip:
 // fused_tile_gate); what the gate kernel then reads of such a tile is this record list instead of ~19 KB of per-position state.
 constexpr uint32_t STAGE_CAP = 24;           // candidate positions of one tile kept here; a tile with more sends the dataset back to the unfused path
@@ -74,7 +74,7 @@ struct StageRec { uint32_t pos_flags, cov, nword, pad; };      // position in th
                                                                // coverage; mismatching A, C, G, T totals, one byte each (< 256: the group's depth bound)
 struct TileStage { uint32_t count, pad[3]; StageRec rec[STAGE_CAP]; };
 constexpr uint32_t WORK_FUSED = 8u;          // WorkItem::part_lo bit: whole-tile item (bit 0: u8 partial row, bits 1-2: allele-total mode)
-constexpr uint32_t MERGE_MAX_PAIRS = 256;    // pairs per merged group of shallow (sample, tile) pairs (pack.cpp; kernels.hip: msnv_pileup_tiles_merged)
+constexpr uint32_t MERGE_MAX_PAIRS = 256;    // pairs per merged group of shallow (sample, tile) pairs (finalize.cpp; kernels.hip: msnv_pileup_tiles_merged)
 constexpr uint32_t MERGE_MAX_DEPTH = 240;    // their depth bounds add up to at most this (byte bins)
 constexpr int COV_PW = 4;                    // (tile, sample) pairs per wavefront of msnv_coverage_tiles
 constexpr uint32_t COV_ITEM_PAIRS = 4;       // pairs per coverage work item (one wavefront x COV_PW)
@@ -105,9 +105,9 @@ struct SampleCols {
     std::vector<int32_t>  tid;       // per read
     std::vector<int32_t>  end;       // per read: contig-relative end of everything the kernels may touch
     std::vector<uint16_t> depth;     // per read: pileup reads alive when this one starts (saturating)
-    std::vector<uint16_t> grp;       // per piece: 0, or 1 + group of a deep (contig, tile) run that was split (pack.cpp: split_deep_runs)
+    std::vector<uint16_t> grp;       // per piece: 0, or 1 + group of a deep (contig, tile) run that was split (finalize.cpp: split_deep_runs)
     std::vector<uint8_t>  seq, qual;
-    // dense layout (pack.cpp: relayout_dense): per (contig, tile) run of pieces a stream of 32-base blocks
+    // dense layout (finalize.cpp: relayout_dense): per (contig, tile) run of pieces a stream of 32-base blocks
     std::vector<uint32_t> blk;            // one descriptor per block (BLK_* fields)
     std::vector<uint32_t> run_blk_lo, run_nblk, run_seq0;   // per run, in run order: first block, block count, seq byte offset
     std::vector<int32_t>  cov_tid, cov_beg, cov_end;   // qaCompute M intervals (index space), reads that pass its filter
@@ -180,7 +180,7 @@ struct DevPackTables {
 struct msnv_dataset;
 namespace msnv {
 // ---- the host stages over a dataset
-// pack.cpp: the per-read stage on host threads, the qualities as the pileup engine sees them, the tile index + upload, a stream dealt by contig owner
+// pack.cpp: the per-read stage on host threads, the qualities as the pileup engine sees them, a stream dealt by contig owner; finalize.cpp: the tile index + upload
 int pack_sample(const msnv_dataset &ds, const uint8_t *rec, uint64_t n_bytes, SampleCols &sc);
 int pileup_qualities(const msnv_dataset &ds, const uint8_t *rec, uint64_t n_bytes, uint8_t *out);
 int finalize_dataset(msnv_dataset &ds);

@@ -12,7 +12,7 @@ namespace msnv {
 
 struct Pair32 { uint32_t x, y; };
 // DeviceCols::tile_nslots[] on the device: cells per site row of the tile (<= 16 384 + padding) and, in the top bit, "some sample of the tile
-// was split into several pairs": only there can two allele events meet in one cell (pack.cpp sets it, the scatter half of the tail reads it)
+// was split into several pairs": only there can two allele events meet in one cell (finalize.cpp: slots sets it, the scatter half of the tail reads it)
 constexpr uint32_t NSLOTS_SPLIT = 1u << 31, NSLOTS_MASK = NSLOTS_SPLIT - 1u;
 struct MergedGroupDev { uint64_t hdr_base; uint32_t tile, pair_lo, n_pairs, n_pieces; };   // one merged group of shallow pairs (gather_merged_block): its
                                                                                         // headers in hdr8m, its pairs
@@ -44,7 +44,7 @@ int  dev_ann_upload(DeviceCols &d, const AnnHost &h);
 // Annotates the d.last_sites device site records; err_gpos[k] = UINT32_MAX when error kind k did not occur.
 int  dev_annotate(DeviceCols &d, uint32_t n_sites, uint32_t drop_gpos, void *stream, double *ms, uint32_t err_gpos[2]);
 
-// One descriptor per active tile for the gate kernels: everything they look up about their tile in one 64-byte load (pack.cpp builds them).
+// One descriptor per active tile for the gate kernels: everything they look up about their tile in one 64-byte load (finalize.cpp: partial_rows builds them).
 // staged: a whole-tile work item leaves the tile's candidates in a record list (then row0 = index of that list); pair_lo / n_plane_pairs:
 // the tile's pairs that write allele planes
 struct GateTile { uint32_t tile, slot_lo, slot_16, slot_w, slot_hi, vbeg, vend, n_slots; uint64_t row0; uint32_t tot_mode, staged, pair_lo, n_plane_pairs, pad0, pad1; };
@@ -56,7 +56,7 @@ struct PassBufs {
     uint32_t *tot = nullptr;         // [4][n_tiles*TILE]: mismatching A, C, G, T summed over samples
     uint8_t  *part = nullptr;        // coverage partial row of every work item (tile-major; u16 per position for narrow items, u32 for wide)
     uint8_t  *spill = nullptr;       // [n_pairs][TILE] per-sample coverage, saturating at 255
-    uint8_t  *aspill = nullptr;      // [n_pairs][4][TILE] per-sample mismatching A, C, G, T counts (allele planes: noisy reads, pack.cpp); else NULL
+    uint8_t  *aspill = nullptr;      // [n_pairs][4][TILE] per-sample mismatching A, C, G, T counts (allele planes: noisy reads, finalize.cpp: intermediates); else NULL
     Pair32   *events = nullptr;      // {gpos, sample<<18 | allele<<16 | count}
     Pair32   *overflow = nullptr;    // {gpos, sample<<16 | cov}
     uint32_t *counters = nullptr;    // two blocks of CNT_WORDS ([0] events [1] overflow [2] sites [4] pop lines [5] indiv lines, then the event
@@ -126,7 +126,7 @@ struct DeviceCols : PassBufs {
     uint32_t  n_work_fused = 0;      // the last n_work_fused merged work items are whole-tile items
     uint32_t  n_fused_tiles = 0;     // tiles handled by whole-tile work items
     bool      fuse_disabled = false; // the passes of this dataset do not use the record lists (tests, experiments)
-    int       qlow_cutoff = 0;       // the -Q cutoff the one-bit quality column was packed with (pack.cpp: pack_lowq); a pass must ask for the same
+    int       qlow_cutoff = 0;       // the -Q cutoff the one-bit quality column was packed with (finalize.cpp: pack_lowq); a pass must ask for the same
     uint32_t  last_ovf_tiles = 0;    // whole-tile work items of the last pass whose candidates did not fit a record list (their tiles took the unfused route)
     bool      wide_tot = false;      // some tile's allele totals need 32 bits per allele (tot_add mode 2): the gate kernel's wide instantiation
     bool      use_dirty = false;     // sparse cohort (few work items per tile): the gate kernel consults tile_dirty before it reads the allele totals

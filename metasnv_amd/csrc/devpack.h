@@ -22,7 +22,7 @@ int devpack_sync_pending(msnv_dataset &ds);
 void devpack_ctx_release(msnv_ctx *ctx);                         // the context's pinned words (msnv_ctx_destroy)
 int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *streams, const uint64_t *n_bytes, int n, bool on_device, const uint8_t *in_place_base = nullptr, uint64_t in_place_capacity = 0);
 // A device-packed sample's bases and quality flags as host staging (SampleCols::seq / qual), for the two re-layouts that still run on
-// the host (pack.cpp: relayout_dense, split_deep_runs' relocation).
+// the host (finalize.cpp: relayout_dense, split_deep_runs' relocation).
 int devpack_sample_to_host(SampleCols &sc);
 int devpack_download_pieces(msnv_dataset &ds);
 void devpack_release(msnv_dataset &ds);                       // the pack's tables, round buffers, work buffers; the pinned block back to the context
@@ -35,11 +35,11 @@ int devpack_fill_padding(DeviceCols &d, const std::vector<uint8_t> &sample_on_de
 struct DevMergedSrc { uint32_t pair, in_group; unsigned long long h_base; };   // a pair of a merged group: its index in the group, first slot of its headers in hdr8m
 struct DevCovPair { uint32_t tile, sample, lo, hi; };                            // intervals [lo, hi) of `sample` (kept ones, sample-relative) may touch `tile`
 int devfin_overhang(msnv_dataset &ds, std::vector<int64_t> &maxend);
-// deep (sample, tile) runs (pack.cpp: split_deep_runs) on the device: exact depth of every run whose bound reaches split_at, runs that are
+// deep (sample, tile) runs (finalize.cpp: split_deep_runs) on the device: exact depth of every run whose bound reaches split_at, runs that are
 // really that deep dealt round robin into groups of pieces that each stay below the byte bins' limit; the sample's headers are permuted group
 // by group and its columns re-laid in header order.  Updates SampleCols::dev_pairs.  *fallback: a run needs more groups than the kernel holds.
 int devfin_deep_runs(msnv_dataset &ds, uint32_t split_at, uint32_t group_depth, bool *fallback);
-// pack.cpp: relayout_dense for device-packed samples: every sample's columns as dense block streams, its descriptors (d_blk) and run_* tables
+// finalize.cpp: relayout_dense for device-packed samples: every sample's columns as dense block streams, its descriptors (d_blk) and run_* tables
 int devfin_dense(msnv_dataset &ds);
 // msnv_records_deal_device (msnv.h): pack.cpp's records_partition for several streams at once, on the device
 int records_deal_device(msnv_ctx *ctx, const uint8_t *const *streams, const uint64_t *n_bytes, int n, bool on_device, const int32_t *owner, int n_contigs, int n_parts,

@@ -2866,14 +2866,6 @@ int Prim::sort64(unsigned long long *kin, unsigned long long *kout, uint32_t *vi
 namespace {
 constexpr int TO_CAREFUL = -1;      // a stage's verdict beside MSNV_OK and the error codes: the careful route has to take this round
 
-// the packed FASTA of the selected contigs is built by the first round, on a thread of its own BESIDE the round's first kernels, which
-// do not read it (round 5: 0.4 ms in front of them); the emit kernels do
-struct TablesJob {
-    std::thread th; int rc = MSNV_OK; std::string msg;
-    int join() { if (th.joinable()) th.join(); if (rc) return fail(rc, "%s", msg.c_str()); return MSNV_OK; }
-    ~TablesJob() { if (th.joinable()) th.join(); }
-};
-
 // Everything one call of devpack_add_round works on.  The stages are member functions; each says what it takes and what it leaves.  Host
 // words that an asynchronous copy reads or writes are members here (or lie in the dataset's pinned block) unless the function that queues
 // the copy also waits for it: no stage leaves a copy in flight into its own frame.
@@ -2882,7 +2874,9 @@ struct Round {
     msnv_dataset &ds; DevPackTables &T; const msnv_params &MP;
     const size_t first; const uint8_t *const *const streams; const uint64_t *const n_bytes; const size_t S, NC; const bool on_device; const uint8_t *const in_place_base;
     const hipStream_t st; DpParams P{}; const DpContig *ctg = nullptr;
-    Timer tm; TablesJob tables;
+    // the packed FASTA of the selected contigs is built by the first round, on a thread of its own BESIDE the round's first kernels, which
+    // do not read it (round 5: 0.4 ms in front of them); the emit kernels do
+    Timer tm; ThreadJob tables;
     // work buffers of the round: taken from the dataset's pool in call order (BufPool: grow-only, so a dataset's second round allocates nothing;
     // with guarded allocations -- MSNV_GUARD_ALLOC=1 -- every buffer is exact and fresh); rocPRIM's storage is one slot of it
     BufPool pool; Prim prim; size_t pool_staged = 0;
@@ -2922,7 +2916,7 @@ struct Round {
           st((hipStream_t)ds_.ctx->stream), tm(st), pool{T.scratch}, prim(st), ss(S), acc(S), cut_marks(S, 0), host_sample(S, 0), sum(S + 1), piece_bytes(S) {
         if (!T.ready) {
             const int device = ds.ctx->device;
-            msnv_dataset *d = &ds; TablesJob *job = &tables;
+            msnv_dataset *d = &ds; ThreadJob *job = &tables;
             tables.th = std::thread([d, job, device]() {
                 (void)hipSetDevice(device);
                 try { job->rc = build_tables(*d); } catch (const std::exception &e) { job->rc = fail_quiet(MSNV_ENOMEM, "device pack tables: %s", e.what()); }

@@ -94,7 +94,7 @@ inline bool debug_sync() { static const bool on = present("MSNV_DEBUG_SYNC"); re
 // MSNV_NO_ADOPT (present): a single round's columns are copied, not adopted.  Per dataset (tests/test_gpu_finalize_routes.py::test_per_read_stage_knob).
 inline bool no_adopt() { return present("MSNV_NO_ADOPT"); }
 
-// ---------------------------------------------------------------------------------- finalize: layout and deep runs (pack.cpp)
+// ---------------------------------------------------------------------------------- finalize: layout and deep runs (finalize.cpp)
 // MSNV_LAYOUT=pieces|dense: 'p' / 'd' force the per-piece / the dense block layout; '\0' = by the mean piece length.  Per dataset
 // (tests/test_gpu_devpack.py, test_gpu_finalize_routes.py).
 inline char layout() { const char c = first("MSNV_LAYOUT"); return c == 'p' || c == 'd' ? c : '\0'; }
@@ -114,7 +114,7 @@ inline bool dense_relayout_on_host() { return first("MSNV_DENSE_RELAYOUT") == 'h
 // MSNV_FILL_PADDING (present): the padding nibbles by finalize's kernel although the emit kernels left them.  Per dataset (tests/test_gpu_devpack.py).
 inline bool fill_padding() { return present("MSNV_FILL_PADDING"); }
 
-// ---------------------------------------------------------------------------------- finalize: work items (pack.cpp)
+// ---------------------------------------------------------------------------------- finalize: work items (finalize.cpp)
 // MSNV_SHALLOW_PIECES (48, at least 0): pieces up to which a pair is merged into a group, 0 = never.  Per dataset (tests/test_gpu_parity.py).
 inline uint32_t shallow_pieces() { return (uint32_t)std::max(0, int_or("MSNV_SHALLOW_PIECES", 48)); }
 // MSNV_MERGE_ALWAYS=1: merge even when the shallow pairs hold < 3 % of the pieces.  Per dataset (tests/test_gpu_devpack.py, test_gpu_parity.py).
@@ -144,12 +144,12 @@ inline char alleles() { const char *e = getenv("MSNV_ALLELES"); return !e ? '\0'
 // list.  Per dataset (tests/test_gpu_parity.py forces the grow-and-rerun path).
 inline uint32_t cap_events(uint32_t by_dataset, long long min_events) { long long v = 0; return i64_of("MSNV_CAP_EVENTS", &v) ? (uint32_t)std::max(min_events, v) : by_dataset; }
 
-// ---------------------------------------------------------------------------------- finalize: the coverage index (pack.cpp, devpack.hip)
+// ---------------------------------------------------------------------------------- finalize: the coverage index (finalize.cpp, devpack.hip)
 // MSNV_COV_INDEX=sort|dense: 'd' the dense table / 's' the sort form whatever the dataset's size; '\0' = by size.  Per dataset
 // (tests/test_gpu_finalize_routes.py::test_coverage_index_route).
 inline char cov_index() { const char c = first("MSNV_COV_INDEX"); return c == 'd' || c == 's' ? c : '\0'; }
 // MSNV_COV_LATE (present): the dense table inside devfin_coverage, waiting, not launched ahead.  MSNV_COV_TABLES=host: pair tables, rows and
-// work items by pack.cpp's host loops.  MSNV_COV_THREAD (present): the host's tables on a helper thread (measured slower).  Per dataset
+// work items by finalize.cpp's host loops (coverage_tables).  MSNV_COV_THREAD (present): the host's tables on a helper thread (measured slower).  Per dataset
 // (tests/test_gpu_finalize_routes.py::test_coverage_index_route).
 inline bool cov_late() { return present("MSNV_COV_LATE"); }
 inline bool cov_tables_on_host() { return first("MSNV_COV_TABLES") == 'h'; }

@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <map>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/msnv.h"
@@ -17,6 +18,14 @@ namespace msnv {
 int  fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 int  fail_quiet(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));   // sets the message, prints nothing
 void clear_error();
+
+// A job on a thread beside its caller (devpack.hip: the first round's pack tables; finalize.cpp: the coverage tables): the thread leaves its
+// return code and, when it failed, its own thread's error message; join() hands both to the caller's thread.  Joins when it goes out of scope.
+struct ThreadJob {
+    std::thread th; int rc = MSNV_OK; std::string msg;
+    int join() { if (th.joinable()) th.join(); if (rc) return fail(rc, "%s", msg.c_str()); return MSNV_OK; }
+    ~ThreadJob() { if (th.joinable()) th.join(); }
+};
 
 // ---------------------------------------------------------------------------------- host-stage timers (msnv.h: msnv_host_timers)
 // Cumulative microseconds since the library was loaded (or the last reset), summed over the host threads that did the work:

@@ -10,7 +10,11 @@ import bamtools as bt
 from metasnv_amd import core
 from parity import run_oracle, first_diff
 
-COLUMNS = ["hdr", "hdr4", "hdr8m", "blk", "seq", "qual", "s_read_base", "s_seq_base", "ref4", "pairs", "work", "chunks", "cov_iv", "cov_pairs", "cov_work"]
+COLUMNS = ["hdr", "hdr4", "hdr8m", "blk", "seq", "qual", "s_read_base", "s_seq_base", "ref4", "pairs", "work", "chunks", "cov_iv", "cov_pairs", "cov_work",
+           # the rest of what finalize uploads (csrc/finalize.cpp; a table the layout does not allocate holds 0 bytes)
+           "ref_lc", "tile_vbeg", "tile_vend", "tile_nslots", "active_tiles", "gather_tiles", "tile_slot_start", "tile_slot_u16", "tile_slot_wide", "slot_off",
+           "gate_tiles", "gate_tiles_dense", "gate_tiles_staged", "tile_stage_idx", "merged_groups", "tile_pair_start", "tile_pair_merged",
+           "s_cov_base", "tile_len", "tile_contig_dev"]
 
 
 class _env:
@@ -66,7 +70,7 @@ def _build(where, names, lengths, seqs, samples, bed=None, params=None, many=Fal
 def _same_dataset(names, lengths, seqs, samples, bed=None, params=None, many=False, device_ptrs=False, check_oracle=True, finalize=None, stats=None):
     """stats: a dict that receives the device-packed dataset's pack_stats() (which route its per-read stage took).
     finalize: None = the tile index of the device-packed dataset is built in HBM where it can be (devfin_*), "host" = its headers come
-    down and the host loops of finalize_dataset build it."""
+    down and the host loops of finalize_dataset (csrc/finalize.cpp) build it."""
     ch, dh, ih = _build("host", names, lengths, seqs, samples, bed, params)
     cd, dd, idv = _build("device", names, lengths, seqs, samples, bed, params, many=many, device_ptrs=device_ptrs, finalize=finalize)
     try:

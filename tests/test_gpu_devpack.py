@@ -44,9 +44,9 @@ def test_sparse_cohort_and_merged_groups_same_columns():
 
 
 def test_deep_runs_are_dealt_into_groups_and_short_reads_into_block_streams_on_the_device():
-    """(sample, tile) runs deeper than the byte bins hold (pack.cpp: split_deep_runs): exact sweep, round-robin groups, header permutation and
+    """(sample, tile) runs deeper than the byte bins hold (finalize.cpp: split_deep_runs): exact sweep, round-robin groups, header permutation and
     the re-layout of the sample's columns run as kernels (devpack.hip: devfin_deep_runs) and give the host stage's bytes; so does the dense
-    block layout of short reads (pack.cpp: relayout_dense; devpack.hip: devfin_dense) -- descriptors, columns and run tables."""
+    block layout of short reads (finalize.cpp: relayout_dense; devpack.hip: devfin_dense) -- descriptors, columns and run tables."""
     syn, samples = synth_case(n_species=1, contig_len=4000, n_samples=3, mean_cov=300.0, sigma_cov=0.3, snv_density=0.02, seed=27)      # runs deeper than 192: dealt into groups
     _same_dataset(syn.names, syn.lengths, syn.seqs, samples)
     with _env(MSNV_PACK="device"):
@@ -88,6 +88,49 @@ def test_many_streams_one_round_and_device_pointers():
     syn, samples = synth_case(n_species=2, contig_len=7000, n_samples=12, mean_cov=8.0, snv_density=0.02, seed=22)
     _same_dataset(syn.names, syn.lengths, syn.seqs, samples, many=True)
     _same_dataset(syn.names, syn.lengths, syn.seqs, samples, device_ptrs=True, check_oracle=False)
+
+
+def test_mixed_dataset_same_as_host(tmp_path):
+    """A dataset of host-packed and device-packed samples (MSNV_PACK is read per add call): finalize brings the device-packed samples' pieces
+    down and takes its host loops (finalize.cpp: decide_route), their columns are copied HBM to HBM (devpack_copy_columns) and their padding
+    is filled by the kernel's per-sample form (devpack_fill_padding).  Against the same four samples all packed on the host: every index
+    table and column byte for byte, the per-sample statistics, the calls -- and those against the oracle.  One contig of 5000 bases: tile
+    seams at 2048 and 4096."""
+    syn, samples = synth_case(n_species=1, contig_len=5000, n_samples=4, mean_cov=8.0, read_len=100, snv_density=0.02, frac_absent=0.0, seed=35)
+    assert list(syn.lengths) == [5000] and all(s.size for s in samples)
+    ch, dh, ih = _build("host", syn.names, syn.lengths, syn.seqs, samples)
+    cm = core.Context(0)
+    dm = core.Dataset(cm, syn.names, syn.lengths, syn.seqs)
+    try:
+        for i, s in enumerate(samples):
+            with _env(MSNV_PACK="host" if i % 2 == 0 else "device"):
+                dm.add_sample_records(s)
+        im = dm.finalize()
+        st = dm.pack_stats()
+        assert 0 < st["pieces"] < im["n_reads"], (st, im)            # some pieces were cut on the device, not all
+        for k in ("n_reads", "n_reads_pileup", "n_pileup_bases", "bytes_headers", "bytes_cigar", "bytes_seq", "bytes_qual", "n_tiles", "n_pairs", "n_work",
+                  "allele_planes", "sampled_mismatch_ppm"):
+            assert ih[k] == im[k], (k, ih[k], im[k])
+        assert im["n_tiles"] == 3
+        for col in COLUMNS:
+            a, b = dh.column(col), dm.column(col)
+            assert a.size == b.size, (col, a.size, b.size)
+            assert np.array_equal(a, b), (col, int(np.flatnonzero(a != b)[0]))
+        for s in range(len(samples)):
+            assert np.array_equal(dh.sample_stats(s), dm.sample_stats(s)), s
+        assert dh.first_line() == dm.first_line()
+        dh.run(); dm.run()
+        out = []
+        for ds in (dh, dm):
+            pp, ip = str(tmp_path / "c"), str(tmp_path / "i")
+            ds.write_calls(pp, ip)
+            out.append((open(pp).read(), open(ip).read()))
+        assert out[0] == out[1]
+        orac = run_oracle(syn.names, syn.lengths, syn.seqs, samples)
+        assert out[1][0] == orac[0] and out[1][1] == orac[1]
+        assert out[1][0].count("\n") > 0
+    finally:
+        dh.close(); dm.close(); ch.close(); cm.close()
 
 
 def test_bed_split_and_thresholds():

@@ -144,7 +144,7 @@ def test_two_three_and_four_alleles_at_one_position_of_one_sample(min_snvs):
 
 def test_sample_split_into_several_pairs_of_a_tile(monkeypatch):
     """Sample 0 is 40 deep: with MSNV_SPLIT_AT=32 and MSNV_GROUP_DEPTH=16 its run is dealt round robin, in start order, into 40 / 16 + 1 = 3
-    pairs of the tile (pack.cpp: split_deep_runs).  Two reads of an allele land in two pairs, one each -- below the threshold in every
+    pairs of the tile (finalize.cpp: split_deep_runs).  Two reads of an allele land in two pairs, one each -- below the threshold in every
     pair, reached in sum: the position goes the unc_bits route and is decided from the per-sample records (msnv_decide_sites); six reads
     land two per pair: the ind4 mark from split pairs.  Every pair writes its own events, so the pass's count is the oracle's triples with a
     split sample's triple counted once per pair that holds it (worked out here from the dealing rule)."""

@@ -1,6 +1,6 @@
 """finalize's routes, each against the oracle and against the default route (KERNELS.md knobs).
 
-Coverage index (devpack.hip: devfin_coverage_launch / devfin_coverage, pack.cpp: cov_index).  The routes and what is compared:
+Coverage index (devpack.hip: devfin_coverage_launch / devfin_coverage, finalize.cpp: coverage_tables).  The routes and what is compared:
   default          dense (sample, tile) table launched ahead, pair tables / rows / work items cut on the device (msnv_cov_*)
   tables_host      MSNV_COV_TABLES=host: the same runs, the pair tables by the host loops  -> cov_iv, cov_pairs, cov_work BYTE-identical
   late             MSNV_COV_LATE=1: the dense table built inside devfin_coverage, waiting   -> BYTE-identical (the same table, the host's pair
@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 from metasnv_amd import core
+from packsame import COLUMNS
 from parity import run_oracle, synth_case, first_diff
 
 pytestmark = pytest.mark.gpu
@@ -182,7 +183,7 @@ def _overflow_caps(tmp_path):
 
 
 def test_chunk_table_overflow_cuts_again_with_the_exact_count(tmp_path):
-    """MSNV_CHUNK_CAP below the narrow chunks' number: the device's cut overflows and finalize cuts again with the exact count (pack.cpp).
+    """MSNV_CHUNK_CAP below the narrow chunks' number: the device's cut overflows and finalize cuts again with the exact count (finalize.cpp: last_wait).
     The chunk, work item and pair tables are byte-identical to the default route's, calls and coverage equal the oracle (in the worker).
     A cap of exactly the count does not overflow.  The dense layout cuts its chunks on the host: the cap changes nothing there."""
     err0, z0 = _chunks(tmp_path, "chunks")
@@ -221,9 +222,6 @@ def test_knobs_read_once_per_process(env, tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ per-read stage knobs (read per call)
-COLUMNS = ["hdr", "hdr4", "hdr8m", "blk", "seq", "qual", "s_read_base", "s_seq_base", "ref4", "pairs", "work", "chunks", "cov_iv", "cov_pairs", "cov_work"]
-
-
 def _build_cols(syn, samples, params, one_round=False):
     ctx = core.Context(0)
     ds = core.Dataset(ctx, syn.names, syn.lengths, syn.seqs, params)

@@ -376,7 +376,7 @@ def test_merged_groups_of_shallow_pairs(shallow_pieces, monkeypatch):
 @pytest.mark.parametrize("fuse,lean", [("1", "1"), ("1", "0"), ("0", "1")])
 def test_whole_tile_work_items(fuse, lean, monkeypatch):
     """Sparse cohorts: a tile whose pairs fit one merged group is piled up by ONE workgroup, which applies the gates and the calling
-    rule itself and leaves a record list for the gate kernel (kernels.hip: fused_tile_gate; pack.cpp: fuse_tile).  MSNV_FUSE=1 forces
+    rule itself and leaves a record list for the gate kernel (kernels.hip: fused_tile_gate; finalize.cpp: pair_classes, fuse_tile).  MSNV_FUSE=1 forces
     the path on cohorts of any shape, 0 switches it off.  Round 6: a whole-tile item of one chunk costs what its pieces cost, not what 2 048
     positions cost (msnv_pileup_tiles_lean: allele bins only, the candidates' coverage counted from the pieces in the registers); MSNV_LEAN=0
     sends the items through the ordinary body.  Same bytes as the oracle for (a) a sparse cohort with a lower-case
@@ -489,7 +489,7 @@ def test_gate_kernel_with_several_tiles_per_workgroup(gate_tiles, monkeypatch):
 @pytest.mark.parametrize("layout", ["pieces", "dense"])
 @pytest.mark.parametrize("tot_mode", ["0", "1", "2"])
 def test_allele_total_modes(tot_mode, layout, monkeypatch):
-    """The allele totals of a tile are as narrow as its summed depth bound allows (pack.cpp: 4 bytes in one word per position,
+    """The allele totals of a tile are as narrow as its summed depth bound allows (finalize.cpp: partial_rows; 4 bytes in one word per position,
     2 x u16 in two words, or four words; kernels.hip tot_add / msnv_gate_sites).  An uneven cohort has tiles of the first two
     kinds (a few shallow samples here, a deep one there, one sample deep enough for the wide kernel); MSNV_TOT_MODE raises the
     narrowest mode allowed so that every width runs on every tile.  Same bytes as the oracle each time, two passes per dataset
@@ -1437,7 +1437,7 @@ def test_randomised_parity_sweep(monkeypatch):
 
 
 def test_randomised_parity_sweep_with_allele_planes(monkeypatch):
-    """The same sweep with the allele bookkeeping of noisy reads forced on (MSNV_ALLELES=planes, pack.cpp): every (sample, tile) pair of
+    """The same sweep with the allele bookkeeping of noisy reads forced on (MSNV_ALLELES=planes, finalize.cpp: intermediates): every (sample, tile) pair of
     an ordinary work item writes its mismatching A / C / G / T counts as four byte planes, the gate kernel sums the planes, the gather
     transposes them into the cells -- no total atomics, no events.  Other seeds than the sweep above."""
     import fuzz_parity

@@ -1,7 +1,7 @@
 """The tail of a pass -- msnv_gather_scatter's two halves -- at the smallest shapes where its forms can go wrong, against the oracle.
 
 Scatter half: an allele event lands with a plain two-byte store where its cell has one writer and with an atomic add in tiles that hold a
-split sample (pack.cpp marks those in tile_nslots); its loop takes four events per trip, the last trip with fewer.  Gather half: tiles
+split sample (finalize.cpp: slots marks those in tile_nslots); its loop takes four events per trip, the last trip with fewer.  Gather half: tiles
 with fewer than 32 sites per workgroup deal their threads as pair lanes x site lanes.  Pileup kernel: the events of a thread's eight
 positions are counted with a masked byte SAD.
 
