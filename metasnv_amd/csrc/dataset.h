@@ -89,7 +89,7 @@ static_assert(sizeof(WorkItem) == 64, "work items are loaded as four 16-byte wor
 struct SiteRec { uint32_t gpos, cov, n[4]; };                          // gate kernel output (24 B)
 
 // What a round of the device pack leaves in HBM besides the columns: its piece headers (tile order, positions still contig-relative) and
-// qaCompute intervals, sample after sample.  finalize builds the tile index from them on the device (devpack.hip: devfin_*); the host sees
+// qaCompute intervals, sample after sample.  finalize builds the tile index from them on the device (devfin.hip: devfin_*); the host sees
 // one DevPair per (sample, contig, tile) run of pieces.
 struct DevRound { void *buf = nullptr; ReadHdr *hdr = nullptr; int32_t *tid = nullptr, *end = nullptr; uint16_t *depth = nullptr;
                   int32_t *cov_tid = nullptr, *cov_beg = nullptr, *cov_end = nullptr; uint64_t n_pieces = 0, n_iv = 0; size_t first_sample = 0;
@@ -125,7 +125,7 @@ struct SampleCols {
     bool     dev_index = false;                       // headers and intervals are still in HBM only (DevPackTables::rounds): hdr / tid / end / depth / cov_* above are empty
     int32_t  dev_round = -1;                          // ... in that round, from these offsets
     uint64_t dev_piece0 = 0, dev_iv0 = 0, n_dev_pieces = 0, n_dev_iv = 0;
-    uint32_t *d_blk = nullptr; uint64_t n_dev_blk = 0;  // dense layout: its block descriptors in HBM (devpack.hip: devfin_dense)
+    uint32_t *d_blk = nullptr; uint64_t n_dev_blk = 0;  // dense layout: its block descriptors in HBM (devfin.hip: devfin_dense)
     std::vector<DevPair> dev_pairs;                   // its (contig, tile) runs of pieces, in order
     msnv_sample_stats st{};          // qaCompute "Other" statistics (qaCompute.cpp:642-654), counted over every record of the BAM
 };
@@ -152,16 +152,25 @@ struct DevPackTables {
     // needs the round finished calls first (the next round, finalize before it decides the allele bookkeeping, the statistics, release)
     struct Pending { bool active = false; size_t first = 0, n = 0; void *ev0 = nullptr, *ev1 = nullptr, *evh = nullptr, *evd = nullptr, *evd2 = nullptr, *evw = nullptr; bool has_evd = false; } pending;      // evd / evd2: around the depth stage on the second stream; evw: the records' tables are written      // evh: behind the small results the host takes while the emit kernels run
     bool      any_overhang_h = false; // some read of some round runs past its contig (msnv_measure_reads): finalize fetches `overhang`
-    void     *cov_event = nullptr;   // recorded behind those kernels: what devfin_coverage waits for
-    // (round 6) the coverage index's pair tables cut on the device: the work memory of their counts, what the second step reads of it
-    struct CovT { uint32_t *tcont, *rid_t, *rowid, *row_sample, *row_contig, *item_off, *lo, *hi; unsigned long long *iv_start; };
-    void     *cov_tables = nullptr; CovT cov_t{}; uint32_t cov_item_intervals = 16384; bool cov_tables_done = false;
-    void     *fin_chunk_event = nullptr; bool fin_chunk_pending = false;      // behind the words devfin_chunks_launch's kernels leave in pinned memory
-    void     *cov_job = nullptr, *cov_tmp = nullptr, *cov_runs = nullptr; bool cov_launched = false;   // finalize: the coverage index's kernels launched ahead of their results (devfin_coverage_launch)
-    void     *fin_tile_base = nullptr;                     // finalize on the device: the contigs' first tiles (devfin_headers)
-    void     *fin_list = nullptr, *fin_cbase = nullptr;   // finalize on the device: the narrow pairs' list and their chunk counts / scan, between devfin_chunk_counts and devfin_chunk_fill
-    std::vector<void *> fin_keep;                          // small device tables of finalize's kernels, which are queued, not waited for: freed with the pack's tables (devpack_finish)
-    uint64_t  fin_chunk_cap = 0; uint32_t fin_chunk_base = 0; bool fin_chunks_async = false;   // the narrow chunks cut without a wait (devfin_chunks_launch): room for them in d.chunks, where they start
+    // Finalize's device state (devfin.hip), grouped by the stage that fills it; released by devfin_release, from devpack_release.
+    struct Fin {
+        // ---- the coverage index launched ahead of its results (devfin_coverage_launch -> devfin_coverage)
+        bool  cov_launched = false;                              // ... and not collected yet
+        void *cov_event = nullptr;                               // recorded behind those kernels: what devfin_coverage waits for
+        void *cov_job = nullptr, *cov_tmp = nullptr, *cov_runs = nullptr;   // the job's one block, rocPRIM's work memory, the (sample, tile) runs inside the block
+        // (round 6) the pair tables cut on the device: the work memory of their counts, what the second step reads of it
+        struct CovT { uint32_t *tcont, *rid_t, *rowid, *row_sample, *row_contig, *item_off, *lo, *hi; unsigned long long *iv_start; };
+        void *cov_tables = nullptr; CovT cov_t{}; uint32_t cov_item_intervals = 16384;
+        bool  cov_tables_done = false;                           // devfin_coverage wrote the pair tables, rows and work items in HBM
+        // ---- the narrow chunks cut without a wait (devfin_chunks_launch -> devfin_chunks_result): room for them in d.chunks, where they start
+        uint64_t chunk_cap = 0; uint32_t chunk_base = 0; bool chunks_async = false;
+        void *chunk_event = nullptr; bool chunk_pending = false; // behind the words the cut's kernels leave in pinned memory
+        void *list = nullptr, *cbase = nullptr;                  // the narrow pairs' list and their chunk counts / scan, between devfin_chunk_counts and devfin_chunk_fill
+        // ---- small device tables of finalize's kernels, which are queued, not waited for: freed with the pack's tables (devpack_finish)
+        void *tile_base = nullptr;                               // the contigs' first tiles (devfin_headers)
+        const void *sample_hdr = nullptr;                        // every sample's headers where its round left them, built at a finalize's first use (one of `keep`)
+        std::vector<void *> keep;
+    } fin;
     // pinned words of THIS dataset (taken from its context's pool, given back by devpack_release): first half = what a round's last kernels
     // leave for the host (DpAcc per sample: devpack_sync_pending), second half = finalize's small results (coverage index, chunk count)
     void     *pin = nullptr; uint64_t pin_cap = 0;

@@ -1,4 +1,5 @@
-// metasnv_amd/csrc/devpack.hip -- the per-read stage as device kernels: raw BAM alignment records in HBM -> packed read columns.
+// metasnv_amd/csrc/devpack.hip -- the per-read stage as device kernels: raw BAM alignment records in HBM -> packed read columns; and the
+// device dealer (msnv_records_deal_device), which shares the record walk with it.
 //
 // What it replaces: the read loop of the reference's tools, per record -- flag / MAPQ / duplicate filter and the walk over the CIGAR's M
 // blocks of qaCompute (/root/reference/src/qaTools/qaCompute.cpp:441-593, the walk :530-552), and what `samtools mpileup` (call site
@@ -35,6 +36,12 @@
 // The sub-segment walk is written once for both routes and the dealer: sub_of / sub_at, guess_entry, scan_sub_body<Walk> and
 // scan_fix_body<Walk> over WalkPlain (offsets) or WalkMeasure (slots and sums), wave_records for the two write kernels; SubWalk on the host
 // (the walk's buffers, the seam loop).  AccAdd is what a record or a sub-segment adds to its sample's accumulators.
+// The dealer -- records_deal_device: scan_records, then msnv_deal_measure, a sort of the records by owner (msnv_deal_iota, msnv_deal_sizes),
+// msnv_deal_copy -- deals the records of several streams to their contigs' owners (pack.cpp: records_partition on the host).
+// Behind the round: devpack_sync_pending, the dataset's pinned block (pin_ensure), devpack_release, and the copies of a device-packed
+// sample to host staging (devpack_download_pieces, devpack_sample_to_host).  Finalize's device side is devfin.hip; what the two files share
+// -- HIP_TRY, DevBuf, BufPool, Prim, the device helpers of a piece's bytes -- is devwork.h, and the two kernels of the round that finalize's
+// deep-run split borrows are behind devpack_gather_pieces / devpack_emit_tail at the end of this file.
 #include <algorithm>
 #include <chrono>
 #include <cstdint>
@@ -43,26 +50,16 @@
 #include <thread>
 #include <vector>
 
-#include <hip/hip_runtime.h>
-#include <rocprim/rocprim.hpp>
-
-#include "device.h"
-#include "devpack.h"
+#include "devfin.h"
+#include "devwork.h"
 
 namespace msnv {
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return fail(MSNV_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 namespace {
 
-struct DpContig { long long len, seq_len, bed_beg, bed_end; unsigned long long pref_off; uint32_t sel, pad; };   // seq_len < 0: no FASTA record
 struct DpParams {
     int flag_filter, min_mapq, count_orphans, cov_min_mapq, max_depth, token_limit, ignore_overlaps;
-    int c_eff, all_low;            // the -Q cutoff as pack.cpp: pack_lowq applies it: flagged = all_low || quality < c_eff
+    int c_eff, all_low;            // the -Q cutoff as finalize.cpp: pack_lowq applies it: flagged = all_low || quality < c_eff
     int n_contigs, has_bed;
 };
 // per sample of the round
@@ -83,8 +80,6 @@ enum : uint8_t { RF_PILE = 1, RF_COV = 2, RF_MAPPED = 4, RF_OVL = 8 };      // R
 enum : uint32_t { NEED_CAP = 1, NEED_TOKEN = 2, NEED_OVL = 4, NEED_BIGC = 8 };      // NEED_OVL: too many alignments of one template wait at once for the device's slots; NEED_BIGC (with NEED_TOKEN):
                                                                                       // an element longer than the records' tables can say -- both are the host pre-pass's
 
-__device__ __forceinline__ uint32_t ld32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
-__device__ __forceinline__ uint64_t ld64(const uint8_t *p) { uint64_t v; __builtin_memcpy(&v, p, 8); return v; }
 
 // fixed part of an alignment record (SAM spec 4.2): block_size refID pos l_read_name mapq bin n_cigar_op flag l_seq next_refID next_pos tlen
 struct Rec {
@@ -143,8 +138,6 @@ __device__ __forceinline__ bool rec_mapped(uint32_t flag, int32_t tid) { return 
 __device__ __forceinline__ bool cg_ref(uint32_t t) { return t == C_M || t == C_D || t == C_N || t == C_EQ || t == C_X; }
 __device__ __forceinline__ bool cg_query(uint32_t t) { return t == C_M || t == C_I || t == C_S || t == C_EQ || t == C_X; }
 __device__ __forceinline__ bool cg_match(uint32_t t) { return t == C_M || t == C_EQ || t == C_X; }
-// seq bytes of a piece of n bases with its alignment padding (pack.cpp: pack_sample)
-__device__ __host__ __forceinline__ uint32_t stored_bytes(uint32_t n) { return ((n + 1u) / 2u + SEQ_ALIGN - 1u) & ~(SEQ_ALIGN - 1u); }
 
 __global__ __launch_bounds__(64) void msnv_acc_fold(DpAcc *acc, uint32_t n_samples) {       // one wavefront per sample, one lane per copy (ACC_COPIES = 64)
     const uint32_t s = blockIdx.x, c = threadIdx.x;
@@ -1510,12 +1503,6 @@ __global__ void msnv_ovl_groups(const uint32_t *starts, uint32_t n_groups, uint3
 }
 
 // ------------------------------------------------------------------------------------------ bases and quality flags
-// Pieces start on 4 bases, so a piece's flags start on bit 0 or 4 of a byte: whole bytes are stored, the two nibbles a piece shares with
-// its neighbours' bytes are OR-ed in atomically (the flag column is cleared first).
-__device__ __forceinline__ void or_byte(uint8_t *p, uint32_t v) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-    atomicOr(reinterpret_cast<uint32_t *>(a & ~(uintptr_t)3), v << (8u * (uint32_t)(a & 3u)));
-}
 // FOUR lanes per piece, 32 bases per lane (round 4; the first form took 16 lanes of 8 bases: 6.4 ms on the benchmark shape against 2.x here):
 // three 8-byte loads of BAM nibbles, four of phred bytes; 16 bytes of the seq column and 32 flags out.
 __device__ __forceinline__ uint64_t nib_swap64(uint64_t b) { return ((b >> 4) & 0x0f0f0f0f0f0f0f0full) | ((b & 0x0f0f0f0f0f0f0f0full) << 4); }
@@ -1524,41 +1511,6 @@ __device__ __forceinline__ uint32_t low_flags8(uint64_t q, uint32_t c) {
     const uint64_t y = (q | 0x8080808080808080ull) - 0x0101010101010101ull * c;            // bit 7 of a byte: (q & 0x7f) >= c; no borrow between bytes
     const uint64_t lt = ~(q | y) & 0x8080808080808080ull;
     return (uint32_t)(((lt >> 7) * 0x0102040810204080ull) >> 56);
-}
-__device__ __forceinline__ void store_bytes(uint8_t *p, uint64_t v, uint32_t n) {          // the n low bytes of v (n <= 8), any address
-    if (n >= 8u) { __builtin_memcpy(p, &v, 8); return; }
-    if (n & 4u) { const uint32_t w = (uint32_t)v; __builtin_memcpy(p, &w, 4); p += 4; v >>= 32; }
-    if (n & 2u) { const uint16_t w = (uint16_t)v; __builtin_memcpy(p, &w, 2); p += 2; v >>= 16; }
-    if (n & 1u) *p = (uint8_t)v;
-}
-// One lane's share of a piece into the columns: st stored nibbles (a multiple of 4) of lane `sub` (32 nibbles per lane), their flags in `bits`.
-__device__ __forceinline__ void put_piece_lane(uint8_t *seq_col, uint8_t *qual_col, uint32_t seqoff, uint32_t sub, uint32_t sb, uint32_t st, uint64_t o0, uint64_t o1,
-                                               uint32_t bits, uint32_t prev_last) {
-    // ---- seq column: st / 2 bytes
-    uint8_t *sp = seq_col + seqoff + 16u * sub;
-    const uint32_t nb = st >> 1;
-    store_bytes(sp, o0, nb < 8u ? nb : 8u);
-    if (nb > 8u) store_bytes(sp + 8, o1, nb - 8u);
-    // ---- flag column: bit index = nibble index of the seq column; the piece starts on bit 0 or 4 of a byte
-    const unsigned long long b0 = 2ull * seqoff + 32u * sub;
-    uint8_t *qp = qual_col + (b0 >> 3);
-    const bool last_lane = sub == ((2u * sb - 1u) >> 5);
-    const uint32_t v = st < 32u ? bits & ((1u << st) - 1u) : bits;
-    if (!(b0 & 4ull)) {
-        const uint32_t full = st >> 3;                                                  // whole bytes of mine
-        store_bytes(qp, v, full);
-        if (st & 4u) or_byte(qp + full, (v >> (8u * full)) & 0xfu);                     // a trailing nibble: the byte's other half is the next piece's (only the last lane ends on one)
-    } else if (sub == 0) {
-        or_byte(qp, (v & 0xfu) << 4);                                                   // the low nibble of the first byte is the previous piece's
-        const uint32_t rest = st - 4u, full = rest >> 3;
-        store_bytes(qp + 1, v >> 4, full);
-        if ((rest & 4u) && last_lane) or_byte(qp + 1 + full, (v >> (4u + 8u * full)) & 0xfu);      // (else lane 1 writes that byte with my nibble in it)
-    } else {
-        const uint64_t w = (uint64_t)v << 4 | (prev_last & 0xfu);                       // the byte I start in, whole: the lane before me left its last nibble there
-        const uint32_t total = st + 4u, full = total >> 3;
-        store_bytes(qp, w, full);
-        if ((total & 4u) && last_lane) or_byte(qp + full, (uint32_t)(w >> (8u * full)) & 0xfu);
-    }
 }
 
 // ------------------------------------------------------------------------------------------ headers, intervals, bases: one block of records per workgroup
@@ -1603,7 +1555,7 @@ template <class Src>
 __device__ __forceinline__ void piece_lane(const Src &src, unsigned long long seq_o, unsigned long long qual_o, uint32_t q0_piece, uint32_t j0, uint32_t have, unsigned long long ref_nib,
                                            uint32_t ref_left, const uint32_t *pref4, const DpParams &P, uint32_t cut_marks, bool sample_this, uint32_t pad_in_tile,
                                            uint64_t &o0, uint64_t &o1, uint32_t &bits, uint32_t &mm) {
-    const bool pad_low = P.c_eff > 0 || P.all_low;                                          // padding: base N, quality byte 0 (pack.cpp: pack_sample, pack_lowq)
+    const bool pad_low = P.c_eff > 0 || P.all_low;                                          // padding: base N, quality byte 0 (pack.cpp: pack_sample; finalize.cpp: pack_lowq)
     o0 = ~0ull; o1 = ~0ull; bits = pad_low ? 0xffffffffu : 0u; mm = 0;
     if (!have) return;
     const bool noseq = q0_piece == 0xffffffffu;
@@ -2092,51 +2044,7 @@ __global__ void msnv_pair_maxd(DevPairRec *recs, uint32_t n_pairs, uint32_t n_pi
     recs[p].maxd = m;
 }
 
-// ------------------------------------------------------------------------------------------ finalize: padding behind the pieces
-// The alignment padding behind a piece (up to the next 4 bases) reads as the reference the kernel compares it with, N beyond the tile
-// (pack.cpp: finalize_dataset; msnv_pileup_tiles_narrow32 masks mismatch flags per group of bases, not per base).
-__global__ void msnv_fill_padding(const ReadHdr *hdr, const unsigned long long *s_read_base, const unsigned long long *s_seq_base, const uint8_t *s_dev, uint32_t n_samples,
-                                  unsigned long long n_pieces, const uint32_t *ref4, uint8_t *seq) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_pieces) return;
-    uint32_t a = 0, b = n_samples;                       // sample of piece i: last s with s_read_base[s] <= i
-    while (b - a > 1) { const uint32_t m = (a + b) / 2; if (s_read_base[m] <= i) a = m; else b = m; }
-    if (s_dev && !s_dev[a]) return;                      // (nullptr: every sample was packed on the device)
-    const ReadHdr h = hdr[i];
-    const uint32_t len = h.cig, stop = (len + 2u * SEQ_ALIGN - 1u) & ~(2u * SEQ_ALIGN - 1u);
-    uint8_t *sp = seq + s_seq_base[a] + h.seqoff;
-    for (uint32_t j = len; j < stop; ++j) {
-        const unsigned long long g = (unsigned long long)h.gpos + j;
-        const uint32_t code = (h.gpos % TILE + j < TILE) ? (ref4[g >> 3] >> (4u * (uint32_t)(g & 7u))) & 0xfu : 0xfu;
-        const uint32_t sh = (j & 1u) * 4u;
-        sp[j >> 1] = (uint8_t)((sp[j >> 1] & ~(0xfu << sh)) | code << sh);
-    }
-}
-
 // ------------------------------------------------------------------------------------------ host side
-struct DevBuf {
-    void *p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { if (p) dev_free(p); }
-    int alloc(uint64_t bytes) { if (p) { dev_free(p); p = nullptr; } return dev_alloc(&p, bytes, nullptr); }
-    template <typename T> T *as() const { return static_cast<T *>(p); }
-    void *release() { void *q = p; p = nullptr; return q; }
-};
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-struct Timer {          // HIP events around a group of launches
-    hipEvent_t a = nullptr, b = nullptr; hipStream_t st;
-    explicit Timer(hipStream_t s) : st(s) { (void)hipEventCreate(&a); (void)hipEventCreate(&b); }
-    ~Timer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    void start() { (void)hipEventRecord(a, st); }
-    double stop() { (void)hipEventRecord(b, st); (void)hipEventSynchronize(b); float ms = 0; (void)hipEventElapsedTime(&ms, a, b); return ms; }
-};
-
-unsigned bit_width_u64(unsigned long long v) { unsigned b = 0; while (v) { ++b; v >>= 1; } return b; }
-inline dim3 grid_for(uint64_t n, uint32_t block) { return dim3((unsigned)std::max<uint64_t>(1, (n + block - 1) / block)); }
-
 // contig table (small: goes up at once, the record scan's walk reads it) ...
 int build_contigs(msnv_dataset &ds) {
     DevPackTables &t = ds.dp;
@@ -2225,8 +2133,9 @@ const char *err_text(uint32_t kind) {
 }  // namespace
 
 // The dataset's pinned block: at least `half` bytes in each of its two halves.  Taken from the context's pool (a fresh dataset of a context
-// that has built one before pins nothing); grown only while nothing is in flight into it.
-static int pin_ensure(msnv_dataset &ds, uint64_t half) {
+// that has built one before pins nothing); grown only while nothing is in flight into it.  The first half is a round's (DpAcc per sample);
+// the second is finalize's result words, sized ONCE per finalize by whichever stage uses them first (devfin.h: FinWords).
+int pin_ensure(msnv_dataset &ds, uint64_t half) {
     DevPackTables &T = ds.dp;
     if (T.pin && T.pin_cap / 2 >= half) return MSNV_OK;
     if (int rc = devpack_sync_pending(ds)) return rc;
@@ -2240,7 +2149,6 @@ static int pin_ensure(msnv_dataset &ds, uint64_t half) {
     T.pin_cap = want;
     return MSNV_OK;
 }
-static uint32_t *pin_fin_words(const DevPackTables &T) { return reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(T.pin) + T.pin_cap / 2); }
 
 int devpack_sync_pending(msnv_dataset &ds) {
     DevPackTables &T = ds.dp;
@@ -2271,12 +2179,10 @@ void devpack_release(msnv_dataset &ds) {
         (void)hipEventDestroy((hipEvent_t)t.pending.evd2); (void)hipEventDestroy((hipEvent_t)t.pending.evw);
         t.pending.ev0 = t.pending.ev1 = t.pending.evh = t.pending.evd = t.pending.evd2 = t.pending.evw = nullptr;
     }
-    if (t.cov_event) { (void)hipEventDestroy((hipEvent_t)t.cov_event); t.cov_event = nullptr; }
-    if (t.fin_chunk_event) { (void)hipEventDestroy((hipEvent_t)t.fin_chunk_event); t.fin_chunk_event = nullptr; t.fin_chunk_pending = false; }
-    if (t.cov_job || t.cov_tables || !t.fin_keep.empty()) (void)hipDeviceSynchronize();
     // everything of the pack goes back in ONE batch (one wait for the device instead of one per buffer: dev_free_batch)
     std::vector<void *> out;
     auto give = [&](void *p) { if (p) out.push_back(p); };
+    devfin_release(t.fin, out);                                     // (finalize's events, the wait for what it left queued, its buffers: devfin.hip)
     give(t.contigs); give(t.pref4); give(t.overhang);
     t.overhang = nullptr; t.any_overhang = nullptr;
     for (DevRound &r : t.rounds) give(r.buf);
@@ -2287,103 +2193,12 @@ void devpack_release(msnv_dataset &ds) {
     t.scratch.clear();
     t.contigs = nullptr; t.pref4 = nullptr; t.ready = false;
     std::vector<uint32_t>().swap(t.h_codes); std::vector<uint32_t>().swap(t.h_lc);
-    give(t.cov_job); t.cov_job = nullptr; t.cov_runs = nullptr;
-    give(t.cov_tables); t.cov_tables = nullptr;
-    give(t.cov_tmp); t.cov_tmp = nullptr;
-    t.cov_launched = false;
-    give(t.fin_tile_base); t.fin_tile_base = nullptr;
-    give(t.fin_list); give(t.fin_cbase);
-    t.fin_list = nullptr; t.fin_cbase = nullptr;
-    for (void *p : t.fin_keep) give(p);
-    t.fin_keep.clear();
     dev_free_batch(out);
     if (t.pin) {
         if (ds.ctx) ds.ctx->pin_pool.emplace_back(t.pin, t.pin_cap); else (void)hipHostFree(t.pin);
         t.pin = nullptr; t.pin_cap = 0;
     }
 }
-
-// Work buffers taken from a grow-only list in call order (a dataset's pool, or a caller's own list).  A failed allocation sticks: every
-// later take() returns NULL and `rc` says why, so a batch of takes is followed by ONE `if (pool.rc) return pool.rc;`.
-struct BufPool {
-    std::vector<std::pair<void *, uint64_t>> &slots;
-    size_t next = 0; int rc = MSNV_OK;
-    bool exact = knob::guard_alloc();
-    void *at(size_t i, uint64_t bytes) {                          // slot i, holding at least `bytes` (guarded allocations: exactly, and fresh)
-        if (rc) return nullptr;
-        std::pair<void *, uint64_t> &b = slots[i];
-        bytes = std::max<uint64_t>(bytes, 16);
-        if (b.second < bytes || (exact && b.second != bytes)) {
-            if (b.first) dev_free(b.first);
-            b.first = nullptr; b.second = 0;
-            const uint64_t want = exact ? bytes : bytes + bytes / 8;
-            if (int r = dev_alloc(&b.first, want, nullptr)) { rc = r; return nullptr; }
-            b.second = want;
-        }
-        return b.first;
-    }
-    void *get(uint64_t bytes) {
-        if (next >= slots.size()) slots.emplace_back(nullptr, 0);
-        return at(next++, bytes);
-    }
-    template <typename T> T *take(uint64_t count) { return static_cast<T *>(get(count * sizeof(T))); }
-    // the slots taken since mark() are handed out again after rewind(mark): in the same order, to the same uses
-    size_t mark() const { return next; }
-    void rewind(size_t m) { next = m; }
-};
-
-// rocPRIM calls with grow-only temporary storage: a buffer of its own (finalize), or after bind() ONE slot of a BufPool (the per-read stage:
-// the slot keeps its index, so a dataset's second round allocates nothing).  Every call is rocPRIM's two -- the size query, room(), the
-// launch; with `ask` it is the query alone (*ask = the larger of the two), for callers that grow the storage ONCE for several calls before
-// they queue anything: a grow frees, and a free waits for the device.
-struct Prim {
-    hipStream_t st; DevBuf own; void *buf = nullptr; size_t cap = 0;
-    BufPool *pool = nullptr; size_t slot = 0;
-    explicit Prim(hipStream_t s) : st(s) {}
-    int bind(BufPool &p, uint64_t bytes) {                        // the pool's next slot, `bytes` to begin with
-        pool = &p; slot = p.next;
-        buf = p.get(bytes);
-        if (!buf) return p.rc;
-        cap = (size_t)p.slots[slot].second;
-        return MSNV_OK;
-    }
-    int room(size_t need) {
-        if (need <= cap) return MSNV_OK;
-        if (pool) { buf = pool->at(slot, need); if (!buf) return pool->rc; cap = (size_t)pool->slots[slot].second; }
-        else { if (int rc = own.alloc(need)) return rc; buf = own.p; cap = need; }
-        return MSNV_OK;
-    }
-    template <typename In, typename Out, typename Op> int inclusive(In in, Out out, size_t n, Op op, size_t *ask = nullptr) {
-        size_t need = 0;
-        HIP_TRY(rocprim::inclusive_scan(nullptr, need, in, out, n, op, st));
-        if (ask) { *ask = std::max(*ask, need); return MSNV_OK; }
-        if (int rc = room(need)) return rc;
-        HIP_TRY(rocprim::inclusive_scan(buf, need, in, out, n, op, st));
-        return MSNV_OK;
-    }
-    template <typename In, typename Out, typename Init, typename Op> int exclusive(In in, Out out, Init init, size_t n, Op op, size_t *ask = nullptr) {
-        size_t need = 0;
-        HIP_TRY(rocprim::exclusive_scan(nullptr, need, in, out, init, n, op, st));
-        if (ask) { *ask = std::max(*ask, need); return MSNV_OK; }
-        if (int rc = room(need)) return rc;
-        HIP_TRY(rocprim::exclusive_scan(buf, need, in, out, init, n, op, st));
-        return MSNV_OK;
-    }
-    template <typename K, typename V> int sort_pairs(K *kin, K *kout, V *vin, V *vout, size_t n, unsigned end_bit, size_t *ask = nullptr) {
-        size_t need = 0;
-        HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, kin, kout, vin, vout, n, 0u, end_bit, st));
-        if (ask) { *ask = std::max(*ask, need); return MSNV_OK; }
-        if (int rc = room(need)) return rc;
-        HIP_TRY(rocprim::radix_sort_pairs(buf, need, kin, kout, vin, vout, n, 0u, end_bit, st));
-        return MSNV_OK;
-    }
-    // The forms most callers use.  Defined further down, not here: rocPRIM's kernels enter the code object in the order in which the compiler
-    // meets their first use, and these definitions stand where the per-read stage and finalize have always had theirs.
-    int scan32(const uint32_t *in, uint32_t *out, size_t n, bool inclusive_);
-    int sort64(unsigned long long *kin, unsigned long long *kout, uint32_t *vin, uint32_t *vout, size_t n, unsigned end_bit);
-    int scan64(const uint32_t *in, unsigned long long *out, size_t n);
-    int reserve_scan32(size_t n);           // room for scans of up to n words before the first launch
-};
 
 // Record streams (host or device memory) side by side in one device buffer and the offsets of their records: what the device pack
 // (devpack_add_round) and the device dealer (msnv_records_deal_device) start from.
@@ -3709,6 +3524,28 @@ int devpack_download_pieces(msnv_dataset &ds) {
     return MSNV_OK;
 }
 
+// The two kernels of the round that finalize's deep-run split borrows (devwork.h)
+int devpack_gather_pieces(hipStream_t st, const uint32_t *src, const DevRound &R, ReadHdr *hdr2, int32_t *tid2, int32_t *end2, uint16_t *depth2) {
+    hipLaunchKernelGGL(msnv_gather_pieces, grid_for(R.n_pieces, 256), dim3(256), 0, st, src, (uint32_t)R.n_pieces, R.hdr, R.tid, R.end, R.depth, hdr2, tid2, end2, depth2);
+    HIP_TRY(hipGetLastError());
+    return MSNV_OK;
+}
+int devpack_emit_tail(msnv_dataset &ds, uint8_t *seq, uint8_t *qual, unsigned long long piece_bytes) {
+    hipStream_t st = (hipStream_t)ds.ctx->stream;
+    const msnv_params &MP = ds.params;
+    DpParams P{}; P.c_eff = std::min(std::max(MP.min_baseq, -127), 127); P.all_low = MP.min_baseq > 127;
+    const DpSampleDst dst{seq, qual, 0ull, 0u, 0u};
+    DevBuf d_dst, d_pb;
+    if (int rc = d_dst.alloc(sizeof(DpSampleDst))) return rc;
+    if (int rc = d_pb.alloc(8)) return rc;
+    HIP_TRY(hipMemcpyAsync(d_dst.p, &dst, sizeof dst, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_pb.p, &piece_bytes, 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(msnv_emit_tail, dim3(1), dim3(64), 0, st, d_dst.as<DpSampleDst>(), d_pb.as<unsigned long long>(), 1u, P);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return MSNV_OK;
+}
+
 int devpack_sample_to_host(SampleCols &sc) {
     if (!sc.on_device) return MSNV_OK;
     const uint64_t nb = sc.d_seq_bytes;
@@ -3716,1280 +3553,10 @@ int devpack_sample_to_host(SampleCols &sc) {
     std::vector<uint8_t> bits((2 * nb + 7) / 8);
     if (nb) HIP_TRY(hipMemcpy(sc.seq.data(), sc.d_seq, nb, hipMemcpyDeviceToHost));
     if (!bits.empty()) HIP_TRY(hipMemcpy(bits.data(), sc.d_qual, bits.size(), hipMemcpyDeviceToHost));
-    // flags back to staging bytes: 0x80 is below every cutoff, 127 below none that flags a real quality (pack.cpp: pack_lowq)
+    // flags back to staging bytes: 0x80 is below every cutoff, 127 below none that flags a real quality (finalize.cpp: pack_lowq)
     sc.qual.resize(2 * nb);
     for (uint64_t i = 0; i < 2 * nb; ++i) sc.qual[i] = (bits[i >> 3] >> (i & 7)) & 1u ? 0x80 : 127;
     sc.on_device = false; sc.d_seq = nullptr; sc.d_qual = nullptr; sc.d_seq_bytes = 0;
-    return MSNV_OK;
-}
-
-int devpack_copy_columns(const SampleCols &sc, uint8_t *dst_seq, uint8_t *dst_qual_bits, void *stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (sc.d_seq_bytes) HIP_TRY(hipMemcpyAsync(dst_seq, sc.d_seq, sc.d_seq_bytes, hipMemcpyDeviceToDevice, st));
-    const uint64_t qb = (2 * sc.d_seq_bytes + 7) / 8;
-    if (qb) HIP_TRY(hipMemcpyAsync(dst_qual_bits, sc.d_qual, qb, hipMemcpyDeviceToDevice, st));
-    return MSNV_OK;
-}
-
-// ------------------------------------------------------------------------------------------ finalize on the device
-// The per-piece and per-interval parts of finalize_dataset (pack.cpp) for a dataset whose samples were all packed here: the headers and
-// intervals never leave HBM; the host works on (sample, tile) pairs only.  Every function mirrors the host loop named beside it and
-// produces the same bytes (tests/test_gpu_devpack.py compares every table of the two builds).
-int Prim::scan64(const uint32_t *in, unsigned long long *out, size_t n) { return exclusive(in, out, 0ull, n, rocprim::plus<unsigned long long>()); }
-int Prim::reserve_scan32(size_t n) {
-    size_t need = 0;
-    if (int rc = exclusive((const uint32_t *)nullptr, (uint32_t *)nullptr, 0u, n, rocprim::plus<uint32_t>(), &need)) return rc;
-    return room(need + 256);
-}
-namespace {
-
-__global__ void msnv_fin_headers(const ReadHdr *src, const int32_t *tid, unsigned long long n, const uint32_t *tile_base, ReadHdr *dst) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    ReadHdr h = src[i];
-    h.gpos += tile_base[tid[i]] * TILE;                           // contig-relative -> linear position of the shard
-    dst[i] = h;
-}
-
-// chunks of the narrow work items' pairs (pack.cpp: "chunk descriptors of the narrow work items", HDR4 form): up to CHUNK_READS consecutive
-// pieces whose seq bytes lie within 2^HDR4_OFF_BITS alignment units of the chunk's lowest offset; FILL writes the descriptors and the
-// 4-byte chunk-relative piece headers.  One WAVEFRONT per pair: 64 pieces a step, the greedy rule's running minimum / maximum as prefix
-// scans over the lanes, the first piece that would stretch the chunk too far found by a ballot (a thread per pair walking ~250 headers
-// one after the other was 1.1 ms of finalize on the benchmark shape).
-__device__ __forceinline__ unsigned long long wave_prefix_min(unsigned long long v) {
-    for (int o = 1; o < 64; o <<= 1) { const unsigned long long y = __shfl_up(v, o); if ((int)(threadIdx.x & 63u) >= o) v = y < v ? y : v; }
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_prefix_max(unsigned long long v) {
-    for (int o = 1; o < 64; o <<= 1) { const unsigned long long y = __shfl_up(v, o); if ((int)(threadIdx.x & 63u) >= o) v = y > v ? y : v; }
-    return v;
-}
-template <bool FILL>
-__global__ __launch_bounds__(256) void msnv_fin_chunks(const TilePair *pairs, const uint32_t *list, uint32_t n, const ReadHdr *const *s_hdr, const unsigned long long *rbase, const unsigned long long *sbase,
-                                                       uint32_t *counts, const uint32_t *chunk_base, ChunkDesc *chunks, uint32_t *hdr4, uint32_t chunk_cap) {
-    const uint32_t j = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
-    if (j >= n) return;
-    const uint32_t k = list[j];
-    const TilePair p = pairs[k];
-    // (the sample's headers where the pack's round left them: positions contig-relative, which is all the same inside a tile -- contigs start
-    // on tile boundaries --, so nothing here waits for the linear copy, msnv_fin_headers)
-    const ReadHdr *h = s_hdr[p.sample];
-    constexpr unsigned long long span_max = (unsigned long long)SEQ_ALIGN << HDR4_OFF_BITS;
-    uint32_t r = p.read_lo, c = 0;
-    while (r < p.read_hi) {
-        // the chunk that starts at r: pieces r .. e - 1
-        unsigned long long lo = ~0ull, hi = 0;                    // of the pieces taken so far (wave-uniform)
-        uint32_t e = r;
-        ReadHdr mine[CHUNK_READS / 64];
-#pragma unroll
-        for (uint32_t step = 0; step < CHUNK_READS / 64; ++step) {
-            const uint32_t i = r + 64u * step + lane;
-            const bool have = i < p.read_hi;
-            if (have) mine[step] = h[i];
-            if (e != r + 64u * step) continue;                     // (the chunk was closed inside an earlier step; wave-uniform)
-            const unsigned long long o = have ? (unsigned long long)mine[step].seqoff : 0ull;
-            unsigned long long pmin = wave_prefix_min(have ? o : ~0ull), pmax = wave_prefix_max(have ? o : 0ull);
-            pmin = pmin < lo ? pmin : lo; pmax = pmax > hi ? pmax : hi;
-            const unsigned long long stop = __ballot(!have || pmax - pmin >= span_max);      // first lane that does not join
-            const uint32_t take = stop ? (uint32_t)__builtin_ctzll(stop) : 64u;
-            if (take) { lo = __shfl(pmin, (int)take - 1); hi = __shfl(pmax, (int)take - 1); }
-            e += take;
-        }
-        if (e == r) e = r + 1;                                     // (a single piece always fits: its span is 0 -- never taken, kept against a stuck loop)
-        if (FILL) {
-#pragma unroll
-            for (uint32_t step = 0; step < CHUNK_READS / 64; ++step) {
-                const uint32_t i = r + 64u * step + lane;
-                if (i < e) hdr4[rbase[p.sample] + i] = (mine[step].gpos % TILE) | mine[step].cig << 11 | (uint32_t)((mine[step].seqoff - lo) >> SEQ_ALIGN_LOG2) << 19;
-            }
-            if (lane == 0 && chunk_base[j] + c < chunk_cap) chunks[chunk_base[j] + c] = ChunkDesc{rbase[p.sample] + r, sbase[p.sample] + lo, p.pad >> 8, k, (e - r) | (e >= p.read_hi ? 1u << 16 : 0u), p.pad & 0xffu};
-        }
-        ++c; r = e;
-    }
-    if (!FILL && lane == 0) counts[j] = c;
-}
-// The narrow work items' chunk ranges from the scanned counts, on the device (round 6: the host used to wait for the scan to write them):
-// item wi owns the listed pairs [item_first[wi], item_first[wi + 1]) and with them the chunks [base + scan[..], base + scan[..]).  The total
-// and "more chunks than there is room for" go to the host through pinned words; it looks at them behind finalize's last wait.
-__global__ void msnv_fin_work_chunks(WorkItem *work, uint32_t n_narrow, const uint32_t *item_first, const uint32_t *scan, uint32_t n_listed, uint32_t base, uint32_t cap, uint32_t *result) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) { result[0] = scan[n_listed]; result[1] = scan[n_listed] > cap ? 1u : 0u; }
-    if (i >= n_narrow) return;
-    work[i].chunk_lo = base + scan[item_first[i]];
-    work[i].chunk_hi = base + scan[item_first[i + 1]];
-}
-// every narrow / merged work item's first chunk descriptor, copied into the item (kernels.hip: a workgroup starts loading without the descriptor stream)
-// (n_room: descriptors the table holds -- after an overflow of the device's cut the items' ranges point behind it until finalize cuts again)
-__global__ void msnv_fin_work_first(WorkItem *work, uint32_t n, const ChunkDesc *chunks, unsigned long long n_room) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (work[i].chunk_hi > work[i].chunk_lo && work[i].chunk_lo < n_room) work[i].first = chunks[work[i].chunk_lo];
-}
-
-__global__ void msnv_fin_merged(const TilePair *pairs, const DevMergedSrc *list, uint32_t n, const ReadHdr *const *s_hdr, const unsigned long long *sbase, PieceHdr *hm) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const DevMergedSrc m = list[j];
-    const TilePair p = pairs[m.pair];
-    const ReadHdr *h = s_hdr[p.sample];                            // (contig-relative positions: only the tile-relative part is used)
-    for (uint32_t r = p.read_lo; r < p.read_hi; ++r) {
-        const unsigned long long so = (sbase[p.sample] + h[r].seqoff) >> SEQ_ALIGN_LOG2;     // 37 bits: bits 32-36 ride in bits 27-31 of the first word
-        hm[m.h_base + (r - p.read_lo)] = PieceHdr{(h[r].gpos % TILE) | h[r].cig << 11 | m.in_group << 19 | (uint32_t)(so >> 32) << 27, (uint32_t)so};
-    }
-}
-
-// qaCompute's intervals -> the coverage kernel's inputs (pack.cpp: "genome coverage index")
-__device__ __forceinline__ uint32_t sample_of(const unsigned long long *iv_start, uint32_t n_samples, unsigned long long j) {
-    uint32_t a = 0, b = n_samples;
-    while (b - a > 1) { const uint32_t m = (a + b) / 2; if (iv_start[m] <= j) a = m; else b = m; }
-    return a;
-}
-__global__ void msnv_fin_cov_measure(const int32_t *ctid, const int32_t *cbeg, const int32_t *cend, unsigned long long n, const DpContig *ctg, const uint32_t *tile_base,
-                                     uint32_t *keep, uint32_t *ntile) {
-    const unsigned long long j = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const int32_t c = ctid[j];
-    const long long L = ctg[c].len, b = cbeg[j];
-    const bool minus_one = b > (long long)cend[j];                                          // {L, L - 1}: "-1 at L - 1" (msnv_emit_headers)
-    const long long e = minus_one ? (long long)cend[j] : ((long long)cend[j] >= L ? L - 1 : (long long)cend[j]);      // qaCompute.cpp:544-549
-    const bool k = minus_one || b < e;
-    uint32_t nt = 0;
-    if (k) {
-        const unsigned long long g0 = (unsigned long long)tile_base[c] * TILE;
-        const uint32_t tf = (uint32_t)((g0 + (unsigned long long)(minus_one ? e : b)) / TILE), tl = minus_one ? tf : (uint32_t)((g0 + (unsigned long long)e - 1) / TILE);
-        nt = tl - tf + 1;
-    }
-    keep[j] = k ? 1u : 0u; ntile[j] = nt;
-}
-// (the round's arrays are indexed by j, the dataset-wide ones -- kidx, iv_start -- by j0 + j; ntile / ebase come offset to the round)
-__global__ void msnv_fin_cov_emit(const int32_t *ctid, const int32_t *cbeg, const int32_t *cend, unsigned long long n, unsigned long long j0, const DpContig *ctg,
-                                  const uint32_t *tile_base, const unsigned long long *iv_start, uint32_t n_samples, const uint32_t *ntile, const uint32_t *kidx_all,
-                                  const uint32_t *ebase, Pair32 *iv, unsigned long long *ekey, uint32_t *eval) {
-    const unsigned long long j = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n || !ntile[j]) return;
-    const uint32_t *kidx = kidx_all + j0;
-    const int32_t c = ctid[j];
-    const long long L = ctg[c].len, b = cbeg[j];
-    const bool minus_one = b > (long long)cend[j];
-    const long long e = minus_one ? (long long)cend[j] : ((long long)cend[j] >= L ? L - 1 : (long long)cend[j]);
-    const unsigned long long g0 = (unsigned long long)tile_base[c] * TILE;
-    iv[kidx[j]] = Pair32{(uint32_t)(g0 + (unsigned long long)b), (uint32_t)(g0 + (unsigned long long)e)};
-    const uint32_t s = sample_of(iv_start, n_samples, j0 + j);
-    const uint32_t idx = kidx[j] - kidx_all[iv_start[s]];                                   // index among the sample's kept intervals
-    const uint32_t tf = (uint32_t)((g0 + (unsigned long long)(minus_one ? e : b)) / TILE), tl = minus_one ? tf : (uint32_t)((g0 + (unsigned long long)e - 1) / TILE);
-    unsigned long long w = ebase[j];
-    for (uint32_t t = tf; t <= tl; ++t, ++w) { ekey[w] = (unsigned long long)s << 32 | t; eval[w] = idx; }
-}
-__global__ void msnv_fin_cov_runs(const unsigned long long *skey, const uint32_t *sval, const uint32_t *flag, const uint32_t *rid_incl, unsigned long long n, DevCovPair *out) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t r = rid_incl[i] - 1u;
-    if (flag[i]) { out[r].tile = (uint32_t)skey[i]; out[r].sample = (uint32_t)(skey[i] >> 32); out[r].lo = sval[i]; }
-    if (i + 1 == n || flag[i + 1]) out[r].hi = sval[i] + 1u;                                  // (stable sort: the run's values ascend)
-}
-// The (sample, tile) runs without a sort: the intervals of a sample come in nearly ascending order, so a run is the RANGE [first, last + 1)
-// of the kept intervals that touch the tile -- a minimum and a maximum per (sample, tile), kept in a dense [sample][tile] table when that
-// table is small beside the interval list (else the sort of (sample, tile, index) entries above).  Consecutive lanes hold consecutive
-// intervals, nearly always of one (sample, tile): the first lane of such a stretch carries its minimum, the last its maximum -- two atomics
-// per stretch instead of two per interval; an interval that touches several tiles adds to the other tiles' entries by itself.
-__global__ __launch_bounds__(256) void msnv_fin_cov_emit_dense(const int32_t *ctid, const int32_t *cbeg, const int32_t *cend, unsigned long long n, unsigned long long j0, const DpContig *ctg,
-                                                               const uint32_t *tile_base, const unsigned long long *iv_start, uint32_t n_samples, const uint32_t *keep_all, const uint32_t *kidx_all,
-                                                               uint32_t n_tiles, Pair32 *iv, uint32_t *lo, uint32_t *hi) {
-    const unsigned long long j = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned long long key = ~0ull; uint32_t idx = 0, tf = 0, tl = 0, s = 0;
-    if (j < n && (!keep_all || keep_all[j0 + j])) {
-        const int32_t c = ctid[j];
-        const long long L = ctg[c].len, b = cbeg[j];
-        const bool minus_one = b > (long long)cend[j];
-        const long long e = minus_one ? (long long)cend[j] : ((long long)cend[j] >= L ? L - 1 : (long long)cend[j]);
-        const unsigned long long g0 = (unsigned long long)tile_base[c] * TILE;
-        const uint32_t place = keep_all ? kidx_all[j0 + j] : (uint32_t)(j0 + j);          // (no tables: every interval is kept -- the device pack writes no other since round 6)
-        iv[place] = Pair32{(uint32_t)(g0 + (unsigned long long)b), (uint32_t)(g0 + (unsigned long long)e)};
-        s = sample_of(iv_start, n_samples, j0 + j);
-        idx = place - (keep_all ? kidx_all[iv_start[s]] : (uint32_t)iv_start[s]);
-        tf = (uint32_t)((g0 + (unsigned long long)(minus_one ? e : b)) / TILE); tl = minus_one ? tf : (uint32_t)((g0 + (unsigned long long)e - 1) / TILE);
-        key = (unsigned long long)s * n_tiles + tf;
-    }
-    const unsigned long long kp = __shfl_up(key, 1), kn = __shfl_down(key, 1);
-    const uint32_t lane = threadIdx.x & 63u;
-    if (key != ~0ull) {
-        if (lane == 0 || kp != key) atomicMin(&lo[key], idx);
-        if (lane == 63 || kn != key) atomicMax(&hi[key], idx + 1u);
-        for (uint32_t t = tf + 1; t <= tl; ++t) { atomicMin(&lo[(unsigned long long)s * n_tiles + t], idx); atomicMax(&hi[(unsigned long long)s * n_tiles + t], idx + 1u); }
-    }
-}
-__global__ void msnv_fin_cov_dense_flags(const uint32_t *hi, unsigned long long n, uint32_t *flag) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i <= n) flag[i] = (i < n && hi[i]) ? 1u : 0u;
-}
-__global__ void msnv_fin_cov_dense_runs(const uint32_t *lo, const uint32_t *hi, const uint32_t *rid_excl, unsigned long long n, uint32_t n_tiles, DevCovPair *out) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || !hi[i]) return;
-    out[rid_excl[i]] = DevCovPair{(uint32_t)(i % n_tiles), (uint32_t)(i / n_tiles), lo[i], hi[i]};
-}
-// ---- the coverage index's pair tables on the device (round 6; pack.cpp: cov_index built them on the host behind finalize's last wait, 0.5 ms of
-// loops over the (sample, tile) runs on the benchmark shape).  The dense [sample][tile] table read TILE-major gives the pairs in their final
-// order (tiles ascending, samples ascending inside a tile) by one scan of its flags; the accumulator rows -- one per (sample, contig) that has
-// intervals -- by a scan of a presence table; the work items (pack.cpp's cut: COV_ITEM_PAIRS pairs, or fewer when one pair alone is deep) by a
-// thread per tile, counted first, written once the host has allocated the tables from the counts that come back with the index's own.
-__global__ void msnv_cov_flags_t(const uint32_t *hi, uint32_t n_samples, uint32_t n_tiles, const uint32_t *tcont, uint32_t n_contigs, uint32_t *flag_t, uint32_t *pres) {
-    const unsigned long long k = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x, n = (unsigned long long)n_samples * n_tiles;
-    if (k > n) return;
-    uint32_t f = 0;
-    if (k < n) {
-        const uint32_t t = (uint32_t)(k / n_samples), sm = (uint32_t)(k % n_samples);
-        f = hi[(unsigned long long)sm * n_tiles + t] ? 1u : 0u;
-        if (f) pres[(unsigned long long)sm * n_contigs + tcont[t]] = 1u;
-    }
-    flag_t[k] = f;
-}
-// (a WAVEFRONT per tile: its lanes ask for 64 samples' table entries at once, the cut -- sequential over the pairs -- runs over them by shuffles.
-// First form: a thread per tile with a loop over the samples, 61 us for the benchmark's 440 tiles x 160 samples: a chain of loads per thread)
-__global__ __launch_bounds__(64) void msnv_cov_count_items(const uint32_t *lo, const uint32_t *hi, uint32_t n_samples, uint32_t n_tiles, uint32_t item_intervals, uint32_t narrow_max, uint32_t *n_item, uint32_t *wide) {
-    const uint32_t t = blockIdx.x, lane = threadIdx.x;
-    if (t > n_tiles) return;
-    uint32_t items = 0;
-    if (t < n_tiles) {
-        unsigned long long acc = 0; uint32_t in_item = 0; bool w = false;
-        for (uint32_t base = 0; base < n_samples; base += 64u) {
-            const uint32_t sm = base + lane;
-            uint32_t span = 0; bool has = false;
-            if (sm < n_samples) {
-                const uint32_t h = hi[(unsigned long long)sm * n_tiles + t];
-                if (h) { has = true; span = h - lo[(unsigned long long)sm * n_tiles + t]; }
-            }
-            w |= has && span > narrow_max;
-            unsigned long long m = __ballot(has);
-            while (m) {                                                  // (uniform: every lane keeps the same cut state)
-                const int k = __builtin_ctzll(m);
-                m &= m - 1ull;
-                acc += __shfl(span, k); ++in_item;
-                if (acc >= item_intervals || in_item >= COV_ITEM_PAIRS) { ++items; acc = 0; in_item = 0; }
-            }
-        }
-        if (in_item) ++items;
-        if (__any(w) && lane == 0) *wide = 1u;
-    }
-    if (lane == 0) n_item[t] = items;
-}
-__global__ void msnv_cov_rows(const uint32_t *pres, const uint32_t *rowid, uint32_t n_samples, uint32_t n_contigs, uint32_t *row_sample, uint32_t *row_contig, uint32_t *row_start) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x, n = (unsigned long long)n_samples * n_contigs;
-    if (i > n) return;
-    if (i < n && pres[i]) { row_sample[rowid[i]] = (uint32_t)(i / n_contigs); row_contig[rowid[i]] = (uint32_t)(i % n_contigs); }
-    if (i % n_contigs == 0u || i == n) row_start[i / n_contigs] = rowid[i];            // (entry n_samples: the rows in all)
-}
-__global__ void msnv_cov_counts(const uint32_t *rid_t, unsigned long long n_tab, const uint32_t *rowid, unsigned long long n_sc, const uint32_t *item_off, uint32_t n_tiles, const uint32_t *wide, uint32_t *out) {
-    if (blockIdx.x || threadIdx.x) return;
-    out[0] = rid_t[n_tab]; out[1] = rowid[n_sc]; out[2] = item_off[n_tiles]; out[3] = *wide;
-}
-__global__ void msnv_cov_write_pairs(const uint32_t *lo, const uint32_t *hi, const uint32_t *rid_t, const uint32_t *rowid, const uint32_t *tcont, const unsigned long long *iv_start,
-                                     uint32_t n_samples, uint32_t n_tiles, uint32_t n_contigs, TilePair *pairs) {
-    const unsigned long long k = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x, n = (unsigned long long)n_samples * n_tiles;
-    if (k >= n) return;
-    const uint32_t t = (uint32_t)(k / n_samples), sm = (uint32_t)(k % n_samples);
-    const uint32_t h = hi[(unsigned long long)sm * n_tiles + t];
-    if (!h) return;
-    const unsigned long long b = iv_start[sm];
-    pairs[rid_t[k]] = TilePair{sm, lo[(unsigned long long)sm * n_tiles + t], h, rowid[(unsigned long long)sm * n_contigs + tcont[t]], (uint32_t)b, (uint32_t)(b >> 32), 0u, 0u};
-}
-__global__ __launch_bounds__(64) void msnv_cov_write_items(const TilePair *pairs, const uint32_t *rid_t, const uint32_t *item_off, uint32_t n_samples, uint32_t n_tiles, uint32_t item_intervals, WorkItem *work) {
-    const uint32_t t = blockIdx.x, lane = threadIdx.x;
-    if (t >= n_tiles) return;
-    const uint32_t p0 = rid_t[(unsigned long long)t * n_samples], p1 = rid_t[(unsigned long long)(t + 1u) * n_samples];
-    uint32_t w = item_off[t], first = p0; unsigned long long acc = 0;
-    for (uint32_t base = p0; base < p1; base += 64u) {
-        const uint32_t k = base + lane;
-        const uint32_t span = k < p1 ? pairs[k].read_hi - pairs[k].read_lo : 0u;
-        const uint32_t n = p1 - base < 64u ? p1 - base : 64u;
-        for (uint32_t j = 0; j < n; ++j) {                               // (uniform)
-            acc += __shfl(span, (int)j);
-            const uint32_t kk = base + j;
-            if (acc >= item_intervals || kk + 1u - first >= COV_ITEM_PAIRS || kk + 1u == p1) {
-                if (lane == 0) { WorkItem it{}; it.tile = t; it.pair_lo = first; it.pair_hi = kk + 1u; work[w] = it; }
-                ++w; first = kk + 1u; acc = 0;
-            }
-        }
-    }
-}
-__global__ void msnv_gather_u32(const uint32_t *src, const unsigned long long *idx, uint32_t n, uint32_t *out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = src[idx[i]];
-}
-}  // namespace
-
-int devfin_overhang(msnv_dataset &ds, std::vector<int64_t> &maxend) {
-    if (!ds.dp.overhang || !ds.dp.any_overhang_h) return MSNV_OK;   // (the measure kernel of every round said whether a read runs past its contig)
-    std::vector<int32_t> oh(ds.names.size());
-    HIP_TRY(hipMemcpy(oh.data(), ds.dp.overhang, oh.size() * 4, hipMemcpyDeviceToHost));
-    for (size_t c = 0; c < oh.size(); ++c) if (ds.sel[c]) maxend[c] = std::max<int64_t>(maxend[c], oh[c]);
-    return MSNV_OK;
-}
-
-// d.hdr (allocated, rbase-sized) from the rounds' headers with the positions made linear; needs ds.tile_base
-int devfin_headers(msnv_dataset &ds, DeviceCols &d, const std::vector<uint64_t> &rbase) {
-    hipStream_t st = (hipStream_t)ds.ctx->stream;
-    DevBuf tb;
-    if (int rc = tb.alloc(std::max<size_t>(1, ds.tile_base.size()) * 4)) return rc;
-    HIP_TRY(hipMemcpyAsync(tb.p, ds.tile_base.data(), ds.tile_base.size() * 4, hipMemcpyHostToDevice, st));
-    for (const DevRound &r : ds.dp.rounds) {
-        if (!r.n_pieces) continue;
-        hipLaunchKernelGGL(msnv_fin_headers, grid_for(r.n_pieces, 256), dim3(256), 0, st, r.hdr, r.tid, (unsigned long long)r.n_pieces, tb.as<uint32_t>(), d.hdr + rbase[r.first_sample]);
-        HIP_TRY(hipGetLastError());
-    }
-    ds.dp.fin_tile_base = tb.release();                            // (read by kernels that may still be queued: freed with the pack's tables; no wait here)
-    return MSNV_OK;
-}
-
-// Every sample's headers where its round left them (device pointers, one per sample): what msnv_fin_chunks / msnv_fin_merged read
-static int sample_hdr_table(msnv_dataset &ds, const ReadHdr *const **out) {
-    DevPackTables &T = ds.dp;
-    const size_t S = ds.samples.size();
-    std::vector<const ReadHdr *> tab(S, nullptr);
-    for (size_t s = 0; s < S; ++s) {
-        const SampleCols &sc = ds.samples[s];
-        if (sc.dev_round >= 0 && (size_t)sc.dev_round < T.rounds.size()) tab[s] = T.rounds[(size_t)sc.dev_round].hdr + sc.dev_piece0;
-    }
-    void *p = nullptr;
-    if (int rc = dev_alloc(&p, std::max<size_t>(1, S) * sizeof(void *), nullptr)) return rc;
-    T.fin_keep.push_back(p);
-    if (S) HIP_TRY(hipMemcpy(p, tab.data(), S * sizeof(void *), hipMemcpyHostToDevice));
-    *out = static_cast<const ReadHdr *const *>(p);
-    return MSNV_OK;
-}
-
-// The narrow pairs' chunks WITHOUT a wait (round 6; round 5 waited for the counts to size the descriptor table and to write the work items'
-// ranges): counts -> scan -> fill -> the work items' ranges, all queued; d.chunks (allocated by the caller) has room for `cap` narrow chunks
-// behind the `base` chunks of the merged groups, which the host wrote.  cap is the host's bound -- per pair ceil(pieces / CHUNK_READS) + 2: a
-// chunk is closed early only where the seq offsets jump by 16 KB, at most once per pair in data the pack laid out --; the true total and an
-// overflow flag arrive through the dataset's pinned words (devfin_chunks_result, behind finalize's last wait): an overflow sends finalize
-// through devfin_chunk_counts / devfin_chunk_fill below, which wait and size exactly (MSNV_CHUNK_CAP forces it: tests).
-int devfin_chunks_launch(msnv_dataset &ds, DeviceCols &d, const std::vector<uint32_t> &narrow_pairs, const std::vector<uint32_t> &item_first, uint32_t base, uint64_t cap) {
-    hipStream_t st = (hipStream_t)ds.ctx->stream;
-    DevPackTables &T = ds.dp;
-    const size_t n = narrow_pairs.size(), n_items = item_first.size() - 1;
-    T.fin_chunks_async = true; T.fin_chunk_cap = cap; T.fin_chunk_base = base;
-    if (int rc = pin_ensure(ds, (ds.samples.size() + 16) * 4)) return rc;
-    uint32_t *res = pin_fin_words(T) + (ds.samples.size() + 4);
-    res[0] = 0; res[1] = 0;
-    if (!n) return MSNV_OK;
-    const ReadHdr *const *s_hdr = nullptr;
-    if (int rc = sample_hdr_table(ds, &s_hdr)) return rc;
-    void *blk = nullptr;
-    const uint64_t b_list = (n * 4 + 255) & ~255ull, b_if = ((n_items + 1) * 4 + 255) & ~255ull, b_cnt = ((n + 1) * 4 + 255) & ~255ull;
-    if (int rc = dev_alloc(&blk, b_list + b_if + 2 * b_cnt + 256, nullptr)) return rc;
-    T.fin_keep.push_back(blk);
-    uint8_t *q = static_cast<uint8_t *>(blk);
-    uint32_t *list = reinterpret_cast<uint32_t *>(q); q += b_list;
-    uint32_t *ifirst = reinterpret_cast<uint32_t *>(q); q += b_if;
-    uint32_t *cnt = reinterpret_cast<uint32_t *>(q); q += b_cnt;
-    uint32_t *scan = reinterpret_cast<uint32_t *>(q); q += b_cnt;
-    uint32_t *dres = reinterpret_cast<uint32_t *>(q);
-    HIP_TRY(hipMemcpy(list, narrow_pairs.data(), n * 4, hipMemcpyHostToDevice));      // (blocking copies on the null stream: the buffers are fresh, nothing to order against)
-    HIP_TRY(hipMemcpy(ifirst, item_first.data(), (n_items + 1) * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemsetAsync(cnt + n, 0, 4, st));
-    hipLaunchKernelGGL(msnv_fin_chunks<false>, grid_for(n * 64, 256), dim3(256), 0, st, d.pairs, list, (uint32_t)n, s_hdr, (const unsigned long long *)d.s_read_base,
-                       (const unsigned long long *)d.s_seq_base, cnt, nullptr, nullptr, nullptr, 0u);
-    HIP_TRY(hipGetLastError());
-    {
-        // (rocPRIM's temporary storage outlives this call: the scan is only queued)
-        Prim pr(st);
-        const int rc = pr.exclusive(cnt, scan, 0u, n + 1, rocprim::plus<uint32_t>());
-        if (pr.own.p) T.fin_keep.push_back(pr.own.release());
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(msnv_fin_chunks<true>, grid_for(n * 64, 256), dim3(256), 0, st, d.pairs, list, (uint32_t)n, s_hdr, (const unsigned long long *)d.s_read_base,
-                       (const unsigned long long *)d.s_seq_base, nullptr, scan, d.chunks + base, d.hdr4, (uint32_t)std::min<uint64_t>(cap, 0xffffffffull));
-    hipLaunchKernelGGL(msnv_fin_work_chunks, grid_for(std::max<size_t>(1, n_items), 256), dim3(256), 0, st, d.work, (uint32_t)n_items, ifirst, scan, (uint32_t)n, base,
-                       (uint32_t)std::min<uint64_t>(cap, 0xffffffffull), dres);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(res, dres, 8, hipMemcpyDeviceToHost, st));
-    // (an event behind the two words: devfin_chunks_result waits for IT.  Until the coverage tables moved to the device the host's half
-    // millisecond of loops over them stood between this launch and the read of the words -- a wait in fact, not in the code)
-    if (!T.fin_chunk_event) { hipEvent_t e = nullptr; HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); T.fin_chunk_event = e; }
-    HIP_TRY(hipEventRecord((hipEvent_t)T.fin_chunk_event, st));
-    T.fin_chunk_pending = true;
-    return MSNV_OK;
-}
-// the narrow chunks that were cut, and whether they all found room (waits for the cut's last kernel)
-int devfin_chunks_result(msnv_dataset &ds, uint64_t *n_chunks, bool *overflow) {
-    if (ds.dp.fin_chunk_pending) { ds.dp.fin_chunk_pending = false; HIP_TRY(hipEventSynchronize((hipEvent_t)ds.dp.fin_chunk_event)); }
-    const uint32_t *res = pin_fin_words(ds.dp) + (ds.samples.size() + 4);
-    *n_chunks = res[0]; *overflow = res[1] != 0;
-    return MSNV_OK;
-}
-
-// ... and the form with ONE wait between counts and fill (exact sizes): counts (+ their exclusive scan, on the device) -> the host learns every
-// pair's first chunk and the total, and allocates the descriptors; then the fill, straight into d.chunks and d.hdr4.  The list and the scan
-// stay in HBM between the two calls (DevPackTables::fin_list / fin_cbase).
-int devfin_chunk_counts(msnv_dataset &ds, DeviceCols &d, const std::vector<uint32_t> &narrow_pairs, std::vector<uint32_t> &cbase) {
-    hipStream_t st = (hipStream_t)ds.ctx->stream;
-    const size_t n = narrow_pairs.size();
-    cbase.assign(n + 1, 0);
-    if (!n) return MSNV_OK;
-    DevPackTables &T = ds.dp;
-    const ReadHdr *const *s_hdr = nullptr;
-    if (int rc = sample_hdr_table(ds, &s_hdr)) return rc;
-    if (T.fin_list) { T.fin_keep.push_back(T.fin_list); T.fin_list = nullptr; }
-    if (T.fin_cbase) { T.fin_keep.push_back(T.fin_cbase); T.fin_cbase = nullptr; }
-    if (int rc = dev_alloc(&T.fin_list, n * 4, nullptr)) return rc;
-    if (int rc = dev_alloc(&T.fin_cbase, (n + 1) * 8, nullptr)) return rc;      // counts (n + 1 words) and their scan behind them
-    uint32_t *cnt = static_cast<uint32_t *>(T.fin_cbase), *scan = cnt + (n + 1);
-    HIP_TRY(hipMemcpyAsync(T.fin_list, narrow_pairs.data(), n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(cnt + n, 0, 4, st));
-    hipLaunchKernelGGL(msnv_fin_chunks<false>, grid_for(n * 64, 256), dim3(256), 0, st, d.pairs, static_cast<const uint32_t *>(T.fin_list), (uint32_t)n, s_hdr, (const unsigned long long *)d.s_read_base,
-                       (const unsigned long long *)d.s_seq_base, cnt, nullptr, nullptr, nullptr, 0u);
-    HIP_TRY(hipGetLastError());
-    Prim pr(st);
-    if (int rc = pr.scan32(cnt, scan, n + 1, false)) return rc;
-    HIP_TRY(hipMemcpyAsync(cbase.data(), scan, (n + 1) * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return MSNV_OK;
-}
-
-// d.chunks[base .. base + n_narrow) and d.hdr4 (both allocated by the caller) from the kept list and scan
-int devfin_chunk_fill(msnv_dataset &ds, DeviceCols &d, size_t n_pairs_listed, uint32_t base) {
-    hipStream_t st = (hipStream_t)ds.ctx->stream;
-    DevPackTables &T = ds.dp;
-    if (n_pairs_listed) {
-        const ReadHdr *const *s_hdr = nullptr;
-        if (int rc = sample_hdr_table(ds, &s_hdr)) return rc;
-        const uint32_t *scan = static_cast<const uint32_t *>(T.fin_cbase) + (n_pairs_listed + 1);
-        hipLaunchKernelGGL(msnv_fin_chunks<true>, grid_for(n_pairs_listed * 64, 256), dim3(256), 0, st, d.pairs, static_cast<const uint32_t *>(T.fin_list), (uint32_t)n_pairs_listed, s_hdr,
-                           (const unsigned long long *)d.s_read_base, (const unsigned long long *)d.s_seq_base, nullptr, scan, d.chunks + base, d.hdr4, 0xffffffffu);
-        HIP_TRY(hipGetLastError());
-    }
-    return MSNV_OK;
-}
-int devfin_work_first(msnv_dataset &ds, DeviceCols &d, uint32_t n_items, uint64_t n_room) {
-    hipStream_t st = (hipStream_t)ds.ctx->stream;
-    if (n_items) { hipLaunchKernelGGL(msnv_fin_work_first, grid_for(n_items, 256), dim3(256), 0, st, d.work, n_items, d.chunks, (unsigned long long)n_room); HIP_TRY(hipGetLastError()); }
-    return MSNV_OK;
-}
-
-int devfin_merged_headers(msnv_dataset &ds, DeviceCols &d, const std::vector<DevMergedSrc> &list) {
-    hipStream_t st = (hipStream_t)ds.ctx->stream;
-    if (list.empty()) return MSNV_OK;
-    const ReadHdr *const *s_hdr = nullptr;
-    if (int rc = sample_hdr_table(ds, &s_hdr)) return rc;
-    void *l = nullptr;
-    if (int rc = dev_alloc(&l, list.size() * sizeof(DevMergedSrc), nullptr)) return rc;
-    ds.dp.fin_keep.push_back(l);                                   // (read by a kernel that is only queued: freed with the pack's tables)
-    HIP_TRY(hipMemcpy(l, list.data(), list.size() * sizeof(DevMergedSrc), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(msnv_fin_merged, grid_for(list.size(), 64), dim3(64), 0, st, d.pairs, static_cast<const DevMergedSrc *>(l), (uint32_t)list.size(), s_hdr,
-                       (const unsigned long long *)d.s_seq_base, d.hdr8m);
-    HIP_TRY(hipGetLastError());
-    return MSNV_OK;
-}
-
-// d.cov_iv (allocated here: kept intervals + 4 idle entries) and, for the host, the kept intervals before every sample (cvbase) and the
-// (sample, tile) runs of the intervals in (sample, tile) order.  Work memory: 12 B per interval + 24 B per (interval, tile) entry in ONE
-// allocation (hipMalloc / hipFree of a dozen multi-gigabyte buffers was most of this step's second at BASELINE configs[2] scale).
-// The coverage index's kernels ahead of their results (round 5): launched as soon as finalize knows the tile layout -- they queue behind
-// whatever the pack left running --, their small results (kept intervals, per-sample bases, number of runs) land in the context's pinned words,
-// and devfin_coverage below only collects them (the host builds the pair tables of the tile index in between).  Dense table form only; when
-// the table would be large beside the interval list nothing is launched here and devfin_coverage runs the sort form, waiting as it goes.
-static bool cov_dense_form(const msnv_dataset &ds, unsigned long long N) {
-    const unsigned long long n_tab = (unsigned long long)ds.samples.size() * ds.n_tiles;
-    bool dense_tab = n_tab <= std::max<unsigned long long>(8ull * N, 1ull << 22) && n_tab < 0xfffffff0ull;
-    if (const char how = knob::cov_index()) dense_tab = how == 'd' ? n_tab < 0xfffffff0ull : false;
-    return dense_tab;
-}
-int devfin_coverage_launch(msnv_dataset &ds, DeviceCols &d) {
-    hipStream_t st = (hipStream_t)ds.ctx->stream;
-    DevPackTables &T = ds.dp;
-    const size_t S = ds.samples.size();
-    std::vector<unsigned long long> iv_start(S + 1, 0);
-    for (size_t s = 0; s < S; ++s) iv_start[s + 1] = iv_start[s] + ds.samples[s].n_dev_iv;
-    const unsigned long long N = iv_start[S];
-    const unsigned long long n_tab = (unsigned long long)S * ds.n_tiles;
-    if (N > 0xfffffff0ull || !cov_dense_form(ds, N) || n_tab > (1ull << 24) || knob::cov_late()) return MSNV_OK;
-    if (int rc = pin_ensure(ds, (2 * S + 64) * 4)) return rc;
-    auto up = [](unsigned long long b) { return (b + 255ull) & ~255ull; };
-    const unsigned long long b_tb = up(std::max<size_t>(1, ds.tile_base.size()) * 4), b_ivs = up((S + 1) * 8), b_cvb = up((S + 4) * 4);
-    const unsigned long long b_n = up((N + 1) * 4), b_t = up((n_tab + 1) * 4), b_r = up((n_tab + 1) * sizeof(DevCovPair));
-    void *blk = nullptr;
-    if (int rc = dev_alloc(&blk, b_tb + b_ivs + b_cvb + 3 * b_n + 4 * b_t + b_r, nullptr)) return rc;
-    T.cov_job = blk;
-    uint8_t *q = static_cast<uint8_t *>(blk);
-    uint32_t *tb = reinterpret_cast<uint32_t *>(q); q += b_tb;
-    unsigned long long *ivs = reinterpret_cast<unsigned long long *>(q); q += b_ivs;
-    uint32_t *cvb = reinterpret_cast<uint32_t *>(q); q += b_cvb;          // [0 .. S]: kept intervals before every sample; [S + 1] kept in all; [S + 2] runs
-    uint32_t *keep = reinterpret_cast<uint32_t *>(q); q += b_n;
-    uint32_t *ntile = reinterpret_cast<uint32_t *>(q); q += b_n;
-    uint32_t *kidx = reinterpret_cast<uint32_t *>(q); q += b_n;
-    uint32_t *lo = reinterpret_cast<uint32_t *>(q); q += b_t;
-    uint32_t *hi = reinterpret_cast<uint32_t *>(q); q += b_t;
-    uint32_t *flag = reinterpret_cast<uint32_t *>(q); q += b_t;
-    uint32_t *rid = reinterpret_cast<uint32_t *>(q); q += b_t;
-    DevCovPair *runs = reinterpret_cast<DevCovPair *>(q);
-    T.cov_runs = runs;
-    HIP_TRY(hipMemcpyAsync(tb, ds.tile_base.data(), ds.tile_base.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ivs, iv_start.data(), (S + 1) * 8, hipMemcpyHostToDevice, st));
-    const DpContig *ctg = static_cast<const DpContig *>(T.contigs);
-    Prim pr(st);
-    if (int rc = pr.reserve_scan32(std::max<unsigned long long>(N, n_tab) + 1)) return rc;
-    unsigned long long o = 0;
-    for (const DevRound &r : T.rounds) o += r.n_iv;
-    if (o != N) return fail(MSNV_EINVAL, "internal: the rounds hold %llu intervals, the samples %llu", o, N);
-    // (every interval of a device-packed round is one the index keeps -- measure_one counts, the emit kernels write, no other: the kept
-    // intervals before every sample are the host's iv_start, and nothing is measured or scanned here any more)
-    (void)keep; (void)ntile; (void)kidx;
-    HIP_TRY(hipMemsetAsync(cvb, 0, (S + 3) * 4, st));
-    if (int rc = dev_alloc((void **)&d.cov_iv, ((uint64_t)N + 4) * sizeof(Pair32), &d.device_bytes)) return rc;      // (N >= the kept ones: no wait for their count)
-    HIP_TRY(hipMemsetAsync(lo, 0xff, b_t, st));
-    HIP_TRY(hipMemsetAsync(hi, 0, b_t, st));
-    o = 0;
-    for (const DevRound &r : T.rounds) {
-        if (r.n_iv) {
-            hipLaunchKernelGGL(msnv_fin_cov_emit_dense, grid_for(r.n_iv, 256), dim3(256), 0, st, r.cov_tid, r.cov_beg, r.cov_end, (unsigned long long)r.n_iv, o, ctg, tb, ivs, (uint32_t)S,
-                               (const uint32_t *)nullptr, (const uint32_t *)nullptr, ds.n_tiles, d.cov_iv, lo, hi);
-            HIP_TRY(hipGetLastError());
-        }
-        o += r.n_iv;
-    }
-    hipLaunchKernelGGL(msnv_fin_cov_dense_flags, grid_for(n_tab + 1, 256), dim3(256), 0, st, hi, n_tab, flag);
-    HIP_TRY(hipGetLastError());
-    if (int rc = pr.scan32(flag, rid, n_tab + 1, false)) return rc;
-    HIP_TRY(hipMemcpyAsync(cvb + (S + 2), rid + n_tab, 4, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(msnv_fin_cov_dense_runs, grid_for(n_tab, 256), dim3(256), 0, st, lo, hi, rid, n_tab, ds.n_tiles, runs);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(pin_fin_words(T), cvb, (S + 3) * 4, hipMemcpyDeviceToHost, st));      // (pinned: the copy does not wait on the host)
-    // ---- the pair tables' counts (round 6: the tables themselves are written on the device once the host has allocated them, devfin_coverage)
-    T.cov_tables = nullptr;
-    {
-        const bool on_host = knob::cov_tables_on_host();
-        const size_t NC = ds.names.size(), nt = ds.n_tiles;
-        const unsigned long long n_sc = (unsigned long long)S * NC;
-        if (!on_host && NC && nt && ds.tile_contig.size() >= nt) {
-            const unsigned long long c_tc = up((nt + 1) * 4), c_ft = b_t, c_sc = up((n_sc + 1) * 4), c_it = up((nt + 2) * 4), c_rs = up((S + 2) * 4);
-            void *tb2 = nullptr;
-            if (int rc = dev_alloc(&tb2, c_tc + 2 * c_ft + 4 * c_sc + 2 * c_it + c_rs + 256, nullptr)) return rc;
-            T.cov_tables = tb2;
-            uint8_t *w = static_cast<uint8_t *>(tb2);
-            uint32_t *tcont = reinterpret_cast<uint32_t *>(w); w += c_tc;
-            uint32_t *flag_t = reinterpret_cast<uint32_t *>(w); w += c_ft;
-            uint32_t *rid_t = reinterpret_cast<uint32_t *>(w); w += c_ft;
-            uint32_t *pres = reinterpret_cast<uint32_t *>(w); w += c_sc;
-            uint32_t *rowid = reinterpret_cast<uint32_t *>(w); w += c_sc;
-            uint32_t *row_sample = reinterpret_cast<uint32_t *>(w); w += c_sc;
-            uint32_t *row_contig = reinterpret_cast<uint32_t *>(w); w += c_sc;
-            uint32_t *n_item = reinterpret_cast<uint32_t *>(w); w += c_it;
-            uint32_t *item_off = reinterpret_cast<uint32_t *>(w); w += c_it;
-            uint32_t *row_start = reinterpret_cast<uint32_t *>(w); w += c_rs;
-            uint32_t *counts = reinterpret_cast<uint32_t *>(w);            // [0] pairs [1] rows [2] work items [3] some pair is wide [4] scratch
-            T.cov_t = DevPackTables::CovT{tcont, rid_t, rowid, row_sample, row_contig, item_off, lo, hi, ivs};
-            HIP_TRY(hipMemcpyAsync(tcont, ds.tile_contig.data(), nt * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemsetAsync(pres, 0, c_sc, st));
-            HIP_TRY(hipMemsetAsync(counts, 0, 32, st));
-            const uint32_t item_intervals = knob::cov_item_intervals();
-            const uint32_t narrow_max = knob::cov_narrow_max();
-            T.cov_item_intervals = item_intervals;
-            hipLaunchKernelGGL(msnv_cov_flags_t, grid_for(n_tab + 1, 256), dim3(256), 0, st, hi, (uint32_t)S, ds.n_tiles, tcont, (uint32_t)NC, flag_t, pres);
-            HIP_TRY(hipGetLastError());
-            if (int rc = pr.scan32(flag_t, rid_t, n_tab + 1, false)) return rc;
-            if (int rc = pr.scan32(pres, rowid, n_sc + 1, false)) return rc;
-            hipLaunchKernelGGL(msnv_cov_count_items, dim3((unsigned)(nt + 1)), dim3(64), 0, st, lo, hi, (uint32_t)S, ds.n_tiles, item_intervals, narrow_max, n_item, counts + 3);
-            HIP_TRY(hipGetLastError());
-            if (int rc = pr.scan32(n_item, item_off, nt + 1, false)) return rc;
-            hipLaunchKernelGGL(msnv_cov_rows, grid_for(n_sc + 1, 256), dim3(256), 0, st, pres, rowid, (uint32_t)S, (uint32_t)NC, row_sample, row_contig, row_start);
-            hipLaunchKernelGGL(msnv_cov_counts, dim3(1), dim3(64), 0, st, rid_t, n_tab, rowid, n_sc, item_off, ds.n_tiles, counts + 3, counts);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(pin_fin_words(T) + (S + 16), counts, 16, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(pin_fin_words(T) + (S + 24), row_start, (S + 1) * 4, hipMemcpyDeviceToHost, st));
-        }
-    }
-    // an event behind the index's kernels: devfin_coverage waits for IT, not for the stream -- the chunk and header kernels finalize queues
-    // behind these run while the host builds the coverage pair tables (round 6)
-    if (!T.cov_event) { hipEvent_t e = nullptr; HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); T.cov_event = e; }
-    HIP_TRY(hipEventRecord((hipEvent_t)T.cov_event, st));
-    T.cov_tmp = pr.own.release();                                  // (rocPRIM's work memory: in use until the kernels above have run)
-    T.cov_launched = true;
-    return MSNV_OK;
-}
-
-int devfin_coverage(msnv_dataset &ds, DeviceCols &d, std::vector<uint64_t> &cvbase, std::vector<DevCovPair> &cp) {
-    hipStream_t st = (hipStream_t)ds.ctx->stream;
-    const size_t S = ds.samples.size();
-    std::vector<unsigned long long> iv_start(S + 1, 0);
-    for (size_t s = 0; s < S; ++s) iv_start[s + 1] = iv_start[s] + ds.samples[s].n_dev_iv;
-    const unsigned long long N = iv_start[S];
-    cvbase.assign(S + 1, 0); cp.clear();
-    ds.dp.cov_tables_done = false;
-    if (ds.dp.cov_launched) {
-        // the kernels were launched ahead (devfin_coverage_launch): their results are in the pinned words, the runs in HBM
-        DevPackTables &T = ds.dp;
-        T.cov_launched = false;
-        HIP_TRY(hipEventSynchronize((hipEvent_t)T.cov_event));
-        const uint32_t *pw = pin_fin_words(T);
-        for (size_t s = 0; s <= S; ++s) cvbase[s] = iv_start[s];       // (every interval is a kept one)
-        const uint32_t n_keep = (uint32_t)N, n_runs = pw[S + 2];
-        d.n_cov_iv = n_keep;
-        HIP_TRY(hipMemsetAsync(d.cov_iv + n_keep, 0, 4 * sizeof(Pair32), st));              // behind the last interval: what the idle lanes of msnv_coverage_tiles load
-        T.cov_tables_done = false;
-        if (T.cov_tables && pw[S + 16 + 3] == 0u) {
-            // the pair tables on the device: their sizes came with the index's counts; the rows' (sample, contig) names come down, nothing else
-            const uint32_t n_pairs = pw[S + 16], n_rows = pw[S + 17], n_work = pw[S + 18];
-            const size_t NC = ds.names.size();
-            const bool guard = knob::guard_alloc();
-            const uint64_t b_p = ((uint64_t)(n_pairs + 1) * sizeof(TilePair) + 255) & ~255ull, b_w = std::max<uint64_t>(16, (uint64_t)(n_work + 1) * sizeof(WorkItem));
-            if (guard) {
-                if (int rc = dev_alloc((void **)&d.cov_pairs, (uint64_t)(n_pairs + 1) * sizeof(TilePair), &d.device_bytes)) return rc;
-                if (int rc = dev_alloc((void **)&d.cov_work, b_w, &d.device_bytes)) return rc;
-            } else {
-                void *blk = nullptr;
-                if (int rc = dev_alloc(&blk, b_p + b_w + 256, &d.device_bytes)) return rc;
-                d.blocks.emplace_back(blk, b_p + b_w + 256);
-                d.cov_pairs = static_cast<TilePair *>(blk);
-                d.cov_work = reinterpret_cast<WorkItem *>(static_cast<uint8_t *>(blk) + b_p);
-            }
-            const DevPackTables::CovT &C = T.cov_t;
-            HIP_TRY(hipMemsetAsync(d.cov_pairs + n_pairs, 0, sizeof(TilePair), st));
-            HIP_TRY(hipMemsetAsync(d.cov_work + n_work, 0, sizeof(WorkItem), st));
-            const unsigned long long n_tab = (unsigned long long)S * ds.n_tiles;
-            if (n_pairs) {
-                hipLaunchKernelGGL(msnv_cov_write_pairs, grid_for(n_tab, 256), dim3(256), 0, st, C.lo, C.hi, C.rid_t, C.rowid, C.tcont, C.iv_start, (uint32_t)S, ds.n_tiles, (uint32_t)NC, d.cov_pairs);
-                hipLaunchKernelGGL(msnv_cov_write_items, dim3(ds.n_tiles), dim3(64), 0, st, d.cov_pairs, C.rid_t, C.item_off, (uint32_t)S, ds.n_tiles, T.cov_item_intervals, d.cov_work);
-                HIP_TRY(hipGetLastError());
-            }
-            ds.cov_row_sample.assign(n_rows, 0); ds.cov_row_contig.assign(n_rows, 0);
-            if (n_rows) {
-                HIP_TRY(hipMemcpy(ds.cov_row_sample.data(), C.row_sample, (size_t)n_rows * 4, hipMemcpyDeviceToHost));      // (blocking copies on the null stream: the context's stream is still busy, and not waited for)
-                HIP_TRY(hipMemcpy(ds.cov_row_contig.data(), C.row_contig, (size_t)n_rows * 4, hipMemcpyDeviceToHost));
-            }
-            ds.cov_row_start.assign(S + 1, 0);
-            for (size_t s = 0; s <= S; ++s) ds.cov_row_start[s] = pw[S + 24 + s];
-            d.n_cov_pairs = n_pairs; d.n_cov_work = n_work; d.n_cov_work_wide = 0; d.n_contigs = (uint32_t)NC;
-            T.cov_tables_done = true;
-            fin_trace("    cov: results of the kernels launched ahead, pair tables written there");
-            return MSNV_OK;
-        }
-        cp.resize(n_runs);
-        if (n_runs) HIP_TRY(hipMemcpy(cp.data(), T.cov_runs, (size_t)n_runs * sizeof(DevCovPair), hipMemcpyDeviceToHost));      // (a blocking copy on the null stream: the context's stream is still busy, and not waited for)
-        // (the job's buffers go back with the pack's tables: a free here would wait for the device)
-        fin_trace("    cov: results of the kernels launched ahead");
-        return MSNV_OK;
-    }
-    if (N > 0xfffffff0ull) return fail(MSNV_EDOMAIN, "more than 2^32 qaCompute intervals in one shard");
-    auto up = [](unsigned long long b) { return (b + 255ull) & ~255ull; };
-    DevBuf small, work;
-    const unsigned long long b_tb = up(std::max<size_t>(1, ds.tile_base.size()) * 4), b_ivs = up((S + 1) * 8), b_cvb = up((S + 1) * 4);
-    if (int rc = small.alloc(b_tb + b_ivs + b_cvb)) return rc;
-    uint32_t *tb = small.as<uint32_t>();
-    unsigned long long *ivs = reinterpret_cast<unsigned long long *>(small.as<uint8_t>() + b_tb);
-    uint32_t *cvb = reinterpret_cast<uint32_t *>(small.as<uint8_t>() + b_tb + b_ivs);
-    HIP_TRY(hipMemcpyAsync(tb, ds.tile_base.data(), ds.tile_base.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ivs, iv_start.data(), (S + 1) * 8, hipMemcpyHostToDevice, st));
-    const unsigned long long b_n = up((N + 1) * 4);
-    if (int rc = work.alloc(3 * b_n)) return rc;
-    uint32_t *keep = work.as<uint32_t>(), *ntile = reinterpret_cast<uint32_t *>(work.as<uint8_t>() + b_n), *kidx = reinterpret_cast<uint32_t *>(work.as<uint8_t>() + 2 * b_n);
-    const DpContig *ctg = static_cast<const DpContig *>(ds.dp.contigs);
-    Prim pr(st);
-    {   // the rounds' intervals where they lie (sample order = round order)
-        unsigned long long o = 0;
-        for (const DevRound &r : ds.dp.rounds) {
-            if (r.n_iv) {
-                hipLaunchKernelGGL(msnv_fin_cov_measure, grid_for(r.n_iv, 256), dim3(256), 0, st, r.cov_tid, r.cov_beg, r.cov_end, (unsigned long long)r.n_iv, ctg, tb, keep + o, ntile + o);
-                HIP_TRY(hipGetLastError());
-            }
-            o += r.n_iv;
-        }
-        if (o != N) return fail(MSNV_EINVAL, "internal: the rounds hold %llu intervals, the samples %llu", o, N);
-        HIP_TRY(hipMemsetAsync(keep + N, 0, 4, st));
-        HIP_TRY(hipMemsetAsync(ntile + N, 0, 4, st));
-    }
-    fin_trace("    cov: allocs + measure launched");
-    if (int rc = pr.scan32(keep, kidx, N + 1, false)) return rc;
-    uint32_t n_keep = 0;
-    HIP_TRY(hipMemcpyAsync(&n_keep, kidx + N, 4, hipMemcpyDeviceToHost, st));
-    hipLaunchKernelGGL(msnv_gather_u32, grid_for(S + 1, 64), dim3(64), 0, st, kidx, ivs, (uint32_t)(S + 1), cvb);
-    HIP_TRY(hipGetLastError());
-    std::vector<uint32_t> cvb_h(S + 1);
-    HIP_TRY(hipMemcpyAsync(cvb_h.data(), cvb, (S + 1) * 4, hipMemcpyDeviceToHost, st));
-    // ---- the (sample, tile) runs: a dense table of minima / maxima when it is small beside the interval list (MSNV_COV_INDEX=sort|dense forces one)
-    const unsigned long long n_tab = (unsigned long long)S * ds.n_tiles;
-    const bool dense_tab = cov_dense_form(ds, N);
-    if (dense_tab) {
-        d.n_cov_iv = 0;
-        if (int rc = dev_alloc((void **)&d.cov_iv, ((uint64_t)N + 4) * sizeof(Pair32), &d.device_bytes)) return rc;      // (N >= the kept ones: no wait for their count)
-        DevBuf tab;
-        const unsigned long long b_t = up((n_tab + 1) * 4);
-        if (int rc = tab.alloc(4 * b_t)) return rc;
-        uint32_t *lo = tab.as<uint32_t>(), *hi = reinterpret_cast<uint32_t *>(tab.as<uint8_t>() + b_t), *flag = reinterpret_cast<uint32_t *>(tab.as<uint8_t>() + 2 * b_t),
-                 *rid = reinterpret_cast<uint32_t *>(tab.as<uint8_t>() + 3 * b_t);
-        HIP_TRY(hipMemsetAsync(lo, 0xff, b_t, st));
-        HIP_TRY(hipMemsetAsync(hi, 0, b_t, st));
-        unsigned long long o = 0;
-        for (const DevRound &r : ds.dp.rounds) {
-            if (r.n_iv) {
-                hipLaunchKernelGGL(msnv_fin_cov_emit_dense, grid_for(r.n_iv, 256), dim3(256), 0, st, r.cov_tid, r.cov_beg, r.cov_end, (unsigned long long)r.n_iv, o, ctg, tb, ivs, (uint32_t)S,
-                                   keep, kidx, ds.n_tiles, d.cov_iv, lo, hi);
-                HIP_TRY(hipGetLastError());
-            }
-            o += r.n_iv;
-        }
-        hipLaunchKernelGGL(msnv_fin_cov_dense_flags, grid_for(n_tab + 1, 256), dim3(256), 0, st, hi, n_tab, flag);
-        HIP_TRY(hipGetLastError());
-        if (int rc = pr.scan32(flag, rid, n_tab + 1, false)) return rc;
-        uint32_t n_runs = 0;
-        HIP_TRY(hipMemcpyAsync(&n_runs, rid + n_tab, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));                               // (n_keep and the per-sample bases arrive with it)
-        for (size_t s = 0; s <= S; ++s) cvbase[s] = cvb_h[s];
-        d.n_cov_iv = n_keep;
-        HIP_TRY(hipMemsetAsync(d.cov_iv + n_keep, 0, 4 * sizeof(Pair32), st));              // behind the last interval: what the idle lanes of msnv_coverage_tiles load
-        DevBuf runs;
-        if (int rc = runs.alloc(std::max<uint64_t>(1, n_runs) * sizeof(DevCovPair))) return rc;
-        hipLaunchKernelGGL(msnv_fin_cov_dense_runs, grid_for(n_tab, 256), dim3(256), 0, st, lo, hi, rid, n_tab, ds.n_tiles, runs.as<DevCovPair>());
-        HIP_TRY(hipGetLastError());
-        cp.resize(n_runs);
-        if (n_runs) HIP_TRY(hipMemcpyAsync(cp.data(), runs.p, (size_t)n_runs * sizeof(DevCovPair), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        fin_trace("    cov: dense table, runs (sync)");
-        return MSNV_OK;
-    }
-    // entry slots: exclusive scan of the tile counts, in place of `keep` (no longer needed once kidx exists)
-    unsigned long long n_ent64 = 0;
-    {
-        DevBuf tot;
-        if (int rc = tot.alloc(16)) return rc;
-        // (a 64-bit total first: the 32-bit scan below must not wrap)
-        size_t need = 0;
-        HIP_TRY(rocprim::reduce(nullptr, need, ntile, tot.as<unsigned long long>(), 0ull, (size_t)N, rocprim::plus<unsigned long long>(), st));
-        if (int rc = pr.room(need)) return rc;
-        HIP_TRY(rocprim::reduce(pr.buf, need, ntile, tot.as<unsigned long long>(), 0ull, (size_t)N, rocprim::plus<unsigned long long>(), st));
-        HIP_TRY(hipMemcpyAsync(&n_ent64, tot.p, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    fin_trace("    cov: scans + reduce (sync)");
-    if (n_ent64 > 0xfffffff0ull) return fail(MSNV_EDOMAIN, "more than 2^32 (interval, tile) entries in one shard");
-    const uint32_t n_ent = (uint32_t)n_ent64;
-    uint32_t *ebase = keep;
-    if (int rc = pr.scan32(ntile, ebase, N + 1, false)) return rc;
-    for (size_t s = 0; s <= S; ++s) cvbase[s] = cvb_h[s];
-    d.n_cov_iv = n_keep;
-    if (int rc = dev_alloc((void **)&d.cov_iv, ((uint64_t)n_keep + 4) * sizeof(Pair32), &d.device_bytes)) return rc;
-    HIP_TRY(hipMemsetAsync(d.cov_iv + n_keep, 0, 4 * sizeof(Pair32), st));                  // behind the last interval: what the idle lanes of msnv_coverage_tiles load
-    DevBuf ent;
-    const unsigned long long b_k = up(((unsigned long long)n_ent + 1) * 8), b_v = up(((unsigned long long)n_ent + 1) * 4);
-    if (int rc = ent.alloc(2 * b_k + 2 * b_v)) return rc;
-    unsigned long long *ekey = ent.as<unsigned long long>(), *skey = reinterpret_cast<unsigned long long *>(ent.as<uint8_t>() + b_k);
-    uint32_t *eval = reinterpret_cast<uint32_t *>(ent.as<uint8_t>() + 2 * b_k), *sval = reinterpret_cast<uint32_t *>(ent.as<uint8_t>() + 2 * b_k + b_v);
-    {
-        unsigned long long o = 0;
-        for (const DevRound &r : ds.dp.rounds) {
-            if (r.n_iv) {
-                hipLaunchKernelGGL(msnv_fin_cov_emit, grid_for(r.n_iv, 256), dim3(256), 0, st, r.cov_tid, r.cov_beg, r.cov_end, (unsigned long long)r.n_iv, o, ctg, tb, ivs, (uint32_t)S,
-                                   ntile + o, kidx, ebase + o, d.cov_iv, ekey, eval);
-                HIP_TRY(hipGetLastError());
-            }
-            o += r.n_iv;
-        }
-    }
-    fin_trace("    cov: allocs + emit launched");
-    if (n_ent) {
-        if (int rc = pr.sort64(ekey, skey, eval, sval, n_ent, 32u + std::max(1u, bit_width_u64(S)))) return rc;
-        // runs of equal (sample, tile): flags and their scan in the unsorted arrays' memory (dead behind the sort)
-        uint32_t *flag = eval, *rid = reinterpret_cast<uint32_t *>(ekey);
-        hipLaunchKernelGGL(msnv_pair_flags, grid_for(n_ent, 256), dim3(256), 0, st, skey, n_ent, flag);
-        HIP_TRY(hipGetLastError());
-        if (int rc = pr.scan32(flag, rid, n_ent, true)) return rc;
-        uint32_t n_runs = 0;
-        HIP_TRY(hipMemcpyAsync(&n_runs, rid + (n_ent - 1), 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        DevBuf runs;
-        if (int rc = runs.alloc((uint64_t)n_runs * sizeof(DevCovPair))) return rc;
-        hipLaunchKernelGGL(msnv_fin_cov_runs, grid_for(n_ent, 256), dim3(256), 0, st, skey, sval, flag, rid, (unsigned long long)n_ent, runs.as<DevCovPair>());
-        HIP_TRY(hipGetLastError());
-        cp.resize(n_runs);
-        HIP_TRY(hipMemcpyAsync(cp.data(), runs.p, (size_t)n_runs * sizeof(DevCovPair), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        fin_trace("    cov: sort + runs (sync)");
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    return MSNV_OK;
-}
-
-// ------------------------------------------------------------------------------------------ deep runs (pack.cpp: split_deep_runs)
-namespace {
-__device__ __forceinline__ int wave_inclusive_scan_int(int v) {
-    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(v, o); if ((int)(threadIdx.x & 63u) >= o) v += y; }
-    return v;
-}
-constexpr uint32_t DEEP_G_CAP = 512;                              // groups a run may be dealt into (depth cap 65535 / group depth 128)
-struct DevDeepRun { unsigned long long piece0; uint32_t n, pad; };   // pieces [piece0, piece0 + n) of a ROUND's header array
-struct DevDeepOut { uint32_t G, exact; };                            // G = 1: not split, `exact` is the run's true depth; G > 1: dealt into G groups (their depths in gmax); G = 0: too many groups
-// largest per-position depth of the pieces g, g + G, g + 2G, ... of the run (one workgroup of 256, a difference array of the tile in LDS)
-__device__ uint32_t deep_sweep(const ReadHdr *h, const uint32_t n, const uint32_t G, const uint32_t g, int *diff, int *wsum) {
-    const int tid = threadIdx.x;
-    for (int i = tid; i < (int)TILE + 8; i += 256) diff[i] = 0;
-    __syncthreads();
-    for (uint32_t j = g + G * (uint32_t)tid; j < n; j += G * 256u) {
-        const ReadHdr x = h[j];
-        const uint32_t s0 = x.gpos % TILE;
-        atomicAdd(&diff[s0], 1); atomicAdd(&diff[s0 + x.cig], -1);
-    }
-    __syncthreads();
-    int v[8], sum = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { v[k] = diff[8 * tid + k]; sum += v[k]; }
-    const int incl = wave_inclusive_scan_int(sum);
-    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
-    __syncthreads();
-    int base = incl - sum;
-    for (int w = 0; w < (tid >> 6); ++w) base += wsum[w];
-    int m = 0, cur = base;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { cur += v[k]; m = cur > m ? cur : m; }
-    for (int o = 32; o > 0; o >>= 1) { const int y = __shfl_down(m, o); m = y > m ? y : m; }
-    __syncthreads();
-    if ((tid & 63) == 0) wsum[4 + (tid >> 6)] = m;
-    __syncthreads();
-    const int r = max(max(wsum[4], wsum[5]), max(wsum[6], wsum[7]));
-    __syncthreads();
-    return (uint32_t)r;
-}
-__global__ __launch_bounds__(256) void msnv_fin_deep_sweep(const ReadHdr *hdr, const DevDeepRun *runs, uint32_t split_at, uint32_t group_depth, DevDeepOut *outs, uint32_t *gmax) {
-    __shared__ int diff[TILE + 8];
-    __shared__ int wsum[8];
-    const DevDeepRun r = runs[blockIdx.x];
-    const ReadHdr *h = hdr + r.piece0;
-    uint32_t *gm = gmax + (size_t)blockIdx.x * DEEP_G_CAP;
-    const uint32_t exact = deep_sweep(h, r.n, 1u, 0u, diff, wsum);
-    if (exact < split_at) { if (threadIdx.x == 0) outs[blockIdx.x] = DevDeepOut{1u, exact}; return; }
-    uint32_t G = exact / group_depth + 1u;
-    for (;; ++G) {
-        if (G > DEEP_G_CAP) { if (threadIdx.x == 0) outs[blockIdx.x] = DevDeepOut{0u, exact}; return; }
-        uint32_t worst = 0;
-        for (uint32_t g = 0; g < G; ++g) { const uint32_t d = deep_sweep(h, r.n, G, g, diff, wsum); if (threadIdx.x == 0) gm[g] = d; worst = d > worst ? d : worst; }
-        if (worst < NARROW_MAX_DEPTH) break;
-    }
-    if (threadIdx.x == 0) outs[blockIdx.x] = DevDeepOut{G, exact};
-}
-// where the piece that ends up at position j of a split run comes from: groups one after the other, a group's pieces in their old order
-struct DevDeepPerm { unsigned long long piece0; uint32_t n, G; };
-__global__ void msnv_fin_deep_perm(const DevDeepPerm *runs, uint32_t *src) {
-    const DevDeepPerm r = runs[blockIdx.x];
-    const uint32_t q = r.n / r.G, rem = r.n % r.G;
-    for (uint32_t k = threadIdx.x; k < r.n; k += blockDim.x) {
-        const uint32_t g = k % r.G, newpos = g * q + (g < rem ? g : rem) + k / r.G;
-        src[r.piece0 + newpos] = (uint32_t)(r.piece0 + k);
-    }
-}
-__global__ void msnv_iota(uint32_t *a, unsigned long long n) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) a[i] = (uint32_t)i;
-}
-__global__ void msnv_fin_stored(const ReadHdr *hdr, unsigned long long n, uint32_t *out) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i <= n) out[i] = i < n ? stored_bytes(hdr[i].cig) : 0u;
-}
-// a sample's columns re-laid in header order: 4 lanes per piece, 32 stored nibbles per lane, from the old offsets to the new
-__global__ __launch_bounds__(256) void msnv_fin_relayout(ReadHdr *hdr, unsigned long long n_pieces, const uint32_t *new_off, const uint8_t *old_seq, const uint8_t *old_qual,
-                                                         uint8_t *new_seq, uint8_t *new_qual) {
-    const unsigned long long gt = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const unsigned long long pc = gt >> 2; const uint32_t sub = (uint32_t)gt & 3u;
-    ReadHdr h{}; uint32_t sb = 0, noff = 0;
-    if (pc < n_pieces) { h = hdr[pc]; sb = stored_bytes(h.cig); noff = new_off[pc]; }
-    const uint32_t st = 2u * sb > 32u * sub ? (2u * sb - 32u * sub < 32u ? 2u * sb - 32u * sub : 32u) : 0u;
-    uint64_t o0 = 0, o1 = 0; uint32_t bits = 0;
-    if (st) {
-        const uint8_t *sp = old_seq + h.seqoff + 16u * sub;
-        o0 = ld64(sp); o1 = ld64(sp + 8);
-        const unsigned long long b = 2ull * h.seqoff + 32u * sub;
-        bits = (uint32_t)(ld64(old_qual + (b >> 3)) >> (uint32_t)(b & 7ull));
-    }
-    const uint32_t prev_last = __shfl_up(bits >> 28, 1);
-    if (st) put_piece_lane(new_seq, new_qual, noff, sub, sb, st, o0, o1, bits, prev_last);
-    if (st && sub == 0) hdr[pc].seqoff = noff;                     // (every lane of the piece has read its header by now: the loads sit above the shuffle)
-}
-}  // namespace
-
-int devfin_deep_runs(msnv_dataset &ds, uint32_t split_at, uint32_t group_depth, bool *fallback) {
-    *fallback = false;
-    hipStream_t st = (hipStream_t)ds.ctx->stream;
-    DevPackTables &T = ds.dp;
-    const size_t S = ds.samples.size();
-    // ---- the runs whose bound reaches split_at, round by round
-    struct Ref { size_t sample, pair; };
-    std::vector<std::vector<DevDeepRun>> runs(T.rounds.size());
-    std::vector<std::vector<Ref>> refs(T.rounds.size());
-    for (size_t s = 0; s < S; ++s) {
-        const SampleCols &sc = ds.samples[s];
-        for (size_t k = 0; k < sc.dev_pairs.size(); ++k) if (sc.dev_pairs[k].maxd >= split_at) {
-            runs[(size_t)sc.dev_round].push_back(DevDeepRun{sc.dev_piece0 + sc.dev_pairs[k].lo, sc.dev_pairs[k].hi - sc.dev_pairs[k].lo, 0u});
-            refs[(size_t)sc.dev_round].push_back(Ref{s, k});
-        }
-    }
-    std::vector<uint8_t> split_sample(S, 0);
-    std::vector<std::vector<DevDeepPerm>> perms(T.rounds.size());
-    struct NewPairs { size_t pair; uint32_t G; std::vector<uint32_t> gmax; };
-    std::vector<std::vector<NewPairs>> edits(S);
-    for (size_t r = 0; r < T.rounds.size(); ++r) {
-        const size_t n = runs[r].size();
-        if (!n) continue;
-        DevBuf d_runs, d_outs, d_gmax;
-        if (int rc = d_runs.alloc(n * sizeof(DevDeepRun))) return rc;
-        if (int rc = d_outs.alloc(n * sizeof(DevDeepOut))) return rc;
-        if (int rc = d_gmax.alloc(n * DEEP_G_CAP * 4)) return rc;
-        HIP_TRY(hipMemcpyAsync(d_runs.p, runs[r].data(), n * sizeof(DevDeepRun), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(msnv_fin_deep_sweep, dim3((unsigned)n), dim3(256), 0, st, T.rounds[r].hdr, d_runs.as<DevDeepRun>(), split_at, group_depth, d_outs.as<DevDeepOut>(), d_gmax.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-        std::vector<DevDeepOut> outs(n);
-        std::vector<uint32_t> gmax(n * DEEP_G_CAP);
-        HIP_TRY(hipMemcpyAsync(outs.data(), d_outs.p, n * sizeof(DevDeepOut), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(gmax.data(), d_gmax.p, n * DEEP_G_CAP * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (size_t i = 0; i < n; ++i) {
-            const Ref ref = refs[r][i];
-            SampleCols &sc = ds.samples[ref.sample];
-            if (outs[i].G == 0u) { *fallback = true; return MSNV_OK; }
-            if (outs[i].G == 1u) { sc.dev_pairs[ref.pair].maxd = outs[i].exact; continue; }      // the start-time bound was pessimistic
-            split_sample[ref.sample] = 1;
-            ++T.n_deep_runs_split;
-            perms[r].push_back(DevDeepPerm{runs[r][i].piece0, runs[r][i].n, outs[i].G});
-            edits[ref.sample].push_back(NewPairs{ref.pair, outs[i].G, std::vector<uint32_t>(gmax.begin() + i * DEEP_G_CAP, gmax.begin() + i * DEEP_G_CAP + outs[i].G)});
-        }
-    }
-    // ---- the pair lists of the samples with split runs: a run of n pieces in G groups becomes G pairs (group g: the pieces g, g + G, ...)
-    for (size_t s = 0; s < S; ++s) {
-        if (edits[s].empty()) continue;
-        SampleCols &sc = ds.samples[s];
-        std::vector<DevPair> np;
-        size_t e = 0;
-        for (size_t k = 0; k < sc.dev_pairs.size(); ++k) {
-            const DevPair p = sc.dev_pairs[k];
-            if (e < edits[s].size() && edits[s][e].pair == k) {
-                const uint32_t n = p.hi - p.lo, G = edits[s][e].G, q = n / G, rem = n % G;
-                uint32_t lo = p.lo;
-                for (uint32_t g = 0; g < G; ++g) { const uint32_t cnt = q + (g < rem ? 1u : 0u); if (cnt) np.push_back(DevPair{p.tid, p.tile, lo, lo + cnt, edits[s][e].gmax[g], 1u + g}); lo += cnt; }
-                ++e;
-            } else np.push_back(p);
-        }
-        sc.dev_pairs.swap(np);
-    }
-    // ---- headers of the split runs group by group, then the columns of their samples in header order
-    for (size_t r = 0; r < T.rounds.size(); ++r) {
-        if (perms[r].empty()) continue;
-        DevRound &R = T.rounds[r];
-        DevBuf d_perm, d_src;
-        if (int rc = d_perm.alloc(perms[r].size() * sizeof(DevDeepPerm))) return rc;
-        if (int rc = d_src.alloc((R.n_pieces + 1) * 4)) return rc;
-        HIP_TRY(hipMemcpyAsync(d_perm.p, perms[r].data(), perms[r].size() * sizeof(DevDeepPerm), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(msnv_iota, grid_for(R.n_pieces, 256), dim3(256), 0, st, d_src.as<uint32_t>(), (unsigned long long)R.n_pieces);
-        hipLaunchKernelGGL(msnv_fin_deep_perm, dim3((unsigned)perms[r].size()), dim3(256), 0, st, d_perm.as<DevDeepPerm>(), d_src.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-        // the round's headers through the permutation, into a buffer of their own (the intervals stay where they are)
-        const uint64_t b_hdr = R.n_pieces * sizeof(ReadHdr), b_4 = ((R.n_pieces * 4) + 15) & ~15ull, b_2 = ((R.n_pieces * 2) + 15) & ~15ull;
-        void *nb = nullptr;
-        if (int rc = dev_alloc(&nb, b_hdr + 2 * b_4 + b_2 + 64, nullptr)) return rc;
-        uint8_t *q = static_cast<uint8_t *>(nb);
-        ReadHdr *h2 = reinterpret_cast<ReadHdr *>(q); q += b_hdr;
-        int32_t *t2 = reinterpret_cast<int32_t *>(q); q += b_4;
-        int32_t *e2 = reinterpret_cast<int32_t *>(q); q += b_4;
-        uint16_t *d2 = reinterpret_cast<uint16_t *>(q);
-        hipLaunchKernelGGL(msnv_gather_pieces, grid_for(R.n_pieces, 256), dim3(256), 0, st, d_src.as<uint32_t>(), (uint32_t)R.n_pieces, R.hdr, R.tid, R.end, R.depth, h2, t2, e2, d2);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(st));
-        T.round_bufs.push_back(R.buf);                             // (the old buffer still holds the round's intervals; freed with the columns)
-        R.buf = nb; R.hdr = h2; R.tid = t2; R.end = e2; R.depth = d2;
-    }
-    Prim pr(st);
-    for (size_t s = 0; s < S; ++s) {
-        if (!split_sample[s]) continue;
-        SampleCols &sc = ds.samples[s];
-        DevRound &R = T.rounds[(size_t)sc.dev_round];
-        ReadHdr *h = R.hdr + sc.dev_piece0;
-        const unsigned long long n = sc.n_dev_pieces;
-        DevBuf d_st, d_off;
-        if (int rc = d_st.alloc((n + 1) * 4)) return rc;
-        if (int rc = d_off.alloc((n + 1) * 4)) return rc;
-        hipLaunchKernelGGL(msnv_fin_stored, grid_for(n + 1, 256), dim3(256), 0, st, h, n, d_st.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-        if (int rc = pr.scan32(d_st.as<uint32_t>(), d_off.as<uint32_t>(), n + 1, false)) return rc;
-        const uint64_t seq_bytes = (sc.d_seq_bytes + 15) & ~15ull, qual_bytes = seq_bytes / 4;
-        void *nb = nullptr;
-        if (int rc = dev_alloc(&nb, seq_bytes + qual_bytes + 64, nullptr)) return rc;
-        T.round_bufs.push_back(nb);
-        uint8_t *nseq = static_cast<uint8_t *>(nb), *nqual = nseq + seq_bytes;
-        HIP_TRY(hipMemsetAsync(nseq, 0xff, seq_bytes, st));
-        HIP_TRY(hipMemsetAsync(nqual, 0, qual_bytes + 64, st));
-        hipLaunchKernelGGL(msnv_fin_relayout, grid_for(n * 4, 256), dim3(256), 0, st, h, n, d_off.as<uint32_t>(), sc.d_seq, sc.d_qual, nseq, nqual);
-        HIP_TRY(hipGetLastError());
-        // tail: 32 bytes of N (the memset) and their flags
-        const msnv_params &MP = ds.params;
-        DpParams P{}; P.c_eff = std::min(std::max(MP.min_baseq, -127), 127); P.all_low = MP.min_baseq > 127;
-        const DpSampleDst dst{nseq, nqual, 0ull, 0u, 0u};
-        const unsigned long long piece_bytes = sc.d_seq_bytes - 32;
-        DevBuf d_dst, d_pb;
-        if (int rc = d_dst.alloc(sizeof(DpSampleDst))) return rc;
-        if (int rc = d_pb.alloc(8)) return rc;
-        HIP_TRY(hipMemcpyAsync(d_dst.p, &dst, sizeof dst, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_pb.p, &piece_bytes, 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(msnv_emit_tail, dim3(1), dim3(64), 0, st, d_dst.as<DpSampleDst>(), d_pb.as<unsigned long long>(), 1u, P);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(st));
-        sc.d_seq = nseq; sc.d_qual = nqual;
-    }
-    return MSNV_OK;
-}
-
-// ------------------------------------------------------------------------------------------ dense block streams (short reads)
-// pack.cpp: relayout_dense as kernels.  A run's stream is cut into blocks of 32 bases: a piece starts on an even base, opens a fresh block
-// when the block it would start in already holds a second segment or when it would end inside that block.  One thread walks one run (the
-// rule is sequential inside a run): first to count the run's blocks, then -- block bases known -- to write descriptors and the pieces' new
-// offsets; the bases and flags move with four lanes per piece.
-namespace {
-struct DevDenseRun { unsigned long long piece0; uint32_t n, blk0, seq0, pad; };        // blk0: index into the round's block array; seq0: byte offset of the run in its sample's seq column
-template <bool WRITE>
-__device__ __forceinline__ uint32_t dense_walk(const ReadHdr *h, uint32_t n, uint32_t seq0, uint32_t *blk, uint32_t *new_off) {
-    uint32_t cursor = 0, nblk = 0, lastw = BLK_EMPTY;                                   // lastw: descriptor of block nblk - 1, not yet written
-    for (uint32_t k = 0; k < n; ++k) {
-        const uint32_t len = h[k].cig, P = h[k].gpos % TILE;
-        cursor = (cursor + 1u) & ~1u;
-        uint32_t o = cursor & 31u;
-        if (o != 0u) {                                                                  // (then the block holding `cursor` is block nblk - 1)
-            const bool has_b = ((lastw >> 17) & 0xfffu) != BLK_NO_B;
-            if (has_b || len < 32u - o) { cursor = ((cursor >> 5) + 1u) << 5; o = 0u; }
-        }
-        if (WRITE) new_off[k] = seq0 + (cursor >> 1);
-        uint32_t done = 0;
-        if (o != 0u) {                                                                  // the head of the piece = segment B of the open block
-            lastw = (lastw & ~(0xfffu << 17)) | ((P - o + 32u) << 17);
-            done = 32u - o;
-            if (done == len) lastw |= BLK_END_B;
-        }
-        bool first = o == 0u;
-        while (done < len) {
-            const uint32_t na = len - done < 32u ? len - done : 32u;
-            if (WRITE && nblk) blk[nblk - 1u] = lastw;
-            ++nblk;
-            lastw = BLK_EMPTY | (P + done) | na << 11 | (first ? BLK_START_A : 0u) | (done + na == len ? BLK_END_A : 0u);
-            first = false; done += na;
-        }
-        cursor += len;
-    }
-    if (WRITE && nblk) blk[nblk - 1u] = lastw;
-    return nblk;
-}
-__global__ void msnv_fin_dense_count(const ReadHdr *hdr, const DevDenseRun *runs, uint32_t n_runs, uint32_t *nblk) {
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_runs) return;
-    nblk[r] = dense_walk<false>(hdr + runs[r].piece0, runs[r].n, 0u, nullptr, nullptr);
-}
-__global__ void msnv_fin_dense_place(const ReadHdr *hdr, const DevDenseRun *runs, uint32_t n_runs, uint32_t *blk, uint32_t *new_off) {
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_runs) return;
-    const DevDenseRun R = runs[r];
-    dense_walk<true>(hdr + R.piece0, R.n, R.seq0, blk + R.blk0, new_off + R.piece0);
-}
-// bits [b0, b0 + n) of a flag column := the n low bits of v (n <= 32).  The column was filled with `ones` everywhere; whole bytes are stored,
-// the bytes shared with a neighbour get ONE atomic (clear what must be 0, or set what must be 1).
-__device__ __forceinline__ void and_byte(uint8_t *p, uint32_t v) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-    const uint32_t sh = 8u * (uint32_t)(a & 3u);
-    atomicAnd(reinterpret_cast<uint32_t *>(a & ~(uintptr_t)3), ~(0xffu << sh) | v << sh);
-}
-__device__ __forceinline__ void put_flag_bits(uint8_t *col, unsigned long long b0, uint32_t n, uint32_t v, bool ones) {
-    uint8_t *p = col + (b0 >> 3);
-    const uint32_t sh = (uint32_t)(b0 & 7ull);
-    const uint64_t m = (n < 32u ? (1ull << n) - 1ull : 0xffffffffull) << sh, w = ((uint64_t)v << sh) & m;
-    const uint32_t nbytes = (sh + n + 7u) >> 3;
-    for (uint32_t k = 0; k < nbytes; ++k) {
-        const uint32_t mb = (uint32_t)(m >> (8u * k)) & 0xffu, wb = (uint32_t)(w >> (8u * k)) & 0xffu;
-        if (mb == 0xffu) p[k] = (uint8_t)wb;
-        else if (ones) and_byte(p + k, (~mb | wb) & 0xffu);
-        else if (wb) or_byte(p + k, wb);
-    }
-}
-// the pieces of one sample into its dense columns: 4 lanes per piece, 32 bases per lane, nothing but the real bases moves
-__global__ __launch_bounds__(256) void msnv_fin_dense_copy(ReadHdr *hdr, unsigned long long n_pieces, const uint32_t *new_off, const uint8_t *old_seq, const uint8_t *old_qual,
-                                                           uint8_t *new_seq, uint8_t *new_qual, uint32_t ones) {
-    const unsigned long long gt = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const unsigned long long pc = gt >> 2; const uint32_t sub = (uint32_t)gt & 3u, j0 = 32u * sub;
-    ReadHdr h{}; uint32_t noff = 0;
-    if (pc < n_pieces) { h = hdr[pc]; noff = new_off[pc]; }
-    const uint32_t have = h.cig > j0 ? (h.cig - j0 < 32u ? h.cig - j0 : 32u) : 0u;
-    if (have) {
-        const uint8_t *sp = old_seq + h.seqoff + 16u * sub;
-        uint64_t o0 = ld64(sp), o1 = ld64(sp + 8);
-        if (have & 1u) { if (have < 16u) o0 |= 0xfull << (4u * have); else o1 |= 0xfull << (4u * (have - 16u)); }      // the pad nibble of an odd piece reads as N
-        const uint32_t nb = (have + 1u) >> 1;
-        uint8_t *dp = new_seq + noff + 16u * sub;
-        store_bytes(dp, o0, nb < 8u ? nb : 8u);
-        if (nb > 8u) store_bytes(dp + 8, o1, nb - 8u);
-        const unsigned long long b = 2ull * h.seqoff + j0;
-        const uint32_t bits = (uint32_t)(ld64(old_qual + (b >> 3)) >> (uint32_t)(b & 7ull));
-        put_flag_bits(new_qual, 2ull * noff + j0, have, bits, ones != 0u);
-    }
-    if (have && sub == 0) hdr[pc].seqoff = noff;                   // (the four lanes of a piece sit in one wavefront: all of them have read the header)
-}
-}  // namespace
-
-int devfin_dense(msnv_dataset &ds) {
-    hipStream_t st = (hipStream_t)ds.ctx->stream;
-    DevPackTables &T = ds.dp;
-    const size_t S = ds.samples.size();
-    const msnv_params &MP = ds.params;
-    const bool ones = std::min(std::max(MP.min_baseq, -127), 127) > 0 || MP.min_baseq > 127;      // what a padding byte's flag is (pack.cpp: pack_lowq of a 0 byte)
-    for (size_t r = 0; r < T.rounds.size(); ++r) {
-        DevRound &R = T.rounds[r];
-        std::vector<DevDenseRun> runs;
-        std::vector<size_t> s_of;                                    // samples of this round, in order
-        for (size_t s = 0; s < S; ++s) if (ds.samples[s].dev_index && (size_t)ds.samples[s].dev_round == r) {
-            s_of.push_back(s);
-            for (const DevPair &p : ds.samples[s].dev_pairs) runs.push_back(DevDenseRun{ds.samples[s].dev_piece0 + p.lo, p.hi - p.lo, 0u, 0u, 0u});
-        }
-        if (s_of.empty()) continue;
-        const size_t n = runs.size();
-        std::vector<uint32_t> nblk(n, 0);
-        DevBuf d_runs, d_nblk, d_off;
-        if (n) {
-            if (int rc = d_runs.alloc(n * sizeof(DevDenseRun))) return rc;
-            if (int rc = d_nblk.alloc(n * 4)) return rc;
-            HIP_TRY(hipMemcpyAsync(d_runs.p, runs.data(), n * sizeof(DevDenseRun), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(msnv_fin_dense_count, grid_for(n, 64), dim3(64), 0, st, R.hdr, d_runs.as<DevDenseRun>(), (uint32_t)n, d_nblk.as<uint32_t>());
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(nblk.data(), d_nblk.p, n * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        }
-        // block bases: per sample (run_* as relayout_dense leaves them), and where the sample's blocks and columns sit in the round's buffers
-        std::vector<uint64_t> blk_at(s_of.size() + 1, 0), col_at(s_of.size() + 1, 0);
-        size_t k = 0;
-        for (size_t i = 0; i < s_of.size(); ++i) {
-            SampleCols &sc = ds.samples[s_of[i]];
-            sc.run_blk_lo.clear(); sc.run_nblk.clear(); sc.run_seq0.clear();
-            uint64_t b = 0;
-            for (size_t j = 0; j < sc.dev_pairs.size(); ++j, ++k) {
-                if (b + nblk[k] > 0x07ffffffull) return fail(MSNV_EDOMAIN, "a sample's dense block stream exceeds 2^27 blocks");
-                runs[k].blk0 = (uint32_t)(blk_at[i] + b); runs[k].seq0 = (uint32_t)(16u * b);
-                sc.run_blk_lo.push_back((uint32_t)b); sc.run_nblk.push_back(nblk[k]); sc.run_seq0.push_back((uint32_t)(16u * b));
-                b += nblk[k];
-            }
-            if (blk_at[i] + b > 0xfffffff0ull) return fail(MSNV_EDOMAIN, "more than 2^32 dense blocks in one round");
-            blk_at[i + 1] = blk_at[i] + b;
-            const uint64_t seq_bytes = 16ull * b + 32ull;            // + the tail padding
-            col_at[i + 1] = col_at[i] + ((seq_bytes + seq_bytes / 4 + 64ull + 15ull) & ~15ull);
-        }
-        void *colbuf = nullptr, *blkbuf = nullptr;
-        if (int rc = dev_alloc(&colbuf, col_at.back() + 64, nullptr)) return rc;
-        T.round_bufs.push_back(colbuf);
-        if (int rc = dev_alloc(&blkbuf, (blk_at.back() + 1) * 4, nullptr)) return rc;
-        T.round_bufs.push_back(blkbuf);
-        if (n) {
-            if (int rc = d_off.alloc((R.n_pieces + 1) * 4)) return rc;
-            HIP_TRY(hipMemcpyAsync(d_runs.p, runs.data(), n * sizeof(DevDenseRun), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(msnv_fin_dense_place, grid_for(n, 64), dim3(64), 0, st, R.hdr, d_runs.as<DevDenseRun>(), (uint32_t)n, static_cast<uint32_t *>(blkbuf), d_off.as<uint32_t>());
-            HIP_TRY(hipGetLastError());
-        }
-        for (size_t i = 0; i < s_of.size(); ++i) {
-            SampleCols &sc = ds.samples[s_of[i]];
-            const uint64_t seq_bytes = 16ull * (blk_at[i + 1] - blk_at[i]) + 32ull;
-            uint8_t *nseq = static_cast<uint8_t *>(colbuf) + col_at[i], *nqual = nseq + seq_bytes;
-            HIP_TRY(hipMemsetAsync(nseq, 0xff, seq_bytes, st));
-            HIP_TRY(hipMemsetAsync(nqual, ones ? 0xff : 0, seq_bytes / 4, st));
-            if (sc.n_dev_pieces) {
-                hipLaunchKernelGGL(msnv_fin_dense_copy, grid_for(sc.n_dev_pieces * 4, 256), dim3(256), 0, st, R.hdr + sc.dev_piece0, (unsigned long long)sc.n_dev_pieces,
-                                   d_off.as<uint32_t>() + sc.dev_piece0, sc.d_seq, sc.d_qual, nseq, nqual, ones ? 1u : 0u);
-                HIP_TRY(hipGetLastError());
-            }
-        }
-        HIP_TRY(hipStreamSynchronize(st));
-        for (size_t i = 0; i < s_of.size(); ++i) {
-            SampleCols &sc = ds.samples[s_of[i]];
-            const uint64_t seq_bytes = 16ull * (blk_at[i + 1] - blk_at[i]) + 32ull;
-            sc.d_seq = static_cast<uint8_t *>(colbuf) + col_at[i]; sc.d_qual = sc.d_seq + seq_bytes; sc.d_seq_bytes = seq_bytes;
-            sc.d_blk = static_cast<uint32_t *>(blkbuf) + blk_at[i]; sc.n_dev_blk = blk_at[i + 1] - blk_at[i];
-            ++T.n_dense_samples;
-        }
-    }
-    return MSNV_OK;
-}
-
-// The columns of a dataset whose samples were all packed here (piece layout, not the dense one): a round's buffer already IS the
-// dataset's layout for its samples, so one round's buffer is adopted as it stands (no copy at all) and several rounds' are copied
-// round by round; a sample whose columns were re-laid behind the pack (deep runs dealt into groups) is copied by itself.
-int devpack_place_columns(msnv_dataset &ds, DeviceCols &d, const std::vector<uint64_t> &sbase) {
-    hipStream_t st = (hipStream_t)ds.ctx->stream;
-    DevPackTables &T = ds.dp;
-    const size_t S = ds.samples.size();
-    auto in_place = [&](const DevRound &R) {
-        for (size_t k = 0; k < R.n_samples; ++k) {
-            const SampleCols &sc = ds.samples[R.first_sample + k];
-            if (sc.d_seq != R.col_seq + (sbase[R.first_sample + k] - sbase[R.first_sample]) || sc.d_qual != R.col_qual + (sbase[R.first_sample + k] - sbase[R.first_sample]) / 4) return false;
-        }
-        return sbase[R.first_sample + R.n_samples] - sbase[R.first_sample] == R.seq_total;
-    };
-    const bool guard = knob::guard_alloc();      // (guarded buffers end at the end of their mapping: no adoption of a buffer that holds two columns)
-    if (T.rounds.size() == 1 && T.rounds[0].first_sample == 0 && T.rounds[0].n_samples == S && in_place(T.rounds[0]) && !guard && !knob::no_adopt()) {
-        DevRound &R = T.rounds[0];
-        d.seq = R.col_seq; d.qual = R.col_qual;
-        d.blocks.emplace_back(R.col_buf, R.seq_total + COL_PAD + R.seq_total / 4 + 64);
-        d.device_bytes += R.seq_total + COL_PAD + R.seq_total / 4 + 64;
-        for (void *&p : T.round_bufs) if (p == R.col_buf) p = nullptr;
-        R.col_buf = nullptr;
-        T.n_columns_adopted += 1;
-        return MSNV_OK;
-    }
-    if (int rc = dev_alloc((void **)&d.seq, sbase[S] + COL_PAD, &d.device_bytes)) return rc;
-    if (int rc = dev_alloc((void **)&d.qual, sbase[S] / 4 + 64, &d.device_bytes)) return rc;
-    HIP_TRY(hipMemsetAsync(d.seq + sbase[S], 0xff, COL_PAD, st));
-    HIP_TRY(hipMemsetAsync(d.qual + sbase[S] / 4, 0, 64, st));
-    for (const DevRound &R : T.rounds) {
-        if (!R.n_samples) continue;
-        const uint64_t o = sbase[R.first_sample];
-        if (in_place(R)) {
-            if (R.seq_total) {
-                HIP_TRY(hipMemcpyAsync(d.seq + o, R.col_seq, R.seq_total, hipMemcpyDeviceToDevice, st));
-                HIP_TRY(hipMemcpyAsync(d.qual + o / 4, R.col_qual, R.seq_total / 4, hipMemcpyDeviceToDevice, st));
-            }
-            continue;
-        }
-        for (size_t k = 0; k < R.n_samples; ++k) {
-            const size_t s = R.first_sample + k;
-            const SampleCols &sc = ds.samples[s];
-            const uint64_t share = sbase[s + 1] - sbase[s];
-            HIP_TRY(hipMemsetAsync(d.seq + sbase[s], 0xff, share, st));
-            HIP_TRY(hipMemsetAsync(d.qual + sbase[s] / 4, 0, share / 4, st));
-            if (int rc = devpack_copy_columns(sc, d.seq + sbase[s], d.qual + sbase[s] / 4, st)) return rc;
-        }
-    }
-    return MSNV_OK;
-}
-
-int devpack_copy_blocks(const SampleCols &sc, uint32_t *dst, void *stream) {
-    if (sc.n_dev_blk) HIP_TRY(hipMemcpyAsync(dst, sc.d_blk, sc.n_dev_blk * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return MSNV_OK;
-}
-
-int devpack_finish(msnv_dataset &ds) {
-    if (!ds.dp.ready && ds.dp.round_bufs.empty()) return MSNV_OK;
-    if (int rc = devpack_sync_pending(ds)) return rc;
-    if (ds.ctx) HIP_TRY(hipStreamSynchronize((hipStream_t)ds.ctx->stream));
-    for (SampleCols &sc : ds.samples) { sc.d_seq = nullptr; sc.d_qual = nullptr; }
-    devpack_release(ds);
-    return MSNV_OK;
-}
-
-int devpack_fill_padding(DeviceCols &d, const std::vector<uint8_t> &sample_on_device, void *stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (!d.n_reads || sample_on_device.empty()) return MSNV_OK;
-    bool any = false, all = true;
-    for (uint8_t v : sample_on_device) { any |= v != 0; all &= v != 0; }
-    if (!any) return MSNV_OK;
-    if (all) {
-        // nothing to tell the kernel apart by, nothing to free behind it: it runs beside the host's coverage tables (round 5: the wait for it
-        // was 0.28 ms of finalize); whoever uses the columns next is on this stream
-        hipLaunchKernelGGL(msnv_fill_padding, grid_for(d.n_reads, 256), dim3(256), 0, st, d.hdr, (const unsigned long long *)d.s_read_base, (const unsigned long long *)d.s_seq_base,
-                           (const uint8_t *)nullptr, (uint32_t)sample_on_device.size(), (unsigned long long)d.n_reads, d.ref4, d.seq);
-        HIP_TRY(hipGetLastError());
-        return MSNV_OK;
-    }
-    DevBuf flags;
-    if (int rc = flags.alloc(sample_on_device.size())) return rc;
-    HIP_TRY(hipMemcpyAsync(flags.p, sample_on_device.data(), sample_on_device.size(), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(msnv_fill_padding, grid_for(d.n_reads, 256), dim3(256), 0, st, d.hdr, (const unsigned long long *)d.s_read_base, (const unsigned long long *)d.s_seq_base,
-                       flags.as<uint8_t>(), (uint32_t)sample_on_device.size(), (unsigned long long)d.n_reads, d.ref4, d.seq);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
     return MSNV_OK;
 }
 

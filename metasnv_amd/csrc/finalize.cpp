@@ -1,7 +1,7 @@
 // metasnv_amd/csrc/finalize.cpp -- a dataset's samples -> its tile index and device columns: every table the pileup, gate, gather and
 // coverage kernels read (device.h: DeviceCols).  finalize_dataset is a short driver over struct Finalize, whose member functions are the
 // stages in the order they run; where a stage has a host form (loops over the samples' staging, pack.cpp's output) and a device form
-// (devfin_* in devpack.hip, for datasets whose samples were all packed there), it picks by Finalize::R at its top.
+// (devfin_* in devfin.hip, for datasets whose samples were all packed on the device), it picks by Finalize::R at its top.
 #include <algorithm>
 #include <atomic>
 #include <climits>
@@ -10,6 +10,7 @@
 #include <thread>
 
 #include "device.h"
+#include "devfin.h"
 #include "devpack.h"
 #if defined(__SSE2__)
 #include <emmintrin.h>
@@ -256,7 +257,7 @@ struct Finalize {
     // ---- decide_route(), and the three flags that follow from it where the layout is known
     struct Route {
         // Device-packed samples (devpack.hip) keep their piece headers and intervals in HBM.  When every sample is one, the per-piece and
-        // per-interval loops run there as kernels (devfin_* in devpack.hip) and the host works on (sample, tile) pairs only.  Mixed datasets
+        // per-interval loops run there as kernels (devfin_* in devfin.hip) and the host works on (sample, tile) pairs only.  Mixed datasets
         // take the host loops: the headers come down first (MSNV_FINALIZE=host forces that; tests compare the two).
         bool fast = false;
         // layout_samples(): the dense block layout of short pieces (layout_dense), decided behind the host's deep-run split
@@ -372,7 +373,7 @@ int Finalize::decide_route() {
         for (const SampleCols &sc : ds.samples) { np += sc.n_dev_pieces; nb += sc.n_pileup_bases; }
         if (layout_dense(np, nb) && knob::dense_relayout_on_host()) R.fast = false;      // (the dense re-layout on host staging: tests compare the two)
         // deep (sample, tile) runs: their exact depth, and -- where a run really is that deep -- its pieces dealt into groups and the sample's
-        // columns re-laid, by kernels (devpack.hip: devfin_deep_runs; MSNV_DEEP_RELOCATE=0, a host-only experiment, takes the host loops)
+        // columns re-laid, by kernels (devfin.hip: devfin_deep_runs; MSNV_DEEP_RELOCATE=0, a host-only experiment, takes the host loops)
         const uint32_t split_at = deep_split_at();
         bool any_deep = false;
         for (const SampleCols &sc : ds.samples) for (const DevPair &p : sc.dev_pairs) if (p.maxd >= split_at) { any_deep = true; break; }
@@ -439,7 +440,7 @@ int Finalize::tile_layout() {
 
 int Finalize::launch_coverage() {
     if (R.fast) if (int rc = devfin_coverage_launch(ds, *d)) return rc;     // (the coverage index's kernels go first: they run while the host builds the pair tables)
-    if (R.fast && ds.dp.cov_launched && knob::cov_thread()) {
+    if (R.fast && ds.dp.fin.cov_launched && knob::cov_thread()) {
         cov_job.th = std::thread([this]() {
             (void)dev_set_device(device);
             try { cov_job.rc = coverage_tables(cov_arena, true); } catch (const std::exception &e) { cov_job.rc = fail_quiet(MSNV_ENOMEM, "coverage index: %s", e.what()); }
@@ -460,12 +461,12 @@ int Finalize::coverage_tables(TableArena &A, bool in_thread) {
     std::vector<CP> flat;                                        // all samples' (tile, sample) runs, sample after sample, tiles ascending inside a sample
     bool tables_on_device = false;                               // (round 6: devfin_coverage has cut the pair tables, the rows and the work items in HBM)
     if (R.fast) {
-        // the intervals are in HBM: filtered, made linear and grouped by (sample, tile) there (devpack.hip: devfin_coverage); the runs come
+        // the intervals are in HBM: filtered, made linear and grouped by (sample, tile) there (devfin.hip: devfin_coverage); the runs come
         // back sample-major with the tiles ascending, which is the order the loops below want
         std::vector<DevCovPair> cp;
         if (int rc = devfin_coverage(ds, *d, cvbase, cp)) return rc;
         if (!in_thread) fin_trace("  devfin_coverage");
-        tables_on_device = ds.dp.cov_tables_done;
+        tables_on_device = ds.dp.fin.cov_tables_done;
         flat.resize(cp.size());
         bool ordered = true;
         for (size_t i = 0; i < cp.size(); ++i) {
@@ -656,7 +657,7 @@ int Finalize::layout_samples() {
     R.dense = layout_dense(all_pieces, all_bases);
     d->dense = R.dense;
     if (R.dense && R.fast) {
-        if (int rc = devfin_dense(ds)) return rc;                    // devpack.hip: block streams, descriptors and run tables of every sample, in HBM
+        if (int rc = devfin_dense(ds)) return rc;                    // devfin.hip: block streams, descriptors and run tables of every sample, in HBM
     } else if (R.dense) {
         for (size_t s = 0; s < S; ++s) if (ds.samples[s].on_device) { if (int rc = dev_set_device(device)) return rc; if (int rc = devpack_sample_to_host(ds.samples[s])) return rc; }
         parallel_for(S, [&](size_t s) {
@@ -695,7 +696,7 @@ int Finalize::pairs_per_sample() {
             const uint64_t gs = (uint64_t)ds.tile_base[c] * TILE + sc.hdr[i].gpos;
             sc.hdr[i].gpos = (uint32_t)gs;
             const uint32_t t = (uint32_t)(gs / TILE);
-            if (!R.dense && !sc.on_device) {                       // (device-packed samples: devpack.hip msnv_fill_padding, once the columns are in place)
+            if (!R.dense && !sc.on_device) {                       // (device-packed samples: devfin.hip msnv_fill_padding, once the columns are in place)
                 // The alignment padding behind a piece (up to the next 16 bases) reads as the reference the kernel compares
                 // it with (N beyond the tile): msnv_pileup_tiles_narrow32 then masks mismatch flags per 16 bases, not per base.
                 const uint32_t len = sc.hdr[i].cig, stop = (len + 2u * SEQ_ALIGN - 1u) & ~(2u * SEQ_ALIGN - 1u);

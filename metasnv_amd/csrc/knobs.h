@@ -144,7 +144,7 @@ inline char alleles() { const char *e = getenv("MSNV_ALLELES"); return !e ? '\0'
 // list.  Per dataset (tests/test_gpu_parity.py forces the grow-and-rerun path).
 inline uint32_t cap_events(uint32_t by_dataset, long long min_events) { long long v = 0; return i64_of("MSNV_CAP_EVENTS", &v) ? (uint32_t)std::max(min_events, v) : by_dataset; }
 
-// ---------------------------------------------------------------------------------- finalize: the coverage index (finalize.cpp, devpack.hip)
+// ---------------------------------------------------------------------------------- finalize: the coverage index (finalize.cpp, devfin.hip)
 // MSNV_COV_INDEX=sort|dense: 'd' the dense table / 's' the sort form whatever the dataset's size; '\0' = by size.  Per dataset
 // (tests/test_gpu_finalize_routes.py::test_coverage_index_route).
 inline char cov_index() { const char c = first("MSNV_COV_INDEX"); return c == 'd' || c == 's' ? c : '\0'; }

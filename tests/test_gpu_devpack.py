@@ -45,8 +45,8 @@ def test_sparse_cohort_and_merged_groups_same_columns():
 
 def test_deep_runs_are_dealt_into_groups_and_short_reads_into_block_streams_on_the_device():
     """(sample, tile) runs deeper than the byte bins hold (finalize.cpp: split_deep_runs): exact sweep, round-robin groups, header permutation and
-    the re-layout of the sample's columns run as kernels (devpack.hip: devfin_deep_runs) and give the host stage's bytes; so does the dense
-    block layout of short reads (finalize.cpp: relayout_dense; devpack.hip: devfin_dense) -- descriptors, columns and run tables."""
+    the re-layout of the sample's columns run as kernels (devfin.hip: devfin_deep_runs) and give the host stage's bytes; so does the dense
+    block layout of short reads (finalize.cpp: relayout_dense; devfin.hip: devfin_dense) -- descriptors, columns and run tables."""
     syn, samples = synth_case(n_species=1, contig_len=4000, n_samples=3, mean_cov=300.0, sigma_cov=0.3, snv_density=0.02, seed=27)      # runs deeper than 192: dealt into groups
     _same_dataset(syn.names, syn.lengths, syn.seqs, samples)
     with _env(MSNV_PACK="device"):

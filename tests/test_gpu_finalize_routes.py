@@ -1,6 +1,6 @@
 """finalize's routes, each against the oracle and against the default route (KERNELS.md knobs).
 
-Coverage index (devpack.hip: devfin_coverage_launch / devfin_coverage, finalize.cpp: coverage_tables).  The routes and what is compared:
+Coverage index (devfin.hip: devfin_coverage_launch / devfin_coverage, finalize.cpp: coverage_tables).  The routes and what is compared:
   default          dense (sample, tile) table launched ahead, pair tables / rows / work items cut on the device (msnv_cov_*)
   tables_host      MSNV_COV_TABLES=host: the same runs, the pair tables by the host loops  -> cov_iv, cov_pairs, cov_work BYTE-identical
   late             MSNV_COV_LATE=1: the dense table built inside devfin_coverage, waiting   -> BYTE-identical (the same table, the host's pair

@@ -154,7 +154,7 @@ PARSING = {
     "item_pieces": ("MSNV_ITEM_PIECES", ["2000", "64", "64", "64", "18446744073709551611", "64", BIG], {"100": "100"}),
     # e ? min(2, max(0, atoi(e))) : 0
     "tot_mode_min": ("MSNV_TOT_MODE", ["0", "0", "0", "1", "0", "0", "2"], {"2": "2"}),
-    # v = e ? atoll(e) : 16384; (uint32_t)min(v > 0 ? v : 16384, 0x7fffffff) -- devpack.hip's form, the stricter of the two
+    # v = e ? atoll(e) : 16384; (uint32_t)min(v > 0 ? v : 16384, 0x7fffffff) -- devfin.hip's form, the stricter of the two
     "cov_item_intervals": ("MSNV_COV_ITEM", ["16384", "16384", "16384", "1", "16384", "16384", "2147483647"], {"64": "64"}),
     # v = e ? atoll(e) : 32767; min(32767, max(1, v))
     "cov_narrow_max": ("MSNV_COV_NARROW_MAX", ["32767", "1", "1", "1", "1", "1", "32767"], {"100": "100"}),
