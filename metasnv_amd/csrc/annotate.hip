@@ -12,14 +12,9 @@
 #include <algorithm>
 
 #include "device.h"
+#include "hiptry.h"
 
 namespace msnv {
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return fail(MSNV_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 // Amino acids by codon index a*16+b*4+c with A0 C1 G2 T3 (gene.h:3-25 re-ordered; X = stop).
 __constant__ char k_amino[65] = "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVVXYXYSSSSXCWCLFLF";

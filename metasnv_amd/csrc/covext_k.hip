@@ -28,14 +28,9 @@
 
 #include "msnv_internal.h"
 #include "device.h"
+#include "hiptry.h"
 
 namespace msnv {
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return fail(MSNV_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 constexpr int CX_NT = 256;
 constexpr int CX_PER = TILE / CX_NT;                   // consecutive positions of one thread

@@ -51,7 +51,7 @@ struct GateTile { uint32_t tile, slot_lo, slot_16, slot_w, slot_hi, vbeg, vend, 
 static_assert(sizeof(GateTile) == 64, "gate tile descriptor");
 
 // What one pass writes and a pass in flight beside it must not share.  A dataset holds two of these (DeviceCols itself and DeviceCols::alt):
-// msnv_pileup_run_many alternates overlapped passes between them.  Allocated, grown, freed and swapped as a whole (kernels.hip: passbufs_*).
+// msnv_pileup_run_many alternates overlapped passes between them.  Allocated, grown and freed as a whole (devmem.hip: passbufs_*), swapped as a whole (kernels.hip: swap_sets).
 struct PassBufs {
     uint32_t *tot = nullptr;         // [4][n_tiles*TILE]: mismatching A, C, G, T summed over samples
     uint8_t  *part = nullptr;        // coverage partial row of every work item (tile-major; u16 per position for narrow items, u32 for wide)
@@ -178,13 +178,14 @@ constexpr uint32_t CNT_WORDS = CNT_UNC + 16;
 
 struct RunCounts { uint32_t n_events, n_overflow, n_sites, err; uint64_t n_cells; };
 
+// ---- devmem.hip: the current device, the caching allocator, copies, fills and streams
 int  dev_set_device(int device);
 uint32_t dev_resident_workgroups(uint32_t per_cu);   // compute units of the current device x per_cu (256 CUs when the query fails)
 int  dev_alloc(void **p, uint64_t bytes, uint64_t *acct);
 void dev_free(void *p);
 void dev_free_batch(const std::vector<void *> &ptrs);
 int dev_memset_async(void *dst, int v, uint64_t bytes, void *stream);
-void dev_cache_trim();                               // cached free blocks back to the runtime (kernels.hip: dev_alloc)
+void dev_cache_trim();                               // cached free blocks back to the runtime (devmem.hip: dev_alloc)
 int  dev_upload(void *dst, const void *src, uint64_t bytes);
 int  dev_download(void *dst, const void *src, uint64_t bytes);
 int  dev_copy_bytes(void *dst_device, const void *src, uint64_t bytes, bool src_on_device, void *stream);      // device <- device or host, on the stream, waited for
@@ -193,7 +194,7 @@ int  dev_stream_wait(void *stream);
 int  dev_stream_create(void **stream);
 void dev_stream_destroy(void *stream);
 
-// One pass of the pipeline (pileup -> gate -> gather -> decide) on `stream`.
+// ---- kernels.hip: one pass of the pipeline (pileup -> gate -> gather -> decide) on `stream`, the coverage pass
 constexpr int COV_BINS = 16;            // histogram bins kept on the device (qaCompute -c <= 15)
 int  dev_run_coverage(DeviceCols &d, int max_cov, void *stream, msnv_run_stats *stats);
 int  dev_coverage_scanned(DeviceCols &d, void *stream, unsigned long long *scanned);      // scanned[n_cov_rows]: positions msnv_coverage_tiles scans per accumulator row
@@ -214,13 +215,18 @@ struct CovxJob {
 int  dev_run_coverage_extras(DeviceCols &d, CovxJob &job, void *stream);
 int  dev_run_pipeline(DeviceCols &d, const msnv_params &p, void *stream, msnv_run_stats *stats, RunCounts *counts);
 int  dev_run_pipeline_many(DeviceCols &d, const msnv_params &p, void *stream, int n, bool overlap, msnv_run_stats *stats, RunCounts *counts);
+// ---- devmem.hip again: everything a dataset holds on the device, and its sets of per-pass buffers
 void dev_free_all(DeviceCols &d);
-// A set of per-pass buffers (kernels.hip).  alloc: every buffer of an EMPTY set from the dataset's shape (d's counts; part_bytes, n_active_tiles,
+// A set of per-pass buffers.  alloc: every buffer of an EMPTY set from the dataset's shape (d's counts; part_bytes, n_active_tiles,
 // n_fused_tiles, allele_planes) and the capacities `caps`, the fills queued on `stream`; grow: events, overflow and sites (with unc_sites) to
 // what a failed pass asked for; free: everything, and the set's bytes leave d.device_bytes with it.
 int  passbufs_alloc(DeviceCols &d, PassBufs &b, const PassBufs &caps, void *stream);
 int  passbufs_grow(DeviceCols &d, PassBufs &b, const RunCounts &need);
 void passbufs_free(DeviceCols &d, PassBufs &b);
+// before a pass: the primary set's output columns hold half as many sites and cells again as the last pass found; before an overlapped
+// batch: the second set exists at the first's capacities (its fills queued on `stream` and waited for)
+int  ensure_out_for_next_pass(DeviceCols &d);
+int  ensure_alt(DeviceCols &d, void *stream);
 int  dev_reserve_passes(DeviceCols &d, int n);
 // one tiny launch per translation unit with kernels: its code object is loaded when the context is made, not inside the first stage that needs it
 void warm_devpack(void *stream), warm_devfin(void *stream), warm_kernels(void *stream), warm_textcall(void *stream), warm_annotate(void *stream), warm_mptext(void *stream);

@@ -1,6 +1,5 @@
 // metasnv_amd/csrc/devwork.h -- what the two device stages of a dataset share on the host side of a launch (HIP only; no kernel lives here):
 // devpack.hip, the per-read stage and the dealer, and devfin.hip, finalize's device side.
-//   HIP_TRY                       a failed runtime call ends the function with MSNV_EHIP and the call's text
 //   DpContig                      a contig as the kernels of both stages see it (DevPackTables::contigs)
 //   ld32 .. put_piece_lane        device helpers both stages' kernels inline: unaligned loads, a piece's stored bytes, its lane's share of the columns
 //   DevBuf, Timer, grid_for ...   an owned device allocation, HIP events around launches, the grid of n threads
@@ -20,14 +19,9 @@
 
 #include "device.h"
 #include "devpack.h"
+#include "hiptry.h"
 
 namespace msnv {
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return fail(MSNV_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 struct DpContig { long long len, seq_len, bed_beg, bed_end; unsigned long long pref_off; uint32_t sel, pad; };   // seq_len < 0: no FASTA record
 

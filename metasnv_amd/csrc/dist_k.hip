@@ -18,14 +18,9 @@
 #include <vector>
 
 #include "msnv_internal.h"
+#include "hiptry.h"
 
 namespace msnv {
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return fail(MSNV_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 __device__ __forceinline__ double absdiff0(const double *__restrict__ x, const double *__restrict__ y, long k) {
     const double a = x[k], b = y[k];

@@ -29,14 +29,9 @@
 #include <vector>
 
 #include "msnv_internal.h"
+#include "hiptry.h"
 
 namespace msnv {
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return fail(MSNV_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 constexpr int NP_BLOCK = 8192;                               // numpy's reduction buffer
 constexpr int NP_LEAF = 128;                                 // numpy's PW_BLOCKSIZE

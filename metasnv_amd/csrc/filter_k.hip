@@ -13,14 +13,9 @@
 
 #include "filter.h"
 #include "msnv_internal.h"
+#include "hiptry.h"
 
 namespace msnv {
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return fail(MSNV_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 __global__ __launch_bounds__(256) void msnv_filter_freq(const uint32_t *__restrict__ cov, const uint32_t *__restrict__ cnt, uint32_t n_samples,
                                                         const uint32_t *__restrict__ row_line, const uint32_t *__restrict__ line_species,

@@ -17,14 +17,9 @@
 
 #include "device.h"
 #include "msnv_internal.h"
+#include "hiptry.h"
 
 namespace msnv {
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return fail(MSNV_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 namespace {
 

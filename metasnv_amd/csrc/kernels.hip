@@ -11,25 +11,21 @@
 // Everything is integer counting: the bound is HBM bandwidth, there is no MFMA-shaped work.
 // One workgroup owns one tile of TILE reference positions and keeps that tile's bins in LDS;
 // reads are streamed from HBM with 16-byte loads per lane; only compact results are written.
+//
+// Behind the kernels, the host side of a pass: struct Pass queues one, dev_run_pipeline / dev_run_pipeline_many drive it, dev_run_coverage is
+// the coverage pass.  No longer here: the device allocator, the copy / fill / stream wrappers and the per-pass buffers (devmem.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
-#include <unordered_map>
 #include <vector>
 
 #include "device.h"
+#include "hiptry.h"
 
 namespace msnv {
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return fail(MSNV_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 constexpr int LANES_PER_READ = 8;              // 8 lanes x 16 bases = one segment piece (<= SEG_MAX bases)
 static_assert(LANES_PER_READ * 16 == SEG_MAX, "segment pieces are sized for 8 lanes of 16 bases");
@@ -2695,336 +2691,8 @@ __global__ __launch_bounds__(C_NT) void msnv_coverage_tiles(const Pair32 *iv, co
 }
 
 // ------------------------------------------------------------------------------------------ host side
-uint32_t dev_resident_workgroups(uint32_t per_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount <= 0) return 256u * per_cu;
-    return (uint32_t)prop.multiProcessorCount * per_cu;
-}
-
-int dev_set_device(int device) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(MSNV_ENODEV, "no HIP device is available (this path has no CPU fallback)");
-    if (device < 0 || device >= n) return fail(MSNV_ENODEV, "HIP device %d does not exist (%d visible)", device, n);
-    HIP_TRY(hipSetDevice(device));
-    return MSNV_OK;
-}
-
-// MSNV_GUARD_ALLOC=1 (debugging; tests/test_gpu_guard.py): every device buffer is mapped through the virtual-memory API so that it ENDS at
-// the end of its mapping, with unmapped address space reserved behind it -- a read or write past the end of a buffer is then a GPU memory
-// fault wherever the allocator would otherwise have put a neighbour (round 3: a rocprofv3 counter pass moved the neighbours and faulted).
-struct GuardedAlloc { void *va; size_t reserved, mapped; hipMemGenericAllocationHandle_t handle; };
-static std::mutex g_guard_mu;
-static std::unordered_map<void *, GuardedAlloc> g_guarded;
-
-// Device memory goes through a small caching allocator: a buffer that is given back keeps its mapping and serves the next request of about
-// its size.  hipFree of the rounds' work buffers and columns was a quarter of finalize's wall time (110 us a call on average, 0.7 ms for the
-// gigabyte-sized ones; a dataset's build makes ~270 of them), and every dataset of a process asks for the same sizes again.  Blocks are
-// keyed by device; a request takes the smallest free block of at least its size and at most 1.5 x (+ 1 MB) of it.  Free blocks are handed
-// back to the runtime when they exceed MSNV_DEV_CACHE_MB in total (default: a sixteenth of the device's memory, at most 16 GB; 0 = no cache),
-// when an allocation fails (then everything cached goes and the allocation is tried again), and by dev_cache_trim() (context destroy).
-// Stream order: a block is handed on only after hipDeviceSynchronize() in dev_free -- what hipFree does itself -- so no kernel of its
-// previous owner is still running when the next owner's first write (possibly on another stream) arrives.
-struct CacheBlock { void *p; uint64_t bytes; int device; };
-static std::mutex g_cache_mu;
-static std::vector<CacheBlock> g_cache_free;
-static std::unordered_map<void *, CacheBlock> g_cache_live;
-static uint64_t g_cache_free_bytes = 0;
-static uint64_t cache_cap_bytes(int dev) {                          // per device: the default is a share of THAT device's memory (the caller has made it current)
-    const long long env_mb = knob::dev_cache_mb();
-    if (env_mb >= 0) return (uint64_t)env_mb << 20;
-    static std::mutex mu;
-    static std::unordered_map<int, uint64_t> caps;
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = caps.find(dev);
-    if (it != caps.end()) return it->second;
-    size_t fr = 0, tot = 0;
-    const uint64_t cap = hipMemGetInfo(&fr, &tot) != hipSuccess ? (uint64_t)1 << 30 : std::min<uint64_t>((uint64_t)tot / 16, (uint64_t)16 << 30);
-    caps[dev] = cap;
-    return cap;
-}
-static uint64_t cache_round(uint64_t bytes) {
-    if (bytes <= 4096) return 4096;
-    if (bytes < (1u << 20)) { uint64_t r = 4096; while (r < bytes) r <<= 1; return r; }     // powers of two below 1 MB
-    return (bytes + (1u << 20) - 1) & ~(uint64_t)((1u << 20) - 1);                          // whole megabytes above
-}
-void dev_cache_trim() {
-    std::vector<CacheBlock> out;
-    { std::lock_guard<std::mutex> lk(g_cache_mu); out.swap(g_cache_free); g_cache_free_bytes = 0; }
-    for (const CacheBlock &b : out) (void)hipFree(b.p);
-}
-
-int dev_alloc(void **p, uint64_t bytes, uint64_t *acct) {
-    *p = nullptr;
-    if (bytes == 0) bytes = 16;
-    if (knob::guard_alloc()) {
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        hipMemAllocationProp prop = {};
-        prop.type = hipMemAllocationTypePinned; prop.location.type = hipMemLocationTypeDevice; prop.location.id = dev;
-        size_t gran = 0;
-        HIP_TRY(hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityMinimum));
-        if (gran == 0) gran = 2u << 20;
-        GuardedAlloc g{};
-        g.mapped = (size_t)((bytes + gran - 1) / gran * gran);
-        g.reserved = g.mapped + gran;                               // one granule behind the buffer stays unmapped
-        HIP_TRY(hipMemAddressReserve(&g.va, g.reserved, gran, nullptr, 0));
-        HIP_TRY(hipMemCreate(&g.handle, g.mapped, &prop, 0));
-        HIP_TRY(hipMemMap(g.va, g.mapped, 0, g.handle, 0));
-        hipMemAccessDesc ad = {};
-        ad.location = prop.location; ad.flags = hipMemAccessFlagsProtReadWrite;
-        HIP_TRY(hipMemSetAccess(g.va, g.mapped, &ad, 1));
-        const size_t used = (size_t)((bytes + 15) & ~(uint64_t)15);  // (the buffers are read with 16-byte loads: keep that alignment)
-        *p = static_cast<char *>(g.va) + (g.mapped - used);
-        if (int fill = 0; knob::guard_fill(&fill)) { HIP_TRY(hipMemset(g.va, fill, g.mapped)); HIP_TRY(hipStreamSynchronize(nullptr)); }      // (fresh mappings are not defined to be zero: 0 or 255 tells a read of unwritten memory)
-        if (knob::guard_log()) fprintf(stderr, "[guard] %p .. %p (%llu bytes; mapping %p + %zu)\n", *p, static_cast<char *>(*p) + bytes, (unsigned long long)bytes, g.va, g.mapped);
-        std::lock_guard<std::mutex> lk(g_guard_mu);
-        g_guarded[*p] = g;
-    } else {
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        if (cache_cap_bytes(dev) == 0) { HIP_TRY(hipMalloc(p, bytes)); if (acct) *acct += bytes; return MSNV_OK; }
-        const uint64_t want = cache_round(bytes);
-        {
-            std::lock_guard<std::mutex> lk(g_cache_mu);
-            size_t best = SIZE_MAX;
-            for (size_t i = 0; i < g_cache_free.size(); ++i) {
-                const CacheBlock &b = g_cache_free[i];
-                if (b.device != dev || b.bytes < want || b.bytes > want + want / 2 + (1u << 20)) continue;
-                if (best == SIZE_MAX || b.bytes < g_cache_free[best].bytes) best = i;
-            }
-            if (best != SIZE_MAX) {
-                const CacheBlock b = g_cache_free[best];
-                g_cache_free[best] = g_cache_free.back(); g_cache_free.pop_back();
-                g_cache_free_bytes -= b.bytes;
-                g_cache_live[b.p] = b;
-                *p = b.p;
-            }
-        }
-        if (!*p) {
-            hipError_t e = hipMalloc(p, want);
-            if (e != hipSuccess) { (void)hipGetLastError(); dev_cache_trim(); e = hipMalloc(p, want); }       // (the cache must never be the reason an allocation fails)
-            if (e != hipSuccess) { *p = nullptr; return fail(MSNV_EHIP, "hipMalloc of %llu bytes failed: %s", (unsigned long long)want, hipGetErrorString(e)); }
-            std::lock_guard<std::mutex> lk(g_cache_mu);
-            g_cache_live[*p] = CacheBlock{*p, want, dev};
-        }
-    }
-    if (acct) *acct += bytes;
-    return MSNV_OK;
-}
-void dev_free(void *p) {
-    if (!p) return;
-    if (knob::guard_alloc()) {
-        GuardedAlloc g{};
-        {
-            std::lock_guard<std::mutex> lk(g_guard_mu);
-            auto it = g_guarded.find(p);
-            if (it == g_guarded.end()) { (void)hipFree(p); return; }
-            g = it->second; g_guarded.erase(it);
-        }
-        (void)hipDeviceSynchronize();                               // (what hipFree does by itself)
-        // the address range stays reserved: a freed buffer's addresses are unmapped for good, so a stale pointer faults too.  (Handing the
-        // range back -- hipMemAddressFree -- and mapping the next buffer over it gave kernels wrong bytes on this runtime, with every
-        // kernel serialised and no stale pointer anywhere: profiles/r03zq notes in MEASURED.md)
-        (void)hipMemUnmap(g.va, g.mapped); (void)hipMemRelease(g.handle);
-        return;
-    }
-    CacheBlock b{nullptr, 0, 0};
-    {
-        std::lock_guard<std::mutex> lk(g_cache_mu);
-        auto it = g_cache_live.find(p);
-        if (it != g_cache_live.end()) { b = it->second; g_cache_live.erase(it); }
-    }
-    if (!b.p) { (void)hipFree(p); return; }                         // (not one of ours: allocated while the cache was off)
-    // no kernel of the old owner is running when the next owner gets the block: the BLOCK's device is the one to wait for (a dataset or a
-    // context may be destroyed while another device is current)
-    int cur = b.device;
-    (void)hipGetDevice(&cur);
-    if (cur != b.device) (void)hipSetDevice(b.device);
-    (void)hipDeviceSynchronize();
-    const uint64_t cap = cache_cap_bytes(b.device);
-    if (cur != b.device) (void)hipSetDevice(cur);
-    std::vector<CacheBlock> evict;
-    {
-        std::lock_guard<std::mutex> lk(g_cache_mu);
-        g_cache_free.push_back(b); g_cache_free_bytes += b.bytes;
-        while (g_cache_free_bytes > cap && !g_cache_free.empty()) {  // over the cap: the largest blocks go first
-            size_t big = 0;
-            for (size_t i = 1; i < g_cache_free.size(); ++i) if (g_cache_free[i].bytes > g_cache_free[big].bytes) big = i;
-            evict.push_back(g_cache_free[big]); g_cache_free_bytes -= g_cache_free[big].bytes;
-            g_cache_free[big] = g_cache_free.back(); g_cache_free.pop_back();
-        }
-    }
-    for (const CacheBlock &e : evict) (void)hipFree(e.p);
-}
-// Many buffers of ONE owner at once (the device pack's tables and work buffers at the end of finalize): one wait for the device, not one per buffer.
-void dev_free_batch(const std::vector<void *> &ptrs) {
-    if (ptrs.empty()) return;
-    if (knob::guard_alloc()) { for (void *p : ptrs) dev_free(p); return; }
-    (void)hipDeviceSynchronize();                                   // (the owner's device is current: devpack_finish / msnv_dataset_destroy set it)
-    std::vector<CacheBlock> evict; std::vector<void *> foreign;
-    {
-        std::lock_guard<std::mutex> lk(g_cache_mu);
-        for (void *p : ptrs) {
-            if (!p) continue;
-            auto it = g_cache_live.find(p);
-            if (it == g_cache_live.end()) { foreign.push_back(p); continue; }
-            g_cache_free.push_back(it->second); g_cache_free_bytes += it->second.bytes;
-            g_cache_live.erase(it);
-        }
-    }
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t cap = cache_cap_bytes(dev);
-    {
-        std::lock_guard<std::mutex> lk(g_cache_mu);
-        while (g_cache_free_bytes > cap && !g_cache_free.empty()) {
-            size_t big = 0;
-            for (size_t i = 1; i < g_cache_free.size(); ++i) if (g_cache_free[i].bytes > g_cache_free[big].bytes) big = i;
-            evict.push_back(g_cache_free[big]); g_cache_free_bytes -= g_cache_free[big].bytes;
-            g_cache_free[big] = g_cache_free.back(); g_cache_free.pop_back();
-        }
-    }
-    for (const CacheBlock &e : evict) (void)hipFree(e.p);
-    for (void *p : foreign) (void)hipFree(p);
-}
-int dev_upload(void *dst, const void *src, uint64_t bytes) {
-    if (!bytes) return MSNV_OK;
-    HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-    return MSNV_OK;
-}
-int dev_download(void *dst, const void *src, uint64_t bytes) { if (bytes) HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); return MSNV_OK; }
-int dev_copy_bytes(void *dst_device, const void *src, uint64_t bytes, bool src_on_device, void *stream) {
-    if (!bytes) return MSNV_OK;
-    HIP_TRY(hipMemcpyAsync(dst_device, src, bytes, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, (hipStream_t)stream));
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    return MSNV_OK;
-}
-// hipMemset of device memory is enqueued on the null stream and returns before it has run, and the passes run on a NON-BLOCKING stream
-// that the null stream does not order: without the wait below the first kernels of a pass can meet buffers that are not zero yet (fresh
-// hipMalloc memory happens to be zero, so nothing showed -- until a profiler's counter pass delayed the fill kernels and the first pass
-// faulted on garbage counters, and the guarded allocator's fresh mappings gave wrong counts; tests/test_gpu_guard.py)
-int dev_memset(void *dst, int v, uint64_t bytes) {
-    if (bytes) { HIP_TRY(hipMemset(dst, v, bytes)); HIP_TRY(hipStreamSynchronize(nullptr)); }
-    return MSNV_OK;
-}
-// ... or on the stream the buffer's first user runs on: ordered before it, nothing to wait for
-int dev_memset_async(void *dst, int v, uint64_t bytes, void *stream) {
-    if (bytes) HIP_TRY(hipMemsetAsync(dst, v, bytes, (hipStream_t)stream));
-    return MSNV_OK;
-}
-int dev_stream_wait(void *stream) { HIP_TRY(hipStreamSynchronize((hipStream_t)stream)); return MSNV_OK; }
-int dev_stream_create(void **stream) { hipStream_t s; HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); *stream = s; return MSNV_OK; }
-void dev_stream_destroy(void *stream) { if (stream) (void)hipStreamDestroy((hipStream_t)stream); }
-
-// (a pointer into one of the dataset's shared allocations is not freed by itself: DeviceCols::blocks)
-static bool dev_in_block(const DeviceCols &d, const void *p) {
-    for (const auto &b : d.blocks) if ((const char *)p >= (const char *)b.first && (const char *)p < (const char *)b.first + b.second) return true;
-    return false;
-}
-
-// ---- a set of per-pass buffers (device.h: PassBufs): the four functions below are the only place that knows its sizes and its members
-// A set's bytes are part of the dataset's count for as long as the set holds them: out while one of the functions remakes buffers, back in when it leaves.
-struct SetBytes { DeviceCols &d; PassBufs &b; SetBytes(DeviceCols &d_, PassBufs &b_) : d(d_), b(b_) { d.device_bytes -= b.bytes; } ~SetBytes() { d.device_bytes += b.bytes; } };
-// one buffer of `elems` elements (and `tail` bytes); a buffer that is there already goes back first, with the `old_elems` it held
-template <typename T> static int set_buf(PassBufs &b, T *&p, uint64_t old_elems, uint64_t elems, uint64_t tail = 0) {
-    if (p) { dev_free(p); p = nullptr; b.bytes -= old_elems * sizeof(T) + tail; }
-    return dev_alloc((void **)&p, elems * sizeof(T) + tail, &b.bytes);
-}
-// the output columns at exactly these capacities (0: none yet -- the first pass sizes them, ensure_out)
-static int set_out_caps(PassBufs &b, uint64_t cap_sites, uint64_t cap_cells) {
-    if (cap_sites != b.cap_out_sites) {
-        if (int rc = set_buf(b, b.site_flags, b.cap_out_sites, cap_sites, 4)) return rc;      // (+4: 32-bit atomics on the byte's aligned word)
-        if (int rc = set_buf(b, b.site_elig, b.cap_out_sites, cap_sites, 4)) return rc;
-        b.cap_out_sites = cap_sites;
-    }
-    if (cap_cells != b.cap_cells) {
-        if (int rc = set_buf(b, b.ncol, 4 * b.cap_cells, 4 * cap_cells, 16)) return rc;
-        if (int rc = set_buf(b, b.cov_col, b.cap_cells, cap_cells, 16)) return rc;
-        b.cap_cells = cap_cells;
-    }
-    return MSNV_OK;
-}
-int passbufs_alloc(DeviceCols &d, PassBufs &b, const PassBufs &caps, void *stream) {
-    SetBytes count(d, b);
-    const uint64_t npos = (uint64_t)d.n_tiles * TILE, nt1 = (uint64_t)d.n_tiles + 1, per64 = npos / 64 + 1;
-    // what starts zeroed stays zeroed between passes: the gate kernel clears the allele totals, the individual-rule bits and the dirty
-    // words it consumes, and the counter blocks alternate (the gate kernel of a pass zeroes the next one), so no pass begins with a memset
-    auto zeroed = [&](auto *&p, uint64_t elems) -> int {
-        if (int rc = set_buf(b, p, 0, elems)) return rc;
-        return dev_memset_async(p, 0, elems * sizeof(*p), stream);
-    };
-    if (int rc = zeroed(b.tot, std::max<uint64_t>(1, 4 * npos))) return rc;
-    if (int rc = set_buf(b, b.part, 0, d.part_bytes)) return rc;
-    if (int rc = set_buf(b, b.spill, 0, std::max<uint64_t>(1, d.n_pairs) * TILE)) return rc;
-    if (d.allele_planes) if (int rc = zeroed(b.aspill, (uint64_t)d.n_pairs * 4 * TILE)) return rc;      // (rows of merged pairs are never written and never read)
-    b.cap_events = caps.cap_events; b.cap_overflow = caps.cap_overflow; b.cap_sites = caps.cap_sites;
-    if (int rc = set_buf(b, b.events, 0, b.cap_events)) return rc;
-    if (int rc = set_buf(b, b.overflow, 0, b.cap_overflow)) return rc;
-    if (int rc = set_buf(b, b.sites, 0, b.cap_sites)) return rc;
-    if (int rc = set_buf(b, b.unc_sites, 0, b.cap_sites)) return rc;      // the list of sites msnv_decide_sites looks at is sized like the sites
-    if (int rc = set_buf(b, b.site_row, 0, per64)) return rc;             // per 64 positions (CellMap::block_row)
-    if (int rc = zeroed(b.tile_dirty, (uint64_t)d.n_work + 1)) return rc;      // one word per work item (by slot)
-    if (int rc = zeroed(b.counters, 2 * CNT_WORDS)) return rc;
-    b.cnt_parity = 0;
-    if (int rc = zeroed(b.ind4, npos / 8 + npos / 32 + 2)) return rc;
-    b.unc_bits = b.ind4 + npos / 8 + 1;
-    if (int rc = set_buf(b, b.site_bits, 0, per64)) return rc;
-    if (int rc = set_buf(b, b.site_rank, 0, per64)) return rc;
-    if (int rc = zeroed(b.tile_site_base, nt1)) return rc;
-    if (int rc = zeroed(b.tile_site_cnt, nt1)) return rc;
-    if (int rc = zeroed(b.tile_cell_base, nt1)) return rc;
-    // whole-tile work items write their candidate records per active tile (+ one index per whole-tile item behind the lists: the tiles
-    // whose candidates do not fit a list -- stage_ovf_list)
-    if (d.n_fused_tiles) {
-        if (int rc = dev_alloc((void **)&b.tile_stage, (uint64_t)d.n_active_tiles * sizeof(TileStage) + (uint64_t)d.n_fused_tiles * sizeof(uint32_t), &b.bytes)) return rc;
-        if (int rc = dev_memset_async(b.tile_stage, 0, (uint64_t)d.n_active_tiles * sizeof(TileStage), stream)) return rc;
-    }
-    return set_out_caps(b, caps.cap_out_sites, caps.cap_cells);
-}
-int passbufs_grow(DeviceCols &d, PassBufs &b, const RunCounts &need) {
-    SetBytes count(d, b);
-    auto grown = [](uint32_t cap, uint32_t n) { return n <= cap ? cap : (uint32_t)std::min<uint64_t>(0x7fffffffull, (uint64_t)n + n / 4 + 1024); };
-    const uint32_t ev = grown(b.cap_events, need.n_events), ov = grown(b.cap_overflow, need.n_overflow), si = grown(b.cap_sites, need.n_sites);
-    if (ev != b.cap_events) { if (int rc = set_buf(b, b.events, b.cap_events, ev)) return rc; b.cap_events = ev; }
-    if (ov != b.cap_overflow) { if (int rc = set_buf(b, b.overflow, b.cap_overflow, ov)) return rc; b.cap_overflow = ov; }
-    if (si != b.cap_sites) {
-        if (int rc = set_buf(b, b.sites, b.cap_sites, si)) return rc;
-        if (int rc = set_buf(b, b.unc_sites, b.cap_sites, si)) return rc;
-        b.cap_sites = si;
-    }
-    return MSNV_OK;
-}
-void passbufs_free(DeviceCols &d, PassBufs &b) {
-    SetBytes count(d, b);
-    void *ptrs[] = {b.tot, b.part, b.spill, b.aspill, b.events, b.overflow, b.counters, b.ind4, b.tile_dirty, b.unc_sites, b.site_row, b.site_bits, b.site_rank, b.sites,
-                    b.tile_site_base, b.tile_site_cnt, b.tile_cell_base, b.ncol, b.cov_col, b.site_flags, b.site_elig, b.tile_stage};      // (unc_bits: inside ind4)
-    for (void *p : ptrs) if (p && !dev_in_block(d, p)) dev_free(p);
-    b = PassBufs{};
-}
-
-void dev_free_all(DeviceCols &d) {
-    passbufs_free(d, d); passbufs_free(d, d.alt);
-    void *ptrs[] = {d.hdr, d.hdr8, d.hdr4, d.hdr8m, d.merged_groups, d.tile_pair_merged, d.blk, d.seq, d.qual, d.s_read_base, d.s_seq_base, d.ref4, d.ref_lc, d.pairs,
-                    d.tile_pair_start, d.work, d.chunks, d.tile_vbeg, d.tile_vend, d.tile_slot_start, d.tile_slot_u16, d.tile_slot_wide, d.slot_off, d.gate_tiles, d.tile_nslots,
-                    d.cov_iv, d.s_cov_base, d.cov_pairs, d.cov_work, d.tile_len, d.tile_contig_dev, d.cov_acc, d.tile_stage_idx, d.gate_tiles_dense, d.gate_tiles_staged, d.gather_tiles, d.active_tiles};
-    for (void *p : ptrs) if (p && !dev_in_block(d, p)) dev_free(p);
-    void *aptrs[] = {d.ann.seg_beg, d.ann.seg_end, d.ann.seg_gene, d.ann.genes, d.ann.contigs, d.ann.codons, d.ann.out, d.ann.err};
-    for (void *p : aptrs) dev_free(p);
-    for (void *e : d.timing_events) if (e) (void)hipEventDestroy((hipEvent_t)e);
-    for (void *e : d.event_pool) (void)hipEventDestroy((hipEvent_t)e);
-    if (d.pinned_cnt) (void)hipHostFree(d.pinned_cnt);
-    for (const auto &b : d.blocks) dev_free(b.first);
-    if (d.stream2) (void)hipStreamDestroy((hipStream_t)d.stream2);
-    d = DeviceCols{};
-}
-
-// the output columns of a set hold at least n_sites / n_cells (with a quarter to spare when they have to grow)
-static int ensure_out(DeviceCols &d, PassBufs &b, uint64_t n_sites, uint64_t n_cells) {
-    SetBytes count(d, b);
-    return set_out_caps(b, n_sites > b.cap_out_sites ? std::max<uint64_t>(n_sites + n_sites / 4, 1024) : b.cap_out_sites,
-                        n_cells > b.cap_cells ? (std::max<uint64_t>(n_cells + n_cells / 4, 1u << 16) + 7) & ~7ull : b.cap_cells);      // (a multiple of 8: every column starts on 16 bytes)
-}
+// What is NOT here: the allocator, the copy / fill / stream wrappers and the per-pass buffers' plumbing (passbufs_*, ensure_out_for_next_pass,
+// ensure_alt, dev_free_all) launch no kernel and live in devmem.hip.  Below: one pass (struct Pass), its two drivers, the coverage pass.
 
 // (the list lives behind the record lists, in the same allocation: the two sets of intermediates swap it with them)
 static inline uint32_t *stage_ovf_list(const DeviceCols &d) { return d.tile_stage ? reinterpret_cast<uint32_t *>(d.tile_stage + d.n_active_tiles) : nullptr; }
@@ -3037,24 +2705,53 @@ static void launch_gate_sites(bool multi, bool wide_tot, bool planes, dim3 grid,
     hipLaunchKernelGGL(k, grid, dim3(GATE_NT), 0, st, g);
 }
 
-// Enqueues one pass (kernels + readback of the pass' counter block into host_cnt[CNT_WORDS]) without waiting for it.
-// ev_begin / ev_pile0 / ev_pile1 are recorded before the pass, before and after the pileup kernel(s); ev3 / ev4 (optional)
-// split the tail.  Buffers must have been sized by ensure_out before.
-static int enqueue_pass(DeviceCols &d, const msnv_params &p, hipStream_t st, hipEvent_t ev_begin, hipEvent_t ev_pile0, hipEvent_t ev_pile1,
-                        hipEvent_t ev3, hipEvent_t ev4, uint32_t *host_cnt, hipEvent_t wait_before_pileup = nullptr) {
-    const uint64_t npos = (uint64_t)d.n_tiles * TILE;
-    if (p.min_baseq != d.qlow_cutoff) return fail(MSNV_EINVAL, "the dataset's quality column was packed for -Q %d, the pass asks for -Q %d", d.qlow_cutoff, p.min_baseq);
-    if (ev_begin) HIP_TRY(hipEventRecord(ev_begin, st));
+// Events a pass records when they are given: before the pass, before and after the pileup kernel(s), behind the gate and behind the tail
+// (the last two split the tail for MSNV_PHASE_TIMES).  `after`: waited for before the pileup -- the previous pass' pileup kernel (other stream).
+struct PassEvents { hipEvent_t begin = nullptr, pile0 = nullptr, pile1 = nullptr, gate_done = nullptr, tail_done = nullptr, after = nullptr; };
+
+// One pass over a dataset on one stream: enqueue() queues the kernels and the readback of the pass' counter block into host_cnt[CNT_WORDS]
+// without waiting for them.  The output columns must have been sized before (ensure_out_for_next_pass).
+struct Pass {
+    DeviceCols &d; const msnv_params &p; const hipStream_t st;
+    const uint64_t npos;
     // nothing to clear: d.tot and the individual-rule bits are zero after finalize and msnv_gate_sites zeroes what a pass has
     // written; the counters live in two blocks that consecutive passes alternate between (the gate kernel zeroes the other one)
-    uint32_t *const counters = d.counters + d.cnt_parity * CNT_WORDS, *const counters_next = d.counters + (d.cnt_parity ^ 1u) * CNT_WORDS;
-    d.cnt_parity ^= 1u;
-    if (wait_before_pileup) HIP_TRY(hipStreamWaitEvent(st, wait_before_pileup, 0));   // the previous pass' pileup kernel (other stream)
+    uint32_t *const counters, *const counters_next;
     // whole-tile work items apply the gates themselves (fused_tile_gate) unless a pass found a tile with too many candidates (check_counts);
     // with a calling threshold below 1 every covered position is a candidate and the unfused path is the one that is defined for it
-    const uint32_t use_stage = (d.n_fused_tiles && !d.fuse_disabled && p.calling_threshold >= 1) ? 1u : 0u;
-    HIP_TRY(hipEventRecord(ev_pile0, st));
-    if (d.n_work) {
+    const uint32_t use_stage;
+    const uint32_t cap_out;
+    const bool need_decide;                                         // some sample's reads sit in several pairs of a tile: sites whose call depends
+                                                                    // on its summed counts are decided behind the scatter (msnv_decide_sites);
+                                                                    // merged groups alone are handled inside the merged gather
+    const CellMap cells;
+
+    Pass(DeviceCols &d_, const msnv_params &p_, hipStream_t st_)
+        : d(d_), p(p_), st(st_), npos((uint64_t)d_.n_tiles * TILE),
+          counters(d_.counters + d_.cnt_parity * CNT_WORDS), counters_next(d_.counters + (d_.cnt_parity ^ 1u) * CNT_WORDS),
+          use_stage((d_.n_fused_tiles && !d_.fuse_disabled && p_.calling_threshold >= 1) ? 1u : 0u),
+          cap_out((uint32_t)std::min<uint64_t>(d_.cap_out_sites, 0xffffffffull)), need_decide(d_.any_split),
+          cells{d_.tile_site_base, d_.tile_cell_base, d_.tile_nslots, d_.cap_cells, d_.site_row} {}
+
+    int mark(hipEvent_t e) { if (e) HIP_TRY(hipEventRecord(e, st)); return MSNV_OK; }
+
+    int enqueue(const PassEvents &ev, uint32_t *host_cnt) {
+        if (p.min_baseq != d.qlow_cutoff) return fail(MSNV_EINVAL, "the dataset's quality column was packed for -Q %d, the pass asks for -Q %d", d.qlow_cutoff, p.min_baseq);
+        if (int rc = mark(ev.begin)) return rc;
+        d.cnt_parity ^= 1u;                                         // (the next pass takes the other counter block)
+        if (ev.after) HIP_TRY(hipStreamWaitEvent(st, ev.after, 0));
+        if (int rc = mark(ev.pile0)) return rc;
+        if (int rc = pileup()) return rc;
+        if (int rc = mark(ev.pile1)) return rc;
+        if (int rc = gate()) return rc;
+        if (int rc = mark(ev.gate_done)) return rc;
+        if (int rc = tail()) return rc;                             // the tail runs on device-side counts: no host round trip inside a pass
+        if (int rc = mark(ev.tail_done)) return rc;
+        if (int rc = decide()) return rc;
+        return read_back(host_cnt);
+    }
+
+    PileupArgs pileup_args() const {
         PileupArgs a;
         a.hdr = d.hdr; a.hdr8 = d.hdr8; a.hdr4 = d.hdr4; a.blk = d.blk; a.seq = d.seq; a.qual = d.qual;
         a.s_read_base = d.s_read_base; a.s_seq_base = d.s_seq_base;
@@ -3064,9 +2761,14 @@ static int enqueue_pass(DeviceCols &d, const msnv_params &p, hipStream_t st, hip
         a.ind4 = d.ind4; a.unc_bits = d.unc_bits; a.slot_dirty = d.tile_dirty; a.min_snvs = (uint32_t)std::max(0, p.calling_threshold);
         a.n_fused_lo = d.n_work_narrow + d.n_work_merged - (use_stage ? d.n_work_fused : 0u); a.min_cov = p.min_coverage; a.min_frac = p.min_fraction; a.ref_lc = d.ref_lc; a.tile_vbeg = d.tile_vbeg; a.tile_vend = d.tile_vend;
         a.tile_stage = d.tile_stage; a.tile_stage_idx = d.tile_stage_idx; a.stage_ovf = stage_ovf_list(d);
-        const uint32_t n_narrow = d.n_work_narrow, n_merged = d.n_work_merged;
+        a.hdr8m = d.hdr8m; a.n_narrow = d.n_work_narrow;
+        return a;
+    }
+    int pileup() {
+        if (!d.n_work) return MSNV_OK;
+        const PileupArgs a = pileup_args();
         // narrow work items (byte bins), merged groups of shallow pairs and wide items (16-bit bins) touch disjoint (tile, sample) pairs
-        a.hdr8m = d.hdr8m; a.n_narrow = n_narrow;
+        const uint32_t n_narrow = d.n_work_narrow, n_merged = d.n_work_merged;
         if (n_narrow && d.dense) hipLaunchKernelGGL(msnv_pileup_tiles_dense, dim3(n_narrow), dim3(N_NT), 0, st, a);      // (the dense layout never merges)
         else {
             // (whole-tile items of a sparse cohort are the last items of the work list: a launch of their own since round 6, msnv_pileup_tiles_lean)
@@ -3082,13 +2784,11 @@ static int enqueue_pass(DeviceCols &d, const msnv_params &p, hipStream_t st, hip
             hipLaunchKernelGGL(msnv_pileup_tiles_wide, dim3(d.n_work - n_narrow - n_merged), dim3(W_NT), 0, st, b);
         }
         HIP_TRY(hipGetLastError());
+        return MSNV_OK;
     }
-    HIP_TRY(hipEventRecord(ev_pile1, st));
-    const uint32_t cap_out = (uint32_t)std::min<uint64_t>(d.cap_out_sites, 0xffffffffull);
-    const bool need_decide = d.any_split;                           // some sample's reads sit in several pairs of a tile: sites whose call depends
-                                                                    // on its summed counts are decided behind the scatter (msnv_decide_sites);
-                                                                    // merged groups alone are handled inside the merged gather
-    if (d.n_active_tiles) {
+
+    // as the first gate launch takes them: the `n_dense` tiles without a record list, one per workgroup, zeroing the next pass' counters
+    GateArgs gate_args(uint32_t n_dense) const {
         GateArgs g;
         g.tot = d.tot; g.part = d.part; g.slot_off = d.slot_off; g.tile_slot_start = d.tile_slot_start; g.tile_slot_u16 = d.tile_slot_u16; g.tile_slot_wide = d.tile_slot_wide;
         g.npos = npos; g.tile_vbeg = d.tile_vbeg; g.tile_vend = d.tile_vend; g.min_cov = p.min_coverage; g.min_snvs = p.calling_threshold; g.min_frac = p.min_fraction;
@@ -3096,21 +2796,24 @@ static int enqueue_pass(DeviceCols &d, const msnv_params &p, hipStream_t st, hip
         g.site_bits = d.site_bits; g.site_rank = d.site_rank; g.sites = d.sites; g.cap_sites = d.cap_sites; g.counters = counters; g.counters_next = counters_next;
         g.tile_site_base = d.tile_site_base; g.tile_site_cnt = d.tile_site_cnt; g.active_tiles = d.active_tiles;
         g.ncol = d.ncol; g.cov_col = d.cov_col; g.site_flags = d.site_flags; g.cap_out = cap_out;
-        g.gate_tiles = d.gate_tiles; g.tile_dirty = d.tile_dirty; g.unc_sites = d.unc_sites;
+        g.gate_tiles = use_stage ? d.gate_tiles_dense : d.gate_tiles; g.tile_dirty = d.tile_dirty; g.unc_sites = d.unc_sites;
         g.use_dirty = d.use_dirty ? 1u : 0u; g.block_row = d.site_row; g.site_elig = d.site_elig; g.any_split = d.any_split ? 1u : 0u;
         g.tile_nslots = d.tile_nslots; g.tile_cell_base = d.tile_cell_base; g.cap_cells = d.cap_cells;
-        // several tiles per workgroup once the tiles outnumber what the device holds at a time several times over (one reservation of
-        // site slots per workgroup: msnv_gate_sites); MSNV_GATE_TILES overrides (tests run every size)
-        g.tile_stage = d.tile_stage; g.tiles_per_wg = 1u;
-        // whole-tile work items left record lists: their tiles go through msnv_gate_staged, the others through msnv_gate_sites
-        const uint32_t n_staged = use_stage ? d.n_fused_tiles : 0u, n_dense = d.n_active_tiles - n_staged;
-        if (use_stage) g.gate_tiles = d.gate_tiles_dense;
+        g.tile_stage = d.tile_stage; g.tiles_per_wg = 1u; g.aspill = d.aspill;
         g.n_active = n_dense;
         g.zero_next = 1u; g.tile_list = nullptr; g.solo_cells = 0u;
+        return g;
+    }
+    int gate() {
+        if (!d.n_active_tiles) { HIP_TRY(hipMemsetAsync(counters_next, 0, CNT_WORDS * sizeof(uint32_t), st)); return MSNV_OK; }   // nobody else would
+        // whole-tile work items left record lists: their tiles go through msnv_gate_staged, the others through msnv_gate_sites
+        const uint32_t n_staged = use_stage ? d.n_fused_tiles : 0u, n_dense = d.n_active_tiles - n_staged;
+        GateArgs g = gate_args(n_dense);
         if (n_dense) {
+            // several tiles per workgroup once the tiles outnumber what the device holds at a time several times over (one reservation of
+            // site slots per workgroup: msnv_gate_sites); MSNV_GATE_TILES overrides (tests run every size)
             g.tiles_per_wg = knob::gate_tiles(n_dense >= 32768u ? 8u : n_dense >= 8192u ? 4u : 1u, (int)GATE_MAX_TILES);
             const dim3 grid((n_dense + g.tiles_per_wg - 1) / g.tiles_per_wg);
-            g.aspill = d.aspill;
             launch_gate_sites(g.tiles_per_wg != 1u, d.wide_tot, d.allele_planes, grid, st, g);
             g.zero_next = 0u;
         }
@@ -3119,24 +2822,23 @@ static int enqueue_pass(DeviceCols &d, const msnv_params &p, hipStream_t st, hip
             // the tiles whose candidates did not fit their record list (counted and listed on the device: fused_tile_gate) through the ordinary
             // gate; the workgroups stride over the list -- as many as the previous pass would have kept busy, a handful when it listed none
             g.gate_tiles = d.gate_tiles; g.tile_list = stage_ovf_list(d); g.n_active = n_staged; g.solo_cells = 1u;
-            g.tiles_per_wg = 1u; g.zero_next = 0u; g.aspill = d.aspill;
+            g.tiles_per_wg = 1u; g.zero_next = 0u;
             const dim3 grid(std::min<uint32_t>(n_staged, std::max<uint32_t>(64u, std::min<uint32_t>(4096u, d.last_ovf_tiles))));
             launch_gate_sites(true, d.wide_tot, d.allele_planes, grid, st, g);
         }
         HIP_TRY(hipGetLastError());
-    } else HIP_TRY(hipMemsetAsync(counters_next, 0, CNT_WORDS * sizeof(uint32_t), st));   // nobody else would
-    if (ev3) HIP_TRY(hipEventRecord(ev3, st));
-    // the tail runs on device-side counts: no host round trip inside a pass
-    if (d.n_active_tiles) {
+        return MSNV_OK;
+    }
+
+    TailArgs tail_args() const {
         TailArgs ta;
         ta.sites = d.sites; ta.tile_site_base = d.tile_site_base; ta.tile_site_cnt = d.tile_site_cnt; ta.tile_pair_start = d.tile_pair_start;
         ta.pairs = d.pairs; ta.spill = d.spill; ta.ncol = d.ncol; ta.cov_col = d.cov_col; ta.cap_out = cap_out; ta.active_tiles = d.gather_tiles;
-        ta.cells = CellMap{d.tile_site_base, d.tile_cell_base, d.tile_nslots, d.cap_cells, d.site_row};
+        ta.cells = cells;
         ta.gather_split = d.gather_split;
         ta.has_wide = d.n_work > d.n_work_narrow + d.n_work_merged ? 1u : 0u;
         ta.aspill = d.allele_planes ? d.aspill : nullptr;
-        const uint32_t tail_skip = knob::tail_skip();
-        ta.debug_skip = tail_skip;
+        ta.debug_skip = knob::tail_skip();
         ta.n_gather_blocks = d.n_gather_tiles * d.gather_split;
         ta.tile_pair_merged = d.tile_pair_merged; ta.merged_groups = d.merged_groups; ta.chunks = d.chunks; ta.hdr8m = d.hdr8m;
         ta.seq = d.seq; ta.qual = d.qual; ta.ref4 = d.ref4; ta.n_merged_run = d.n_merged_groups - (use_stage ? d.n_groups_solo : 0u);
@@ -3144,25 +2846,35 @@ static int enqueue_pass(DeviceCols &d, const msnv_params &p, hipStream_t st, hip
         ta.site_flags = d.site_flags; ta.site_elig = d.site_elig; ta.ind_in_gather = d.any_split ? 0u : 1u; ta.min_snvs = (uint32_t)std::max(1, p.calling_threshold);
         ta.events = d.events; ta.overflow = d.overflow; ta.counters = counters; ta.cap_list = d.cap_events / EV_LISTS; ta.cap_overflow = d.cap_overflow;
         ta.site_bits = d.site_bits; ta.site_rank = d.site_rank;
-        const uint32_t scatter_blocks = knob::scatter_blocks(SCATTER_BLOCKS_PER_LIST);
-        ta.scatter_blocks = scatter_blocks;
+        ta.scatter_blocks = knob::scatter_blocks(SCATTER_BLOCKS_PER_LIST);
+        return ta;
+    }
+    int tail() {
+        if (!d.n_active_tiles) return MSNV_OK;
+        const TailArgs ta = tail_args();
         const dim3 grid(ta.n_gather_blocks + ta.n_merged_blocks + ta.scatter_blocks * EV_LISTS + 1u);      // + 1: the event total
         if (ta.n_merged_blocks) hipLaunchKernelGGL(msnv_gather_scatter<true>, grid, dim3(256), 0, st, ta);
         else hipLaunchKernelGGL(msnv_gather_scatter<false>, grid, dim3(256), 0, st, ta);
         HIP_TRY(hipGetLastError());
+        return MSNV_OK;
     }
-    if (ev4) HIP_TRY(hipEventRecord(ev4, st));
-    if (need_decide && d.n_active_tiles) {
+
+    int decide() {
+        if (!need_decide || !d.n_active_tiles) return MSNV_OK;
         // (one wavefront per listed site, grid-stride: a launch that fills the chip -- with 256 workgroups half a million listed sites
         // of a deep, uneven cohort took 1.6 ms)
         static const uint32_t decide_grid = dev_resident_workgroups(8);          // (queried once: the device properties call is slow)
         hipLaunchKernelGGL(msnv_decide_sites, dim3(decide_grid), dim3(256), 0, st, d.sites, d.unc_sites, counters, d.cap_sites, cap_out, d.ref4, d.ref_lc,
-                           d.ncol, CellMap{d.tile_site_base, d.tile_cell_base, d.tile_nslots, d.cap_cells, d.site_row}, p.calling_threshold, p.min_fraction, d.site_flags);
+                           d.ncol, cells, p.calling_threshold, p.min_fraction, d.site_flags);
         HIP_TRY(hipGetLastError());
+        return MSNV_OK;
     }
-    HIP_TRY(hipMemcpyAsync(host_cnt, counters, CNT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    return MSNV_OK;
-}
+
+    int read_back(uint32_t *host_cnt) {
+        HIP_TRY(hipMemcpyAsync(host_cnt, counters, CNT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        return MSNV_OK;
+    }
+};
 
 static int check_counts(DeviceCols &d, const uint32_t *cnt, RunCounts *counts) {
     RunCounts c{cnt[0], cnt[1], cnt[2], cnt[3], (uint64_t)cnt[CNT_CELLS] | (uint64_t)cnt[CNT_CELLS + 1] << 32};
@@ -3176,19 +2888,35 @@ static int check_counts(DeviceCols &d, const uint32_t *cnt, RunCounts *counts) {
     return MSNV_OK;
 }
 
-int dev_run_pipeline(DeviceCols &d, const msnv_params &p, void *stream_, msnv_run_stats *stats, RunCounts *counts) {
-    hipStream_t st = (hipStream_t)stream_;
-    hipEvent_t ev[6];                                      // created once per dataset: event create / destroy costs host time in every pass
-    for (int i = 0; i < 6; ++i) {
+// what a pass' counter block says about it
+static void fill_stats(msnv_run_stats &s, const uint32_t *cnt, const DeviceCols &d) {
+    s.n_sites = cnt[2]; s.n_events = cnt[0]; s.n_overflow = cnt[1];
+    s.n_called_pop = cnt[4] + cnt[CNT_TALLY]; s.n_called_indiv = cnt[5] + cnt[CNT_TALLY + 1];    // msnv_decide_sites' lines + the gate kernel's (and the merged gather's)
+    s.algorithmic_bytes = d.algorithmic_bytes;
+}
+
+// the first n of the dataset's timing events, created once per dataset: event create / destroy costs host time in every pass
+static int timing_events(DeviceCols &d, hipEvent_t *ev, int n) {
+    for (int i = 0; i < n; ++i) {
         if (!d.timing_events[i]) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); d.timing_events[i] = e; }
         ev[i] = (hipEvent_t)d.timing_events[i];
     }
+    return MSNV_OK;
+}
+
+int dev_run_pipeline(DeviceCols &d, const msnv_params &p, void *stream_, msnv_run_stats *stats, RunCounts *counts) {
+    hipStream_t st = (hipStream_t)stream_;
+    hipEvent_t ev[6];
+    if (int rc = timing_events(d, ev, 6)) return rc;
     // every event record costs ~6 us of stream time (the next kernel waits for the marker): the per-phase split of
     // the tail is only recorded on request (MSNV_PHASE_TIMES=1, profiles/phase_times.py)
     const bool phase_times = knob::phase_times();
-    if (int rc = ensure_out(d, d, std::max<uint64_t>(d.last_sites + d.last_sites / 2, 4096), std::max<uint64_t>(d.last_cells + d.last_cells / 2, 1u << 18))) return rc;
+    if (int rc = ensure_out_for_next_pass(d)) return rc;
     uint32_t cnt[CNT_WORDS] = {0};
-    if (int rc = enqueue_pass(d, p, st, ev[0], ev[1], ev[2], phase_times ? ev[3] : nullptr, phase_times ? ev[4] : nullptr, cnt)) return rc;
+    PassEvents pe;
+    pe.begin = ev[0]; pe.pile0 = ev[1]; pe.pile1 = ev[2];
+    if (phase_times) { pe.gate_done = ev[3]; pe.tail_done = ev[4]; }
+    if (int rc = Pass(d, p, st).enqueue(pe, cnt)) return rc;
     HIP_TRY(hipEventRecord(ev[5], st));
     HIP_TRY(hipStreamSynchronize(st));
     if (int rc = check_counts(d, cnt, counts)) return rc;
@@ -3201,34 +2929,14 @@ int dev_run_pipeline(DeviceCols &d, const msnv_params &p, void *stream_, msnv_ru
             HIP_TRY(hipEventElapsedTime(&ms, ev[3], ev[4])); stats->ms_gather = ms;
             HIP_TRY(hipEventElapsedTime(&ms, ev[4], ev[5])); stats->ms_decide = ms;
         }
-        stats->n_sites = cnt[2]; stats->n_events = cnt[0]; stats->n_overflow = cnt[1];
-        stats->n_called_pop = cnt[4] + cnt[CNT_TALLY]; stats->n_called_indiv = cnt[5] + cnt[CNT_TALLY + 1];    // msnv_decide_sites' lines + the gate kernel's (and the merged gather's)
-        stats->algorithmic_bytes = d.algorithmic_bytes;
+        fill_stats(*stats, cnt, d);
     }
     return MSNV_OK;
 }
 
-// Second set of per-pass buffers, sized like the first (re-made when the first set was grown).  Its fills are queued on `stream` and waited
-// for: the passes run on two streams that nothing else orders behind them.
-static int ensure_alt(DeviceCols &d, void *stream) {
-    PassBufs &a = d.alt;
-    if (a.tot && a.cap_events == d.cap_events && a.cap_overflow == d.cap_overflow && a.cap_sites == d.cap_sites && a.cap_out_sites == d.cap_out_sites && a.cap_cells == d.cap_cells) return MSNV_OK;
-    passbufs_free(d, a);
-    if (int rc = passbufs_alloc(d, a, d, stream)) return rc;
-    return dev_stream_wait(stream);
-}
 // (both sets hold aspill under allele_planes and tile_stage under n_fused_tiles: a null swaps with a null)
 static void swap_sets(DeviceCols &d) { std::swap(static_cast<PassBufs &>(d), d.alt); }
 
-// n passes, ONE host synchronisation at the end; with `overlap` they are in flight on two streams (a queue of shards / repeated passes keeps the
-// GPU busy: the host round trip of the single-pass form costs ~40 us of idle GPU per pass).  Consecutive passes use
-// alternating sets of intermediates and alternating streams; the pileup kernels are serialised among themselves by an
-// event (they saturate the chip), so what overlaps is the latency-bound tail of pass i (gate, gather, scatter, decide,
-// ~0.12 ms at a fraction of the chip) with the memsets and the pileup kernel of pass i+1.  Measured (one box, 30 passes):
-// step time 0.810 -> 0.770 ms (+5 % bases/s), while the pileup kernel itself reads 0.673 -> 0.736 ms because it shares
-// the chip with the tail kernels -- which is why bench.py measures the roofline on the non-overlapped form.  stats[i]: pileup-kernel time
-// of pass i from its own event pair (recorded after the cross-stream wait); ms_total = batch time / n.  On return the
-// primary set holds the last pass.
 // events and the pinned counter blocks of a batch of n passes are pooled in the dataset: creating ~4n events and a pinned buffer per call
 // costs about a millisecond of host time before the first pass is even enqueued (msnv_pileup_reserve does it ahead of a timed batch)
 int dev_reserve_passes(DeviceCols &d, int n) {
@@ -3242,10 +2950,19 @@ int dev_reserve_passes(DeviceCols &d, int n) {
     return MSNV_OK;
 }
 
+// n passes, ONE host synchronisation at the end; with `overlap` they are in flight on two streams (a queue of shards / repeated passes keeps the
+// GPU busy: the host round trip of the single-pass form costs ~40 us of idle GPU per pass).  Consecutive passes use
+// alternating sets of intermediates and alternating streams; the pileup kernels are serialised among themselves by an
+// event (they saturate the chip), so what overlaps is the latency-bound tail of pass i (gate, gather, scatter, decide,
+// ~0.12 ms at a fraction of the chip) with the memsets and the pileup kernel of pass i+1.  Measured (one box, 30 passes):
+// step time 0.810 -> 0.770 ms (+5 % bases/s), while the pileup kernel itself reads 0.673 -> 0.736 ms because it shares
+// the chip with the tail kernels -- which is why bench.py measures the roofline on the non-overlapped form.  stats[i]: pileup-kernel time
+// of pass i from its own event pair (recorded after the cross-stream wait); ms_total = batch time / n.  On return the
+// primary set holds the last pass.
 int dev_run_pipeline_many(DeviceCols &d, const msnv_params &p, void *stream_, int n, bool overlap, msnv_run_stats *stats, RunCounts *counts) {
     if (n <= 0) return MSNV_OK;
     hipStream_t s0 = (hipStream_t)stream_, s1 = s0;
-    if (int rc = ensure_out(d, d, std::max<uint64_t>(d.last_sites + d.last_sites / 2, 4096), std::max<uint64_t>(d.last_cells + d.last_cells / 2, 1u << 18))) return rc;
+    if (int rc = ensure_out_for_next_pass(d)) return rc;
     if (overlap && n > 1) {
         if (!d.stream2) { hipStream_t s; HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); d.stream2 = s; }
         s1 = (hipStream_t)d.stream2;
@@ -3254,52 +2971,48 @@ int dev_run_pipeline_many(DeviceCols &d, const msnv_params &p, void *stream_, in
     const bool two = s1 != s0;
     if (int rc = dev_reserve_passes(d, n)) return rc;
     hipEvent_t *ev = reinterpret_cast<hipEvent_t *>(d.event_pool.data());
-    auto cleanup = [] {};
     uint32_t *cnt = d.pinned_cnt;
     int rc = MSNV_OK;
-    hipError_t he = hipSuccess;
+    auto hip = [&rc](hipError_t e) { if (!rc && e != hipSuccess) rc = fail(MSNV_EHIP, "batched passes: %s", hipGetErrorString(e)); };      // (the first error is the one reported)
     bool swapped = false;                                     // true while d's primary fields hold the second set
-    for (int i = 0; i < n && !rc && he == hipSuccess; ++i) {
-        hipStream_t st = (i & 1) ? s1 : s0;
+    for (int i = 0; i < n && !rc; ++i) {
         if (two && (i & 1) != (swapped ? 1 : 0)) { swap_sets(d); swapped = !swapped; }
         // the pileup kernel of pass i starts after the one of pass i-1 (other stream) has finished; its memsets do not wait
         // (only the first pass records a begin event: every event record costs stream time)
-        rc = enqueue_pass(d, p, st, i == 0 ? ev[0] : nullptr, ev[4 * i + 1], ev[4 * i + 2], nullptr, nullptr, cnt + (size_t)CNT_WORDS * i, (two && i > 0) ? ev[4 * (i - 1) + 2] : nullptr);
+        PassEvents pe;
+        pe.begin = i == 0 ? ev[0] : nullptr; pe.pile0 = ev[4 * i + 1]; pe.pile1 = ev[4 * i + 2]; pe.after = (two && i > 0) ? ev[4 * (i - 1) + 2] : nullptr;
+        rc = Pass(d, p, (i & 1) ? s1 : s0).enqueue(pe, cnt + (size_t)CNT_WORDS * i);
     }
-    if (!rc && he == hipSuccess) he = hipEventRecord(ev[4 * n], s0);
-    if (!rc && he == hipSuccess) he = hipEventRecord(ev[4 * n + 1], s1);
-    if (he == hipSuccess) he = hipStreamSynchronize(s0);
-    if (he == hipSuccess && two) he = hipStreamSynchronize(s1);
+    if (!rc) hip(hipEventRecord(ev[4 * n], s0));
+    if (!rc) hip(hipEventRecord(ev[4 * n + 1], s1));
+    hip(hipStreamSynchronize(s0));                            // (also when an enqueue failed: nothing of the batch is in flight on return)
+    if (two) hip(hipStreamSynchronize(s1));
     // leave the set of the LAST pass in the primary fields (results, annotation and filters read them)
-    if (two && swapped != (((n - 1) & 1) != 0)) { swap_sets(d); swapped = !swapped; }
-    if (!rc && he != hipSuccess) rc = fail(MSNV_EHIP, "batched passes: %s", hipGetErrorString(he));
+    if (two && swapped != (((n - 1) & 1) != 0)) swap_sets(d);
+    if (rc) return rc;
     float total = 0, t1 = 0;
-    if (!rc) {
-        (void)hipEventElapsedTime(&total, ev[0], ev[4 * n]);
-        if (two && hipEventElapsedTime(&t1, ev[0], ev[4 * n + 1]) == hipSuccess) total = std::max(total, t1);
-    }
-    for (int i = 0; i < n && !rc; ++i) {
-        rc = check_counts(d, cnt + (size_t)CNT_WORDS * i, counts);
-        if (rc || !stats) continue;
-        float ms = 0;
+    (void)hipEventElapsedTime(&total, ev[0], ev[4 * n]);
+    if (two && hipEventElapsedTime(&t1, ev[0], ev[4 * n + 1]) == hipSuccess) total = std::max(total, t1);
+    for (int i = 0; i < n; ++i) {
+        const uint32_t *c = cnt + (size_t)CNT_WORDS * i;
+        if (int bad = check_counts(d, c, counts)) return bad;
+        if (!stats) continue;
         msnv_run_stats &s = stats[i];
         s = msnv_run_stats{};
         s.ms_total = total / (float)n;
+        float ms = 0;
         if (hipEventElapsedTime(&ms, ev[4 * i + 1], ev[4 * i + 2]) == hipSuccess) s.ms_pileup = ms;
-        const uint32_t *c = cnt + (size_t)CNT_WORDS * i;
-        s.n_sites = c[2]; s.n_events = c[0]; s.n_overflow = c[1]; s.n_called_pop = c[4] + c[CNT_TALLY]; s.n_called_indiv = c[5] + c[CNT_TALLY + 1];
-        s.algorithmic_bytes = d.algorithmic_bytes;
+        fill_stats(s, c, d);
     }
-    cleanup();
-    return rc;
+    return MSNV_OK;
 }
 
 int dev_run_coverage(DeviceCols &d, int max_cov, void *stream_, msnv_run_stats *stats) {
     hipStream_t st = (hipStream_t)stream_;
     if (max_cov < 1 || max_cov >= COV_BINS) return fail(MSNV_EINVAL, "coverage histogram cutoff must be in [1, %d]", COV_BINS - 1);
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, st));
+    hipEvent_t ev[2];                                       // (the dataset's: no pass is in flight beside a coverage pass)
+    if (int rc = timing_events(d, ev, 2)) return rc;
+    HIP_TRY(hipEventRecord(ev[0], st));
     HIP_TRY(hipMemsetAsync(d.cov_acc, 0, (uint64_t)d.cov_copies * std::max<uint64_t>(1, d.n_cov_rows) * (1 + COV_BINS) * sizeof(unsigned long long), st));
     if (d.n_cov_work) {
         // work items that hold a pair of more than 32 767 intervals are the last n_cov_work_wide of the list (pack.cpp)
@@ -3310,12 +3023,11 @@ int dev_run_coverage(DeviceCols &d, int max_cov, void *stream_, msnv_run_stats *
                                                   d.tile_len, d.cov_acc, (uint32_t)d.n_cov_rows, max_cov, d.cov_copies, d.n_cov_iv);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(e1, st));
+    HIP_TRY(hipEventRecord(ev[1], st));
     HIP_TRY(hipStreamSynchronize(st));
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
     if (stats) stats->ms_coverage = ms;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     return MSNV_OK;
 }
 
@@ -3357,9 +3069,3 @@ __global__ void msnv_warm_kernels() {}
 void warm_kernels(void *stream) { hipLaunchKernelGGL(msnv_warm_kernels, dim3(1), dim3(1), 0, (hipStream_t)stream); (void)hipGetLastError(); }
 
 }  // namespace msnv
-
-extern "C" int msnv_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}

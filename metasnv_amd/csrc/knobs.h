@@ -161,7 +161,7 @@ inline bool cov_thread() { return present("MSNV_COV_THREAD"); }
 inline uint32_t cov_item_intervals() { const long long v = i64_or("MSNV_COV_ITEM", 16384); return (uint32_t)std::min<long long>(v > 0 ? v : 16384, 0x7fffffffll); }
 inline uint32_t cov_narrow_max() { return (uint32_t)std::min<long long>(32767, std::max<long long>(1, i64_or("MSNV_COV_NARROW_MAX", 32767))); }
 
-// ---------------------------------------------------------------------------------- the pass and the allocator (kernels.hip)
+// ---------------------------------------------------------------------------------- the pass (kernels.hip) and the allocator (devmem.hip)
 // MSNV_MERGED_GATHER=block|wave: 1 a workgroup / 2 a wavefront per merged group; 0 = by the dataset's groups.  Per pass (tests/fuzz_parity.py).
 inline int merged_gather() { const char c = first("MSNV_MERGED_GATHER"); return c == 'b' ? 1 : c == 'w' ? 2 : 0; }
 // MSNV_LEAN=0: whole-tile work items through the ordinary body of msnv_pileup_tiles_narrow32.  Per pass (tests/test_gpu_parity.py::test_whole_tile_work_items).

@@ -12,10 +12,9 @@
 
 #include "device.h"
 #include "msnv_internal.h"
+#include "hiptry.h"
 
 namespace msnv {
-
-#define HIP_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(MSNV_EHIP, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
 
 // out[row * S + s]: the frequency, or NaN for "below the depth cutoff" (the host prints -1 there)
 __global__ void msnv_allele_freq_pct(const uint32_t *cov, const uint32_t *cnt, const uint32_t *row_line, uint32_t n_samples,

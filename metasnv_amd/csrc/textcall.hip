@@ -26,14 +26,9 @@
 
 #include "device.h"
 #include "msnv_internal.h"
+#include "hiptry.h"
 
 namespace msnv {
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return fail(MSNV_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 
 constexpr uint32_t TOK_CAP = 10000;            // call_vC.cpp:482: characters of a token that toksplit keeps

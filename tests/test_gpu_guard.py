@@ -1,5 +1,5 @@
 """Out-of-bounds accesses of the kernels: the parity cohorts of every kernel family with guarded device buffers (MSNV_GUARD_ALLOC=1:
-kernels.hip dev_alloc maps every buffer so that it ends at the end of its mapping, unmapped addresses behind it).  In a process of
+devmem.hip dev_alloc maps every buffer so that it ends at the end of its mapping, unmapped addresses behind it).  In a process of
 its own: a GPU memory fault kills the process that caused it."""
 import os
 import subprocess

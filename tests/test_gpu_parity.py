@@ -527,7 +527,7 @@ def test_event_list_grows_when_a_sub_list_overflows(monkeypatch):
 
 
 def test_second_set_follows_a_grown_first_set(monkeypatch):
-    """The overlapped batch keeps a second set of per-pass buffers at the first set's capacities (kernels.hip: ensure_alt).  A dataset
+    """The overlapped batch keeps a second set of per-pass buffers at the first set's capacities (devmem.hip: ensure_alt).  A dataset
     whose event list starts at 1024 grows its first set in run(); the overlapped batches behind that build the second set at the grown
     capacities, end on either set, and the single-pass form runs on whichever set is primary -- the same bytes and the same event count
     as a dataset that never grew, after every step.  The second sequence makes its first overlapped batch right behind the grow and
