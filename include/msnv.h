@@ -263,7 +263,8 @@ void msnv_dataset_destroy(msnv_dataset *ds);
  *   [5] write-pass kernel ms, [6] batches of text that left the device (MSNV_MPTEXT_BATCH bytes each at most, whole tiles),
  *   [7] rounds of samples that went up (MSNV_MPTEXT_ROUND each).
  * DESIGN.md section 7 lists the one divergence from samtools' text (the quality character of a deletion / ref-skip element of the
- * first mate in front of an overlap). */
+ * first mate in front of an overlap).
+ * msnv_mpileup_text(ctx, args, stats) is msnv_mpileup_text_ex(ctx, args, NULL, stats). */
 typedef struct {
     const char *const *bam_paths;
     int32_t     n_bams;
@@ -274,12 +275,37 @@ typedef struct {
     msnv_params params;
 } msnv_mpileup_text_args;
 int msnv_mpileup_text(msnv_ctx *ctx, const msnv_mpileup_text_args *args, uint64_t stats[8]);
+/* msnv_mpileup_text_opts  <-  samtools mpileup -a / -aa, -s (--output-MQ), -O (--output-BP) (samtools >= 1.10 bam_plcmd.c [EXT],
+ * unpinned like the rest of SURVEY.md Appendix C: restated from the manual and from memory of the source, no samtools binary was run
+ * against them).  With them a line is `name \t pos \t REF { \t cnt \t bases \t quals [\t MQ] [\t BP] }`:
+ *   MQ: one character min(mapq + 33, 126) per element the bases column keeps, in its order (the character behind a `^`);
+ *   BP: the 1-based offset in the read, qpos + 1, of every kept element, joined by `,` (deletion / ref-skip element: the read
+ *       bases consumed before it; not strand-aware, not clamped for a read without SEQ);
+ *   a cell without kept elements prints `0 \t * \t *` and `\t *` per extra column.
+ *   all_positions 1: a zero-depth line as well for every other position of every contig that prints a line without it -- 1 to the
+ *   contig's @SQ length, cut to the contig's -l region; REF is the FASTA character, N beyond the FASTA or without a FASTA record.
+ *   all_positions 2: the same for every contig of the header, reads or none (with -l: the listed regions).
+ * Every field 0 (msnv_mpileup_text_opts_default) or opts = NULL: the text of msnv_mpileup_text, byte for byte.  all_positions outside
+ * 0..2 or reserved != 0: MSNV_EINVAL. */
+typedef struct {
+    int32_t all_positions;   /* 0 = lines under reads only, 1 = -a, 2 = -aa               */
+    int32_t output_mq;       /* -s: a MAPQ column behind the qualities                     */
+    int32_t output_bp;       /* -O: a read-offset column behind that                       */
+    int32_t reserved;        /* 0                                                          */
+} msnv_mpileup_text_opts;
+void msnv_mpileup_text_opts_default(msnv_mpileup_text_opts *o);
+int  msnv_mpileup_text_ex(msnv_ctx *ctx, const msnv_mpileup_text_args *args, const msnv_mpileup_text_opts *opts, uint64_t stats[8]);
 /* The same text from record streams in memory (what sam_read1() yields, one stream per sample; the reference as msnv_ref_desc,
  * the -l regions as for msnv_dataset_set_bed: at most one per contig, n_bed = 0 for none).  *text is released with msnv_free;
  * the text is not NUL-terminated.  What the tests and the Python layer use. */
 int msnv_mpileup_text_records(msnv_ctx *ctx, const msnv_ref_desc *ref, const msnv_params *params, int32_t n_bed, const int32_t *bed_tid,
                               const int64_t *bed_beg, const int64_t *bed_end, const uint8_t *const *records, const uint64_t *n_bytes,
                               int32_t n, char **text, uint64_t *text_bytes, uint64_t stats[8]);
+/* msnv_mpileup_text_records with options behind `params` (NULL: none; msnv_mpileup_text_records is this call with opts = NULL). */
+int msnv_mpileup_text_records_ex(msnv_ctx *ctx, const msnv_ref_desc *ref, const msnv_params *params, const msnv_mpileup_text_opts *opts,
+                                 int32_t n_bed, const int32_t *bed_tid, const int64_t *bed_beg, const int64_t *bed_end,
+                                 const uint8_t *const *records, const uint64_t *n_bytes, int32_t n, char **text, uint64_t *text_bytes,
+                                 uint64_t stats[8]);
 /* The sizes at which the kernels' forms change (tests): positions per tile, read descriptors taken through LDS at a time. */
 void msnv_mpileup_text_geometry(int32_t *tile_positions, int32_t *lds_reads);
 

@@ -67,6 +67,10 @@ class MpileupTextArgs(C.Structure):
                 ("out_path", C.c_char_p), ("host_threads", C.c_int32), ("params", Params)]
 
 
+class MpileupTextOpts(C.Structure):
+    _fields_ = [("all_positions", C.c_int32), ("output_mq", C.c_int32), ("output_bp", C.c_int32), ("reserved", C.c_int32)]
+
+
 class RefDesc(C.Structure):
     _fields_ = [("n_contigs", C.c_int32), ("names", C.POINTER(C.c_char_p)), ("lengths", C.POINTER(C.c_int64)),
                 ("seqs", C.POINTER(C.c_char_p)), ("seq_lens", C.POINTER(C.c_int64))]
@@ -141,6 +145,10 @@ SYMBOLS = [
     ("msnv_mpileup_text", C.c_int, [_vp, P(MpileupTextArgs), P(C.c_uint64)]),
     ("msnv_mpileup_text_records", C.c_int, [_vp, P(RefDesc), P(Params), C.c_int32, P(C.c_int32), P(C.c_int64), P(C.c_int64), P(_vp), P(C.c_uint64), C.c_int32,
                                             P(P(C.c_char)), P(C.c_uint64), P(C.c_uint64)]),
+    ("msnv_mpileup_text_opts_default", None, [P(MpileupTextOpts)]),
+    ("msnv_mpileup_text_ex", C.c_int, [_vp, P(MpileupTextArgs), P(MpileupTextOpts), P(C.c_uint64)]),
+    ("msnv_mpileup_text_records_ex", C.c_int, [_vp, P(RefDesc), P(Params), P(MpileupTextOpts), C.c_int32, P(C.c_int32), P(C.c_int64), P(C.c_int64), P(_vp), P(C.c_uint64),
+                                               C.c_int32, P(P(C.c_char)), P(C.c_uint64), P(C.c_uint64)]),
     ("msnv_mpileup_text_geometry", None, [P(C.c_int32), P(C.c_int32)]),
     ("msnv_bam_records_many", C.c_int, [_vp, P(C.c_char_p), C.c_int32, C.c_int32, P(P(C.c_uint8)), P(C.c_uint64)]),
     ("msnv_bgzf_inflate", C.c_int, [_vp, C.c_char_p, C.c_int32, P(P(C.c_uint8)), P(C.c_uint64), P(C.c_uint64)]),

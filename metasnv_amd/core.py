@@ -46,11 +46,12 @@ class Context:
             lib.msnv_ctx_destroy(self._h)
             self._h = C.c_void_p()
 
-    def mpileup_text(self, names, lengths, seqs, samples, bed=None, **params):
+    def mpileup_text(self, names, lengths, seqs, samples, bed=None, all_positions=0, output_mq=False, output_bp=False, **params):
         """The text of `samtools mpileup -f REF [-l BED] -B -b LIST` for record streams in memory (msnv_mpileup_text_records), formatted on
         the device.  samples: one stream of raw BAM records (bytes / numpy uint8) per sample; seqs: FASTA characters per contig, None for a
         contig the FASTA lacks, or None for no reference at all; bed: (tid, beg, end) regions, 0-based half-open, at most one per contig;
         params: the mpileup fields of msnv_params (min_baseq, flag_filter, count_orphans, max_depth, min_mapq, ignore_overlaps).
+        all_positions (0, 1: -a, 2: -aa), output_mq (-s), output_bp (-O): msnv_mpileup_text_opts; all off: the text as it is without them.
         Returns the text as bytes; self.mpileup_stats holds the call's statistics."""
         n = len(names)
         c_names = _cstr_array(names)
@@ -71,7 +72,8 @@ class Context:
         text = C.POINTER(C.c_char)()
         nb = C.c_uint64()
         st = (C.c_uint64 * 8)()
-        check(lib.msnv_mpileup_text_records(self._h, C.byref(rd), C.byref(p), len(bed), bt, bb, be, ptrs, sizes, m, C.byref(text), C.byref(nb), st))
+        o = _mpileup_opts(all_positions, output_mq, output_bp)
+        check(lib.msnv_mpileup_text_records_ex(self._h, C.byref(rd), C.byref(p), C.byref(o), len(bed), bt, bb, be, ptrs, sizes, m, C.byref(text), C.byref(nb), st))
         try:
             out = C.string_at(text, nb.value)
         finally:
@@ -79,9 +81,9 @@ class Context:
         self.mpileup_stats = _mpileup_stats(st)
         return out
 
-    def mpileup_files(self, bams, fasta, out, bed=None, host_threads=0, **params):
-        """`samtools mpileup -f fasta [-l bed] -B -b <bams> > out` (msnv_mpileup_text); out None or "-": stdout; bed: the path of a BED
-        file.  Returns the call's statistics."""
+    def mpileup_files(self, bams, fasta, out, bed=None, host_threads=0, all_positions=0, output_mq=False, output_bp=False, **params):
+        """`samtools mpileup -f fasta [-l bed] -B -b <bams> [-a | -aa] [-s] [-O] > out` (msnv_mpileup_text_ex); out None or "-": stdout;
+        bed: the path of a BED file; all_positions, output_mq, output_bp as for mpileup_text.  Returns the call's statistics."""
         a = _lib.MpileupTextArgs()
         paths = _cstr_array(list(bams))
         a.bam_paths = paths; a.n_bams = len(bams)
@@ -91,7 +93,8 @@ class Context:
         a.host_threads = host_threads
         a.params = default_params(**params)
         st = (C.c_uint64 * 8)()
-        check(lib.msnv_mpileup_text(self._h, C.byref(a), st))
+        o = _mpileup_opts(all_positions, output_mq, output_bp)
+        check(lib.msnv_mpileup_text_ex(self._h, C.byref(a), C.byref(o), st))
         self.mpileup_stats = _mpileup_stats(st)
         return self.mpileup_stats
 
@@ -113,6 +116,13 @@ def mpileup_text_geometry():
     t, b = C.c_int32(), C.c_int32()
     lib.msnv_mpileup_text_geometry(C.byref(t), C.byref(b))
     return t.value, b.value
+
+
+def _mpileup_opts(all_positions, output_mq, output_bp):
+    o = _lib.MpileupTextOpts()
+    lib.msnv_mpileup_text_opts_default(C.byref(o))
+    o.all_positions, o.output_mq, o.output_bp = int(all_positions), int(bool(output_mq)), int(bool(output_bp))
+    return o
 
 
 def _mpileup_stats(st):

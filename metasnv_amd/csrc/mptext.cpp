@@ -1,11 +1,14 @@
-// metasnv_amd/csrc/mptext.cpp -- msnv_mpileup_text / msnv_mpileup_text_records (include/msnv.h): the text `samtools mpileup -f REF
+// metasnv_amd/csrc/mptext.cpp -- msnv_mpileup_text[_ex] / msnv_mpileup_text_records[_ex] (include/msnv.h): the text `samtools mpileup -f REF
 // [-l BED] -B -b LIST` pipes into snpCall (metaSNV.py:160-165), formatted on the device (mptext_k.hip).  This file is the host side:
 //
 //   rounds   the samples come in rounds of MSNV_MPTEXT_ROUND.  Per round the sequential read-level steps run on host threads -- pack.cpp's
 //            host_prepass on a context-less dataset: read filters, depth cap, the overlapping-mates quality edit; token_limit is 0, mpileup
 //            cuts nothing -- and the record streams (edited qualities), and per sample the table of its pushed reads in file order, go up.
 //   tiles    MPT_T positions of one contig; per (tile, sample) the read list: from the first read with end > t0 to the first with
-//            pos >= t0 + MPT_T.  Tiles no list reaches are never made.  Tiles go to the device in groups that bound the per-cell tables.
+//            pos >= t0 + MPT_T.  Tiles no list reaches are never made -- unless every position is asked for (msnv_mpileup_text_opts
+//            all_positions): then they are EMPTY tiles (MptTile contig < 0), which carry no read lists, get no workgroups and are
+//            written a lane per line, but are tiles of their group like any other: the same scan, the same offsets, the same batches.
+//            Tiles go to the device in groups that bound the per-cell tables.
 //   batches  a group is measured and scanned at once; its text is written in batches of whole tiles of at most MSNV_MPTEXT_BATCH bytes
 //            (a tile that is longer is a batch of its own), through two device buffers and two pinned buffers: the copy and the file
 //            write of batch k run under the kernels of batch k + 1.  Neither the text nor a genome-wide cell table is ever resident.
@@ -88,8 +91,9 @@ struct Run {
     void *pin_text[2] = {nullptr, nullptr}, *pin_small = nullptr, *ev[8] = {};
     uint64_t rounds = 0, batches = 0; double ms_measure = 0, ms_write = 0;
     unsigned long long totals[2] = {0, 0};
+    uint32_t opt = 0; int32_t all_level = 0;       // MPT_ALL | MPT_MQ | MPT_BP; 1: -a, 2: -aa
 
-    Run(msnv_ctx *c, msnv_dataset *d, Sink &s) : ctx(c), ds(d), sink(s) {}
+    Run(msnv_ctx *c, msnv_dataset *d, Sink &s, uint32_t o, int32_t lvl) : ctx(c), ds(d), sink(s), opt(o), all_level(lvl) {}
     ~Run() {
         if (ctx) { (void)dev_stream_wait(ctx->stream); if (ctx->stream2) (void)dev_stream_wait(ctx->stream2); }
         for (void *p : dev) dev_free(p);
@@ -133,19 +137,22 @@ struct Run {
     int format();
 };
 
-// Tiles in (contig, position) order, made on demand.
+// Tiles in (contig, position) order, made on demand.  all: the positions [fb, fe) of a contig in play -- its @SQ length cut to its BED
+// region -- have lines whether a read covers them or not, so the stretches of them no read list reaches become empty tiles.
 struct Tiler {
-    const msnv_dataset &ds; const std::vector<SampleTab> &tabs; const std::vector<int32_t> &play;      // play: contigs that hold pushed reads, ascending
+    const msnv_dataset &ds; const std::vector<SampleTab> &tabs; const std::vector<int32_t> &play;      // play: the contigs that print lines, ascending
+    const bool all;
     size_t ci = 0; bool open = false; int64_t t0 = 0;
     std::vector<size_t> run; std::vector<uint32_t> lo, hi, end;      // per sample: cursor into its runs; list cursors and end of the contig's run
-    Tiler(const msnv_dataset &d, const std::vector<SampleTab> &t, const std::vector<int32_t> &p) : ds(d), tabs(t), play(p), run(t.size(), 0), lo(t.size()), hi(t.size()), end(t.size()) {}
-    // the next tile and its S ranges (appended); false: no tile is left
-    bool next(std::vector<MptTile> &tiles, std::vector<MptRange> &ranges) {
+    Tiler(const msnv_dataset &d, const std::vector<SampleTab> &t, const std::vector<int32_t> &p, bool a) : ds(d), tabs(t), play(p), all(a), run(t.size(), 0), lo(t.size()), hi(t.size()), end(t.size()) {}
+    // the next tile; a tile that holds reads appends its index to work and its S ranges to ranges; false: no tile is left
+    bool next(std::vector<MptTile> &tiles, std::vector<MptRange> &ranges, std::vector<uint32_t> &work) {
         const size_t S = tabs.size();
         for (;;) {
             if (ci >= play.size()) return false;
             const int32_t tid = play[ci];
             const int64_t bb = ds.bed_beg[(size_t)tid], be = ds.bed_end[(size_t)tid];
+            const int64_t fb = std::max<int64_t>(bb, 0), fe = all ? std::min<int64_t>(be, std::min<int64_t>(ds.lengths[(size_t)tid], (int64_t)INT32_MAX)) : INT64_MIN;
             if (!open) {
                 int64_t first = INT64_MAX;
                 for (size_t s = 0; s < S; ++s) {
@@ -154,7 +161,7 @@ struct Tiler {
                     if (run[s] < t.run_tid.size() && t.run_tid[run[s]] == tid) { lo[s] = hi[s] = t.run_lo[run[s]]; end[s] = t.run_lo[run[s] + 1]; first = std::min<int64_t>(first, t.pos[lo[s]]); }
                     else lo[s] = hi[s] = end[s] = 0;
                 }
-                t0 = std::max(first, bb) / MPT_T * MPT_T;
+                t0 = (fb < fe ? fb : std::max(first, bb)) / MPT_T * MPT_T;      // (fb <= max(first, bb))
                 open = true;
             }
             if (t0 >= be) { open = false; ++ci; continue; }
@@ -167,11 +174,17 @@ struct Tiler {
                 any |= lo[s] < hi[s];
                 if (hi[s] < end[s]) { left = true; ahead = std::min<int64_t>(ahead, t.pos[hi[s]]); }
             }
+            if (!any && t0 < fe) {
+                tiles.push_back(MptTile{~(int32_t)ci, (int32_t)t0, (int32_t)std::max<int64_t>(t0, fb), (int32_t)std::min<int64_t>(t0 + MPT_T, fe)});
+                t0 += MPT_T;
+                return true;
+            }
             if (!any) {
                 if (!left) { open = false; ++ci; continue; }
                 t0 = ahead / MPT_T * MPT_T;                      // (ahead >= t0 + MPT_T: the position of a read no list has reached)
                 continue;
             }
+            work.push_back((uint32_t)tiles.size());
             tiles.push_back(MptTile{(int32_t)ci, (int32_t)t0, (int32_t)std::max<int64_t>(t0, bb), (int32_t)std::min<int64_t>(t0 + MPT_T, std::min<int64_t>(be, (int64_t)INT32_MAX))});
             for (size_t s = 0; s < S; ++s) ranges.push_back(MptRange{lo[s], hi[s]});
             t0 += MPT_T;
@@ -182,16 +195,17 @@ struct Tiler {
 
 int Run::format() {
     const size_t S = tabs.size();
-    // ---- contigs in play: names and reference characters
+    // ---- contigs in play: names and reference characters.  -aa: every contig of the header prints lines, reads or none
     std::vector<int32_t> play;
-    for (const SampleTab &t : tabs) play.insert(play.end(), t.run_tid.begin(), t.run_tid.end());
+    if (all_level >= 2) for (size_t c = 0; c < ds->names.size(); ++c) play.push_back((int32_t)c);
+    else for (const SampleTab &t : tabs) play.insert(play.end(), t.run_tid.begin(), t.run_tid.end());
     std::sort(play.begin(), play.end());
     play.erase(std::unique(play.begin(), play.end()), play.end());
     if (play.empty() || S == 0) return MSNV_OK;
     std::vector<MptContig> contigs; std::vector<char> names, ref;
     for (int32_t tid : play) {
         const std::string &nm = ds->names[(size_t)tid];
-        MptContig c{ref.size(), ds->has_seq[(size_t)tid] ? (int64_t)ds->seqs[(size_t)tid].size() : -1, (uint32_t)names.size(), (uint32_t)nm.size()};
+        MptContig c{ref.size(), ds->has_seq[(size_t)tid] ? (int64_t)ds->seqs[(size_t)tid].size() : -1, (uint32_t)names.size(), (uint32_t)nm.size(), ds->lengths[(size_t)tid]};
         names.insert(names.end(), nm.begin(), nm.end());
         if (c.ref_len > 0) ref.insert(ref.end(), ds->seqs[(size_t)tid].begin(), ds->seqs[(size_t)tid].end());
         contigs.push_back(c);
@@ -204,12 +218,13 @@ int Run::format() {
     if (int rc = up(&d_recs, d_rec)) return rc;
     if (int rc = up(&d_tabs, d_reads)) return rc;
     J.contigs = d_contigs; J.names = d_names; J.ref = d_ref; J.rec = d_recs; J.reads = d_tabs;
-    J.S = (uint32_t)S; J.min_baseq = ds->params.min_baseq;
+    J.S = (uint32_t)S; J.min_baseq = ds->params.min_baseq; J.opt = opt;
 
-    // ---- the group's tables: at most 64 MB of cells
-    const uint32_t G = (uint32_t)std::min<uint64_t>(2048, std::max<uint64_t>(1, (64ull << 20) / ((uint64_t)MPT_T * S * 12)));
+    // ---- the group's tables: at most 64 MB of cells (cnt, blen, rel; bplen with the read-offset column)
+    const uint64_t cell_bytes = 12 + ((opt & MPT_BP) ? 4 : 0);
+    const uint32_t G = (uint32_t)std::min<uint64_t>(2048, std::max<uint64_t>(1, (64ull << 20) / ((uint64_t)MPT_T * S * cell_bytes)));
     J.lines_cap = G * MPT_T;
-    MptTile *d_tiles = nullptr; MptRange *d_ranges = nullptr; uint8_t *d_small = nullptr;
+    MptTile *d_tiles = nullptr; MptRange *d_ranges = nullptr; uint32_t *d_work = nullptr; uint8_t *d_small = nullptr;
     auto table = [&](auto *&dst, uint64_t bytes) -> int {
         void *q = nullptr;
         if (int rc = alloc(&q, bytes)) return rc;
@@ -221,13 +236,15 @@ int Run::format() {
     if (int rc = table(J.cnt, (uint64_t)J.lines_cap * S * 4)) return rc;
     if (int rc = table(J.blen, (uint64_t)J.lines_cap * S * 4)) return rc;
     if (int rc = table(J.rel, (uint64_t)J.lines_cap * S * 4)) return rc;
+    if (opt & MPT_BP) if (int rc = table(J.bplen, (uint64_t)J.lines_cap * S * 4)) return rc;
+    if (opt & MPT_ALL) if (int rc = table(d_work, (uint64_t)G * 4)) return rc;
     if (int rc = table(J.active, (uint64_t)J.lines_cap * 4)) return rc;
     if (int rc = table(J.line_len, (uint64_t)J.lines_cap * 4)) return rc;
     if (int rc = table(J.line_off, ((uint64_t)J.lines_cap + 1) * 8)) return rc;
     if (int rc = table(J.tile_off, ((uint64_t)G + 1) * 8)) return rc;
     if (int rc = table(d_small, 32)) return rc;
     if (int rc = dev_memset(d_small, 0, 32)) return rc;
-    J.tiles = d_tiles; J.ranges = d_ranges;
+    J.tiles = d_tiles; J.ranges = d_ranges; J.work = d_work;
     J.totals = reinterpret_cast<unsigned long long *>(d_small); J.flag = reinterpret_cast<uint32_t *>(d_small + 16);
     // pinned: the group's tile offsets, and per text buffer the self-check flag as it stood behind the batch
     if (int rc = mpt_pinned_alloc(&pin_small, ((uint64_t)G + 1) * 8 + 64)) return rc;
@@ -252,18 +269,19 @@ int Run::format() {
         return sink.put((const char *)pin_text[pend.slot], pend.bytes);
     };
 
-    Tiler tiler(*ds, tabs, play);
-    std::vector<MptTile> tiles; std::vector<MptRange> ranges;
+    Tiler tiler(*ds, tabs, play, (opt & MPT_ALL) != 0);
+    std::vector<MptTile> tiles; std::vector<MptRange> ranges; std::vector<uint32_t> work;      // work: the group's tiles that hold reads
     for (;;) {
-        tiles.clear(); ranges.clear();
-        while (tiles.size() < G && tiler.next(tiles, ranges)) {}
+        tiles.clear(); ranges.clear(); work.clear();
+        while (tiles.size() < G && tiler.next(tiles, ranges, work)) {}
         if (tiles.empty()) break;
         const uint32_t nt = (uint32_t)tiles.size();
         if (int rc = dev_stream_wait(sa)) return rc;                       // the last group's write kernels have read its tables
         if (int rc = dev_upload(d_tiles, tiles.data(), tiles.size() * sizeof(MptTile))) return rc;
         if (int rc = dev_upload(d_ranges, ranges.data(), ranges.size() * sizeof(MptRange))) return rc;
+        if (opt & MPT_ALL) if (int rc = dev_upload(d_work, work.data(), work.size() * sizeof(uint32_t))) return rc;
         if (int rc = mpt_event_record(ev_m0, sa)) return rc;
-        if (int rc = mpt_measure(J, nt, sa)) return rc;
+        if (int rc = mpt_measure(J, nt, (uint32_t)work.size(), sa)) return rc;
         if (int rc = mpt_event_record(ev_m1, sa)) return rc;
         if (int rc = mpt_copy_to_host_async(h_tile_off, J.tile_off, ((uint64_t)nt + 1) * 8, sa)) return rc;
         if (int rc = flush()) return rc;                                   // (the last batch's file write runs under the measure pass)
@@ -293,7 +311,9 @@ int Run::format() {
             const int slot = (int)(batches & 1);
             if (batches >= 2) if (int rc = mpt_stream_wait_event(sa, ev_copy[slot])) return rc;      // the copy of batch k - 2 has read this buffer
             if (int rc = mpt_event_record(ev_start[slot], sa)) return rc;
-            if (int rc = mpt_write(J, lo_t, j, base, d_text[slot], sa)) return rc;
+            const uint32_t w_lo = (uint32_t)(std::lower_bound(work.begin(), work.end(), lo_t) - work.begin());      // (without MPT_ALL: lo_t and j)
+            const uint32_t w_hi = (uint32_t)(std::lower_bound(work.begin(), work.end(), j) - work.begin());
+            if (int rc = mpt_write(J, lo_t, j, w_lo, w_hi, base, d_text[slot], sa)) return rc;
             if (int rc = mpt_event_record(ev_kernel[slot], sa)) return rc;
             if (int rc = mpt_stream_wait_event(sb, ev_kernel[slot])) return rc;
             if (int rc = mpt_copy_to_host_async(pin_text[slot], d_text[slot], bytes, sb)) return rc;
@@ -327,7 +347,7 @@ void fill_stats(uint64_t stats[8], const Run &r, const Sink &sink) {
 namespace msnv {
 
 int mptext_records(msnv_ctx *ctx, const msnv_ref_desc *ref, const msnv_params *params, const MptBed &bed, const uint8_t *const *records,
-                   const uint64_t *n_bytes, int32_t n, char **text, uint64_t *text_bytes, uint64_t stats[8]) {
+                   const uint64_t *n_bytes, int32_t n, uint32_t opt, int32_t all_level, char **text, uint64_t *text_bytes, uint64_t stats[8]) {
     msnv_params P;
     mpileup_params(params, P);
     msnv_dataset *ds = nullptr;
@@ -336,7 +356,7 @@ int mptext_records(msnv_ctx *ctx, const msnv_ref_desc *ref, const msnv_params *p
     Sink sink; sink.to_mem = true;
     if (!rc) rc = dev_set_device(ctx->device);
     if (!rc) {
-        Run run(ctx, ds, sink);
+        Run run(ctx, ds, sink, opt, all_level);
         const int per = knob::mptext_round_samples();
         for (int i = 0; i < n && !rc; i += per) rc = run.add_round(records + i, n_bytes + i, std::min(per, n - i), 0);
         if (!rc) rc = run.format();
@@ -351,7 +371,7 @@ int mptext_records(msnv_ctx *ctx, const msnv_ref_desc *ref, const msnv_params *p
 }
 
 int mptext_files(msnv_ctx *ctx, const char *const *bam_paths, int32_t n_bams, const char *ref_fasta, const char *bed_path, const char *out_path,
-                 int32_t host_threads, const msnv_params *params, uint64_t stats[8]) {
+                 int32_t host_threads, const msnv_params *params, uint32_t opt, int32_t all_level, uint64_t stats[8]) {
     msnv_params P;
     mpileup_params(params, P);
     msnv_dataset *ds = nullptr;
@@ -364,7 +384,7 @@ int mptext_files(msnv_ctx *ctx, const char *const *bam_paths, int32_t n_bams, co
     }
     if (!rc) rc = dev_set_device(ctx->device);
     if (!rc) {
-        Run run(ctx, ds, sink);
+        Run run(ctx, ds, sink, opt, all_level);
         const int per = knob::mptext_round_samples();
         for (int i = 0; i < n_bams && !rc; i += per) {                  // a round of files: read and inflated by the host threads, then released
             const int m = std::min(per, n_bams - i);
@@ -391,24 +411,53 @@ int mptext_files(msnv_ctx *ctx, const char *const *bam_paths, int32_t n_bams, co
 
 }  // namespace msnv
 
-extern "C" int msnv_mpileup_text(msnv_ctx *ctx, const msnv_mpileup_text_args *a, uint64_t stats[8]) {
+namespace {
+
+// opts (NULL: none) as the kernels' option bits and the -a level
+int read_opts(const char *who, const msnv_mpileup_text_opts *o, uint32_t &opt, int32_t &all_level) {
+    opt = 0; all_level = 0;
+    if (!o) return MSNV_OK;
+    if (o->all_positions < 0 || o->all_positions > 2) return fail(MSNV_EINVAL, "%s: all_positions is %d, not 0, 1 (-a) or 2 (-aa)", who, o->all_positions);
+    if (o->reserved != 0) return fail(MSNV_EINVAL, "%s: the reserved field of msnv_mpileup_text_opts is %d, not 0", who, o->reserved);
+    all_level = o->all_positions;
+    opt = (all_level ? MPT_ALL : 0u) | (o->output_mq ? MPT_MQ : 0u) | (o->output_bp ? MPT_BP : 0u);
+    return MSNV_OK;
+}
+
+}  // namespace
+
+extern "C" void msnv_mpileup_text_opts_default(msnv_mpileup_text_opts *o) { if (o) *o = msnv_mpileup_text_opts{0, 0, 0, 0}; }
+
+extern "C" int msnv_mpileup_text_ex(msnv_ctx *ctx, const msnv_mpileup_text_args *a, const msnv_mpileup_text_opts *opts, uint64_t stats[8]) {
     clear_error();
     if (!ctx || !a || !a->bam_paths || a->n_bams <= 0) return fail(MSNV_EINVAL, "msnv_mpileup_text: ctx and bam_paths are required");
     for (int i = 0; i < a->n_bams; ++i) if (!a->bam_paths[i]) return fail(MSNV_EINVAL, "msnv_mpileup_text: BAM path %d is NULL", i);
-    try { return mptext_files(ctx, a->bam_paths, a->n_bams, a->ref_fasta, a->bed_split_path, a->out_path, a->host_threads, &a->params, stats); }
+    uint32_t opt; int32_t lvl;
+    if (int rc = read_opts("msnv_mpileup_text_ex", opts, opt, lvl)) return rc;
+    try { return mptext_files(ctx, a->bam_paths, a->n_bams, a->ref_fasta, a->bed_split_path, a->out_path, a->host_threads, &a->params, opt, lvl, stats); }
     catch (const std::exception &e) { return fail(MSNV_ENOMEM, "msnv_mpileup_text: %s", e.what()); }
 }
 
-extern "C" int msnv_mpileup_text_records(msnv_ctx *ctx, const msnv_ref_desc *ref, const msnv_params *params, int32_t n_bed, const int32_t *bed_tid,
-                                         const int64_t *bed_beg, const int64_t *bed_end, const uint8_t *const *records, const uint64_t *n_bytes, int32_t n,
-                                         char **text, uint64_t *text_bytes, uint64_t stats[8]) {
+extern "C" int msnv_mpileup_text(msnv_ctx *ctx, const msnv_mpileup_text_args *a, uint64_t stats[8]) { return msnv_mpileup_text_ex(ctx, a, nullptr, stats); }
+
+extern "C" int msnv_mpileup_text_records_ex(msnv_ctx *ctx, const msnv_ref_desc *ref, const msnv_params *params, const msnv_mpileup_text_opts *opts, int32_t n_bed,
+                                            const int32_t *bed_tid, const int64_t *bed_beg, const int64_t *bed_end, const uint8_t *const *records,
+                                            const uint64_t *n_bytes, int32_t n, char **text, uint64_t *text_bytes, uint64_t stats[8]) {
     clear_error();
     if (!ctx || !ref || !text || !text_bytes || n < 0 || (n && (!records || !n_bytes)) || n_bed < 0 || (n_bed && (!bed_tid || !bed_beg || !bed_end)))
         return fail(MSNV_EINVAL, "msnv_mpileup_text_records: bad argument");
     for (int i = 0; i < n; ++i) if (n_bytes[i] && !records[i]) return fail(MSNV_EINVAL, "msnv_mpileup_text_records: stream %d is NULL", i);
     *text = nullptr; *text_bytes = 0;
-    try { return mptext_records(ctx, ref, params, MptBed{n_bed, bed_tid, bed_beg, bed_end}, records, n_bytes, n, text, text_bytes, stats); }
+    uint32_t opt; int32_t lvl;
+    if (int rc = read_opts("msnv_mpileup_text_records_ex", opts, opt, lvl)) return rc;
+    try { return mptext_records(ctx, ref, params, MptBed{n_bed, bed_tid, bed_beg, bed_end}, records, n_bytes, n, opt, lvl, text, text_bytes, stats); }
     catch (const std::exception &e) { return fail(MSNV_ENOMEM, "msnv_mpileup_text_records: %s", e.what()); }
+}
+
+extern "C" int msnv_mpileup_text_records(msnv_ctx *ctx, const msnv_ref_desc *ref, const msnv_params *params, int32_t n_bed, const int32_t *bed_tid,
+                                         const int64_t *bed_beg, const int64_t *bed_end, const uint8_t *const *records, const uint64_t *n_bytes, int32_t n,
+                                         char **text, uint64_t *text_bytes, uint64_t stats[8]) {
+    return msnv_mpileup_text_records_ex(ctx, ref, params, nullptr, n_bed, bed_tid, bed_beg, bed_end, records, n_bytes, n, text, text_bytes, stats);
 }
 
 extern "C" void msnv_mpileup_text_geometry(int32_t *tile_positions, int32_t *lds_reads) {

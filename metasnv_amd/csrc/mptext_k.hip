@@ -9,9 +9,15 @@
 //   mpt_cells<false>   per cell: kept elements (cnt), length of the bases string, "a pushed read covers the position"
 //   mpt_cell_offsets   per line: the cells' offsets behind the header, the line's length (0: no read there, or outside the BED)
 //   mpt_scan_lines     exclusive scan of the line lengths, 64-bit
-//   mpt_cells<true>    the bytes, at the offsets; every cell's writer checks that it ended where the next cell starts
+//   mpt_cells<true>    the bytes, at the offsets; every column's writer checks that it ended where the next column or cell starts
+//   mpt_empty_lines    MPT_ALL: the lines of the tiles no read list reaches, a lane per line, all S cells of it
 //
 // A lane spends work on reads of its pair that do not cover its position (at most MPT_T - 1 positions to either side): fine for short reads.
+//
+// The options of msnv_mpileup_text_opts are the template argument OPT (MPT_ALL | MPT_MQ | MPT_BP, mptext.h): OPT = 0 is the text of
+// `samtools mpileup` without -a / -s / -O and compiles to the kernels as they were before the options existed.
+#include <type_traits>
+
 #include <hip/hip_runtime.h>
 
 #include "mptext.h"
@@ -93,10 +99,11 @@ __device__ __forceinline__ bool resolve_elem(const MptRead &d, const uint8_t *ci
 
 // One lane's walk over the read list of its (tile, sample).  Every lane of the wavefront takes part in the LDS hand-over; a lane whose
 // position has no line (`mine` false) handles no read.  WRITE: the element's characters go to bases / quals, which advance; otherwise only
-// cnt / blen / covered are counted -- by the same expressions.
-template <bool WRITE>
+// cnt / blen / covered are counted -- by the same expressions.  MPT_MQ: one character per kept element goes to mqc; MPT_BP: bplen counts
+// ",<qpos + 1>" per kept element (the caller takes the first comma off), bpc receives the numbers.
+template <bool WRITE, uint32_t OPT>
 __device__ __forceinline__ void mpt_traverse(const MptJob &J, const MptRange rg, const uint8_t *rec, const MptRead *reads, const MptContig &ct, int32_t p, bool mine,
-                                             MptRead *sh, uint32_t &cnt, uint32_t &blen, bool &covered, char *&bases, char *&quals) {
+                                             MptRead *sh, uint32_t &cnt, uint32_t &blen, uint32_t &bplen, bool &covered, char *&bases, char *&quals, char *&mqc, char *&bpc) {
     const int lane = threadIdx.x;
     const char *ref = ct.ref_len >= 0 ? J.ref + ct.ref_off : nullptr;
     for (uint32_t b0 = rg.lo; b0 < rg.hi; b0 += MPT_B) {
@@ -123,6 +130,7 @@ __device__ __forceinline__ void mpt_traverse(const MptJob &J, const MptRange rg,
             const uint32_t n_indel = (uint32_t)(e.indel < 0 ? -e.indel : e.indel);
             ++cnt;
             blen += (head ? 2u : 0u) + 1u + (n_indel ? 1u + dec_digits(n_indel) + n_indel : 0u) + (tail ? 1u : 0u);
+            if (OPT & MPT_BP) bplen += 1u + dec_digits((uint32_t)e.qpos + 1u);
             if (WRITE) {
                 char *o = bases;
                 if (head) { const uint32_t mq = d.flags & 0xffu; *o++ = '^'; *o++ = (char)(mq > 93u ? 126u : mq + 33u); }
@@ -148,26 +156,31 @@ __device__ __forceinline__ void mpt_traverse(const MptJob &J, const MptRange rg,
                 if (tail) *o++ = '$';
                 bases = o;
                 *quals++ = (char)min(q + 33u, 126u);
+                if (OPT & MPT_MQ) *mqc++ = (char)min((d.flags & 0xffu) + 33u, 126u);
+                if (OPT & MPT_BP) { if (cnt > 1u) *bpc++ = ','; bpc = put_dec(bpc, (uint32_t)e.qpos + 1u); }
             }
         }
     }
 }
 
-// grid: n_tiles * S workgroups of MPT_T lanes; workgroup b = (tile b / S of the group, sample b % S).  WRITE: the lines of tiles
-// [tile_lo, ...) go to text, whose first byte is byte base_off of the group's text.
-template <bool WRITE>
-__global__ __launch_bounds__(MPT_T) void mpt_cells(const MptJob J, uint32_t tile_lo, unsigned long long base_off, char *text) {
+// grid: n_items * S workgroups of MPT_T lanes; workgroup b = (work item item_lo + b / S of the group, sample b % S).  A work item is a
+// tile; with MPT_ALL it is an entry of J.work, the tiles that hold reads (the empty ones are mpt_empty_lines').  WRITE: the lines go to
+// text, whose first byte is byte base_off of the group's text.
+template <bool WRITE, uint32_t OPT>
+__global__ __launch_bounds__(MPT_T) void mpt_cells(const MptJob J, uint32_t item_lo, unsigned long long base_off, char *text) {
     __shared__ __align__(16) MptRead sh[MPT_B];
-    const uint32_t tile = tile_lo + blockIdx.x / J.S, s = blockIdx.x % J.S;
+    const uint32_t item = item_lo + blockIdx.x / J.S, s = blockIdx.x % J.S;
+    const uint32_t tile = (OPT & MPT_ALL) ? J.work[item] : item;
     const MptTile tl = J.tiles[tile];
-    const MptRange rg = J.ranges[(size_t)tile * J.S + s];
+    const MptRange rg = J.ranges[(size_t)item * J.S + s];
     const MptContig ct = J.contigs[tl.contig];
     const int32_t p = tl.t0 + (int32_t)threadIdx.x;
     const uint32_t line = tile * MPT_T + threadIdx.x;
     const size_t cell = (size_t)s * J.lines_cap + line;
     bool mine = p >= tl.vbeg && p < tl.vend;
-    uint32_t cnt = 0, blen = 0; bool covered = false;
+    uint32_t cnt = 0, blen = 0, bplen = 0; bool covered = false;
     char *bases = nullptr, *quals = nullptr, *bases_end = nullptr, *next_cell = nullptr;
+    char *mqc = nullptr, *bpc = nullptr, *quals_end = nullptr, *mq_end = nullptr;      // MPT_MQ / MPT_BP: the columns behind the qualities
     if (WRITE) {
         const unsigned long long off = J.line_off[line], off_next = J.line_off[line + 1];
         mine = mine && off_next > off;
@@ -189,34 +202,69 @@ __global__ __launch_bounds__(MPT_T) void mpt_cells(const MptJob J, uint32_t tile
             quals = bases_end + 1;
             next_cell = s + 1 < J.S ? lp + hl + J.rel[cell + J.lines_cap] : text + (off_next - base_off) - 1;
             if (s + 1 == J.S) *next_cell = '\n';
-            if (want_cnt == 0) { *bases++ = '*'; *quals++ = '*'; mine = false; }      // no read there, or every element below -Q
+            if (OPT & (MPT_MQ | MPT_BP)) {                                            // each column: a tab, then max(its length, 1) bytes
+                char *e = quals + max(want_cnt, 1u);
+                quals_end = e;
+                if (OPT & MPT_MQ) { *e = '\t'; mqc = e + 1; e = mqc + max(want_cnt, 1u); mq_end = e; }
+                if (OPT & MPT_BP) { *e = '\t'; bpc = e + 1; }                         // (ends at next_cell)
+            }
+            if (want_cnt == 0) {                                                      // no read there, or every element below -Q
+                *bases++ = '*'; *quals++ = '*'; mine = false;
+                if (OPT & MPT_MQ) *mqc++ = '*';
+                if (OPT & MPT_BP) *bpc++ = '*';
+            }
         }
     }
-    mpt_traverse<WRITE>(J, rg, J.rec[s], J.reads[s], ct, p, mine, sh, cnt, blen, covered, bases, quals);
+    mpt_traverse<WRITE, OPT>(J, rg, J.rec[s], J.reads[s], ct, p, mine, sh, cnt, blen, bplen, covered, bases, quals, mqc, bpc);
     if (WRITE) {
-        if (bases_end && (bases != bases_end || quals != next_cell)) *J.flag = 1u;      // (every writer stores the same value)
+        if (bases_end) {                                                              // (every writer stores the same value)
+            bool bad = bases != bases_end;
+            if (!(OPT & (MPT_MQ | MPT_BP))) bad |= quals != next_cell;
+            else {
+                bad |= quals != quals_end;
+                if (OPT & MPT_MQ) bad |= mqc != ((OPT & MPT_BP) ? mq_end : next_cell);
+                if (OPT & MPT_BP) bad |= bpc != next_cell;
+            }
+            if (bad) *J.flag = 1u;
+        }
     } else {
         J.cnt[cell] = cnt; J.blen[cell] = blen;
+        if (OPT & MPT_BP) J.bplen[cell] = bplen ? bplen - 1u : 0u;                     // (no comma in front of the first number)
         if (covered) J.active[line] = 1u;                                              // (likewise)
     }
 }
 
-// one lane per line of the group
+// bytes of a zero-depth cell: "\t0\t*\t*" and "\t*" per extra column
+template <uint32_t OPT> __device__ __forceinline__ constexpr uint32_t empty_cell_len() { return 6u + ((OPT & MPT_MQ) ? 2u : 0u) + ((OPT & MPT_BP) ? 2u : 0u); }
+
+// one lane per line of the group.  MPT_ALL: a line is active under a read or not -- every position of [vbeg, vend) up to the contig's
+// length in a tile that holds reads, every position of [vbeg, vend) (the host has cut it) in an empty tile, whose cells have no tables.
+template <uint32_t OPT>
 __global__ __launch_bounds__(256) void mpt_cell_offsets(const MptJob J, uint32_t n_lines) {
     const uint32_t line = blockIdx.x * blockDim.x + threadIdx.x;
     if (line >= n_lines) return;
     uint32_t len = 0;
-    if (J.active[line]) {
+    bool active = J.active[line] != 0u;
+    if (OPT & MPT_ALL) {
+        const MptTile t = J.tiles[line / MPT_T];
+        const int32_t p = t.t0 + (int32_t)(line % MPT_T);
+        active = t.contig < 0 ? p >= t.vbeg && p < t.vend : active || (p >= t.vbeg && p < t.vend && p < J.contigs[t.contig].len);
+    }
+    if (active) {
         const MptTile tl = J.tiles[line / MPT_T];
+        const bool empty = (OPT & MPT_ALL) && tl.contig < 0;
         uint32_t acc = 0; unsigned long long kept = 0;
-        for (uint32_t s = 0; s < J.S; ++s) {
+        if (empty) acc = J.S * empty_cell_len<OPT>();
+        else for (uint32_t s = 0; s < J.S; ++s) {
             const size_t cell = (size_t)s * J.lines_cap + line;
             const uint32_t cnt = J.cnt[cell], blen = J.blen[cell];
             J.rel[cell] = acc;
             acc += 1u + dec_digits(cnt) + 1u + max(blen, 1u) + 1u + max(cnt, 1u);
+            if (OPT & MPT_MQ) acc += 1u + max(cnt, 1u);
+            if (OPT & MPT_BP) acc += 1u + max(J.bplen[cell], 1u);
             kept += cnt;
         }
-        len = header_len(J.contigs[tl.contig], tl.t0 + (int32_t)(line % MPT_T)) + acc + 1u;
+        len = header_len(J.contigs[empty ? ~tl.contig : tl.contig], tl.t0 + (int32_t)(line % MPT_T)) + acc + 1u;
         atomicAdd(&J.totals[0], 1ull); atomicAdd(&J.totals[1], kept);               // statistics only
     }
     J.line_len[line] = len;
@@ -246,25 +294,72 @@ __global__ __launch_bounds__(MPT_SCAN_NT) void mpt_scan_lines(const MptJob J, ui
     }
 }
 
+// MPT_ALL: one lane per line of tiles [tile_lo, tile_hi); a lane whose tile is empty writes its whole line -- the head and S zero-depth
+// cells -- and checks that it ended where the next line starts.
+template <uint32_t OPT>
+__global__ __launch_bounds__(256) void mpt_empty_lines(const MptJob J, uint32_t tile_lo, uint32_t tile_hi, unsigned long long base_off, char *text) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (tile_hi - tile_lo) * MPT_T) return;
+    const uint32_t line = tile_lo * MPT_T + i;
+    const MptTile tl = J.tiles[line / MPT_T];
+    if (tl.contig >= 0) return;
+    const unsigned long long off = J.line_off[line], off_next = J.line_off[line + 1];
+    if (off_next == off) return;
+    const MptContig ct = J.contigs[~tl.contig];
+    const int32_t p = tl.t0 + (int32_t)(line % MPT_T);
+    char *o = text + (off - base_off);
+    const char *nm = J.names + ct.name_off;
+    for (uint32_t k = 0; k < ct.name_len; ++k) *o++ = nm[k];
+    *o++ = '\t'; o = put_dec(o, (uint32_t)p + 1u); *o++ = '\t';
+    *o++ = ct.ref_len >= 0 && p < ct.ref_len ? J.ref[ct.ref_off + p] : 'N';
+    for (uint32_t s = 0; s < J.S; ++s) {
+        *o++ = '\t'; *o++ = '0'; *o++ = '\t'; *o++ = '*'; *o++ = '\t'; *o++ = '*';
+        if (OPT & MPT_MQ) { *o++ = '\t'; *o++ = '*'; }
+        if (OPT & MPT_BP) { *o++ = '\t'; *o++ = '*'; }
+    }
+    *o++ = '\n';
+    if (o != text + (off_next - base_off)) *J.flag = 1u;
+}
+
 __global__ void msnv_warm_mptext() {}
+
+// f(std::integral_constant<uint32_t, opt>): the instantiation of a kernel for the call's options
+template <typename F> void with_opt(uint32_t opt, F &&f) {
+    switch (opt & 7u) {
+        case 0: f(std::integral_constant<uint32_t, 0>{}); break;
+        case 1: f(std::integral_constant<uint32_t, 1>{}); break;
+        case 2: f(std::integral_constant<uint32_t, 2>{}); break;
+        case 3: f(std::integral_constant<uint32_t, 3>{}); break;
+        case 4: f(std::integral_constant<uint32_t, 4>{}); break;
+        case 5: f(std::integral_constant<uint32_t, 5>{}); break;
+        case 6: f(std::integral_constant<uint32_t, 6>{}); break;
+        default: f(std::integral_constant<uint32_t, 7>{}); break;
+    }
+}
 
 }  // namespace
 
-int mpt_measure(const MptJob &j, uint32_t n_tiles, void *stream_) {
+int mpt_measure(const MptJob &j, uint32_t n_tiles, uint32_t n_work, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     const uint32_t n_lines = n_tiles * MPT_T;
-    if (n_tiles == 0 || n_lines > j.lines_cap) return fail(MSNV_EINVAL, "mpt_measure: %u tiles do not fit the group's tables", n_tiles);
+    if (n_tiles == 0 || n_lines > j.lines_cap || n_work > n_tiles) return fail(MSNV_EINVAL, "mpt_measure: %u tiles do not fit the group's tables", n_tiles);
     HIP_TRY(hipMemsetAsync(j.active, 0, (size_t)n_lines * sizeof(uint32_t), stream));
-    hipLaunchKernelGGL(mpt_cells<false>, dim3(n_tiles * j.S), dim3(MPT_T), 0, stream, j, 0u, 0ull, (char *)nullptr);
-    hipLaunchKernelGGL(mpt_cell_offsets, dim3((n_lines + 255) / 256), dim3(256), 0, stream, j, n_lines);
+    with_opt(j.opt & ~MPT_MQ, [&](auto o) {                      // (the MAPQ column is as long as the qualities: nothing to measure)
+        if (n_work) hipLaunchKernelGGL((mpt_cells<false, decltype(o)::value>), dim3(n_work * j.S), dim3(MPT_T), 0, stream, j, 0u, 0ull, (char *)nullptr);
+    });
+    with_opt(j.opt, [&](auto o) { hipLaunchKernelGGL((mpt_cell_offsets<decltype(o)::value>), dim3((n_lines + 255) / 256), dim3(256), 0, stream, j, n_lines); });
     hipLaunchKernelGGL(mpt_scan_lines, dim3(1), dim3(MPT_SCAN_NT), 0, stream, j, n_lines);
     HIP_TRY(hipGetLastError());
     return MSNV_OK;
 }
 
-int mpt_write(const MptJob &j, uint32_t tile_lo, uint32_t tile_hi, unsigned long long base_off, char *text, void *stream) {
+int mpt_write(const MptJob &j, uint32_t tile_lo, uint32_t tile_hi, uint32_t work_lo, uint32_t work_hi, unsigned long long base_off, char *text, void *stream) {
     if (tile_hi <= tile_lo) return MSNV_OK;
-    hipLaunchKernelGGL(mpt_cells<true>, dim3((tile_hi - tile_lo) * j.S), dim3(MPT_T), 0, (hipStream_t)stream, j, tile_lo, base_off, text);
+    with_opt(j.opt, [&](auto o) {
+        constexpr uint32_t O = decltype(o)::value;
+        if (work_hi > work_lo) hipLaunchKernelGGL((mpt_cells<true, O>), dim3((work_hi - work_lo) * j.S), dim3(MPT_T), 0, (hipStream_t)stream, j, work_lo, base_off, text);
+        if constexpr ((O & MPT_ALL) != 0u) hipLaunchKernelGGL((mpt_empty_lines<O>), dim3(((tile_hi - tile_lo) * MPT_T + 255) / 256), dim3(256), 0, (hipStream_t)stream, j, tile_lo, tile_hi, base_off, text);
+    });
     HIP_TRY(hipGetLastError());
     return MSNV_OK;
 }

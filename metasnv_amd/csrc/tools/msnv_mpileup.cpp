@@ -1,6 +1,7 @@
 // msnv_mpileup -- process-level replacement of the left half of the pipe metaSNV.py:160-176 runs:
 //   samtools mpileup -f REF [-l SPLIT] -B -b LIST [-q INT] [-Q INT] [-A] [-x] [-d INT] [--ff INT]  > pileup text
-// Same options, the text on stdout (or -o FILE) like samtools; the lines are formatted on the GPU (msnv_mpileup_text).
+// and three options the driver does not pass: -a / -aa (a line for every position), -s (a MAPQ column), -O / --output-BP (a read-offset column).
+// Same options, the text on stdout (or -o FILE) like samtools; the lines are formatted on the GPU (msnv_mpileup_text_ex).
 //   msnv_mpileup -f REF -B -b LIST | snpCall -f REF -i INDIV -c C -t T > CALLED        runs the reference's caller on this pileup
 // -B is REQUIRED: without it samtools recomputes the base qualities (BAQ), which is not built.  Every other samtools option is
 // refused with exit status 1, never ignored.  Exit status: 0 ok, > 0 failure (the driver treats v > 0 as fatal, metaSNV.py:212-221).
@@ -16,7 +17,10 @@
 
 static void usage() {
     fprintf(stderr, "Usage: msnv_mpileup -f REF.fa [-l BED] -B -b BAM_LIST [-q MIN_MAPQ=0] [-Q MIN_BASEQ=13] [-A] [-x] [-d MAX_DEPTH=8000]\n"
-                    "                    [--ff FLAGS=0x704] [-o FILE] [-@ HOST_THREADS] > mpileup text\n"
+                    "                    [--ff FLAGS=0x704] [-a | -aa] [-s] [-O | --output-BP] [-o FILE] [-@ HOST_THREADS] > mpileup text\n"
+                    "       -a: a line for every position of every contig that has reads, -aa (or -a -a): of every contig of the header\n"
+                    "       -s: a mapping-quality column behind the qualities (spelled -s only; the long form --output-MQ is not taken)\n"
+                    "       -O, --output-BP: a column of 1-based offsets in the read behind that\n"
                     "       -B is required (no BAQ: base qualities are never recomputed); other samtools options are not supported\n");
 }
 
@@ -32,10 +36,13 @@ int main(int argc, char **argv) {
     std::string ref, list, bed, out;
     msnv_params p;
     msnv_params_default(&p);
+    msnv_mpileup_text_opts o;
+    msnv_mpileup_text_opts_default(&o);
     int threads = 0, arg, no_baq = 0;
-    static const option longopts[] = {{"ff", required_argument, nullptr, 1}, {"excl-flags", required_argument, nullptr, 1}, {nullptr, 0, nullptr, 0}};
+    static const option longopts[] = {{"ff", required_argument, nullptr, 1}, {"excl-flags", required_argument, nullptr, 1}, {"output-BP", no_argument, nullptr, 'O'},
+                                      {nullptr, 0, nullptr, 0}};
     opterr = 0;
-    while ((arg = getopt_long(argc, argv, "+f:l:b:q:Q:d:o:@:BAx", longopts, nullptr)) >= 0) {
+    while ((arg = getopt_long(argc, argv, "+f:l:b:q:Q:d:o:@:BAxasO", longopts, nullptr)) >= 0) {
         bool ok = true;
         switch (arg) {
         case 'f': ref = optarg; break;
@@ -45,6 +52,9 @@ int main(int argc, char **argv) {
         case 'B': no_baq = 1; break;
         case 'A': p.count_orphans = 1; break;
         case 'x': p.ignore_overlaps = 1; break;
+        case 'a': if (o.all_positions < 2) ++o.all_positions; break;
+        case 's': o.output_mq = 1; break;
+        case 'O': o.output_bp = 1; break;
         case 'q': ok = parse_int(optarg, 10, &p.min_mapq); break;
         case 'Q': ok = parse_int(optarg, 10, &p.min_baseq); break;
         case 'd': ok = parse_int(optarg, 10, &p.max_depth); break;
@@ -78,7 +88,7 @@ int main(int argc, char **argv) {
     a.out_path = out.empty() ? nullptr : out.c_str();
     a.host_threads = threads;
     a.params = p;
-    const int rc = msnv_mpileup_text(ctx, &a, nullptr);
+    const int rc = msnv_mpileup_text_ex(ctx, &a, &o, nullptr);
     if (rc) fprintf(stderr, "msnv_mpileup: %s\n", msnv_last_error());
     msnv_ctx_destroy(ctx);
     return rc;
