@@ -225,6 +225,37 @@ int msnv_genotyping_subset(const char *const *hap_paths, int32_t n_hap, const ch
                            const char *out_dir, uint64_t *n_positions, uint64_t *n_lines_written);
 int msnv_snv_allele_freq(msnv_ctx *ctx, const char *pos_path, int32_t min_depth, uint64_t *n_rows, double *ms_kernel);
 
+/* subpopr's correlateSubpopProfileWithGeneProfiles (src/subpopr/R/correlateSubpopProfileWithGeneProfiles.R): every cluster's
+ * abundance vector against every gene family's, Spearman and Pearson, on the device in fp64.
+ *
+ * msnv_gene_corr -- the array form (doCorr, :141-153).  clust holds n_clusters rows of n_samples values (the caller appends the
+ * species row, the column sums), genes n_genes rows; both row-major, already cut to the samples and genes in use.  For
+ * every (cluster c, gene g), at [c * n_genes + g]: rho = Pearson coefficient of the average ranks, r = Pearson coefficient of
+ * log10(v + pseudocount), valid = 0 where either raw vector has max == min (rho and r are then NaN).  *pseudocount = the smallest
+ * cell above 0 of genes / 1000.  3 <= n_samples <= 8192 (one workgroup ranks a row in LDS), else MSNV_EDOMAIN; negative or
+ * non-finite cells, or no cell above 0, are MSNV_EDOMAIN too.  pseudocount / ms_kernel may be NULL.
+ *
+ * msnv_corr_stats -- cor.test's derived columns of one table and p.adjust(p, "BH") over its n rows: per row the statistic
+ * (MSNV_CORR_PEARSON: sqrt(n_obs - 2) e / sqrt(1 - e^2); MSNV_CORR_SPEARMAN: (n_obs^3 - n_obs)(1 - e) / 6), the two-sided p of
+ * the t approximation (exact = FALSE), for Pearson the Fisher interval (NaN at n_obs = 3; conf_low / conf_high may be NULL)
+ * and q.  An estimate of exactly +-1 gives p = 0 and, for Pearson, an infinite statistic.  n_obs < 3 is MSNV_EDOMAIN.
+ *
+ * msnv_gene_corr_files -- the whole stage: reads <species>_allClust_relativeAbund.tab (write.table's layout) and the gene-family
+ * table (TSV, '#' lines skipped, header id + samples), keeps the clusters seen in >= 3 samples, the samples both tables hold
+ * (retrying with gene column + sample_suffix when none match and a suffix is given; none at all: MSNV_EDOMAIN) and the genes
+ * present in them, and writes <out_prefix>-spearman.tsv, -pearson.tsv, -clusterSpecificGenes.tsv and -speciesSpecificGenes.tsv
+ * (selectSubspeciesSpecificGenes with its defaults, :238-303).  counts = clusters tested, genes kept, samples used, specific
+ * genes; all 0 and nothing written when no cluster is seen in 3 samples.  A cell that is NA, empty or not a number is
+ * MSNV_EFORMAT (R drops such pairs silently). */
+#define MSNV_CORR_PEARSON  0
+#define MSNV_CORR_SPEARMAN 1
+int msnv_gene_corr(msnv_ctx *ctx, int32_t n_clusters, int64_t n_genes, int32_t n_samples, const double *clust, const double *genes,
+                   double *rho, double *r, uint8_t *valid, double *pseudocount, double *ms_kernel);
+int msnv_corr_stats(msnv_ctx *ctx, int32_t method, uint64_t n, const double *estimate, const int32_t *n_obs, double *statistic,
+                    double *p_value, double *conf_low, double *conf_high, double *q_value);
+int msnv_gene_corr_files(msnv_ctx *ctx, const char *clust_abund_path, const char *gene_abund_path, const char *sample_suffix,
+                         const char *out_prefix, uint64_t counts[4]);
+
 /* ------------------------------------------------------------------------------------
  * Staged form of the same path.
  * ------------------------------------------------------------------------------------ */

@@ -21,6 +21,7 @@ class MsnvError(RuntimeError):
 
 OK, EINVAL, EIO, EFORMAT, ENODEV, EHIP, ENOMEM, EDOMAIN, ECAPACITY = range(9)
 DIV, DIV_NS = 0, 1                                             # msnv_div_file modes (include/msnv.h)
+CORR_PEARSON, CORR_SPEARMAN = 0, 1                             # msnv_corr_stats methods
 
 
 class Params(C.Structure):
@@ -217,6 +218,11 @@ SYMBOLS = [
                                 C.c_uint64, C.c_char_p, C.c_char_p, P(C.c_int32), P(C.c_uint64), P(C.c_double)]),
     ("msnv_genotyping_subset", C.c_int, [P(C.c_char_p), C.c_int32, P(C.c_char_p), C.c_int32, C.c_char_p, P(C.c_uint64), P(C.c_uint64)]),
     ("msnv_snv_allele_freq", C.c_int, [_vp, C.c_char_p, C.c_int32, P(C.c_uint64), P(C.c_double)]),
+    ("msnv_gene_corr", C.c_int, [_vp, C.c_int32, C.c_int64, C.c_int32, P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_uint8),
+                                 P(C.c_double), P(C.c_double)]),
+    ("msnv_corr_stats", C.c_int, [_vp, C.c_int32, C.c_uint64, P(C.c_double), P(C.c_int32), P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double),
+                                  P(C.c_double)]),
+    ("msnv_gene_corr_files", C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, P(C.c_uint64)]),
     ("msnv_format_float", C.c_int, [C.c_double, C.c_char_p, C.c_int32]),
     ("msnv_filter_files", C.c_int, [_vp, P(C.c_char_p), C.c_int32, C.c_int32, P(FilterSpecies), C.c_int32, C.c_double, C.c_double,
                                    C.c_char_p, P(C.c_uint64), P(C.c_double)]),

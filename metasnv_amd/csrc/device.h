@@ -242,7 +242,7 @@ int  dev_inflate_resident(msnv_ctx *ctx, const uint8_t *host_in, uint64_t comp_b
                           uint32_t check_every, std::vector<uint32_t> &status, double *ms_kernel);
 int  dev_inflate_patch(msnv_ctx *ctx, uint64_t out_off, const uint8_t *data, uint32_t n);
 
-// ---- the stages that work on files (textcall.hip; dist.cpp + dist_k.hip; div.cpp + div_k.hip; subpopr.cpp + subpopr_k.hip)
+// ---- the stages that work on files (textcall.hip; dist.cpp + dist_k.hip; div.cpp + div_k.hip; subpopr.cpp + subpopr_k.hip; genecorr.cpp + genecorr_k.hip)
 int  text_call(msnv_ctx *ctx, const char *text, uint64_t n_text, const msnv_params &p, const char *ref_fasta, const char *ann_path,
                const char *called_path, const char *indiv_path, uint64_t stats[8]);
 int  dist_file(msnv_ctx *ctx, const char *freq_path, const char *mann_path, const char *allele_path, double threshold,
@@ -255,5 +255,10 @@ int dev_div(const double *xs, const uint64_t *bits, long n_single, long n_words,
             int n_samples, void *stream, double *out, double *ms_kernel);
 int dev_allele_freq(const std::vector<uint32_t> &cov, const std::vector<uint32_t> &cnt, const std::vector<uint32_t> &row_line,
                     uint32_t n_samples, long long min_depth, void *stream, std::vector<double> &freq, double *ms_kernel);
+// genecorr.cpp + genecorr_k.hip: subpopr's correlateSubpopProfileWithGeneProfiles.  One workgroup ranks one row of samples in LDS, which bounds the row
+constexpr uint32_t GENECORR_MAX_SAMPLES = 8192;
+int dev_gene_corr(uint32_t n_clust_rows, uint64_t n_genes, uint32_t n_samples, const double *clust, const double *genes, void *stream, double *rho, double *r,
+                  uint8_t *valid, double *pseudocount, double *ms_kernel);
+int dev_corr_stats(int method, uint64_t n, const double *est, const int32_t *n_obs, void *stream, double *stat, double *p, double *lo, double *hi, double *q);
 
 }  // namespace msnv
