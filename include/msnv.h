@@ -256,6 +256,70 @@ int msnv_corr_stats(msnv_ctx *ctx, int32_t method, uint64_t n, const double *est
 int msnv_gene_corr_files(msnv_ctx *ctx, const char *clust_abund_path, const char *gene_abund_path, const char *sample_suffix,
                          const char *out_prefix, uint64_t counts[4]);
 
+/* subpopr's computeClusters -> getClusteringResult (src/subpopr/R/clustering.R:20-133, :289-427): how many subspecies a species has and
+ * which samples belong to which.  Every PAM run is one workgroup of one launch; the n x n distance matrix (row-major fp64, 2 <= n <=
+ * 4096) stays on the device.  It must be symmetric with a zero diagonal (pam sees a dist object), every cell finite and >= 0: anything
+ * else is MSNV_EDOMAIN.
+ *
+ * msnv_pam_tasks -- cluster::pam(diss = TRUE, pamonce = 0) of many index subsets.  Task t is task_m[t] sample indices (its list, in idx
+ * behind the lists of the tasks before it) and task_k[t], 1 <= k < m.  Out, in the same packing: medoids (task_k[t] positions in the
+ * task's list, 0-based, ascending; packed behind each other), cluster (per list entry, 1..k, numbered by ascending medoid position) and
+ * n_swaps[t].  The rules, restated from pam.c (unpinned, no R was run):
+ *   BUILD   dysma[j] = 1.1 max(d) + 1 (max over the task's sub-matrix); k times: beter[i] = sum over j ascending of (dysma[j] - d(i,j)
+ *           where that is > 0) for every non-medoid i, the LAST i with the largest beter becomes a medoid, dysma[j] = min(dysma[j],
+ *           d(i,j)); sky = sum of dysma[j], j ascending
+ *   SWAP    (k > 1) dysma[j] / dysmb[j] = nearest / second nearest medoid distance, medoids ascending, strict <; for every non-medoid h
+ *           ascending and medoid i ascending, dz = sum over j ascending of: d(i,j) == dysma[j] ? min(dysmb[j], d(h,j)) - dysma[j] :
+ *           d(h,j) < dysma[j] ? d(h,j) - dysma[j] : nothing; the FIRST smallest dz < 1 is dzsky; swapped while dzsky < -16 DBL_EPSILON
+ *           |sky|, sky += dzsky
+ *   assign  nearest medoid, medoids ascending, strict <
+ * All sums are sequential fp64 sums without contraction, so the result is a function of the task alone, not of its place in the batch.
+ *
+ * msnv_pred_strength -- predStrengthCustom (:152-216) for given permutations: perms holds, for k = 2..k_max and l = 0..M-1 in that
+ * order, one permutation of 0..n-1 (n entries each).  Its first floor(n / 2) entries are half 1, the rest half 2; both are clustered
+ * by PAM, every member is classified by the OTHER half's medoids (nearest, first on ties), and for half i, cluster kk of nik > 1 members,
+ * with a = its members among the half's first nf[i] - 1 entries (the reference leaves the last entry out of the numerator only):
+ * ps = (#ordered pairs of a with equal classification, self-pairs included, - |a|) / (nik (nik - 1)); clusters of one member score 0.
+ * prederr[(k - 2) * M + l] = (min ps[1,] + min ps[2,]) / 2; mean_pred[0] = 1 and mean_pred[k - 1] = R's mean() of the M values of k
+ * (long double, two passes), k_max entries; *optimalk = the largest k with mean_pred[k - 1] > cutoff.  2 <= k_max < floor(n / 2),
+ * M >= 1, 0 <= cutoff < 1.
+ *
+ * msnv_cluster_file -- the stage on files, computeClusters with its defaults: reads dist_path (<species>.filtered.mann.dist as
+ * metaSNV_DistDiv.py --dist writes it; an NA or empty cell is MSNV_EFORMAT) and, when freq_path is not NULL, the *.filtered.freq
+ * table; removes outliers (removeOutliersFromDistMatrixMinDissim, 3 sd, at most 5), writes <species>_freq_composition.tab and keeps the
+ * samples whose 10/90 proportion is >= 0.8, picks the number of clusters by prediction strength (M = 50, up to 15 clusters of >= 3),
+ * runs PAM, rates the stability of the number (>= 10 samples; stability_iters subsamples at each proportion, 10 / 5 there), drops
+ * clusters under 3 members, and writes <prefix>_PS_values.tab, _distMatrixUsedForClustMedoidDefns.txt, _clustering.tab and
+ * _clusNumStability.tab (prefix = <species>_mann) into out_dir, out_dir/noClustering/ (one cluster) or
+ * out_dir/clustMedoidDefnFailed/.  Doubles are printed with %.15g.  result: [0] MSNV_CLUSTER_* [1] clusters [2] samples clustered
+ * [3] outliers removed [4] stability score (1 Low, 2 Medium, 3 High; 0 not rated) [5] optimalk [6] PAM tasks run [7] 0.
+ *
+ * Randomness: R's generator is not reproduced.  With mix(x) = splitmix64's output function of state x + 0x9e3779b97f4a7c15
+ * (z = x + 0x9e3779b97f4a7c15; z = (z ^ z >> 30) * 0xbf58476d1ce4e5b9; z = (z ^ z >> 27) * 0x94d049bb133111eb; z ^ z >> 31), all mod 2^64:
+ *   rand(seed, ordinal, i) = mix(mix(mix(seed) + ordinal) + i)
+ *   permutation(seed, ordinal, n): p = 0..n-1; for i = n-1 down to 1: swap p[i], p[rand(seed, ordinal, i) mod (i + 1)]
+ * The main run's permutation of (k, l) has ordinal (k - 2) * 50 + l.  Stability run r = 1 + 1024 * (index of the proportion) + iteration
+ * draws its subsample as the first floor(n * prop) entries of permutation(seed, r << 32 | 0xffffffff, n) and the permutation of its
+ * (k, l) with ordinal r << 32 | (k - 2) * 50 + l.  A draw depends on the seed and its ordinal alone, never on how tasks were batched. */
+#define MSNV_CLUSTER_OK            0   /* two or more clusters, files in out_dir                                              */
+#define MSNV_CLUSTER_NONE          1   /* one cluster: files in out_dir/noClustering/                                         */
+#define MSNV_CLUSTER_MEDOID_FAILED 2   /* Gmax <= 1 ("Cluster medoid definition failed"): one cluster, matrix also in clustMedoidDefnFailed/ */
+#define MSNV_CLUSTER_TOO_FEW       3   /* fewer than 6 samples with extreme SNV frequencies: only the composition file, in clustMedoidDefnFailed/ */
+#define MSNV_CLUSTER_ALL_EQUAL     4   /* all remaining distances equal: likewise                                             */
+typedef struct {
+    uint64_t seed;
+    double   ps_cut;            /* psCut, 0.8                                                   */
+    int32_t  stability_iters;   /* clusNumStabilityIter, 10 (tests lower it); 1..1024           */
+    int32_t  reserved;          /* 0                                                            */
+} msnv_cluster_opts;
+void msnv_cluster_opts_default(msnv_cluster_opts *o);
+int msnv_pam_tasks(msnv_ctx *ctx, int32_t n, const double *dist, int64_t n_tasks, const int32_t *task_m, const int32_t *task_k,
+                   const int32_t *idx, int32_t *medoids, int32_t *cluster, int32_t *n_swaps, double *ms_kernel);
+int msnv_pred_strength(msnv_ctx *ctx, int32_t n, const double *dist, int32_t k_max, int32_t M, const int32_t *perms, double cutoff,
+                       double *prederr, double *mean_pred, int32_t *optimalk, double *ms_kernel);
+int msnv_cluster_file(msnv_ctx *ctx, const char *dist_path, const char *freq_path, const char *species, const char *out_dir,
+                      const msnv_cluster_opts *opts, int64_t result[8], double *ms_kernel);
+
 /* ------------------------------------------------------------------------------------
  * Staged form of the same path.
  * ------------------------------------------------------------------------------------ */

@@ -22,6 +22,7 @@ class MsnvError(RuntimeError):
 OK, EINVAL, EIO, EFORMAT, ENODEV, EHIP, ENOMEM, EDOMAIN, ECAPACITY = range(9)
 DIV, DIV_NS = 0, 1                                             # msnv_div_file modes (include/msnv.h)
 CORR_PEARSON, CORR_SPEARMAN = 0, 1                             # msnv_corr_stats methods
+CLUSTER_OK, CLUSTER_NONE, CLUSTER_MEDOID_FAILED, CLUSTER_TOO_FEW, CLUSTER_ALL_EQUAL = range(5)   # msnv_cluster_file result[0]
 
 
 class Params(C.Structure):
@@ -70,6 +71,10 @@ class MpileupTextArgs(C.Structure):
 
 class MpileupTextOpts(C.Structure):
     _fields_ = [("all_positions", C.c_int32), ("output_mq", C.c_int32), ("output_bp", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ClusterOpts(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("ps_cut", C.c_double), ("stability_iters", C.c_int32), ("reserved", C.c_int32)]
 
 
 class RefDesc(C.Structure):
@@ -223,6 +228,12 @@ SYMBOLS = [
     ("msnv_corr_stats", C.c_int, [_vp, C.c_int32, C.c_uint64, P(C.c_double), P(C.c_int32), P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double),
                                   P(C.c_double)]),
     ("msnv_gene_corr_files", C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, P(C.c_uint64)]),
+    ("msnv_cluster_opts_default", None, [P(ClusterOpts)]),
+    ("msnv_pam_tasks", C.c_int, [_vp, C.c_int32, P(C.c_double), C.c_int64, P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_int32),
+                                 P(C.c_double)]),
+    ("msnv_pred_strength", C.c_int, [_vp, C.c_int32, P(C.c_double), C.c_int32, C.c_int32, P(C.c_int32), C.c_double, P(C.c_double), P(C.c_double), P(C.c_int32),
+                                     P(C.c_double)]),
+    ("msnv_cluster_file", C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, P(ClusterOpts), P(C.c_int64), P(C.c_double)]),
     ("msnv_format_float", C.c_int, [C.c_double, C.c_char_p, C.c_int32]),
     ("msnv_filter_files", C.c_int, [_vp, P(C.c_char_p), C.c_int32, C.c_int32, P(FilterSpecies), C.c_int32, C.c_double, C.c_double,
                                    C.c_char_p, P(C.c_uint64), P(C.c_double)]),

@@ -242,7 +242,7 @@ int  dev_inflate_resident(msnv_ctx *ctx, const uint8_t *host_in, uint64_t comp_b
                           uint32_t check_every, std::vector<uint32_t> &status, double *ms_kernel);
 int  dev_inflate_patch(msnv_ctx *ctx, uint64_t out_off, const uint8_t *data, uint32_t n);
 
-// ---- the stages that work on files (textcall.hip; dist.cpp + dist_k.hip; div.cpp + div_k.hip; subpopr.cpp + subpopr_k.hip; genecorr.cpp + genecorr_k.hip)
+// ---- the stages that work on files (textcall.hip; dist.cpp + dist_k.hip; div.cpp + div_k.hip; subpopr.cpp + subpopr_k.hip; genecorr.cpp + genecorr_k.hip; cluster.cpp + cluster_k.hip)
 int  text_call(msnv_ctx *ctx, const char *text, uint64_t n_text, const msnv_params &p, const char *ref_fasta, const char *ann_path,
                const char *called_path, const char *indiv_path, uint64_t stats[8]);
 int  dist_file(msnv_ctx *ctx, const char *freq_path, const char *mann_path, const char *allele_path, double threshold,
@@ -260,5 +260,20 @@ constexpr uint32_t GENECORR_MAX_SAMPLES = 8192;
 int dev_gene_corr(uint32_t n_clust_rows, uint64_t n_genes, uint32_t n_samples, const double *clust, const double *genes, void *stream, double *rho, double *r,
                   uint8_t *valid, double *pseudocount, double *ms_kernel);
 int dev_corr_stats(int method, uint64_t n, const double *est, const int32_t *n_obs, void *stream, double *stat, double *p, double *lo, double *hi, double *q);
+
+// cluster.cpp + cluster_k.hip: subpopr's computeClusters.  The distance matrix of one species, resident on the device for every PAM task run on it
+constexpr uint32_t CLUSTER_MAX_SAMPLES = 4096, PAM_MAX_SWAPS = 65536;   // a task that swaps more often than this is refused, not waited for
+struct ClusterDev {
+    double *dist = nullptr; uint32_t n = 0;
+    ClusterDev() = default;
+    ClusterDev(const ClusterDev &) = delete;
+    ~ClusterDev();
+};
+int dev_cluster_upload(ClusterDev &c, const double *dist, uint32_t n, void *stream);
+// tasks and splits as include/msnv.h packs them; a split is a list of len global indices whose first floor(len / 2) entries are half 1
+int dev_pam_tasks(const ClusterDev &c, uint64_t n_tasks, const uint32_t *m, const uint32_t *k, const int32_t *idx, void *stream, int32_t *med, int32_t *clus,
+                  int32_t *swaps, double *ms_kernel);
+int dev_pred_strength(const ClusterDev &c, uint64_t n_splits, const uint32_t *len, const uint32_t *k, const int32_t *idx, void *stream, double *prederr, double *ms_kernel);
+int dev_freq_bands(const double *rows, uint64_t n_pos, uint32_t n_samples, void *stream, uint64_t *counts, double *ms_kernel);   // counts[sample][4]
 
 }  // namespace msnv

@@ -10,8 +10,14 @@
       <outDir>/<species>_allClust_relativeAbund.tab + the gene-family table  ->  <outDir>/<species>_corr<type>-{spearman,pearson,
       clusterSpecificGenes,speciesSpecificGenes}.tsv
 
-The first is a text filter (native, no device work); the frequencies of the second and the correlations of the third are
-computed on the GPU (msnv_snv_allele_freq, msnv_gene_corr, msnv_corr_stats) and there is no CPU fallback for them."""
+  clusterSubpops.py <dist_file> <outDir> [--freq FILE] [--seed N] [--ps-cut X]
+      (src/subpopr/R/clustering.R computeClusters with its defaults; species = the dist file's name up to its first '.')
+      <species>.filtered.mann.dist (+ <species>.filtered.freq)  ->  <outDir>[/noClustering|/clustMedoidDefnFailed]/<species>_mann_{PS_values.tab,
+      distMatrixUsedForClustMedoidDefns.txt,clustering.tab,clusNumStability.tab} and <species>_freq_composition.tab
+
+The first is a text filter (native, no device work); the frequencies of the second, the correlations of the third and every PAM run
+of the fourth are computed on the GPU (msnv_snv_allele_freq, msnv_gene_corr, msnv_corr_stats, msnv_pam_tasks, msnv_pred_strength)
+and there is no CPU fallback for them."""
 import ctypes as C
 import glob
 import os
@@ -167,3 +173,111 @@ def correlate_gene_profiles_main(argv=None):                   # correlateSubpop
     if n == 0:
         print("No cluster-specific genes found for species " + species)         # :214
     return n
+
+
+def _iptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def pam_tasks(ctx, dist, tasks):
+    """cluster::pam(diss = TRUE) of many index subsets of dist [n x n] in one launch (msnv_pam_tasks).  tasks: (indices, k) pairs.
+    Returns one dict per task: medoids (0-based positions in the task's list, ascending), cluster (1..k per list entry), n_swaps; and the kernel's ms."""
+    import numpy as np
+    from ._lib import lib, check
+    dist = np.ascontiguousarray(dist, dtype=np.float64)
+    if dist.ndim != 2 or dist.shape[0] != dist.shape[1]:
+        raise ValueError("pam_tasks: dist must be a square matrix")
+    lists = [np.asarray(ix, dtype=np.int32).ravel() for ix, _ in tasks]
+    m = np.array([len(x) for x in lists], dtype=np.int32)
+    k = np.array([kk for _, kk in tasks], dtype=np.int32)
+    idx = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, dtype=np.int32), dtype=np.int32)
+    med = np.zeros(max(int(k.clip(min=0).sum()), 1), dtype=np.int32)
+    clus = np.zeros(max(idx.size, 1), dtype=np.int32)
+    swaps = np.zeros(max(len(tasks), 1), dtype=np.int32)
+    ms = C.c_double()
+    check(lib.msnv_pam_tasks(ctx._h, dist.shape[0], _dptr(dist), len(tasks), _iptr(m), _iptr(k), _iptr(idx), _iptr(med), _iptr(clus), _iptr(swaps), C.byref(ms)))
+    out, o, mo = [], 0, 0
+    for t in range(len(tasks)):
+        out.append({"medoids": med[mo:mo + k[t]].copy(), "cluster": clus[o:o + m[t]].copy(), "n_swaps": int(swaps[t])})
+        o += m[t]
+        mo += k[t]
+    return out, ms.value
+
+
+def prediction_strength(ctx, dist, k_max, perms, cutoff=0.8):
+    """predStrengthCustom for given permutations (msnv_pred_strength): perms [k_max - 1][M][n], one permutation of 0..n-1 per (k, l).
+    Returns prederr [k_max - 1][M], mean_pred [k_max] (entry 0 is k = 1: 1.0), optimalk and the kernels' ms."""
+    import numpy as np
+    from ._lib import lib, check
+    dist = np.ascontiguousarray(dist, dtype=np.float64)
+    perms = np.ascontiguousarray(perms, dtype=np.int32)
+    n = dist.shape[0]
+    if dist.ndim != 2 or dist.shape[1] != n or perms.ndim != 3 or perms.shape[0] != k_max - 1 or perms.shape[2] != n:
+        raise ValueError("prediction_strength: dist [n x n], perms [k_max - 1][M][n]")
+    big_m = perms.shape[1]
+    prederr = np.empty((k_max - 1, big_m))
+    mean_pred = np.empty(k_max)
+    ok, ms = C.c_int32(), C.c_double()
+    check(lib.msnv_pred_strength(ctx._h, n, _dptr(dist), k_max, big_m, _iptr(perms), float(cutoff), _dptr(prederr), _dptr(mean_pred), C.byref(ok), C.byref(ms)))
+    return {"prederr": prederr, "mean_pred": mean_pred, "optimalk": ok.value, "ms_kernel": ms.value}
+
+
+CLUSTER_REASONS = {                                            # what computeClusters returns instead of a table (clustering.R:64-74, :314)
+    2: "Cluster medoid definition failed",
+    3: "After removing samples that do not have extreme SNV frequencies, insufficient samples (< 6) remain to pick the number of clusters and cluster medoids.",
+    4: "After removing samples that do not have extreme SNV frequencies, all values in the distance matrix are equivalent.",
+}
+
+
+def cluster_file(ctx, dist_path, out_dir, species=None, freq_path=None, seed=None, ps_cut=None, stability_iters=None):
+    """The stage on files (msnv_cluster_file).  Returns a dict: status (_lib.CLUSTER_*), n_clusters, n_samples, n_outliers, stability_score
+    (1 Low, 2 Medium, 3 High, 0 not rated), optimalk, n_pam_tasks, ms_kernel."""
+    from ._lib import lib, check, ClusterOpts
+    if species is None:
+        species = os.path.basename(dist_path).split(".")[0]
+    o = ClusterOpts()
+    lib.msnv_cluster_opts_default(C.byref(o))
+    if seed is not None:
+        o.seed = int(seed)
+    if ps_cut is not None:
+        o.ps_cut = float(ps_cut)
+    if stability_iters is not None:
+        o.stability_iters = int(stability_iters)
+    res = (C.c_int64 * 8)()
+    ms = C.c_double()
+    check(lib.msnv_cluster_file(ctx._h, dist_path.encode(), None if freq_path is None else freq_path.encode(), species.encode(), out_dir.encode(),
+                                C.byref(o), res, C.byref(ms)))
+    return {"status": res[0], "n_clusters": res[1], "n_samples": res[2], "n_outliers": res[3], "stability_score": res[4], "optimalk": res[5],
+            "n_pam_tasks": res[6], "ms_kernel": ms.value}
+
+
+def cluster_subpops_main(argv=None):                           # clustering.R:20-133 computeClusters
+    import argparse
+    ap = argparse.ArgumentParser(prog="clusterSubpops.py", description="Cluster a species' samples into subspecies (subpopr's computeClusters) on the GPU.")
+    ap.add_argument("dist_file", metavar="DIST_FILE", help="<species>.filtered.mann.dist of metaSNV_DistDiv.py --dist")
+    ap.add_argument("out_dir", metavar="OUTDIR")
+    ap.add_argument("--freq", metavar="FILE", help="<species>.filtered.freq: keep only samples with extreme SNV frequencies")
+    ap.add_argument("--seed", type=int, default=None, metavar="N")
+    ap.add_argument("--ps-cut", type=float, default=None, metavar="X", help="prediction-strength cutoff (0.8)")
+    a = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    for f in (a.dist_file, a.freq):
+        if f is not None and not os.path.exists(f):
+            sys.exit("ERROR: missing input file: " + f)
+    from . import core
+    try:
+        ctx = core.Context(0)
+    except core._lib.MsnvError as e:
+        sys.exit("\nERROR:  {}\n\nSOLUTION: run on a node with an AMD Instinct GPU (there is no CPU fallback)\n".format(e))
+    try:
+        res = cluster_file(ctx, a.dist_file, a.out_dir, freq_path=a.freq, seed=a.seed, ps_cut=a.ps_cut)
+    except core._lib.MsnvError as e:
+        sys.exit("ERROR: {}".format(e))
+    finally:
+        ctx.close()
+    species = os.path.basename(a.dist_file).split(".")[0]
+    if res["status"] in CLUSTER_REASONS:
+        print("Species " + species + ": " + CLUSTER_REASONS[res["status"]])
+    else:
+        print("Species " + species + ": " + str(res["n_clusters"]) + " cluster(s) from " + str(res["n_samples"]) + " samples; cluster number stability: "
+              + ("not rated", "Low", "Medium", "High")[res["stability_score"]])
+    return res
