@@ -320,6 +320,44 @@ int msnv_pred_strength(msnv_ctx *ctx, int32_t n, const double *dist, int32_t k_m
 int msnv_cluster_file(msnv_ctx *ctx, const char *dist_path, const char *freq_path, const char *species, const char *out_dir,
                       const msnv_cluster_opts *opts, int64_t result[8], double *ms_kernel);
 
+/* subpopr's writeGenotypeFreqs -> computeUniquePosPerCluster (src/subpopr/R/writeGenotypeFreqs.R:2-112, :195-277): which SNVs tell one
+ * subspecies from every other.  Restated from reading the R code; no R was run (unpinned).
+ *
+ * msnv_genotype_rows -- the rule on arrays.  rows: host memory, row-major [n_pos][n_samples], NaN for no coverage, scaled to 0..100.
+ * clust[s]: 0 for a column not in use, or 1..n_clusters.  2 <= n_clusters <= 32, 1 <= n_samples <= 65536, every cluster has a column,
+ * every non-NaN cell lies in [0, 100]: anything else is MSNV_EDOMAIN.  For row p and cluster i, with C_i the columns of cluster i, N_i the
+ * in-use columns outside it and na(X) the NaN cells of the row over X, bit i - 1 of select_mask[p] is set when
+ *   1. (double)na(C_i) / |C_i| < 0.2
+ *   2. (double)na(N_i) / |N_i| < 0.2
+ *   3. for every other cluster j: |mean(C_i) - mean(C_j)| > threshold, strictly; means over the non-NaN cells, a cluster without one
+ *      gives a difference of 0
+ * and bit i - 1 of flip_mask[p] is set where the select bit is and, among the non-NaN cells of C_i, more are < 50 than >= 50
+ * (majorAllel(...) == 0, computeSnvFreqStats.R:48-57: the median of a 0 / 1 vector is 0 exactly when the zeros outnumber the ones).
+ * The means of condition 3 are R's rowMeans: a long double sum in ascending column order over the count, rounded to double.  The kernel
+ * sums in fp64 in its own order, which is off by at most n * 100 * 2^-53 < 7.3e-10 per mean (cells in [0, 100], n <= 65536), under 2e-9
+ * for a difference of two; every row with a comparison within 1e-6 of the threshold is redone on the host by the long double rule and
+ * *n_rechecked counts those rows.  The masks are therefore the long double rule's on every row.  The table goes to the device in slabs,
+ * so it may be larger than device memory.  *ms_kernel: the kernel's time by events, summed over the slabs.
+ *
+ * msnv_genotype_file -- the stage on files.  freq_path: the *.filtered.freq table (a non-NaN cell above 1 is MSNV_EDOMAIN; cells are then
+ * multiplied by 100).  clustering_path: <species>_mann_clustering.tab as msnv_cluster_file writes it (a header "clust", then
+ * name<TAB>integer; anything else is MSNV_EFORMAT).  0 < uniq_threshold < 1 (uniqSubpopSnvFreqThreshold, 0.8).  The samples in use are the
+ * freq columns the clustering lists, in freq column order; the clusters are numbered by first appearance in that order.  Written into
+ * out_dir (created if missing): <species>_hap_out.txt, per cluster with positions <species>_<id>_hap_positions.tab (header posId<TAB>flip,
+ * rows counter<TAB>row label<TAB>TRUE|FALSE in table order), and on MSNV_GENOTYPE_OK <species>_hap_freq_mean.tab and _median.tab: per
+ * cluster and per sample in use, R's mean() and median() over that cluster's selected rows, flipped rows as 100 - x, NA skipped (%.15g).
+ * result: [0] MSNV_GENOTYPE_* [1] clusters [2] samples in use [3] table rows [4] genotyping positions over all clusters [5] rows
+ * rechecked on the host [6] nCorrAssign [7] good samples. */
+#define MSNV_GENOTYPE_OK              0   /* every cluster has positions and the samples' summed medians are coherent            */
+#define MSNV_GENOTYPE_SINGLE          1   /* one distinct cluster or none: "Single cluster", no kernel runs                      */
+#define MSNV_GENOTYPE_NO_POSITIONS    2   /* no cluster has a genotyping position                                                */
+#define MSNV_GENOTYPE_CLUSTER_MISSING 3   /* at least one cluster has none                                                       */
+#define MSNV_GENOTYPE_CUTOFF_BAD      4   /* more than 15 % of the samples sum to > 120 or < 80 over their cluster medians       */
+int msnv_genotype_rows(msnv_ctx *ctx, uint64_t n_pos, int32_t n_samples, const double *rows, const int32_t *clust, int32_t n_clusters,
+                       double threshold, uint32_t *select_mask, uint32_t *flip_mask, uint64_t *n_rechecked, double *ms_kernel);
+int msnv_genotype_file(msnv_ctx *ctx, const char *clustering_path, const char *freq_path, const char *species, const char *out_dir,
+                       double uniq_threshold, int64_t result[8], double *ms_kernel);
+
 /* ------------------------------------------------------------------------------------
  * Staged form of the same path.
  * ------------------------------------------------------------------------------------ */

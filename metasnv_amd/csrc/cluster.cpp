@@ -42,6 +42,8 @@ void permutation(uint64_t seed, uint64_t ordinal, uint32_t n, std::vector<int32_
     for (uint32_t i = n; i-- > 1;) std::swap(p[i], p[draw(seed, ordinal, i) % (i + 1)]);
 }
 
+}  // namespace
+
 // R's mean(): a long double sum over n, then the long double mean of the residuals added to it
 double r_mean(const double *x, size_t n) {
     long double s = 0;
@@ -52,6 +54,29 @@ double r_mean(const double *x, size_t n) {
     s += t / (long double)n;
     return (double)s;
 }
+
+void r_double(double v, std::string &out) {                            // %.15g, NaN and NA as R writes them
+    if (v != v) { out += "NaN"; return; }
+    char buf[40];
+    snprintf(buf, sizeof buf, "%.15g", v);
+    out += buf;
+}
+
+int write_text(const std::string &path, const std::string &text) {
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) return fail(MSNV_EIO, "Cannot open %s: %s", path.c_str(), strerror(errno));
+    fwrite(text.data(), 1, text.size(), f);
+    if (fclose(f) != 0) return fail(MSNV_EIO, "write error on %s: %s", path.c_str(), strerror(errno));
+    return MSNV_OK;
+}
+
+int make_dir(const std::string &path) {
+    if (mkdir(path.c_str(), 0777) != 0 && errno != EEXIST) return fail(MSNV_EIO, "Cannot create %s: %s", path.c_str(), strerror(errno));
+    return MSNV_OK;
+}
+
+namespace {
+
 // R's sd(): the n - 1 form, deviations from mean() summed in long double
 double r_sd(const double *x, size_t n) {
     const double m = r_mean(x, n);
@@ -100,26 +125,6 @@ struct Splits {
             }
     }
 };
-
-void r_double(double v, std::string &out) {                            // %.15g, NaN and NA as R writes them
-    if (v != v) { out += "NaN"; return; }
-    char buf[40];
-    snprintf(buf, sizeof buf, "%.15g", v);
-    out += buf;
-}
-
-int write_text(const std::string &path, const std::string &text) {
-    FILE *f = fopen(path.c_str(), "w");
-    if (!f) return fail(MSNV_EIO, "Cannot open %s: %s", path.c_str(), strerror(errno));
-    fwrite(text.data(), 1, text.size(), f);
-    if (fclose(f) != 0) return fail(MSNV_EIO, "write error on %s: %s", path.c_str(), strerror(errno));
-    return MSNV_OK;
-}
-
-int make_dir(const std::string &path) {
-    if (mkdir(path.c_str(), 0777) != 0 && errno != EEXIST) return fail(MSNV_EIO, "Cannot create %s: %s", path.c_str(), strerror(errno));
-    return MSNV_OK;
-}
 
 // write.table(as.matrix(d), sep = "\t", quote = F) of the samples `members` of the matrix
 int write_dist(const std::string &path, const std::vector<std::string> &names, const std::vector<double> &d, size_t n, const std::vector<int32_t> &members) {

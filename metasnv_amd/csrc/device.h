@@ -242,7 +242,7 @@ int  dev_inflate_resident(msnv_ctx *ctx, const uint8_t *host_in, uint64_t comp_b
                           uint32_t check_every, std::vector<uint32_t> &status, double *ms_kernel);
 int  dev_inflate_patch(msnv_ctx *ctx, uint64_t out_off, const uint8_t *data, uint32_t n);
 
-// ---- the stages that work on files (textcall.hip; dist.cpp + dist_k.hip; div.cpp + div_k.hip; subpopr.cpp + subpopr_k.hip; genecorr.cpp + genecorr_k.hip; cluster.cpp + cluster_k.hip)
+// ---- the stages that work on files (textcall.hip; dist.cpp + dist_k.hip; div.cpp + div_k.hip; subpopr.cpp + subpopr_k.hip; genecorr.cpp + genecorr_k.hip; cluster.cpp + cluster_k.hip; genotype.cpp + genotype_k.hip)
 int  text_call(msnv_ctx *ctx, const char *text, uint64_t n_text, const msnv_params &p, const char *ref_fasta, const char *ann_path,
                const char *called_path, const char *indiv_path, uint64_t stats[8]);
 int  dist_file(msnv_ctx *ctx, const char *freq_path, const char *mann_path, const char *allele_path, double threshold,
@@ -275,5 +275,13 @@ int dev_pam_tasks(const ClusterDev &c, uint64_t n_tasks, const uint32_t *m, cons
                   int32_t *swaps, double *ms_kernel);
 int dev_pred_strength(const ClusterDev &c, uint64_t n_splits, const uint32_t *len, const uint32_t *k, const int32_t *idx, void *stream, double *prederr, double *ms_kernel);
 int dev_freq_bands(const double *rows, uint64_t n_pos, uint32_t n_samples, void *stream, uint64_t *counts, double *ms_kernel);   // counts[sample][4]
+
+// genotype.cpp + genotype_k.hip: subpopr's computeUniquePosPerCluster.  col[] lists the columns in use in cluster order, seg[k] is the first
+// entry of cluster k (seg[K] = the list's length).  A row with a mean difference within GENO_GUARD of the threshold is flagged near.
+constexpr uint32_t GENO_MAX_CLUSTERS = 32, GENO_MAX_SAMPLES = 65536, GENO_ROWS_PER_BLOCK = 4, GENO_GRID_BLOCKS = 2048;
+constexpr uint64_t GENO_SLAB_BYTES = 1ull << 30;
+constexpr double GENO_GUARD = 1e-6;
+int dev_genotype_rows(const double *rows, uint64_t n_pos, uint32_t n_samples, const uint32_t *col, const uint32_t *seg, uint32_t n_clusters, double threshold,
+                      void *stream, uint32_t *select_mask, uint32_t *flip_mask, uint8_t *near_flag, double *ms_kernel);
 
 }  // namespace msnv

@@ -119,6 +119,11 @@ void py_repr(double x, std::string &out);                                   // f
 bool pandas_strtod(const char *s, const char *end, double &out);            // dist.cpp: pandas' default float converter
 int read_freq(const char *freq_path, std::vector<std::string> &names, std::vector<std::string> *labels, std::vector<double> &rows, uint64_t &n_pos);   // dist.cpp: a *.filtered.freq table
 int write_matrix(const char *path, const std::vector<std::string> &names, const std::vector<double> &m);
+// ... and as R does (cluster.cpp; the subpopr stages share them)
+double r_mean(const double *x, size_t n);                                   // mean(): long double, two passes
+void r_double(double v, std::string &out);                                  // write.table's %.15g; NaN as "NaN"
+int write_text(const std::string &path, const std::string &text);
+int make_dir(const std::string &path);                                      // an existing directory is fine
 
 // ---------------------------------------------------------------------------------- synthetic workload (synth.cpp)
 std::vector<std::string> synth_contigs(const msnv_synth_params &p);

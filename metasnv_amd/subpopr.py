@@ -15,9 +15,14 @@
       <species>.filtered.mann.dist (+ <species>.filtered.freq)  ->  <outDir>[/noClustering|/clustMedoidDefnFailed]/<species>_mann_{PS_values.tab,
       distMatrixUsedForClustMedoidDefns.txt,clustering.tab,clusNumStability.tab} and <species>_freq_composition.tab
 
-The first is a text filter (native, no device work); the frequencies of the second, the correlations of the third and every PAM run
-of the fourth are computed on the GPU (msnv_snv_allele_freq, msnv_gene_corr, msnv_corr_stats, msnv_pam_tasks, msnv_pred_strength)
-and there is no CPU fallback for them."""
+  writeGenotypeFreqs.py <species> <clustering.tab> <freq_file> <outDir> [--uniq-threshold X]
+      (src/subpopr/R/writeGenotypeFreqs.R writeGenotypeFreqs with computeUniquePosPerCluster)
+      <species>_mann_clustering.tab + <species>.filtered.freq  ->  <outDir>/<species>_<cluster>_hap_positions.tab, <species>_hap_out.txt and
+      <species>_hap_freq_{mean,median}.tab
+
+The first is a text filter (native, no device work); the frequencies of the second, the correlations of the third, every PAM run
+of the fourth and the fifth's walk over the frequency table are computed on the GPU (msnv_snv_allele_freq, msnv_gene_corr,
+msnv_corr_stats, msnv_pam_tasks, msnv_pred_strength, msnv_genotype_rows) and there is no CPU fallback for them."""
 import ctypes as C
 import glob
 import os
@@ -280,4 +285,75 @@ def cluster_subpops_main(argv=None):                           # clustering.R:20
     else:
         print("Species " + species + ": " + str(res["n_clusters"]) + " cluster(s) from " + str(res["n_samples"]) + " samples; cluster number stability: "
               + ("not rated", "Low", "Medium", "High")[res["stability_score"]])
+    return res
+
+
+def genotype_rows(ctx, rows, clust, threshold=80.0):
+    """computeUniquePosPerCluster's rule on arrays (msnv_genotype_rows).  rows [P x S] in 0..100 with NaN for no coverage; clust [S]: 0 for a
+    column not in use, else 1..K.  Returns select and flip (uint32 [P], bit i - 1 = cluster i), n_rechecked (rows redone on the host in long
+    double) and the kernel's ms."""
+    import numpy as np
+    from ._lib import lib, check
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    clust = np.ascontiguousarray(clust, dtype=np.int32).ravel()
+    if rows.ndim != 2 or rows.shape[1] != clust.size:
+        raise ValueError("genotype_rows: rows [P x S] and clust [S] must share S")
+    p, s = rows.shape
+    select, flip = np.zeros(max(p, 1), dtype=np.uint32), np.zeros(max(p, 1), dtype=np.uint32)
+    n, ms = C.c_uint64(), C.c_double()
+    u32 = C.POINTER(C.c_uint32)
+    check(lib.msnv_genotype_rows(ctx._h, p, s, _dptr(rows), _iptr(clust), int(clust.max(initial=0)), float(threshold), select.ctypes.data_as(u32),
+                                 flip.ctypes.data_as(u32), C.byref(n), C.byref(ms)))
+    return {"select": select[:p], "flip": flip[:p], "n_rechecked": n.value, "ms_kernel": ms.value}
+
+
+def genotype_file(ctx, clustering_path, freq_path, out_dir, species=None, uniq_threshold=0.8):
+    """The stage on files (msnv_genotype_file).  Returns a dict: status (_lib.GENOTYPE_*), n_clusters, n_samples, n_rows, n_positions,
+    n_rechecked, n_correct, n_good, ms_kernel."""
+    from ._lib import lib, check
+    if species is None:
+        species = os.path.basename(freq_path).split(".")[0]
+    res = (C.c_int64 * 8)()
+    ms = C.c_double()
+    check(lib.msnv_genotype_file(ctx._h, clustering_path.encode(), freq_path.encode(), species.encode(), out_dir.encode(), float(uniq_threshold), res, C.byref(ms)))
+    return {"status": res[0], "n_clusters": res[1], "n_samples": res[2], "n_rows": res[3], "n_positions": res[4], "n_rechecked": res[5], "n_correct": res[6],
+            "n_good": res[7], "ms_kernel": ms.value}
+
+
+GENOTYPE_ENDINGS = {                                           # what <species>_hap_out.txt ends with (writeGenotypeFreqs.R:12-105)
+    1: "a single cluster: nothing to genotype",
+    2: "no genotyping positions",
+    3: "at least one cluster is missing genotyping positions",
+    4: "the genotype-specific SNV frequency cutoff is bad",
+}
+
+
+def write_genotype_freqs_main(argv=None):                      # writeGenotypeFreqs.R:2-112
+    import argparse
+    ap = argparse.ArgumentParser(prog="writeGenotypeFreqs.py", description="Select each subspecies' genotyping SNVs (subpopr's writeGenotypeFreqs) on the GPU.")
+    ap.add_argument("species", metavar="SPECIES")
+    ap.add_argument("clustering", metavar="CLUSTERING_TAB", help="<species>_mann_clustering.tab of clusterSubpops.py")
+    ap.add_argument("freq", metavar="FREQ_FILE", help="<species>.filtered.freq")
+    ap.add_argument("out_dir", metavar="OUTDIR")
+    ap.add_argument("--uniq-threshold", type=float, default=0.8, metavar="X", help="mean frequency difference to every other cluster, as a proportion (0.8)")
+    a = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    for f in (a.clustering, a.freq):
+        if not os.path.exists(f):
+            sys.exit("ERROR: missing input file: " + f)
+    from . import core
+    try:
+        ctx = core.Context(0)
+    except core._lib.MsnvError as e:
+        sys.exit("\nERROR:  {}\n\nSOLUTION: run on a node with an AMD Instinct GPU (there is no CPU fallback)\n".format(e))
+    try:
+        res = genotype_file(ctx, a.clustering, a.freq, a.out_dir, species=a.species, uniq_threshold=a.uniq_threshold)
+    except core._lib.MsnvError as e:
+        sys.exit("ERROR: {}".format(e))
+    finally:
+        ctx.close()
+    if res["status"] in GENOTYPE_ENDINGS:
+        print("Species " + a.species + ": " + GENOTYPE_ENDINGS[res["status"]] + " (see " + os.path.join(a.out_dir, a.species + "_hap_out.txt") + ")")
+    else:
+        print("Species " + a.species + ": " + str(res["n_positions"]) + " genotyping positions for " + str(res["n_clusters"]) + " clusters from " + str(res["n_rows"])
+              + " SNVs; " + str(res["n_correct"]) + " of " + str(res["n_good"]) + " classified samples assigned to their own cluster")
     return res
