@@ -358,6 +358,51 @@ int msnv_genotype_rows(msnv_ctx *ctx, uint64_t n_pos, int32_t n_samples, const d
 int msnv_genotype_file(msnv_ctx *ctx, const char *clustering_path, const char *freq_path, const char *species, const char *out_dir,
                        double uniq_threshold, int64_t result[8], double *ms_kernel);
 
+/* subpopr's useGenotypesToProfileSubpops -> writeSubpopsForAllSamples (src/subpopr/R/profileSubpops.R:228-274, writeSubpopsForAllSamples.R) and
+ * useSpeciesAbundToCalcSubspeciesAbund -> writeSubpopAbundSpeciesAbund (profileSubpops.R:277-310, writeSubpopAbund.R:99-169): how abundant each
+ * subspecies is in every sample metaSNV was run on.  Restated from reading the R code; no R was run (unpinned).
+ *
+ * msnv_subpop_profile_columns -- the kernel on arrays.  rows: host memory, row-major [n_rows][n_samples], NaN for no coverage, every other cell
+ * within [0, 100] (else MSNV_EDOMAIN); flip: one byte per row, a row with a non-zero byte counts as 100 - x (the fp64 subtraction R does).
+ * 1 <= n_samples <= 65536 and 1 <= n_rows <= 2^31 - 1, else MSNV_EDOMAIN.  Per column s, over its called (non-NaN) cells: n_called, n_gt0 (> 0),
+ * n_ge5 (>= 5), n_eq0 (== 0), n_eq100 (== 100), and mid_lo / mid_hi, the order statistics of 0-based ranks (n - 1) / 2 and n / 2 (integer
+ * division): equal when n is odd, NaN when n is 0, otherwise values that occur in the column, bit for bit (-0.0 counts as +0.0).  Everything is
+ * exact; median(x) is mean({mid_lo, mid_hi}).  The matrix goes to the device in bands of columns: cols_per_pass = 0 sizes a band from half of
+ * the free device memory, a positive value forces that width.  *ms_kernel: the kernel's time by events, summed over the bands.
+ *
+ * msnv_subpop_profile_files -- writeSubpopsForAllSamples on files.  Sample names: the basenames of the lines of all_samples_path, in order.
+ * Cluster files: <out_dir>/<species>_*.pos.freq in byte order of their names (msnv_snv_allele_freq writes them: id contig:ann:pos:base, then one
+ * cell per sample, -1 = NA; another column count is MSNV_EFORMAT); the cluster number is the text between the last '_' and the first '.' of the
+ * name (not an integer: MSNV_EFORMAT), and <out_dir>/<species>_<cluster>_hap_positions.tab (as msnv_genotype_file writes it) lists the cluster's
+ * positions and flips.  Ids are matched as contig:pos:base; a duplicate id in either file is MSNV_EFORMAT; a listed position the .pos.freq lacks
+ * is one all-NA row.  With G listed positions a sample is kept when n_called >= max_prop_uncalled * G (fp64 product; 0 < max_prop_uncalled <= 1,
+ * else MSNV_EDOMAIN); a cluster with fewer than two kept samples is skipped.  Written into out_dir, every file as write.table(sep = '\t',
+ * quote = F) prints it with %.15g: <species>_extended_clustering_abundanceSummaryStats.tsv (per usable cluster and kept sample: Sample, Cluster,
+ * mean, median, standardDeviation, prevalence, prevalenceGte5, n0, n100, nNoCoverage; mean and sd by R's long double rules on the host),
+ * _wFreq_unfiltered.tab (the samples with a median in every usable cluster, a column of medians per cluster), _wFreq.tab (those whose long double
+ * row sum lies in [80, 120], minus the samples with median > 30 and prevalence < 0.75 in any cluster), _clustering.tab (column "clust": the
+ * 1-based position of the single median above min_genotype_abundance, else NA) and lines appended to _stat.txt.  When the first usable cluster
+ * is not cluster 1, or no sample has a median in every usable cluster, R binds columns of different samples: the summary table is written and
+ * the call returns MSNV_EDOMAIN.  result: [0] MSNV_PROFILE_* [1] cluster files found [2] usable [3] samples in the unfiltered table [4] in the
+ * filtered one [5] rejected for their sum [6] rejected as bad [7] assigned a cluster.
+ *
+ * msnv_subpop_abundance_files -- writeSubpopAbundSpeciesAbund on files; host only.  Reads <out_dir>/<species>_extended_clustering_wFreq.tab
+ * (numeric headers get R's X prefix) and the species abundance table ('#' lines skipped; first line: a corner cell and the sample names; first
+ * column: species), takes the samples both hold in the table's column order (none, and a suffix given: retried with the suffix appended to the
+ * table's names), and writes freq / 100 * abundance to <species>_allClust_relativeAbund.tab and, per column x = 1.., to
+ * <species>_clust_<x>_hap_coverage_extended_normed.tab.  Species absent or listed twice, no frequency rows, no shared sample: MSNV_EDOMAIN with
+ * R's text.  counts: samples used, clusters, samples in wFreq.tab, sample columns of the abundance table. */
+#define MSNV_PROFILE_OK          0   /* the five files are written                                                                      */
+#define MSNV_PROFILE_NO_FILES    1   /* no <species>_*.pos.freq: "0/0 clusters had usable placing data." appended to _stat.txt          */
+#define MSNV_PROFILE_NONE_USABLE 2   /* no cluster has two kept samples: "0/<n> clusters ..." appended, nothing else written             */
+int msnv_subpop_profile_columns(msnv_ctx *ctx, int64_t n_rows, int32_t n_samples, const double *rows, const uint8_t *flip, int32_t cols_per_pass,
+                                uint32_t *n_called, uint32_t *n_gt0, uint32_t *n_ge5, uint32_t *n_eq0, uint32_t *n_eq100, double *mid_lo,
+                                double *mid_hi, double *ms_kernel);
+int msnv_subpop_profile_files(msnv_ctx *ctx, const char *species, const char *out_dir, const char *all_samples_path, double max_prop_uncalled,
+                              double min_genotype_abundance, int64_t result[8], double *ms_kernel);
+int msnv_subpop_abundance_files(const char *species, const char *out_dir, const char *abundance_path, const char *sample_suffix,
+                                uint64_t counts[4]);
+
 /* ------------------------------------------------------------------------------------
  * Staged form of the same path.
  * ------------------------------------------------------------------------------------ */

@@ -24,6 +24,7 @@ DIV, DIV_NS = 0, 1                                             # msnv_div_file m
 CORR_PEARSON, CORR_SPEARMAN = 0, 1                             # msnv_corr_stats methods
 CLUSTER_OK, CLUSTER_NONE, CLUSTER_MEDOID_FAILED, CLUSTER_TOO_FEW, CLUSTER_ALL_EQUAL = range(5)   # msnv_cluster_file result[0]
 GENOTYPE_OK, GENOTYPE_SINGLE, GENOTYPE_NO_POSITIONS, GENOTYPE_CLUSTER_MISSING, GENOTYPE_CUTOFF_BAD = range(5)   # msnv_genotype_file result[0]
+PROFILE_OK, PROFILE_NO_FILES, PROFILE_NONE_USABLE = range(3)   # msnv_subpop_profile_files result[0]
 
 
 class Params(C.Structure):
@@ -238,6 +239,10 @@ SYMBOLS = [
     ("msnv_genotype_rows", C.c_int, [_vp, C.c_uint64, C.c_int32, P(C.c_double), P(C.c_int32), C.c_int32, C.c_double, P(C.c_uint32), P(C.c_uint32), P(C.c_uint64),
                                      P(C.c_double)]),
     ("msnv_genotype_file", C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_double, P(C.c_int64), P(C.c_double)]),
+    ("msnv_subpop_profile_columns", C.c_int, [_vp, C.c_int64, C.c_int32, P(C.c_double), P(C.c_uint8), C.c_int32, P(C.c_uint32), P(C.c_uint32), P(C.c_uint32), P(C.c_uint32),
+                                              P(C.c_uint32), P(C.c_double), P(C.c_double), P(C.c_double)]),
+    ("msnv_subpop_profile_files", C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_double, C.c_double, P(C.c_int64), P(C.c_double)]),
+    ("msnv_subpop_abundance_files", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, P(C.c_uint64)]),
     ("msnv_format_float", C.c_int, [C.c_double, C.c_char_p, C.c_int32]),
     ("msnv_filter_files", C.c_int, [_vp, P(C.c_char_p), C.c_int32, C.c_int32, P(FilterSpecies), C.c_int32, C.c_double, C.c_double,
                                    C.c_char_p, P(C.c_uint64), P(C.c_double)]),

@@ -75,8 +75,6 @@ int make_dir(const std::string &path) {
     return MSNV_OK;
 }
 
-namespace {
-
 // R's sd(): the n - 1 form, deviations from mean() summed in long double
 double r_sd(const double *x, size_t n) {
     const double m = r_mean(x, n);
@@ -84,6 +82,8 @@ double r_sd(const double *x, size_t n) {
     for (size_t i = 0; i < n; ++i) { const long double d = (long double)x[i] - m; q += d * d; }
     return std::sqrt((double)(q / (long double)(n - 1)));
 }
+
+namespace {
 
 int check_matrix(const char *who, int64_t n, const double *d) {
     if (n < 2 || n > (int64_t)CLUSTER_MAX_SAMPLES) return fail(MSNV_EDOMAIN, "%s: %lld samples (2 to %u)", who, (long long)n, CLUSTER_MAX_SAMPLES);

@@ -242,7 +242,7 @@ int  dev_inflate_resident(msnv_ctx *ctx, const uint8_t *host_in, uint64_t comp_b
                           uint32_t check_every, std::vector<uint32_t> &status, double *ms_kernel);
 int  dev_inflate_patch(msnv_ctx *ctx, uint64_t out_off, const uint8_t *data, uint32_t n);
 
-// ---- the stages that work on files (textcall.hip; dist.cpp + dist_k.hip; div.cpp + div_k.hip; subpopr.cpp + subpopr_k.hip; genecorr.cpp + genecorr_k.hip; cluster.cpp + cluster_k.hip; genotype.cpp + genotype_k.hip)
+// ---- the stages that work on files (textcall.hip; dist.cpp + dist_k.hip; div.cpp + div_k.hip; subpopr.cpp + subpopr_k.hip; genecorr.cpp + genecorr_k.hip; cluster.cpp + cluster_k.hip; genotype.cpp + genotype_k.hip; profile.cpp + profile_k.hip)
 int  text_call(msnv_ctx *ctx, const char *text, uint64_t n_text, const msnv_params &p, const char *ref_fasta, const char *ann_path,
                const char *called_path, const char *indiv_path, uint64_t stats[8]);
 int  dist_file(msnv_ctx *ctx, const char *freq_path, const char *mann_path, const char *allele_path, double threshold,
@@ -283,5 +283,11 @@ constexpr uint64_t GENO_SLAB_BYTES = 1ull << 30;
 constexpr double GENO_GUARD = 1e-6;
 int dev_genotype_rows(const double *rows, uint64_t n_pos, uint32_t n_samples, const uint32_t *col, const uint32_t *seg, uint32_t n_clusters, double threshold,
                       void *stream, uint32_t *select_mask, uint32_t *flip_mask, uint8_t *near_flag, double *ms_kernel);
+
+// profile.cpp + profile_k.hip: subpopr's writeSubpopsForAllSamples.  A workgroup of PROF_WAVES wavefronts owns PROF_COLS adjacent columns; counts[i][s]
+// are the called cells, those > 0, >= 5, == 0 and == 100 of column s; *outside: a cell that is neither NaN nor within [0, 100] was seen.
+constexpr uint32_t PROF_COLS = 16, PROF_WAVES = 16;
+int dev_profile_columns(const double *rows, uint32_t n_rows, uint32_t n_samples, const uint8_t *flip, uint32_t cols_per_pass, void *stream, uint32_t *counts[5],
+                        double *mid_lo, double *mid_hi, bool *outside, double *ms_kernel);
 
 }  // namespace msnv

@@ -121,7 +121,8 @@ int read_freq(const char *freq_path, std::vector<std::string> &names, std::vecto
 int write_matrix(const char *path, const std::vector<std::string> &names, const std::vector<double> &m);
 // ... and as R does (cluster.cpp; the subpopr stages share them)
 double r_mean(const double *x, size_t n);                                   // mean(): long double, two passes
-void r_double(double v, std::string &out);                                  // write.table's %.15g; NaN as "NaN"
+double r_sd(const double *x, size_t n);                                     // sd(): squared deviations from mean() in long double, n - 1; n >= 2
+void r_double(double v, std::string &out);                                 // write.table's %.15g; NaN as "NaN"
 int write_text(const std::string &path, const std::string &text);
 int make_dir(const std::string &path);                                      // an existing directory is fine
 

@@ -20,9 +20,20 @@
       <species>_mann_clustering.tab + <species>.filtered.freq  ->  <outDir>/<species>_<cluster>_hap_positions.tab, <species>_hap_out.txt and
       <species>_hap_freq_{mean,median}.tab
 
-The first is a text filter (native, no device work); the frequencies of the second, the correlations of the third, every PAM run
-of the fourth and the fifth's walk over the frequency table are computed on the GPU (msnv_snv_allele_freq, msnv_gene_corr,
-msnv_corr_stats, msnv_pam_tasks, msnv_pred_strength, msnv_genotype_rows) and there is no CPU fallback for them."""
+  profileSubpops.py <species> <metaSNVdir> <outDir> [--max-prop-uncalled X] [--min-genotype-abundance X]
+      (src/subpopr/R/profileSubpops.R useGenotypesToProfileSubpops with writeSubpopsForAllSamples.R)
+      <metaSNVdir>/all_samples + <outDir>/<species>_<cluster>.pos.freq + <species>_<cluster>_hap_positions.tab  ->
+      <outDir>/<species>_extended_clustering_{abundanceSummaryStats.tsv,wFreq_unfiltered.tab,wFreq.tab,stat.txt} and <species>_extended_clustering.tab
+
+  writeSubpopAbund.py <species> <outDir> <speciesAbundanceFile> [--sample-suffix S]
+      (src/subpopr/R/writeSubpopAbund.R writeSubpopAbundSpeciesAbund; the mOTU variant is not built)
+      <outDir>/<species>_extended_clustering_wFreq.tab + a species x samples abundance table  ->  <outDir>/<species>_allClust_relativeAbund.tab and
+      <species>_clust_<x>_hap_coverage_extended_normed.tab
+
+The first and the last are text filters (native, no device work); the frequencies of the second, the correlations of the third, every PAM run
+of the fourth, the fifth's walk over the frequency table and the sixth's counts and medians per sample are computed on the GPU
+(msnv_snv_allele_freq, msnv_gene_corr, msnv_corr_stats, msnv_pam_tasks, msnv_pred_strength, msnv_genotype_rows, msnv_subpop_profile_columns)
+and there is no CPU fallback for them."""
 import ctypes as C
 import glob
 import os
@@ -357,3 +368,112 @@ def write_genotype_freqs_main(argv=None):                      # writeGenotypeFr
         print("Species " + a.species + ": " + str(res["n_positions"]) + " genotyping positions for " + str(res["n_clusters"]) + " clusters from " + str(res["n_rows"])
               + " SNVs; " + str(res["n_correct"]) + " of " + str(res["n_good"]) + " classified samples assigned to their own cluster")
     return res
+
+
+def profile_columns(ctx, rows, flip, cols_per_pass=0):
+    """Per column of rows [G x S] (0..100, NaN for no coverage; a row with flip[g] set counts as 100 - x): the counts and the two middle order
+    statistics of its called cells (msnv_subpop_profile_columns).  Returns n_called, n_gt0, n_ge5, n_eq0, n_eq100 (uint32 [S]), mid_lo, mid_hi
+    (float64 [S]: ranks (n - 1) // 2 and n // 2, NaN at n = 0) and the kernel's ms.  cols_per_pass: the width of a column band (0: from free memory)."""
+    import numpy as np
+    from ._lib import lib, check
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    flip = np.ascontiguousarray(flip).astype(np.uint8).ravel()
+    if rows.ndim != 2 or rows.shape[0] != flip.size:
+        raise ValueError("profile_columns: rows [G x S] and flip [G] must share G")
+    g, s = rows.shape
+    out = {k: np.zeros(max(s, 1), dtype=np.uint32) for k in ("n_called", "n_gt0", "n_ge5", "n_eq0", "n_eq100")}
+    lo, hi = np.zeros(max(s, 1)), np.zeros(max(s, 1))
+    ms = C.c_double()
+    u32 = C.POINTER(C.c_uint32)
+    check(lib.msnv_subpop_profile_columns(ctx._h, g, s, _dptr(rows), flip.ctypes.data_as(C.POINTER(C.c_uint8)), int(cols_per_pass),
+                                          *[out[k].ctypes.data_as(u32) for k in ("n_called", "n_gt0", "n_ge5", "n_eq0", "n_eq100")], _dptr(lo), _dptr(hi), C.byref(ms)))
+    res = {k: v[:s] for k, v in out.items()}
+    res.update(mid_lo=lo[:s], mid_hi=hi[:s], ms_kernel=ms.value)
+    return res
+
+
+def subpop_profile_files(ctx, species, out_dir, all_samples_path, max_prop_uncalled=0.2, min_genotype_abundance=80.0):
+    """writeSubpopsForAllSamples on files (msnv_subpop_profile_files).  Returns a dict: status (_lib.PROFILE_*), n_files, n_usable, n_full, n_filtered,
+    n_incoherent, n_bad, n_assigned, ms_kernel."""
+    from ._lib import lib, check
+    res = (C.c_int64 * 8)()
+    ms = C.c_double()
+    check(lib.msnv_subpop_profile_files(ctx._h, species.encode(), out_dir.encode(), all_samples_path.encode(), float(max_prop_uncalled), float(min_genotype_abundance),
+                                        res, C.byref(ms)))
+    return {"status": res[0], "n_files": res[1], "n_usable": res[2], "n_full": res[3], "n_filtered": res[4], "n_incoherent": res[5], "n_bad": res[6],
+            "n_assigned": res[7], "ms_kernel": ms.value}
+
+
+def subpop_abundance_files(species, out_dir, abundance_path, sample_suffix=None):
+    """writeSubpopAbundSpeciesAbund on files (msnv_subpop_abundance_files; host only).  Returns (samples used, clusters, samples in wFreq.tab,
+    sample columns of the abundance table)."""
+    from ._lib import lib, check
+    counts = (C.c_uint64 * 4)()
+    check(lib.msnv_subpop_abundance_files(species.encode(), out_dir.encode(), abundance_path.encode(), None if sample_suffix is None else sample_suffix.encode(), counts))
+    return tuple(counts)
+
+
+PROFILE_ENDINGS = {                                            # what <species>_extended_clustering_stat.txt ends with (writeSubpopsForAllSamples.R:16-117)
+    1: "no <species>_*.pos.freq file: run getGenotypingSNVSubset.py and convertSNVtoAlleleFreq.py first",
+    2: "no cluster had usable placing data",
+}
+
+
+def profile_subpops_main(argv=None):                           # profileSubpops.R:228-274 useGenotypesToProfileSubpops
+    import argparse
+    ap = argparse.ArgumentParser(prog="profileSubpops.py", description="Profile subspecies in every sample (subpopr's useGenotypesToProfileSubpops) on the GPU.")
+    ap.add_argument("species", metavar="SPECIES")
+    ap.add_argument("metasnv_dir", metavar="METASNV_DIR", help="metaSNV's output directory (holds all_samples)")
+    ap.add_argument("out_dir", metavar="OUTDIR", help="holds <species>_<cluster>.pos.freq and <species>_<cluster>_hap_positions.tab")
+    ap.add_argument("--max-prop-uncalled", type=float, default=0.2, metavar="X", help="a sample is kept when it has at least X * (genotyping positions) called (0.2)")
+    ap.add_argument("--min-genotype-abundance", type=float, default=80.0, metavar="X", help="median above which a sample is assigned to a cluster (80)")
+    a = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    median_path = os.path.join(a.out_dir, a.species + "_hap_freq_median.tab")
+    if not os.path.exists(median_path):                        # :243-248
+        print("No distinctive genotyping positions for species " + a.species + ", perhaps the cutoff was bad. See "
+              + os.path.join(a.out_dir, a.species + "_hap_out.txt") + " for details. (Required file does not exist: " + median_path + ")")
+        return None
+    all_samples = os.path.join(a.metasnv_dir, "all_samples")
+    if not os.path.exists(all_samples):                        # :250-254
+        sys.exit("ERROR: File with paths to samples does not exist. This should have been created by metaSNV.Expected path: " + all_samples)
+    from . import core
+    try:
+        ctx = core.Context(0)
+    except core._lib.MsnvError as e:
+        sys.exit("\nERROR:  {}\n\nSOLUTION: run on a node with an AMD Instinct GPU (there is no CPU fallback)\n".format(e))
+    try:
+        res = subpop_profile_files(ctx, a.species, a.out_dir, all_samples, a.max_prop_uncalled, a.min_genotype_abundance)
+    except core._lib.MsnvError as e:
+        sys.exit("ERROR: {}".format(e))
+    finally:
+        ctx.close()
+    if res["status"] in PROFILE_ENDINGS:
+        print("Species " + a.species + ": " + PROFILE_ENDINGS[res["status"]])
+        print("Species does not have cluster frequencies. Species: " + a.species)      # :269-271
+    else:
+        print("Species " + a.species + ": " + str(res["n_usable"]) + " of " + str(res["n_files"]) + " clusters profiled; " + str(res["n_filtered"]) + " of "
+              + str(res["n_full"]) + " samples kept, " + str(res["n_assigned"]) + " assigned to a cluster")
+        if res["n_filtered"] == 0:
+            print("Species does not have cluster frequencies. Species: " + a.species)
+    return res
+
+
+def write_subpop_abund_main(argv=None):                        # profileSubpops.R:277-310 useSpeciesAbundToCalcSubspeciesAbund, species abundances
+    import argparse
+    ap = argparse.ArgumentParser(prog="writeSubpopAbund.py", description="Scale subspecies frequencies by the species' abundance (subpopr's writeSubpopAbundSpeciesAbund).")
+    ap.add_argument("species", metavar="SPECIES")
+    ap.add_argument("out_dir", metavar="OUTDIR", help="holds <species>_extended_clustering_wFreq.tab")
+    ap.add_argument("abundance", metavar="SPECIES_ABUNDANCE_FILE", help="species x samples table: first line the sample names, first column the species")
+    ap.add_argument("--sample-suffix", default=None, metavar="S", help="appended to the table's sample names when none matches")
+    a = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    freq_path = os.path.join(a.out_dir, a.species + "_extended_clustering_wFreq.tab")
+    if not os.path.exists(freq_path):                          # :280-283
+        print("Species " + a.species + " does not have cluster frequencies. File does not exist: " + freq_path)
+        return None
+    if not os.path.exists(a.abundance):                        # :291-296
+        sys.exit("ERROR: Cannot compute overall subspecies abundances. Required species abundance file not found: " + a.abundance)
+    from ._lib import MsnvError
+    try:
+        return subpop_abundance_files(a.species, a.out_dir, a.abundance, a.sample_suffix)
+    except MsnvError as e:
+        sys.exit("ERROR: {}".format(e))
