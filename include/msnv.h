@@ -320,6 +320,55 @@ int msnv_pred_strength(msnv_ctx *ctx, int32_t n, const double *dist, int32_t k_m
 int msnv_cluster_file(msnv_ctx *ctx, const char *dist_path, const char *freq_path, const char *species, const char *out_dir,
                       const msnv_cluster_opts *opts, int64_t result[8], double *ms_kernel);
 
+/* The stability of each cluster's membership: getClusMembStability -> clusterAssignSubsample -> getClusMembStabScore
+ * (src/subpopr/R/clusteringStability.R:129-148, :170-176, :224-237), i.e. fpc::clusterboot(bootmethod = "subset", clustermethod = claraCBI,
+ * usepam = TRUE, dissolution = 0.5, recover = 0.75).  Restated from reading the R code and from memory of fpc; no R was run (DESIGN.md
+ * section 7: unpinned).
+ *
+ * msnv_cluster_boot -- the array form.  dist: the n x n matrix, as for msnv_pam_tasks.  members: m sample indices, ascending: the clustered
+ * samples.  1 <= k <= 32 and k < m.  Subset t is set_m[t] distinct positions 0..m-1 into the member list, in the order given, packed behind
+ * each other in set_pos; k < set_m[t] <= m.  Anything else is MSNV_EDOMAIN or MSNV_EINVAL before any launch.  Out: cluster[m] (1..k) and
+ * medoids[k], the PAM of the members in list order; and, for subset t re-clustered by PAM in its own order with the same k and every
+ * original cluster j = 1..k, best_inter / best_union [t * k + j - 1]: over the new clusters c that have a member, ascending,
+ *   inter = #(entries of the subset in j and in c), union = #(entries of the subset in j) + #(entries in c) - inter,
+ * the FIRST c with the largest inter / union, fractions compared exactly as integers (a / b > c / d <=> a d > c b).  An original cluster
+ * without an entry in the subset gets inter = 0; a union is never 0.  The Jaccard value is (double)inter / (double)union.  Two launches
+ * for any number of subsets (at most 2^26 list entries in one call, else MSNV_ECAPACITY): the PAM kernel over the members and every
+ * subset, then one workgroup per subset over the cluster ids the first left on the device.  A subset's result does not depend on its
+ * place in the batch.
+ *
+ * msnv_membership_stability_file -- the stage on files.  dist_used_path: <species>_mann_distMatrixUsedForClustMedoidDefns.txt as
+ * msnv_cluster_file writes it (write.table's form: n names in the header without a leading cell); all of its n samples are the members.
+ * n < 10: MSNV_MEMBSTAB_NOT_RATED, nothing written.  Else 1 <= k <= 32 and k < n (MSNV_EDOMAIN).  The proportions and subset sizes are
+ * those of msnv_cluster_file's number-stability run: low = max(0.3, ceil(10 / n * 10) / 10), prop = low + 0.1 pi while <= 1 + 1e-10, size =
+ * min(n, floor(n prop)); subset b (0 <= b < boot_iters) of proportion pi is the first size entries of permutation(seed, 1 << 62 | pi << 32 |
+ * b, n), in that order.  A proportion whose size is <= k is not clustered: its rows hold NA (R's pam stops there: a divergence).  Per
+ * proportion and original cluster j, over the boot_iters values J_b = inter / union:
+ *   clusterStabilityJaccardMean = R's mean();  clusterStabilityPropRecover = #(J_b >= 0.75) / #(J_b <= 0.5) as a double division (Inf for
+ *   x / 0, NaN for 0 / 0): clusterboot's subsetrecover / subsetbrd, which is what the reference divides by.
+ * Written into out_dir (%.15g, NaN, Inf, NA):
+ *   <species>_mann_clusMembStability.tab   clusterID, nSamplesInCluster (of the original PAM partition), subsampleProp,
+ *                                          clusterStabilityJaccardMean, clusterStabilityPropRecover; one row per (proportion, cluster)
+ *   <species>_mann_stabilityAssessment.tab name, score: numClusters = getNClusStabScore of clus_num_stability_path (NA when NULL), then
+ *                                          clust1..clustk = getClusMembStabScore: 1 + (recover@0.9 > 0.8 & jaccard@0.9 > 0.8) +
+ *                                          (recover@0.7 > 0.9 & jaccard@0.7 > 0.9) with R's three-valued &, a NaN, NA or missing row
+ *                                          being NA; Low, Medium, High or NA
+ * result: [0] MSNV_MEMBSTAB_* [1] k [2] n [3] proportions [4] subsets clustered [5] the numClusters score (1..3, 0 = NA) [6] the lowest
+ * cluster score (0 when any is NA) [7] 0. */
+#define MSNV_MEMBSTAB_OK        0
+#define MSNV_MEMBSTAB_NOT_RATED 1   /* fewer than 10 samples: the reference rates stability from 10 on */
+typedef struct {
+    uint64_t seed;
+    int32_t  boot_iters;        /* clusterboot's B, 100 (tests lower it); 1..1024               */
+    int32_t  reserved;          /* 0                                                            */
+} msnv_membstab_opts;
+void msnv_membstab_opts_default(msnv_membstab_opts *o);
+int msnv_cluster_boot(msnv_ctx *ctx, int32_t n, const double *dist, int32_t m, const int32_t *members, int32_t k, int64_t n_sets,
+                      const int32_t *set_m, const int32_t *set_pos, int32_t *medoids, int32_t *cluster, int32_t *best_inter,
+                      int32_t *best_union, double *ms_kernel);
+int msnv_membership_stability_file(msnv_ctx *ctx, const char *dist_used_path, const char *clus_num_stability_path, const char *species,
+                                   int32_t k, const char *out_dir, const msnv_membstab_opts *opts, int64_t result[8], double *ms_kernel);
+
 /* subpopr's writeGenotypeFreqs -> computeUniquePosPerCluster (src/subpopr/R/writeGenotypeFreqs.R:2-112, :195-277): which SNVs tell one
  * subspecies from every other.  Restated from reading the R code; no R was run (unpinned).
  *

@@ -6,6 +6,10 @@
 //   msnv_cluster_file    the stage: outliers (filterSamples.R:42-72), SNV frequency composition (computeSnvFreqStats.R:1-24, :139-147), Gmax
 //                        (:218-236), prediction strength, PAM, the stability of the cluster number (:359-381, clusteringStability.R:6-24,
 //                        :201-221), small clusters (:383-400), the files
+//   msnv_cluster_boot    fpc::clusterboot(bootmethod = "subset") on given subsets: PAM of the members and of every subset, each original cluster's
+//                        best Jaccard match per subset as integers
+//   msnv_membership_stability_file   the stability of each cluster's membership (clusteringStability.R:129-148, :170-176, :224-237) on the
+//                        matrix msnv_cluster_file wrote: the two stability files (at the end of this file)
 // What is on the host: reading and writing, the outlier rule (n numbers), the draws (include/msnv.h), R's mean() of each k's M values and the
 // stability score.  Every PAM run, classification and pair count is on the device; there is no CPU fallback.
 // Divergences: rmNAfromDistMatrix is not built (an NA cell is MSNV_EFORMAT); R's generator is not reproduced; when Gmax <= 1
@@ -105,6 +109,20 @@ void ps_summary(const double *prederr, uint32_t gmax, uint32_t M, double cutoff,
     for (uint32_t k = 1; k <= gmax; ++k) if (mean_pred[k - 1] > cutoff) optimalk = (int32_t)k;
 }
 
+// The subsample proportions of both stability assessments (clustering.R:359-381): from the proportion that leaves 10 samples, 0.3 at the least, to
+// 1 in steps of 0.1, each with its subsample size.  n >= 10.
+struct SubsampleStep { double prop; uint32_t size; };
+std::vector<SubsampleStep> subsample_steps(uint32_t n) {
+    std::vector<SubsampleStep> steps;
+    const double low = std::max(0.3, std::ceil(10.0 / n * 10) / 10);
+    for (uint32_t pi = 0;; ++pi) {
+        const double prop = low + pi * 0.1;
+        if (!(prop <= 1 + 1e-10)) break;
+        steps.push_back(SubsampleStep{prop, std::min(n, (uint32_t)std::floor(n * prop))});
+    }
+    return steps;
+}
+
 uint32_t max_clusters_to_try(uint32_t n, uint32_t dflt, uint32_t min_size) {      // getMaxNumClustersToTry (:218-236); may be "negative": 0
     const int64_t a = (int64_t)(n / 2) - 1, b = n / min_size, lim = std::min(a, b);
     return (uint32_t)std::max<int64_t>(0, std::min<int64_t>(dflt, lim));
@@ -139,8 +157,9 @@ int write_dist(const std::string &path, const std::vector<std::string> &names, c
     return write_text(path, text);
 }
 
-// <species>.filtered.mann.dist as write_matrix of dist.cpp writes it: a header of names behind an empty cell, then name + n cells per row
-int read_dist(const char *path, std::vector<std::string> &names, std::vector<double> &d) {
+// <species>.filtered.mann.dist as write_matrix of dist.cpp writes it: a header of names behind an empty cell, then name + n cells per row.
+// r_form: the header as write.table prints it (write_dist above), n names and no leading cell.
+int read_dist(const char *path, std::vector<std::string> &names, std::vector<double> &d, bool r_form = false) {
     FILE *in = fopen(path, "r");
     if (!in) return fail(MSNV_EIO, "Cannot open %s: %s", path, strerror(errno));
     char *line = nullptr; size_t cap = 0; ssize_t len;
@@ -158,7 +177,7 @@ int read_dist(const char *path, std::vector<std::string> &names, std::vector<dou
             if (!t) break;
             s = t + 1;
         }
-        if (lineno == 1) { names.assign(f.begin() + 1, f.end()); continue; }
+        if (lineno == 1) { names.assign(f.begin() + (r_form ? 0 : 1), f.end()); continue; }
         if (f.size() != names.size() + 1) { rc = fail(MSNV_EFORMAT, "%s:%llu: %zu cells for %zu samples", path, (unsigned long long)lineno, f.size() - 1, names.size()); break; }
         if (n_rows >= names.size() || f[0] != names[n_rows]) { rc = fail(MSNV_EFORMAT, "%s:%llu: row '%s' does not follow the header's order", path, (unsigned long long)lineno, f[0].c_str()); break; }
         for (size_t c = 1; c < f.size(); ++c) {
@@ -367,15 +386,14 @@ extern "C" int msnv_cluster_file(msnv_ctx *ctx, const char *dist_path, const cha
     std::vector<int32_t> stab_num;
     int score = 0;
     if (n >= 10) {
-        const double low = std::max(0.3, std::ceil(10.0 / n * 10) / 10);
+        const std::vector<SubsampleStep> steps = subsample_steps(n);
         Splits sp;
         struct Run { size_t first; uint32_t gmax; };
         std::vector<Run> runs;
         std::vector<int32_t> p, sub;
-        for (uint32_t pi = 0;; ++pi) {
-            const double prop = low + pi * 0.1;
-            if (!(prop <= 1 + 1e-10)) break;
-            const uint32_t size = std::min(n, (uint32_t)std::floor(n * prop));
+        for (uint32_t pi = 0; pi < steps.size(); ++pi) {
+            const double prop = steps[pi].prop;
+            const uint32_t size = steps[pi].size;
             for (int32_t it = 0; it < o.stability_iters; ++it) {
                 const uint64_t r = 1 + 1024ull * pi + (uint64_t)it;
                 permutation(o.seed, r << 32 | 0xffffffffull, n, p);
@@ -436,6 +454,214 @@ extern "C" int msnv_cluster_file(msnv_ctx *ctx, const char *dist_path, const cha
     if (result) {
         result[0] = gmax <= 1 ? MSNV_CLUSTER_MEDOID_FAILED : one ? MSNV_CLUSTER_NONE : MSNV_CLUSTER_OK;
         result[1] = one ? 1 : n_big; result[2] = n; result[4] = score; result[5] = optimalk; result[6] = (int64_t)n_tasks;
+    }
+    if (ms_kernel) *ms_kernel = ms;
+    return MSNV_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- the stability of each cluster's membership
+// getClusMembStability -> clusterAssignSubsample -> getClusMembStabScore (clusteringStability.R:129-148, :170-176, :224-237).  On the host: the
+// draws, the quotients inter / union of the integers the device returns, R's mean() of them, the two counts, the score and the files.
+namespace msnv {
+namespace {
+
+// the members clustered, then every subset re-clustered and matched: the input is valid.  best: [n_sets][k][2]
+int boot_run(msnv_ctx *ctx, const ClusterDev &dev, const std::vector<int32_t> &members, uint32_t k, const std::vector<uint32_t> &set_m, const std::vector<int32_t> &set_pos,
+             int32_t *medoids, int32_t *cluster, std::vector<int32_t> &best, double *ms) {
+    std::vector<uint32_t> m{(uint32_t)members.size()};
+    m.insert(m.end(), set_m.begin(), set_m.end());
+    std::vector<int32_t> idx(members);
+    idx.reserve(members.size() + set_pos.size());
+    for (int32_t p : set_pos) idx.push_back(members[p]);
+    best.assign(set_m.size() * k * 2, 0);
+    return dev_cluster_boot(dev, set_m.size(), m.data(), k, idx.data(), set_pos.data(), ctx->stream, medoids, cluster, best.data(), ms);
+}
+
+struct MembRow { bool na; double jaccard, recover; };                  // one (proportion, cluster) of _clusMembStability.tab
+
+void r_value(double v, std::string &out) {                             // r_double, and Inf as R writes it
+    if (std::isinf(v)) out += v > 0 ? "Inf" : "-Inf";
+    else r_double(v, out);
+}
+
+// R's three-valued logic: 0 FALSE, 1 TRUE, 2 NA
+int above3(const MembRow *r, double v, double thr) { return (!r || r->na || v != v) ? 2 : v > thr ? 1 : 0; }
+int and3(int a, int b) { return (a == 0 || b == 0) ? 0 : (a == 2 || b == 2) ? 2 : 1; }
+
+// getClusMembStabScore of cluster j (0-based): 1 Low, 2 Medium, 3 High, 0 NA
+int memb_score(const std::vector<SubsampleStep> &steps, const std::vector<MembRow> &rows, uint32_t k, uint32_t j) {
+    auto term = [&](long tenth, double thr) {
+        const MembRow *r = nullptr;
+        for (size_t pi = 0; pi < steps.size() && !r; ++pi) if (std::lround(steps[pi].prop * 10.0) == tenth) r = &rows[pi * k + j];
+        return and3(above3(r, r ? r->recover : 0.0, thr), above3(r, r ? r->jaccard : 0.0, thr));
+    };
+    const int at90 = term(9, 0.8), at70 = term(7, 0.9);
+    return (at90 == 2 || at70 == 2) ? 0 : 1 + at90 + at70;
+}
+
+// <species>_mann_clusNumStability.tab as msnv_cluster_file writes it; num < 0 = NA
+int read_num_stability(const char *path, std::vector<double> &prop, std::vector<int32_t> &num) {
+    FILE *in = fopen(path, "r");
+    if (!in) return fail(MSNV_EIO, "Cannot open %s: %s", path, strerror(errno));
+    char *line = nullptr; size_t cap = 0; ssize_t len;
+    uint64_t lineno = 0;
+    int rc = MSNV_OK;
+    while (rc == MSNV_OK && (len = getline(&line, &cap, in)) >= 0) {
+        ++lineno;
+        while (len && (line[len - 1] == '\n' || line[len - 1] == '\r')) line[--len] = 0;
+        if (lineno == 1 || len == 0) continue;
+        char *e = nullptr;
+        const double p = strtod(line, &e);
+        if (e == line || *e != '\t') { rc = fail(MSNV_EFORMAT, "%s:%llu: a proportion and a cluster number are expected", path, (unsigned long long)lineno); break; }
+        const char *cell = e + 1;
+        long v = -1;
+        if (strcmp(cell, "NA") != 0) {
+            v = strtol(cell, &e, 10);
+            if (e == cell || *e || v < 0 || v > INT32_MAX) { rc = fail(MSNV_EFORMAT, "%s:%llu: cluster number '%s'", path, (unsigned long long)lineno, cell); break; }
+        }
+        prop.push_back(p); num.push_back((int32_t)v);
+    }
+    free(line);
+    fclose(in);
+    return rc;
+}
+
+const char *const SCORE_NAMES[4] = {"NA", "Low", "Medium", "High"};
+
+}  // namespace
+}  // namespace msnv
+
+extern "C" void msnv_membstab_opts_default(msnv_membstab_opts *o) { if (o) *o = msnv_membstab_opts{1, 100, 0}; }
+
+extern "C" int msnv_cluster_boot(msnv_ctx *ctx, int32_t n, const double *dist, int32_t m, const int32_t *members, int32_t k, int64_t n_sets, const int32_t *set_m,
+                                 const int32_t *set_pos, int32_t *medoids, int32_t *cluster, int32_t *best_inter, int32_t *best_union, double *ms_kernel) {
+    clear_error();
+    if (!ctx || !dist || !members || !medoids || !cluster || n_sets < 0 || (n_sets && (!set_m || !set_pos || !best_inter || !best_union)))
+        return fail(MSNV_EINVAL, "msnv_cluster_boot: NULL argument or a negative count");
+    if (ms_kernel) *ms_kernel = 0;
+    if (int rc = check_matrix("msnv_cluster_boot", n, dist)) return rc;
+    if (m < 2 || m > n) return fail(MSNV_EDOMAIN, "msnv_cluster_boot: %d members of %d samples (2 <= m <= n)", m, n);
+    for (int32_t a = 0; a < m; ++a)
+        if (members[a] < 0 || members[a] >= n || (a && members[a] <= members[a - 1]))
+            return fail(MSNV_EDOMAIN, "msnv_cluster_boot: member %d is sample %d (0 <= sample < %d, ascending)", a, members[a], n);
+    if (k < 1 || k > (int32_t)CLUSTER_BOOT_MAX_K || k >= m) return fail(MSNV_EDOMAIN, "msnv_cluster_boot: k = %d with %d members (1 <= k <= %u, k < m)", k, m, CLUSTER_BOOT_MAX_K);
+    std::vector<int64_t> seen((size_t)m, -1);
+    std::vector<uint32_t> sm((size_t)n_sets);
+    uint64_t off = 0;
+    for (int64_t t = 0; t < n_sets; ++t) {
+        if (set_m[t] <= k || set_m[t] > m) return fail(MSNV_EDOMAIN, "msnv_cluster_boot: subset %lld has %d entries (k = %d < entries <= m = %d)", (long long)t, set_m[t], k, m);
+        for (int32_t e = 0; e < set_m[t]; ++e) {
+            const int32_t p = set_pos[off + e];
+            if (p < 0 || p >= m) return fail(MSNV_EDOMAIN, "msnv_cluster_boot: subset %lld lists position %d of %d", (long long)t, p, m);
+            if (seen[p] == t) return fail(MSNV_EDOMAIN, "msnv_cluster_boot: subset %lld lists position %d twice", (long long)t, p);
+            seen[p] = t;
+        }
+        sm[t] = (uint32_t)set_m[t]; off += sm[t];
+    }
+    if (int rc = dev_set_device(ctx->device)) return rc;
+    ClusterDev dev;
+    if (int rc = dev_cluster_upload(dev, dist, (uint32_t)n, ctx->stream)) return rc;
+    std::vector<int32_t> best;
+    if (int rc = boot_run(ctx, dev, std::vector<int32_t>(members, members + m), (uint32_t)k, sm, std::vector<int32_t>(set_pos, set_pos + off), medoids, cluster, best, ms_kernel)) return rc;
+    for (size_t i = 0; i < (size_t)n_sets * k; ++i) { best_inter[i] = best[2 * i]; best_union[i] = best[2 * i + 1]; }
+    return MSNV_OK;
+}
+
+extern "C" int msnv_membership_stability_file(msnv_ctx *ctx, const char *dist_used_path, const char *clus_num_stability_path, const char *species, int32_t k,
+                                              const char *out_dir, const msnv_membstab_opts *opts, int64_t result[8], double *ms_kernel) {
+    clear_error();
+    if (!ctx || !dist_used_path || !species || !out_dir) return fail(MSNV_EINVAL, "msnv_membership_stability_file: NULL argument");
+    msnv_membstab_opts o;
+    msnv_membstab_opts_default(&o);
+    if (opts) o = *opts;
+    if (o.reserved != 0 || o.boot_iters < 1 || o.boot_iters > 1024)
+        return fail(MSNV_EINVAL, "msnv_membership_stability_file: boot_iters = %d, reserved = %d (1..1024 iterations, reserved 0)", o.boot_iters, o.reserved);
+    if (result) for (int i = 0; i < 8; ++i) result[i] = 0;
+    if (ms_kernel) *ms_kernel = 0;
+    double ms = 0;
+    std::vector<std::string> names;
+    std::vector<double> d;
+    if (int rc = read_dist(dist_used_path, names, d, true)) return rc;
+    const uint32_t n = (uint32_t)names.size();
+    if (names.size() < 10) {                                           // clustering.R:359: the stability is rated when nSamples >= 10
+        if (result) { result[0] = MSNV_MEMBSTAB_NOT_RATED; result[1] = k; result[2] = n; }
+        return MSNV_OK;
+    }
+    if (int rc = check_matrix(dist_used_path, (int64_t)names.size(), d.data())) return rc;
+    if (k < 1 || k > (int32_t)CLUSTER_BOOT_MAX_K || (uint32_t)k >= n)
+        return fail(MSNV_EDOMAIN, "msnv_membership_stability_file: k = %d with %u samples (1 <= k <= %u, k < samples)", k, n, CLUSTER_BOOT_MAX_K);
+    int num_score = 0;
+    if (clus_num_stability_path) {
+        std::vector<double> prop;
+        std::vector<int32_t> num;
+        if (int rc = read_num_stability(clus_num_stability_path, prop, num)) return rc;
+        num_score = stab_score(prop, num);
+    }
+    if (int rc = dev_set_device(ctx->device)) return rc;
+    if (int rc = make_dir(out_dir)) return rc;
+
+    // ---- the subsets of every proportion that can be clustered, in one batch
+    const uint32_t K = (uint32_t)k, B = (uint32_t)o.boot_iters;
+    const std::vector<SubsampleStep> steps = subsample_steps(n);
+    std::vector<int32_t> members(n), set_pos, p;
+    for (uint32_t i = 0; i < n; ++i) members[i] = (int32_t)i;
+    std::vector<uint32_t> set_m;
+    for (uint32_t pi = 0; pi < steps.size(); ++pi) {
+        if (steps[pi].size <= K) continue;                             // pam stops at k >= n: rows of NA
+        for (uint32_t b = 0; b < B; ++b) {
+            permutation(o.seed, 1ull << 62 | (uint64_t)pi << 32 | b, n, p);
+            set_m.push_back(steps[pi].size);
+            set_pos.insert(set_pos.end(), p.begin(), p.begin() + steps[pi].size);
+        }
+    }
+    ClusterDev dev;
+    if (int rc = dev_cluster_upload(dev, d.data(), n, ctx->stream)) return rc;
+    std::vector<int32_t> medoids(K), clus(n), best;
+    if (int rc = boot_run(ctx, dev, members, K, set_m, set_pos, medoids.data(), clus.data(), best, &ms)) return rc;
+
+    // ---- per proportion and cluster: mean Jaccard, recovered / dissolved
+    std::vector<MembRow> rows(steps.size() * K, MembRow{true, 0.0, 0.0});
+    std::vector<double> jac(B);
+    size_t t0 = 0;
+    for (uint32_t pi = 0; pi < steps.size(); ++pi) {
+        if (steps[pi].size <= K) continue;
+        for (uint32_t j = 0; j < K; ++j) {
+            uint32_t recovered = 0, dissolved = 0;
+            for (uint32_t b = 0; b < B; ++b) {
+                const int32_t *pair = &best[((t0 + b) * K + j) * 2];
+                jac[b] = (double)pair[0] / (double)pair[1];
+                recovered += jac[b] >= 0.75; dissolved += jac[b] <= 0.5;
+            }
+            rows[(size_t)pi * K + j] = MembRow{false, r_mean(jac.data(), B), (double)recovered / (double)dissolved};
+        }
+        t0 += B;
+    }
+    std::vector<uint32_t> sizes(K, 0);
+    for (int32_t c : clus) ++sizes[c - 1];
+
+    // ---- the files
+    const std::string prefix = std::string(out_dir) + "/" + species + "_mann";
+    std::string text = "clusterID\tnSamplesInCluster\tsubsampleProp\tclusterStabilityJaccardMean\tclusterStabilityPropRecover\n";
+    for (uint32_t pi = 0; pi < steps.size(); ++pi)
+        for (uint32_t j = 0; j < K; ++j) {
+            const MembRow &r = rows[(size_t)pi * K + j];
+            text += std::to_string(j + 1) + "\t" + std::to_string(sizes[j]) + "\t";
+            r_double(steps[pi].prop, text);
+            if (r.na) text += "\tNA\tNA\n";
+            else { text.push_back('\t'); r_value(r.jaccard, text); text.push_back('\t'); r_value(r.recover, text); text.push_back('\n'); }
+        }
+    if (int rc = write_text(prefix + "_clusMembStability.tab", text)) return rc;
+    int lowest = 3;
+    text = std::string("name\tscore\nnumClusters\t") + SCORE_NAMES[num_score] + "\n";
+    for (uint32_t j = 0; j < K; ++j) {
+        const int sc = memb_score(steps, rows, K, j);
+        lowest = std::min(lowest, sc);
+        text += "clust" + std::to_string(j + 1) + "\t" + SCORE_NAMES[sc] + "\n";
+    }
+    if (int rc = write_text(prefix + "_stabilityAssessment.tab", text)) return rc;
+    if (result) {
+        result[0] = MSNV_MEMBSTAB_OK; result[1] = k; result[2] = n; result[3] = (int64_t)steps.size(); result[4] = (int64_t)set_m.size();
+        result[5] = num_score; result[6] = lowest;
     }
     if (ms_kernel) *ms_kernel = ms;
     return MSNV_OK;

@@ -4,6 +4,8 @@
 //   msnv_ps_splits_k     predStrengthCustom's tail (:176-201) of many splits: classify each half by the other half's medoids, count the
 //                        co-classified pairs, prederr = (min ps[1,] + min ps[2,]) / 2; one workgroup per split
 //   msnv_freq_bands_k    computeSnvFreqStats (computeSnvFreqStats.R:1-24): per sample column, cells outside 20/80, 10/90, 5/95 and cells that count
+//   msnv_boot_match_k    fpc::clusterboot(bootmethod = "subset")'s comparison (clusteringStability.R:129-148): per re-clustered subset, the contingency
+//                        table of (original cluster, new cluster) and each original cluster's best Jaccard pair; one workgroup per subset
 //
 // One route.  A task's m x m sub-matrix is never gathered: d(i, j) is read from the full n x n matrix through the task's index list, as
 // D[col[j] * n + col[i]] -- the matrix is symmetric, so the lanes of a wavefront (different i or h, the same j) read one row of it.  At the
@@ -219,6 +221,47 @@ __global__ void __launch_bounds__(PAM_THREADS) msnv_ps_splits_k(const double *__
     }
 }
 
+// Task 0 is the original partition (its list = the members), task s + 1 re-clusters subset s; pos holds, packed in the subsets' order, each entry's
+// position in task 0's list.  Per subset: tab[j][c] = entries in original cluster j and new cluster c (LDS atomics on integers: their order does
+// not matter), row and column sums, then one lane per original cluster walks the new clusters in ascending order and keeps the FIRST largest
+// inter / union, compared as inter * best_union > best_inter * union (at most 4096 * 8192, inside 32 bits).  A new cluster without a member (its
+// medoid is a duplicate of an earlier one) is passed over, so a union is never 0.  best[(s * k + j) * 2] = inter, + 1 = union.
+// A workgroup per subset, not a wavefront: a subset has up to 4096 entries (16 per lane here, 64 per lane of one wavefront), the PAM launch before
+// it is shaped the same way, and the statics are one table per workgroup with no bookkeeping of which wavefront owns which slice.
+__global__ void __launch_bounds__(PAM_THREADS) msnv_boot_match_k(const PamTask *__restrict__ tasks, unsigned long long n_sets, const int32_t *__restrict__ pos,
+                                                                 const int32_t *__restrict__ clus, int32_t *__restrict__ best) {
+    __shared__ uint32_t tab[CLUSTER_BOOT_MAX_K * CLUSTER_BOOT_MAX_K], rowsum[CLUSTER_BOOT_MAX_K], colsum[CLUSTER_BOOT_MAX_K];
+    const uint32_t tid = threadIdx.x;
+    const PamTask O = tasks[0];
+    const uint32_t k = O.k;
+    for (unsigned long long s = blockIdx.x; s < n_sets; s += gridDim.x) {
+        const PamTask T = tasks[s + 1];
+        __syncthreads();                                               // the subset before is done with the table
+        for (uint32_t c = tid; c < k * k; c += PAM_THREADS) tab[c] = 0;
+        __syncthreads();
+        for (uint32_t e = tid; e < T.m; e += PAM_THREADS) {
+            const uint32_t j = (uint32_t)clus[O.off + (uint32_t)pos[T.off - O.m + e]] - 1, c = (uint32_t)clus[T.off + e] - 1;
+            atomicAdd(&tab[j * k + c], 1u);
+        }
+        __syncthreads();
+        if (tid < k) {
+            uint32_t r = 0, cs = 0;
+            for (uint32_t c = 0; c < k; ++c) { r += tab[tid * k + c]; cs += tab[c * k + tid]; }
+            rowsum[tid] = r; colsum[tid] = cs;
+        }
+        __syncthreads();
+        if (tid < k) {
+            uint32_t bi = 0, bu = 0;
+            for (uint32_t c = 0; c < k; ++c) {
+                if (colsum[c] == 0) continue;
+                const uint32_t inter = tab[tid * k + c], uni = rowsum[tid] + colsum[c] - inter;
+                if (bu == 0 || inter * bu > bi * uni) { bi = inter; bu = uni; }
+            }
+            best[(s * k + tid) * 2] = (int32_t)bi; best[(s * k + tid) * 2 + 1] = (int32_t)bu;
+        }
+    }
+}
+
 // counts[sample][4]: cells < 20 or > 80, < 10 or > 90, < 5 or > 95, cells that count (not NaN: read_freq turns -1 and NA into NaN).
 // A thread per sample column, a block row per FREQ_ROWS positions: the lanes of a wavefront read one table row.
 constexpr uint32_t FREQ_ROWS = 512;
@@ -255,9 +298,13 @@ struct Timer {
 
 constexpr uint64_t BATCH_ENTRIES = 1ull << 26;                         // list entries of one launch: 256 MiB of indices, as much of cluster ids
 
-// One launch of the PAM kernel over tasks[t0, t1) (their offsets rebased to the batch) and, when splits are asked for, one of the tail kernel.
+// msnv_cluster_boot's second launch: the batch is task 0 = the original partition and one task per subset (the whole batch, never a part of one)
+struct Boot { const int32_t *pos; int32_t *med0, *clus0, *best; };
+
+// One launch of the PAM kernel over tasks[t0, t1) (their offsets rebased to the batch) and, when splits are asked for, one of the tail kernel; with
+// boot, one of the matching kernel over the cluster ids the PAM kernel left on the device.
 int run_batch(const ClusterDev &c, const std::vector<PamTask> &tasks, uint64_t t0, uint64_t t1, const int32_t *idx, bool splits, hipStream_t st,
-              int32_t *med, int32_t *clus, int32_t *swaps, double *prederr, float &ms_sum) {
+              int32_t *med, int32_t *clus, int32_t *swaps, double *prederr, float &ms_sum, const Boot *boot = nullptr) {
     const uint64_t nt = t1 - t0, off0 = tasks[t0].off, med0 = tasks[t0].med_off;
     const uint64_t n_idx = tasks[t1 - 1].off + tasks[t1 - 1].m - off0, n_med = tasks[t1 - 1].med_off + tasks[t1 - 1].k - med0;
     std::vector<PamTask> local(tasks.begin() + t0, tasks.begin() + t1);
@@ -268,7 +315,7 @@ int run_batch(const ClusterDev &c, const std::vector<PamTask> &tasks, uint64_t t
         if (splits && !(t & 1)) max_len = std::max(max_len, local[t].m + local[t + 1].m);
     }
     const uint64_t ns = splits ? nt / 2 : 0;
-    Buf d_tasks, d_idx, d_med, d_clus, d_swaps, d_err, d_pe;
+    Buf d_tasks, d_idx, d_med, d_clus, d_swaps, d_err, d_pe, d_pos, d_best;
     HIP_TRY(hipMalloc(&d_tasks.p, nt * sizeof(PamTask)));
     HIP_TRY(hipMalloc(&d_idx.p, n_idx * 4));
     HIP_TRY(hipMalloc(&d_med.p, n_med * 4));
@@ -279,6 +326,12 @@ int run_batch(const ClusterDev &c, const std::vector<PamTask> &tasks, uint64_t t
     HIP_TRY(hipMemcpyAsync(d_idx.p, idx + off0, n_idx * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(d_err.p, 0, 16, st));
     if (ns) HIP_TRY(hipMalloc(&d_pe.p, ns * 8));
+    const uint64_t n_sets = boot ? nt - 1 : 0, n_pos = boot ? n_idx - local[0].m : 0, n_best = n_sets * max_k * 2;
+    if (n_sets) {
+        HIP_TRY(hipMalloc(&d_pos.p, n_pos * 4));
+        HIP_TRY(hipMalloc(&d_best.p, n_best * 4));
+        HIP_TRY(hipMemcpyAsync(d_pos.p, boot->pos, n_pos * 4, hipMemcpyHostToDevice, st));
+    }
     const size_t lds_pam = (size_t)max_m * 28, lds_ps = (size_t)max_len * 4 + (size_t)max_k * 24;
     if (lds_pam > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)msnv_pam_tasks_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pam));
     if (lds_ps > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)msnv_ps_splits_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ps));
@@ -295,9 +348,19 @@ int run_batch(const ClusterDev &c, const std::vector<PamTask> &tasks, uint64_t t
                            (unsigned long long)ns, d_idx.as<int32_t>(), max_len, d_med.as<int32_t>(), d_clus.as<int32_t>(), d_pe.as<double>());
         HIP_TRY(hipGetLastError());
     }
+    if (n_sets) {
+        hipLaunchKernelGGL(msnv_boot_match_k, dim3((uint32_t)std::min<uint64_t>(n_sets, dev_resident_workgroups(8))), dim3(PAM_THREADS), 0, st, d_tasks.as<PamTask>(),
+                           (unsigned long long)n_sets, d_pos.as<int32_t>(), d_clus.as<int32_t>(), d_best.as<int32_t>());
+        HIP_TRY(hipGetLastError());
+    }
     HIP_TRY(hipEventRecord(tm.e1, st));
     uint32_t err = 0;
     HIP_TRY(hipMemcpyAsync(&err, d_err.p, 4, hipMemcpyDeviceToHost, st));
+    if (boot) {
+        HIP_TRY(hipMemcpyAsync(boot->med0, d_med.p, (size_t)local[0].k * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(boot->clus0, d_clus.p, (size_t)local[0].m * 4, hipMemcpyDeviceToHost, st));
+        if (n_sets) HIP_TRY(hipMemcpyAsync(boot->best, d_best.p, n_best * 4, hipMemcpyDeviceToHost, st));
+    }
     if (med) HIP_TRY(hipMemcpyAsync(med + med0, d_med.p, n_med * 4, hipMemcpyDeviceToHost, st));
     if (clus) HIP_TRY(hipMemcpyAsync(clus + off0, d_clus.p, n_idx * 4, hipMemcpyDeviceToHost, st));
     if (swaps) HIP_TRY(hipMemcpyAsync(swaps + t0, d_swaps.p, nt * 4, hipMemcpyDeviceToHost, st));
@@ -344,6 +407,19 @@ int dev_pam_tasks(const ClusterDev &c, uint64_t n_tasks, const uint32_t *m, cons
     uint64_t off = 0, med_off = 0;
     for (uint64_t t = 0; t < n_tasks; ++t) { tasks[t] = PamTask{off, med_off, m[t], k[t]}; off += m[t]; med_off += k[t]; }
     return run_all(c, tasks, idx, false, stream, med, clus, swaps, nullptr, ms_kernel);
+}
+
+int dev_cluster_boot(const ClusterDev &c, uint64_t n_sets, const uint32_t *m, uint32_t k, const int32_t *idx, const int32_t *pos, void *stream, int32_t *med0,
+                     int32_t *clus0, int32_t *best, double *ms_kernel) {
+    std::vector<PamTask> tasks(n_sets + 1);
+    uint64_t off = 0;
+    for (uint64_t t = 0; t <= n_sets; ++t) { tasks[t] = PamTask{off, t * k, m[t], k}; off += m[t]; }
+    if (off > BATCH_ENTRIES) return fail(MSNV_ECAPACITY, "cluster boot: %llu list entries in one call (at most %llu)", (unsigned long long)off, (unsigned long long)BATCH_ENTRIES);
+    const Boot boot{pos, med0, clus0, best};
+    float ms_sum = 0;
+    if (int rc = run_batch(c, tasks, 0, tasks.size(), idx, false, (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr, ms_sum, &boot)) return rc;
+    if (ms_kernel) *ms_kernel += ms_sum;
+    return MSNV_OK;
 }
 
 int dev_pred_strength(const ClusterDev &c, uint64_t n_splits, const uint32_t *len, const uint32_t *k, const int32_t *idx, void *stream, double *prederr, double *ms_kernel) {

@@ -263,6 +263,7 @@ int dev_corr_stats(int method, uint64_t n, const double *est, const int32_t *n_o
 
 // cluster.cpp + cluster_k.hip: subpopr's computeClusters.  The distance matrix of one species, resident on the device for every PAM task run on it
 constexpr uint32_t CLUSTER_MAX_SAMPLES = 4096, PAM_MAX_SWAPS = 65536;   // a task that swaps more often than this is refused, not waited for
+constexpr uint32_t CLUSTER_BOOT_MAX_K = 32;                             // msnv_cluster_boot: the k x k table of one subset is 4 KB of LDS
 struct ClusterDev {
     double *dist = nullptr; uint32_t n = 0;
     ClusterDev() = default;
@@ -273,6 +274,10 @@ int dev_cluster_upload(ClusterDev &c, const double *dist, uint32_t n, void *stre
 // tasks and splits as include/msnv.h packs them; a split is a list of len global indices whose first floor(len / 2) entries are half 1
 int dev_pam_tasks(const ClusterDev &c, uint64_t n_tasks, const uint32_t *m, const uint32_t *k, const int32_t *idx, void *stream, int32_t *med, int32_t *clus,
                   int32_t *swaps, double *ms_kernel);
+// task 0 = m[0] members clustered into k, then n_sets subsets (m[1..]; idx as for dev_pam_tasks, pos = each subset entry's position in task 0's list):
+// med0[k], clus0[m[0]] and best[n_sets][k][2] = (inter, union) of every original cluster's best match; two launches
+int dev_cluster_boot(const ClusterDev &c, uint64_t n_sets, const uint32_t *m, uint32_t k, const int32_t *idx, const int32_t *pos, void *stream, int32_t *med0,
+                     int32_t *clus0, int32_t *best, double *ms_kernel);
 int dev_pred_strength(const ClusterDev &c, uint64_t n_splits, const uint32_t *len, const uint32_t *k, const int32_t *idx, void *stream, double *prederr, double *ms_kernel);
 int dev_freq_bands(const double *rows, uint64_t n_pos, uint32_t n_samples, void *stream, uint64_t *counts, double *ms_kernel);   // counts[sample][4]
 

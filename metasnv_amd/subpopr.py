@@ -15,6 +15,15 @@
       <species>.filtered.mann.dist (+ <species>.filtered.freq)  ->  <outDir>[/noClustering|/clustMedoidDefnFailed]/<species>_mann_{PS_values.tab,
       distMatrixUsedForClustMedoidDefns.txt,clustering.tab,clusNumStability.tab} and <species>_freq_composition.tab
 
+  clusterMembStability.py <species> <dir> [--k N] [--ps-cut X] [--seed N] [--boot N]
+      (src/subpopr/R/clusteringStability.R getClusMembStability and getClusMembStabScore; <dir> = clusterSubpops.py's outDir or its noClustering/)
+      <dir>/<species>_mann_distMatrixUsedForClustMedoidDefns.txt (+ _PS_values.tab, _clusNumStability.tab)  ->  <dir>/<species>_mann_{clusMembStability.tab,
+      stabilityAssessment.tab}
+
+  summariseClustering.py <outDir>
+      (src/subpopr/R/summariseClusteringResults.R summariseClusteringResultsForAll, from the files above instead of the .rds; host only)
+      ->  <outDir>/summary_clustering.csv
+
   writeGenotypeFreqs.py <species> <clustering.tab> <freq_file> <outDir> [--uniq-threshold X]
       (src/subpopr/R/writeGenotypeFreqs.R writeGenotypeFreqs with computeUniquePosPerCluster)
       <species>_mann_clustering.tab + <species>.filtered.freq  ->  <outDir>/<species>_<cluster>_hap_positions.tab, <species>_hap_out.txt and
@@ -30,10 +39,11 @@
       <outDir>/<species>_extended_clustering_wFreq.tab + a species x samples abundance table  ->  <outDir>/<species>_allClust_relativeAbund.tab and
       <species>_clust_<x>_hap_coverage_extended_normed.tab
 
-The first and the last are text filters (native, no device work); the frequencies of the second, the correlations of the third, every PAM run
-of the fourth, the fifth's walk over the frequency table and the sixth's counts and medians per sample are computed on the GPU
-(msnv_snv_allele_freq, msnv_gene_corr, msnv_corr_stats, msnv_pam_tasks, msnv_pred_strength, msnv_genotype_rows, msnv_subpop_profile_columns)
-and there is no CPU fallback for them."""
+getGenotypingSNVSubset.py and writeSubpopAbund.py are text filters (native, no device work) and summariseClustering.py reads and writes small
+tables in Python; the frequencies of convertSNVtoAlleleFreq.py, the correlations, every PAM run of clusterSubpops.py and clusterMembStability.py
+with the matching of the re-clustered subsets, writeGenotypeFreqs.py's walk over the frequency table and profileSubpops.py's counts and medians
+per sample are computed on the GPU (msnv_snv_allele_freq, msnv_gene_corr, msnv_corr_stats, msnv_pam_tasks, msnv_pred_strength, msnv_cluster_boot,
+msnv_genotype_rows, msnv_subpop_profile_columns) and there is no CPU fallback for them."""
 import ctypes as C
 import glob
 import os
@@ -297,6 +307,183 @@ def cluster_subpops_main(argv=None):                           # clustering.R:20
         print("Species " + species + ": " + str(res["n_clusters"]) + " cluster(s) from " + str(res["n_samples"]) + " samples; cluster number stability: "
               + ("not rated", "Low", "Medium", "High")[res["stability_score"]])
     return res
+
+
+def cluster_boot(ctx, dist, members, k, sets):
+    """The PAM partition of dist's samples `members` (ascending indices) into k clusters, and how well each of its clusters is found again when
+    every subset of `sets` (lists of distinct positions into members, clustered in the order given) is clustered on its own (msnv_cluster_boot).
+    Returns cluster (1..k per member), medoids (positions in members), pairs [n_sets][k][2] = (inter, union) of every original cluster's best
+    Jaccard match in every subset, and the kernels' ms."""
+    import numpy as np
+    from ._lib import lib, check
+    dist = np.ascontiguousarray(dist, dtype=np.float64)
+    if dist.ndim != 2 or dist.shape[0] != dist.shape[1]:
+        raise ValueError("cluster_boot: dist must be a square matrix")
+    members = np.ascontiguousarray(members, dtype=np.int32).ravel()
+    lists = [np.asarray(s, dtype=np.int32).ravel() for s in sets]
+    set_m = np.array([len(s) for s in lists], dtype=np.int32)
+    pos = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, dtype=np.int32), dtype=np.int32)
+    k = int(k)
+    med = np.zeros(max(k, 1), dtype=np.int32)
+    clus = np.zeros(max(members.size, 1), dtype=np.int32)
+    inter = np.zeros(max(len(lists) * max(k, 0), 1), dtype=np.int32)
+    union = np.zeros_like(inter)
+    ms = C.c_double()
+    check(lib.msnv_cluster_boot(ctx._h, dist.shape[0], _dptr(dist), members.size, _iptr(members), k, len(lists), _iptr(set_m), _iptr(pos), _iptr(med), _iptr(clus),
+                                _iptr(inter), _iptr(union), C.byref(ms)))
+    nk = len(lists) * k
+    pairs = np.stack([inter[:nk], union[:nk]], axis=1).reshape(len(lists), k, 2)
+    return {"cluster": clus[:members.size].copy(), "medoids": med[:k].copy(), "pairs": pairs, "ms_kernel": ms.value}
+
+
+STABILITY_SCORES = ("NA", "Low", "Medium", "High")
+
+
+def membership_stability_file(ctx, dist_used_path, species, k, out_dir, clus_num_stability_path=None, seed=None, boot_iters=None):
+    """The stage on files (msnv_membership_stability_file): writes <species>_mann_clusMembStability.tab and _stabilityAssessment.tab into out_dir.
+    Returns a dict: status (_lib.MEMBSTAB_*), k, n_samples, n_proportions, n_sets, num_clusters_score and lowest_cluster_score (1 Low, 2 Medium,
+    3 High, 0 NA), ms_kernel."""
+    from ._lib import lib, check, MembStabOpts
+    o = MembStabOpts()
+    lib.msnv_membstab_opts_default(C.byref(o))
+    if seed is not None:
+        o.seed = int(seed)
+    if boot_iters is not None:
+        o.boot_iters = int(boot_iters)
+    res = (C.c_int64 * 8)()
+    ms = C.c_double()
+    check(lib.msnv_membership_stability_file(ctx._h, dist_used_path.encode(), None if clus_num_stability_path is None else clus_num_stability_path.encode(),
+                                             species.encode(), int(k), out_dir.encode(), C.byref(o), res, C.byref(ms)))
+    return {"status": res[0], "k": res[1], "n_samples": res[2], "n_proportions": res[3], "n_sets": res[4], "num_clusters_score": res[5],
+            "lowest_cluster_score": res[6], "ms_kernel": ms.value}
+
+
+def _ps_values(path):
+    """<species>_mann_PS_values.tab: a header "x", then k <TAB> mean prediction strength.  Returns {k: value}."""
+    out = {}
+    with open(path) as f:
+        for ln in f.read().splitlines()[1:]:
+            if ln:
+                a, b = ln.split("\t")
+                out[int(a)] = float(b)
+    return out
+
+
+def clusters_from_ps_values(directory, species, ps_cut=0.8):
+    """The k msnv_cluster_file ran PAM with: the largest k whose prediction strength exceeds the cut; 1 when no PS values were written."""
+    path = os.path.join(directory, species + "_mann_PS_values.tab")
+    if not os.path.exists(path):
+        return 1
+    return max([k for k, v in _ps_values(path).items() if v > ps_cut] or [1])
+
+
+def cluster_memb_stability_main(argv=None):                    # clustering.R:356-381 getClusteringResult, the membership half
+    import argparse
+    ap = argparse.ArgumentParser(prog="clusterMembStability.py", description="Rate how stable each subspecies cluster's membership is (subpopr's getClusMembStability) on the GPU.")
+    ap.add_argument("species", metavar="SPECIES")
+    ap.add_argument("dir", metavar="DIR", help="holds the species' files of clusterSubpops.py: its output directory or the noClustering/ below it")
+    ap.add_argument("--k", type=int, default=None, metavar="N", help="number of clusters (default: from <species>_mann_PS_values.tab)")
+    ap.add_argument("--ps-cut", type=float, default=0.8, metavar="X", help="prediction-strength cutoff used to pick k (0.8)")
+    ap.add_argument("--seed", type=int, default=None, metavar="N")
+    ap.add_argument("--boot", type=int, default=None, metavar="N", help="subsets per proportion (100)")
+    a = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    dist_used = os.path.join(a.dir, a.species + "_mann_distMatrixUsedForClustMedoidDefns.txt")
+    if not os.path.exists(dist_used):
+        sys.exit("ERROR: missing input file: " + dist_used)
+    k = a.k if a.k is not None else clusters_from_ps_values(a.dir, a.species, a.ps_cut)
+    num_path = os.path.join(a.dir, a.species + "_mann_clusNumStability.tab")
+    from . import core
+    try:
+        ctx = core.Context(0)
+    except core._lib.MsnvError as e:
+        sys.exit("\nERROR:  {}\n\nSOLUTION: run on a node with an AMD Instinct GPU (there is no CPU fallback)\n".format(e))
+    try:
+        res = membership_stability_file(ctx, dist_used, a.species, k, a.dir, clus_num_stability_path=num_path if os.path.exists(num_path) else None,
+                                        seed=a.seed, boot_iters=a.boot)
+    except core._lib.MsnvError as e:
+        sys.exit("ERROR: {}".format(e))
+    finally:
+        ctx.close()
+    if res["status"] == core._lib.MEMBSTAB_NOT_RATED:
+        print("Species " + a.species + ": " + str(res["n_samples"]) + " samples, fewer than 10: cluster stability is not rated")
+    else:
+        print("Species " + a.species + ": " + str(k) + " cluster(s), " + str(res["n_sets"]) + " subsets of " + str(res["n_samples"]) + " samples re-clustered; lowest cluster "
+              "membership stability: " + STABILITY_SCORES[res["lowest_cluster_score"]])
+    return res
+
+
+def _csv_cell(v):
+    """write.csv(quote = TRUE): strings quoted (a quote doubled), numbers and NA bare."""
+    if v is None:
+        return "NA"
+    if isinstance(v, str):
+        return '"' + v.replace('"', '""') + '"'
+    if isinstance(v, float):
+        return "%.15g" % v
+    return str(v)
+
+
+def _table(path):
+    with open(path) as f:
+        return [ln.split("\t") for ln in f.read().splitlines()[1:] if ln]
+
+
+def summarise_clustering(out_dir):
+    """summariseClusteringResultsForAll (src/subpopr/R/summariseClusteringResults.R:1-65) from the stage's files instead of the .rds: writes
+    <out_dir>/summary_clustering.csv, one row per *_mann_clustering.tab of out_dir and out_dir/noClustering/.  Host only.  Returns the rows."""
+    suffix = "_mann_clustering.tab"
+    rels = [f for f in os.listdir(out_dir) if f.endswith(suffix)]
+    none_dir = os.path.join(out_dir, "noClustering")
+    if os.path.isdir(none_dir):
+        rels += ["noClustering/" + f for f in os.listdir(none_dir) if f.endswith(suffix)]
+    cols = ["speciesID", "speciesName", "numberOfSamplesUsedForClusterDetection", "numberOfClusters", "predictionStrengthValue", "confidenceInNumberOfClusters",
+            "confidencePerCluster", "clusterSizes", "detailedClusteringResultsFile"]
+    rows = []
+    for rel in sorted(rels, key=lambda r: r.encode()):
+        sub, name = os.path.split(rel)
+        species = name[:-len(suffix)]
+        prefix = os.path.join(out_dir, sub, species + "_mann")
+        row = dict.fromkeys(cols)
+        row["speciesID"] = species
+        if os.path.exists(prefix + "_distMatrixUsedForClustMedoidDefns.txt"):
+            row["numberOfSamplesUsedForClusterDetection"] = len(_table(prefix + "_distMatrixUsedForClustMedoidDefns.txt"))
+        if os.path.exists(prefix + "_clusMembStability.tab"):
+            memb = _table(prefix + "_clusMembStability.tab")
+            first = [r for r in memb if r[2] == memb[0][2]]                 # the rows of the first proportion: one per cluster
+            k = len(first)
+            row["clusterSizes"] = "-".join(r[1] for r in first)
+        else:
+            k = clusters_from_ps_values(os.path.join(out_dir, sub), species)
+        row["numberOfClusters"] = k
+        if os.path.exists(prefix + "_PS_values.tab"):
+            ps = _ps_values(prefix + "_PS_values.tab")
+            if k in ps:
+                row["predictionStrengthValue"] = float(round(ps[k], 4))
+        if os.path.exists(prefix + "_stabilityAssessment.tab"):
+            scores = dict(_table(prefix + "_stabilityAssessment.tab"))
+            num = scores.get("numClusters", "NA")
+            row["confidenceInNumberOfClusters"] = None if num == "NA" else num
+            row["confidencePerCluster"] = "-".join(scores.get("clust%d" % (j + 1), "NA") for j in range(k))
+        row["detailedClusteringResultsFile"] = "./" + (sub + "/" if sub else "") + species + "_detailedSpeciesReport.html"
+        rows.append(row)
+    text = ",".join(_csv_cell(c) for c in [""] + cols) + "\n"
+    for row in rows:
+        text += ",".join([_csv_cell(row["speciesID"])] + [_csv_cell(row[c]) for c in cols]) + "\n"
+    with open(os.path.join(out_dir, "summary_clustering.csv"), "w") as f:
+        f.write(text)
+    return rows
+
+
+def summarise_clustering_main(argv=None):                      # summariseClusteringResults.R:48-55 summariseClusteringResultsForAll
+    import argparse
+    ap = argparse.ArgumentParser(prog="summariseClustering.py", description="Write summary_clustering.csv for every species clustered into OUTDIR (subpopr's summariseClusteringResultsForAll).")
+    ap.add_argument("out_dir", metavar="OUTDIR")
+    a = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    if not os.path.isdir(a.out_dir):
+        sys.exit("ERROR: not a directory: " + a.out_dir)
+    rows = summarise_clustering(a.out_dir)
+    print(str(len(rows)) + " species summarised in " + os.path.join(a.out_dir, "summary_clustering.csv"))
+    return rows
 
 
 def genotype_rows(ctx, rows, clust, threshold=80.0):
