@@ -5,7 +5,8 @@ byte-equal.
 msnv_boot_match_k has one route: a workgroup of 256 lanes per subset, the k x k table in LDS.  The subset sizes are those where its entry loop and
 the PAM kernel's loops change shape: 2 and 3 (the smallest), 63 / 64 / 65 (a wavefront), 255 / 256 / 257 (the workgroup: one entry per lane, then
 two for lane 0), each with k = 1, 2, 15 and 32 where k < size.  The "dups" matrix has 10 distinct points, so at k = 15 and 32 medoids are
-duplicates of each other and new clusters stay empty."""
+duplicates of each other and new clusters stay empty.  One call has 1756 members (the PAM launch before the matching raises its LDS limit above
+48 KiB) and subsets of 1755, 900, 257 and 4 entries."""
 import ctypes as C
 import os
 
@@ -78,6 +79,21 @@ def test_a_batch_larger_than_the_grid_gives_each_set_its_own_result(ctx, kind):
     assert got["cluster"].tolist() == clus.tolist() and got["medoids"].tolist() == med.tolist()
     assert got["pairs"].tolist() == pairs[order].tolist()
     assert got["pairs"][0].tolist() == got["pairs"][-1].tolist()
+
+
+@pytest.mark.parametrize("kind", ["real1756", "integer1756"])
+def test_cluster_boot_on_a_long_list(ctx, kind):
+    # 1756 members: the PAM launch raises its LDS limit (28 bytes per member, 49 168), the subsets of 1755, 900, 257 and 4 entries share it, and
+    # the matching kernel's entry loop makes up to seven trips
+    d = cases.large_matrix(kind)
+    members = np.arange(1756, dtype=np.int32)
+    rng = np.random.default_rng(17)
+    sets = [rng.choice(1756, size=s, replace=False).astype(np.int32) for s in (1755, 900, 257, 4)]
+    got = subpopr.cluster_boot(ctx, d, members, 3, sets)
+    want = model.cluster_boot(d, members, 3, sets)
+    print("%s: %.1f ms in the kernels, pairs %s" % (kind, got["ms_kernel"], got["pairs"].tolist()))
+    assert got["pairs"].shape == (4, 3, 2) and same(got, want), kind
+    assert (got["pairs"][:, :, 1] > 0).all() and sorted(set(got["cluster"].tolist())) == [1, 2, 3]
 
 
 def test_the_whole_list_in_another_order_and_a_set_without_a_cluster(ctx):

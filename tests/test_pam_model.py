@@ -1,6 +1,8 @@
 """tests/pammodel.py, the numpy restatement the GPU clustering tests compare with (tests/test_gpu_cluster.py), pinned on its own: hand-worked
 PAM cases with every tie rule, local and exhaustive optimality, predStrengthCustom's last-entry quirk, planted clusters, the stability score,
-the layout of _clustering.tab against the reference tutorial's file, and the launcher's refusal to run without a device."""
+the layout of _clustering.tab against the reference tutorial's file, and the launcher's refusal to run without a device.  The results the GPU
+tests lean on at 1755, 1756 and 4096 members are checked by brute force, and the band table of the frequency-composition cases is shown to
+tell the strict rule from a lenient one."""
 import itertools
 import os
 import subprocess
@@ -64,6 +66,63 @@ def test_no_single_swap_improves_and_the_optimum_is_usually_reached():
         optimal += have <= best + 1e-12
         assert (clus == np.argmin(d[med], axis=0) + 1).all()
     assert optimal >= 24, optimal
+
+
+def test_the_matrix_filled_in_blocks_is_the_manhattan_matrix():
+    a = cases.planted_dist_blocks(300, 4, 21)                      # a second block of 44 rows
+    assert a.tobytes() == cases.planted_dist(300, 4, 21, n_pos=12, noise=30.0).tobytes()
+    for kind in ("real1756", "integer1756", "real4096"):           # what check_matrix asks for
+        d = cases.large_matrix(kind)
+        assert (d == d.T).all() and (np.diag(d) == 0).all() and np.isfinite(d).all() and (d >= 0).all(), kind
+
+
+@pytest.mark.parametrize("kind,m,k", cases.LARGE_PAM)
+def test_the_large_results_are_local_optima(kind, m, k):
+    # The GPU tests at 1755, 1756 and 4096 members rest on the model alone, so here is what it gives checked without it: the cost recomputed
+    # with numpy's own (pairwise) sums, and every exchange of one medoid for one non-medoid by brute force.  The model's sums over the m members
+    # are sequential, numpy's pairwise: the two differ by less than m * 2^-52 * cost (each of m - 1 additions rounds by at most 2^-53 of a
+    # partial sum no larger than the cost, in either order), so an exchange the model had to take would show as a gain above that.
+    ix = cases.large_members(kind, m)
+    d = cases.large_matrix(kind)[np.ix_(ix, ix)]
+    med, clus, _ = cases.large_want(kind, m, k)
+    assert len(set(med.tolist())) == k and (np.diff(med) > 0).all() and (clus == np.argmin(d[med], axis=0) + 1).all()
+    have = np.min(d[med], axis=0).sum()
+    others = np.setdiff1d(np.arange(m), med)
+    best = np.inf
+    for out in range(k):
+        rest = np.min(d[np.delete(med, out)], axis=0) if k > 1 else np.full(m, np.inf)
+        best = min(best, np.minimum(d[others], rest[None, :]).sum(axis=1).min())      # every h in the place of medoid `out`
+    assert len(others) * k == (m - k) * k and best >= have - m * 2.0 ** -52 * have, (have, best)
+
+
+@pytest.mark.parametrize("s,n_pos", [(255, 511), (256, 512), (257, 513), (600, 1100)])
+def test_the_band_table_tells_the_strict_rule_from_a_lenient_one(s, n_pos):
+    table = cases.band_table(n_pos, s, 50 + s)
+    nan = cases.band_nan_column(s)
+    assert table.shape == (n_pos, s) and np.isnan(table[:, nan]).all() and (nan == 256) == (s > 256)
+    valid = [c for c in range(s) if c != nan]
+    assert not np.isnan(table[:, valid]).all(axis=0).any() and np.isnan(table[:, valid]).any()
+    for b in range(0, s, 256):                                     # every edge in every block of 256 columns, and not only in the NaN column
+        cols = [c for c in range(b, min(b + 256, s)) if c != nan]
+        for edge in cases.BAND_EDGES + (4.999, 95.001):            # (s = 257: the second block is the NaN column alone)
+            assert (table[:, cols] == edge).any() or not cols, (b, edge)
+    for p in range(0, n_pos, 512):                                 # and in every block row of 512 positions
+        for edge in cases.BAND_EDGES:
+            assert (table[p:p + 512, valid] == edge).any(), (p, edge)
+    with np.errstate(invalid="ignore"):
+        for c in valid:
+            x = table[~np.isnan(table[:, c]), c]
+            strict = model.freq_bands(table[:, c])
+            lenient = [((x <= lo) | (x >= hi)).sum() / len(x) for lo, hi in ((20, 80), (10, 90), (5, 95))]
+            assert all(a < b for a, b in zip(strict, lenient)), c  # a kernel with <= or >= would write another number in every column
+    assert all(v != v for v in model.freq_bands(table[:, nan]))
+
+
+def test_a_header_only_table_gives_nan_in_every_row():
+    names = cases.sample_names(5)
+    files, info = model.cluster_files(names, cases.planted_dist(5, 0, 3), "sp", freq=(names[:3] + ["x"], cases.band_table(0, 4, 1)))
+    assert info["status"] == 3 and files == {"clustMedoidDefnFailed/sp_freq_composition.tab":
+        "freq_data_sample_20_80\tfreq_data_sample_10_90\tfreq_data_sample_5_95\n" + "".join(n + "\tNaN\tNaN\tNaN\n" for n in names[:3] + ["x"])}
 
 
 def test_the_last_entry_of_a_half_is_left_out_of_the_numerator_only():
