@@ -14,8 +14,6 @@
 // stability score.  Every PAM run, classification and pair count is on the device; there is no CPU fallback.
 // Divergences: rmNAfromDistMatrix is not built (an NA cell is MSNV_EFORMAT); R's generator is not reproduced; when Gmax <= 1
 // no _PS_values.tab is written (the reference hands write.table a NULL there); a stability group that holds an NA does not count as constant.
-#include <sys/stat.h>
-
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -45,49 +43,6 @@ void permutation(uint64_t seed, uint64_t ordinal, uint32_t n, std::vector<int32_
     for (uint32_t i = 0; i < n; ++i) p[i] = (int32_t)i;
     for (uint32_t i = n; i-- > 1;) std::swap(p[i], p[draw(seed, ordinal, i) % (i + 1)]);
 }
-
-}  // namespace
-
-// R's mean(): a long double sum over n, then the long double mean of the residuals added to it
-double r_mean(const double *x, size_t n) {
-    long double s = 0;
-    for (size_t i = 0; i < n; ++i) s += x[i];
-    s /= (long double)n;
-    long double t = 0;
-    for (size_t i = 0; i < n; ++i) t += x[i] - s;
-    s += t / (long double)n;
-    return (double)s;
-}
-
-void r_double(double v, std::string &out) {                            // %.15g, NaN and NA as R writes them
-    if (v != v) { out += "NaN"; return; }
-    char buf[40];
-    snprintf(buf, sizeof buf, "%.15g", v);
-    out += buf;
-}
-
-int write_text(const std::string &path, const std::string &text) {
-    FILE *f = fopen(path.c_str(), "w");
-    if (!f) return fail(MSNV_EIO, "Cannot open %s: %s", path.c_str(), strerror(errno));
-    fwrite(text.data(), 1, text.size(), f);
-    if (fclose(f) != 0) return fail(MSNV_EIO, "write error on %s: %s", path.c_str(), strerror(errno));
-    return MSNV_OK;
-}
-
-int make_dir(const std::string &path) {
-    if (mkdir(path.c_str(), 0777) != 0 && errno != EEXIST) return fail(MSNV_EIO, "Cannot create %s: %s", path.c_str(), strerror(errno));
-    return MSNV_OK;
-}
-
-// R's sd(): the n - 1 form, deviations from mean() summed in long double
-double r_sd(const double *x, size_t n) {
-    const double m = r_mean(x, n);
-    long double q = 0;
-    for (size_t i = 0; i < n; ++i) { const long double d = (long double)x[i] - m; q += d * d; }
-    return std::sqrt((double)(q / (long double)(n - 1)));
-}
-
-namespace {
 
 int check_matrix(const char *who, int64_t n, const double *d) {
     if (n < 2 || n > (int64_t)CLUSTER_MAX_SAMPLES) return fail(MSNV_EDOMAIN, "%s: %lld samples (2 to %u)", who, (long long)n, CLUSTER_MAX_SAMPLES);
@@ -478,11 +433,6 @@ int boot_run(msnv_ctx *ctx, const ClusterDev &dev, const std::vector<int32_t> &m
 }
 
 struct MembRow { bool na; double jaccard, recover; };                  // one (proportion, cluster) of _clusMembStability.tab
-
-void r_value(double v, std::string &out) {                             // r_double, and Inf as R writes it
-    if (std::isinf(v)) out += v > 0 ? "Inf" : "-Inf";
-    else r_double(v, out);
-}
 
 // R's three-valued logic: 0 FALSE, 1 TRUE, 2 NA
 int above3(const MembRow *r, double v, double thr) { return (!r || r->na || v != v) ? 2 : v > thr ? 1 : 0; }

@@ -23,7 +23,7 @@
 
 #include "device.h"
 #include "msnv_internal.h"
-#include "hiptry.h"
+#include "stagedev.h"
 
 #pragma clang fp contract(off)
 
@@ -285,17 +285,6 @@ __global__ void __launch_bounds__(256) msnv_freq_bands_k(const double *__restric
 // ---------------------------------------------------------------------------------------------- host side of the launches
 namespace {
 
-struct Buf {
-    void *p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-    template <class T> T *as() const { return (T *)p; }
-};
-
-struct Timer {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Timer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-};
-
 constexpr uint64_t BATCH_ENTRIES = 1ull << 26;                         // list entries of one launch: 256 MiB of indices, as much of cluster ids
 
 // msnv_cluster_boot's second launch: the batch is task 0 = the original partition and one task per subset (the whole batch, never a part of one)
@@ -304,7 +293,7 @@ struct Boot { const int32_t *pos; int32_t *med0, *clus0, *best; };
 // One launch of the PAM kernel over tasks[t0, t1) (their offsets rebased to the batch) and, when splits are asked for, one of the tail kernel; with
 // boot, one of the matching kernel over the cluster ids the PAM kernel left on the device.
 int run_batch(const ClusterDev &c, const std::vector<PamTask> &tasks, uint64_t t0, uint64_t t1, const int32_t *idx, bool splits, hipStream_t st,
-              int32_t *med, int32_t *clus, int32_t *swaps, double *prederr, float &ms_sum, const Boot *boot = nullptr) {
+              int32_t *med, int32_t *clus, int32_t *swaps, double *prederr, KernelTimer &tm, const Boot *boot = nullptr) {
     const uint64_t nt = t1 - t0, off0 = tasks[t0].off, med0 = tasks[t0].med_off;
     const uint64_t n_idx = tasks[t1 - 1].off + tasks[t1 - 1].m - off0, n_med = tasks[t1 - 1].med_off + tasks[t1 - 1].k - med0;
     std::vector<PamTask> local(tasks.begin() + t0, tasks.begin() + t1);
@@ -316,30 +305,25 @@ int run_batch(const ClusterDev &c, const std::vector<PamTask> &tasks, uint64_t t
     }
     const uint64_t ns = splits ? nt / 2 : 0;
     Buf d_tasks, d_idx, d_med, d_clus, d_swaps, d_err, d_pe, d_pos, d_best;
-    HIP_TRY(hipMalloc(&d_tasks.p, nt * sizeof(PamTask)));
-    HIP_TRY(hipMalloc(&d_idx.p, n_idx * 4));
-    HIP_TRY(hipMalloc(&d_med.p, n_med * 4));
-    HIP_TRY(hipMalloc(&d_clus.p, n_idx * 4));
-    HIP_TRY(hipMalloc(&d_swaps.p, nt * 4));
-    HIP_TRY(hipMalloc(&d_err.p, 16));
-    HIP_TRY(hipMemcpyAsync(d_tasks.p, local.data(), nt * sizeof(PamTask), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_idx.p, idx + off0, n_idx * 4, hipMemcpyHostToDevice, st));
+    MSNV_TRY(d_tasks.upload(local.data(), nt * sizeof(PamTask), st));
+    MSNV_TRY(d_idx.upload(idx + off0, n_idx * 4, st));
+    MSNV_TRY(d_med.alloc(n_med * 4));
+    MSNV_TRY(d_clus.alloc(n_idx * 4));
+    MSNV_TRY(d_swaps.alloc(nt * 4));
+    MSNV_TRY(d_err.alloc(16));
     HIP_TRY(hipMemsetAsync(d_err.p, 0, 16, st));
-    if (ns) HIP_TRY(hipMalloc(&d_pe.p, ns * 8));
+    if (ns) MSNV_TRY(d_pe.alloc(ns * 8));
     const uint64_t n_sets = boot ? nt - 1 : 0, n_pos = boot ? n_idx - local[0].m : 0, n_best = n_sets * max_k * 2;
     if (n_sets) {
-        HIP_TRY(hipMalloc(&d_pos.p, n_pos * 4));
-        HIP_TRY(hipMalloc(&d_best.p, n_best * 4));
-        HIP_TRY(hipMemcpyAsync(d_pos.p, boot->pos, n_pos * 4, hipMemcpyHostToDevice, st));
+        MSNV_TRY(d_pos.upload(boot->pos, n_pos * 4, st));
+        MSNV_TRY(d_best.alloc(n_best * 4));
     }
     const size_t lds_pam = (size_t)max_m * 28, lds_ps = (size_t)max_len * 4 + (size_t)max_k * 24;
     if (lds_pam > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)msnv_pam_tasks_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pam));
     if (lds_ps > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)msnv_ps_splits_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ps));
     const uint32_t per_cu = (uint32_t)std::min<size_t>(8, std::max<size_t>(1, (160 * 1024) / (lds_pam + 4096)));
     const uint32_t grid = (uint32_t)std::min<uint64_t>(nt, dev_resident_workgroups(per_cu));
-    Timer tm;
-    HIP_TRY(hipEventCreate(&tm.e0)); HIP_TRY(hipEventCreate(&tm.e1));
-    HIP_TRY(hipEventRecord(tm.e0, st));
+    MSNV_TRY(tm.begin(st));
     hipLaunchKernelGGL(msnv_pam_tasks_k, dim3(grid), dim3(PAM_THREADS), lds_pam, st, c.dist, c.n, d_tasks.as<PamTask>(), (unsigned long long)nt, d_idx.as<int32_t>(), max_m,
                        d_med.as<int32_t>(), d_clus.as<int32_t>(), d_swaps.as<int32_t>(), d_err.as<uint32_t>());
     HIP_TRY(hipGetLastError());
@@ -348,12 +332,10 @@ int run_batch(const ClusterDev &c, const std::vector<PamTask> &tasks, uint64_t t
                            (unsigned long long)ns, d_idx.as<int32_t>(), max_len, d_med.as<int32_t>(), d_clus.as<int32_t>(), d_pe.as<double>());
         HIP_TRY(hipGetLastError());
     }
-    if (n_sets) {
+    if (n_sets)
         hipLaunchKernelGGL(msnv_boot_match_k, dim3((uint32_t)std::min<uint64_t>(n_sets, dev_resident_workgroups(8))), dim3(PAM_THREADS), 0, st, d_tasks.as<PamTask>(),
                            (unsigned long long)n_sets, d_pos.as<int32_t>(), d_clus.as<int32_t>(), d_best.as<int32_t>());
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(tm.e1, st));
+    MSNV_TRY(tm.stop(st));
     uint32_t err = 0;
     HIP_TRY(hipMemcpyAsync(&err, d_err.p, 4, hipMemcpyDeviceToHost, st));
     if (boot) {
@@ -365,10 +347,7 @@ int run_batch(const ClusterDev &c, const std::vector<PamTask> &tasks, uint64_t t
     if (clus) HIP_TRY(hipMemcpyAsync(clus + off0, d_clus.p, n_idx * 4, hipMemcpyDeviceToHost, st));
     if (swaps) HIP_TRY(hipMemcpyAsync(swaps + t0, d_swaps.p, nt * 4, hipMemcpyDeviceToHost, st));
     if (prederr) HIP_TRY(hipMemcpyAsync(prederr + t0 / 2, d_pe.p, ns * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    float t = 0;
-    HIP_TRY(hipEventElapsedTime(&t, tm.e0, tm.e1));
-    ms_sum += t;
+    MSNV_TRY(tm.wait(st));
     if (err) return fail(MSNV_EDOMAIN, "PAM: a task swapped more than %u times without settling", PAM_MAX_SWAPS);
     return MSNV_OK;
 }
@@ -376,15 +355,15 @@ int run_batch(const ClusterDev &c, const std::vector<PamTask> &tasks, uint64_t t
 // tasks in launches of at most BATCH_ENTRIES list entries (a split's two halves stay together)
 int run_all(const ClusterDev &c, const std::vector<PamTask> &tasks, const int32_t *idx, bool splits, void *stream, int32_t *med, int32_t *clus, int32_t *swaps,
             double *prederr, double *ms_kernel) {
-    float ms_sum = 0;
+    KernelTimer tm;
     const uint64_t step = splits ? 2 : 1;
     for (uint64_t t0 = 0; t0 < tasks.size();) {
         uint64_t t1 = t0 + step;
         while (t1 < tasks.size() && tasks[t1 + step - 1].off + tasks[t1 + step - 1].m - tasks[t0].off <= BATCH_ENTRIES) t1 += step;
-        if (int rc = run_batch(c, tasks, t0, t1, idx, splits, (hipStream_t)stream, med, clus, swaps, prederr, ms_sum)) return rc;
+        MSNV_TRY(run_batch(c, tasks, t0, t1, idx, splits, (hipStream_t)stream, med, clus, swaps, prederr, tm));
         t0 = t1;
     }
-    if (ms_kernel) *ms_kernel += ms_sum;
+    if (ms_kernel) *ms_kernel += tm.ms;
     return MSNV_OK;
 }
 
@@ -416,9 +395,9 @@ int dev_cluster_boot(const ClusterDev &c, uint64_t n_sets, const uint32_t *m, ui
     for (uint64_t t = 0; t <= n_sets; ++t) { tasks[t] = PamTask{off, t * k, m[t], k}; off += m[t]; }
     if (off > BATCH_ENTRIES) return fail(MSNV_ECAPACITY, "cluster boot: %llu list entries in one call (at most %llu)", (unsigned long long)off, (unsigned long long)BATCH_ENTRIES);
     const Boot boot{pos, med0, clus0, best};
-    float ms_sum = 0;
-    if (int rc = run_batch(c, tasks, 0, tasks.size(), idx, false, (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr, ms_sum, &boot)) return rc;
-    if (ms_kernel) *ms_kernel += ms_sum;
+    KernelTimer tm;
+    MSNV_TRY(run_batch(c, tasks, 0, tasks.size(), idx, false, (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr, tm, &boot));
+    if (ms_kernel) *ms_kernel += tm.ms;
     return MSNV_OK;
 }
 
@@ -437,33 +416,24 @@ int dev_pred_strength(const ClusterDev &c, uint64_t n_splits, const uint32_t *le
 int dev_freq_bands(const double *rows, uint64_t n_pos, uint32_t S, void *stream_, uint64_t *counts, double *ms_kernel) {
     hipStream_t st = (hipStream_t)stream_;
     Buf d_rows, d_cnt;
-    HIP_TRY(hipMalloc(&d_cnt.p, (size_t)S * 32));
+    MSNV_TRY(d_cnt.alloc((size_t)S * 32));
     HIP_TRY(hipMemsetAsync(d_cnt.p, 0, (size_t)S * 32, st));
-    Timer tm;
-    HIP_TRY(hipEventCreate(&tm.e0)); HIP_TRY(hipEventCreate(&tm.e1));
-    float ms_sum = 0;
     // position chunks that fit the device and the grid's second dimension
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     const uint64_t row_bytes = (uint64_t)S * 8;
-    const uint64_t chunk = std::min<uint64_t>(std::min<uint64_t>(std::max<uint64_t>(n_pos, 1), (uint64_t)(free_b * 0.5) / row_bytes), (uint64_t)FREQ_ROWS * 65535);
-    if (chunk == 0) return fail(MSNV_ENOMEM, "SNV frequency composition: %llu bytes of device memory left, one table row takes %llu", (unsigned long long)free_b, (unsigned long long)row_bytes);
-    HIP_TRY(hipMalloc(&d_rows.p, chunk * row_bytes));
+    uint64_t chunk = 0;
+    MSNV_TRY(slab_rows(n_pos, row_bytes, 0.5, (uint64_t)FREQ_ROWS * 65535, "SNV frequency composition", &chunk));
+    MSNV_TRY(d_rows.alloc(chunk * row_bytes));
+    KernelTimer tm;
     for (uint64_t p0 = 0; p0 < n_pos; p0 += chunk) {
         const uint64_t np = std::min(chunk, n_pos - p0);
         HIP_TRY(hipMemcpyAsync(d_rows.p, rows + p0 * S, np * row_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(tm.e0, st));
+        MSNV_TRY(tm.begin(st));
         hipLaunchKernelGGL(msnv_freq_bands_k, dim3((S + 255) / 256, (uint32_t)((np + FREQ_ROWS - 1) / FREQ_ROWS)), dim3(256), 0, st, d_rows.as<double>(), (unsigned long long)np, S,
                            d_cnt.as<unsigned long long>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(tm.e1, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        float t = 0;
-        HIP_TRY(hipEventElapsedTime(&t, tm.e0, tm.e1));
-        ms_sum += t;
+        MSNV_TRY(tm.end(st));
     }
     HIP_TRY(hipMemcpy(counts, d_cnt.p, (size_t)S * 32, hipMemcpyDeviceToHost));
-    if (ms_kernel) *ms_kernel += ms_sum;
+    if (ms_kernel) *ms_kernel += tm.ms;
     return MSNV_OK;
 }
 

@@ -18,7 +18,7 @@
 #include <vector>
 
 #include "msnv_internal.h"
-#include "hiptry.h"
+#include "stagedev.h"
 
 namespace msnv {
 
@@ -111,13 +111,11 @@ static void pairwise_plan(long lo, long n, std::vector<DistLeaf> &leaves, std::v
 
 int dev_dist(const double *xt_host, int n_samples, long n_pos, double threshold, void *stream_, double *mann, double *allele, double *ms_kernel) {
     hipStream_t st = (hipStream_t)stream_;
-    struct Buf { void *p = nullptr; ~Buf() { if (p) (void)hipFree(p); } };
     Buf d_x, d_m, d_a;
-    const size_t xb = (size_t)n_samples * (size_t)std::max<long>(n_pos, 1) * sizeof(double), mb = (size_t)n_samples * n_samples * sizeof(double);
-    HIP_TRY(hipMalloc(&d_x.p, xb));
-    HIP_TRY(hipMalloc(&d_m.p, std::max<size_t>(mb, 16)));
-    HIP_TRY(hipMalloc(&d_a.p, std::max<size_t>(mb, 16)));
-    if (n_pos > 0) HIP_TRY(hipMemcpyAsync(d_x.p, xt_host, (size_t)n_samples * n_pos * sizeof(double), hipMemcpyHostToDevice, st));
+    const size_t xb = (size_t)n_samples * (size_t)n_pos * sizeof(double), mb = (size_t)n_samples * n_samples * sizeof(double);
+    MSNV_TRY(d_x.upload(xt_host, xb, st));
+    MSNV_TRY(d_m.alloc(mb));
+    MSNV_TRY(d_a.alloc(mb));
     std::vector<DistLeaf> leaves; std::vector<unsigned char> prog;
     for (long lo = 0; lo < n_pos; lo += DIST_BLOCK) {           // 0.0 + pw(block 0) + pw(block 1) + ...
         pairwise_plan(lo, std::min(DIST_BLOCK, n_pos - lo), leaves, prog);
@@ -125,29 +123,19 @@ int dev_dist(const double *xt_host, int n_samples, long n_pos, double threshold,
     }
     const long n_pairs = (long)n_samples * (n_samples + 1) / 2;
     Buf d_l, d_p, d_s;
-    HIP_TRY(hipMalloc(&d_l.p, std::max<size_t>(leaves.size() * sizeof(DistLeaf), 16)));
-    HIP_TRY(hipMalloc(&d_p.p, std::max<size_t>(prog.size(), 16)));
-    if (!leaves.empty()) HIP_TRY(hipMemcpyAsync(d_l.p, leaves.data(), leaves.size() * sizeof(DistLeaf), hipMemcpyHostToDevice, st));
-    if (!prog.empty()) HIP_TRY(hipMemcpyAsync(d_p.p, prog.data(), prog.size(), hipMemcpyHostToDevice, st));
-    if ((int)leaves.size() > DIST_MAX_LEAVES_LDS) HIP_TRY(hipMalloc(&d_s.p, (size_t)n_pairs * leaves.size() * sizeof(double)));
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    hipError_t he = hipEventRecord(e0, st);
-    if (he == hipSuccess && n_pairs) {
-        hipLaunchKernelGGL(msnv_dist_pairs, dim3((unsigned)n_pairs), dim3(64), 0, st, (const double *)d_x.p, n_samples, n_pos, threshold,
-                           (const DistLeaf *)d_l.p, (int)leaves.size(), (const unsigned char *)d_p.p, (int)prog.size(), (double *)d_s.p,
-                           (double *)d_m.p, (double *)d_a.p);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess) he = hipEventRecord(e1, st);
-    if (he == hipSuccess && mb) he = hipMemcpyAsync(mann, d_m.p, mb, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess && mb) he = hipMemcpyAsync(allele, d_a.p, mb, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess) he = hipStreamSynchronize(st);
-    float t = 0;
-    if (he == hipSuccess) he = hipEventElapsedTime(&t, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (he != hipSuccess) return fail(MSNV_EHIP, "distance kernel: %s", hipGetErrorString(he));
-    if (ms_kernel) *ms_kernel = t;
+    MSNV_TRY(d_l.upload(leaves.data(), leaves.size() * sizeof(DistLeaf), st));
+    MSNV_TRY(d_p.upload(prog.data(), prog.size(), st));
+    if ((int)leaves.size() > DIST_MAX_LEAVES_LDS) MSNV_TRY(d_s.alloc((size_t)n_pairs * leaves.size() * sizeof(double)));
+    KernelTimer tm;
+    MSNV_TRY(tm.begin(st));
+    if (n_pairs)
+        hipLaunchKernelGGL(msnv_dist_pairs, dim3((unsigned)n_pairs), dim3(64), 0, st, d_x.as<double>(), n_samples, n_pos, threshold, d_l.as<DistLeaf>(),
+                           (int)leaves.size(), d_p.as<unsigned char>(), (int)prog.size(), d_s.as<double>(), d_m.as<double>(), d_a.as<double>());
+    MSNV_TRY(tm.stop(st));
+    if (mb) HIP_TRY(hipMemcpyAsync(mann, d_m.p, mb, hipMemcpyDeviceToHost, st));
+    if (mb) HIP_TRY(hipMemcpyAsync(allele, d_a.p, mb, hipMemcpyDeviceToHost, st));
+    MSNV_TRY(tm.wait(st));
+    if (ms_kernel) *ms_kernel += tm.ms;
     return MSNV_OK;
 }
 

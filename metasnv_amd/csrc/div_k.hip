@@ -29,7 +29,7 @@
 #include <vector>
 
 #include "msnv_internal.h"
-#include "hiptry.h"
+#include "stagedev.h"
 
 namespace msnv {
 
@@ -267,37 +267,25 @@ __global__ __launch_bounds__(64) void msnv_div_pairs(const double *__restrict__ 
 int dev_div(const double *xs, const uint64_t *bits, long n_single, long n_words, const double *xg, const long *goff, long n_groups, long n_grouped,
             int n_samples, void *stream_, double *out, double *ms_kernel) {
     hipStream_t st = (hipStream_t)stream_;
-    struct Buf { void *p = nullptr; ~Buf() { if (p) (void)hipFree(p); } };
     Buf d_xs, d_b, d_xg, d_go, d_out;
     const size_t S = (size_t)n_samples;
     const size_t xsb = S * (size_t)n_single * sizeof(double), bb = S * (size_t)n_words * sizeof(uint64_t);
     const size_t xgb = S * (size_t)n_grouped * sizeof(double), gob = (size_t)(n_groups + 1) * sizeof(long), ob = S * S * sizeof(double);
-    HIP_TRY(hipMalloc(&d_xs.p, std::max<size_t>(xsb, 16)));
-    HIP_TRY(hipMalloc(&d_b.p, std::max<size_t>(bb, 16)));
-    HIP_TRY(hipMalloc(&d_xg.p, std::max<size_t>(xgb, 16)));
-    HIP_TRY(hipMalloc(&d_go.p, std::max<size_t>(gob, 16)));
-    HIP_TRY(hipMalloc(&d_out.p, std::max<size_t>(ob, 16)));
-    if (xsb) HIP_TRY(hipMemcpyAsync(d_xs.p, xs, xsb, hipMemcpyHostToDevice, st));
-    if (bb) HIP_TRY(hipMemcpyAsync(d_b.p, bits, bb, hipMemcpyHostToDevice, st));
-    if (xgb) HIP_TRY(hipMemcpyAsync(d_xg.p, xg, xgb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_go.p, goff, gob, hipMemcpyHostToDevice, st));
+    MSNV_TRY(d_xs.upload(xs, xsb, st));
+    MSNV_TRY(d_b.upload(bits, bb, st));
+    MSNV_TRY(d_xg.upload(xg, xgb, st));
+    MSNV_TRY(d_go.upload(goff, gob, st));
+    MSNV_TRY(d_out.alloc(ob));
     const long n_pairs = (long)n_samples * (n_samples + 1) / 2;
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    hipError_t he = hipEventRecord(e0, st);
-    if (he == hipSuccess && n_pairs) {
-        hipLaunchKernelGGL(msnv_div_pairs, dim3((unsigned)n_pairs), dim3(64), 0, st, (const double *)d_xs.p, (const unsigned long long *)d_b.p,
-                           n_single, n_words, (const double *)d_xg.p, (const long *)d_go.p, n_groups, n_grouped, n_samples, (double *)d_out.p);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess) he = hipEventRecord(e1, st);
-    if (he == hipSuccess && ob) he = hipMemcpyAsync(out, d_out.p, ob, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess) he = hipStreamSynchronize(st);
-    float t = 0;
-    if (he == hipSuccess) he = hipEventElapsedTime(&t, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (he != hipSuccess) return fail(MSNV_EHIP, "diversity kernel: %s", hipGetErrorString(he));
-    if (ms_kernel) *ms_kernel += t;
+    KernelTimer tm;
+    MSNV_TRY(tm.begin(st));
+    if (n_pairs)
+        hipLaunchKernelGGL(msnv_div_pairs, dim3((unsigned)n_pairs), dim3(64), 0, st, d_xs.as<double>(), d_b.as<unsigned long long>(), n_single, n_words,
+                           d_xg.as<double>(), d_go.as<long>(), n_groups, n_grouped, n_samples, d_out.as<double>());
+    MSNV_TRY(tm.stop(st));
+    if (ob) HIP_TRY(hipMemcpyAsync(out, d_out.p, ob, hipMemcpyDeviceToHost, st));
+    MSNV_TRY(tm.wait(st));
+    if (ms_kernel) *ms_kernel += tm.ms;
     return MSNV_OK;
 }
 

@@ -13,7 +13,7 @@
 
 #include "filter.h"
 #include "msnv_internal.h"
-#include "hiptry.h"
+#include "stagedev.h"
 
 namespace msnv {
 
@@ -49,39 +49,27 @@ int dev_filter_batch(const FilterBatch &b, const FilterSpecies &sp, double min_c
     const uint32_t n_rows = (uint32_t)b.row_line.size(), n_lines = (uint32_t)b.line_species.size();
     freq.assign(b.n_out, 0.0); line_pass.assign(n_lines, 0);
     if (!n_rows) return MSNV_OK;
-    struct Buf { void *p = nullptr; ~Buf() { if (p) (void)hipFree(p); } };
     Buf d_cov, d_cnt, d_rl, d_ls, d_so, d_si, d_ro, d_fr, d_lp;
-    auto up = [&](Buf &buf, const void *src, size_t bytes) -> int {
-        HIP_TRY(hipMalloc(&buf.p, bytes ? bytes : 16));
-        if (bytes) HIP_TRY(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, st));
-        return MSNV_OK;
-    };
-    if (int rc = up(d_cov, b.cov.data(), b.cov.size() * 4)) return rc;
-    if (int rc = up(d_cnt, b.cnt.data(), b.cnt.size() * 4)) return rc;
-    if (int rc = up(d_rl, b.row_line.data(), b.row_line.size() * 4)) return rc;
-    if (int rc = up(d_ls, b.line_species.data(), b.line_species.size() * 4)) return rc;
-    if (int rc = up(d_so, sp.soi_off.data(), sp.soi_off.size() * 4)) return rc;
-    if (int rc = up(d_si, sp.soi_idx.data(), sp.soi_idx.size() * 4)) return rc;
-    if (int rc = up(d_ro, b.row_out.data(), b.row_out.size() * 8)) return rc;
-    HIP_TRY(hipMalloc(&d_fr.p, std::max<size_t>(16, b.n_out * sizeof(double))));
-    HIP_TRY(hipMalloc(&d_lp.p, std::max<size_t>(16, n_lines)));
+    MSNV_TRY(d_cov.upload(b.cov.data(), b.cov.size() * 4, st));
+    MSNV_TRY(d_cnt.upload(b.cnt.data(), b.cnt.size() * 4, st));
+    MSNV_TRY(d_rl.upload(b.row_line.data(), b.row_line.size() * 4, st));
+    MSNV_TRY(d_ls.upload(b.line_species.data(), b.line_species.size() * 4, st));
+    MSNV_TRY(d_so.upload(sp.soi_off.data(), sp.soi_off.size() * 4, st));
+    MSNV_TRY(d_si.upload(sp.soi_idx.data(), sp.soi_idx.size() * 4, st));
+    MSNV_TRY(d_ro.upload(b.row_out.data(), b.row_out.size() * 8, st));
+    MSNV_TRY(d_fr.alloc(b.n_out * sizeof(double)));
+    MSNV_TRY(d_lp.alloc(n_lines));
     HIP_TRY(hipMemsetAsync(d_lp.p, 0, n_lines, st));
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    hipError_t he = hipEventRecord(e0, st);
-    hipLaunchKernelGGL(msnv_filter_freq, dim3((n_rows + 3) / 4), dim3(256), 0, st, (const uint32_t *)d_cov.p, (const uint32_t *)d_cnt.p, b.n_samples,
-                       (const uint32_t *)d_rl.p, (const uint32_t *)d_ls.p, (const uint32_t *)d_so.p, (const uint32_t *)d_si.p,
-                       (const unsigned long long *)d_ro.p, n_rows, min_cov, min_prop, (double *)d_fr.p, (uint8_t *)d_lp.p);
-    if (he == hipSuccess) he = hipGetLastError();
-    if (he == hipSuccess) he = hipEventRecord(e1, st);
-    if (he == hipSuccess && b.n_out) he = hipMemcpyAsync(freq.data(), d_fr.p, b.n_out * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess) he = hipMemcpyAsync(line_pass.data(), d_lp.p, n_lines, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess) he = hipStreamSynchronize(st);
-    float t = 0;
-    if (he == hipSuccess) he = hipEventElapsedTime(&t, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (he != hipSuccess) return fail(MSNV_EHIP, "filter kernel: %s", hipGetErrorString(he));
-    if (ms_kernel) *ms_kernel += t;
+    KernelTimer tm;
+    MSNV_TRY(tm.begin(st));
+    hipLaunchKernelGGL(msnv_filter_freq, dim3((n_rows + 3) / 4), dim3(256), 0, st, d_cov.as<uint32_t>(), d_cnt.as<uint32_t>(), b.n_samples,
+                       d_rl.as<uint32_t>(), d_ls.as<uint32_t>(), d_so.as<uint32_t>(), d_si.as<uint32_t>(),
+                       d_ro.as<unsigned long long>(), n_rows, min_cov, min_prop, d_fr.as<double>(), d_lp.as<uint8_t>());
+    MSNV_TRY(tm.stop(st));
+    if (b.n_out) HIP_TRY(hipMemcpyAsync(freq.data(), d_fr.p, b.n_out * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(line_pass.data(), d_lp.p, n_lines, hipMemcpyDeviceToHost, st));
+    MSNV_TRY(tm.wait(st));
+    if (ms_kernel) *ms_kernel += tm.ms;
     return MSNV_OK;
 }
 

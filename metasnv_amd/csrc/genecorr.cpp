@@ -9,7 +9,6 @@
 // Divergences: a cell that is NA, empty or not a number is refused with MSNV_EFORMAT (R drops such pairs);
 // labels sort in byte order (R sorts in its locale); numbers are printed as the shortest digits that read back, exponent unpadded.
 #include <algorithm>
-#include <cerrno>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -27,25 +26,6 @@ namespace msnv {
 
 namespace {
 
-typedef std::pair<const char *, const char *> Span;
-
-int slurp(const char *path, std::string &out) {
-    FILE *f = fopen(path, "rb");
-    if (!f) return fail(MSNV_EIO, "Cannot open %s: %s", path, strerror(errno));
-    char buf[1 << 16];
-    size_t n;
-    while ((n = fread(buf, 1, sizeof buf, f)) > 0) out.append(buf, n);
-    fclose(f);
-    return MSNV_OK;
-}
-
-void split_tabs(const char *s, const char *e, std::vector<Span> &out) {
-    out.clear();
-    const char *b = s;
-    for (const char *p = s; p <= e; ++p)
-        if (p == e || *p == '\t') { out.emplace_back(b, p); b = p + 1; }
-}
-
 inline Span trimmed(Span x) {                                          // readr's trim_ws
     while (x.first < x.second && (*x.first == ' ' || *x.first == '\r')) ++x.first;
     while (x.second > x.first && (x.second[-1] == ' ' || x.second[-1] == '\r')) --x.second;
@@ -53,15 +33,9 @@ inline Span trimmed(Span x) {                                          // readr'
 }
 
 // a finite number, nothing else (NA, the empty field, nan and inf are refused)
-bool parse_cell(Span x, double &v) {
+inline bool parse_cell(Span x, double &v) {
     x = trimmed(x);
-    if (x.first == x.second) return false;
-    const char c = *x.first;
-    if (!((c >= '0' && c <= '9') || c == '.' || c == '-' || c == '+')) return false;
-    std::string t(x.first, x.second);
-    char *end = nullptr;
-    v = strtod(t.c_str(), &end);
-    return end == t.c_str() + t.size() && std::isfinite(v);
+    return parse_finite(x.first, x.second, v);
 }
 
 // lines of a text, without their newline (and without a carriage return before it)
@@ -98,41 +72,33 @@ struct Table {                                                         // one me
     std::vector<double> est, stat, p, lo, hi, q;
 };
 
+// The text of a table is built whole and handed to write_text: about 120 bytes per row, next to the gene table's text and matrix that the stage holds anyway
 int write_table(const std::string &path, bool pearson, const Table &t, const std::vector<std::string> &labels, const std::vector<std::string> &gene_names, int32_t n_obs) {
-    FILE *f = fopen(path.c_str(), "w");
-    if (!f) return fail(MSNV_EIO, "Cannot open %s: %s", path.c_str(), strerror(errno));
-    std::string line = pearson ? "geneFamily\tcluster\tstatistic\tp.value\testimate\tnull.value\talternative\tmethod\tconf.int\tconf.int.low\tconf.int.high\tnObs\tq.valueBH\n"
+    std::string text = pearson ? "geneFamily\tcluster\tstatistic\tp.value\testimate\tnull.value\talternative\tmethod\tconf.int\tconf.int.low\tconf.int.high\tnObs\tq.valueBH\n"
                                : "geneFamily\tcluster\tstatistic\tp.value\testimate\tnull.value\talternative\tmethod\tnObs\tq.valueBH\n";
-    fwrite(line.data(), 1, line.size(), f);
     const std::string nobs = std::to_string(n_obs);
     for (size_t i = 0; i < t.est.size(); ++i) {
-        line = gene_names[t.gene[i]]; line.push_back('\t'); line += labels[t.clust[i]]; line.push_back('\t');
-        r_number(t.stat[i], line); line.push_back('\t');
-        r_number(t.p[i], line); line.push_back('\t');
-        r_number(t.est[i], line);
-        line += pearson ? "\t0\ttwo.sided\tpearson\tFALSE\t" : "\t0\ttwo.sided\tspearman\t";
-        if (pearson) { r_number(t.lo[i], line); line.push_back('\t'); r_number(t.hi[i], line); line.push_back('\t'); }
-        line += nobs; line.push_back('\t');
-        r_number(t.q[i], line); line.push_back('\n');
-        fwrite(line.data(), 1, line.size(), f);
+        text += gene_names[t.gene[i]]; text.push_back('\t'); text += labels[t.clust[i]]; text.push_back('\t');
+        r_number(t.stat[i], text); text.push_back('\t');
+        r_number(t.p[i], text); text.push_back('\t');
+        r_number(t.est[i], text);
+        text += pearson ? "\t0\ttwo.sided\tpearson\tFALSE\t" : "\t0\ttwo.sided\tspearman\t";
+        if (pearson) { r_number(t.lo[i], text); text.push_back('\t'); r_number(t.hi[i], text); text.push_back('\t'); }
+        text += nobs; text.push_back('\t');
+        r_number(t.q[i], text); text.push_back('\n');
     }
-    if (fclose(f) != 0) return fail(MSNV_EIO, "write error on %s: %s", path.c_str(), strerror(errno));
-    return MSNV_OK;
+    return write_text(path, text);
 }
 
 struct Group { std::string gene; uint32_t clust; bool corr, not_corr; };
 
 int write_groups(const std::string &path, const std::vector<Group> &rows, const std::vector<std::string> &labels) {
-    FILE *f = fopen(path.c_str(), "w");
-    if (!f) return fail(MSNV_EIO, "Cannot open %s: %s", path.c_str(), strerror(errno));
     std::string text = "geneFamily\tcluster\tgeneIsCorrelated\tgeneIsNotCorrelated\n";
     for (const Group &g : rows) {
         text += g.gene; text.push_back('\t'); text += labels[g.clust];
         text += g.corr ? "\tTRUE" : "\tFALSE"; text += g.not_corr ? "\tTRUE\n" : "\tFALSE\n";
     }
-    fwrite(text.data(), 1, text.size(), f);
-    if (fclose(f) != 0) return fail(MSNV_EIO, "write error on %s: %s", path.c_str(), strerror(errno));
-    return MSNV_OK;
+    return write_text(path, text);
 }
 
 std::string first_three(const std::vector<std::string> &v) {
@@ -195,7 +161,7 @@ extern "C" int msnv_gene_corr_files(msnv_ctx *ctx, const char *clust_abund_path,
     if (int rc = each_line(ctext, [&](const char *s, const char *e) -> int {
             ++lineno;
             if (s == e) return MSNV_OK;
-            split_tabs(s, e, f);
+            split_span(s, e, '\t', f);
             if (lineno == 1) { for (Span x : f) cnames.emplace_back(x.first, x.second); return MSNV_OK; }
             if (f.size() != cnames.size() + 1) return fail(MSNV_EFORMAT, "%s:%llu: %zu fields, the header names %zu clusters (expected the sample name and one value per cluster)", clust_abund_path, (unsigned long long)lineno, f.size(), cnames.size());
             csamples.emplace_back(f[0].first, f[0].second);
@@ -235,7 +201,7 @@ extern "C" int msnv_gene_corr_files(msnv_ctx *ctx, const char *clust_abund_path,
     int rc = each_line(gtext, [&](const char *s, const char *e) -> int {
         ++lineno;
         if (s == e || *s == '#') return MSNV_OK;
-        split_tabs(s, e, f);
+        split_span(s, e, '\t', f);
         if (!have_header) {
             have_header = true;
             for (size_t k = 1; k < f.size(); ++k) { Span x = trimmed(f[k]); gcols.emplace_back(x.first, x.second); }

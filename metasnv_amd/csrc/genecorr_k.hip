@@ -26,7 +26,7 @@
 
 #include "device.h"
 #include "msnv_internal.h"
-#include "hiptry.h"
+#include "stagedev.h"
 
 namespace msnv {
 
@@ -374,17 +374,6 @@ __global__ void __launch_bounds__(BH_THREADS) msnv_bh_scan(const double *key, co
 // ---------------------------------------------------------------------------------------------- host side of the launches
 namespace {
 
-struct Buf {
-    void *p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-    template <class T> T *as() const { return (T *)p; }
-};
-
-struct Timer {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Timer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-};
-
 inline uint32_t pad_pow2(uint32_t s) { uint32_t p = 64; while (p < s) p <<= 1; return p; }
 
 }  // namespace
@@ -400,46 +389,31 @@ int dev_gene_corr(uint32_t K1, uint64_t G, uint32_t S, const double *clust, cons
     }
     const uint64_t row_bytes = (uint64_t)S * 8, n_out = (uint64_t)K1 * G;
     Buf d_clust, d_crank, d_clog, d_csum, d_cvalid, d_flags, d_rho, d_r, d_valid, d_genes;
-    HIP_TRY(hipMalloc(&d_clust.p, K1 * row_bytes));
-    HIP_TRY(hipMalloc(&d_crank.p, K1 * row_bytes));
-    HIP_TRY(hipMalloc(&d_clog.p, K1 * row_bytes));
-    HIP_TRY(hipMalloc(&d_csum.p, (size_t)K1 * 16));
-    HIP_TRY(hipMalloc(&d_cvalid.p, K1));
-    HIP_TRY(hipMalloc(&d_flags.p, 16));                                // [0..7] bits of the smallest positive cell, [8..11] bad-cell flag
-    HIP_TRY(hipMalloc(&d_rho.p, n_out * 8));
-    HIP_TRY(hipMalloc(&d_r.p, n_out * 8));
-    HIP_TRY(hipMalloc(&d_valid.p, n_out));
+    MSNV_TRY(d_clust.upload(clust, K1 * row_bytes, st));
+    MSNV_TRY(d_crank.alloc(K1 * row_bytes));
+    MSNV_TRY(d_clog.alloc(K1 * row_bytes));
+    MSNV_TRY(d_csum.alloc((size_t)K1 * 16));
+    MSNV_TRY(d_cvalid.alloc(K1));
+    MSNV_TRY(d_flags.alloc(16));                                       // [0..7] bits of the smallest positive cell, [8..11] bad-cell flag
+    MSNV_TRY(d_rho.alloc(n_out * 8));
+    MSNV_TRY(d_r.alloc(n_out * 8));
+    MSNV_TRY(d_valid.alloc(n_out));
     // the gene matrix in row chunks that fit the device: whole when it does (then it is uploaded once for both passes)
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    const uint64_t budget = (uint64_t)(free_b * 0.8);
-    if (budget < row_bytes) return fail(MSNV_ENOMEM, "gene correlation: %llu bytes of device memory left, one gene row takes %llu", (unsigned long long)free_b, (unsigned long long)row_bytes);
-    const uint64_t chunk_rows = std::min<uint64_t>(std::min<uint64_t>(G, budget / row_bytes), 0x7fffffffull);
-    HIP_TRY(hipMalloc(&d_genes.p, chunk_rows * row_bytes));
-    const bool whole = chunk_rows == G;
-    Timer tm;
-    HIP_TRY(hipEventCreate(&tm.e0)); HIP_TRY(hipEventCreate(&tm.e1));
-    float ms_sum = 0;
-    auto timed_end = [&]() -> int {
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(tm.e1, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        float t = 0;
-        HIP_TRY(hipEventElapsedTime(&t, tm.e0, tm.e1));
-        ms_sum += t;
-        return MSNV_OK;
-    };
-    HIP_TRY(hipMemcpyAsync(d_clust.p, clust, K1 * row_bytes, hipMemcpyHostToDevice, st));
+    uint64_t chunk_rows = 0;
+    MSNV_TRY(slab_rows(G, row_bytes, 0.8, 0x7fffffffull, "gene correlation", &chunk_rows));
+    MSNV_TRY(d_genes.alloc(chunk_rows * row_bytes));
+    const bool whole = chunk_rows >= G;
+    KernelTimer tm;
     HIP_TRY(hipMemsetAsync(d_flags.p, 0xff, 8, st));
     HIP_TRY(hipMemsetAsync((char *)d_flags.p + 8, 0, 8, st));
     // pass 1: the pseudocount, finished before anything takes a logarithm
     for (uint64_t g0 = 0; g0 < G; g0 += chunk_rows) {
         const uint64_t rows = std::min(chunk_rows, G - g0), cells = rows * S;
         HIP_TRY(hipMemcpyAsync(d_genes.p, genes + g0 * S, rows * row_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(tm.e0, st));
+        MSNV_TRY(tm.begin(st));
         const uint32_t blocks = (uint32_t)std::min<uint64_t>((cells + 255) / 256, dev_resident_workgroups(8));
         hipLaunchKernelGGL(msnv_gc_min_positive, dim3(blocks), dim3(256), 0, st, d_genes.as<double>(), cells, d_flags.as<unsigned long long>());
-        if (int rc = timed_end()) return rc;
+        MSNV_TRY(tm.end(st));
     }
     unsigned long long min_bits = 0;
     HIP_TRY(hipMemcpy(&min_bits, d_flags.p, 8, hipMemcpyDeviceToHost));
@@ -448,18 +422,18 @@ int dev_gene_corr(uint32_t K1, uint64_t G, uint32_t S, const double *clust, cons
     memcpy(&min_pos, &min_bits, 8);
     const double pc = min_pos / 1000.0;
     uint32_t *bad = (uint32_t *)((char *)d_flags.p + 8);
-    HIP_TRY(hipEventRecord(tm.e0, st));
+    MSNV_TRY(tm.begin(st));
     hipLaunchKernelGGL(msnv_gc_cluster_rows, dim3(K1), dim3(T), lds, st, d_clust.as<double>(), S, P, pc, d_crank.as<double>(), d_clog.as<double>(),
                        d_csum.as<double>(), d_cvalid.as<uint8_t>(), bad);
-    if (int rc = timed_end()) return rc;
+    MSNV_TRY(tm.end(st));
     // pass 2: one workgroup per gene row
     for (uint64_t g0 = 0; g0 < G; g0 += chunk_rows) {
         const uint64_t rows = std::min(chunk_rows, G - g0);
         if (!whole) HIP_TRY(hipMemcpyAsync(d_genes.p, genes + g0 * S, rows * row_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(tm.e0, st));
+        MSNV_TRY(tm.begin(st));
         hipLaunchKernelGGL(msnv_gc_gene_rows, dim3((uint32_t)rows), dim3(T), lds, st, d_genes.as<double>(), S, P, pc, K1, d_crank.as<double>(), d_clog.as<double>(),
                            d_csum.as<double>(), d_cvalid.as<uint8_t>(), G, g0, d_rho.as<double>(), d_r.as<double>(), d_valid.as<uint8_t>(), bad);
-        if (int rc = timed_end()) return rc;
+        MSNV_TRY(tm.end(st));
     }
     uint32_t bad_host = 0;
     HIP_TRY(hipMemcpy(&bad_host, bad, 4, hipMemcpyDeviceToHost));
@@ -468,7 +442,7 @@ int dev_gene_corr(uint32_t K1, uint64_t G, uint32_t S, const double *clust, cons
     HIP_TRY(hipMemcpy(r, d_r.p, n_out * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(valid, d_valid.p, n_out, hipMemcpyDeviceToHost));
     if (pseudocount) *pseudocount = pc;
-    if (ms_kernel) *ms_kernel += ms_sum;
+    if (ms_kernel) *ms_kernel += tm.ms;
     return MSNV_OK;
 }
 
@@ -479,12 +453,10 @@ int dev_corr_stats(int method, uint64_t n, const double *est, const int32_t *n_o
     while (n_pad < n) n_pad <<= 1;
     const bool ci = method == 0 && lo && hi;
     Buf d_est, d_nobs, d_stat, d_p, d_lo, d_hi, d_q, d_key, d_idx;
-    HIP_TRY(hipMalloc(&d_est.p, n * 8)); HIP_TRY(hipMalloc(&d_nobs.p, n * 4));
-    HIP_TRY(hipMalloc(&d_stat.p, n * 8)); HIP_TRY(hipMalloc(&d_p.p, n * 8)); HIP_TRY(hipMalloc(&d_q.p, n * 8));
-    if (ci) { HIP_TRY(hipMalloc(&d_lo.p, n * 8)); HIP_TRY(hipMalloc(&d_hi.p, n * 8)); }
-    HIP_TRY(hipMalloc(&d_key.p, n_pad * 8)); HIP_TRY(hipMalloc(&d_idx.p, n_pad * 4));
-    HIP_TRY(hipMemcpyAsync(d_est.p, est, n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_nobs.p, n_obs, n * 4, hipMemcpyHostToDevice, st));
+    MSNV_TRY(d_est.upload(est, n * 8, st)); MSNV_TRY(d_nobs.upload(n_obs, n * 4, st));
+    MSNV_TRY(d_stat.alloc(n * 8)); MSNV_TRY(d_p.alloc(n * 8)); MSNV_TRY(d_q.alloc(n * 8));
+    if (ci) { MSNV_TRY(d_lo.alloc(n * 8)); MSNV_TRY(d_hi.alloc(n * 8)); }
+    MSNV_TRY(d_key.alloc(n_pad * 8)); MSNV_TRY(d_idx.alloc(n_pad * 4));
     hipLaunchKernelGGL(msnv_gc_stats, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, method, n, d_est.as<double>(), d_nobs.as<int32_t>(), d_stat.as<double>(),
                        d_p.as<double>(), d_lo.as<double>(), d_hi.as<double>());
     hipLaunchKernelGGL(msnv_bh_init, dim3((uint32_t)((n_pad + 255) / 256)), dim3(256), 0, st, d_p.as<double>(), n, n_pad, d_key.as<double>(), d_idx.as<uint32_t>());

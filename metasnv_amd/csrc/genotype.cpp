@@ -109,12 +109,9 @@ int read_clustering(const char *path, std::unordered_map<std::string, int64_t> &
         if (len == 0) continue;
         const char *t = (const char *)memchr(line, '\t', (size_t)len);
         if (!t || t == line || memchr(t + 1, '\t', (size_t)(line + len - t - 1))) { rc = fail(MSNV_EFORMAT, "%s:%llu: a row is a sample name and one cluster id", path, (unsigned long long)lineno); break; }
-        const char *d = t + 1;
-        if (*d == '-' || *d == '+') ++d;
-        bool digits = *d != 0 && strlen(d) <= 9;
-        for (const char *q = d; *q; ++q) digits = digits && *q >= '0' && *q <= '9';
-        if (!digits) { rc = fail(MSNV_EFORMAT, "%s:%llu: the cluster id '%s' is not an integer", path, (unsigned long long)lineno, t + 1); break; }
-        if (!id_of.emplace(std::string((const char *)line, t),(int64_t)atoll(t + 1)).second) rc = fail(MSNV_EFORMAT, "%s:%llu: sample '%.*s' is listed twice", path, (unsigned long long)lineno, (int)(t - line), line);
+        int64_t id;
+        if (!parse_small_int(t + 1, line + len, id)) { rc = fail(MSNV_EFORMAT, "%s:%llu: the cluster id '%s' is not an integer", path, (unsigned long long)lineno, t + 1); break; }
+        if (!id_of.emplace(std::string((const char *)line, t), id).second) rc = fail(MSNV_EFORMAT, "%s:%llu: sample '%.*s' is listed twice", path, (unsigned long long)lineno, (int)(t - line), line);
     }
     free(line);
     fclose(in);

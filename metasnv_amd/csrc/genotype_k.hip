@@ -22,7 +22,7 @@
 
 #include "device.h"
 #include "msnv_internal.h"
-#include "hiptry.h"
+#include "stagedev.h"
 
 #pragma clang fp contract(off)
 
@@ -84,62 +84,37 @@ __global__ void __launch_bounds__(GENO_ROWS_PER_BLOCK * 64) msnv_genotype_rows_k
     }
 }
 
-namespace {
-
-struct Buf {
-    void *p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-    template <class T> T *as() const { return (T *)p; }
-};
-
-struct Timer {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Timer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-};
-
-}  // namespace
-
 int dev_genotype_rows(const double *rows, uint64_t n_pos, uint32_t S, const uint32_t *col, const uint32_t *seg, uint32_t K, double threshold, void *stream_,
                       uint32_t *select_mask, uint32_t *flip_mask, uint8_t *near_flag, double *ms_kernel) {
     hipStream_t st = (hipStream_t)stream_;
     if (n_pos == 0) return MSNV_OK;
     const uint32_t n_used = seg[K];
     Buf d_rows, d_col, d_seg, d_sel, d_flip, d_near;
-    HIP_TRY(hipMalloc(&d_col.p, (size_t)std::max(n_used, 1u) * 4));
-    HIP_TRY(hipMalloc(&d_seg.p, (size_t)(K + 1) * 4));
-    HIP_TRY(hipMemcpyAsync(d_col.p, col, (size_t)n_used * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_seg.p, seg, (size_t)(K + 1) * 4, hipMemcpyHostToDevice, st));
-    Timer tm;
-    HIP_TRY(hipEventCreate(&tm.e0)); HIP_TRY(hipEventCreate(&tm.e1));
-    float ms_sum = 0;
+    MSNV_TRY(d_col.upload(col, (size_t)n_used * 4, st));
+    MSNV_TRY(d_seg.upload(seg, (size_t)(K + 1) * 4, st));
     // row slabs that fit the device: the table's slab and 9 bytes of results per row
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    const uint64_t row_bytes = (uint64_t)S * 8, per_row = row_bytes + 9;
-    const uint64_t chunk = std::min<uint64_t>(std::min<uint64_t>(n_pos, (uint64_t)(free_b * 0.5) / per_row), std::max<uint64_t>(1, GENO_SLAB_BYTES / row_bytes));
-    if (chunk == 0) return fail(MSNV_ENOMEM, "genotyping positions: %llu bytes of device memory left, one table row takes %llu", (unsigned long long)free_b, (unsigned long long)per_row);
-    HIP_TRY(hipMalloc(&d_rows.p, chunk * row_bytes));
-    HIP_TRY(hipMalloc(&d_sel.p, chunk * 4));
-    HIP_TRY(hipMalloc(&d_flip.p, chunk * 4));
-    HIP_TRY(hipMalloc(&d_near.p, chunk));
+    const uint64_t row_bytes = (uint64_t)S * 8;
+    uint64_t chunk = 0;
+    MSNV_TRY(slab_rows(n_pos, row_bytes + 9, 0.5, std::max<uint64_t>(1, GENO_SLAB_BYTES / row_bytes), "genotyping positions", &chunk));
+    MSNV_TRY(d_rows.alloc(chunk * row_bytes));
+    MSNV_TRY(d_sel.alloc(chunk * 4));
+    MSNV_TRY(d_flip.alloc(chunk * 4));
+    MSNV_TRY(d_near.alloc(chunk));
+    KernelTimer tm;
     for (uint64_t p0 = 0; p0 < n_pos; p0 += chunk) {
         const uint64_t np = std::min(chunk, n_pos - p0);
         HIP_TRY(hipMemcpyAsync(d_rows.p, rows + p0 * S, np * row_bytes, hipMemcpyHostToDevice, st));
         const uint32_t grid = (uint32_t)std::min<uint64_t>((np + GENO_ROWS_PER_BLOCK - 1) / GENO_ROWS_PER_BLOCK, GENO_GRID_BLOCKS);
-        HIP_TRY(hipEventRecord(tm.e0, st));
+        MSNV_TRY(tm.begin(st));
         hipLaunchKernelGGL(msnv_genotype_rows_k, dim3(grid), dim3(GENO_ROWS_PER_BLOCK * 64), 0, st, d_rows.as<double>(), (unsigned long long)np, S, d_col.as<uint32_t>(),
                            d_seg.as<uint32_t>(), K, threshold, d_sel.as<uint32_t>(), d_flip.as<uint32_t>(), d_near.as<uint8_t>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(tm.e1, st));
+        MSNV_TRY(tm.stop(st));
         HIP_TRY(hipMemcpyAsync(select_mask + p0, d_sel.p, np * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(flip_mask + p0, d_flip.p, np * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(near_flag + p0, d_near.p, np, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        float t = 0;
-        HIP_TRY(hipEventElapsedTime(&t, tm.e0, tm.e1));
-        ms_sum += t;
+        MSNV_TRY(tm.wait(st));
     }
-    if (ms_kernel) *ms_kernel += ms_sum;
+    if (ms_kernel) *ms_kernel += tm.ms;
     return MSNV_OK;
 }
 

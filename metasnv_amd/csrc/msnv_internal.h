@@ -119,12 +119,19 @@ void py_repr(double x, std::string &out);                                   // f
 bool pandas_strtod(const char *s, const char *end, double &out);            // dist.cpp: pandas' default float converter
 int read_freq(const char *freq_path, std::vector<std::string> &names, std::vector<std::string> *labels, std::vector<double> &rows, uint64_t &n_pos);   // dist.cpp: a *.filtered.freq table
 int write_matrix(const char *path, const std::vector<std::string> &names, const std::vector<double> &m);
-// ... and as R does (cluster.cpp; the subpopr stages share them)
+// ... and as R does, with the text helpers the subpopr stages share (rtext.cpp)
 double r_mean(const double *x, size_t n);                                   // mean(): long double, two passes
 double r_sd(const double *x, size_t n);                                     // sd(): squared deviations from mean() in long double, n - 1; n >= 2
 void r_double(double v, std::string &out);                                 // write.table's %.15g; NaN as "NaN"
+void r_value(double v, std::string &out);                                  // r_double, and Inf / -Inf as R writes them
+int slurp(const std::string &path, std::string &out);                       // the whole file, appended to out
 int write_text(const std::string &path, const std::string &text);
+int append_line(const std::string &path, const std::string &line);          // R's write(x, file, append = T): the line and a newline
 int make_dir(const std::string &path);                                      // an existing directory is fine
+typedef std::pair<const char *, const char *> Span;                         // [first, second) of a text that outlives it; no terminator behind it
+void split_span(const char *s, const char *e, char sep, std::vector<Span> &out);   // str.split(sep): every field, empty ones included
+bool parse_finite(const char *s, const char *e, double &v);                 // a finite number that starts with a digit, '.', '+' or '-' and is consumed whole
+bool parse_small_int(const char *s, const char *e, int64_t &v);             // an optional sign and one to nine digits
 
 // ---------------------------------------------------------------------------------- synthetic workload (synth.cpp)
 std::vector<std::string> synth_contigs(const msnv_synth_params &p);

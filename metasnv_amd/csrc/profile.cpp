@@ -13,7 +13,7 @@
 // copy that also goes to the device.  R computes them in long double (a sequential 80-bit sum, a second pass over the deviations, for sd the
 // squared deviations about the mean rounded to double); an fp64 device sum cannot reproduce that bit for bit, and no guard is practical: the long
 // double rule's own error bound, about G * 2^-64 relative, already reaches the 15th printed digit at real G, so a device value could not be told
-// from a wrong one by a bound.  The two columns drive no decision; r_mean and r_sd (cluster.cpp) state the rule.
+// from a wrong one by a bound.  The two columns drive no decision; r_mean and r_sd (rtext.cpp) state the rule.
 // Everything here is restated from reading the R code; no R was run (unpinned, with the divergences: byte order of the cluster
 // files where list.files sorts by locale; a listed position the .pos.freq lacks is one all-NA row whether flipped or not; the two cases where R binds
 // columns of different samples are refused; a duplicate id is refused; a single frequency column is kept a table in the abundance stage).
@@ -33,16 +33,6 @@
 namespace msnv {
 
 namespace {
-
-int slurp(const std::string &path, std::string &out) {
-    FILE *f = fopen(path.c_str(), "rb");
-    if (!f) return fail(MSNV_EIO, "Cannot open %s: %s", path.c_str(), strerror(errno));
-    char buf[1 << 16];
-    size_t n;
-    while ((n = fread(buf, 1, sizeof buf, f)) > 0) out.append(buf, n);
-    fclose(f);
-    return MSNV_OK;
-}
 
 // the non-empty lines of a text, without their newline and a carriage return before it
 std::vector<std::string> lines_of(const std::string &text) {
@@ -67,22 +57,7 @@ std::vector<std::string> split(const std::string &s, char sep) {
     return out;
 }
 
-bool parse_number(const std::string &t, double &v) {
-    if (t.empty()) return false;
-    const char c = t[0];
-    if (!((c >= '0' && c <= '9') || c == '.' || c == '-' || c == '+')) return false;
-    char *end = nullptr;
-    v = strtod(t.c_str(), &end);
-    return end == t.c_str() + t.size() && std::isfinite(v);
-}
-
-bool parse_int(const std::string &t, int64_t &v) {
-    size_t d = (!t.empty() && (t[0] == '-' || t[0] == '+')) ? 1 : 0;
-    if (t.size() == d || t.size() - d > 9) return false;
-    for (size_t i = d; i < t.size(); ++i) if (t[i] < '0' || t[i] > '9') return false;
-    v = atoll(t.c_str());
-    return true;
-}
+inline bool parse_number(const std::string &t, double &v) { return parse_finite(t.data(), t.data() + t.size(), v); }
 
 // contig:ann:pos:base -> contig:pos:base (writeSubpopsForAllSamples.R:57-58)
 bool freq_id(const std::string &id, std::string &out) {
@@ -128,17 +103,6 @@ struct Cluster {
     int64_t number;
     std::vector<SummaryRow> rows;                                      // kept columns, in sample order
 };
-
-void put_int(uint64_t v, std::string &out) { out += std::to_string(v); }
-
-int append_line(const std::string &path, const std::string &line) {     // write(x, file, append = T)
-    FILE *f = fopen(path.c_str(), "a");
-    if (!f) return fail(MSNV_EIO, "Cannot open %s: %s", path.c_str(), strerror(errno));
-    fwrite(line.data(), 1, line.size(), f);
-    fputc('\n', f);
-    if (fclose(f) != 0) return fail(MSNV_EIO, "write error on %s: %s", path.c_str(), strerror(errno));
-    return MSNV_OK;
-}
 
 // one cluster: the G x S matrix in the order of the positions file, the kernel, the kept columns
 int profile_cluster(msnv_ctx *ctx, const std::string &freq_path, const std::string &hap_path, const std::vector<std::string> &samples, double max_prop_uncalled,
@@ -299,7 +263,7 @@ extern "C" int msnv_subpop_profile_files(msnv_ctx *ctx, const char *species, con
         const std::string spec_hap = name.substr(0, name.find('.'));
         const size_t us = spec_hap.rfind('_');
         Cluster cl;
-        if (us == std::string::npos || !parse_int(spec_hap.substr(us + 1), cl.number))
+        if (us == std::string::npos || !parse_small_int(spec_hap.data() + us + 1, spec_hap.data() + spec_hap.size(), cl.number))
             return fail(MSNV_EFORMAT, "Species-cluster name did not conform to expectations. Expected something like: 537011_1 or ref_mOTU_v2_2227_1 where final number after "
                         "underscore is the cluster. Instead got: %s", spec_hap.c_str());
         if (int rc = profile_cluster(ctx, dir + name, dir + spec_hap + "_hap_positions.tab", samples, max_prop_uncalled, cl, ms_kernel)) return rc;
@@ -320,7 +284,7 @@ extern "C" int msnv_subpop_profile_files(msnv_ctx *ctx, const char *species, con
                 r_double(r.mean, t); t.push_back('\t'); r_double(r.median, t); t.push_back('\t');
                 if (r.sd_na) t += "NA"; else r_double(r.sd, t);
                 t.push_back('\t'); r_double(r.prevalence, t); t.push_back('\t'); r_double(r.prevalence5, t); t.push_back('\t');
-                put_int(r.n0, t); t.push_back('\t'); put_int(r.n100, t); t.push_back('\t'); put_int(r.n_na, t); t.push_back('\n');
+                t += std::to_string(r.n0); t.push_back('\t'); t += std::to_string(r.n100); t.push_back('\t'); t += std::to_string(r.n_na); t.push_back('\n');
             }
         if (int rc = write_text(prefix + "_abundanceSummaryStats.tsv", t)) return rc;
     }

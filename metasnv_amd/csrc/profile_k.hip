@@ -25,7 +25,7 @@
 
 #include "device.h"
 #include "msnv_internal.h"
-#include "hiptry.h"
+#include "stagedev.h"
 
 namespace msnv {
 
@@ -133,21 +133,6 @@ __global__ void __launch_bounds__(PROF_WAVES * 64) msnv_profile_columns_k(const 
     }
 }
 
-namespace {
-
-struct Buf {
-    void *p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-    template <class T> T *as() const { return (T *)p; }
-};
-
-struct Timer {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Timer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-};
-
-}  // namespace
-
 int dev_profile_columns(const double *rows, uint32_t n_rows, uint32_t S, const uint8_t *flip, uint32_t cols_per_pass, void *stream_, uint32_t *counts[5],
                         double *mid_lo, double *mid_hi, bool *outside, double *ms_kernel) {
     hipStream_t st = (hipStream_t)stream_;
@@ -162,41 +147,34 @@ int dev_profile_columns(const double *rows, uint32_t n_rows, uint32_t S, const u
     if (!cols_per_pass && band < S && band > PROF_COLS) band -= band % PROF_COLS;       // whole workgroups, rows that start on a 128-byte line
     const uint32_t ld = (uint32_t)band;
     Buf d_rows, d_flip, d_counts, d_mids, d_flag;
-    HIP_TRY(hipMalloc(&d_rows.p, (size_t)n_rows * ld * 8));
-    HIP_TRY(hipMalloc(&d_flip.p, n_rows));
-    HIP_TRY(hipMalloc(&d_counts.p, (size_t)5 * ld * 4));
-    HIP_TRY(hipMalloc(&d_mids.p, (size_t)2 * ld * 8));
-    HIP_TRY(hipMalloc(&d_flag.p, 4));
-    HIP_TRY(hipMemcpyAsync(d_flip.p, flip, n_rows, hipMemcpyHostToDevice, st));
+    MSNV_TRY(d_rows.alloc((size_t)n_rows * ld * 8));
+    MSNV_TRY(d_flip.upload(flip, n_rows, st));
+    MSNV_TRY(d_counts.alloc((size_t)5 * ld * 4));
+    MSNV_TRY(d_mids.alloc((size_t)2 * ld * 8));
+    MSNV_TRY(d_flag.alloc(4));
     HIP_TRY(hipMemsetAsync(d_flag.p, 0, 4, st));
-    Timer tm;
-    HIP_TRY(hipEventCreate(&tm.e0)); HIP_TRY(hipEventCreate(&tm.e1));
-    float ms_sum = 0;
+    KernelTimer tm;
     std::vector<uint32_t> h_counts((size_t)5 * ld);
     std::vector<double> h_mids((size_t)2 * ld);
     for (uint32_t c0 = 0; c0 < S; c0 += ld) {
         const uint32_t nc = std::min(ld, S - c0);
         if (nc == S) HIP_TRY(hipMemcpyAsync(d_rows.p, rows, (size_t)n_rows * S * 8, hipMemcpyHostToDevice, st));
         else HIP_TRY(hipMemcpy2DAsync(d_rows.p, (size_t)ld * 8, rows + c0, (size_t)S * 8, (size_t)nc * 8, n_rows, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(tm.e0, st));
+        MSNV_TRY(tm.begin(st));
         hipLaunchKernelGGL(msnv_profile_columns_k, dim3((nc + PROF_COLS - 1) / PROF_COLS), dim3(PROF_WAVES * 64), 0, st, d_rows.as<double>(), n_rows, ld, nc,
                            d_flip.as<uint8_t>(), d_counts.as<uint32_t>(), d_mids.as<double>(), d_flag.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(tm.e1, st));
+        MSNV_TRY(tm.stop(st));
         HIP_TRY(hipMemcpyAsync(h_counts.data(), d_counts.p, h_counts.size() * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(h_mids.data(), d_mids.p, h_mids.size() * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        MSNV_TRY(tm.wait(st));
         for (uint32_t i = 0; i < 5; ++i) std::copy_n(h_counts.data() + (size_t)i * ld, nc, counts[i] + c0);
         std::copy_n(h_mids.data(), nc, mid_lo + c0);
         std::copy_n(h_mids.data() + ld, nc, mid_hi + c0);
-        float t = 0;
-        HIP_TRY(hipEventElapsedTime(&t, tm.e0, tm.e1));
-        ms_sum += t;
     }
     uint32_t flag = 0;
     HIP_TRY(hipMemcpy(&flag, d_flag.p, 4, hipMemcpyDeviceToHost));
     *outside = flag != 0;
-    if (ms_kernel) *ms_kernel += ms_sum;
+    if (ms_kernel) *ms_kernel += tm.ms;
     return MSNV_OK;
 }
 

@@ -22,26 +22,8 @@ namespace msnv {
 
 namespace {
 
-int read_file(const char *path, std::string &out) {
-    FILE *f = fopen(path, "rb");
-    if (!f) return fail(MSNV_EIO, "Cannot open %s: %s", path, strerror(errno));
-    char buf[1 << 16];
-    size_t n;
-    while ((n = fread(buf, 1, sizeof buf, f)) > 0) out.append(buf, n);
-    fclose(f);
-    return MSNV_OK;
-}
-
 // str.rstrip(): Python's whitespace set for ASCII text
 inline bool py_space(char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\v' || c == '\f' || c == '\x1c' || c == '\x1d' || c == '\x1e' || c == '\x1f'; }
-
-// str.split(sep) into string views (every field, empty ones included)
-void split_char(const char *s, const char *e, char sep, std::vector<std::pair<const char *, const char *>> &out) {
-    out.clear();
-    const char *b = s;
-    for (const char *p = s; p <= e; ++p)
-        if (p == e || *p == sep) { out.emplace_back(b, p); b = p + 1; }
-}
 
 // int(text) for the digit strings these files hold (optional sign, surrounding blanks); false when Python would raise
 bool py_int(const char *s, const char *e, long long &v) {
@@ -73,7 +55,7 @@ extern "C" int msnv_genotyping_subset(const char *const *hap_paths, int32_t n_ha
     std::unordered_map<std::string, int> file_of;                     // species + ".pos" -> index
     std::unordered_map<std::string, std::vector<int>> wanted;         // "contig:pos" -> the files that listed it, in listing order
     auto close_all = [&]() { for (FILE *f : files) if (f) fclose(f); };
-    std::vector<std::pair<const char *, const char *>> f, c;
+    std::vector<Span> f, c;
     for (int i = 0; i < n_hap; ++i) {
         std::string base = hap_paths[i];
         const size_t slash = base.rfind('/');
@@ -89,7 +71,7 @@ extern "C" int msnv_genotyping_subset(const char *const *hap_paths, int32_t n_ha
             fi = (int)files.size(); files.push_back(o); file_of.emplace(key, fi);
         } else fi = it->second;
         std::string text;
-        if (int rc = read_file(hap_paths[i], text)) { close_all(); return rc; }
+        if (int rc = slurp(hap_paths[i], text)) { close_all(); return rc; }
         const char *p = text.data(), *end = p + text.size();
         const char *nl = (const char *)memchr(p, '\n', (size_t)(end - p));
         p = nl ? nl + 1 : end;                                       // the header line (:26)
@@ -97,9 +79,9 @@ extern "C" int msnv_genotyping_subset(const char *const *hap_paths, int32_t n_ha
             nl = (const char *)memchr(p, '\n', (size_t)(end - p));
             const char *le = nl ? nl : end, *next = nl ? nl + 1 : end;
             while (le > p && py_space(le[-1])) --le;                  // line.rstrip()
-            split_char(p, le, '\t', f);
+            split_span(p, le, '\t', f);
             if (f.size() < 2) { close_all(); return fail(MSNV_EFORMAT, "%s: a line has no second field (the reference stops with an IndexError)", hap_paths[i]); }
-            split_char(f[1].first, f[1].second, ':', c);
+            split_span(f[1].first, f[1].second, ':', c);
             if (c.size() < 3) { close_all(); return fail(MSNV_EFORMAT, "%s: position id without contig:gene:pos (the reference stops with an IndexError)", hap_paths[i]); }
             std::string code(c[0].first, c[0].second);
             code.push_back(':'); code.append(c[2].first, c[2].second);
@@ -116,7 +98,7 @@ extern "C" int msnv_genotyping_subset(const char *const *hap_paths, int32_t n_ha
     std::string code;
     for (int i = 0; i < n_snp; ++i) {
         std::string text;
-        if (int rc = read_file(snp_paths[i], text)) { close_all(); return rc; }
+        if (int rc = slurp(snp_paths[i], text)) { close_all(); return rc; }
         const char *p = text.data(), *end = p + text.size();
         while (p < end) {
             const char *nl = (const char *)memchr(p, '\n', (size_t)(end - p));
@@ -145,23 +127,23 @@ extern "C" int msnv_snv_allele_freq(msnv_ctx *ctx, const char *pos_path, int32_t
     if (int rc = dev_set_device(ctx->device)) return rc;
     if (ms_kernel) *ms_kernel = 0;
     std::string text;
-    if (int rc = read_file(pos_path, text)) return rc;
+    if (int rc = slurp(pos_path, text)) return rc;
     const std::string out_path = std::string(pos_path) + ".freq";
     FILE *out = fopen(out_path.c_str(), "w");                         // created before the first line is read (:4)
     if (!out) return fail(MSNV_EIO, "Cannot open %s: %s", out_path.c_str(), strerror(errno));
     std::vector<uint32_t> cov, cnt, row_line;
     std::vector<std::string> ids;
     uint32_t S = 0, n_lines = 0;
-    std::vector<std::pair<const char *, const char *>> c, cv, al, s;
+    std::vector<Span> c, cv, al, s;
     const char *p = text.data(), *end = p + text.size();
     int rc = MSNV_OK;
     while (p < end && !rc) {
         const char *nl = (const char *)memchr(p, '\n', (size_t)(end - p));
         const char *le = nl ? nl : end, *next = nl ? nl + 1 : end;
         while (le > p && py_space(le[-1])) --le;                      // line.rstrip()
-        split_char(p, le, '\t', c);
+        split_span(p, le, '\t', c);
         if (c.size() < 6) { rc = fail(MSNV_EFORMAT, "%s: line %u has fewer than six fields (the reference stops with an IndexError)", pos_path, n_lines + 1); break; }
-        split_char(c[4].first, c[4].second, '|', cv);
+        split_span(c[4].first, c[4].second, '|', cv);
         if (n_lines == 0) S = (uint32_t)cv.size();
         // one kernel launch over a rectangular table: every line must carry the same number of samples (one run's files do)
         if (cv.size() != S) { rc = fail(MSNV_EFORMAT, "%s: line %u lists %zu coverages, the first line %u", pos_path, n_lines + 1, cv.size(), S); break; }
@@ -175,9 +157,9 @@ extern "C" int msnv_snv_allele_freq(msnv_ctx *ctx, const char *pos_path, int32_t
         if (rc) break;
         std::string id(c[0].first, c[0].second);
         id.push_back(':'); id.append(c[1].first, c[1].second); id.push_back(':'); id.append(c[2].first, c[2].second);
-        split_char(c[5].first, c[5].second, ',', al);
+        split_span(c[5].first, c[5].second, ',', al);
         for (auto &a : al) {
-            split_char(a.first, a.second, '|', s);
+            split_span(a.first, a.second, '|', s);
             if (s.size() < 2) { rc = fail(MSNV_EFORMAT, "%s: line %u: allele entry without a base (the reference stops with an IndexError)", pos_path, n_lines + 1); break; }
             if (s.size() != (size_t)S + 3 && !(s.size() < 3 && S == 0)) {
                 if (s.size() > (size_t)S + 3) rc = fail(MSNV_EFORMAT, "%s: line %u: more allele counts than coverages (the reference stops with an IndexError)", pos_path, n_lines + 1);

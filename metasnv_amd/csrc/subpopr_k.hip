@@ -12,7 +12,7 @@
 
 #include "device.h"
 #include "msnv_internal.h"
-#include "hiptry.h"
+#include "stagedev.h"
 
 namespace msnv {
 
@@ -34,32 +34,20 @@ int dev_allele_freq(const std::vector<uint32_t> &cov, const std::vector<uint32_t
     const uint64_t n_cells = cnt.size();
     freq.assign(n_cells, 0.0);
     if (!n_cells) return MSNV_OK;
-    struct Buf { void *p = nullptr; ~Buf() { if (p) (void)hipFree(p); } };
     Buf d_cov, d_cnt, d_rl, d_fr;
-    auto up = [&](Buf &buf, const void *src, size_t bytes) -> int {
-        HIP_TRY(hipMalloc(&buf.p, bytes ? bytes : 16));
-        if (bytes) HIP_TRY(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, st));
-        return MSNV_OK;
-    };
-    if (int rc = up(d_cov, cov.data(), cov.size() * 4)) return rc;
-    if (int rc = up(d_cnt, cnt.data(), cnt.size() * 4)) return rc;
-    if (int rc = up(d_rl, row_line.data(), row_line.size() * 4)) return rc;
-    HIP_TRY(hipMalloc(&d_fr.p, n_cells * sizeof(double)));
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    hipError_t he = hipEventRecord(e0, st);
+    MSNV_TRY(d_cov.upload(cov.data(), cov.size() * 4, st));
+    MSNV_TRY(d_cnt.upload(cnt.data(), cnt.size() * 4, st));
+    MSNV_TRY(d_rl.upload(row_line.data(), row_line.size() * 4, st));
+    MSNV_TRY(d_fr.alloc(n_cells * sizeof(double)));
+    KernelTimer tm;
+    MSNV_TRY(tm.begin(st));
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_cells + 255) / 256, 65536);
-    hipLaunchKernelGGL(msnv_allele_freq_pct, dim3(blocks), dim3(256), 0, st, (const uint32_t *)d_cov.p, (const uint32_t *)d_cnt.p,
-                       (const uint32_t *)d_rl.p, n_samples, n_cells, min_depth, (double *)d_fr.p);
-    if (he == hipSuccess) he = hipGetLastError();
-    if (he == hipSuccess) he = hipEventRecord(e1, st);
-    if (he == hipSuccess) he = hipMemcpyAsync(freq.data(), d_fr.p, n_cells * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess) he = hipStreamSynchronize(st);
-    float t = 0;
-    if (he == hipSuccess) he = hipEventElapsedTime(&t, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (he != hipSuccess) return fail(MSNV_EHIP, "allele frequency kernel: %s", hipGetErrorString(he));
-    if (ms_kernel) *ms_kernel += t;
+    hipLaunchKernelGGL(msnv_allele_freq_pct, dim3(blocks), dim3(256), 0, st, d_cov.as<uint32_t>(), d_cnt.as<uint32_t>(), d_rl.as<uint32_t>(), n_samples, n_cells,
+                       min_depth, d_fr.as<double>());
+    MSNV_TRY(tm.stop(st));
+    HIP_TRY(hipMemcpyAsync(freq.data(), d_fr.p, n_cells * sizeof(double), hipMemcpyDeviceToHost, st));
+    MSNV_TRY(tm.wait(st));
+    if (ms_kernel) *ms_kernel += tm.ms;
     return MSNV_OK;
 }
 

@@ -60,6 +60,7 @@ static const Row rows[] = {
     {"tail_skip", [] { return unum(knob::tail_skip()); }},
     {"dev_cache_mb", [] { return num(knob::dev_cache_mb()); }},
     {"text_repeat", [] { return num(knob::text_repeat()); }},
+    {"stage_slab_rows", [] { return unum(knob::stage_slab_rows()); }},
     // integers over a default of the call site
     {"gather_split_2", [] { return unum(knob::gather_split(2)); }},
     {"chunk_cap_777", [] { return unum(knob::chunk_cap(777)); }},

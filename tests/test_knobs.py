@@ -173,6 +173,8 @@ PARSING = {
     "dev_cache_mb": ("MSNV_DEV_CACHE_MB", ["-1", "0", "0", "1", "0", "0", BIG], {}),
     # e ? max(1, atoi(e)) : 1
     "text_repeat": ("MSNV_TEXT_REPEAT", ["1", "1", "1", "1", "1", "1", ATOI_BIG], {"3": "3"}),
+    # max(0, e ? atoll(e) : 0): 0 = no cap (new with stagedev.h: written from the accessor's comment, not from an earlier site)
+    "stage_slab_rows": ("MSNV_STAGE_SLAB_ROWS", ["0", "0", "0", "1", "0", "0", BIG], {"7": "7"}),
     # if (e) gather_split = max(1, atoi(e)) -- over the dataset's 2
     "gather_split_2": ("MSNV_GATHER_SPLIT", ["2", "1", "1", "1", "1", "1", ATOI_BIG], {"4": "4"}),
     # if (e) chunk_cap = max(0, atoll(e)) -- over the dataset's 777
@@ -207,7 +209,8 @@ def test_an_accessor_returns_what_its_sites_returned(harness, accessor):
 PER_CALL = [("pack_on_host", "MSNV_PACK", "host", "0", "1"), ("inflate_where", "MSNV_INFLATE", "device", "-", "d"), ("cov_late", "MSNV_COV_LATE", "1", "0", "1"),
             ("split_at_255", "MSNV_SPLIT_AT", "40", "192", "40"), ("group_depth", "MSNV_GROUP_DEPTH", "24", "128", "24"), ("cov_narrow_max", "MSNV_COV_NARROW_MAX", "1", "32767", "1"),
             ("scan_sub_bytes_round", "MSNV_SCAN_SUB", "256", "6144", "256"), ("chunk_cap_777", "MSNV_CHUNK_CAP", "5", "777", "5"), ("taper_at", "MSNV_TAPER_AT", "1,2,3", "1.8,0.73,0.27", "1,2,3"),
-            ("inflate_check_every", "MSNV_INFLATE_CHECK", "0", "1", "0"), ("guard_fill", "MSNV_GUARD_FILL", "255", "-", "255"), ("merged_gather", "MSNV_MERGED_GATHER", "block", "0", "1")]
+            ("inflate_check_every", "MSNV_INFLATE_CHECK", "0", "1", "0"), ("guard_fill", "MSNV_GUARD_FILL", "255", "-", "255"), ("merged_gather", "MSNV_MERGED_GATHER", "block", "0", "1"),
+            ("stage_slab_rows", "MSNV_STAGE_SLAB_ROWS", "5", "0", "5")]
 ONCE = [("guard_alloc", "MSNV_GUARD_ALLOC", "1", "0"), ("inflate_zlib", "MSNV_INFLATE", "zlib", "0"), ("debug_sync", "MSNV_DEBUG_SYNC", "1", "0"),
         ("depth_on_main", "MSNV_DEPTH_STREAM", "main", "0"), ("scatter_blocks_16", "MSNV_SCATTER_BLOCKS", "64", "16"), ("finalize_trace", "MSNV_FINALIZE_TRACE", "1", "0"),
         ("crc_table", "MSNV_CRC", "table", "0"), ("huge_pages", "MSNV_HUGE", "2", "1"), ("tail_skip", "MSNV_TAIL_SKIP", "3", "0"), ("dev_cache_mb", "MSNV_DEV_CACHE_MB", "5", "-1")]
