@@ -369,6 +369,46 @@ int msnv_cluster_boot(msnv_ctx *ctx, int32_t n, const double *dist, int32_t m, c
 int msnv_membership_stability_file(msnv_ctx *ctx, const char *dist_used_path, const char *clus_num_stability_path, const char *species,
                                    int32_t k, const char *out_dir, const msnv_membstab_opts *opts, int64_t result[8], double *ms_kernel);
 
+/* subpopr's computePCoA (src/subpopr/R/clustering.R:120-126, :472-505): ape::pcoa(correction = "none") of a species' distance matrix, the
+ * numbers behind the ordination plots.  Restated from reading the R code and from memory of ape; no R was run (DESIGN.md section 7:
+ * unpinned).  The eigen solver is hand-written and its result is a function of the matrix alone.
+ *
+ * msnv_pcoa -- the array form.  dist: the n x n matrix under msnv_pam_tasks' checks (2 <= n <= 4096, symmetric, zero diagonal, finite,
+ * >= 0: else MSNV_EDOMAIN); 1 <= n_axes <= n (else MSNV_EINVAL).  Every operation is one fp64 operation, never contracted.
+ *   centring   A_ij = -0.5 (d_ij d_ij); r_i = (sum of A_ij, j ascending) / n; g = (sum of r_i, i ascending) / n;
+ *              B_ij = ((A_ij - r_i) - r_j) + g for i <= j, mirrored into j > i; trace = sum of B_ii, i ascending
+ *   Jacobi     two-sided, cyclic, round-robin: m = n + (n & 1); a sweep is the steps r = 0..m-2; step r holds slot 0 = (m - 1, r) and slot
+ *              i = ((r + i) mod (m - 1), (r - i) mod (m - 1)), i = 1..m/2-1, each ordered p < q; a slot that holds index n is the bye
+ *              (one index).  A pair rotates when |a_pq| > tol = 2^-52 max |B_ij|: theta = (a_qq - a_pp) / (2 a_pq), t = (theta >= 0 ? 1
+ *              : -1) / (|theta| + sqrt(theta theta + 1)), c = 1 / sqrt(t t + 1), s = t c; else t = 0, c = 1, s = 0.  All rotations of a
+ *              step are applied together, block by block: the 2 x 2 block (rows of slot I, columns of slot J), I < J, becomes, columns
+ *              first, x' = c_J x - s_J y, y' = s_J x + c_J y, then rows with c_I, s_I in the same form, and is written to itself and,
+ *              transposed, to its mirror; the bye's blocks have one row and take the columns' rotation alone.  A pair's own block:
+ *              a_pp - t a_pq, a_qq + t a_pq, a_pq = a_qp = 0 when it rotated.  V starts as I and takes the column form of every step.
+ *              The solve ends after the first sweep in which no pair rotated; 64 sweeps without that are MSNV_EDOMAIN.
+ *   output     eig[n]: the diagonal sorted descending (equal values in ascending diagonal position), |lambda| < sqrt(2^-52) set to 0;
+ *              rel_eig = lambda / trace; axis_pct = max(lambda, 0) / (sum of max(lambda, 0) in sorted order) * 100 (getEig); k = the
+ *              number of lambda > sqrt(2^-52); vectors row-major [n][n_axes]: column a < k is the eigenvector times sqrt(lambda_a),
+ *              negated when its component of largest magnitude (the first of equals) is negative -- R's signs are LAPACK's accident --
+ *              and a column a >= k is all NaN.
+ * info: [0] MSNV_PCOA_* [1] sweeps [2] rotations applied [3] k [4] eigenvalues < -sqrt(2^-52) [5..7] 0.
+ *
+ * msnv_pcoa_file -- the stage on files.  Reads dist_path (<species>.filtered.mann.dist, as msnv_cluster_file does), removes outliers by
+ * the same routine and ordinates the remaining samples with two axes.  dir is msnv_cluster_file's out_dir or its noClustering/: clust
+ * comes from dir/<species>_mann_clustering.tab (a sample it does not list: NA), propFreqHomog from the freq_data_sample_10_90 column of
+ * dir/<species>_freq_composition.tab (NA when the file is absent or does not list the sample).  Written into dir, as write.table(sep =
+ * '\t', quote = F) prints them, doubles with %.15g:
+ *   <species>_mann_pcoa_proj.tab   Axis.1, Axis.2, propFreqHomog, clust; one row per sample.  Not written on MSNV_PCOA_TOO_FEW_AXES, the
+ *                                  reference's "Error during pcoa"
+ *   <species>_mann_pcoa_eig.tab    Eigenvalues, Relative_eig, axisPercent; rows 1..n.  Our own file: the reference keeps these numbers
+ *                                  for the axis labels of its plots only
+ * result: info's [0..4], then [5] samples ordinated [6] outliers removed [7] 0. */
+#define MSNV_PCOA_OK            0
+#define MSNV_PCOA_TOO_FEW_AXES  1   /* k < 2 */
+int msnv_pcoa(msnv_ctx *ctx, int32_t n, const double *dist, int32_t n_axes, double *eig, double *rel_eig, double *axis_pct, double *vectors,
+              int64_t info[8], double *ms_kernel);
+int msnv_pcoa_file(msnv_ctx *ctx, const char *dist_path, const char *dir, const char *species, int64_t result[8], double *ms_kernel);
+
 /* subpopr's writeGenotypeFreqs -> computeUniquePosPerCluster (src/subpopr/R/writeGenotypeFreqs.R:2-112, :195-277): which SNVs tell one
  * subspecies from every other.  Restated from reading the R code; no R was run (unpinned).
  *

@@ -28,6 +28,73 @@
 
 namespace msnv {
 
+// ---- what msnv_pcoa and msnv_pcoa_file (pcoa.cpp) share with this file (device.h)
+int check_matrix(const char *who, int64_t n, const double *d) {
+    if (n < 2 || n > (int64_t)CLUSTER_MAX_SAMPLES) return fail(MSNV_EDOMAIN, "%s: %lld samples (2 to %u)", who, (long long)n, CLUSTER_MAX_SAMPLES);
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t j = 0; j <= i; ++j) {
+            const double v = d[i * n + j];
+            if (!(v >= 0.0) || !std::isfinite(v)) return fail(MSNV_EDOMAIN, "%s: the distance of samples %lld and %lld is %g (distances are finite and >= 0)", who, (long long)i, (long long)j, v);
+            if (v != d[j * n + i]) return fail(MSNV_EDOMAIN, "%s: the matrix is not symmetric at (%lld, %lld)", who, (long long)i, (long long)j);
+            if (i == j && v != 0.0) return fail(MSNV_EDOMAIN, "%s: the diagonal is %g at sample %lld, not 0", who, v, (long long)i);
+        }
+    return MSNV_OK;
+}
+
+// <species>.filtered.mann.dist as write_matrix of dist.cpp writes it: a header of names behind an empty cell, then name + n cells per row.
+// r_form: the header as write.table prints it (write_dist below), n names and no leading cell.
+int read_dist(const char *path, std::vector<std::string> &names, std::vector<double> &d, bool r_form) {
+    FILE *in = fopen(path, "r");
+    if (!in) return fail(MSNV_EIO, "Cannot open %s: %s", path, strerror(errno));
+    char *line = nullptr; size_t cap = 0; ssize_t len;
+    uint64_t lineno = 0, n_rows = 0;
+    int rc = MSNV_OK;
+    while (rc == MSNV_OK && (len = getline(&line, &cap, in)) >= 0) {
+        ++lineno;
+        while (len && (line[len - 1] == '\n' || line[len - 1] == '\r')) line[--len] = 0;
+        if (lineno > 1 && len == 0) continue;
+        std::vector<std::string> f;
+        const char *s = line, *end = line + len;
+        while (true) {
+            const char *t = (const char *)memchr(s, '\t', (size_t)(end - s));
+            f.emplace_back(s, t ? t : end);
+            if (!t) break;
+            s = t + 1;
+        }
+        if (lineno == 1) { names.assign(f.begin() + (r_form ? 0 : 1), f.end()); continue; }
+        if (f.size() != names.size() + 1) { rc = fail(MSNV_EFORMAT, "%s:%llu: %zu cells for %zu samples", path, (unsigned long long)lineno, f.size() - 1, names.size()); break; }
+        if (n_rows >= names.size() || f[0] != names[n_rows]) { rc = fail(MSNV_EFORMAT, "%s:%llu: row '%s' does not follow the header's order", path, (unsigned long long)lineno, f[0].c_str()); break; }
+        for (size_t c = 1; c < f.size(); ++c) {
+            char *e = nullptr;
+            const double v = f[c].empty() || f[c] == "NA" ? 0.0 : strtod(f[c].c_str(), &e);
+            if (!e || e != f[c].c_str() + f[c].size()) { rc = fail(MSNV_EFORMAT, "%s:%llu: cell '%s' is not a number (NA and empty cells are refused: rmNAfromDistMatrix is not built)", path, (unsigned long long)lineno, f[c].c_str()); break; }
+            d.push_back(v);
+        }
+        ++n_rows;
+    }
+    free(line);
+    fclose(in);
+    if (rc) return rc;
+    if (n_rows != names.size()) return fail(MSNV_EFORMAT, "%s: %llu rows for %zu samples", path, (unsigned long long)n_rows, names.size());
+    return MSNV_OK;
+}
+
+// removeOutliersFromDistMatrixMinDissim(maxTimesSd = 3, maxNoutliers = 5) (filterSamples.R:42-72): the samples that stay, in matrix order.  A sample
+// whose smallest distance to another lies more than 3 sd from the mean of those is an outlier; none or more than 5 of them: everybody stays.
+std::vector<int32_t> remove_outliers(const std::vector<double> &d, size_t n_all) {
+    std::vector<double> mind(n_all);
+    for (size_t i = 0; i < n_all; ++i) {
+        double m = INFINITY;
+        for (size_t j = 0; j < n_all; ++j) if (j != i) m = std::min(m, d[i * n_all + j]);
+        mind[i] = m;
+    }
+    const double mean = r_mean(mind.data(), n_all), sd = r_sd(mind.data(), n_all), hi = mean + 3 * sd, lo = mean - 3 * sd;
+    std::vector<int32_t> keep, all(n_all);
+    for (size_t i = 0; i < n_all; ++i) { all[i] = (int32_t)i; if (!(mind[i] > hi || mind[i] < lo)) keep.push_back((int32_t)i); }
+    const size_t n_out = n_all - keep.size();
+    return (n_out == 0 || n_out > 5) ? all : keep;
+}
+
 namespace {
 
 // ---- the draws (include/msnv.h)
@@ -42,18 +109,6 @@ void permutation(uint64_t seed, uint64_t ordinal, uint32_t n, std::vector<int32_
     p.resize(n);
     for (uint32_t i = 0; i < n; ++i) p[i] = (int32_t)i;
     for (uint32_t i = n; i-- > 1;) std::swap(p[i], p[draw(seed, ordinal, i) % (i + 1)]);
-}
-
-int check_matrix(const char *who, int64_t n, const double *d) {
-    if (n < 2 || n > (int64_t)CLUSTER_MAX_SAMPLES) return fail(MSNV_EDOMAIN, "%s: %lld samples (2 to %u)", who, (long long)n, CLUSTER_MAX_SAMPLES);
-    for (int64_t i = 0; i < n; ++i)
-        for (int64_t j = 0; j <= i; ++j) {
-            const double v = d[i * n + j];
-            if (!(v >= 0.0) || !std::isfinite(v)) return fail(MSNV_EDOMAIN, "%s: the distance of samples %lld and %lld is %g (distances are finite and >= 0)", who, (long long)i, (long long)j, v);
-            if (v != d[j * n + i]) return fail(MSNV_EDOMAIN, "%s: the matrix is not symmetric at (%lld, %lld)", who, (long long)i, (long long)j);
-            if (i == j && v != 0.0) return fail(MSNV_EDOMAIN, "%s: the diagonal is %g at sample %lld, not 0", who, v, (long long)i);
-        }
-    return MSNV_OK;
 }
 
 // mean.pred and optimalk from the prederr of one run (k = 2..gmax, M values each)
@@ -110,44 +165,6 @@ int write_dist(const std::string &path, const std::vector<std::string> &names, c
         text.push_back('\n');
     }
     return write_text(path, text);
-}
-
-// <species>.filtered.mann.dist as write_matrix of dist.cpp writes it: a header of names behind an empty cell, then name + n cells per row.
-// r_form: the header as write.table prints it (write_dist above), n names and no leading cell.
-int read_dist(const char *path, std::vector<std::string> &names, std::vector<double> &d, bool r_form = false) {
-    FILE *in = fopen(path, "r");
-    if (!in) return fail(MSNV_EIO, "Cannot open %s: %s", path, strerror(errno));
-    char *line = nullptr; size_t cap = 0; ssize_t len;
-    uint64_t lineno = 0, n_rows = 0;
-    int rc = MSNV_OK;
-    while (rc == MSNV_OK && (len = getline(&line, &cap, in)) >= 0) {
-        ++lineno;
-        while (len && (line[len - 1] == '\n' || line[len - 1] == '\r')) line[--len] = 0;
-        if (lineno > 1 && len == 0) continue;
-        std::vector<std::string> f;
-        const char *s = line, *end = line + len;
-        while (true) {
-            const char *t = (const char *)memchr(s, '\t', (size_t)(end - s));
-            f.emplace_back(s, t ? t : end);
-            if (!t) break;
-            s = t + 1;
-        }
-        if (lineno == 1) { names.assign(f.begin() + (r_form ? 0 : 1), f.end()); continue; }
-        if (f.size() != names.size() + 1) { rc = fail(MSNV_EFORMAT, "%s:%llu: %zu cells for %zu samples", path, (unsigned long long)lineno, f.size() - 1, names.size()); break; }
-        if (n_rows >= names.size() || f[0] != names[n_rows]) { rc = fail(MSNV_EFORMAT, "%s:%llu: row '%s' does not follow the header's order", path, (unsigned long long)lineno, f[0].c_str()); break; }
-        for (size_t c = 1; c < f.size(); ++c) {
-            char *e = nullptr;
-            const double v = f[c].empty() || f[c] == "NA" ? 0.0 : strtod(f[c].c_str(), &e);
-            if (!e || e != f[c].c_str() + f[c].size()) { rc = fail(MSNV_EFORMAT, "%s:%llu: cell '%s' is not a number (NA and empty cells are refused: rmNAfromDistMatrix is not built)", path, (unsigned long long)lineno, f[c].c_str()); break; }
-            d.push_back(v);
-        }
-        ++n_rows;
-    }
-    free(line);
-    fclose(in);
-    if (rc) return rc;
-    if (n_rows != names.size()) return fail(MSNV_EFORMAT, "%s: %llu rows for %zu samples", path, (unsigned long long)n_rows, names.size());
-    return MSNV_OK;
 }
 
 // getNClusStabScore (clusteringStability.R:201-221).  num < 0 = NA; a group that is empty, single or holds an NA is not "constant"
@@ -253,22 +270,8 @@ extern "C" int msnv_cluster_file(msnv_ctx *ctx, const char *dist_path, const cha
     if (int rc = make_dir(out_dir)) return rc;
 
     // ---- removeOutliersFromDistMatrixMinDissim(maxTimesSd = 3, maxNoutliers = 5)
-    std::vector<int32_t> qc;                                           // samples after outlier removal, in matrix order
-    {
-        std::vector<double> mind(n_all);
-        for (size_t i = 0; i < n_all; ++i) {
-            double m = INFINITY;
-            for (size_t j = 0; j < n_all; ++j) if (j != i) m = std::min(m, d[i * n_all + j]);
-            mind[i] = m;
-        }
-        const double mean = r_mean(mind.data(), n_all), sd = r_sd(mind.data(), n_all), hi = mean + 3 * sd, lo = mean - 3 * sd;
-        std::vector<int32_t> keep;
-        for (size_t i = 0; i < n_all; ++i) if (!(mind[i] > hi || mind[i] < lo)) keep.push_back((int32_t)i);
-        const size_t n_out = n_all - keep.size();
-        if (n_out == 0 || n_out > 5) { qc.resize(n_all); for (size_t i = 0; i < n_all; ++i) qc[i] = (int32_t)i; }
-        else qc = keep;
-        if (result) result[3] = (int64_t)(n_all - qc.size());
-    }
+    const std::vector<int32_t> qc = remove_outliers(d, n_all);         // samples after outlier removal, in matrix order
+    if (result) result[3] = (int64_t)(n_all - qc.size());
     if (qc.size() < 2) return fail(MSNV_EDOMAIN, "%s: %zu samples left after outlier removal", dist_path, qc.size());
 
     // ---- computeSnvFreqStats + onlyKeepSamplesWithDistinctFreqs(minPropHomogSnvAllelesPerSample = 0.8)

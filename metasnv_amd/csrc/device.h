@@ -242,7 +242,7 @@ int  dev_inflate_resident(msnv_ctx *ctx, const uint8_t *host_in, uint64_t comp_b
                           uint32_t check_every, std::vector<uint32_t> &status, double *ms_kernel);
 int  dev_inflate_patch(msnv_ctx *ctx, uint64_t out_off, const uint8_t *data, uint32_t n);
 
-// ---- the stages that work on files (textcall.hip; dist.cpp + dist_k.hip; div.cpp + div_k.hip; subpopr.cpp + subpopr_k.hip; genecorr.cpp + genecorr_k.hip; cluster.cpp + cluster_k.hip; genotype.cpp + genotype_k.hip; profile.cpp + profile_k.hip)
+// ---- the stages that work on files (textcall.hip; dist.cpp + dist_k.hip; div.cpp + div_k.hip; subpopr.cpp + subpopr_k.hip; genecorr.cpp + genecorr_k.hip; cluster.cpp + cluster_k.hip; pcoa.cpp + pcoa_k.hip; genotype.cpp + genotype_k.hip; profile.cpp + profile_k.hip)
 int  text_call(msnv_ctx *ctx, const char *text, uint64_t n_text, const msnv_params &p, const char *ref_fasta, const char *ann_path,
                const char *called_path, const char *indiv_path, uint64_t stats[8]);
 int  dist_file(msnv_ctx *ctx, const char *freq_path, const char *mann_path, const char *allele_path, double threshold,
@@ -280,6 +280,18 @@ int dev_cluster_boot(const ClusterDev &c, uint64_t n_sets, const uint32_t *m, ui
                      int32_t *clus0, int32_t *best, double *ms_kernel);
 int dev_pred_strength(const ClusterDev &c, uint64_t n_splits, const uint32_t *len, const uint32_t *k, const int32_t *idx, void *stream, double *prederr, double *ms_kernel);
 int dev_freq_bands(const double *rows, uint64_t n_pos, uint32_t n_samples, void *stream, uint64_t *counts, double *ms_kernel);   // counts[sample][4]
+// cluster.cpp, shared with pcoa.cpp: the checks of a distance matrix (include/msnv.h), the reader of <species>.filtered.mann.dist (r_form: the
+// header as write.table prints it), and removeOutliersFromDistMatrixMinDissim(3 sd, at most 5): the samples that stay, in matrix order
+int check_matrix(const char *who, int64_t n, const double *d);
+int read_dist(const char *path, std::vector<std::string> &names, std::vector<double> &d, bool r_form = false);
+std::vector<int32_t> remove_outliers(const std::vector<double> &d, size_t n_all);
+
+// pcoa.cpp + pcoa_k.hip: subpopr's computePCoA, ape::pcoa(correction = "none") by two-sided cyclic Jacobi in round-robin order (include/msnv.h).
+// dist: a checked n x n matrix.  Out: eig[n] sorted descending with the cut-off applied, rel_eig[n], axis_pct[n], vectors[n][n_axes] (NaN columns from
+// k on), info[8] as msnv_pcoa's.  who names the caller (a species) in the message of a solve that has not settled after PCOA_MAX_SWEEPS sweeps.
+constexpr uint32_t PCOA_MAX_SWEEPS = 64;
+int dev_pcoa(const char *who, const double *dist, uint32_t n, uint32_t n_axes, void *stream, double *eig, double *rel_eig, double *axis_pct, double *vectors,
+             int64_t info[8], double *ms_kernel);
 
 // genotype.cpp + genotype_k.hip: subpopr's computeUniquePosPerCluster.  col[] lists the columns in use in cluster order, seg[k] is the first
 // entry of cluster k (seg[K] = the list's length).  A row with a mean difference within GENO_GUARD of the threshold is flagged near.

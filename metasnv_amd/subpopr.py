@@ -15,6 +15,11 @@
       <species>.filtered.mann.dist (+ <species>.filtered.freq)  ->  <outDir>[/noClustering|/clustMedoidDefnFailed]/<species>_mann_{PS_values.tab,
       distMatrixUsedForClustMedoidDefns.txt,clustering.tab,clusNumStability.tab} and <species>_freq_composition.tab
 
+  pcoaSubpops.py <dist_file> <dir> [--species S]
+      (src/subpopr/R/clustering.R computePCoA: ape::pcoa of the matrix after outlier removal; <dir> = clusterSubpops.py's outDir or its noClustering/)
+      <species>.filtered.mann.dist + <dir>/<species>_mann_clustering.tab (+ <species>_freq_composition.tab)  ->  <dir>/<species>_mann_pcoa_proj.tab
+      and, our own file, <species>_mann_pcoa_eig.tab
+
   clusterMembStability.py <species> <dir> [--k N] [--ps-cut X] [--seed N] [--boot N]
       (src/subpopr/R/clusteringStability.R getClusMembStability and getClusMembStabScore; <dir> = clusterSubpops.py's outDir or its noClustering/)
       <dir>/<species>_mann_distMatrixUsedForClustMedoidDefns.txt (+ _PS_values.tab, _clusNumStability.tab)  ->  <dir>/<species>_mann_{clusMembStability.tab,
@@ -41,9 +46,10 @@
 
 getGenotypingSNVSubset.py and writeSubpopAbund.py are text filters (native, no device work) and summariseClustering.py reads and writes small
 tables in Python; the frequencies of convertSNVtoAlleleFreq.py, the correlations, every PAM run of clusterSubpops.py and clusterMembStability.py
-with the matching of the re-clustered subsets, writeGenotypeFreqs.py's walk over the frequency table and profileSubpops.py's counts and medians
-per sample are computed on the GPU (msnv_snv_allele_freq, msnv_gene_corr, msnv_corr_stats, msnv_pam_tasks, msnv_pred_strength, msnv_cluster_boot,
-msnv_genotype_rows, msnv_subpop_profile_columns) and there is no CPU fallback for them."""
+with the matching of the re-clustered subsets, pcoaSubpops.py's centring and eigendecomposition, writeGenotypeFreqs.py's walk over the frequency
+table and profileSubpops.py's counts and medians per sample are computed on the GPU (msnv_snv_allele_freq, msnv_gene_corr, msnv_corr_stats,
+msnv_pam_tasks, msnv_pred_strength, msnv_cluster_boot, msnv_pcoa, msnv_genotype_rows, msnv_subpop_profile_columns) and there is no CPU fallback
+for them."""
 import ctypes as C
 import glob
 import os
@@ -306,6 +312,67 @@ def cluster_subpops_main(argv=None):                           # clustering.R:20
     else:
         print("Species " + species + ": " + str(res["n_clusters"]) + " cluster(s) from " + str(res["n_samples"]) + " samples; cluster number stability: "
               + ("not rated", "Low", "Medium", "High")[res["stability_score"]])
+    return res
+
+
+def pcoa(ctx, dist, n_axes=2):
+    """ape::pcoa(correction = "none") of dist [n x n] by the device's Jacobi solver (msnv_pcoa).  Returns a dict: eig, rel_eig, axis_pct
+    (float64 [n], descending), vectors [n x n_axes] (NaN columns from k on), status (_lib.PCOA_*), sweeps, rotations, k, n_negative, ms_kernel."""
+    import numpy as np
+    from ._lib import lib, check
+    dist = np.ascontiguousarray(dist, dtype=np.float64)
+    if dist.ndim != 2 or dist.shape[0] != dist.shape[1]:
+        raise ValueError("pcoa: dist must be a square matrix")
+    n, n_axes = dist.shape[0], int(n_axes)
+    eig, rel, pct = np.zeros(max(n, 1)), np.zeros(max(n, 1)), np.zeros(max(n, 1))
+    vectors = np.zeros((max(n, 1), max(n_axes, 1)))
+    info = (C.c_int64 * 8)()
+    ms = C.c_double()
+    check(lib.msnv_pcoa(ctx._h, n, _dptr(dist), n_axes, _dptr(eig), _dptr(rel), _dptr(pct), _dptr(vectors), info, C.byref(ms)))
+    return {"eig": eig, "rel_eig": rel, "axis_pct": pct, "vectors": vectors, "status": info[0], "sweeps": info[1], "rotations": info[2], "k": info[3],
+            "n_negative": info[4], "ms_kernel": ms.value}
+
+
+def pcoa_file(ctx, dist_path, directory, species=None):
+    """The stage on files (msnv_pcoa_file): writes <species>_mann_pcoa_eig.tab and, unless fewer than two axes come out, <species>_mann_pcoa_proj.tab
+    into directory.  Returns a dict: status (_lib.PCOA_*), sweeps, rotations, k, n_negative, n_samples, n_outliers, ms_kernel."""
+    from ._lib import lib, check
+    if species is None:
+        species = os.path.basename(dist_path).split(".")[0]
+    res = (C.c_int64 * 8)()
+    ms = C.c_double()
+    check(lib.msnv_pcoa_file(ctx._h, dist_path.encode(), directory.encode(), species.encode(), res, C.byref(ms)))
+    return {"status": res[0], "sweeps": res[1], "rotations": res[2], "k": res[3], "n_negative": res[4], "n_samples": res[5], "n_outliers": res[6],
+            "ms_kernel": ms.value}
+
+
+def pcoa_subpops_main(argv=None):                              # clustering.R:120-126, :486-505 computePCoA
+    import argparse
+    ap = argparse.ArgumentParser(prog="pcoaSubpops.py", description="Ordinate a species' samples (subpopr's computePCoA: ape::pcoa of the distance matrix) on the GPU.")
+    ap.add_argument("dist_file", metavar="DIST_FILE", help="<species>.filtered.mann.dist of metaSNV_DistDiv.py --dist")
+    ap.add_argument("dir", metavar="DIR", help="holds the species' files of clusterSubpops.py: its output directory or the noClustering/ below it")
+    ap.add_argument("--species", default=None, metavar="S", help="default: the dist file's name up to its first '.'")
+    a = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    species = a.species if a.species is not None else os.path.basename(a.dist_file).split(".")[0]
+    for f in (a.dist_file, os.path.join(a.dir, species + "_mann_clustering.tab")):
+        if not os.path.exists(f):
+            sys.exit("ERROR: missing input file: " + f)
+    from . import core
+    try:
+        ctx = core.Context(0)
+    except core._lib.MsnvError as e:
+        sys.exit("\nERROR:  {}\n\nSOLUTION: run on a node with an AMD Instinct GPU (there is no CPU fallback)\n".format(e))
+    try:
+        res = pcoa_file(ctx, a.dist_file, a.dir, species=species)
+    except core._lib.MsnvError as e:
+        sys.exit("ERROR: {}".format(e))
+    finally:
+        ctx.close()
+    if res["status"] == core._lib.PCOA_TOO_FEW_AXES:
+        print("Species " + species + ": Error during pcoa - check distance matrix (after optional filtering): " + str(res["k"]) + " axis")      # :125
+    else:
+        print("Species " + species + ": " + str(res["n_samples"]) + " samples ordinated, " + str(res["k"]) + " axes with a positive eigenvalue, "
+              + str(res["n_negative"]) + " negative; " + str(res["sweeps"]) + " Jacobi sweeps")
     return res
 
 
