@@ -110,6 +110,15 @@ __device__ __forceinline__ int wave_inclusive_scan(int x) {      // LLVM's DPP s
     x = dpp_add<0x143, 0xc>(x);   // row_bcast:31 -> rows 2 and 3
     return x;
 }
+// A returning LDS add of a PER-LANE value by the active lanes, as one instruction.  (atomicAdd on a value that differs from lane to lane is
+// rewritten by the compiler's atomic optimizer into a scalar loop over the active lanes -- a readlane / writelane pair each -- and one add by
+// one lane: the wavefront-wide sequence narrow_pass<LATE> is rid of.)  The wait is part of it: the compiler does not count an asm's LDS operation.
+__device__ __forceinline__ uint32_t lds_add_returning(uint32_t *p, const uint32_t v) {
+    uint32_t old;
+    const uint32_t addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)p;
+    asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(old) : "v"(addr), "v"(v) : "memory");
+    return old;
+}
 
 // Allele totals of a tile: 4 x TILE words, position-major, as narrow as the tile's summed depth bound allows (pack.cpp sets the
 // mode per tile; bits 1-2 of WorkItem::part_lo, GateTile::tot_mode): 0 = the four counts in the bytes of one word per position
@@ -412,7 +421,8 @@ struct alignas(16) NarrowLds {
 // LATE (msnv_pileup_tiles_narrow32's ordinary items): the pass stages a position's allele WORD -- one 8-byte record {tile position | split << 11 |
 // sample << 12, word} per position that holds an allele -- and flush_alleles, where the workgroup meets with all 256 lanes anyway, makes the
 // total atomics, the individual rule's marks and the events of it.  What left the pass: the event count, the walk over a word's alleles and
-// two to three global atomics per allele, at ~7 active lanes of 64 between barriers (B) and (A).
+// two to three global atomics per allele, at ~7 active lanes of 64 between barriers (B) and (A).  Its records are placed per LANE: one
+// returning LDS add by the lanes that hold a position, nothing for the other lanes to issue.
 template <typename LDS, int EXC_PAD, bool MERGED = false, bool FUSED = false, bool DA = false, bool LATE = false>
 __device__ __forceinline__ void narrow_pass(LDS &L, const PileupArgs &a, uint32_t (&tc)[N_PPT / 2], bool &dirty, const uint32_t t0,
                                             const int tid, const int lane, const int wave, const uint32_t sample, const uint32_t k,
@@ -539,56 +549,59 @@ __device__ __forceinline__ void narrow_pass(LDS &L, const PileupArgs &a, uint32_
         }
     };
     if constexpr (LATE) {
-        // slots for the wavefront's POSITIONS, taken or not taken (the compare-and-swap of the form below, and why it is one)
+        // Slots for MY positions: one returning add by the lanes that hold any -- no scan over the wavefront, no lane that reserves for the
+        // others.  The fill count only GROWS between two flushes and no reservation is ever taken back, so a reservation lies below N_EVCAP
+        // or it does not, whatever the other lanes and wavefronts do meanwhile, and the flush (min(L.evn, N_EVCAP) records) sees every slot
+        // below the cap written in THIS fill: by its owner, or -- the one reservation that straddles the cap -- with the zero records below.
+        // (What an add that IS taken back does: a second wavefront reserves above the first one's transient count; when that is taken back
+        // the fill count lies below the second one's slots, its events are never flushed and the slots flushed in their place still hold
+        // events of an earlier flush -- a per-sample count doubled at one site in 1 of ~10 000 fuzz cases, the form until round 3;
+        // profiles/stress_case.py shows it in seconds.  The other instantiations keep their compare-and-swap, below.)
         const uint32_t np = (uint32_t)__builtin_popcount(pm);
-        uint32_t pi = (uint32_t)wave_inclusive_scan((int)np);
-        asm volatile("" : "+v"(pi));                         // (kept whole: summed back from the scan's six shifted terms, `pi - np` below costs each of its steps a zero fill and a move)
-        uint32_t got = 0;
-        if (lane == 63) {
-            uint32_t cur = atomicAdd(&L.evn, 0u);
-            for (;;) {
-                if (cur + pi > (uint32_t)N_EVCAP) { got = 0x80000000u; break; }      // staging full (noisy pair): this wavefront expands its alleles itself, below
-                const uint32_t seen = atomicCAS(&L.evn, cur, cur + pi);
-                if (seen == cur) { got = cur; break; }
-                cur = seen;
-            }
-        }
-        got = (uint32_t)__builtin_amdgcn_readlane((int)got, 63);
-        if (!(got & 0x80000000u)) {
-            uint32_t slot = got + pi - np;
+        uint32_t cur = 0;
+        if (pm) cur = lds_add_returning(&L.evn, np);
+        const bool fits = cur + np <= (uint32_t)N_EVCAP;       // (a lane without a position: 0 + 0)
+        {
             const uint32_t tag = (split ? 1u << 11 : 0u) | sample << 12;
-            while (pm) {
+            while (fits && pm) {                                 // (`pm` and `cur` themselves: the registers of the next chunk's loads are live here)
                 const uint32_t j = (uint32_t)__builtin_ctz(pm);
                 pm &= pm - 1u;
                 const uint32_t word = L.al[N_PPT * tid + j];
                 L.al[N_PPT * tid + j] = 0u;
-                L.ev[slot++] = Pair32{(uint32_t)(N_PPT * tid) + j | tag, word};
+                L.ev[cur++] = Pair32{(uint32_t)(N_PPT * tid) + j | tag, word};
             }
-            return;
         }
-        // staging full: the wavefront's alleles go straight into the list, the way the other form does it below (its event count from the bins: rare)
+        if (__all(fits)) return;
+        // staging full (noisy pair): some lane of this wavefront holds a reservation that ends above the cap.  The one that straddles the cap
+        // fills the slots it holds below it -- at most N_PPT - 1 -- with zero records: a zero allele word expands to nothing in
+        // flush_alleles, and the hole cannot replay a record of an earlier flush.  L.evn stays above the cap until that flush resets it.
+        // Then such a lane's alleles go straight into the list, its slots one add of its own event count (from the bins: rare)
+        if (!fits && cur < (uint32_t)N_EVCAP) {
+            uint32_t zero = 0u;
+            asm volatile("" : "+v"(zero));                       // (made HERE: as a constant the pair of zeros is hoisted out of the chunk loop, two registers the kernel does not have)
+            for (uint32_t s = cur; s < (uint32_t)N_EVCAP; ++s) L.ev[s] = Pair32{zero, zero};
+        }
         for (uint32_t q = pm; q; q &= q - 1u) myev += (uint32_t)__builtin_popcount(nz_bytes(L.al[N_PPT * tid + (uint32_t)__builtin_ctz(q)]));
-    }
-    const uint32_t ei = (uint32_t)wave_inclusive_scan((int)myev);   // exclusive prefix of the lanes' event counts = their slots
-    uint32_t res = 0;
-    if (lane == 63 && ei) {
-        // A wavefront's slots in the staging buffer are reserved with compare-and-swap: they are taken or they are not.  (Add first, take
-        // it back when the buffer is full -- the form until round 3 -- lets a second wavefront reserve ABOVE the first one's transient
-        // count; when that is taken back the fill count lies below the second one's slots: its events are never flushed and the slots
-        // that are flushed in their place still hold events of an earlier flush -- a per-sample count doubled at one site in 1 of ~10 000
-        // fuzz cases once the buffer held 224 events instead of 256; profiles/stress_case.py shows it in seconds.)
-        uint32_t cur = atomicAdd(&L.evn, 0u);
-        for (;;) {
-            if (LATE || cur + ei > (uint32_t)N_EVCAP) { res = 0x80000000u | atomicAdd(a.ev_count, ei); break; }   // straight into the list (LATE: the staging buffer holds records, not events)
-            const uint32_t seen = atomicCAS(&L.evn, cur, cur + ei);
-            if (seen == cur) { res = cur; break; }                                 // staged: flushed behind a later barrier (A)
-            cur = seen;
+        expand(pm, myev ? atomicAdd(a.ev_count, myev) : 0u, true);
+    } else {
+        const uint32_t ei = (uint32_t)wave_inclusive_scan((int)myev);   // exclusive prefix of the lanes' event counts = their slots
+        uint32_t res = 0;
+        if (lane == 63 && ei) {
+            // A wavefront's slots in the staging buffer are reserved with compare-and-swap: they are taken or they are not (an add that is
+            // taken back when the buffer is full loses events: see above)
+            uint32_t cur = atomicAdd(&L.evn, 0u);
+            for (;;) {
+                if (cur + ei > (uint32_t)N_EVCAP) { res = 0x80000000u | atomicAdd(a.ev_count, ei); break; }   // straight into the list
+                const uint32_t seen = atomicCAS(&L.evn, cur, cur + ei);
+                if (seen == cur) { res = cur; break; }                                 // staged: flushed behind a later barrier (A)
+                cur = seen;
+            }
         }
+        res = (uint32_t)__builtin_amdgcn_readlane((int)res, 63);
+        const bool direct = (res & 0x80000000u) != 0u;
+        uint32_t slot = (res & 0x7fffffffu) + ei - myev;
+        expand(pm, slot, direct);
     }
-    res = (uint32_t)__builtin_amdgcn_readlane((int)res, 63);
-    const bool direct = (res & 0x80000000u) != 0u;
-    uint32_t slot = (res & 0x7fffffffu) + ei - myev;
-    expand(pm, slot, direct);
 }
 
 // The flush of the staged allele records (narrow_pass<LATE>): called by all threads between barriers, like flush_events.  A thread takes ONE
@@ -968,7 +981,14 @@ __device__ __forceinline__ void pileup_tiles_narrow32_body(PileupArgs a, NarrowL
         }
         return;
     }
-    if (!MERGED && !DA) flush_alleles(L, a, tid, lane, wave, t0, tot_mode_of(w));
+    if (!MERGED && !DA) {
+        // (lane and wavefront worked out again from a thread index the compiler cannot trace back: the pass no longer asks for the lane, and
+        // the two would be kept in registers over the whole chunk loop for this one use behind it -- the two registers that tip the kernel
+        // into scratch memory)
+        int t = tid;
+        asm volatile("" : "+v"(t));
+        flush_alleles(L, a, t, t & 63, t >> 6, t0, tot_mode_of(w));
+    }
     store_part_row(a.part, w, tc, tid);
     store_item_dirty(a.slot_dirty, w, dirty, tid);
 }
