@@ -8,15 +8,19 @@ sees all samples but only its contigs' reads.  The kernels need no collective.  
     reference's split processes each inflate every BAM, metaSNV.py:196-215) and the decoded records travel to
     the rank that owns their contig -- one all_to_all of byte streams per batch of BAMs (exchange_records).
     The contig owners are fixed by the reference's rule, whole species heaviest-first by genome length x
-    coverage (createOptimumSplit.py:46-62), with the coverage taken from the first round of decoded BAMs;
+    coverage (createOptimumSplit.py:46-62), with the coverage taken from the first round of decoded BAMs.
+    feed_sharded runs it as the stages of one Feed: plan_owners, then per round decode and deliver (deal, exchange, append), finish;
   * after: the GATHER of the result tables TO RANK 0, compressed (gather_to_root: one all_to_all in which only
     rank 0 receives, exact sizes, no padding):
       - called-site records in the cell form (a cell per sample that holds something at the site, not
         n_samples entries per site: core.Dataset.results_cells);
       - coverage accumulators: the non-zero (sample, contig) rows only.
 """
+import contextlib
 import os
 import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -334,95 +338,177 @@ def _stageable(paths):
         return False
 
 
-def feed_sharded(ds, bam_paths, owner, cov_min_mapq=1, batch=1, read_records=None, metrics=None, plan=None, pack_threads=0, ctx_when_ready=None, feed_overlap=None):
-    """Decode-sharded input of one dataset per rank: every BAM is read and inflated by ONE rank, its records are dealt by
-    contig owner (core.partition_records) and exchanged, and every rank appends all samples in all_samples order holding
-    only its contigs' records.  Returns stats[n_samples][6] (qaCompute's per-BAM statistics, counted by the decoder and
-    all-gathered).  read_records(path) -> uint8 array replaces the BAM reader in tests.
+def _read_ahead_hint(paths):
+    """Asks the kernel to bring these files into the page cache: a hint, not a read."""
+    for p in paths:
+        try:
+            fd = os.open(p, os.O_RDONLY)
+            try:
+                os.posix_fadvise(fd, 0, 0, os.POSIX_FADV_WILLNEED)
+            finally:
+                os.close(fd)
+        except (OSError, AttributeError):
+            pass
 
-    owner = None: the contig owners are fixed HERE, after the first round has been decoded and before anything is dealt --
-    plan = (names, lengths); the ranks add up the aligned bases per contig of their first-round samples (= genome length x
-    coverage, the reference's split weight, createOptimumSplit.py:46-50), shard_contigs assigns the species, the dataset gets
-    its contig mask and metrics["owner"] the assignment."""
+
+def _all_sample_stats(ds, n):
+    """The statistics rows of all n samples of ds, as feed_sharded returns them."""
     from . import core
-    n = len(bam_paths)
-    if _dist is None and read_records is None:           # nothing to exchange: decode + pack inside the library's thread pool
-        if owner is None and metrics is not None:
+    return np.stack([ds.sample_stats(i) for i in range(n)]) if n else np.zeros((0, len(core.STATS_FIELDS)), np.uint32)
+
+
+def _feed_one_process(ds, bam_paths, owner, batch, metrics, plan, ctx_when_ready):
+    """feed_sharded with nothing to exchange: decode + pack inside the library's thread pool."""
+    if metrics is not None:
+        if owner is None:
             metrics["owner"] = [0] * len(plan[0])
-        if metrics is not None:
-            metrics["inflated_record_bytes"] = None
-        if getattr(ds, "ctx", None) is None and callable(ctx_when_ready):
-            # (cli.py's choice for hosts with few cores; MSNV_ONESHOT=device | host) wait for the context, then everything on the device (BGZF blocks inflated and checked there, records packed
-            # there) instead of inflating on host threads meanwhile.  On a host that grants the job 16 cores the two are close (one-shot run of
-            # the 160 BAMs: 0.82 vs 0.89 s wall, profiles/e2e_ab.sh); with 32 real cores the host threads finish under the runtime's start-up
-            for p in bam_paths:                              # (the page cache may fill while the runtime comes up: a hint, not a read)
-                try:
-                    fd = os.open(p, os.O_RDONLY)
-                    try:
-                        os.posix_fadvise(fd, 0, 0, os.POSIX_FADV_WILLNEED)
-                    finally:
-                        os.close(fd)
-                except (OSError, AttributeError):
-                    pass
-            ds.attach_context(ctx_when_ready())
-            ds.add_sample_bams(bam_paths, batch)
-            return np.stack([ds.sample_stats(i) for i in range(n)]) if n else np.zeros((0, len(core.STATS_FIELDS)), np.uint32)
-        if getattr(ds, "ctx", None) is None and hasattr(ds, "stage_sample_bams") and not knobs.pack_on_host() and _stageable(bam_paths):
-            # the device is still coming up (cli.py brings the HIP runtime up on a thread of its own): the files are read and inflated now,
-            # their records are packed by kernels once the context is attached (finalize); the statistics exist then
-            ds.stage_sample_bams(bam_paths, batch)
-            return None
-        ds.add_sample_bams(bam_paths, batch)
-        return np.stack([ds.sample_stats(i) for i in range(n)]) if n else np.zeros((0, len(core.STATS_FIELDS)), np.uint32)
-    read_many = None
-    if read_records is None:                             # the library reads a round's files in one call (device inflate when they are large)
-        read_many = lambda paths: core.read_bam_records(paths, ctx=getattr(ds, "ctx", None), threads=max(1, len(paths)))
-    stats = np.zeros((n, len(core.STATS_FIELDS)), dtype=np.uint32)
-    inflated = 0
-    batch = max(1, min(batch, -(-n // _world)))          # fewer samples than world x batch: every rank still decodes its share
-    class DealtRound:
-        """A round that left decode_round already dealt on the device: the send tensor with the parts destination-major behind their gaps."""
-        def __init__(self, tensor, part_bytes, stats, record_bytes, gap):
-            self.tensor, self.part_bytes, self.stats, self.record_bytes, self.gap = tensor, part_bytes, stats, record_bytes, gap
+        metrics["inflated_record_bytes"] = None
+    if getattr(ds, "ctx", None) is None and callable(ctx_when_ready):
+        # (cli.py's choice for hosts with few cores; MSNV_ONESHOT=device | host) wait for the context, then everything on the device (BGZF blocks inflated and checked there, records packed
+        # there) instead of inflating on host threads meanwhile.  On a host that grants the job 16 cores the two are close (one-shot run of
+        # the 160 BAMs: 0.82 vs 0.89 s wall, profiles/e2e_ab.sh); with 32 real cores the host threads finish under the runtime's start-up
+        _read_ahead_hint(bam_paths)                          # (the page cache may fill while the runtime comes up)
+        ds.attach_context(ctx_when_ready())
+    elif getattr(ds, "ctx", None) is None and hasattr(ds, "stage_sample_bams") and not knobs.pack_on_host() and _stageable(bam_paths):
+        # the device is still coming up (cli.py brings the HIP runtime up on a thread of its own): the files are read and inflated now,
+        # their records are packed by kernels once the context is attached (finalize); the statistics exist then
+        ds.stage_sample_bams(bam_paths, batch)
+        return None
+    ds.add_sample_bams(bam_paths, batch)
+    return _all_sample_stats(ds, len(bam_paths))
 
-    class HeldOnDevice:
-        """A round decoded BEFORE the owners are known, held in HBM: its record streams in one tensor (inflated there), their statistics and the
-        aligned bases per contig the planner asked for; deliver() deals them from where they lie."""
-        def __init__(self, tensor, offsets, sizes, stats, bases):
-            self.tensor, self.offsets, self.sizes, self.stats, self.bases = tensor, offsets, sizes, stats, bases
 
-    def device_route(need_owner=True):
-        return ((owner is not None or not need_owner) and _dist is not None and getattr(ds, "ctx", None) is not None and hasattr(ds, "deal_bams_device")
-                and not knobs.pack_on_host() and not knobs.deal_on_host()
-                and knobs.inflate_where("d") == "d" and _device().type == "cuda")
+@contextlib.contextmanager
+def _timed(seconds, key):
+    """Where the wall seconds of the feed go: adds those of the block to seconds[key]."""
+    t0 = time.perf_counter()
+    try:
+        yield
+    finally:
+        seconds[key] += time.perf_counter() - t0
 
-    def deal_files_on_device(paths):
+
+def _size_tables(tsend, pb, gap):
+    """The size table of my samples' parts (int64 each) into the gap the dealer left in front of every part; returns the bytes per destination."""
+    import torch
+    sizes, o = [], 0
+    for q in range(_world):
+        tsend[o:o + gap] = torch.from_numpy(np.ascontiguousarray(pb[:, q], dtype=np.int64).view(np.uint8).copy()).to(_device())
+        sizes.append(gap + int(pb[:, q].sum()))
+        o += sizes[-1]
+    return sizes
+
+
+def unpack_ranges(plan_round, base, batch, world, sizes_of):
+    """Where a round's samples lie in what the exchange delivered.  A sender's part is [int64 size of each of its samples | their bytes], and
+    sender r holds samples base + r * batch ... of the round; sizes_of[r] = the sizes in sender r's header.  Returns, per sample in sample
+    order, (sender, offset of the sample's bytes in that sender's part, their number)."""
+    starts = [8 * len(sizes_of[r]) + np.concatenate([[0], np.cumsum(sizes_of[r])]).astype(np.int64) for r in range(world)]
+    out = []
+    for i, r in plan_round:
+        k = i - base - r * batch                             # index among the sender's samples of this round
+        out.append((r, int(starts[r][k]), int(sizes_of[r][k])))
+    return out
+
+
+# What Feed.decode hands to Feed.deliver for a round (its "carrier"): the plain list of this rank's host-decoded record arrays, or one of the
+# two below when the files were inflated in HBM (Feed.dealt_on_device takes each of the three to the same five values).
+class DealtRound:
+    """A round that left decode already dealt on the device: the send tensor with the parts destination-major behind their gaps."""
+
+    def __init__(self, tensor, part_bytes, stats, record_bytes, gap):
+        self.tensor, self.part_bytes, self.stats, self.record_bytes, self.gap = tensor, part_bytes, stats, record_bytes, gap
+
+
+class HeldOnDevice:
+    """A round decoded BEFORE the owners are known, held in HBM: its record streams in one tensor (inflated there), their statistics and the
+    aligned bases per contig the planner asked for; they are dealt from where they lie."""
+
+    def __init__(self, tensor, offsets, sizes, stats, bases):
+        self.tensor, self.offsets, self.sizes, self.stats, self.bases = tensor, offsets, sizes, stats, bases
+
+
+class Feed:
+    """One feed_sharded call that exchanges records: the state the rounds share, and the stages as methods in the order they run -- files_per_round,
+    [plan_owners,] stream (per round: decode, then deliver = deal, exchange, append), finish.
+    Every rank issues the same collectives in the same order: while the owners are planned one gather_fixed vote per held round (also on a
+    rank whose decode failed) and one gather_fixed of the bases; per round exactly one exchange_records (also on a rank with no sample in
+    it or with a failure to report); at the end agree, then gather_fixed of the statistics.  A decode or deal failure travels in the status
+    word of its own round's exchange; an append failure waits in `pending` for the next round's status word, or for agree."""
+
+    def __init__(self, ds, bam_paths, owner, cov_min_mapq, batch, read_records, metrics, pack_threads, feed_overlap):
+        from . import core
+        self.core, self.ds, self.bam_paths, self.owner, self.cov_min_mapq = core, ds, bam_paths, owner, cov_min_mapq
+        self.read_records, self.pack_threads, self.feed_overlap = read_records, pack_threads, feed_overlap
+        self.metrics = metrics if metrics is not None else {}
+        self.batch = self.files_per_round(batch)
+        self.rounds = list(deal_samples(len(bam_paths), self.batch))     # the rounds still to come
+        self.stats = np.zeros((len(bam_paths), len(core.STATS_FIELDS)), dtype=np.uint32)
+        self.inflated = 0
+        self.pending = None                                  # a failure of THIS rank while it appended a round (pack: ENOMEM, EDOMAIN ...)
+        # decoding (read + inflate, or a test's / benchmark's generator) apart from dealing, exchanging and packing -- a benchmark whose
+        # "decoder" is a synthetic generator reports the two separately
+        self.seconds = {"decode_s": 0.0, "deliver_s": 0.0}
+        self.overlap = self.second_context = False
+
+    def on_device(self, what, need_owner=True):
+        """Does this step of a round run on the device?  what = "inflate": the round's files are inflated in HBM and dealt (or, with
+        need_owner=False, held) there -- never with a decoder of the caller's; "deal": host-decoded records are dealt by kernels;
+        "pack": the received streams stay in HBM and are packed there (MSNV_PACK=host keeps the round trip; it does not ask how they travelled)."""
+        ds = self.ds
+        if getattr(ds, "ctx", None) is None or knobs.pack_on_host():
+            return False
+        if what == "pack":
+            return hasattr(ds, "add_samples_records_device")
+        if _dist is None or knobs.deal_on_host() or _device().type != "cuda":
+            return False
+        if what == "deal":
+            return hasattr(ds, "add_samples_records_device")
+        return (self.read_records is None and (self.owner is not None or not need_owner) and hasattr(ds, "deal_bams_device")
+                and knobs.inflate_where("d") == "d")
+
+    def files_per_round(self, batch):
+        """Files a rank decodes per round: the caller's (= --threads, what host decode threads want) -- but the DEVICE route inflates a round's files
+        in one launch of one wavefront per BGZF block, and seven files are ~3 000 blocks for 5 000 wavefront slots: as many files as fit three
+        quarters of a batch of the device inflate (the feed of the benchmark's 160 BAMs: 0.65 s at 7 files a round, 0.43 s at 32; round 6).
+        Every rank computes the same number from the same list.  MSNV_FEED_BATCH overrides."""
+        if knobs.feed_batch():
+            batch = knobs.feed_batch()
+        elif self.on_device("inflate", need_owner=False):
+            try:
+                largest = max(os.path.getsize(p) for p in self.bam_paths) if self.bam_paths else 0
+                room = (knobs.inflate_batch_mb() << 20) * 3 // 4
+                batch = max(batch, min(64, max(1, room // max(1, largest + 32))))
+            except OSError:
+                pass
+        return max(1, min(batch, -(-len(self.bam_paths) // _world)))      # fewer samples than world x batch: every rank still decodes its share
+
+    # ---- decode: the only stage that may run on the ahead-thread
+    def deal_files_on_device(self, paths):
         import torch
-        torch.cuda.set_device(_device())                         # (the round ahead runs on a thread of its own: torch's current device is per thread)
+        torch.cuda.set_device(_device())                     # (the round ahead runs on a thread of its own: torch's current device is per thread)
         gap = 8 * len(paths)
-        comp = sum(os.path.getsize(p) for p in paths)
-        cap = 8 * comp + (1 << 20) + _world * gap             # (BAM inflates 2.5-4 x; the call answers MSNV_ECAPACITY when this is not enough)
+        cap = 8 * sum(os.path.getsize(p) for p in paths) + (1 << 20) + _world * gap      # (BAM inflates 2.5-4 x; the call answers MSNV_ECAPACITY when this is not enough)
         tsend = torch.empty(cap, dtype=torch.uint8, device=_device())
         torch.cuda.current_stream().synchronize()
         try:
-            pb, st, rb = ds.deal_bams_device(paths, owner, _world, tsend.data_ptr(), cap, gap=gap, cov_min_mapq=cov_min_mapq, host_threads=max(1, len(paths)))
-        except core._lib.MsnvError as e:
-            if e.code in (core._lib.EDOMAIN, core._lib.ECAPACITY):
+            pb, st, rb = self.ds.deal_bams_device(paths, self.owner, _world, tsend.data_ptr(), cap, gap=gap, cov_min_mapq=self.cov_min_mapq, host_threads=max(1, len(paths)))
+        except self.core._lib.MsnvError as e:
+            if e.code in (self.core._lib.EDOMAIN, self.core._lib.ECAPACITY):
                 return None
             raise
         return DealtRound(tsend, pb, st, rb, gap)
 
-    def hold_files_on_device(paths, n_contigs):
+    def hold_files_on_device(self, paths, n_contigs):
         import torch
-        comp = sum(os.path.getsize(p) for p in paths)
-        cap = 8 * comp + (1 << 20) + 32 * len(paths)
+        cap = 8 * sum(os.path.getsize(p) for p in paths) + (1 << 20) + 32 * len(paths)
         t = torch.empty(cap, dtype=torch.uint8, device=_device())
         torch.cuda.current_stream().synchronize()
         cb = np.zeros(n_contigs, dtype=np.uint64)
         try:
-            offs, sizes, st = ds.inflate_bams_device(paths, t.data_ptr(), cap, contig_bases=cb, host_threads=max(1, len(paths)))
-        except core._lib.MsnvError as e:
-            if e.code in (core._lib.EDOMAIN, core._lib.ECAPACITY):
+            offs, sizes, st = self.ds.inflate_bams_device(paths, t.data_ptr(), cap, contig_bases=cb, host_threads=max(1, len(paths)))
+        except self.core._lib.MsnvError as e:
+            if e.code in (self.core._lib.EDOMAIN, self.core._lib.ECAPACITY):
                 return None
             raise
         used = int(offs[-1] + sizes[-1]) + 32 if len(offs) else 32
@@ -430,218 +516,42 @@ def feed_sharded(ds, bam_paths, owner, cov_min_mapq=1, batch=1, read_records=Non
         del t
         return HeldOnDevice(held_t, offs, sizes, st, cb)
 
-    def decode_round(plan_round, hold_contigs=0):
-        """My samples of this round, decoded; a failure here is carried to every rank by the exchange (status word).
-        hold_contigs > 0: the split planner's call -- over RCCL the files are inflated on the device and HELD there (HeldOnDevice)."""
+    def decode(self, plan_round, hold_contigs=0):
+        """My samples of this round, decoded: (mine, carrier, failure); a failure here is carried to every rank by the exchange (status word).
+        hold_contigs > 0: the split planner's call -- over RCCL the files are inflated on the device and HELD there (HeldOnDevice).
+        Runs on the ahead-thread of stream() while deliver() runs for the round before: it READS bam_paths, owner, ds and the decoder, and
+        writes nothing but seconds["decode_s"] -- not stats, inflated, pending or a metrics counter, which belong to deliver()."""
         mine = [i for i, r in plan_round if r == _rank]
-        failure, decoded = None, []
-        try:
-            if hold_contigs and read_many is not None and mine and device_route(need_owner=False):
-                held_dev = hold_files_on_device([bam_paths[i] for i in mine], hold_contigs)
-                if held_dev is not None:
-                    return mine, held_dev, None
-            if read_many is not None and mine and device_route():
-                # owners known, RCCL, device pack: the round's files are inflated, CRC-checked and dealt ON THE DEVICE (core.Dataset.deal_bams_device:
-                # nothing of the inflated bytes on the host); a round that does not fit one batch of the device inflate, or an output that turns
-                # out too small for its inflated bytes, takes the host route below
-                dealt = deal_files_on_device([bam_paths[i] for i in mine])
-                if dealt is not None:
-                    return mine, dealt, None
-            if read_many is not None:
-                decoded = read_many([bam_paths[i] for i in mine])
-            elif len(mine) > 1:                              # the library releases the GIL: one decode thread per BAM of the round
-                from concurrent.futures import ThreadPoolExecutor
-                with ThreadPoolExecutor(max_workers=len(mine)) as ex:
-                    decoded = list(ex.map(read_records, [bam_paths[i] for i in mine]))
-            else:
-                decoded = [read_records(bam_paths[i]) for i in mine]
-        except Exception as e:                               # noqa: BLE001 -- re-raised by deliver(), after the other ranks have been told
-            failure, decoded = e, []
-        return mine, decoded, failure
-
-    def size_tables(tsend, pb, gap):
-        """The size table of my samples' parts (int64 each) into the gap the dealer left in front of every part; returns the bytes per destination."""
-        import torch
-        sizes, o = [], 0
-        for q in range(_world):
-            tsend[o:o + gap] = torch.from_numpy(np.ascontiguousarray(pb[:, q], dtype=np.int64).view(np.uint8).copy()).to(_device())
-            sizes.append(gap + int(pb[:, q].sum()))
-            o += sizes[-1]
-        return sizes
-
-    def deliver(base, plan_round, mine, decoded, failure):
-        """Deals the round's records to the contig owners, exchanges them, appends the round's samples to this rank's dataset."""
-        nonlocal inflated
-        if failure is None and pending[0] is not None:      # the previous round's append failed here: this round's status word says so
-            failure, pending[0] = pending[0], None
-        per_dest = [[] for _ in range(_world)]              # per destination rank: (sample, bytes) in sample order
-        # over RCCL with the device pack, the dealing itself runs on the device (core.deal_records_device: one upload of the round's streams,
-        # kernels put every record where the all-to-all sends it from): no host walk over the records, no host copy of the parts
-        # (MSNV_DEAL=host keeps the host threads)
-        dev_send = None
-        if failure is None and isinstance(decoded, HeldOnDevice):
+        paths = [self.bam_paths[i] for i in mine]
+        with _timed(self.seconds, "decode_s"):
             try:
-                import torch
-                gap = 8 * len(mine)
-                cap = int(decoded.sizes.sum()) + _world * gap
-                tsend = torch.empty(max(cap, 16), dtype=torch.uint8, device=_device())
-                torch.cuda.current_stream().synchronize()
-                base_ptr = decoded.tensor.data_ptr()
-                pb, _st = core.deal_records_device(ds.ctx, [base_ptr + int(o) for o in decoded.offsets], owner, _world, tsend.data_ptr(), cap, gap=gap, cov_min_mapq=cov_min_mapq,
-                                                   on_device=True, sizes=[int(x) for x in decoded.sizes])
-                sizes = size_tables(tsend, pb, gap)
-                for i, row, nb in zip(mine, decoded.stats, decoded.sizes):
-                    inflated += int(nb)
-                    stats[i] = row
-                dev_send = DeviceSend(tsend, sizes)
-                if metrics is not None:
-                    metrics["records_dealt_on_device_bytes"] = metrics.get("records_dealt_on_device_bytes", 0) + int(decoded.sizes.sum())
-                    metrics["bams_inflated_on_device_bytes"] = metrics.get("bams_inflated_on_device_bytes", 0) + int(decoded.sizes.sum())
-            except Exception as e:                           # noqa: BLE001
-                failure, dev_send = e, None
-            decoded = []
-        if failure is None and isinstance(decoded, DealtRound):
-            try:
-                import torch
-                pb, gap, tsend = decoded.part_bytes, decoded.gap, decoded.tensor
-                sizes = size_tables(tsend, pb, gap)
-                for i, row, nb in zip(mine, decoded.stats, decoded.record_bytes):
-                    inflated += int(nb)
-                    stats[i] = row
-                dev_send = DeviceSend(tsend, sizes)
-                if metrics is not None:
-                    metrics["records_dealt_on_device_bytes"] = metrics.get("records_dealt_on_device_bytes", 0) + int(decoded.record_bytes.sum())
-                    metrics["bams_inflated_on_device_bytes"] = metrics.get("bams_inflated_on_device_bytes", 0) + int(decoded.record_bytes.sum())
-            except Exception as e:                           # noqa: BLE001
-                failure, dev_send = e, None
-            decoded = []
-        deal_on_device = (dev_send is None and failure is None and len(decoded) > 0 and _dist is not None and getattr(ds, "ctx", None) is not None and hasattr(ds, "add_samples_records_device")
-                          and not knobs.pack_on_host() and not knobs.deal_on_host() and _device().type == "cuda")
-        if deal_on_device:
-            try:
-                import torch
-                gap = 8 * len(mine)
-                cap = int(sum(int(r.size) for r in decoded)) + _world * gap
-                tsend = torch.empty(max(cap, 16), dtype=torch.uint8, device=_device())
-                torch.cuda.current_stream().synchronize()
-                pb, st = core.deal_records_device(ds.ctx, decoded, owner, _world, tsend.data_ptr(), cap, gap=gap, cov_min_mapq=cov_min_mapq)
-                sizes = size_tables(tsend, pb, gap)
-                for i, rec, row in zip(mine, decoded, st):
-                    inflated += int(rec.size)
-                    stats[i] = row
-                dev_send = DeviceSend(tsend, sizes)
-                if metrics is not None:
-                    metrics["records_dealt_on_device_bytes"] = metrics.get("records_dealt_on_device_bytes", 0) + int(sum(int(r.size) for r in decoded))
-            except Exception as e:                           # noqa: BLE001
-                failure, dev_send = e, None
-        if failure is None and dev_send is None:
-            try:
-                # one walk over every sample's records (msnv_records_partition: owner of every record's contig, qaCompute's statistics); the
-                # library releases the GIL, so the round's samples are dealt side by side (one after the other this was 0.3 s per GB and rank)
-                deal = lambda rec: core.partition_records(rec, owner, _world, cov_min_mapq)
-                if len(decoded) > 1:
-                    from concurrent.futures import ThreadPoolExecutor
-                    with ThreadPoolExecutor(max_workers=min(len(decoded), max(1, batch))) as ex:
-                        dealt = list(ex.map(deal, decoded))
-                else:
-                    dealt = [deal(rec) for rec in decoded]
-                for i, rec, (parts, st) in zip(mine, decoded, dealt):
-                    inflated += int(rec.size)
-                    stats[i] = st
-                    for q in range(_world):
-                        per_dest[q].append(parts[q])
-            except Exception as e:                           # noqa: BLE001
-                failure, per_dest = e, [[] for _ in range(_world)]
-        # one exchange per round: [sizes of my samples' parts | bytes], per destination
-        send = []
-        for q in range(_world):
-            hdr = np.array([p.size for p in per_dest[q]], dtype=np.int64).view(np.uint8)
-            send.append(np.concatenate([hdr] + per_dest[q]) if per_dest[q] else np.zeros(0, np.uint8))
-        # over RCCL the received streams stay in HBM and are parsed / filtered / packed there (csrc/devpack.hip): no copy to the host, no host
-        # pack, no second upload (MSNV_PACK=host keeps the round trip)
-        on_device = getattr(ds, "ctx", None) is not None and hasattr(ds, "add_samples_records_device") and not knobs.pack_on_host()
-        try:
-            got = exchange_records(dev_send if dev_send is not None else send, status=0 if failure is None else int(getattr(failure, "code", 0)) or 99, keep_on_device=on_device)
-        except RankError:
-            if failure is not None:
-                raise failure
-            raise
-        # unpack in sample order: sender r holds samples base + r * batch ...
-        n_from = [0] * _world
-        for _, r in plan_round:
-            n_from[r] += 1
-        if isinstance(got, DeviceParts):
-            sizes_of = [got.head(r, 8 * n_from[r]).view(np.int64) for r in range(_world)]
-            starts = [8 * n_from[r] + np.concatenate([[0], np.cumsum(sizes_of[r])]).astype(np.int64) for r in range(_world)]
-            ptrs, sizes = [], []
-            for i, r in plan_round:
-                k = i - base - r * batch
-                ptrs.append(got.address(r, starts[r][k]) if int(sizes_of[r][k]) else 0)
-                sizes.append(int(sizes_of[r][k]))
-            try:
-                ds.add_samples_records_device(ptrs, sizes)
-            except Exception as e:                           # noqa: BLE001 -- told to the other ranks by the next round's status word / agree()
-                pending[0] = e
-            if metrics is not None:
-                metrics["records_packed_on_device_bytes"] = metrics.get("records_packed_on_device_bytes", 0) + int(sum(sizes))
-            return
-        sizes_of = [got[r][:8 * n_from[r]].view(np.int64) for r in range(_world)]
-        starts = [8 * n_from[r] + np.concatenate([[0], np.cumsum(sizes_of[r])]).astype(np.int64) for r in range(_world)]
-        streams = []
-        for i, r in plan_round:
-            k = i - base - r * batch                     # index among the sender's samples of this round
-            o = int(starts[r][k])
-            streams.append(got[r][o:o + int(sizes_of[r][k])])
-        try:
-            if hasattr(ds, "add_samples_records"):       # the round's samples are packed side by side by the library
-                ds.add_samples_records(streams, pack_threads)
-            else:
-                for s in streams:
-                    ds.add_sample_records(s)
-        except Exception as e:                               # noqa: BLE001
-            pending[0] = e
+                if hold_contigs and mine and self.on_device("inflate", need_owner=False):
+                    held = self.hold_files_on_device(paths, hold_contigs)
+                    if held is not None:
+                        return mine, held, None
+                if mine and self.on_device("inflate"):
+                    # owners known, RCCL, device pack: the round's files are inflated, CRC-checked and dealt ON THE DEVICE (core.Dataset.deal_bams_device:
+                    # nothing of the inflated bytes on the host); a round that does not fit one batch of the device inflate, or an output that turns
+                    # out too small for its inflated bytes, takes the host route below
+                    dealt = self.deal_files_on_device(paths)
+                    if dealt is not None:
+                        return mine, dealt, None
+                if self.read_records is None:                # the library reads a round's files in one call (device inflate when they are large)
+                    return mine, self.core.read_bam_records(paths, ctx=getattr(self.ds, "ctx", None), threads=max(1, len(paths))), None
+                if len(mine) > 1:                            # the library releases the GIL: one decode thread per BAM of the round
+                    with ThreadPoolExecutor(max_workers=len(mine)) as ex:
+                        return mine, list(ex.map(self.read_records, paths)), None
+                return mine, [self.read_records(p) for p in paths], None
+            except Exception as e:                           # noqa: BLE001 -- re-raised by exchange(), after the other ranks have been told
+                return mine, [], e
 
-    # Files a rank decodes per round: the caller's (= --threads, what host decode threads want) -- but the DEVICE route inflates a round's files
-    # in one launch of one wavefront per BGZF block, and seven files are ~3 000 blocks for 5 000 wavefront slots: as many files as fit three
-    # quarters of a batch of the device inflate (the feed of the benchmark's 160 BAMs: 0.65 s at 7 files a round, 0.43 s at 32; round 6).
-    # Every rank computes the same number from the same list.  MSNV_FEED_BATCH overrides.
-    if knobs.feed_batch():
-        batch = knobs.feed_batch()
-    elif read_many is not None and device_route(need_owner=False):
-        try:
-            largest = max(os.path.getsize(p) for p in bam_paths) if bam_paths else 0
-            room = (knobs.inflate_batch_mb() << 20) * 3 // 4
-            batch = max(batch, min(64, max(1, room // max(1, largest + 32))))
-        except OSError:
-            pass
-    batch = max(1, min(batch, -(-n // _world)))
-    pending = [None]                                         # a failure of THIS rank while it appended a round (pack: ENOMEM, EDOMAIN ...)
-    rounds = list(deal_samples(n, batch))
-    k = 0
-    # where the wall seconds of the feed go (metrics): decoding (read + inflate, or a test's / benchmark's generator) apart from dealing,
-    # exchanging and packing -- a benchmark whose "decoder" is a synthetic generator reports the two separately
-    import time
-    split = {"decode_s": 0.0, "deliver_s": 0.0}
-    _decode_round, _deliver = decode_round, deliver
-
-    def decode_round(plan_round, hold_contigs=0):            # noqa: F811
-        t0 = time.perf_counter()
-        try:
-            return _decode_round(plan_round, hold_contigs)
-        finally:
-            split["decode_s"] += time.perf_counter() - t0
-
-    def deliver(*a):                                         # noqa: F811
-        t0 = time.perf_counter()
-        try:
-            return _deliver(*a)
-        finally:
-            split["deliver_s"] += time.perf_counter() - t0
-    if owner is None:
-        # The contig owners are fixed by the reference's rule -- whole species, heaviest first, weight = genome length x coverage = aligned
-        # bases (createOptimumSplit.py:46-62, which runs AFTER qaCompute has seen every BAM) -- from as many rounds as fit the planning
-        # budget: decoded rounds are HELD (MSNV_PLAN_MB of record bytes per rank, default a quarter of the host memory divided by the
-        # ranks) and dealt once the owners are known; whatever follows streams through.  A small cohort is planned on all of its reads.
+    # ---- plan_owners: owner = None
+    def plan_owners(self, plan):
+        """The contig owners are fixed by the reference's rule -- whole species, heaviest first, weight = genome length x coverage = aligned
+        bases (createOptimumSplit.py:46-62, which runs AFTER qaCompute has seen every BAM) -- from as many rounds as fit the planning
+        budget: decoded rounds are HELD (MSNV_PLAN_MB of record bytes per rank, default a quarter of the host memory divided by the
+        ranks) and dealt once the owners are known; whatever follows streams through.  A small cohort is planned on all of its reads."""
+        core, ds, metrics = self.core, self.ds, self.metrics
         names, lengths = plan
         local = np.zeros(len(names), dtype=np.uint64)
         budget = knobs.plan_bytes()
@@ -650,107 +560,214 @@ def feed_sharded(ds, bam_paths, owner, cov_min_mapq=1, batch=1, read_records=Non
                 budget = os.sysconf("SC_PAGE_SIZE") * os.sysconf("SC_PHYS_PAGES") // 4 // max(1, _world)
             except (OSError, ValueError):
                 budget = 1 << 30
-        if read_many is not None and device_route(need_owner=False):      # rounds held in HBM (hold_files_on_device): a third of what is free there at most
+        if self.on_device("inflate", need_owner=False):      # rounds held in HBM (hold_files_on_device): a third of what is free there at most
             import torch
             budget = min(budget, int(torch.cuda.mem_get_info()[0]) // 3)
         held, held_bytes = [], 0
-        while k < len(rounds):
-            base, plan_round = rounds[k]
-            mine, decoded, failure = decode_round(plan_round, hold_contigs=len(names))
-            if failure is None and isinstance(decoded, HeldOnDevice):
-                local += decoded.bases                          # (counted by the kernel that measured the streams)
+        while self.rounds:
+            base, plan_round = self.rounds.pop(0)
+            mine, carrier, failure = self.decode(plan_round, hold_contigs=len(names))
+            if failure is None and isinstance(carrier, HeldOnDevice):
+                local += carrier.bases                       # (counted by the kernel that measured the streams)
             elif failure is None:
                 try:
-                    if len(decoded) > 1:                     # (one walk over every record's CIGAR: the round's samples side by side, the library releases the GIL)
-                        from concurrent.futures import ThreadPoolExecutor
-                        with ThreadPoolExecutor(max_workers=min(len(decoded), max(1, batch))) as ex:
-                            for part in ex.map(lambda rec: core.contig_bases(rec, len(names)), decoded):
+                    if len(carrier) > 1:                     # (one walk over every record's CIGAR: the round's samples side by side, the library releases the GIL)
+                        with ThreadPoolExecutor(max_workers=min(len(carrier), self.batch)) as ex:
+                            for part in ex.map(lambda rec: core.contig_bases(rec, len(names)), carrier):
                                 local += part
                     else:
-                        for rec in decoded:
+                        for rec in carrier:
                             core.contig_bases(rec, len(names), into=local)
                 except Exception as e:                       # noqa: BLE001
-                    failure, decoded = e, []
-            held.append((base, plan_round, mine, decoded, failure))
-            held_bytes += int(decoded.sizes.sum()) if isinstance(decoded, HeldOnDevice) else sum(int(r.size) for r in decoded)
-            k += 1
+                    failure, carrier = e, []
+            held.append((base, plan_round, mine, carrier, failure))
+            held_bytes += int(carrier.sizes.sum()) if isinstance(carrier, HeldOnDevice) else sum(int(r.size) for r in carrier)
             stop = gather_fixed(np.array([1 if (held_bytes > budget or failure is not None) else 0], dtype=np.int64))
             if any(int(x[0]) for x in stop):
                 break
         total = sum(a.astype(np.uint64) for a in gather_fixed(local))
-        owner = shard_contigs(names, lengths, _world, contig_bases=total)
+        self.owner = shard_contigs(names, lengths, _world, contig_bases=total)
         if _world > 1 and hasattr(ds, "set_contig_mask"):
-            ds.set_contig_mask([o == _rank for o in owner])
-        if metrics is not None:
-            metrics["owner"] = list(owner)
-            metrics["first_round_bases"] = int(total.sum())
-            metrics["plan_rounds"] = len(held)
-            metrics["plan_samples"] = int(sum(len(h[1]) for h in held))
+            ds.set_contig_mask([o == _rank for o in self.owner])
+        metrics["owner"] = list(self.owner)
+        metrics["first_round_bases"] = int(total.sum())
+        metrics["plan_rounds"] = len(held)
+        metrics["plan_samples"] = int(sum(len(h[1]) for h in held))
         while held:
-            deliver(*held.pop(0))
-    # The rounds that stream through (round 5): round k + 1 is DECODED WHILE round k is dealt, exchanged and packed -- on a thread of its own
-    # when the decoder stays on the host (a test's / benchmark's read_records, MSNV_INFLATE=host: the library releases the GIL and touches
-    # nothing of the context), and as a read-ahead hint for the files of the next round when it does not: the device route inflates and
-    # deals with the context's own staging buffers and stream, which the pack of round k is using (one context, one thread at a time).
-    def read_ahead(plan_round):
-        if read_records is not None:
-            return
-        for i, r in plan_round:
-            if r != _rank:
-                continue
-            try:
-                fd = os.open(bam_paths[i], os.O_RDONLY)
-                try:
-                    os.posix_fadvise(fd, 0, 0, os.POSIX_FADV_WILLNEED)
-                finally:
-                    os.close(fd)
-            except (OSError, AttributeError):
-                pass
-    host_decoder = read_records is not None or knobs.inflate_where("d") == "h"
-    want_overlap = feed_overlap if feed_overlap is not None else knobs.feed_overlap()      # (an argument of the run; the environment is the default)
-    overlap = host_decoder and want_overlap and len(rounds) - k > 1
-    # ... and on the DEVICE route (round 6): the upload, inflate, CRC check and dealing of round k + 1 run on a second context of the device
-    # (core.Dataset.set_feed_context: its own stream, staging buffers and pinned words) from a thread of its own, under the exchange and the
-    # pack of round k on the dataset's context -- the inflate kernel is bound by latency per symbol and leaves most of the chip to the pack
-    feed_ctx = None
-    if not overlap and want_overlap and len(rounds) - k > 1 and read_many is not None and device_route() and hasattr(ds, "set_feed_context"):
+            self.deliver(*held.pop(0))
+
+    # ---- deliver = deal, exchange, append
+    def dealt_on_device(self, carrier, n_mine):
+        """A round's carrier -> (send tensor, part_bytes[n][world], gap, statistics rows, record bytes per sample): the parts destination-major
+        behind their gaps.  A DealtRound has them; a HeldOnDevice's streams are dealt where they lie, host-decoded arrays from the host
+        (core.deal_records_device into a send tensor of their size)."""
+        if isinstance(carrier, DealtRound):
+            return carrier.tensor, carrier.part_bytes, carrier.gap, carrier.stats, carrier.record_bytes
+        import torch
+        held = isinstance(carrier, HeldOnDevice)
+        sizes = [int(x) for x in carrier.sizes] if held else [int(r.size) for r in carrier]
+        gap = 8 * n_mine
+        cap = sum(sizes) + _world * gap
+        tsend = torch.empty(max(cap, 16), dtype=torch.uint8, device=_device())
+        torch.cuda.current_stream().synchronize()
+        if held:                                             # (its statistics were counted by the kernel that measured the streams)
+            base_ptr = carrier.tensor.data_ptr()
+            pb, _ = self.core.deal_records_device(self.ds.ctx, [base_ptr + int(o) for o in carrier.offsets], self.owner, _world, tsend.data_ptr(), cap, gap=gap,
+                                                  cov_min_mapq=self.cov_min_mapq, on_device=True, sizes=sizes)
+            return tsend, pb, gap, carrier.stats, sizes
+        pb, st = self.core.deal_records_device(self.ds.ctx, carrier, self.owner, _world, tsend.data_ptr(), cap, gap=gap, cov_min_mapq=self.cov_min_mapq)
+        return tsend, pb, gap, st, sizes
+
+    def deal(self, mine, carrier, failure):
+        """carrier -> (what this rank sends, failure): a DeviceSend where the dealing ran on the device, else per destination [sizes of my samples'
+        parts | bytes] as host arrays.  Any exception here becomes the failure, and the round goes out empty with a non-zero status."""
+        nothing = [np.zeros(0, np.uint8)] * _world
+        if failure is not None:
+            return nothing, failure
+        in_hbm = isinstance(carrier, (DealtRound, HeldOnDevice))
         try:
-            feed_ctx = core.Context(ds.ctx.device)
-            ds.set_feed_context(feed_ctx)
-            overlap = True
-        except Exception:                                        # noqa: BLE001 -- no second context: one round after the other, as before
-            feed_ctx = None
-    if overlap:
-        from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=1) as ahead:
-            nxt = ahead.submit(decode_round, rounds[k][1])
-            while k < len(rounds):
-                base, plan_round = rounds[k]
-                got = nxt.result()
-                nxt = ahead.submit(decode_round, rounds[k + 1][1]) if k + 1 < len(rounds) else None
-                deliver(base, plan_round, *got)
-                k += 1
-    while k < len(rounds):
-        base, plan_round = rounds[k]
-        if k + 1 < len(rounds):
-            read_ahead(rounds[k + 1][1])
-        deliver(base, plan_round, *decode_round(plan_round))
-        k += 1
-    if feed_ctx is not None:
-        ds.set_feed_context(None)
-        feed_ctx.close()
-    if metrics is not None:
-        metrics.update(split)
-        metrics["decode_overlapped"] = bool(overlap)
-        metrics["decode_on_second_context"] = feed_ctx is not None
-    agree(pending[0], "the last round of records was appended")
-    allstats = gather_fixed(stats)
-    stats = np.maximum.reduce(allstats) if len(allstats) > 1 else stats      # every row is non-zero on exactly one rank
-    if metrics is not None:
-        metrics["inflated_record_bytes"] = inflated
-        if "owner" not in metrics and owner is not None:
-            metrics["owner"] = list(owner)
-    return stats
+            # over RCCL with the device pack, the dealing itself runs on the device (core.deal_records_device: one upload of the round's streams,
+            # kernels put every record where the all-to-all sends it from): no host walk over the records, no host copy of the parts
+            # (MSNV_DEAL=host keeps the host threads)
+            if in_hbm or (len(carrier) > 0 and self.on_device("deal")):
+                tsend, pb, gap, rows, record_bytes = self.dealt_on_device(carrier, len(mine))
+                sizes = _size_tables(tsend, pb, gap)
+                for i, row, nb in zip(mine, rows, record_bytes):
+                    self.inflated += int(nb)
+                    self.stats[i] = row
+                send = DeviceSend(tsend, sizes)
+                for key in ("records_dealt_on_device_bytes",) + (("bams_inflated_on_device_bytes",) if in_hbm else ()):
+                    self.metrics[key] = self.metrics.get(key, 0) + sum(int(nb) for nb in record_bytes)
+                return send, None
+            # one walk over every sample's records (msnv_records_partition: owner of every record's contig, qaCompute's statistics); the
+            # library releases the GIL, so the round's samples are dealt side by side (one after the other this was 0.3 s per GB and rank)
+            deal = lambda rec: self.core.partition_records(rec, self.owner, _world, self.cov_min_mapq)
+            if len(carrier) > 1:
+                with ThreadPoolExecutor(max_workers=min(len(carrier), self.batch)) as ex:
+                    dealt = list(ex.map(deal, carrier))
+            else:
+                dealt = [deal(rec) for rec in carrier]
+            per_dest = [[] for _ in range(_world)]          # per destination rank: my samples' parts in sample order
+            for i, rec, (parts, st) in zip(mine, carrier, dealt):
+                self.inflated += int(rec.size)
+                self.stats[i] = st
+                for q in range(_world):
+                    per_dest[q].append(parts[q])
+            return [np.concatenate([np.array([p.size for p in dest], dtype=np.int64).view(np.uint8)] + dest) if dest else nothing[0] for dest in per_dest], None
+        except Exception as e:                               # noqa: BLE001
+            return nothing, e
+
+    def exchange(self, send, failure):
+        """One exchange per round, whatever this rank has to send; its status word carries my failure: I raise my own exception then, the
+        other ranks RankError.  Over RCCL the received streams stay in HBM where the pack runs there."""
+        try:
+            return exchange_records(send, status=0 if failure is None else int(getattr(failure, "code", 0)) or 99, keep_on_device=self.on_device("pack"))
+        except RankError:
+            if failure is not None:
+                raise failure
+            raise
+
+    def append(self, base, plan_round, got):
+        """The received parts -> the round's samples, in sample order, appended to this rank's dataset: in HBM where they stayed there (parsed,
+        filtered and packed by csrc/devpack.hip: no copy to the host, no host pack, no second upload), else as host arrays.  A failure waits
+        in `pending`: the other ranks hear of it in the next round's status word, or in agree()."""
+        ds, in_hbm = self.ds, isinstance(got, DeviceParts)
+        n_from = [sum(1 for _, r in plan_round if r == q) for q in range(_world)]
+        sizes_of = [(got.head(r, 8 * n_from[r]) if in_hbm else got[r][:8 * n_from[r]]).view(np.int64) for r in range(_world)]
+        where = unpack_ranges(plan_round, base, self.batch, _world, sizes_of)
+        try:
+            if in_hbm:
+                ds.add_samples_records_device([got.address(r, o) if n else 0 for r, o, n in where], [n for _, _, n in where])
+            elif hasattr(ds, "add_samples_records"):         # the round's samples are packed side by side by the library
+                ds.add_samples_records([got[r][o:o + n] for r, o, n in where], self.pack_threads)
+            else:
+                for r, o, n in where:
+                    ds.add_sample_records(got[r][o:o + n])
+        except Exception as e:                               # noqa: BLE001
+            self.pending = e
+        if in_hbm:
+            self.metrics["records_packed_on_device_bytes"] = self.metrics.get("records_packed_on_device_bytes", 0) + sum(n for _, _, n in where)
+
+    def deliver(self, base, plan_round, mine, carrier, failure):
+        """Deals the round's records to the contig owners, exchanges them, appends the round's samples to this rank's dataset."""
+        with _timed(self.seconds, "deliver_s"):
+            if failure is None and self.pending is not None:     # the previous round's append failed here: this round's status word says so
+                failure, self.pending = self.pending, None
+            send, failure = self.deal(mine, carrier, failure)
+            got = self.exchange(send, failure)
+            self.append(base, plan_round, got)
+            del send, got                                    # (a round's bytes go back inside the timed block, where deliver_s has always counted that)
+
+    # ---- stream: the rounds that flow through
+    def stream(self):
+        """Round k + 1 is DECODED WHILE round k is dealt, exchanged and packed (MSNV_FEED_OVERLAP) -- on a thread of its own when the decoder
+        stays on the host (a test's / benchmark's read_records, MSNV_INFLATE=host: the library releases the GIL and touches nothing of the
+        context); on the DEVICE route through a second context of the device (core.Dataset.set_feed_context: its own stream, staging buffers
+        and pinned words), again from a thread of its own, under the exchange and the pack of round k on the dataset's context -- the inflate
+        kernel is bound by latency per symbol and leaves most of the chip to the pack.  Else one round after the other, with a read-ahead
+        hint for the files of the next: one context, one thread at a time."""
+        rounds, ds = self.rounds, self.ds
+        host_decoder = self.read_records is not None or knobs.inflate_where("d") == "h"
+        want_overlap = self.feed_overlap if self.feed_overlap is not None else knobs.feed_overlap()      # (an argument of the run; the environment is the default)
+        self.overlap = bool(host_decoder and want_overlap and len(rounds) > 1)
+        feed_ctx = None
+        if not self.overlap and want_overlap and len(rounds) > 1 and self.on_device("inflate") and hasattr(ds, "set_feed_context"):
+            try:
+                feed_ctx = self.core.Context(ds.ctx.device)
+                ds.set_feed_context(feed_ctx)
+                self.overlap = self.second_context = True
+            except Exception:                                # noqa: BLE001 -- no second context: one round after the other
+                feed_ctx = None
+        try:
+            if self.overlap:
+                with ThreadPoolExecutor(max_workers=1) as ahead:
+                    nxt = ahead.submit(self.decode, rounds[0][1])
+                    for j, (base, plan_round) in enumerate(rounds):
+                        got = nxt.result()
+                        nxt = ahead.submit(self.decode, rounds[j + 1][1]) if j + 1 < len(rounds) else None
+                        self.deliver(base, plan_round, *got)
+                return
+            for j, (base, plan_round) in enumerate(rounds):
+                if j + 1 < len(rounds) and self.read_records is None:
+                    _read_ahead_hint([self.bam_paths[i] for i, r in rounds[j + 1][1] if r == _rank])
+                self.deliver(base, plan_round, *self.decode(plan_round))
+        finally:
+            if feed_ctx is not None:
+                ds.set_feed_context(None)
+                feed_ctx.close()
+
+    def finish(self):
+        """The last append's failure reaches every rank; the statistics rows, each counted by its sample's decoder, reach every rank too."""
+        metrics = self.metrics
+        metrics.update(self.seconds)
+        metrics["decode_overlapped"] = self.overlap
+        metrics["decode_on_second_context"] = self.second_context
+        agree(self.pending, "the last round of records was appended")
+        allstats = gather_fixed(self.stats)
+        metrics["inflated_record_bytes"] = self.inflated
+        if "owner" not in metrics and self.owner is not None:
+            metrics["owner"] = list(self.owner)
+        return np.maximum.reduce(allstats) if len(allstats) > 1 else self.stats      # every row is non-zero on exactly one rank
+
+
+def feed_sharded(ds, bam_paths, owner, cov_min_mapq=1, batch=1, read_records=None, metrics=None, plan=None, pack_threads=0, ctx_when_ready=None, feed_overlap=None):
+    """Decode-sharded input of one dataset per rank: every BAM is read and inflated by ONE rank, its records are dealt by
+    contig owner (core.partition_records) and exchanged, and every rank appends all samples in all_samples order holding
+    only its contigs' records.  Returns stats[n_samples][6] (qaCompute's per-BAM statistics, counted by the decoder and
+    all-gathered), or None where the streams were staged for finalize to pack.  read_records(path) -> uint8 array replaces the
+    BAM reader in tests.
+
+    owner = None: the contig owners are fixed HERE, after the first round has been decoded and before anything is dealt --
+    plan = (names, lengths); the ranks add up the aligned bases per contig of their first-round samples (= genome length x
+    coverage, the reference's split weight, createOptimumSplit.py:46-50), shard_contigs assigns the species, the dataset gets
+    its contig mask and metrics["owner"] the assignment."""
+    if _dist is None and read_records is None:
+        return _feed_one_process(ds, bam_paths, owner, batch, metrics, plan, ctx_when_ready)
+    feed = Feed(ds, bam_paths, owner, cov_min_mapq, batch, read_records, metrics, pack_threads, feed_overlap)
+    if owner is None:
+        feed.plan_owners(plan)
+    feed.stream()
+    return feed.finish()
 
 
 # ------------------------------------------------------------------------------------ gather of the result tables
@@ -882,7 +899,6 @@ def resident_project_run(ctx, first_bam, fasta_path, bam_paths, params, batch=1,
       names, lengths, n_samples, stats[n_samples][6], acc (SparseAcc on rank 0, None elsewhere / without coverage),
       sites / row_off / cell_sample / cells / ann (merged, (tid, pos) order, `dropped` marks the global first line; rank 0 only),
       first_any / first_from1 (per contig, see core.Dataset.first_lines), metrics."""
-    import time
     from . import core
     # ctx may be a zero-argument callable that returns the context when it is first needed (cli.py creates it on a thread of its own:
     # the HIP runtime takes ~0.5 s to come up, which a one-process run spends reading and packing BAMs with host threads)
@@ -919,7 +935,7 @@ def resident_project_run(ctx, first_bam, fasta_path, bam_paths, params, batch=1,
         agree(err, "the datasets were finalized")
         metrics["finalize_s"] = time.perf_counter() - t0
         if res["stats"] is None:                           # staged streams: packed by finalize
-            res["stats"] = np.stack([ds.sample_stats(i) for i in range(len(bam_paths))]) if bam_paths else np.zeros((0, len(core.STATS_FIELDS)), np.uint32)
+            res["stats"] = _all_sample_stats(ds, len(bam_paths))
         if hasattr(ds, "pack_stats"):
             metrics["pack_on_device"] = ds.pack_stats()
         gstats = {}

@@ -1,4 +1,4 @@
-"""Worker of the world_size-2 gloo test of the decode-sharded input (parallel.feed_sharded): every sample is "decoded" by
+"""Worker of the gloo tests (two ranks, three ranks) of the decode-sharded input (parallel.feed_sharded): every sample is "decoded" by
 exactly one rank, its records are dealt by contig owner and exchanged, and every rank must end up with all samples in
 order holding exactly its own contigs' records.  No GPU: the dataset is a recorder."""
 import os
@@ -13,10 +13,14 @@ from metasnv_amd import core, parallel  # noqa: E402
 
 
 class Recorder:
-    def __init__(self):
-        self.samples = []
+    """fail_append_at = f: the append of sample index f fails on this rank (what a pack that runs out of memory does)."""
+
+    def __init__(self, fail_append_at=-1):
+        self.samples, self.fail_append_at = [], fail_append_at
 
     def add_sample_records(self, rec):
+        if len(self.samples) == self.fail_append_at:
+            raise core._lib.MsnvError(6, "sample %d: no memory for its records (test)" % len(self.samples))
         self.samples.append(np.array(rec, dtype=np.uint8, copy=True))
 
 
@@ -30,6 +34,7 @@ def main():
     decoded = []
 
     fail_at = int(sys.argv[3]) if len(sys.argv) > 3 else -1
+    fail_append_at = int(sys.argv[4]) if len(sys.argv) > 4 else -1       # (on rank 1 only)
 
     def read_records(path):
         if int(path) == fail_at:
@@ -37,13 +42,14 @@ def main():
         decoded.append(int(path))
         return syn.sample_records(int(path))
 
-    rec = Recorder()
+    rec = Recorder(fail_append_at if rank == 1 else -1)
     metrics = {}
     try:
         stats = parallel.feed_sharded(rec, [str(i) for i in range(sp.n_samples)], owner, 1, batch, read_records=read_records, metrics=metrics)
     except (core._lib.MsnvError, parallel.RankError) as e:
         # the rank that failed raises its own error, the others learn of it in the exchange: nobody waits in a collective
         open(os.path.join(work, "error%d" % rank), "w").write("%s: %s" % (type(e).__name__, e))
+        open(os.path.join(work, "appended%d" % rank), "w").write("%d" % len(rec.samples))
         parallel.abort(3)
     np.save(os.path.join(work, "stats%d.npy" % rank), stats)
     np.save(os.path.join(work, "decoded%d.npy" % rank), np.array(decoded, dtype=np.int64))

@@ -44,7 +44,18 @@ def main():
     rank, world, local = parallel.init_from_env()
     rec = Recorder()
     metrics = {}
-    parallel.feed_sharded(rec, [str(i) for i in range(6)], None, 1, 1, read_records=lambda p: sample_records(int(p)), metrics=metrics, plan=(NAMES, LENGTHS))
+    fail_at = int(sys.argv[2]) if len(sys.argv) > 2 else -1
+
+    def read_records(p):
+        if int(p) == fail_at:
+            raise core._lib.MsnvError(3, "sample %s: malformed BAM (test)" % p)
+        return sample_records(int(p))
+
+    try:
+        parallel.feed_sharded(rec, [str(i) for i in range(6)], None, 1, 1, read_records=read_records, metrics=metrics, plan=(NAMES, LENGTHS))
+    except (core._lib.MsnvError, parallel.RankError) as e:
+        open(os.path.join(work, "error%d" % rank), "w").write("%s: %s | %d appended" % (type(e).__name__, e, len(rec.samples)))
+        parallel.abort(3)
     owner = metrics["owner"]
     assert rec.mask == [o == rank for o in owner]
     mine = np.zeros(len(NAMES), dtype=np.uint64)

@@ -100,45 +100,77 @@ def _records(buf):
     return out
 
 
+def _torchrun(world, worker, args, env=None, timeout=300):
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=%d" % world, "--master-addr", "127.0.0.1",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "tests", worker)] + [str(a) for a in args]
+    return subprocess.run(cmd, env=dict(os.environ, MASTER_ADDR="127.0.0.1", **(env or {})), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=timeout)
+
+
+def _feed_deals_every_record_to_its_owner(work, world, batch, env, serial):
+    r = _torchrun(world, "_feed_worker.py", [work, batch], env)
+    assert r.returncode == 0, r.stdout.decode()[-3000:]
+    ranks = range(world)
+    for k in ranks:                                                              # (several rounds stream through: the decoder ran ahead unless told not to)
+        assert int(open(os.path.join(work, "n%d" % k)).read().split()[2]) == (0 if serial else 1)
+    sp = core.synth_params(n_species=5, contig_len=2500, n_samples=7, mean_cov=6.0, frac_absent=0.3, seed=77)
+    syn = core.Synth(sp)
+    owner = np.load(os.path.join(work, "owner.npy"))
+    assert set(owner.tolist()) == set(ranks)
+    dec = [np.load(os.path.join(work, "decoded%d.npy" % k)).tolist() for k in ranks]
+    assert sorted(sum(dec, [])) == list(range(sp.n_samples))                     # every BAM decoded once in the whole job
+    assert max(len(d) for d in dec) - min(len(d) for d in dec) <= batch
+    # rank r decodes samples base + r * batch ... of every round of world x batch samples
+    assert [sorted(d) for d in dec] == [[i for i in range(sp.n_samples) if i % (world * batch) // batch == k] for k in ranks]
+    total = 0
+    nbytes = [int(open(os.path.join(work, "n%d" % k)).read().split()[1]) for k in ranks]
+    for i in range(sp.n_samples):
+        full = syn.sample_records(i)
+        total += full.size
+        recs = _records(full)
+        for k in ranks:
+            got = np.fromfile(os.path.join(work, "r%d_s%d.bin" % (k, i)), dtype=np.uint8)
+            want = b"".join(b for t, b in recs if t >= 0 and owner[t] == k)
+            assert bytes(got) == want, (i, k)
+        # statistics counted by the decoder reach every rank
+        parts, st = core.partition_records(full, owner, world, 1)
+        for k in ranks:
+            assert (np.load(os.path.join(work, "stats%d.npy" % k))[i] == st).all()
+        assert st[0] == len(recs)
+    assert sum(nbytes) == total and max(nbytes) <= 0.75 * total
+
+
 @pytest.mark.parametrize("batch,slice_kb", [(1, None), (2, None), (2, "4"), (1, "serial")])
 def test_two_rank_decode_sharding_deals_every_record_to_its_owner(tmp_path, batch, slice_kb):
     """parallel.feed_sharded over gloo: each sample is read by exactly one rank (per-rank decoded bytes ~ 1/N of the job),
     and after the all-to-all every rank holds, per sample and in order, exactly the records of the contigs it owns.  Round k + 1 is
     decoded while round k is exchanged (round 5; "serial": MSNV_FEED_OVERLAP=0, one after the other)."""
     serial = slice_kb == "serial"
-    slice_kb = None if serial else slice_kb
-    work = str(tmp_path)
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "tests", "_feed_worker.py"), work, str(batch)]
     # slice_kb: the byte exchange in slices of 4 KB (parallel.exchange_records walks a large round in slices: uneven parts, parts that end early)
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", **({"MSNV_A2A_SLICE_KB": slice_kb} if slice_kb else {}), **({"MSNV_FEED_OVERLAP": "0"} if serial else {}))
-    r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
-    assert r.returncode == 0, r.stdout.decode()[-3000:]
-    for k in (0, 1):                                                             # (several rounds stream through: the decoder ran ahead unless told not to)
-        assert int(open(os.path.join(work, "n%d" % k)).read().split()[2]) == (0 if serial else 1)
-    sp = core.synth_params(n_species=5, contig_len=2500, n_samples=7, mean_cov=6.0, frac_absent=0.3, seed=77)
-    syn = core.Synth(sp)
-    owner = np.load(os.path.join(work, "owner.npy"))
-    assert set(owner.tolist()) == {0, 1}
-    dec = [np.load(os.path.join(work, "decoded%d.npy" % k)).tolist() for k in (0, 1)]
-    assert sorted(dec[0] + dec[1]) == list(range(sp.n_samples))                  # every BAM decoded once in the whole job
-    assert abs(len(dec[0]) - len(dec[1])) <= batch
-    total = 0
-    nbytes = [int(open(os.path.join(work, "n%d" % k)).read().split()[1]) for k in (0, 1)]
-    for i in range(sp.n_samples):
-        full = syn.sample_records(i)
-        total += full.size
-        recs = _records(full)
-        for k in (0, 1):
-            got = np.fromfile(os.path.join(work, "r%d_s%d.bin" % (k, i)), dtype=np.uint8)
-            want = b"".join(b for t, b in recs if t >= 0 and owner[t] == k)
-            assert bytes(got) == want, (i, k)
-        # statistics counted by the decoder reach every rank
-        parts, st = core.partition_records(full, owner, 2, 1)
-        for k in (0, 1):
-            assert (np.load(os.path.join(work, "stats%d.npy" % k))[i] == st).all()
-        assert st[0] == len(recs)
-    assert nbytes[0] + nbytes[1] == total and max(nbytes) <= 0.75 * total
+    env = {"MSNV_FEED_OVERLAP": "0"} if serial else {"MSNV_A2A_SLICE_KB": slice_kb} if slice_kb else {}
+    _feed_deals_every_record_to_its_owner(str(tmp_path), 2, batch, env, serial)
+
+
+@pytest.mark.parametrize("batch", [2, 1])
+def test_three_rank_decode_sharding_deals_every_record_to_its_owner(tmp_path, batch):
+    """Three senders per round, and rounds in which some of them send nothing: 7 samples are one round of 6 and a round in which ranks 1
+    and 2 decode nothing at batch 2, three rounds of which the last has one decoder at batch 1 (a sample's index among its sender's
+    samples of the round is i - base - r * batch)."""
+    _feed_deals_every_record_to_its_owner(str(tmp_path), 3, batch, {}, False)
+
+
+@pytest.mark.parametrize("overlap", [None, "0"])
+@pytest.mark.parametrize("fail_at,where,appended", [(2, "the records were decoded", (4, 2)), (6, "the last round of records was appended", (7, 6))])
+def test_two_rank_append_failure_reaches_every_rank(tmp_path, fail_at, where, appended, overlap):
+    """A rank whose APPEND of sample f fails goes on to the next collective and says so there: in the status word of the next round's
+    exchange (every rank has appended that round by then: 2 samples a round), or after the last round in agree().  It raises its own error,
+    the other rank a RankError that names it.  Batch 1; run with the decoder ahead and with MSNV_FEED_OVERLAP=0."""
+    work = str(tmp_path)
+    r = _torchrun(2, "_feed_worker.py", [work, 1, -1, fail_at], {"MSNV_FEED_OVERLAP": overlap} if overlap else {}, timeout=120)
+    assert r.returncode != 0
+    e = [open(os.path.join(work, "error%d" % k)).read() for k in (0, 1)]
+    assert e[1].startswith("MsnvError") and e[1].endswith("sample %d: no memory for its records (test)" % fail_at)
+    assert e[0] == "RankError: rank 1 reported error 6 while " + where
+    assert tuple(int(open(os.path.join(work, "appended%d" % k)).read()) for k in (0, 1)) == appended
 
 
 def test_two_rank_decode_failure_reaches_every_rank(tmp_path):
@@ -171,6 +203,44 @@ def test_two_rank_owners_follow_length_times_coverage(tmp_path):
     from metasnv_amd import parallel
     by_len = parallel.shard_contigs(["sp%d.x.c1" % k for k in range(6)], [20000] * 6, 2)
     assert sorted(np.bincount(by_len).tolist()) == [3, 3]
+
+
+def test_two_rank_decode_failure_while_the_owners_are_planned_reaches_every_rank(tmp_path):
+    """owner=None: sample 1 (rank 1's of the first round) fails to decode while the rounds are held for the split planner.  Both ranks
+    stop holding rounds in that round (the vote), fix the owners, and leave in the held round's exchange -- nobody waits in a gather
+    (the time limit is the assertion), nothing is appended."""
+    work = str(tmp_path)
+    r = _torchrun(2, "_lpt_worker.py", [work, 1], timeout=120)
+    assert r.returncode != 0
+    e = [open(os.path.join(work, "error%d" % k)).read() for k in (0, 1)]
+    assert e[1] == "MsnvError: libmsnv error 3: sample 1: malformed BAM (test) | 0 appended"
+    assert e[0] == "RankError: rank 1 reported error 3 while the records were decoded | 0 appended"
+
+
+def test_unpack_ranges_tile_every_senders_part_in_sample_order():
+    """parallel.unpack_ranges without a process group: for every world, batch and cohort size, each round's samples come back in sample
+    order, each from the rank that decoded it, and the ranges of a sender's samples tile its part behind the 8-byte-per-sample header
+    (zero-length samples included: a third of them)."""
+    from metasnv_amd import parallel
+    rng = np.random.default_rng(11)
+    for world in range(1, 5):
+        for batch in range(1, 4):
+            for n in range(1, world * batch * 2 + 2):
+                size = (rng.integers(0, 3, n) > 0) * rng.integers(1, 50, n)
+                for base in range(0, n, world * batch):
+                    plan_round = [(i, (i - base) // batch) for i in range(base, min(n, base + world * batch))]
+                    held = [[i for i, r in plan_round if r == q] for q in range(world)]
+                    sizes_of = [np.array([size[i] for i in held[q]], dtype=np.int64) for q in range(world)]
+                    got = parallel.unpack_ranges(plan_round, base, batch, world, sizes_of)
+                    assert [r for r, _, _ in got] == [r for _, r in plan_round]
+                    assert [nb for _, _, nb in got] == [int(size[i]) for i, _ in plan_round]
+                    for q in range(world):
+                        at = 8 * len(held[q])
+                        for (i, _), (r, o, nb) in zip(plan_round, got):
+                            if r == q:
+                                assert o == at, (world, batch, n, i)
+                                at += nb
+                        assert at == 8 * len(held[q]) + int(sizes_of[q].sum())
 
 
 def test_shard_contigs_weights():
