@@ -409,6 +409,58 @@ int msnv_pcoa(msnv_ctx *ctx, int32_t n, const double *dist, int32_t n_axes, doub
               int64_t info[8], double *ms_kernel);
 int msnv_pcoa_file(msnv_ctx *ctx, const char *dist_path, const char *dir, const char *species, int64_t result[8], double *ms_kernel);
 
+/* The row order of the four distance heatmaps of subpopr's per-species report (src/subpopr/inst/rmd/detailedSpeciesReport.rmd:142, :222, :250,
+ * :402): heatmap(distfun = as.dist, hclustfun = hclust(method = ...)).  Restated from memory of R's hclust.f, hcass2, as.dendrogram.hclust,
+ * reorder.dendrogram and heatmap; no R was run (unpinned).
+ *
+ * msnv_hclust_tasks -- the array form.  dist: the n x n matrix under msnv_pam_tasks' checks (else MSNV_EDOMAIN).  A task is a list of m distinct
+ * sample indices (2 <= m <= n; a repeated or outlying index: MSNV_EDOMAIN) and a method (not one of MSNV_HCLUST_*, or n_tasks < 1: MSNV_EINVAL);
+ * the lists are packed behind each other in idx, at most 2^26 entries in one call (MSNV_ECAPACITY).  Positions 0..m-1 are positions in the
+ * list: W[a][b] = D[idx[a]][idx[b]], size[a] = 1, every position active.
+ *   step s = 1..m-1   among the active pairs a < b the smallest W[a][b]; among equal values the smallest a, then the smallest b; h_s = W[a][b].
+ *              For every other active k: W[k][a] = W[a][k] = f(W[k][a], W[k][b]) with f(x, y) =
+ *                MSNV_HCLUST_AVERAGE   (size[a] x + size[b] y) / (size[a] + size[b]), sizes as doubles: two products, one sum, one quotient
+ *                MSNV_HCLUST_COMPLETE  max(x, y)          MSNV_HCLUST_SINGLE  min(x, y)          MSNV_HCLUST_MCQUITTY  0.5 x + 0.5 y
+ *              each one fp64 operation, never contracted.  Then size[a] += size[b] and b is inactive.  All four are monotone: h_1 <= ... <= h_{m-1}.
+ *   merge      R's hc$merge: a singleton is -(position + 1), the cluster made at step s is s; row s holds the labels of the clusters at a and
+ *              at b -- two singletons in the order (a, b), a singleton before a cluster, of two clusters the smaller step first
+ *   height     height[s - 1] = h_s
+ *   order      R's hc$order, as 0-based positions: the leaves of the tree left to right, row s's first entry the left child
+ * With off_t the sum of the earlier m: task t's merge is 2 (m_t - 1) ints (row by row) at 2 (off_t - t), its height m_t - 1 doubles at
+ * off_t - t, its order m_t ints at off_t.  One workgroup per task in one launch; a batch whose gathered sub-matrices (8 m^2 bytes each) pass the
+ * scratch budget is cut into several launches.  The result is a function of the task alone.
+ * Known divergence: R finds the minimum through nearest-neighbour lists that it repairs lazily; when an update creates a value equal to a row's
+ * current nearest distance at a smaller column index, R keeps the old column and this rule takes the new one.  Without equal cells among the
+ * candidates the two agree.
+ *
+ * msnv_heatmap_order -- reorder(as.dendrogram(hc), weights) with agglo.FUN = sum, then order.dendrogram; host only, no context.  A leaf's value is
+ * its weight; at every node, bottom up, the two children are put in ascending order of value (equal values keep their merge order) and the node's
+ * value is the long double sum of the two in that order, rounded to double.  order: the leaves left to right, 0-based positions.  m < 2 or a
+ * merge that is not a tree in the encoding above: MSNV_EINVAL; a weight that is not finite: MSNV_EDOMAIN.
+ *
+ * msnv_heatmap_file -- the stage on files.  Reads dist_path (<species>.filtered.mann.dist, as msnv_cluster_file does; an NA or empty cell is
+ * MSNV_EFORMAT) and the sample names in the header of dir/<species>_mann_distMatrixUsedForClustMedoidDefns.txt -- the discovery subset, whose
+ * cells are taken from dist_path; a name dist_path does not hold, or one listed twice: MSNV_EFORMAT -- and clust from
+ * dir/<species>_mann_clustering.tab (the file absent or a sample not listed: NA).  Both trees run in one call of the array form: every sample
+ * with MSNV_HCLUST_AVERAGE (:142, :222, :402), the discovery subset with MSNV_HCLUST_COMPLETE (:250).  The weights are R's rowMeans of the tree's
+ * sub-matrix: a long double sum over ascending columns, divided by m, rounded to double.  Written into dir, as write.table(sep = '\t', quote = F)
+ * prints them, doubles with %.15g (our own files: the reference keeps these numbers as pixels only):
+ *   <species>_mann_hclust_{all,discovery}.tab    merge1, merge2, height; rows 1..m-1
+ *   <species>_mann_heatmap_{all,discovery}.tab   one row per sample in heatmap order, named by the sample: index (1-based place in the tree's
+ *                                                sample list), hclustPos (1-based place in hc$order), inDiscoverySubset (TRUE / FALSE), clust
+ * result: [0] MSNV_HEATMAP_* (NO_DISCOVERY: the medoid-definition file is absent or names fewer than two samples; the two _all files are
+ * written) [1] samples in the full tree [2] samples in the discovery tree [3] 1 when a clustering file was read [4..7] 0. */
+#define MSNV_HCLUST_AVERAGE   0
+#define MSNV_HCLUST_COMPLETE  1
+#define MSNV_HCLUST_SINGLE    2
+#define MSNV_HCLUST_MCQUITTY  3
+#define MSNV_HEATMAP_OK            0
+#define MSNV_HEATMAP_NO_DISCOVERY  1
+int msnv_hclust_tasks(msnv_ctx *ctx, int32_t n, const double *dist, int64_t n_tasks, const int32_t *task_m, const int32_t *task_method, const int32_t *idx,
+                      int32_t *merge, double *height, int32_t *order, double *ms_kernel);
+int msnv_heatmap_order(int32_t m, const int32_t *merge, const double *weights, int32_t *order);
+int msnv_heatmap_file(msnv_ctx *ctx, const char *dist_path, const char *dir, const char *species, int64_t result[8], double *ms_kernel);
+
 /* subpopr's writeGenotypeFreqs -> computeUniquePosPerCluster (src/subpopr/R/writeGenotypeFreqs.R:2-112, :195-277): which SNVs tell one
  * subspecies from every other.  Restated from reading the R code; no R was run (unpinned).
  *

@@ -25,6 +25,8 @@ CORR_PEARSON, CORR_SPEARMAN = 0, 1                             # msnv_corr_stats
 CLUSTER_OK, CLUSTER_NONE, CLUSTER_MEDOID_FAILED, CLUSTER_TOO_FEW, CLUSTER_ALL_EQUAL = range(5)   # msnv_cluster_file result[0]
 MEMBSTAB_OK, MEMBSTAB_NOT_RATED = range(2)                      # msnv_membership_stability_file result[0]
 PCOA_OK, PCOA_TOO_FEW_AXES = range(2)                           # msnv_pcoa info[0], msnv_pcoa_file result[0]
+HCLUST_AVERAGE, HCLUST_COMPLETE, HCLUST_SINGLE, HCLUST_MCQUITTY = range(4)   # msnv_hclust_tasks methods
+HEATMAP_OK, HEATMAP_NO_DISCOVERY = range(2)                     # msnv_heatmap_file result[0]
 GENOTYPE_OK, GENOTYPE_SINGLE, GENOTYPE_NO_POSITIONS, GENOTYPE_CLUSTER_MISSING, GENOTYPE_CUTOFF_BAD = range(5)   # msnv_genotype_file result[0]
 PROFILE_OK, PROFILE_NO_FILES, PROFILE_NONE_USABLE = range(3)   # msnv_subpop_profile_files result[0]
 
@@ -248,6 +250,10 @@ SYMBOLS = [
     ("msnv_membership_stability_file", C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_char_p, P(MembStabOpts), P(C.c_int64), P(C.c_double)]),
     ("msnv_pcoa", C.c_int, [_vp, C.c_int32, P(C.c_double), C.c_int32, P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_int64), P(C.c_double)]),
     ("msnv_pcoa_file", C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_char_p, P(C.c_int64), P(C.c_double)]),
+    ("msnv_hclust_tasks", C.c_int, [_vp, C.c_int32, P(C.c_double), C.c_int64, P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_double), P(C.c_int32),
+                                    P(C.c_double)]),
+    ("msnv_heatmap_order", C.c_int, [C.c_int32, P(C.c_int32), P(C.c_double), P(C.c_int32)]),
+    ("msnv_heatmap_file", C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_char_p, P(C.c_int64), P(C.c_double)]),
     ("msnv_genotype_rows", C.c_int, [_vp, C.c_uint64, C.c_int32, P(C.c_double), P(C.c_int32), C.c_int32, C.c_double, P(C.c_uint32), P(C.c_uint32), P(C.c_uint64),
                                      P(C.c_double)]),
     ("msnv_genotype_file", C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_double, P(C.c_int64), P(C.c_double)]),

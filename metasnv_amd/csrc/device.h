@@ -4,6 +4,7 @@
 #include <cstdint>
 
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "dataset.h"
@@ -242,7 +243,7 @@ int  dev_inflate_resident(msnv_ctx *ctx, const uint8_t *host_in, uint64_t comp_b
                           uint32_t check_every, std::vector<uint32_t> &status, double *ms_kernel);
 int  dev_inflate_patch(msnv_ctx *ctx, uint64_t out_off, const uint8_t *data, uint32_t n);
 
-// ---- the stages that work on files (textcall.hip; dist.cpp + dist_k.hip; div.cpp + div_k.hip; subpopr.cpp + subpopr_k.hip; genecorr.cpp + genecorr_k.hip; cluster.cpp + cluster_k.hip; pcoa.cpp + pcoa_k.hip; genotype.cpp + genotype_k.hip; profile.cpp + profile_k.hip)
+// ---- the stages that work on files (textcall.hip; dist.cpp + dist_k.hip; div.cpp + div_k.hip; subpopr.cpp + subpopr_k.hip; genecorr.cpp + genecorr_k.hip; cluster.cpp + cluster_k.hip; pcoa.cpp + pcoa_k.hip; hclust.cpp + hclust_k.hip; genotype.cpp + genotype_k.hip; profile.cpp + profile_k.hip)
 int  text_call(msnv_ctx *ctx, const char *text, uint64_t n_text, const msnv_params &p, const char *ref_fasta, const char *ann_path,
                const char *called_path, const char *indiv_path, uint64_t stats[8]);
 int  dist_file(msnv_ctx *ctx, const char *freq_path, const char *mann_path, const char *allele_path, double threshold,
@@ -292,6 +293,16 @@ std::vector<int32_t> remove_outliers(const std::vector<double> &d, size_t n_all)
 constexpr uint32_t PCOA_MAX_SWEEPS = 64;
 int dev_pcoa(const char *who, const double *dist, uint32_t n, uint32_t n_axes, void *stream, double *eig, double *rel_eig, double *axis_pct, double *vectors,
              int64_t info[8], double *ms_kernel);
+// pcoa.cpp, shared with hclust.cpp: the cell of column `column` per row name, as text, of a table as write.table(sep = '\t', quote = F) prints it
+int read_r_column(const std::string &path, const char *column, std::unordered_map<std::string, std::string> &cell);
+bool file_exists(const std::string &path);
+
+// hclust.cpp + hclust_k.hip: hclust(method = average | complete | single | mcquitty) of many index lists of one resident matrix, one workgroup of
+// HCLUST_THREADS per task (include/msnv.h).  One launch over the tasks given, lists packed as msnv_hclust_tasks packs them; out, per task at
+// (the sum of the earlier m) - t: the m - 1 steps (a, b, h) in positions of the list.  The caller cuts a batch by its scratch, 8 * sum(m^2) bytes.
+constexpr uint32_t HCLUST_THREADS = 256;
+int dev_hclust_batch(const ClusterDev &c, uint64_t n_tasks, const uint32_t *m, const uint32_t *method, const int32_t *idx, void *stream, int32_t *step_a, int32_t *step_b,
+                     double *step_h, double *ms_kernel);
 
 // genotype.cpp + genotype_k.hip: subpopr's computeUniquePosPerCluster.  col[] lists the columns in use in cluster order, seg[k] is the first
 // entry of cluster k (seg[K] = the list's length).  A row with a mean difference within GENO_GUARD of the threshold is flagged near.

@@ -206,5 +206,10 @@ inline int mptext_round_samples() { return std::max(1, int_or("MSNV_MPTEXT_ROUND
 // most n rows, so that a table of a few rows walks several slabs.  Per call (tests/test_gpu_stage_slabs.py).
 inline uint64_t stage_slab_rows() { return (uint64_t)std::max<long long>(0, i64_or("MSNV_STAGE_SLAB_ROWS", 0)); }
 
+// ---------------------------------------------------------------------------------- the hclust batches (hclust.cpp)
+// MSNV_HCLUST_SCRATCH_KB (1048576 = 1 GiB; at least 1): kilobytes of gathered sub-matrices, 8 m^2 bytes per task, that one launch of
+// msnv_hclust_tasks_k may hold; a task that is larger is a launch of its own.  Per call (tests/test_gpu_hclust.py sets 1 to cut a batch).
+inline uint64_t hclust_scratch_bytes() { return (uint64_t)std::max<long long>(1, i64_or("MSNV_HCLUST_SCRATCH_KB", 1ll << 20)) << 10; }
+
 }  // namespace knob
 }  // namespace msnv

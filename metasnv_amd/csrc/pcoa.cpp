@@ -18,8 +18,7 @@
 
 namespace msnv {
 
-namespace {
-
+// ---- what msnv_heatmap_file (hclust.cpp) shares with this file (device.h)
 // A table as write.table(sep = '\t', quote = F) prints it: a header without a cell for the row names, then name + cells.  Returns the cell of column
 // `column` per row name, as text.
 int read_r_column(const std::string &path, const char *column, std::unordered_map<std::string, std::string> &cell) {
@@ -51,7 +50,6 @@ bool file_exists(const std::string &path) {
     return f != nullptr;
 }
 
-}  // namespace
 }  // namespace msnv
 
 using namespace msnv;

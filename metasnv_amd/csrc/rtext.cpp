@@ -1,4 +1,4 @@
-// metasnv_amd/csrc/rtext.cpp -- what the subpopr stages (subpopr.cpp, cluster.cpp, pcoa.cpp, genotype.cpp, profile.cpp, genecorr.cpp) share on the host:
+// metasnv_amd/csrc/rtext.cpp -- what the subpopr stages (subpopr.cpp, cluster.cpp, pcoa.cpp, hclust.cpp, genotype.cpp, profile.cpp, genecorr.cpp) share on the host:
 // numbers as R computes and writes them, whole files in and out, and the parsing of a field of a tab-separated table.  Declared in
 // msnv_internal.h.  How a stage walks the LINES of its text stays with the stage: each follows what its reference's reader does with blank
 // lines, carriage returns and the last newline.

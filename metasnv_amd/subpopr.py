@@ -20,6 +20,11 @@
       <species>.filtered.mann.dist + <dir>/<species>_mann_clustering.tab (+ <species>_freq_composition.tab)  ->  <dir>/<species>_mann_pcoa_proj.tab
       and, our own file, <species>_mann_pcoa_eig.tab
 
+  heatmapSubpops.py <dist_file> <dir> [--species S]
+      (src/subpopr/inst/rmd/detailedSpeciesReport.rmd:142, :222, :250, :402: the row order of the distance heatmaps, hclust + reorder.dendrogram)
+      <species>.filtered.mann.dist (+ <dir>/<species>_mann_distMatrixUsedForClustMedoidDefns.txt, _clustering.tab)  ->  our own files
+      <dir>/<species>_mann_{hclust,heatmap}_{all,discovery}.tab
+
   clusterMembStability.py <species> <dir> [--k N] [--ps-cut X] [--seed N] [--boot N]
       (src/subpopr/R/clusteringStability.R getClusMembStability and getClusMembStabScore; <dir> = clusterSubpops.py's outDir or its noClustering/)
       <dir>/<species>_mann_distMatrixUsedForClustMedoidDefns.txt (+ _PS_values.tab, _clusNumStability.tab)  ->  <dir>/<species>_mann_{clusMembStability.tab,
@@ -46,10 +51,10 @@
 
 getGenotypingSNVSubset.py and writeSubpopAbund.py are text filters (native, no device work) and summariseClustering.py reads and writes small
 tables in Python; the frequencies of convertSNVtoAlleleFreq.py, the correlations, every PAM run of clusterSubpops.py and clusterMembStability.py
-with the matching of the re-clustered subsets, pcoaSubpops.py's centring and eigendecomposition, writeGenotypeFreqs.py's walk over the frequency
-table and profileSubpops.py's counts and medians per sample are computed on the GPU (msnv_snv_allele_freq, msnv_gene_corr, msnv_corr_stats,
-msnv_pam_tasks, msnv_pred_strength, msnv_cluster_boot, msnv_pcoa, msnv_genotype_rows, msnv_subpop_profile_columns) and there is no CPU fallback
-for them."""
+with the matching of the re-clustered subsets, pcoaSubpops.py's centring and eigendecomposition, heatmapSubpops.py's agglomerations,
+writeGenotypeFreqs.py's walk over the frequency table and profileSubpops.py's counts and medians per sample are computed on the GPU
+(msnv_snv_allele_freq, msnv_gene_corr, msnv_corr_stats, msnv_pam_tasks, msnv_pred_strength, msnv_cluster_boot, msnv_pcoa, msnv_hclust_tasks,
+msnv_genotype_rows, msnv_subpop_profile_columns) and there is no CPU fallback for them."""
 import ctypes as C
 import glob
 import os
@@ -373,6 +378,88 @@ def pcoa_subpops_main(argv=None):                              # clustering.R:12
     else:
         print("Species " + species + ": " + str(res["n_samples"]) + " samples ordinated, " + str(res["k"]) + " axes with a positive eigenvalue, "
               + str(res["n_negative"]) + " negative; " + str(res["sweeps"]) + " Jacobi sweeps")
+    return res
+
+
+def hclust_tasks(ctx, dist, tasks):
+    """hclust of many index lists of dist [n x n], one workgroup per task (msnv_hclust_tasks).  tasks: (indices, method) pairs, method one of
+    _lib.HCLUST_*.  Returns one dict per task: merge (int32 [m - 1, 2], R's hc$merge), height (float64 [m - 1]), order (0-based positions in the
+    task's list, R's hc$order - 1); and the kernel's ms."""
+    import numpy as np
+    from ._lib import lib, check
+    dist = np.ascontiguousarray(dist, dtype=np.float64)
+    if dist.ndim != 2 or dist.shape[0] != dist.shape[1]:
+        raise ValueError("hclust_tasks: dist must be a square matrix")
+    lists = [np.asarray(ix, dtype=np.int32).ravel() for ix, _ in tasks]
+    m = np.array([len(x) for x in lists] + [0], dtype=np.int32)
+    method = np.array([mt for _, mt in tasks] + [0], dtype=np.int32)
+    idx = np.ascontiguousarray(np.concatenate(lists + [np.zeros(1, dtype=np.int32)]), dtype=np.int32)
+    merge = np.zeros(2 * idx.size, dtype=np.int32)
+    height = np.zeros(idx.size)
+    order = np.zeros(idx.size, dtype=np.int32)
+    ms = C.c_double()
+    check(lib.msnv_hclust_tasks(ctx._h, dist.shape[0], _dptr(dist), len(tasks), _iptr(m), _iptr(method), _iptr(idx), _iptr(merge), _dptr(height), _iptr(order), C.byref(ms)))
+    out, o = [], 0
+    for t in range(len(tasks)):
+        mt = int(m[t])
+        out.append({"merge": merge[2 * (o - t):2 * (o - t + mt - 1)].reshape(mt - 1, 2).copy(), "height": height[o - t:o - t + mt - 1].copy(), "order": order[o:o + mt].copy()})
+        o += mt
+    return out, ms.value
+
+
+def heatmap_order(merge, weights):
+    """reorder(as.dendrogram(hc), weights), then order.dendrogram (msnv_heatmap_order; host only): the leaves left to right, 0-based, after the
+    two children of every node are put in ascending order of their summed weights.  merge: hc$merge [m - 1, 2]."""
+    import numpy as np
+    from ._lib import lib, check
+    merge = np.ascontiguousarray(merge, dtype=np.int32)
+    weights = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+    m = weights.size
+    if merge.size != 2 * max(m - 1, 0):
+        raise ValueError("heatmap_order: merge must hold 2 (m - 1) entries for m weights")
+    order = np.zeros(max(m, 1), dtype=np.int32)
+    check(lib.msnv_heatmap_order(m, _iptr(merge), _dptr(weights), _iptr(order)))
+    return order[:m]
+
+
+def heatmap_file(ctx, dist_path, directory, species=None):
+    """The stage on files (msnv_heatmap_file): writes <species>_mann_hclust_all.tab and _heatmap_all.tab and, when the directory holds a discovery
+    subset of two samples or more, _hclust_discovery.tab and _heatmap_discovery.tab into directory.  Returns a dict: status (_lib.HEATMAP_*),
+    n_samples, n_discovery, have_clustering, ms_kernel."""
+    from ._lib import lib, check
+    if species is None:
+        species = os.path.basename(dist_path).split(".")[0]
+    res = (C.c_int64 * 8)()
+    ms = C.c_double()
+    check(lib.msnv_heatmap_file(ctx._h, dist_path.encode(), directory.encode(), species.encode(), res, C.byref(ms)))
+    return {"status": res[0], "n_samples": res[1], "n_discovery": res[2], "have_clustering": bool(res[3]), "ms_kernel": ms.value}
+
+
+def heatmap_subpops_main(argv=None):                           # detailedSpeciesReport.rmd:142, :222, :250, :402
+    import argparse
+    ap = argparse.ArgumentParser(prog="heatmapSubpops.py", description="Order a species' samples for the report's distance heatmaps (hclust and the dendrogram reorder) on the GPU.")
+    ap.add_argument("dist_file", metavar="DIST_FILE", help="<species>.filtered.mann.dist of metaSNV_DistDiv.py --dist")
+    ap.add_argument("dir", metavar="DIR", help="holds the species' files of clusterSubpops.py: its output directory, or the noClustering/ or clustMedoidDefnFailed/ below it")
+    ap.add_argument("--species", default=None, metavar="S", help="default: the dist file's name up to its first '.'")
+    a = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    species = a.species if a.species is not None else os.path.basename(a.dist_file).split(".")[0]
+    if not os.path.exists(a.dist_file):
+        sys.exit("ERROR: missing input file: " + a.dist_file)
+    if not os.path.isdir(a.dir):
+        sys.exit("ERROR: missing directory: " + a.dir)
+    from . import core
+    try:
+        ctx = core.Context(0)
+    except core._lib.MsnvError as e:
+        sys.exit("\nERROR:  {}\n\nSOLUTION: run on a node with an AMD Instinct GPU (there is no CPU fallback)\n".format(e))
+    try:
+        res = heatmap_file(ctx, a.dist_file, a.dir, species=species)
+    except core._lib.MsnvError as e:
+        sys.exit("ERROR: {}".format(e))
+    finally:
+        ctx.close()
+    print("Species " + species + ": " + str(res["n_samples"]) + " samples ordered (average linkage)"
+          + ("; no discovery subset" if res["status"] == core._lib.HEATMAP_NO_DISCOVERY else "; " + str(res["n_discovery"]) + " of the discovery subset (complete linkage)"))
     return res
 
 
