@@ -184,7 +184,8 @@ int msnv_filter_resident(struct msnv_dataset *ds, int32_t which, const msnv_filt
  * numpy's pairwise summation).  Writes the manhattan (mean |f1 - f2|) and the allele (share of positions with
  * |f1 - f2| > threshold, 0.6 in the reference) matrices as DataFrame.to_csv(sep='\t') does.  Out pointers may be NULL. */
 /* The value pandas' default CSV float converter (precise_xstrtod) gives `text` -- what computeDist sees after
- * pd.read_table; not always the correctly rounded one.  Returns 0, or MSNV_EFORMAT when text is not a plain number. */
+ * pd.read_table; not always the correctly rounded one.  Returns 0, or MSNV_EFORMAT when text is not a plain number or
+ * overflows a double (beyond 1e308, where pandas leaves the column as text). */
 int msnv_parse_float(const char *text, double *value);
 
 int msnv_dist_file(msnv_ctx *ctx, const char *freq_path, const char *mann_path, const char *allele_path, double threshold,
@@ -203,7 +204,9 @@ int msnv_dist_file(msnv_ctx *ctx, const char *freq_path, const char *mann_path, 
  *   row_order:        the permutation sort_index applies to the rows' contig:gene:pos keys (numpy's argsort of them,
  *                     quicksort for MSNV_DIV, stable for MSNV_DIV_NS; identity when already sorted); must sort the keys
  * Writes the lower-triangular matrices as DataFrame.to_csv(sep='\t') does.  Out pointers may be NULL; ms_kernel is the
- * kernels' time summed over the tables. */
+ * kernels' time summed over the tables.  A position key with more than 55 rows (after the class split and the matched
+ * filter) is MSNV_EDOMAIN before any launch, with ms_kernel 0 and neither file written: its m(m-1)+1 values per sample
+ * make an outer product one lane would sum for more than a second per pair. */
 #define MSNV_DIV    0
 #define MSNV_DIV_NS 1
 int msnv_div_file(msnv_ctx *ctx, const char *freq_path, int32_t mode, int32_t matched, int64_t genome_length,

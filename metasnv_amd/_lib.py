@@ -21,6 +21,8 @@ class MsnvError(RuntimeError):
 
 OK, EINVAL, EIO, EFORMAT, ENODEV, EHIP, ENOMEM, EDOMAIN, ECAPACITY = range(9)
 DIV, DIV_NS = 0, 1                                             # msnv_div_file modes (include/msnv.h)
+DIV_MAX_ALLELES_DEVICE = 55                                    # csrc/device.h: rows under one position key that one lane sums within a second per pair
+DIV_MAX_ALLELES = min(108, DIV_MAX_ALLELES_DEVICE)             # ... and that the reference's np.outer holds in 1 GiB; more is MSNV_EDOMAIN
 CORR_PEARSON, CORR_SPEARMAN = 0, 1                             # msnv_corr_stats methods
 CLUSTER_OK, CLUSTER_NONE, CLUSTER_MEDOID_FAILED, CLUSTER_TOO_FEW, CLUSTER_ALL_EQUAL = range(5)   # msnv_cluster_file result[0]
 MEMBSTAB_OK, MEMBSTAB_NOT_RATED = range(2)                      # msnv_membership_stability_file result[0]

@@ -252,6 +252,11 @@ int  div_file(msnv_ctx *ctx, const char *freq_path, int32_t mode, int32_t matche
               int32_t n_cov, const int64_t *row_order, uint64_t n_order, const char *out_a, const char *out_b, int32_t *n_samples_out,
               uint64_t *n_rows_out, double *ms_kernel);
 int dev_dist(const double *xt_host, int n_samples, long n_pos, double threshold, void *stream, double *mann, double *allele, double *ms_kernel);
+// div.cpp + div_k.hip: the rows one position key may hold (m alleles -> k = m(m-1)+1 values per column, k^2 products summed by ONE lane per pair).
+// The smaller of (a) what the reference still computes: np.outer allocates 8 k^2 bytes, within 1 GiB up to m = 108 (k = 11 557), MemoryError not far
+// beyond; (b) what one lane sums in a second per pair at the measured rate (MEASURED.md "--div / --divNS").  A larger group is refused on the host.
+constexpr uint32_t DIV_MAX_ALLELES_REFERENCE = 108, DIV_MAX_ALLELES_DEVICE = 55;
+constexpr uint32_t DIV_MAX_ALLELES = DIV_MAX_ALLELES_REFERENCE < DIV_MAX_ALLELES_DEVICE ? DIV_MAX_ALLELES_REFERENCE : DIV_MAX_ALLELES_DEVICE;
 int dev_div(const double *xs, const uint64_t *bits, long n_single, long n_words, const double *xg, const long *goff, long n_groups, long n_grouped,
             int n_samples, void *stream, double *out, double *ms_kernel);
 int dev_allele_freq(const std::vector<uint32_t> &cov, const std::vector<uint32_t> &cnt, const std::vector<uint32_t> &row_line,

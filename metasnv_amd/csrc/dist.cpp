@@ -4,6 +4,8 @@
 // (header = tab + sample names, floats as repr(), NaN as the empty string).  The reader and the matrix writer serve
 // --div / --divNS too (div.cpp).
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 
 #include "dataset.h"
@@ -17,10 +19,17 @@ namespace msnv {
 // before the decimal point counts), the rest is dropped, and the result is scaled by ONE multiplication or division
 // with a power of ten.  It is not correctly rounded -- about every tenth 17-digit repr() lands one ulp off -- and the
 // reference's distances carry those errors, so they are reproduced here instead of calling strtod.
-static const double k_pow10[] = {
-    1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22, 1e23, 1e24,
-    1e25, 1e26, 1e27, 1e28, 1e29, 1e30, 1e31, 1e32, 1e33, 1e34, 1e35, 1e36, 1e37, 1e38, 1e39, 1e40, 1e41, 1e42, 1e43, 1e44, 1e45, 1e46, 1e47, 1e48,
-    1e49, 1e50, 1e51, 1e52, 1e53, 1e54, 1e55, 1e56, 1e57, 1e58, 1e59, 1e60, 1e61, 1e62, 1e63, 1e64};
+// The powers of ten are pandas' table of literals 1e0 .. 1e308, i.e. the correctly rounded doubles strtod gives.
+static const double *pow10_table() {
+    static double t[309];
+    static const bool filled = [] {
+        char lit[8];
+        for (int k = 0; k <= 308; ++k) { snprintf(lit, sizeof lit, "1e%d", k); t[k] = strtod(lit, nullptr); }
+        return true;
+    }();
+    (void)filled;
+    return t;
+}
 bool pandas_strtod(const char *s, const char *end, double &out) {
     const char *p = s;
     bool neg = false;
@@ -50,8 +59,14 @@ bool pandas_strtod(const char *s, const char *end, double &out) {
         exponent += eneg ? -n : n;
     }
     if (p != end) return false;
-    if (exponent > 64 || exponent < -64) return false;       // far outside anything a frequency table holds
-    if (exponent > 0) number *= k_pow10[exponent]; else number /= k_pow10[-exponent];
+    const double *e = pow10_table();
+    if (exponent > 308) return false;                         // pandas: ERANGE, the column is no longer numeric and the reference fails on it
+    if (exponent > 0) number *= e[exponent];
+    else if (exponent < -308) {                               // subnormal: two divisions
+        if (exponent < -616) number = 0.0;
+        else { number /= e[-308 - exponent]; number /= e[308]; }
+    } else number /= e[-exponent];
+    if (number - number != 0) return false;                   // overflowed to infinity: ERANGE as above
     out = number;
     return true;
 }

@@ -25,9 +25,17 @@ bool drop_key(const std::vector<double> &rows, size_t S, const std::vector<uint6
     return (double)nans > (double)len * 0.1;
 }
 
-// compute_diversity for every pair (i <= j) of one table, given its rows in order (indices into `rows`)
-int diversity_pairs(msnv_ctx *ctx, const std::vector<double> &rows, size_t S, const std::vector<std::string> &keys,
-                    std::vector<uint64_t> sel, bool matched, std::vector<double> &cd, double *ms_kernel) {
+// One table's rows ready for the pair kernel: the single rows and the multi-allelic groups as sample-major columns (div_k.hip)
+struct PairTable {
+    std::vector<double> xs, xg;
+    std::vector<uint64_t> bits;                                 // bit r % 64 of word r / 64: single row r present
+    std::vector<long> goff{0};
+    long ns = 0, nw = 0, ng = 0;
+};
+
+// The host half of compute_diversity for one table, given its rows in order (indices into `rows`): the --matched filter, the split into
+// single rows and groups, the refusal of a group no launch should be given.  Nothing here touches the device.
+int pair_table(const std::vector<double> &rows, size_t S, const std::vector<std::string> &keys, std::vector<uint64_t> sel, bool matched, PairTable &t) {
     if (matched) {
         std::vector<uint64_t> kept;
         for (size_t lo = 0; lo < sel.size();) {
@@ -38,34 +46,42 @@ int diversity_pairs(msnv_ctx *ctx, const std::vector<double> &rows, size_t S, co
         }
         sel.swap(kept);
     }
-    std::vector<uint64_t> single;
-    std::vector<long> goff{0};
-    std::vector<uint64_t> grouped;
+    std::vector<uint64_t> single, grouped;
     for (size_t lo = 0; lo < sel.size();) {
         size_t hi = lo + 1;
         while (hi < sel.size() && keys[sel[hi]] == keys[sel[lo]]) ++hi;
         if (hi - lo == 1) single.push_back(sel[lo]);
         else {
-            if (hi - lo > 46340) return fail(MSNV_EDOMAIN, "a position with %zu alleles: outside what the reference computes", hi - lo);
+            if (hi - lo > DIV_MAX_ALLELES) {
+                const double k = (double)(hi - lo) * (double)(hi - lo - 1) + 1;
+                return fail(MSNV_EDOMAIN, "position %s has %zu rows, at most %u are computed: the reference's np.outer of the %.0f values per sample allocates "
+                                          "%.1f GiB there (MemoryError where it cannot)", keys[sel[lo]].c_str(), hi - lo, DIV_MAX_ALLELES, k, 8.0 * k * k / 1073741824.0);
+            }
             grouped.insert(grouped.end(), sel.begin() + lo, sel.begin() + hi);
-            goff.push_back((long)grouped.size());
+            t.goff.push_back((long)grouped.size());
         }
         lo = hi;
     }
-    const long ns = (long)single.size(), nw = (ns + 63) / 64, ng = (long)grouped.size(), G = (long)goff.size() - 1;
-    std::vector<double> xs(S * ns), xg(S * ng);                // sample-major columns
-    std::vector<uint64_t> bits(S * nw, 0);                      // bit r % 64 of word r / 64: row r present
+    const long ns = t.ns = (long)single.size(), nw = t.nw = (ns + 63) / 64, ng = t.ng = (long)grouped.size();
+    t.xs.resize(S * ns);                                        // sample-major columns
+    t.xg.resize(S * ng);
+    t.bits.assign(S * nw, 0);
     for (long r = 0; r < ns; ++r)
         for (size_t s = 0; s < S; ++s) {
             const double v = rows[single[r] * S + s];
-            xs[s * ns + r] = v;
-            if (v == v) bits[s * nw + r / 64] |= 1ull << (r % 64);
+            t.xs[s * ns + r] = v;
+            if (v == v) t.bits[s * nw + r / 64] |= 1ull << (r % 64);
         }
     for (long r = 0; r < ng; ++r)
-        for (size_t s = 0; s < S; ++s) xg[s * ng + r] = rows[grouped[r] * S + s];
+        for (size_t s = 0; s < S; ++s) t.xg[s * ng + r] = rows[grouped[r] * S + s];
+    return MSNV_OK;
+}
+
+// compute_diversity for every pair (i <= j) of one prepared table
+int diversity_pairs(msnv_ctx *ctx, const PairTable &t, size_t S, std::vector<double> &cd, double *ms_kernel) {
     cd.assign(S * S, std::nan(""));
     if (!S) return MSNV_OK;
-    return dev_div(xs.data(), bits.data(), ns, nw, xg.data(), goff.data(), G, ng, (int)S, ctx->stream, cd.data(), ms_kernel);
+    return dev_div(t.xs.data(), t.bits.data(), t.ns, t.nw, t.xg.data(), t.goff.data(), (long)t.goff.size() - 1, t.ng, (int)S, ctx->stream, cd.data(), ms_kernel);
 }
 
 }  // namespace
@@ -120,7 +136,9 @@ int div_file(msnv_ctx *ctx, const char *freq_path, int32_t mode, int32_t matched
     };
     std::vector<double> cd;
     if (mode == 0) {
-        if (int rc = diversity_pairs(ctx, rows, S, keys, order, matched != 0, cd, ms_kernel)) return rc;
+        PairTable t;
+        if (int rc = pair_table(rows, S, keys, order, matched != 0, t)) return rc;
+        if (int rc = diversity_pairs(ctx, t, S, cd, ms_kernel)) return rc;
         const std::vector<double> d = divide(cd);
         std::vector<double> fst(S * S, std::nan(""));
         for (size_t j = 0; j < S; ++j)
@@ -136,8 +154,11 @@ int div_file(msnv_ctx *ctx, const char *freq_path, int32_t mode, int32_t matched
         if (sel[0].empty() || sel[1].empty())                   // metaSNV_DistDiv.py:252-260
             return fail(MSNV_EDOMAIN, "%s: no %s SNV in the table: synonymous and non-synonymous diversity need both types (was the SNV calling "
                                       "given gene annotation?)", freq_path, sel[0].empty() ? "non-synonymous (N)" : "synonymous (S)");
+        PairTable t[2];                                         // both classes are prepared before either is launched: a refusal leaves no file
+        for (int c = 0; c < 2; ++c)
+            if (int rc = pair_table(rows, S, keys, sel[c], matched != 0, t[c])) return rc;
         for (int c = 0; c < 2; ++c) {
-            if (int rc = diversity_pairs(ctx, rows, S, keys, sel[c], matched != 0, cd, ms_kernel)) return rc;
+            if (int rc = diversity_pairs(ctx, t[c], S, cd, ms_kernel)) return rc;
             if (int rc = write_matrix(c == 0 ? out_a : out_b, names, divide(cd))) return rc;
         }
     }

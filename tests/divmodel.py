@@ -1,7 +1,12 @@
 """Test-side model of metaSNV_DistDiv.py --div / --divNS / --matched (the semantics restated with numpy / pandas
 primitives, one sample pair at a time).  tests/test_diversity_model.py pins it against the files the reference script
 wrote (tests/golden/python_callers/diversity); tests/test_gpu_diversity.py compares the device against it on random
-tables.  Slow on purpose: every sum is numpy's own."""
+tables.  Slow on purpose: every sum is numpy's own.
+
+`plan` (Table.diversity, species_outputs) replaces numpy's sum of the single rows' products and of the group values by a
+restated one -- distmodel.blocked_sum (numpy's tree), distmodel.flat_sum (one tree over the whole array) or sequential_sum
+below -- so that tests/test_diversity_model.py can require inputs on which a wrong tree prints a different cell.  The sums
+inside a group (np.outer, np.nansum) stay numpy's.  `group_sum` replaces the Kahan restatement by pandas' own groupby."""
 import math
 import os
 
@@ -64,10 +69,26 @@ def kahan(xs):
     return s
 
 
+def pandas_group_sum(xs):
+    """The same sum by pandas itself: one group through groupby().sum()."""
+    import pandas as pd
+    xs = np.asarray(xs, dtype=np.float64)
+    return float(pd.DataFrame({'k': ['p'] * len(xs), 'x': xs}).groupby('k').sum()['x'].iloc[0])
+
+
+def sequential_sum(a):
+    """A plain loop over every column of a [n x m], first element first (what a kernel without numpy's tree would do)."""
+    return 0.0 + (np.cumsum(np.ascontiguousarray(a.T), axis=1)[:, -1] if a.shape[0] else np.zeros(a.shape[1]))
+
+
+def _sum(x, plan):
+    return x.sum() if plan is None else plan(np.ascontiguousarray(x)[:, None])[0]
+
+
 class Table:
     """One table's rows (in order) split into single rows and groups, with each group's k-vector per sample."""
 
-    def __init__(self, rows, keys, values):
+    def __init__(self, rows, keys, values, group_sum=kahan):
         self.S = values.shape[1]
         single, groups, k = [], [], 0
         while k < len(rows):
@@ -81,14 +102,15 @@ class Table:
         for g in groups:
             m = len(g)
             rep = np.tile(values[g], (m - 1, 1))                # the m rows repeated m - 1 times
-            ref = np.array([1. - kahan(rep[:, s]) for s in range(self.S)])
+            ref = np.array([1. - group_sum(rep[:, s]) for s in range(self.S)])
             self.vec.append(np.vstack([rep, ref[None, :]]).T.copy())
 
-    def diversity(self, i, j):
+    def diversity(self, i, j, plan=None):
+        plan_s, plan_g = plan if isinstance(plan, tuple) else (plan, plan)  # (single rows, group values)
         a, b = self.xs[:, i], self.xs[:, j]
         ok = ~(np.isnan(a) | np.isnan(b))
         a, b = a[ok], b[ok]
-        nd = (a * (1 - b) + (1 - a) * b).sum()
+        nd = _sum(a * (1 - b) + (1 - a) * b, plan_s)
         if not self.vec:
             return nd
         vals = np.empty(len(self.vec))
@@ -96,7 +118,7 @@ class Table:
             out = np.outer(v[i], v[j])
             vals[g] = np.nansum(out) - np.nansum(out.diagonal())
         vals[np.isnan(vals)] = 0.0
-        return vals.sum() + nd
+        return _sum(vals, plan_g) + nd
 
 
 def _matrix_text(names, rows):
@@ -107,7 +129,7 @@ def _matrix_text(names, rows):
     return buf.getvalue()
 
 
-def species_outputs(freq_path, mode, matched, h, v, L):
+def species_outputs(freq_path, mode, matched, h, v, L, plan=None, group_sum=kahan):
     """{file name: text} of one species table; h / v: {sample: Percentage_1x / Average_cov}, L: genome length (int)."""
     names, labels, values = read_freq(freq_path)
     species = os.path.basename(freq_path).split('.')[0]
@@ -124,8 +146,8 @@ def species_outputs(freq_path, mode, matched, h, v, L):
         def div_of(rows):
             if matched:
                 rows = matched_filter(rows, keys, values)
-            t = Table(rows, keys, values)
-            return [[t.diversity(i, j) / corr[j][i] for i in range(j + 1)] + [math.nan] * (S - j - 1) for j in range(S)]
+            t = Table(rows, keys, values, group_sum)
+            return [[t.diversity(i, j, plan) / corr[j][i] for i in range(j + 1)] + [math.nan] * (S - j - 1) for j in range(S)]
 
         if mode == 'div':
             d = div_of(sorted_rows(labels, 'div'))

@@ -1,6 +1,8 @@
 """metaSNV_DistDiv.py --div / --divNS / --matched on the device (msnv_div_file through metasnv_amd.distdiv): byte-identical
 with the files the reference script wrote (tests/golden/python_callers/diversity), and with the test-side model
-(tests/divmodel.py, itself pinned against those files by tests/test_diversity_model.py) on random tables."""
+(tests/divmodel.py, itself pinned against those files by tests/test_diversity_model.py) on random tables.  In these tables a
+pair's count of valid rows is whatever the seed gave; the counts at which the kernel's loops change shape are prescribed in
+tests/divcases.py and run by tests/test_gpu_div_sizes.py."""
 import json
 import os
 import random

@@ -108,3 +108,24 @@ def test_float_parse_matches_pandas_default_converter():
         off += v.value != float(tok)
     assert off > 100                                # the converter really is inexact: this is not strtod
     assert lib.msnv_parse_float(b"abc", C.byref(v)) != 0 and lib.msnv_parse_float(b"1.5x", C.byref(v)) != 0
+
+
+def test_float_parser_reads_the_exponents_pandas_reads():
+    """Up to 1e308 and down into the subnormals, as precise_xstrtod scales them (one multiplication, one or two divisions); a
+    value that overflows is refused (pandas leaves such a column as text and the reference fails on it)."""
+    import ctypes as C
+    import io
+    import random
+    pd = pytest.importorskip("pandas")
+    from metasnv_amd._lib import lib
+    rnd = random.Random(9)
+    toks = ["1e308", "1e65", "1e-65", "1.7976931348623157e308", "12345678901234567890e280", "0.000001e314", "1e-320", "3e-310", "1e-700", "-1e308"]
+    toks += ["%se%d" % (repr(rnd.random() * 10)[:rnd.randint(3, 19)], rnd.randint(-330, 306)) for _ in range(3000)]
+    want = pd.read_csv(io.StringIO("x\n" + "\n".join(toks) + "\n"), dtype=float)["x"].values
+    v = C.c_double()
+    for tok, w in zip(toks, want):
+        assert lib.msnv_parse_float(tok.encode(), C.byref(v)) == 0, tok
+        assert v.value == w, (tok, repr(v.value), repr(w))
+    for tok in ("1e309", "1.8e308", "-1.8e308", "1e100000"):
+        assert pd.read_csv(io.StringIO("x\n" + tok + "\n0.5\n"))["x"].dtype == object
+        assert lib.msnv_parse_float(tok.encode(), C.byref(v)) != 0, tok
