@@ -646,7 +646,7 @@ int  msnv_dataset_add_sample_records(msnv_dataset *ds, const uint8_t *records, u
 int  msnv_dataset_add_sample_records_many(msnv_dataset *ds, const uint8_t *const *records, const uint64_t *n_bytes, int32_t n, int32_t host_threads);
 /* The same for record streams that already lie in the HBM of the dataset's device -- what an all-to-all over RCCL has just received
  * (metasnv_amd/parallel.py: exchange_records), what the device inflate has written: the records never visit a host core.  The per-read
- * stage of both reference tools runs as kernels over them (csrc/devpack.hip): record boundaries, the read loop and CIGAR walk of
+ * stage of both reference tools runs as kernels over them (csrc/devscan.hip, csrc/devpack.hip): record boundaries, the read loop and CIGAR walk of
  * qaCompute (qaCompute.cpp:441-593) and, for `samtools mpileup` (metaSNV.py:160-165), its read filters, the CIGAR walk to aligned
  * segments and the -Q test of every base.  The streams are copied; the caller may release them when the call returns.
  * Every add_sample_* entry point takes this route when the dataset has a device context (MSNV_PACK=host keeps the stage on the
@@ -858,7 +858,7 @@ typedef struct { uint32_t total_reads, unmapped, zero_quality, proper_pairs, dup
  * part_bytes[n_parts] their sizes; stats (may be NULL) the sample's qaCompute statistics over ALL records. */
 int  msnv_records_partition(const uint8_t *records, uint64_t n_bytes, const int32_t *contig_owner, int32_t n_contigs,
                             int32_t n_parts, int32_t cov_min_mapq, uint8_t *out, uint64_t *part_bytes, msnv_sample_stats *stats);
-/* msnv_records_partition for n streams at once, ON THE DEVICE (csrc/devpack.hip): the streams (host memory, or device memory when on_device
+/* msnv_records_partition for n streams at once, ON THE DEVICE (csrc/devdeal.hip): the streams (host memory, or device memory when on_device
  * != 0) are dealt by kernels into `out` -- DEVICE memory of `capacity` bytes, e.g. the send tensor of an all-to-all over RCCL -- destination-
  * major: part 0 of stream 0, of stream 1, ..., part 1 of stream 0, ..., with `gap` bytes left free in front of every part (the caller's size
  * table; capacity >= sum of n_bytes + n_parts * gap).  part_bytes[i * n_parts + k] = bytes of stream i in part k; stats[i] = stream i's

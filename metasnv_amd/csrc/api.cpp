@@ -34,7 +34,7 @@ extern "C" int msnv_ctx_create(int device_id, msnv_ctx **out) {
     msnv_ctx *c = new msnv_ctx();
     c->device = device_id;
     if (int rc = dev_stream_create(&c->stream)) { delete c; return rc; }
-    warm_devpack(c->stream); warm_devfin(c->stream); warm_kernels(c->stream); warm_textcall(c->stream); warm_annotate(c->stream); warm_mptext(c->stream);      // (code objects loaded now, not inside the first stage that needs them)
+    warm_devpack(c->stream); warm_devscan(c->stream); warm_devdeal(c->stream); warm_devfin(c->stream); warm_kernels(c->stream); warm_textcall(c->stream); warm_annotate(c->stream); warm_mptext(c->stream);      // (code objects loaded now, not inside the first stage that needs them)
     *out = c;
     return MSNV_OK;
 }

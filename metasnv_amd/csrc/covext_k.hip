@@ -88,7 +88,7 @@ __global__ __launch_bounds__(CX_NT) void msnv_coverage_extras(const CovxArgs a) 
     }
     for (uint32_t k = w.pair_lo; k < w.pair_hi && k < a.n_pairs; ++k) {
         const TilePair pr = a.pairs[k];
-        const uint32_t row = pr.max_depth;                   // accumulator row of the pair's (sample, contig) (pack.cpp)
+        const uint32_t row = pr.max_depth;                   // accumulator row of the pair's (sample, contig) (finalize.cpp)
         if (row < a.row_lo || row >= a.row_hi) continue;     // (the same for every thread)
         reinterpret_cast<int4 *>(s_diff)[2 * tid] = make_int4(0, 0, 0, 0);
         reinterpret_cast<int4 *>(s_diff)[2 * tid + 1] = make_int4(0, 0, 0, 0);

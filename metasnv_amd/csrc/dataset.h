@@ -162,10 +162,8 @@ struct DevPackTables {
         struct CovT { uint32_t *tcont, *rid_t, *rowid, *row_sample, *row_contig, *item_off, *lo, *hi; unsigned long long *iv_start; };
         void *cov_tables = nullptr; CovT cov_t{}; uint32_t cov_item_intervals = 16384;
         bool  cov_tables_done = false;                           // devfin_coverage wrote the pair tables, rows and work items in HBM
-        // ---- the narrow chunks cut without a wait (devfin_chunks_launch -> devfin_chunks_result): room for them in d.chunks, where they start
-        uint64_t chunk_cap = 0; uint32_t chunk_base = 0; bool chunks_async = false;
+        // ---- the narrow chunks cut without a wait (devfin_chunks_launch -> devfin_chunks_result)
         void *chunk_event = nullptr; bool chunk_pending = false; // behind the words the cut's kernels leave in pinned memory
-        void *list = nullptr, *cbase = nullptr;                  // the narrow pairs' list and their chunk counts / scan, between devfin_chunk_counts and devfin_chunk_fill
         // ---- small device tables of finalize's kernels, which are queued, not waited for: freed with the pack's tables (devpack_finish)
         void *tile_base = nullptr;                               // the contigs' first tiles (devfin_headers)
         const void *sample_hdr = nullptr;                        // every sample's headers where its round left them, built at a finalize's first use (one of `keep`)

@@ -29,9 +29,7 @@ int devfin_deep_runs(msnv_dataset &ds, uint32_t split_at, uint32_t group_depth, 
 int devfin_dense(msnv_dataset &ds);
 int devpack_copy_blocks(const SampleCols &sc, uint32_t *dst, void *stream);
 int devfin_headers(msnv_dataset &ds, DeviceCols &d, const std::vector<uint64_t> &rbase);
-int devfin_chunk_counts(msnv_dataset &ds, DeviceCols &d, const std::vector<uint32_t> &narrow_pairs, std::vector<uint32_t> &cbase);   // cbase: first chunk of every listed pair, total behind them
-int devfin_chunk_fill(msnv_dataset &ds, DeviceCols &d, size_t n_pairs_listed, uint32_t base);        // d.chunks[base .. base + total), d.hdr4
-// the same without a wait: item_first[wi] = index of narrow work item wi's first pair in the list (n_work_narrow + 1 entries); the chunks
+// the narrow pairs' chunks (d.chunks, d.hdr4) cut without a wait: item_first[wi] = index of narrow work item wi's first pair in the list (n_work_narrow + 1 entries); the chunks
 // go behind the `base` chunks the host wrote, `cap` of them at most; devfin_chunks_result (behind a wait for the stream) says how many there were
 int devfin_chunks_launch(msnv_dataset &ds, DeviceCols &d, const std::vector<uint32_t> &narrow_pairs, const std::vector<uint32_t> &item_first, uint32_t base, uint64_t cap);
 int devfin_chunks_result(msnv_dataset &ds, uint64_t *n_chunks, bool *overflow);

@@ -27,7 +27,6 @@
 //   devpack_fill_padding     columns            msnv_fill_padding, when the emit kernels did not leave the padding nibbles
 //   devfin_chunks_result     last_wait          the cut's two pinned words, behind its event
 //   devpack_finish           last_wait          the last waits; the pack's buffers and finalize's own (devfin_release) go back
-// devfin_chunk_counts / devfin_chunk_fill are the cut with one wait between counts and fill; no stage calls them today.
 // State between the calls: DevPackTables::Fin (dataset.h); the small results come to the host through FinWords (devfin.h).
 // Buffers are carved from one block each by Carve / carve_block; what both device files share is devwork.h.
 #include <algorithm>
@@ -415,7 +414,6 @@ int devfin_chunks_launch(msnv_dataset &ds, DeviceCols &d, const std::vector<uint
     hipStream_t st = (hipStream_t)ds.ctx->stream;
     DevPackTables::Fin &F = ds.dp.fin;
     const size_t n = narrow_pairs.size(), n_items = item_first.size() - 1;
-    F.chunks_async = true; F.chunk_cap = cap; F.chunk_base = base;
     FinWords pw;
     if (int rc = fin_words_ensure(ds, &pw)) return rc;
     uint32_t *res = pw.chunks();
@@ -461,49 +459,6 @@ int devfin_chunks_result(msnv_dataset &ds, uint64_t *n_chunks, bool *overflow) {
     if (F.chunk_pending) { F.chunk_pending = false; HIP_TRY(hipEventSynchronize((hipEvent_t)F.chunk_event)); }
     const uint32_t *res = fin_words(ds).chunks();
     *n_chunks = res[0]; *overflow = res[1] != 0;
-    return MSNV_OK;
-}
-
-// ... and the form with ONE wait between counts and fill (exact sizes): counts (+ their exclusive scan, on the device) -> the host learns every
-// pair's first chunk and the total, and allocates the descriptors; then the fill, straight into d.chunks and d.hdr4.  The list and the scan
-// stay in HBM between the two calls (DevPackTables::Fin::list / cbase).
-int devfin_chunk_counts(msnv_dataset &ds, DeviceCols &d, const std::vector<uint32_t> &narrow_pairs, std::vector<uint32_t> &cbase) {
-    hipStream_t st = (hipStream_t)ds.ctx->stream;
-    const size_t n = narrow_pairs.size();
-    cbase.assign(n + 1, 0);
-    if (!n) return MSNV_OK;
-    DevPackTables::Fin &F = ds.dp.fin;
-    const ReadHdr *const *s_hdr = nullptr;
-    if (int rc = sample_hdr_table(ds, &s_hdr)) return rc;
-    if (F.list) { F.keep.push_back(F.list); F.list = nullptr; }
-    if (F.cbase) { F.keep.push_back(F.cbase); F.cbase = nullptr; }
-    if (int rc = dev_alloc(&F.list, n * 4, nullptr)) return rc;
-    if (int rc = dev_alloc(&F.cbase, (n + 1) * 8, nullptr)) return rc;      // counts (n + 1 words) and their scan behind them
-    uint32_t *cnt = static_cast<uint32_t *>(F.cbase), *scan = cnt + (n + 1);
-    HIP_TRY(hipMemcpyAsync(F.list, narrow_pairs.data(), n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(cnt + n, 0, 4, st));
-    hipLaunchKernelGGL(msnv_fin_chunks<false>, grid_for(n * 64, 256), dim3(256), 0, st, d.pairs, static_cast<const uint32_t *>(F.list), (uint32_t)n, s_hdr, (const unsigned long long *)d.s_read_base,
-                       (const unsigned long long *)d.s_seq_base, cnt, nullptr, nullptr, nullptr, 0u);
-    HIP_TRY(hipGetLastError());
-    Prim pr(st);
-    if (int rc = pr.scan32(cnt, scan, n + 1, false)) return rc;
-    HIP_TRY(hipMemcpyAsync(cbase.data(), scan, (n + 1) * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return MSNV_OK;
-}
-
-// d.chunks[base .. base + n_narrow) and d.hdr4 (both allocated by the caller) from the kept list and scan
-int devfin_chunk_fill(msnv_dataset &ds, DeviceCols &d, size_t n_pairs_listed, uint32_t base) {
-    hipStream_t st = (hipStream_t)ds.ctx->stream;
-    DevPackTables::Fin &F = ds.dp.fin;
-    if (n_pairs_listed) {
-        const ReadHdr *const *s_hdr = nullptr;
-        if (int rc = sample_hdr_table(ds, &s_hdr)) return rc;
-        const uint32_t *scan = static_cast<const uint32_t *>(F.cbase) + (n_pairs_listed + 1);
-        hipLaunchKernelGGL(msnv_fin_chunks<true>, grid_for(n_pairs_listed * 64, 256), dim3(256), 0, st, d.pairs, static_cast<const uint32_t *>(F.list), (uint32_t)n_pairs_listed, s_hdr,
-                           (const unsigned long long *)d.s_read_base, (const unsigned long long *)d.s_seq_base, nullptr, scan, d.chunks + base, d.hdr4, 0xffffffffu);
-        HIP_TRY(hipGetLastError());
-    }
     return MSNV_OK;
 }
 int devfin_work_first(msnv_dataset &ds, DeviceCols &d, uint32_t n_items, uint64_t n_room) {
@@ -1316,7 +1271,7 @@ void devfin_release(DevPackTables::Fin &f, std::vector<void *> &out) {
     if (f.cov_event) (void)hipEventDestroy((hipEvent_t)f.cov_event);
     if (f.chunk_event) (void)hipEventDestroy((hipEvent_t)f.chunk_event);
     if (f.cov_job || f.cov_tables || !f.keep.empty()) (void)hipDeviceSynchronize();
-    for (void *p : {f.cov_job, f.cov_tables, f.cov_tmp, f.tile_base, f.list, f.cbase}) if (p) out.push_back(p);
+    for (void *p : {f.cov_job, f.cov_tables, f.cov_tmp, f.tile_base}) if (p) out.push_back(p);
     for (void *p : f.keep) if (p) out.push_back(p);
     f = DevPackTables::Fin{};
 }

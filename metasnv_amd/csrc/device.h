@@ -230,7 +230,7 @@ int  ensure_out_for_next_pass(DeviceCols &d);
 int  ensure_alt(DeviceCols &d, void *stream);
 int  dev_reserve_passes(DeviceCols &d, int n);
 // one tiny launch per translation unit with kernels: its code object is loaded when the context is made, not inside the first stage that needs it
-void warm_devpack(void *stream), warm_devfin(void *stream), warm_kernels(void *stream), warm_textcall(void *stream), warm_annotate(void *stream), warm_mptext(void *stream);
+void warm_devpack(void *stream), warm_devscan(void *stream), warm_devdeal(void *stream), warm_devfin(void *stream), warm_kernels(void *stream), warm_textcall(void *stream), warm_annotate(void *stream), warm_mptext(void *stream);
 
 // ---- BGZF blocks inflated on the device (inflate_k.hip; bamfeed.cpp drives it)
 struct InfBlock { unsigned long long in_off, out_off; uint32_t in_size, out_size; };      // offsets into the batch's compressed / inflated bytes

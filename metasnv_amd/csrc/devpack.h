@@ -26,7 +26,7 @@ int devpack_add_round(msnv_dataset &ds, size_t first, const uint8_t *const *stre
 int devpack_sample_to_host(SampleCols &sc);
 int devpack_download_pieces(msnv_dataset &ds);
 void devpack_release(msnv_dataset &ds);                       // the pack's tables, round buffers, work buffers; the pinned block back to the context
-// msnv_records_deal_device (msnv.h): pack.cpp's records_partition for several streams at once, on the device
+// msnv_records_deal_device (msnv.h): pack.cpp's records_partition for several streams at once, on the device (devdeal.hip)
 int records_deal_device(msnv_ctx *ctx, const uint8_t *const *streams, const uint64_t *n_bytes, int n, bool on_device, const int32_t *owner, int n_contigs, int n_parts,
                         int cov_min_mapq, uint8_t *out, uint64_t capacity, uint64_t gap, uint64_t *part_bytes, msnv_sample_stats *stats, uint64_t *contig_bases);
 

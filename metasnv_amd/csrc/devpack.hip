@@ -1,5 +1,5 @@
-// metasnv_amd/csrc/devpack.hip -- the per-read stage as device kernels: raw BAM alignment records in HBM -> packed read columns; and the
-// device dealer (msnv_records_deal_device), which shares the record walk with it.
+// metasnv_amd/csrc/devpack.hip -- the per-read stage as device kernels: raw BAM alignment records in HBM -> packed read columns.  The record
+// scan it starts from is devscan.hip, the device dealer (msnv_records_deal_device) devdeal.hip; what the three share is devrec.h.
 //
 // What it replaces: the read loop of the reference's tools, per record -- flag / MAPQ / duplicate filter and the walk over the CIGAR's M
 // blocks of qaCompute (/root/reference/src/qaTools/qaCompute.cpp:441-593, the walk :530-552), and what `samtools mpileup` (call site
@@ -9,7 +9,7 @@
 // the two produce the same columns byte for byte (tests/test_gpu_devpack.py).
 //
 // Stages of one round of samples (round 6; DESIGN.md section 3 has the table with the kernels' times), the function of each beside it
-// (members of `Round`; devpack_add_round is their driver).  Round::stage (stage_streams) puts the streams in place.  The QUICK route, the
+// (members of `Round`; devpack_add_round is their driver).  Round::stage (devscan.hip: stage_streams) puts the streams in place.  The QUICK route, the
 // default -- Round::front_quick, then launch_emit and collect:
 //   msnv_scan_sub2        one LANE per sub-segment of a few kilobytes of a stream: guesses where the block_size chain enters its bytes, walks the
 //                         records that start there and MEASURES each as it goes (header, CIGAR geometry, the read filters of both tools,
@@ -24,7 +24,7 @@
 //                         (the pieces a read leaves in the next tile are placed by counting); msnv_emit_block_slow takes what it lists
 //                         -- Round::launch_emit, both routes; Round::collect waits for the small results and can hand the round to the careful route
 //   the (sample, tile) pairs (Round::tile_pairs: by counting over the groups, or the rocPRIM sort) and the samples' host fields (Round::publish)
-// The CAREFUL route -- Round::front_careful: scan_records (scan_sub_walk: msnv_scan_sub; scan_segments: msnv_scan_segments), then per pass
+// The CAREFUL route -- Round::front_careful: scan_records (devscan.hip), then per pass
 // measure (msnv_measure_reads), tables_and_depth (msnv_tables_from_measure, msnv_depth2), list_overlaps, sequential_edits (the host pre-pass:
 // host_prepass_samples), a wait between the stages; then Round::edit_qualities (msnv_ovl_groups, msnv_token_*) -- takes the
 // rounds the quick one leaves: paired reads, chains that break, the general tile-order sort -- and the three SEQUENTIAL edits of the host
@@ -33,11 +33,8 @@
 // the cap; two or more reads pass htslib's overlap_push precondition; the upper bound of a base string reaches the limit).  The host
 // pre-pass (pack.cpp: host_prepass) keeps three corner cases (a template with more alignments than the overlap kernel's slots, reads that
 // span more than 16 384 reference positions, an indel of half a million bases) and MSNV_PREPASS=host.
-// The sub-segment walk is written once for both routes and the dealer: sub_of / sub_at, guess_entry, scan_sub_body<Walk> and
-// scan_fix_body<Walk> over WalkPlain (offsets) or WalkMeasure (slots and sums), wave_records for the two write kernels; SubWalk on the host
-// (the walk's buffers, the seam loop).  AccAdd is what a record or a sub-segment adds to its sample's accumulators.
-// The dealer -- records_deal_device: scan_records, then msnv_deal_measure, a sort of the records by owner (msnv_deal_iota, msnv_deal_sizes),
-// msnv_deal_copy -- deals the records of several streams to their contigs' owners (pack.cpp: records_partition on the host).
+// The sub-segment walk is written once for both routes and the dealer (devrec.h); this file's Walk is WalkMeasure (slots and sums).  AccAdd
+// is what a record or a sub-segment adds to its sample's accumulators.
 // Behind the round: devpack_sync_pending, the dataset's pinned block (pin_ensure), devpack_release, and the copies of a device-packed
 // sample to host staging (devpack_download_pieces, devpack_sample_to_host).  Finalize's device side is devfin.hip; what the two files share
 // -- HIP_TRY, DevBuf, BufPool, Prim, the device helpers of a piece's bytes -- is devwork.h, and the two kernels of the round that finalize's
@@ -51,7 +48,7 @@
 #include <vector>
 
 #include "devfin.h"
-#include "devwork.h"
+#include "devrec.h"
 
 namespace msnv {
 
@@ -80,64 +77,6 @@ enum : uint8_t { RF_PILE = 1, RF_COV = 2, RF_MAPPED = 4, RF_OVL = 8 };      // R
 enum : uint32_t { NEED_CAP = 1, NEED_TOKEN = 2, NEED_OVL = 4, NEED_BIGC = 8 };      // NEED_OVL: too many alignments of one template wait at once for the device's slots; NEED_BIGC (with NEED_TOKEN):
                                                                                       // an element longer than the records' tables can say -- both are the host pre-pass's
 
-
-// fixed part of an alignment record (SAM spec 4.2): block_size refID pos l_read_name mapq bin n_cigar_op flag l_seq next_refID next_pos tlen
-struct Rec {
-    int32_t tid, pos, l_seq, mtid, mpos, tlen;
-    uint32_t bs, l_name, n_cigar, flag, mapq;
-    const uint8_t *cigar, *seq, *qual;
-    bool ok;
-};
-__device__ __forceinline__ Rec rec_load(const uint8_t *p, uint64_t avail) {
-    Rec r;
-    uint4 h0, h1; __builtin_memcpy(&h0, p, 16); __builtin_memcpy(&h1, p + 16, 16);      // (two 16-byte loads and a word instead of four 8-byte ones and a word: the walks that call this are bound by the NUMBER of memory requests)
-    r.bs = h0.x; r.tid = (int32_t)h0.y; r.pos = (int32_t)h0.z;
-    const uint32_t w = h0.w;
-    r.l_name = w & 0xffu; r.mapq = (w >> 8) & 0xffu;
-    const uint32_t fn = h1.x;
-    r.n_cigar = fn & 0xffffu; r.flag = fn >> 16; r.l_seq = (int32_t)h1.y;
-    r.mtid = (int32_t)h1.z; r.mpos = (int32_t)h1.w; r.tlen = (int32_t)ld32(p + 32);
-    r.cigar = p + 36 + r.l_name;
-    r.seq = r.cigar + 4ull * r.n_cigar;
-    r.qual = r.seq + ((uint64_t)(uint32_t)r.l_seq + 1) / 2;
-    const uint64_t need = 36ull + r.l_name + 4ull * r.n_cigar + ((uint64_t)(uint32_t)r.l_seq + 1) / 2 + (uint64_t)(uint32_t)r.l_seq;
-    r.ok = avail >= 36 && (int32_t)r.bs >= 32 && (uint64_t)r.bs + 4 <= avail && r.l_seq >= 0 && need <= (uint64_t)r.bs + 4;      // hostio.cpp: rec_parse
-    // a CIGAR that lives in the CG:B,I field behind a placeholder `<l_seq>S<ref_len>N` (more than 65535 operations; sam.c bam_tag2cigar
-    // [EXT]): the walk below is taken by such records only (hostio.cpp: rec_parse states the conditions)
-    if (r.ok && r.n_cigar > 0 && r.tid >= 0 && r.pos >= 0) {
-        const uint32_t c0 = ld32(r.cigar);
-        if ((c0 & 15u) == C_S && (int32_t)(c0 >> 4) == r.l_seq) {
-            const uint8_t *aux = r.qual + (uint32_t)r.l_seq, *end = p + 4ull + r.bs;
-            while (aux + 3 <= end) {
-                const uint8_t t = aux[2], *v = aux + 3;
-                unsigned long long sz;
-                if (t == 'A' || t == 'c' || t == 'C') sz = 1;
-                else if (t == 's' || t == 'S') sz = 2;
-                else if (t == 'i' || t == 'I' || t == 'f') sz = 4;
-                else if (t == 'd') sz = 8;
-                else if (t == 'Z' || t == 'H') { const uint8_t *q = v; while (q < end && *q) ++q; sz = (unsigned long long)(q - v) + 1; }
-                else if (t == 'B') {
-                    if (v + 5 > end) break;
-                    const unsigned long long es = (v[0] == 'c' || v[0] == 'C') ? 1 : (v[0] == 's' || v[0] == 'S') ? 2 : 4, n = ld32(v + 1);
-                    if (aux[0] == 'C' && aux[1] == 'G') {
-                        if ((v[0] == 'I' || v[0] == 'i') && n >= r.n_cigar && n < (1ull << 29) && v + 5 + 4 * n <= end) { r.cigar = v + 5; r.n_cigar = (uint32_t)n; }
-                        break;
-                    }
-                    sz = 5 + es * n;
-                } else break;
-                if (aux[0] == 'C' && aux[1] == 'G') break;
-                if (v + sz > end) break;
-                aux = v + sz;
-            }
-        }
-    }
-    return r;
-}
-__device__ __forceinline__ bool rec_mapped(uint32_t flag, int32_t tid) { return !(flag & 4u) && tid >= 0; }
-
-__device__ __forceinline__ bool cg_ref(uint32_t t) { return t == C_M || t == C_D || t == C_N || t == C_EQ || t == C_X; }
-__device__ __forceinline__ bool cg_query(uint32_t t) { return t == C_M || t == C_I || t == C_S || t == C_EQ || t == C_X; }
-__device__ __forceinline__ bool cg_match(uint32_t t) { return t == C_M || t == C_EQ || t == C_X; }
 
 __global__ __launch_bounds__(64) void msnv_acc_fold(DpAcc *acc, uint32_t n_samples) {       // one wavefront per sample, one lane per copy (ACC_COPIES = 64)
     const uint32_t s = blockIdx.x, c = threadIdx.x;
@@ -205,327 +144,6 @@ __device__ __forceinline__ void acc_add(DpAcc &a, const AccAdd &x) {       // (a
     if (x.err != ~0ull) atomicMin(&a.err, x.err);
     if (x.first_pile != ~0ull) atomicMin(&a.first_pile, x.first_pile);
     if (x.beyond != ~0ull) atomicMin(&a.beyond, x.beyond);
-}
-
-// ------------------------------------------------------------------------------------------ record boundaries
-// The records of a BAM are a chain: the next one starts block_size + 4 bytes behind this one (qaCompute.cpp:441 reads them with sam_read1
-// one at a time).  A stream is cut into segments of MSNV_SCAN_SEG_KB (256 KB); one wavefront per segment stages 16 KB windows of it in LDS
-// (sixteen 16-byte loads per lane in flight, the next window fetched while this one is walked) and walks the chain there.  Where does the
-// chain enter a segment that is not a stream's first?  The wavefront looks for the first offset whose 36 header bytes are those of a
-// plausible record (sizes consistent, contig ids in range) and whose two successors are too -- a GUESS, 64 offsets tested per step --
-// and the host then checks every seam: a segment's walk must end exactly where the next segment's began.  Accepted seams make the
-// concatenated chain the true one by induction from offset 0; a segment that guessed wrong is walked again from the true entry point
-// (never seen on real streams; tests force it).
-constexpr uint32_t SCAN_WIN = 16384;
-struct ScanSeg { unsigned long long beg, end, s_end, start, out_base; };     // [beg, end) of the round buffer, the stream's end, forced entry point or ~0 (search), first slot of tmp_off
-struct ScanOut { unsigned long long first, stop, bad; uint32_t cnt, pad; };  // entry point used (~0: none found), where the walk stopped (first record start >= end), malformed chain at (~0: none)
-
-__device__ __forceinline__ uint32_t lds_u32(const uint32_t *w32, uint32_t o) { return __builtin_amdgcn_alignbyte(w32[(o >> 2) + 1], w32[o >> 2], o & 3u); }
-// plausibility of a record header at absolute offset o (fields from global memory, unaligned)
-__device__ __forceinline__ bool plausible_at(const uint8_t *raw, unsigned long long o, unsigned long long s_end, int n_contigs, uint32_t &bs_out) {
-    if (s_end - o < 36) return false;
-    const Rec r = rec_load(raw + o, s_end - o);
-    bs_out = r.bs;
-    return r.ok && r.tid >= -1 && r.tid < n_contigs && r.pos >= -1 && r.l_name >= 1 && r.mtid >= -1 && r.mtid < n_contigs && r.mpos >= -1 && r.bs < (1u << 28);
-}
-
-__global__ __launch_bounds__(64) void msnv_scan_segments(const uint8_t *raw, const ScanSeg *segs, uint32_t n_segs, int n_contigs, unsigned long long *tmp_off, ScanOut *outs) {
-    __shared__ uint4 win[SCAN_WIN / 16 + 1];
-    __shared__ unsigned long long obuf[64];
-    const uint32_t sg = blockIdx.x, lane = threadIdx.x;
-    if (sg >= n_segs) return;
-    const ScanSeg S = segs[sg];
-    const uint32_t *w32 = reinterpret_cast<const uint32_t *>(win);
-    unsigned long long wlo = 0, whi = 0;                         // window = [wlo, whi) of the round buffer, wlo on 16 bytes
-    unsigned long long plo = ~0ull, phi = 0;                     // the prefetched window (in registers)
-    uint4 pre[16];
-    auto fetch = [&](unsigned long long lo, unsigned long long &hi_out) {   // 16 KB from lo (on 16 bytes) into registers, clipped to the stream (+ 16 bytes: the round buffer has slack)
-        const unsigned long long lim = (S.s_end + 15) & ~15ull;
-        const unsigned long long hi = lo + SCAN_WIN < lim ? lo + SCAN_WIN : lim;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const unsigned long long a = lo + 16ull * (64u * k + lane);
-            pre[k] = a < hi ? *reinterpret_cast<const uint4 *>(raw + a) : make_uint4(0, 0, 0, 0);
-        }
-        hi_out = hi;
-    };
-    auto commit = [&]() {                                        // registers -> LDS
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 16; ++k) win[64 * k + lane] = pre[k];
-        __syncthreads();
-    };
-    auto need = [&](unsigned long long from, unsigned long long upto) {     // make [from, upto) readable from LDS (upto - from <= a few hundred bytes)
-        if (from >= wlo && upto <= whi) return;
-        const unsigned long long lo = from & ~15ull;
-        if (!(plo != ~0ull && lo >= plo && upto <= phi)) { plo = lo; fetch(plo, phi); }
-        commit();
-        wlo = plo; whi = phi;
-        plo = whi >= 16 ? whi - 16 : 0;                          // the chain enters the next window within its first 16 bytes, unless a record jumps over it
-        if (plo < ((S.s_end + 15) & ~15ull)) fetch(plo, phi); else plo = ~0ull;
-    };
-    // ---- entry point
-    unsigned long long first = S.start;
-    if (first == ~0ull) {
-        for (unsigned long long base = S.beg; base < S.end && first == ~0ull; base += 64) {
-            const unsigned long long o = base + lane;
-            const unsigned long long upto = base + 64 + 36 < S.s_end ? base + 64 + 36 : S.s_end;
-            need(base, upto);
-            bool ok = o < S.end && S.s_end - o >= 36;
-            uint32_t bs = 0;
-            if (ok) {
-                const uint32_t b = (uint32_t)(o - wlo);
-                bs = lds_u32(w32, b);
-                const int32_t tid = (int32_t)lds_u32(w32, b + 4), pos = (int32_t)lds_u32(w32, b + 8);
-                const uint32_t w = lds_u32(w32, b + 12), fn = lds_u32(w32, b + 16);
-                const int32_t l_seq = (int32_t)lds_u32(w32, b + 20), mtid = (int32_t)lds_u32(w32, b + 24), mpos = (int32_t)lds_u32(w32, b + 28);
-                const uint32_t l_name = w & 0xffu, n_cigar = fn & 0xffffu;
-                const unsigned long long needb = 36ull + l_name + 4ull * n_cigar + ((unsigned long long)(uint32_t)l_seq + 1) / 2 + (unsigned long long)(uint32_t)l_seq;
-                ok = (int32_t)bs >= 32 && bs < (1u << 28) && (unsigned long long)bs + 4 <= S.s_end - o && tid >= -1 && tid < n_contigs && pos >= -1 && l_name >= 1 &&
-                     l_seq >= 0 && needb <= (unsigned long long)bs + 4 && mtid >= -1 && mtid < n_contigs && mpos >= -1;
-            }
-            if (ok) {                                            // its two successors (global memory: few lanes get here)
-                unsigned long long o2 = o + 4ull + bs;
-                for (int d = 0; d < 2 && ok && o2 < S.s_end; ++d) { uint32_t b2 = 0; ok = plausible_at(raw, o2, S.s_end, n_contigs, b2); o2 += 4ull + b2; }
-            }
-            const unsigned long long m = __ballot(ok);
-            if (m) first = base + (unsigned long long)__builtin_ctzll(m);
-        }
-    }
-    // ---- walk
-    unsigned long long off = first, bad = ~0ull, stop = ~0ull;
-    unsigned long long *out = tmp_off + S.out_base;
-    uint32_t cnt = 0;
-    if (first != ~0ull) {
-        while (off < S.end) {
-            if (S.s_end - off < 36) { bad = off; break; }
-            need(off, off + 4);
-            const uint32_t bs = lds_u32(w32, (uint32_t)(off - wlo));
-            if ((int32_t)bs < 32 || (unsigned long long)bs + 4 > S.s_end - off) { bad = off; break; }
-            if (lane == 0) obuf[cnt & 63u] = off;
-            ++cnt;
-            if ((cnt & 63u) == 0u) { __syncthreads(); out[cnt - 64u + lane] = obuf[lane]; __syncthreads(); }
-            off += 4ull + bs;
-        }
-        stop = off;
-        __syncthreads();
-        if (lane < (cnt & 63u)) out[(cnt & ~63u) + lane] = obuf[lane];
-    }
-    if (lane == 0) outs[sg] = ScanOut{first, stop, bad, cnt, 0u};
-}
-
-// ---- the same chain, found by many short walks side by side (round 5).  A stream is cut into SUB-SEGMENTS of a few kilobytes, one LANE
-// each: the lane guesses where the chain enters its bytes -- the first offset whose 36 header bytes are those of a plausible record (sizes
-// consistent, contig ids in range, the read name's terminating NUL where l_read_name says) and whose two successors are too --, walks the
-// ~20 records that start there and leaves their offsets (16-bit, relative to the sub-segment) in its slots.  A second kernel checks every
-// seam on the device -- a sub-segment's walk must have begun exactly where the chain stood after the sub-segments before it (running maximum
-// of the walks' ends) --, a scan of the accepted counts gives every sub-segment its first record, a third kernel writes the offsets out.
-// One wait, for the record count.  A seam that does not hold (a wrong guess: a record longer than a sub-segment with something
-// header-like inside) is repaired on the device: msnv_scan_check finds every stream's first such sub-segment, msnv_scan_fix walks it again
-// from the true entry (below).  Only a chain that breaks from its true entry, or a sub-segment with more records than slots, sends the round
-// through msnv_scan_segments above, which words the error.
-struct SubStream { unsigned long long beg, end; uint32_t sub0, pad; };        // bytes [beg, end) of the round buffer, first sub-segment
-__device__ __forceinline__ bool hdr_plausible(const uint8_t *raw, unsigned long long o, unsigned long long s_end, int n_contigs, uint32_t &bs_out) {
-    if (s_end - o < 36) return false;
-    const uint64_t a = ld64(raw + o);
-    const uint32_t bs = (uint32_t)a; const int32_t tid = (int32_t)(a >> 32);
-    bs_out = bs;
-    if ((int32_t)bs < 32 || bs >= (1u << 28) || (unsigned long long)bs + 4 > s_end - o || tid < -1 || tid >= n_contigs) return false;
-    const uint64_t b = ld64(raw + o + 8), c = ld64(raw + o + 16), d = ld64(raw + o + 24);
-    const int32_t pos = (int32_t)(uint32_t)b, l_seq = (int32_t)(c >> 32), mtid = (int32_t)(uint32_t)d, mpos = (int32_t)(d >> 32);
-    const uint32_t l_name = (uint32_t)(b >> 32) & 0xffu, n_cigar = (uint32_t)c & 0xffffu;
-    if (pos < -1 || l_name < 1 || l_seq < 0 || mtid < -1 || mtid >= n_contigs || mpos < -1) return false;
-    const unsigned long long need = 36ull + l_name + 4ull * n_cigar + ((unsigned long long)(uint32_t)l_seq + 1) / 2 + (unsigned long long)(uint32_t)l_seq;
-    if (need > (unsigned long long)bs + 4) return false;
-    // (a GUESS may be as strict as it likes -- a sub-segment without one is walked from the true entry by msnv_scan_fix.  More than 64 KB of
-    // auxiliary fields and a read name that does not begin and end on a printable character are turned down: four bytes in front of a true
-    // header the last qualities of the record before read as a block_size of millions, the true block_size as a contig number -- with the
-    // 2 500 contigs of BASELINE configs[2] that passed every other test ~20 times per stream, a repair pass each)
-    if ((unsigned long long)bs + 4 - need > 65536ull) return false;
-    if (raw[o + 36 + l_name - 1] != 0) return false;
-    if (l_name >= 2) { const uint8_t c0 = raw[o + 36], c1 = raw[o + 36 + l_name - 2]; if (c0 < 33 || c0 > 126 || c1 < 33 || c1 > 126) return false; }
-    return true;
-}
-__device__ __forceinline__ uint32_t sub_stream_of(const SubStream *ss, uint32_t n_streams, uint32_t g) {        // last stream whose first sub-segment is at or before g
-    uint32_t a = 0, b = n_streams;
-    while (b - a > 1) { const uint32_t m = (a + b) / 2; if (ss[m].sub0 <= g) a = m; else b = m; }
-    return a;
-}
-// Sub-segment g: its stream (si, S) and its bytes [b, e) of the round buffer.  sub_at when the stream is known, sub_of finds it.
-struct Sub { SubStream S; uint32_t si; unsigned long long b, e; };
-__device__ __forceinline__ Sub sub_at(const SubStream *ss, uint32_t si, uint32_t g, uint32_t sub_bytes) {
-    Sub u; u.S = ss[si]; u.si = si;
-    u.b = u.S.beg + (unsigned long long)(g - u.S.sub0) * sub_bytes; u.e = u.b + sub_bytes < u.S.end ? u.b + sub_bytes : u.S.end;
-    return u;
-}
-__device__ __forceinline__ Sub sub_of(const SubStream *ss, uint32_t n_streams, uint32_t g, uint32_t sub_bytes) { return sub_at(ss, sub_stream_of(ss, n_streams, g), g, sub_bytes); }
-// Where the chain enters [b, e), guessed: the first offset that is plausible with its two successors (~0: none)
-__device__ __forceinline__ unsigned long long guess_entry(const uint8_t *raw, const SubStream &S, unsigned long long b, unsigned long long e, int n_contigs) {
-    // sixteen offsets a step from 32 bytes in registers (a load per offset made the kernel L2-bound: every lane steps through its own
-    // cache lines); block_size and refID of a candidate are looked at first -- almost nothing else passes them
-    unsigned long long f = ~0ull;
-    const unsigned long long a0 = b & ~15ull;                  // (aligned 16-byte pieces; the buffer is readable 256 bytes past the last stream)
-    uint4 lo4 = *reinterpret_cast<const uint4 *>(raw + a0);
-    for (unsigned long long base16 = a0; base16 < e && f == ~0ull; base16 += 16) {
-        const uint4 hi4 = *reinterpret_cast<const uint4 *>(raw + base16 + 16);
-        const uint32_t w[7] = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z};
-#pragma unroll
-        for (uint32_t k = 0; k < 16u; ++k) {
-            const uint32_t bs = __builtin_amdgcn_alignbyte(w[(k >> 2) + 1], w[k >> 2], k & 3u);
-            const int32_t tid = (int32_t)__builtin_amdgcn_alignbyte(w[(k >> 2) + 2], w[(k >> 2) + 1], k & 3u);
-            const unsigned long long o = base16 + k;
-            if ((int32_t)bs < 32 || bs >= (1u << 28) || tid < -1 || tid >= n_contigs || o < b || o >= e || f != ~0ull) continue;
-            uint32_t bs1 = 0;
-            if (!hdr_plausible(raw, o, S.end, n_contigs, bs1)) continue;
-            bool ok = true;
-            unsigned long long o2 = o + 4ull + bs1;
-            for (int d = 0; d < 2 && ok && o2 < S.end; ++d) { uint32_t b2 = 0; ok = hdr_plausible(raw, o2, S.end, n_contigs, b2); o2 += 4ull + b2; }
-            if (ok) f = o;
-        }
-        lo4 = hi4;
-    }
-    return f;
-}
-// A Walk goes over one sub-segment's records.  Two exist: WalkPlain here (the offsets: the careful route, the dealer) and WalkMeasure
-// further down (the slots and the sub-segment's SubInfo: the quick route).  What the scan and the fix body ask of one:
-//   walk(g, entry, b, e, s_end, cap, sums, n, off)   from `entry`, the records that start in [b, e): the first `cap` into sub-segment g's
-//                                                    slots; leaves their number in n, the chain's next offset in off, and adds what it
-//                                                    sums to `sums`; returns whether the chain held
-//   Sums, none()                                     what a walk sums, and its empty value (WalkPlain: nothing)
-//   keep(g, sums)                                    stores the sums of an ACCEPTED walk -- info[g] is written by the measuring walk only
-struct WalkPlain {
-    struct Sums {};
-    const uint8_t *raw; uint16_t *delta;
-    static __device__ __forceinline__ Sums none() { return Sums{}; }
-    __device__ __forceinline__ bool walk(uint32_t g, unsigned long long entry, unsigned long long b, unsigned long long e, unsigned long long s_end, uint32_t cap, Sums &,
-                                         uint32_t &n, unsigned long long &off) const {
-        uint16_t *dl = delta + (size_t)g * cap;
-        n = 0; off = entry;
-        while (off < e) {
-            if (s_end - off < 36) return false;
-            const uint32_t bs = ld32(raw + off);
-            if ((int32_t)bs < 32 || (unsigned long long)bs + 4 > s_end - off) return false;
-            if (n < cap) dl[n] = (uint16_t)(off - b);
-            ++n;
-            off += 4ull + bs;
-        }
-        return true;
-    }
-    __device__ __forceinline__ void keep(uint32_t, const Sums &) const {}
-};
-// One lane per sub-segment: the entry (the stream's first byte, or a guess), the walk from it, the verdict.
-template <typename Walk>
-__device__ __forceinline__ void scan_sub_body(const uint8_t *raw, const SubStream *ss, uint32_t n_streams, uint32_t n_sub, uint32_t sub_bytes, uint32_t cap, int n_contigs,
-                                              unsigned long long *first, unsigned long long *stop, uint32_t *cnt, uint32_t *flags, const Walk &wk) {
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_sub) return;
-    const Sub u = sub_of(ss, n_streams, g, sub_bytes);
-    const bool guessed = g != u.S.sub0;
-    const unsigned long long f = guessed ? guess_entry(raw, u.S, u.b, u.e, n_contigs) : u.S.beg;
-    uint32_t n = 0; unsigned long long off = f;
-    bool ok = true;
-    typename Walk::Sums sums = Walk::none();
-    if (f != ~0ull) ok = wk.walk(g, f, u.b, u.e, u.S.end, cap, sums, n, off);
-    ok = ok && n <= cap;
-    if (!ok && guessed) { first[g] = ~0ull - 1ull; stop[g] = 0ull; cnt[g] = 0u; return; }      // a walk from a GUESSED entry that breaks: a wrong guess (the fix kernel walks again from the true one)
-    first[g] = f; stop[g] = f != ~0ull ? off : 0ull; cnt[g] = n;
-    wk.keep(g, sums);
-    if (!ok) atomicOr(flags, 1u);                                   // a malformed chain from the stream's first byte (or more records than slots): the careful kernel / route reports or takes it
-}
-__global__ __launch_bounds__(256) void msnv_scan_sub(const uint8_t *raw, const SubStream *ss, uint32_t n_streams, uint32_t n_sub, uint32_t sub_bytes, uint32_t cap, int n_contigs,
-                                                     unsigned long long *first, unsigned long long *stop, uint32_t *cnt, uint16_t *delta, uint32_t *flags) {
-    scan_sub_body(raw, ss, n_streams, n_sub, sub_bytes, cap, n_contigs, first, stop, cnt, flags, WalkPlain{raw, delta});
-}
-// seams: cur = where the chain stands in front of sub-segment g = the largest end of a walk before it (the stream's first byte for its first
-// sub-segment: ends of earlier streams lie before it)
-// Seams of the quick scan, checked AND repaired (round 5): a sub-segment whose walk did not begin where the chain of the earlier ones stands
-// (stop_max: running maximum of their ends) guessed wrong -- a false header inside a read name or a quality string: one in ~1e7 sub-segments,
-// i.e. several in every round of BASELINE configs[2], where sending the whole round through the careful kernel cost 3 x the scan (85 of 128 ms).
-// Only the FIRST such sub-segment of a stream can be trusted to be wrong (everything in front of it is the true chain; a wrong walk's end --
-// it may lie a whole stream further on -- makes the ones behind it LOOK wrong): msnv_scan_check finds it, msnv_scan_fix walks it again from the
-// true entry, the host scans the ends again and asks once more -- as many passes as the worst stream has wrong guesses (usually none).
-// Flags: 2 = a sub-segment was fixed, 4 = the chain breaks from its TRUE entry (malformed input: the careful kernel words the error).
-__device__ __forceinline__ unsigned long long chain_before(const Sub &u, const unsigned long long *stop_max, uint32_t g) {      // (g is not its stream's first sub-segment)
-    const unsigned long long cur = stop_max[g - 1];
-    return cur > u.S.beg ? cur : u.S.beg;
-}
-__global__ void msnv_scan_check(const SubStream *ss, uint32_t n_streams, uint32_t n_sub, uint32_t sub_bytes, const unsigned long long *first, const unsigned long long *stop_max, uint32_t *cnt, uint32_t *first_bad) {
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_sub) { if (g == n_sub) cnt[g] = 0; return; }
-    const Sub u = sub_of(ss, n_streams, g, sub_bytes);
-    if (g == u.S.sub0) return;                                      // (entered at the stream's first byte)
-    const unsigned long long cur = chain_before(u, stop_max, g);
-    const unsigned long long want = cur >= u.e ? ~0ull : cur;       // cur >= e: a record runs across the whole sub-segment, nothing starts here
-    if (first[g] != want) atomicMin(&first_bad[u.si], g);
-}
-// One lane per stream: its first sub-segment that guessed wrong, walked again from where the chain stands.
-template <typename Walk>
-__device__ __forceinline__ void scan_fix_body(const SubStream *ss, uint32_t n_streams, uint32_t sub_bytes, uint32_t cap, unsigned long long *first, unsigned long long *stop,
-                                              const unsigned long long *stop_max, uint32_t *cnt, uint32_t *first_bad, uint32_t *flags, const Walk &wk) {
-    const uint32_t si = blockIdx.x * blockDim.x + threadIdx.x;
-    if (si >= n_streams) return;
-    const uint32_t g = first_bad[si];
-    first_bad[si] = 0xffffffffu;                                    // (for the next pass)
-    if (g == 0xffffffffu) return;
-    const Sub u = sub_at(ss, si, g, sub_bytes);
-    const unsigned long long cur = chain_before(u, stop_max, g);
-    atomicOr(flags, 2u);
-    typename Walk::Sums sums = Walk::none();
-    if (cur >= u.e) { first[g] = ~0ull; stop[g] = 0ull; cnt[g] = 0u; wk.keep(g, sums); return; }
-    uint32_t n = 0; unsigned long long off = cur;
-    if (!wk.walk(g, cur, u.b, u.e, u.S.end, cap, sums, n, off) || n > cap) { atomicOr(flags, 4u); return; }
-    first[g] = cur; stop[g] = off; cnt[g] = n;
-    wk.keep(g, sums);
-}
-__global__ void msnv_scan_fix(const uint8_t *raw, const SubStream *ss, uint32_t n_streams, uint32_t sub_bytes, uint32_t cap, unsigned long long *first, unsigned long long *stop,
-                              const unsigned long long *stop_max, uint32_t *cnt, uint16_t *delta, uint32_t *first_bad, uint32_t *flags) {
-    scan_fix_body(ss, n_streams, sub_bytes, cap, first, stop, stop_max, cnt, first_bad, flags, WalkPlain{raw, delta});
-}
-struct U64Max { __device__ __host__ unsigned long long operator()(unsigned long long a, unsigned long long b) const { return a > b ? a : b; } };
-// The records in record order: a wavefront takes 64 consecutive sub-segments (n_here of them exist), whose records [w of lane 0, j_hi) are
-// consecutive in the list, 64 a step; record j finds its sub-segment among the wavefront's by bisection over the lanes' first records (w).
-// EVERY lane calls per_record(j, owner lane) in EVERY step -- it may shuffle the owner's values to itself, and a shuffle needs all lanes --,
-// so per_record guards its own stores with j < j_hi.
-template <typename PerRecord>
-__device__ __forceinline__ void wave_records(uint32_t w, uint32_t n_here, uint32_t j_hi, PerRecord &&per_record) {
-    const uint32_t lane = threadIdx.x & 63u, j_lo = __shfl(w, 0);
-    for (uint32_t j0 = j_lo; j0 < j_hi; j0 += 64u) {
-        const uint32_t j = j0 + lane;
-        uint32_t lo = 0, hi = n_here;                              // last lane t (< n_here) whose first record is at or before j
-#pragma unroll
-        for (int it = 0; it < 6; ++it) {                           // (six halvings of at most 64 lanes; every lane takes every step: the shuffles need all lanes)
-            const uint32_t m = (lo + hi) / 2;
-            const uint32_t bm = __shfl(w, (int)m);
-            if (hi - lo > 1) { if (bm <= j) lo = m; else hi = m; }
-        }
-        per_record(j, lo);
-    }
-}
-// the offsets out
-__global__ __launch_bounds__(256) void msnv_scan_write(const SubStream *ss, uint32_t n_streams, uint32_t n_sub, uint32_t sub_bytes, uint32_t cap, const uint32_t *cnt, const uint32_t *base,
-                                                       const uint16_t *delta, unsigned long long *rec_off, uint16_t *rec_sample, uint32_t *rec_base) {
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63u, g0 = g - lane;
-    if (g0 >= n_sub) return;
-    uint32_t si = 0, w = 0xffffffffu; unsigned long long b = 0;
-    if (g < n_sub) {
-        const Sub u = sub_of(ss, n_streams, g, sub_bytes);
-        si = u.si; b = u.b;
-        w = base[g];
-        if (g == u.S.sub0) rec_base[si] = w;
-    }
-    const uint32_t n_here = (n_sub - g0 < 64u ? n_sub - g0 : 64u);
-    const uint32_t j_hi = base[g0 + n_here];                        // (base has n_sub + 1 entries)
-    wave_records(w, n_here, j_hi, [&](uint32_t j, uint32_t lo) {
-        const uint32_t wt = __shfl(w, (int)lo), st = __shfl(si, (int)lo);
-        const unsigned long long bt = __shfl(b, (int)lo);
-        if (j < j_hi) { rec_off[j] = bt + delta[(size_t)(g0 + lo) * cap + (j - wt)]; rec_sample[j] = (uint16_t)st; }
-    });
-}
-
-struct CompactSeg { unsigned long long src; uint32_t dst, cnt, sample, pad; };
-__global__ void msnv_compact_offsets(const unsigned long long *tmp_off, const CompactSeg *segs, unsigned long long *rec_off, uint16_t *rec_sample) {
-    const CompactSeg c = segs[blockIdx.x];
-    for (uint32_t k = threadIdx.x; k < c.cnt; k += blockDim.x) { rec_off[c.dst + k] = tmp_off[c.src + k]; rec_sample[c.dst + k] = (uint16_t)c.sample; }
 }
 
 // ------------------------------------------------------------------------------------------ per-record measure
@@ -755,7 +373,7 @@ struct DpRun { uint32_t sample; int32_t tid, first_any, first_from1; };
 struct DevGroupRec { uint32_t sample; int32_t tid; uint32_t tile, a, b, end, md_own, md_next; };
 struct DpSampleDst { uint8_t *seq, *qual; unsigned long long pbase0; uint32_t cut_marks, pad; };      // where a sample's columns lie in the round's buffer, its first piece
 // ------------------------------------------------------------------------------------------ round 6: scan and measure in ONE walk
-// The quick scan's lane (one per sub-segment of a stream, above) has every record's header line in hand when it reads block_size; the
+// The quick scan's lane (one per sub-segment of a stream: devrec.h) has every record's header line in hand when it reads block_size; the
 // measure kernel then went to the same lines again, one thread per record, for everything else (3.1 GB of sector fetches for the 3.07 GB of
 // the benchmark's records, 0.92 ms + a wait).  Here the walk measures as it goes (measure_one) and leaves per RECORD a 32-byte slot -- key,
 // end, flags, first tile and its places among the sub-segment's records: pieces, intervals, next-tile pieces, seq bytes, rank among the
@@ -2200,478 +1818,6 @@ void devpack_release(msnv_dataset &ds) {
     }
 }
 
-// Record streams (host or device memory) side by side in one device buffer and the offsets of their records: what the device pack
-// (devpack_add_round) and the device dealer (msnv_records_deal_device) start from.
-struct ScanResult {
-    uint8_t *raw = nullptr; uint64_t raw_bytes = 0;
-    std::vector<unsigned long long> s_beg, s_end, bad_off;      // per stream: first / end byte in raw; offset of a malformed record (~0: none)
-    std::vector<uint32_t> rec_base, n_rec;                       // per stream: index of its first record / its record count
-    uint32_t NR = 0;
-    uint32_t *d_recbase = nullptr; unsigned long long *d_send = nullptr, *d_recoff = nullptr; uint16_t *d_recsample = nullptr;
-    double wall_upload_s = 0, ms_scan = 0; uint64_t n_redone = 0;
-};
-// The round's streams side by side in one buffer: every stream starts on 16 bytes, readable bytes behind the last.  Nothing is scanned.
-static int stage_streams(hipStream_t st, const int device, BufPool &pool, const uint8_t *const *streams, const uint64_t *n_bytes, const size_t S, const bool on_device, ScanResult &R,
-                         const uint8_t *in_place_base = nullptr) {
-    R.s_beg.assign(S, 0); R.s_end.assign(S, 0);
-    if (in_place_base) {
-        // the streams where they lie: offsets into the caller's buffer (api.cpp / bamfeed.cpp have checked order, alignment of the base and the bytes behind the last)
-        for (size_t s = 0; s < S; ++s) { R.s_beg[s] = (unsigned long long)(streams[s] - in_place_base); R.s_end[s] = R.s_beg[s] + n_bytes[s]; }
-        R.raw = const_cast<uint8_t *>(in_place_base);
-        for (size_t s = 0; s < S; ++s) R.raw_bytes += n_bytes[s];     // (accounting: the records' bytes)
-        return MSNV_OK;
-    }
-    for (size_t s = 0; s < S; ++s) { R.s_beg[s] = R.raw_bytes; R.s_end[s] = R.raw_bytes + n_bytes[s]; R.raw_bytes += (n_bytes[s] + 15 + 16) & ~15ull; }
-    uint8_t *const raw = pool.take<uint8_t>(R.raw_bytes + 256);
-    if (pool.rc) return pool.rc;
-    const double t0 = now_s();
-    if (on_device) {
-        for (size_t s = 0; s < S; ++s) if (n_bytes[s]) HIP_TRY(hipMemcpyAsync(raw + R.s_beg[s], streams[s], n_bytes[s], hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    } else {
-        // pageable host memory: a few copies in flight keep the link busy (the runtime stages them)
-        std::atomic<size_t> next{0}; std::atomic<int> bad{0};
-        auto w = [&]() {
-            (void)hipSetDevice(device);
-            for (;;) { const size_t s = next.fetch_add(1); if (s >= S) break; if (n_bytes[s] && hipMemcpy(raw + R.s_beg[s], streams[s], n_bytes[s], hipMemcpyHostToDevice) != hipSuccess) bad.store(1); }
-        };
-        std::vector<std::thread> th;
-        for (size_t k = 0; k < std::min<size_t>(S, 6); ++k) th.emplace_back(w);
-        for (auto &x : th) x.join();
-        if (bad.load()) return fail(MSNV_EHIP, "upload of the record streams failed: %s", hipGetErrorString(hipGetLastError()));
-    }
-    R.wall_upload_s += now_s() - t0;
-    R.raw = raw;
-    return MSNV_OK;
-}
-
-// What the sub-segment walk of either route works on: the sub-segments' entries, ends, counts and offsets, the seam check's words.  A route
-// adds its own buffers and kernels: the walk and the fix kernel, and what it queues behind the repair before the one wait.
-struct SubWalk {
-    uint32_t n_sub = 0, sub_bytes = 0, cap = 0; size_t S = 0;
-    SubStream *d_ss = nullptr; unsigned long long *d_first = nullptr, *d_stop = nullptr, *d_stopmax = nullptr; uint32_t *d_cnt = nullptr; uint16_t *d_delta = nullptr;
-    uint32_t *d_fl = nullptr, *d_firstbad = nullptr;
-    SubWalk(size_t n_streams, uint32_t n_sub_, uint32_t sub_bytes_, uint32_t cap_) : n_sub(n_sub_), sub_bytes(sub_bytes_), cap(cap_), S(n_streams) {}
-    void take(BufPool &pool) {                                    // (the caller looks at pool.rc after its own takes)
-        d_ss = pool.take<SubStream>(S);
-        d_first = pool.take<unsigned long long>((uint64_t)n_sub + 1);
-        d_stop = pool.take<unsigned long long>((uint64_t)n_sub + 1);
-        d_stopmax = pool.take<unsigned long long>((uint64_t)n_sub + 1);
-        d_cnt = pool.take<uint32_t>((uint64_t)n_sub + 1);
-        d_delta = pool.take<uint16_t>((uint64_t)n_sub * cap + 8);
-        d_fl = pool.take<uint32_t>(4);
-        d_firstbad = pool.take<uint32_t>(S);
-    }
-    // the streams' sub-segments and ends up (d_send: the route's own copy of the ends), the flags cleared
-    int upload(hipStream_t st, const std::vector<SubStream> &ss, const std::vector<unsigned long long> &s_end, unsigned long long *d_send) {
-        HIP_TRY(hipMemcpyAsync(d_ss, ss.data(), S * sizeof(SubStream), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_send, s_end.data(), S * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(d_fl, 0, 16, st));
-        HIP_TRY(hipMemsetAsync(d_firstbad, 0xff, S * 4, st));
-        return MSNV_OK;
-    }
-    // The seams, behind the walk kernel: checked, every stream's first sub-segment that guessed wrong walked again -- fix() launches the route's
-    // fix kernel --, until none is left (usually the first look).  after() queues what the route wants behind the repair, so that every pass
-    // has ONE wait.  Leaves the flag word in `fl` (0: every seam holds; else the walk does not stand) and counts the repair passes.
-    template <typename Fix, typename After>
-    int settle(hipStream_t st, Prim &prim, Fix fix, After after, uint32_t &fl, uint64_t &n_redone) {
-        for (int pass = 0;; ++pass) {
-            if (int rc = prim.inclusive(d_stop, d_stopmax, (size_t)n_sub, U64Max())) return rc;
-            hipLaunchKernelGGL(msnv_scan_check, grid_for((uint64_t)n_sub + 1, 256), dim3(256), 0, st, d_ss, (uint32_t)S, n_sub, sub_bytes, d_first, d_stopmax, d_cnt, d_firstbad);
-            fix();
-            HIP_TRY(hipGetLastError());
-            if (int rc = after()) return rc;
-            HIP_TRY(hipMemcpyAsync(&fl, d_fl, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            if (!(fl & 2u) || (fl & 5u) || pass >= 4096) return MSNV_OK;
-            n_redone += 1;                                        // (counted: a repair pass)
-            HIP_TRY(hipMemsetAsync(d_fl, 0, 4, st));
-        }
-    }
-};
-
-// Record boundaries of staged streams, the quick way: sub-segments walked side by side, seams checked on the device.  `found` says whether
-// the walk stands; a chain that breaks or a sub-segment with more records than its slots leaves the round to scan_segments (counted).
-static int scan_sub_walk(hipStream_t st, BufPool &pool, const uint64_t *n_bytes, const size_t S, const size_t NC, ScanResult &R, bool &found) {
-    found = false;
-    const uint32_t sub_bytes = knob::scan_sub_bytes(knob::SCAN_SUB_STREAMS);   // (per call: tests shrink it)
-    std::vector<SubStream> ss(S);
-    uint64_t n_sub64 = 0;
-    for (size_t s = 0; s < S; ++s) { ss[s] = SubStream{R.s_beg[s], R.s_end[s], (uint32_t)n_sub64, 0u}; n_sub64 += std::max<uint64_t>(1, (n_bytes[s] + sub_bytes - 1) / sub_bytes); }
-    if (n_sub64 >= 0x7ffffff0ull) return MSNV_OK;
-    SubWalk W(S, (uint32_t)n_sub64, sub_bytes, sub_bytes / 36u + 2u);
-    const uint32_t n_sub = W.n_sub;
-    uint8_t *const raw = R.raw;
-    Timer tm(st);
-    Prim prim(st);
-    const size_t pool_from = pool.mark();
-    W.take(pool);
-    auto *d_base = pool.take<uint32_t>((uint64_t)n_sub + 1);
-    auto *d_recbase = pool.take<uint32_t>(S + 1);
-    auto *d_send = pool.take<unsigned long long>(S);
-    if (pool.rc) return pool.rc;
-    if (int rc = prim.bind(pool, 1u << 20)) return rc;
-    tm.start();
-    if (int rc = W.upload(st, ss, R.s_end, d_send)) return rc;
-    hipLaunchKernelGGL(msnv_scan_sub, grid_for(n_sub, 256), dim3(256), 0, st, raw, W.d_ss, (uint32_t)S, n_sub, sub_bytes, W.cap, (int)NC, W.d_first, W.d_stop, W.d_cnt, W.d_delta, W.d_fl);
-    HIP_TRY(hipGetLastError());
-    size_t need = 0;                                              // both scans' storage before either is queued
-    if (int rc = prim.inclusive(W.d_stop, W.d_stopmax, (size_t)n_sub, U64Max(), &need)) return rc;
-    if (int rc = prim.exclusive(W.d_cnt, d_base, 0u, (size_t)n_sub + 1, rocprim::plus<uint32_t>(), &need)) return rc;
-    if (int rc = prim.room(need)) return rc;
-    uint32_t fl = 0;
-    auto fix = [&]() {
-        hipLaunchKernelGGL(msnv_scan_fix, grid_for(S, 64), dim3(64), 0, st, raw, W.d_ss, (uint32_t)S, sub_bytes, W.cap, W.d_first, W.d_stop, W.d_stopmax, W.d_cnt, W.d_delta, W.d_firstbad, W.d_fl);
-    };
-    if (int rc = W.settle(st, prim, fix, []() { return MSNV_OK; }, fl, R.n_redone)) return rc;
-    if (fl) {
-        R.ms_scan += tm.stop();
-        R.n_redone += 1;                                          // (counted: the round goes through the careful kernel)
-        pool.rewind(pool_from);
-        return MSNV_OK;
-    }
-    if (int rc = prim.exclusive(W.d_cnt, d_base, 0u, (size_t)n_sub + 1, rocprim::plus<uint32_t>())) return rc;
-    HIP_TRY(hipMemcpyAsync(&R.NR, d_base + n_sub, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    // (a 32-bit count that wrapped would show as a total below the sub-segments' sum; 2^32 records need 150 GB of stream in one round -- refused by size)
-    if (R.raw_bytes / 36 > 0xfffffff0ull) return fail(MSNV_EDOMAIN, "more than 2^32 records in one round of the device pack");
-    const uint32_t NR = R.NR;
-    auto *d_recoff = pool.take<unsigned long long>((uint64_t)NR + 1);
-    auto *d_recsample = pool.take<uint16_t>((uint64_t)NR + 1);
-    if (pool.rc) return pool.rc;
-    hipLaunchKernelGGL(msnv_scan_write, grid_for(n_sub, 256), dim3(256), 0, st, W.d_ss, (uint32_t)S, n_sub, sub_bytes, W.cap, W.d_cnt, d_base, W.d_delta, d_recoff, d_recsample, d_recbase);
-    HIP_TRY(hipGetLastError());
-    R.rec_base.assign(S + 1, 0);
-    HIP_TRY(hipMemcpyAsync(d_recbase + S, &R.NR, 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(R.rec_base.data(), d_recbase, S * 4, hipMemcpyDeviceToHost, st));
-    R.ms_scan += tm.stop();                                       // (waits: both copies are done)
-    R.rec_base[S] = NR;
-    R.n_rec.assign(S, 0); R.bad_off.assign(S, ~0ull);
-    for (size_t s = 0; s < S; ++s) R.n_rec[s] = R.rec_base[s + 1] - R.rec_base[s];
-    R.d_recbase = d_recbase; R.d_send = d_send; R.d_recoff = d_recoff; R.d_recsample = d_recsample;
-    found = true;
-    return MSNV_OK;
-}
-
-// Record boundaries of staged streams, the careful way: segments, guessed entry points, seams checked on the host; words malformed input.
-static int scan_segments(hipStream_t st, BufPool &pool, const size_t S, const size_t NC, ScanResult &R) {
-    const std::vector<unsigned long long> &s_beg = R.s_beg, &s_end = R.s_end;
-    uint8_t *const raw = R.raw;
-    Timer tm(st);
-    const uint64_t seg_bytes = knob::scan_seg_bytes();   // (per call: tests shrink it)
-    std::vector<ScanSeg> segs;
-    std::vector<uint32_t> seg_lo(S + 1, 0);                       // per stream: its first segment
-    uint64_t cap_total = 0;
-    for (size_t s = 0; s < S; ++s) {
-        seg_lo[s] = (uint32_t)segs.size();
-        for (uint64_t o = s_beg[s]; o < s_end[s]; o += seg_bytes) {
-            const uint64_t e = std::min<uint64_t>(o + seg_bytes, s_end[s]);
-            segs.push_back(ScanSeg{o, e, s_end[s], o == s_beg[s] ? o : ~0ull, cap_total});
-            cap_total += (e - o) / 36 + 2;
-        }
-    }
-    seg_lo[S] = (uint32_t)segs.size();
-    const size_t NSEG = segs.size();
-    if (NSEG > 0x7fffffffull) return fail(MSNV_EDOMAIN, "too many scan segments in one round");
-    auto *d_segs = pool.take<ScanSeg>(NSEG + 1);
-    auto *d_outs = pool.take<ScanOut>(NSEG + 1);
-    auto *d_tmpoff = pool.take<unsigned long long>(cap_total + 64);
-    if (pool.rc) return pool.rc;
-    std::vector<ScanOut> outs(NSEG);
-    std::vector<uint32_t> &n_rec = R.n_rec; n_rec.assign(S, 0); std::vector<uint32_t> acc_cnt(NSEG, 0);
-    std::vector<unsigned long long> &bad_off = R.bad_off; bad_off.assign(S, ~0ull);
-    tm.start();
-    if (NSEG) {
-        HIP_TRY(hipMemcpyAsync(d_segs, segs.data(), NSEG * sizeof(ScanSeg), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(msnv_scan_segments, dim3((unsigned)NSEG), dim3(64), 0, st, raw, d_segs, (uint32_t)NSEG, (int)NC, d_tmpoff, d_outs);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(outs.data(), d_outs, NSEG * sizeof(ScanOut), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        // seams: cur = where the true chain stands; a segment is accepted when its walk began exactly there
-        std::vector<unsigned long long> cur(S);
-        std::vector<uint32_t> at(S);                             // next segment to look at, per stream
-        for (size_t s = 0; s < S; ++s) { cur[s] = s_beg[s]; at[s] = seg_lo[s]; }
-        const size_t repair_lists = pool.mark();                  // (the two lists below are reused by every repair round)
-        for (int round_no = 0;; ++round_no) {
-            std::vector<uint32_t> redo;
-            for (size_t s = 0; s < S; ++s) {
-                while (at[s] < seg_lo[s + 1] && bad_off[s] == ~0ull) {
-                    const uint32_t k = at[s];
-                    if (cur[s] >= segs[k].end) { acc_cnt[k] = 0; ++at[s]; continue; }          // a record runs across the whole segment
-                    if (outs[k].first != cur[s]) { segs[k].start = cur[s]; redo.push_back(k); break; }
-                    acc_cnt[k] = outs[k].cnt;
-                    if (outs[k].bad != ~0ull) { bad_off[s] = outs[k].bad - s_beg[s]; break; }
-                    cur[s] = outs[k].stop;
-                    ++at[s];
-                }
-            }
-            if (redo.empty()) break;
-            if (round_no > (int)NSEG + 1) return fail(MSNV_EINVAL, "internal: the record scan does not converge");
-            // walk the segments that guessed wrong again, from the true entry point (one launch over just those)
-            std::vector<ScanSeg> again;
-            for (uint32_t k : redo) again.push_back(segs[k]);
-            auto *d_again = pool.take<ScanSeg>(again.size());
-            auto *d_aout = pool.take<ScanOut>(again.size());
-            if (pool.rc) return pool.rc;
-            std::vector<ScanOut> aout(again.size());
-            HIP_TRY(hipMemcpyAsync(d_again, again.data(), again.size() * sizeof(ScanSeg), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(msnv_scan_segments, dim3((unsigned)again.size()), dim3(64), 0, st, raw, d_again, (uint32_t)again.size(), (int)NC, d_tmpoff, d_aout);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(aout.data(), d_aout, again.size() * sizeof(ScanOut), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            for (size_t j = 0; j < redo.size(); ++j) outs[redo[j]] = aout[j];
-            R.n_redone += redo.size();
-            pool.rewind(repair_lists);
-        }
-    }
-    R.ms_scan += tm.stop();                                       // (the lists below are allocated outside the timed region)
-    std::vector<uint32_t> &rec_base = R.rec_base; rec_base.assign(S + 1, 0);
-    std::vector<CompactSeg> csegs;
-    {
-        uint64_t total = 0;
-        for (size_t s = 0; s < S; ++s) {
-            rec_base[s] = (uint32_t)total;
-            for (uint32_t k = seg_lo[s]; k < seg_lo[s + 1]; ++k) {
-                if (acc_cnt[k]) csegs.push_back(CompactSeg{segs[k].out_base, (uint32_t)total, acc_cnt[k], (uint32_t)s, 0u});
-                total += acc_cnt[k];
-                if (total > 0xfffffff0ull) return fail(MSNV_EDOMAIN, "more than 2^32 records in one round of the device pack");
-            }
-            n_rec[s] = (uint32_t)total - rec_base[s];
-        }
-        rec_base[S] = (uint32_t)total;
-    }
-    R.NR = rec_base[S];
-    const uint64_t NRa = (uint64_t)R.NR + 1;
-    R.d_recbase = pool.take<uint32_t>(S + 1);
-    R.d_send = pool.take<unsigned long long>(S);
-    R.d_recoff = pool.take<unsigned long long>(NRa);
-    R.d_recsample = pool.take<uint16_t>(NRa);
-    auto *d_csegs = pool.take<CompactSeg>(csegs.size() + 1);
-    if (pool.rc) return pool.rc;
-    tm.start();
-    HIP_TRY(hipMemcpyAsync(R.d_recbase, rec_base.data(), (S + 1) * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(R.d_send, s_end.data(), S * 8, hipMemcpyHostToDevice, st));
-    if (!csegs.empty()) {
-        HIP_TRY(hipMemcpyAsync(d_csegs, csegs.data(), csegs.size() * sizeof(CompactSeg), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(msnv_compact_offsets, dim3((unsigned)csegs.size()), dim3(256), 0, st, d_tmpoff, d_csegs, R.d_recoff, R.d_recsample);
-        HIP_TRY(hipGetLastError());
-    }
-    R.ms_scan += tm.stop();                                       // (waits: csegs' bytes are up)
-    return MSNV_OK;
-}
-// Where the records of staged streams begin: the sub-segment walk, and the segment scan for what it leaves (and under MSNV_SCAN=segments).
-static int scan_records(hipStream_t st, BufPool &pool, const uint64_t *n_bytes, const size_t S, const size_t NC, ScanResult &R) {
-    if (!knob::scan_segments() && S > 0) {
-        bool found = false;
-        if (int rc = scan_sub_walk(st, pool, n_bytes, S, NC, R, found)) return rc;
-        if (found) return MSNV_OK;
-    }
-    return scan_segments(st, pool, S, NC, R);
-}
-
-
-// ------------------------------------------------------------------------------------------ records dealt to their owners, on the device
-// The N-rank feed (metasnv_amd/parallel.py: feed_sharded): the rank that decoded a BAM sends every mapped record to the rank that owns its
-// contig.  pack.cpp: records_partition does that on a host thread (two walks over the stream + a copy); here the streams go up once, the
-// record scan of the device pack finds the records, one thread per record reads its contig, flag and MAPQ (owner, qaCompute's
-// statistics, optionally the aligned bases per contig that the split planner weighs contigs by), one stable rocPRIM sort by owner and
-// one scan of the sizes give every record its place, and sixteen lanes per record copy it there.  Output: destination-major -- part 0
-// of stream 0, of stream 1, ..., part 1 of stream 0, ... -- with `gap` bytes left free in front of every part (the caller's size table),
-// i.e. exactly the send buffer of the all-to-all; part_bytes[i * n_parts + k] = bytes of stream i in part k.
-namespace {
-constexpr uint32_t DEAL_COPIES = 64;                   // per-stream counters in this many copies (same-address atomics: msnv_measure_reads)
-struct DealAcc { uint32_t total, unmapped, zero_q, proper, dup, any_mapped, bad_tid, bad_owner; };
-__global__ __launch_bounds__(256) void msnv_deal_measure(const uint8_t *raw, const unsigned long long *rec_off, const uint16_t *rec_sample, uint32_t n_rec, const unsigned long long *s_end,
-                                                         const int32_t *owner, int n_contigs, int n_parts, int cov_min_mapq, uint32_t *key, uint32_t *size,
-                                                         DealAcc *acc, unsigned long long *contig_bases) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    int32_t tid = -1; unsigned long long m = 0;
-    // what this record adds to its stream's counters: bit 0 a record, 1 unmapped, 2 below the MAPQ cutoff, 3 proper pair, 4 duplicate, 5 mapped,
-    // 6 a contig beyond the header, 7 an owner beyond the parts
-    uint32_t f = 0, s = 0xffffffffu;
-    if (i < n_rec) {
-        s = rec_sample[i];
-        const Rec r = rec_load(raw + rec_off[i], s_end[s] - rec_off[i]);
-        f = 1u;
-        uint32_t k = 0xffu;                                    // 0xff: the record goes nowhere (unmapped, or its contig is outside every shard)
-        if (!r.ok) f |= 256u;                                  // its inner fields do not fit its block_size: not walked, not forwarded (the host partition's MSNV_EFORMAT)
-        else if ((r.flag & BAM_FUNMAP) || r.tid < 0) f |= 2u;
-        else {
-            f |= 32u;
-            if ((int)r.mapq >= cov_min_mapq) f |= ((r.flag & BAM_FPROPER_PAIR) ? 8u : 0u) | ((r.flag & BAM_FDUP) ? 16u : 0u);
-            else f |= 4u;
-            if (r.tid >= n_contigs) f |= 64u;
-            else {
-                const int32_t o = owner[r.tid];
-                if (o >= n_parts) f |= 128u;
-                else if (o >= 0) k = (uint32_t)o;
-                if (contig_bases) {
-                    tid = r.tid;
-                    for (uint32_t c = 0; c < r.n_cigar; ++c) { const uint32_t w = ld32(r.cigar + 4ull * c); if (cg_match(w & 15u)) m += w >> 4; }
-                }
-            }
-        }
-        key[i] = k;
-        size[i] = k == 0xffu ? 0u : r.bs + 4u;
-    }
-    {
-        // a wavefront's records nearly always belong to one stream: its lanes' bits are counted by ballots and one lane adds them (a lane
-        // per record on the same few words was 5 ms of same-address atomics for 16 M records)
-        const uint32_t s0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s);
-        if (__all(s == s0 || f == 0u)) {
-            if (s0 != 0xffffffffu) {
-                const unsigned long long b0 = __ballot(f & 1u), b1 = __ballot(f & 2u), b2 = __ballot(f & 4u), b3 = __ballot(f & 8u), b4 = __ballot(f & 16u), b5 = __ballot(f & 32u),
-                                         b6 = __ballot(f & 64u), b7 = __ballot(f & 128u);
-                if ((threadIdx.x & 63) == 0) {
-                    DealAcc &a = acc[(size_t)s0 * DEAL_COPIES + (blockIdx.x % DEAL_COPIES)];
-                    atomicAdd(&a.total, (uint32_t)__popcll(b0));
-                    if (b1) atomicAdd(&a.unmapped, (uint32_t)__popcll(b1));
-                    if (b2) atomicAdd(&a.zero_q, (uint32_t)__popcll(b2));
-                    if (b3) atomicAdd(&a.proper, (uint32_t)__popcll(b3));
-                    if (b4) atomicAdd(&a.dup, (uint32_t)__popcll(b4));
-                    if (b5) a.any_mapped = 1u;
-                    if (b6) atomicOr(&a.bad_tid, 1u);
-                    if (b7) a.bad_owner = 1u;
-                    if (__ballot(f & 256u)) atomicOr(&a.bad_tid, 2u);
-                }
-            }
-        } else if (f) {
-            DealAcc &a = acc[(size_t)s * DEAL_COPIES + (blockIdx.x % DEAL_COPIES)];
-            atomicAdd(&a.total, 1u);
-            if (f & 2u) atomicAdd(&a.unmapped, 1u);
-            if (f & 4u) atomicAdd(&a.zero_q, 1u);
-            if (f & 8u) atomicAdd(&a.proper, 1u);
-            if (f & 16u) atomicAdd(&a.dup, 1u);
-            if (f & 32u) a.any_mapped = 1u;
-            if (f & 64u) atomicOr(&a.bad_tid, 1u);
-            if (f & 128u) a.bad_owner = 1u;
-            if (f & 256u) atomicOr(&a.bad_tid, 2u);
-        }
-    }
-    if (contig_bases) {
-        // records are sorted by contig: a wavefront's lanes nearly always share one -- one atomic per wavefront then
-        const int32_t t0 = __builtin_amdgcn_readfirstlane(tid);
-        if (__all(tid == t0 || tid < 0)) {
-            unsigned long long sum = tid == t0 ? m : 0ull;
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o);
-            if ((threadIdx.x & 63) == 0 && t0 >= 0 && sum) atomicAdd(&contig_bases[t0], sum);
-        } else if (tid >= 0 && m) atomicAdd(&contig_bases[tid], m);
-    }
-}
-__global__ void msnv_deal_iota(uint32_t *a, uint32_t n) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) a[i] = i;
-}
-__global__ void msnv_deal_sizes(const uint32_t *order, const uint32_t *size, uint32_t n, uint32_t *out) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n) out[j] = size[order[j]];
-}
-// sixteen lanes per record: 16-byte pieces of the record, any alignment on either side; the per-(stream, part) byte counts in DEAL_COPIES copies
-__global__ __launch_bounds__(256) void msnv_deal_copy(const uint8_t *raw, const unsigned long long *rec_off, const uint16_t *rec_sample, const uint32_t *order, const uint32_t *skey,
-                                                      const uint32_t *ssize, const unsigned long long *pos, uint32_t n, uint32_t n_parts, uint32_t n_streams, unsigned long long gap, uint8_t *out,
-                                                      unsigned long long *part_bytes) {
-    const unsigned long long gt = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t j = (uint32_t)(gt >> 4), l = (uint32_t)gt & 15u;
-    if (j >= n) return;
-    const uint32_t k = skey[j];
-    if (k == 0xffu) return;
-    const uint32_t i = order[j], sz = ssize[j];
-    const uint8_t *src = raw + rec_off[i];
-    uint8_t *dst = out + pos[j] + (unsigned long long)(k + 1u) * gap;
-    for (uint32_t o = 16u * l; o + 16u <= sz; o += 256u) { uint4 v; __builtin_memcpy(&v, src + o, 16); __builtin_memcpy(dst + o, &v, 16); }
-    if (l == 0) {
-        for (uint32_t o = sz & ~15u; o < sz; ++o) dst[o] = src[o];
-        atomicAdd(&part_bytes[((size_t)(blockIdx.x % DEAL_COPIES) * n_streams + rec_sample[i]) * n_parts + k], (unsigned long long)sz);
-    }
-}
-}  // namespace
-
-int records_deal_device(msnv_ctx *ctx, const uint8_t *const *streams, const uint64_t *n_bytes, int n, bool on_device, const int32_t *owner, int n_contigs, int n_parts,
-                        int cov_min_mapq, uint8_t *out, uint64_t capacity, uint64_t gap, uint64_t *part_bytes, msnv_sample_stats *stats, uint64_t *contig_bases) {
-    if (n <= 0) return MSNV_OK;
-    if (n > 2048) return fail(MSNV_EINVAL, "msnv_records_deal_device: at most 2048 streams per call");
-    if (n_parts < 1 || n_parts > 254) return fail(MSNV_EINVAL, "msnv_records_deal_device: 1 .. 254 parts");
-    if (int rc = dev_set_device(ctx->device)) return rc;
-    hipStream_t st = (hipStream_t)ctx->stream;
-    const size_t S = (size_t)n;
-    std::vector<std::pair<void *, uint64_t>> slots;                // this call's work buffers
-    struct FreeSlots { std::vector<std::pair<void *, uint64_t>> &v; ~FreeSlots() { for (auto &b : v) if (b.first) dev_free(b.first); } } free_slots{slots};
-    BufPool pool{slots};
-    ScanResult SR;
-    if (int rc = stage_streams(st, ctx->device, pool, streams, n_bytes, S, on_device, SR)) return rc;
-    if (int rc = scan_records(st, pool, n_bytes, S, (size_t)n_contigs, SR)) return rc;
-    for (size_t s = 0; s < S; ++s) if (SR.bad_off[s] != ~0ull) return fail(MSNV_EFORMAT, "malformed BAM record at byte %llu of stream %zu", (unsigned long long)SR.bad_off[s], s);
-    const uint32_t NR = SR.NR;
-    const bool measure_only = out == nullptr;                      // statistics and aligned bases only (the split planner's pass over held streams)
-    uint64_t need = (uint64_t)n_parts * gap;
-    for (size_t s = 0; s < S; ++s) need += n_bytes[s];
-    if (!measure_only && capacity < need) return fail(MSNV_ECAPACITY, "msnv_records_deal_device: the output holds %llu bytes, up to %llu are needed", (unsigned long long)capacity, (unsigned long long)need);
-    for (size_t i = 0; i < S * (size_t)n_parts; ++i) part_bytes[i] = 0;
-    for (size_t s = 0; s < S; ++s) stats[s] = msnv_sample_stats{};
-    if (!NR) return MSNV_OK;
-    auto *d_owner = pool.take<int32_t>(std::max(1, n_contigs));
-    auto *d_key = pool.take<uint32_t>((uint64_t)NR + 1);
-    auto *d_size = pool.take<uint32_t>((uint64_t)NR + 1);
-    auto *d_idx = pool.take<uint32_t>((uint64_t)NR + 1);
-    auto *d_skey = pool.take<uint32_t>((uint64_t)NR + 1);
-    auto *d_order = pool.take<uint32_t>((uint64_t)NR + 1);
-    auto *d_ssize = pool.take<uint32_t>((uint64_t)NR + 1);
-    auto *d_pos = pool.take<unsigned long long>((uint64_t)NR + 1);
-    auto *d_acc = pool.take<DealAcc>(S * DEAL_COPIES);
-    auto *d_pb = pool.take<unsigned long long>((uint64_t)DEAL_COPIES * S * (uint64_t)n_parts + 1);
-    auto *d_cb = pool.take<unsigned long long>(std::max(1, n_contigs));
-    if (pool.rc) return pool.rc;
-    // (per-(stream, part) byte counts: copy c of stream s, part k at ((c * S) + s) * n_parts + k -- indexed below with the same formula)
-    const uint64_t pb_words = (uint64_t)DEAL_COPIES * S * (uint64_t)n_parts;
-    HIP_TRY(hipMemcpyAsync(d_owner, owner, (size_t)n_contigs * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(d_acc, 0, S * DEAL_COPIES * sizeof(DealAcc), st));
-    HIP_TRY(hipMemsetAsync(d_pb, 0, pb_words * 8, st));
-    if (contig_bases) HIP_TRY(hipMemsetAsync(d_cb, 0, (size_t)std::max(1, n_contigs) * 8, st));
-    hipLaunchKernelGGL(msnv_deal_measure, grid_for(NR, 256), dim3(256), 0, st, SR.raw, SR.d_recoff, SR.d_recsample, NR, SR.d_send, d_owner, n_contigs, n_parts, cov_min_mapq,
-                       d_key, d_size, d_acc, contig_bases ? d_cb : nullptr);
-    HIP_TRY(hipGetLastError());
-    if (!measure_only) {   // stable sort by owner (8 bits), then the places: exclusive scan of the sizes in that order
-        hipLaunchKernelGGL(msnv_deal_iota, grid_for(NR, 256), dim3(256), 0, st, d_idx, NR);
-        HIP_TRY(hipGetLastError());
-        Prim prim(st);
-        size_t tmp_need = 0;                                       // the sort's and the scan's storage before either is queued
-        if (int rc = prim.sort_pairs(d_key, d_skey, d_idx, d_order, (size_t)NR, 8u, &tmp_need)) return rc;
-        if (int rc = prim.exclusive(d_ssize, d_pos, 0ull, (size_t)NR, rocprim::plus<unsigned long long>(), &tmp_need)) return rc;
-        if (int rc = prim.bind(pool, tmp_need + 16)) return rc;
-        if (int rc = prim.sort_pairs(d_key, d_skey, d_idx, d_order, (size_t)NR, 8u)) return rc;
-        hipLaunchKernelGGL(msnv_deal_sizes, grid_for(NR, 256), dim3(256), 0, st, d_order, d_size, NR, d_ssize);
-        HIP_TRY(hipGetLastError());
-        if (int rc = prim.exclusive(d_ssize, d_pos, 0ull, (size_t)NR, rocprim::plus<unsigned long long>())) return rc;
-    }
-    if (!measure_only) hipLaunchKernelGGL(msnv_deal_copy, grid_for((uint64_t)NR * 16, 256), dim3(256), 0, st, SR.raw, SR.d_recoff, SR.d_recsample, d_order, d_skey, d_ssize, d_pos, NR, (uint32_t)n_parts, (uint32_t)S,
-                       (unsigned long long)gap, out, d_pb);
-    HIP_TRY(hipGetLastError());
-    std::vector<DealAcc> acc(S * DEAL_COPIES);
-    std::vector<unsigned long long> pb(pb_words);
-    HIP_TRY(hipMemcpyAsync(acc.data(), d_acc, acc.size() * sizeof(DealAcc), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(pb.data(), d_pb, pb_words * 8, hipMemcpyDeviceToHost, st));
-    std::vector<unsigned long long> cb((size_t)std::max(1, n_contigs), 0);
-    if (contig_bases) HIP_TRY(hipMemcpyAsync(cb.data(), d_cb, cb.size() * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (size_t s = 0; s < S; ++s) {
-        msnv_sample_stats &o = stats[s];
-        bool bad_tid = false, bad_owner = false, bad_rec = false;
-        for (uint32_t c = 0; c < DEAL_COPIES; ++c) {
-            const DealAcc &a = acc[s * DEAL_COPIES + c];
-            o.total_reads += a.total; o.unmapped += a.unmapped; o.zero_quality += a.zero_q; o.proper_pairs += a.proper; o.duplicates += a.dup; o.any_mapped |= a.any_mapped;
-            bad_tid |= (a.bad_tid & 1u) != 0; bad_rec |= (a.bad_tid & 2u) != 0; bad_owner |= a.bad_owner != 0;
-        }
-        if (bad_rec) return fail(MSNV_EFORMAT, "stream %zu: malformed BAM record (its name, CIGAR and bases do not fit its block_size)", s);
-        if (bad_tid) return fail(MSNV_EFORMAT, "stream %zu: a record refers to a contig beyond the header's %d", s, n_contigs);
-        if (bad_owner) return fail(MSNV_EINVAL, "stream %zu: a contig is owned by a part beyond %d", s, n_parts);
-    }
-    for (uint32_t c = 0; c < DEAL_COPIES; ++c) for (size_t s = 0; s < S; ++s) for (int k = 0; k < n_parts; ++k)
-        part_bytes[s * (size_t)n_parts + (size_t)k] += pb[((size_t)c * S + s) * (size_t)n_parts + (size_t)k];
-    if (contig_bases) for (int c = 0; c < n_contigs; ++c) contig_bases[c] += cb[(size_t)c];
-    return MSNV_OK;
-}
-
 int Prim::scan32(const uint32_t *in, uint32_t *out, size_t n, bool inclusive_) {
     return inclusive_ ? inclusive(in, out, n, rocprim::plus<uint32_t>()) : exclusive(in, out, 0u, n, rocprim::plus<uint32_t>());
 }
@@ -2900,7 +2046,7 @@ struct Round {
         hipLaunchKernelGGL(msnv_scan_sub2, grid_for(n_sub, 256), dim3(256), 0, st, raw, W.d_ss, (uint32_t)S, n_sub, sub_bytes, cap2, (int)NC, ctg, P, W.d_first, W.d_stop, W.d_cnt, W.d_delta, d_slots, d_info, W.d_fl);
         HIP_TRY(hipGetLastError());
         size_t need = 0;                                          // both scans' storage before either is queued
-        if (int rc = prim.inclusive(W.d_stop, W.d_stopmax, (size_t)n_sub, U64Max(), &need)) return rc;
+        if (int rc = W.scan_stops(prim, &need)) return rc;
         if (int rc = prim.exclusive(d_subcnt, d_subbase, SubCnt{}, (size_t)n_sub + 1, SubCntSum(), &need)) return rc;
         if (int rc = prim.room(need)) return rc;
         auto fix = [&]() {

@@ -1,5 +1,5 @@
 // metasnv_amd/csrc/devwork.h -- what the two device stages of a dataset share on the host side of a launch (HIP only; no kernel lives here):
-// devpack.hip, the per-read stage and the dealer, and devfin.hip, finalize's device side.
+// devpack.hip, the per-read stage (with devscan.hip, the record scan, and devdeal.hip, the dealer: devrec.h), and devfin.hip, finalize's device side.
 //   DpContig                      a contig as the kernels of both stages see it (DevPackTables::contigs)
 //   ld32 .. put_piece_lane        device helpers both stages' kernels inline: unaligned loads, a piece's stored bytes, its lane's share of the columns
 //   DevBuf, Timer, grid_for ...   an owned device allocation, HIP events around launches, the grid of n threads
@@ -174,10 +174,12 @@ struct Prim {
         HIP_TRY(rocprim::radix_sort_pairs(buf, need, kin, kout, vin, vout, n, 0u, end_bit, st));
         return MSNV_OK;
     }
-    // The forms most callers use, each defined out of line in ONE of the two files, so that its rocPRIM kernels are compiled once: scan32 and
-    // sort64 in devpack.hip (behind the dealer, in front of the round), scan64 and reserve_scan32 at the top of devfin.hip.  rocPRIM's kernels
-    // enter a code object in the order in which the compiler meets their first use; the templates above are instantiated wherever they are
-    // called, so devfin.hip's own exclusive scan of uint32_t (the chunk cut) is in both objects.
+    // The forms most callers use, each defined out of line in ONE file, so that its rocPRIM kernels are compiled once: scan32 and sort64 in
+    // devpack.hip (in front of the round), scan64 and reserve_scan32 at the top of devfin.hip.  rocPRIM's kernels enter a code object in the
+    // order in which the compiler meets their first use; the templates above are instantiated wherever they are called, so devfin.hip's own
+    // exclusive scan of uint32_t (the chunk cut) is in both objects.  Forms with one owner: the running maximum of the walks' ends
+    // (SubWalk::scan_stops, behind which both routes reach it) and scan_sub_walk's exclusive scan over uint32_t * in devscan.hip; the sort of
+    // uint32_t pairs and the scan of uint32_t into unsigned long long in devdeal.hip; the scans of RecCnt and SubCnt in devpack.hip.
     int scan32(const uint32_t *in, uint32_t *out, size_t n, bool inclusive_);
     int sort64(unsigned long long *kin, unsigned long long *kout, uint32_t *vin, uint32_t *vout, size_t n, unsigned end_bit);
     int scan64(const uint32_t *in, unsigned long long *out, size_t n);

@@ -419,7 +419,7 @@ bool rec_parse(const uint8_t *p, uint64_t avail, RecView &r) {
     // A CIGAR of more than 65535 operations travels in the auxiliary field CG:B,I behind a placeholder `<l_seq>S<ref_len>N`; htslib puts it
     // back when it reads the record (sam.c bam_tag2cigar, called by bam_read1 [EXT]), so samtools mpileup and qaCompute (sam_read1,
     // qaCompute.cpp:441) both walk the real one.  Same conditions here: mapped, first operation a soft clip of exactly l_seq bases, a CG
-    // field of type B,I / B,i with at least as many operations as the placeholder (devpack.hip: rec_load does the same on the device).
+    // field of type B,I / B,i with at least as many operations as the placeholder (devrec.h: rec_load does the same on the device).
     if (r.n_cigar > 0 && r.tid >= 0 && r.pos >= 0) {
         const uint32_t c0 = ld_u32(r.cigar);
         if ((c0 & 15u) == C_S && (int32_t)(c0 >> 4) == r.l_seq) {

@@ -38,7 +38,7 @@ struct PileupArgs {
     const PieceHdr *hdr8m;        // headers of the merged groups (pair index in bits 19+, absolute seq offset / 8)
     uint32_t        n_narrow;     // narrow32 launch: work items [0, n_narrow) are ordinary, the rest hold merged groups
     const uint8_t  *seq;
-    const uint8_t  *qual;         // ONE BIT per base, in the order of the seq column's nibbles: the base's quality is below the -Q cutoff (pack.cpp packs them at upload: the cutoff is a parameter of the dataset)
+    const uint8_t  *qual;         // ONE BIT per base, in the order of the seq column's nibbles: the base's quality is below the -Q cutoff (finalize.cpp packs them at upload: the cutoff is a parameter of the dataset)
     const uint64_t *s_read_base, *s_seq_base;
     const uint32_t *ref4;
     const TilePair *pairs;
@@ -120,7 +120,7 @@ __device__ __forceinline__ uint32_t lds_add_returning(uint32_t *p, const uint32_
     return old;
 }
 
-// Allele totals of a tile: 4 x TILE words, position-major, as narrow as the tile's summed depth bound allows (pack.cpp sets the
+// Allele totals of a tile: 4 x TILE words, position-major, as narrow as the tile's summed depth bound allows (finalize.cpp sets the
 // mode per tile; bits 1-2 of WorkItem::part_lo, GateTile::tot_mode): 0 = the four counts in the bytes of one word per position
 // (ONE atomic adds a pair's byte bin as it is), 1 = A | C << 16 and G | T << 16 in two words, 2 = four words.  No field can carry
 // into its neighbour: every total is at most the bound.
@@ -358,7 +358,7 @@ __global__ __launch_bounds__(W_NT) void msnv_pileup_tiles_wide(PileupArgs a) {
 //     the CIGAR and splits at tile boundaries): one code path, no clipping, no branches on data;
 //   * chunk descriptors are staged in LDS, headers are prefetched one chunk ahead, and all data
 //     loads of a 128-piece chunk are issued before the first one is consumed;
-//   * BQ cutoff: resolved by the host into ONE BIT per base (pack.cpp: pack_lowq; the cutoff is a parameter of the dataset) -- a
+//   * BQ cutoff: resolved by the host into ONE BIT per base (finalize.cpp: pack_lowq; the cutoff is a parameter of the dataset) -- a
 //     lane's 32 flags are one 8-byte load and a shift; match = nibble equality against the LDS-staged reference (host rewrites
 //     '=' codes); mismatch flags stay in the nibble domain (they are rare);
 //   * low-quality bases reach the byte bins 8 positions at a time: 8 flag bits become 8 bytes (two 24-bit multiplies: spread_bits)
@@ -411,12 +411,12 @@ struct alignas(16) NarrowLds {
 // cover position 512 w - 1, counted while they were classified), so the prefix sum never leaves the wavefront; allele
 // events are placed per wavefront too (one LDS reservation in the staging buffer, or -- staging full, noisy reads --
 // one reservation in the event list; the lanes write at their prefix-sum offsets).
-// MERGED: the bins hold a GROUP of shallow (sample, tile) pairs (pack.cpp: merged groups).  Their pieces went into the same
+// MERGED: the bins hold a GROUP of shallow (sample, tile) pairs (finalize.cpp: merged groups).  Their pieces went into the same
 // bins and nobody needs their per-sample bytes or allele events: the gather recomputes the few per-sample cells at called
 // positions -- coverage and allele counts -- from the pieces themselves (gather_merged_block), so the pass only adds the group to
 // the running totals and the allele totals, marks positions where one sample MIGHT hold >= min_snvs reads of an allele (the
 // calling rule then reads the summed per-sample records), and leaves every bin zero.
-// DA ("dense alleles", pack.cpp: allele planes): the pair's mismatch counts leave as four byte planes -- plain stores next to the coverage
+// DA ("dense alleles", finalize.cpp: allele planes): the pair's mismatch counts leave as four byte planes -- plain stores next to the coverage
 // bytes -- instead of one total atomic + one event per (position, allele): what a pass costs no longer depends on how noisy the reads are.
 // LATE (msnv_pileup_tiles_narrow32's ordinary items): the pass stages a position's allele WORD -- one 8-byte record {tile position | split << 11 |
 // sample << 12, word} per position that holds an allele -- and flush_alleles, where the workgroup meets with all 256 lanes anyway, makes the
@@ -1187,7 +1187,7 @@ __global__ __launch_bounds__(N_NT, MSNV_N32_WAVES) void msnv_pileup_tiles_narrow
     else if (blockIdx.x < a.n_fused_lo) { a.hdr8 = a.hdr8m; pileup_tiles_narrow32_body<true>(a, L); }
     else { a.hdr8 = a.hdr8m; pileup_tiles_narrow32_body<true, true>(a, L); }      // whole-tile items (the last ones; none when the pass runs unfused)
 }
-// The same launch for noisy reads (pack.cpp: allele planes): the ordinary work items write their pairs' allele counts as byte planes;
+// The same launch for noisy reads (finalize.cpp: allele planes): the ordinary work items write their pairs' allele counts as byte planes;
 // merged groups and whole-tile items keep their own bookkeeping (a group's few per-sample cells are recomputed from the pieces).
 __global__ __launch_bounds__(N_NT, MSNV_N32_WAVES) void msnv_pileup_tiles_narrow32_planes(PileupArgs a) {
     __shared__ NarrowLds L;
@@ -1196,7 +1196,7 @@ __global__ __launch_bounds__(N_NT, MSNV_N32_WAVES) void msnv_pileup_tiles_narrow
     else { a.hdr8 = a.hdr8m; pileup_tiles_narrow32_body<true, true>(a, L); }
 }
 // ------------------------------------------------------------------------------------------
-// msnv_pileup_tiles_dense: the narrow algorithm over the DENSE layout (dataset.h: BLK_*, pack.cpp: relayout_dense).
+// msnv_pileup_tiles_dense: the narrow algorithm over the DENSE layout (dataset.h: BLK_*, finalize.cpp: relayout_dense).
 // The pieces of a (sample, tile) pair form a stream of 32-base blocks without alignment padding; ONE lane owns ONE
 // block: 2 x 16 B of qualities + 16 B of bases, all 16-byte aligned and contiguous across the wavefront, and a 4-byte
 // descriptor (no LDS staging of headers).  A block holds bits [0, nA) of one piece and at most bits [sB, 32) of the
@@ -1205,7 +1205,7 @@ __global__ __launch_bounds__(N_NT, MSNV_N32_WAVES) void msnv_pileup_tiles_narrow
 // 32 positions of front padding.  Versus the per-piece layout: no padding bytes (-6 % HBM traffic) and no idle lanes
 // behind short pieces.  Measured (same box, pileup kernel, ms): reads of 50 bases: pieces 0.802 / dense 0.658;
 // 100: 0.670 / 0.677; 150: 0.618 / 0.672; 250: 0.567 / 0.645 -- the second segment costs what the padding saves at
-// 100 bases and more, so finalize picks this layout only for short pieces (pack.cpp: layout choice).
+// 100 bases and more, so finalize picks this layout only for short pieces (finalize.cpp: layout choice).
 // ------------------------------------------------------------------------------------------
 constexpr int D_PAD = 4;                       // 4 exception words / reference words = 32 positions of front padding
 struct DenseLds {
@@ -1368,7 +1368,7 @@ constexpr int GATE_PPT = TILE / GATE_NT;       // 8 consecutive positions per th
 static_assert(GATE_PPT == 8, "the gate kernel is written for 8 positions per thread (one site_bits word per 8 lanes)");
 
 // Per-sample records of the called positions are stored per TILE SLOT, not per sample: a tile's sites own rows of
-// tile_nslots[tile] cells -- one per sample that has reads in the tile (pack.cpp numbers them; the pairs of a split sample share
+// tile_nslots[tile] cells -- one per sample that has reads in the tile (finalize.cpp numbers them; the pairs of a split sample share
 // one) -- so a sparse cohort (BASELINE configs[3]: 500 samples, a species carried by a handful) does not pay 500 cells per
 // site.  The host expands to all samples when it fetches.  Cell of (site, slot): tile_cell_base[tile] + (site - first site of
 // the tile) * slots + slot; the gate kernel reserves a tile's cells with one 64-bit atomic (counters[6..7]).
@@ -1985,7 +1985,7 @@ constexpr uint32_t GW_ROW = 34;                // words per LDS row of 64 slots 
 // the many-site gather waited for (stores off: 1.90 -> 0.38 ms on the sigma = 2 cohort).  Here a block of 64 sites x 64 SLOTS is
 // assembled in LDS -- a wavefront reads one pair's bytes at the 64 sites and adds them to the pair's slot column, so the pairs of a
 // split sample sum up right there, no global atomic -- and written out as rows of cells, eight cells (16 bytes) per lane.  That needs
-// rows that start on 16 bytes: the tile's cell stride is a multiple of 8 (pack.cpp pads tiles of >= 16 slots) and so is its first
+// rows that start on 16 bytes: the tile's cell stride is a multiple of 8 (finalize.cpp pads tiles of >= 16 slots) and so is its first
 // cell (the gate kernels reserve in multiples of 8).  Slots of merged pairs (behind the others) belong to gather_merged_block: the
 // group of eight that straddles their first slot is written cell by cell.
 constexpr uint32_t GW_MAX_BLOCKS = 64;         // 64-slot blocks of a tile this form takes (<= 4096 slots; larger cohorts keep the two-byte form)
@@ -2044,7 +2044,7 @@ __device__ __forceinline__ void gather_cov_wide(const TailArgs &a, uint32_t *s_a
     }
 }
 
-// The same for the ALLELE ROWS of noisy reads (pack.cpp: allele planes): a pair's word A | C << 8 | G << 16 | T << 24 at a site goes
+// The same for the ALLELE ROWS of noisy reads (finalize.cpp: allele planes): a pair's word A | C << 8 | G << 16 | T << 24 at a site goes
 // into four u16 column blocks in LDS -- [site][allele][32 slots], one LDS atomic per allele the word holds (mostly one) -- and every
 // allele column is written as rows of 32 slots, eight cells (16 bytes) per lane.  One load per (site, pair) for all four alleles.
 constexpr uint32_t GA_SLOTS = 32;              // slots per LDS block of the allele gather
@@ -2260,7 +2260,7 @@ __device__ __forceinline__ void scatter_events_block(const TailArgs &a, const ui
             for (uint32_t u = 0; u < U; ++u) {
                 unsigned long long row;
                 if ((u && i + u * stride >= n_k) || !cell_at(e[u].x, w[u], row0[u], ns[u], row)) continue;
-                // events carry the SLOT of their sample in the tile (pack.cpp), one event per (site, pair, allele).  Only the pairs of a SPLIT
+                // events carry the SLOT of their sample in the tile (finalize.cpp), one event per (site, pair, allele).  Only the pairs of a SPLIT
                 // sample meet in a cell: their tile (NSLOTS_SPLIT) adds with memory-side atomics.  In every other tile the cell -- zero since
                 // the gate kernel -- has this one writer: a plain two-byte store, nothing for the memory side to read, modify and write
                 uint16_t *dst = &a.ncol[ncol_base((e[u].y >> 16) & 3u, a.cells.cap_cells) + row + (e[u].y >> 18)];
@@ -2535,7 +2535,7 @@ __device__ __forceinline__ uint32_t row_sum16(uint32_t x) {
 }
 
 // WIDE = false: the difference array holds two positions per word (16-bit halves biased by 0x8000, so that a half never borrows
-// from or carries into its neighbour) -- good for pairs of at most 32 767 intervals, which pack.cpp guarantees for the work items it hands
+// from or carries into its neighbour) -- good for pairs of at most 32 767 intervals, which finalize.cpp guarantees for the work items it hands
 // to this variant; WIDE = true: one word per position, any number of intervals (a pile-up of tens of thousands of reads with one
 // start: a handful of work items at most).
 template <bool WIDE>
@@ -2573,7 +2573,7 @@ __global__ __launch_bounds__(C_NT) void msnv_coverage_tiles(const Pair32 *iv, co
     };
     const uint32_t lim = (uint32_t)min(max((int)tl - 32 * lane, 0), 32);      // scanned positions among my 32 (i < contig length)
     const uint32_t lim_mask = lim >= 32u ? 0xffffffffu : (1u << lim) - 1u;
-    // A work item holds at most COV_PW pairs (pack.cpp): ALL their descriptors are loaded up front, and the first 256 intervals of
+    // A work item holds at most COV_PW pairs (finalize.cpp): ALL their descriptors are loaded up front, and the first 256 intervals of
     // a pair while the pair before it is worked on (the kernel waited on one dependent descriptor -> intervals chain per pair, and
     // then on the intervals beyond the first 128).  A lane takes FOUR CONSECUTIVE intervals (two 16-byte loads): the 64 lanes of one
     // scatter step are then four intervals apart in the sorted list and seldom meet on an LDS word (64 consecutive intervals at 10x
@@ -2586,7 +2586,7 @@ __global__ __launch_bounds__(C_NT) void msnv_coverage_tiles(const Pair32 *iv, co
         prs[j] = kk < w.pair_hi ? pairs[kk] : TilePair{0, 0, 0, 0, 0, 0, 0, 0};
     }
     auto load4 = [&](const Pair32 *v, const uint32_t first, const uint32_t n, uint4 &a, uint4 &b) {
-        // lanes without an interval load the {0, 0} entries behind the last one (pack.cpp; they touch nothing): a load under a lane
+        // lanes without an interval load the {0, 0} entries behind the last one (finalize.cpp; they touch nothing): a load under a lane
         // condition gets its own wait right behind it, and the round trips then run one after the other instead of under the work
         // on the pair before.  The entries past a pair's last interval are somebody else's: scatter4 leaves them alone
         const Pair32 *p = first < n ? v + first : iv + n_iv;
@@ -2702,7 +2702,7 @@ __global__ __launch_bounds__(C_NT) void msnv_coverage_tiles(const Pair32 *iv, co
         uint32_t idx = 1u + bin;
         if (lane == 4) { val = ws; idx = 0u; }
         if ((k < 4u || lane == 4) && val && idx <= (uint32_t)max_cov + 1u) {
-            // one accumulator row per (sample, contig) that HAS intervals (pack.cpp numbers them; TilePair::max_depth carries the row): a
+            // one accumulator row per (sample, contig) that HAS intervals (finalize.cpp numbers them; TilePair::max_depth carries the row): a
             // 500-sample cohort over a million contigs would need 100 GB as a dense [sample][contig] table, and holds a few million rows
             unsigned long long *dst = acc + ((uint64_t)(w.tile % n_copies) * n_rows + pr.max_depth) * (1 + COV_BINS);
             atomicAdd(&dst[idx], (unsigned long long)(long long)val);
@@ -3035,7 +3035,7 @@ int dev_run_coverage(DeviceCols &d, int max_cov, void *stream_, msnv_run_stats *
     HIP_TRY(hipEventRecord(ev[0], st));
     HIP_TRY(hipMemsetAsync(d.cov_acc, 0, (uint64_t)d.cov_copies * std::max<uint64_t>(1, d.n_cov_rows) * (1 + COV_BINS) * sizeof(unsigned long long), st));
     if (d.n_cov_work) {
-        // work items that hold a pair of more than 32 767 intervals are the last n_cov_work_wide of the list (pack.cpp)
+        // work items that hold a pair of more than 32 767 intervals are the last n_cov_work_wide of the list (finalize.cpp)
         const uint32_t n_narrow = d.n_cov_work - d.n_cov_work_wide;
         if (n_narrow) hipLaunchKernelGGL(msnv_coverage_tiles<false>, dim3(n_narrow), dim3(C_NT), 0, st, d.cov_iv, d.cov_pairs, d.cov_work,
                                          d.tile_len, d.cov_acc, (uint32_t)d.n_cov_rows, max_cov, d.cov_copies, d.n_cov_iv);

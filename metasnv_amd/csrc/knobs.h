@@ -58,7 +58,7 @@ inline bool feed_trace() { static const bool on = first("MSNV_FEED_TRACE") == '1
 // Per call.  Profiling only.
 inline char stage_free() { const char c = first("MSNV_STAGE_FREE"); return c == 's' || c == 'n' ? c : '\0'; }
 
-// ---------------------------------------------------------------------------------- the per-read stage (api.cpp, bamfeed.cpp, devpack.hip)
+// ---------------------------------------------------------------------------------- the per-read stage (api.cpp, bamfeed.cpp, devscan.hip, devpack.hip)
 // MSNV_PACK=host: BAM records are packed by the host stage (pack.cpp) although the dataset has a context.  Per call (tests/test_gpu_devpack.py, bench.py).
 inline bool pack_on_host() { return first("MSNV_PACK") == 'h'; }
 // MSNV_PACK_ROUND_MB (6144, at least 1): record megabytes per round of the device pack.  Per call (tests/test_gpu_devpack.py).

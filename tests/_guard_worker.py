@@ -20,7 +20,7 @@ CASES = {
                          dict(min_coverage=3, calling_threshold=3)),
     "noisy_planes": (dict(n_species=2, contig_len=12000, n_samples=12, mean_cov=12.0, error_rate=0.04, seed=76), dict()),
     "many_sites": (dict(n_species=2, contig_len=8000, n_samples=20, mean_cov=10.0, snv_density=0.3, seed=77), dict(min_coverage=2, calling_threshold=2)),
-    # round 4: overlapping mates, aux tags, SEQ `*` and CG-tag CIGARs through the device pack's kernels (devpack.hip: msnv_ovl_*, rec_load)
+    # round 4: overlapping mates, aux tags, SEQ `*` and CG-tag CIGARs through the device pack's kernels (devpack.hip: msnv_ovl_*; devrec.h: rec_load)
     "paired_aux_records": (dict(n_species=2, contig_len=15000, n_samples=10, mean_cov=14.0, frac_paired=0.6, frac_aux=0.5, frac_noseq=0.05, read_len=90, seed=78), dict()),
     # ... and BAM FILES through the resident device inflate (inflate_k.hip: msnv_inflate_blocks + msnv_crc_blocks) into the device pack
     "bam_files_device_inflate": (dict(n_species=2, contig_len=25000, n_samples=6, mean_cov=12.0, frac_paired=0.3, seed=79), dict()),

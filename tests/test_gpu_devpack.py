@@ -316,7 +316,7 @@ def test_errors_carry_the_host_stage_codes():
 
 def test_record_scan_across_segment_seams():
     """The record chain is walked piecewise with GUESSED entry points checked at every seam -- round 5: a lane per sub-segment, seams checked
-    on the device, wrong guesses walked again there (devpack.hip: msnv_scan_sub2 / msnv_scan_fix2, and msnv_scan_sub / msnv_scan_fix under MSNV_FRONT=careful; MSNV_SCAN_SUB bytes); the careful form (msnv_scan_segments, MSNV_SCAN=segments,
+    on the device, wrong guesses walked again there (devpack.hip: msnv_scan_sub2 / msnv_scan_fix2, and devscan.hip: msnv_scan_sub / msnv_scan_fix under MSNV_FRONT=careful; MSNV_SCAN_SUB bytes); the careful form (msnv_scan_segments, MSNV_SCAN=segments,
     MSNV_SCAN_SEG_KB) repairs wrong guesses on the host and takes over when the quick form meets a chain that breaks.  Tiny pieces put a seam into almost
     every record (and records longer than a sub-segment next to it); a read name that holds plausible record headers makes guesses go wrong."""
     syn, samples = synth_case(n_species=2, contig_len=6000, n_samples=4, mean_cov=9.0, snv_density=0.02, seed=25)

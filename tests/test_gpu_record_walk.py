@@ -1,4 +1,4 @@
-"""The front of the device pack (csrc/devpack.hip: msnv_scan_sub2 / msnv_scan_sub, msnv_scan_check, msnv_scan_fix / fix2, msnv_sub_bounds,
+"""The front of the device pack (csrc/devpack.hip, csrc/devscan.hip: msnv_scan_sub2 / msnv_scan_sub, msnv_scan_check, msnv_scan_fix / fix2, msnv_sub_bounds,
 msnv_scan_write2 / msnv_scan_write, msnv_scan_segments behind them) on HAND-PLACED streams: every record's offset is chosen against the
 seams of the walk (multiples of MSNV_SCAN_SUB from a stream's first byte), the slot limits, the boundary search and the order in which
 errors are found.  The reference is the host stage's sequential walk (csrc/pack.cpp, MSNV_PACK=host): every column, the per-sample

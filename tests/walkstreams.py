@@ -1,5 +1,5 @@
 """Hand-placed record streams for tests/test_gpu_record_walk.py: every record's offset is chosen against the seams of the device pack's
-record walk (csrc/devpack.hip: a stream is cut into sub-segments of MSNV_SCAN_SUB bytes counted from its first byte).  A builder places
+record walk (csrc/devrec.h: a stream is cut into sub-segments of MSNV_SCAN_SUB bytes counted from its first byte).  A builder places
 the records, then asserts in plain Python the property its case is named for -- a fixture that drifts fails here, on the CPU, before
 anything touches the device (tests/test_record_walk_fixtures.py runs every builder)."""
 import random
