@@ -464,6 +464,53 @@ int msnv_hclust_tasks(msnv_ctx *ctx, int32_t n, const double *dist, int64_t n_ta
 int msnv_heatmap_order(int32_t m, const int32_t *merge, const double *weights, int32_t *order);
 int msnv_heatmap_file(msnv_ctx *ctx, const char *dist_path, const char *dir, const char *species, int64_t result[8], double *ms_kernel);
 
+/* The numbers behind the two SNV-frequency plots of subpopr's per-species report (src/subpopr/R/snvFreqPlot.R:1-113, drawn by defineSubpopulations,
+ * profileSubpops.R:152-158; shown by detailedSpeciesReport.rmd:176-212), and the band the clustering's sample selection applies
+ * (clustering.R:43-51, computeSnvFreqStats.R:31-46).  Restated from reading the R code; no R was run (unpinned).
+ *
+ * msnv_freq_curves -- the array form.  rows: host memory, row-major [n_pos][n_samples], on the percent scale, NaN for a cell without coverage.
+ * n_samples >= 1, n_pos >= 0 (else MSNV_EINVAL; n_pos = 0 gives all zeros); a NaN band is MSNV_EINVAL.  counts: uint64 [n_samples][102]:
+ *   [k], k = 0..49   cells <= k                      [50 + k]   cells >= 100 - k
+ *   [100]            covered (non-NaN) cells         [101]      cells < strict_lo or > strict_hi
+ * A cell that is neither NaN nor within [0, 100] is MSNV_EDOMAIN (R would count a stray negative cell as low: a divergence).  The counts are
+ * integers summed with integer atomics: they do not depend on the grid, on the slab cuts (MSNV_STAGE_SLAB_ROWS) or on the order of the blocks.
+ * The table goes to the device in row slabs, so it may be larger than device memory.  *ms_kernel: the kernel's time by events, summed over the slabs.
+ * msnv_freq_curves_geometry: the rows and the sample columns one block of the kernel covers (for tests that sit on those seams).
+ *
+ * msnv_freq_bands -- computeSnvFreqStats (computeSnvFreqStats.R:1-24) on the same arrays, the kernel msnv_cluster_file counts with.  counts: uint64
+ * [n_samples][4]: cells < 20 or > 80, < 10 or > 90, < 5 or > 95, covered cells.  No domain check.  The yardstick profiles/snvfreq_time.py holds
+ * msnv_freq_curves against.
+ *
+ * msnv_snvfreq_file -- the stage on files.  freq_path: the *.filtered.freq table on metaSNV's [0, 1] scale (-1 and NA: no coverage); a cell above 1 is
+ * MSNV_EDOMAIN with the reference's message (profileSubpops.R:145-147), any other cell outside [0, 1] MSNV_EDOMAIN; cells are then multiplied by 100
+ * in double.  opts NULL: the defaults; a value outside [0, 1] or a reserved field that is not 0: MSNV_EINVAL.  With x = max_prop_reads_non_homog, y =
+ * min_prop_homog_snv, n the covered cells of a sample and N the rows, every quotient one double division of two integers (n = 0: NaN):
+ *   cutoffIndex = 1..50, k = cutoffIndex - 1:  propLow = #(cell <= k) / n, propHigh = #(cell >= 100 - k) / n, propSuffCov = n / N, propPass = propLow +
+ *     propHigh; sampleUsedForMedoidDefn = NA unless (double)cutoffIndex == x * 100 + 1 as computed in double (0.07: index 8; 0.29: 29.999999999999996,
+ *     no index), there propPass > y, NA when propPass is NaN
+ *   h = x > 0.5 ? 1 - x : x, t = h * 100, hi = max(100 - t, t), lo = min(100 - t, t):  propHomogStrict = #(cell < lo | cell > hi) / n;
+ *     selectedForDiscovery = propHomogStrict >= y (NaN: FALSE) -- the rule computeClusters selects samples by; it differs from the plot's in all
+ *     three comparisons
+ * Written into out_dir/snvFreqPlots/ (both created when missing), as write.table(sep = '\t', quote = F, row.names = F) prints them: doubles with
+ * %.15g, NaN, logicals TRUE / FALSE / NA (our own files: the reference keeps these numbers as pixels only; the histogram's bins are not written):
+ *   <species>_snvFreq_cutoffs.tab   cutoffIndex, sampleID, propLow, propHigh, propSuffCov, propPass, sampleUsedForMedoidDefn; expand.grid order:
+ *                                   samples in column order, cutoffIndex 1..50 within a sample
+ *   <species>_snvFreq_fixed.tab     sampleID, propPass, propSuffCov, sampleUsedForMedoidDefn (the first file's row at the matching cutoffIndex; NA, NA,
+ *                                   NA when none matches), propHomogStrict, selectedForDiscovery; one row per sample
+ * result: [0] samples [1] rows [2] the matching cutoffIndex or 0 [3] samples with sampleUsedForMedoidDefn TRUE [4] samples selectedForDiscovery
+ * [5] samples without a covered cell [6], [7] 0. */
+typedef struct {
+    double  max_prop_reads_non_homog;   /* subpopr -x fixReadThreshold, 0.1; 0..1                     */
+    double  min_prop_homog_snv;         /* subpopr -y fixSnvThreshold, 0.8; 0..1                      */
+    int32_t reserved[2];                /* 0                                                          */
+} msnv_snvfreq_opts;
+void msnv_snvfreq_opts_default(msnv_snvfreq_opts *o);
+void msnv_freq_curves_geometry(int32_t *rows_per_block, int32_t *columns_per_block);
+int msnv_freq_curves(msnv_ctx *ctx, const double *rows, int64_t n_pos, int32_t n_samples, double strict_lo, double strict_hi, uint64_t *counts, double *ms_kernel);
+int msnv_freq_bands(msnv_ctx *ctx, const double *rows, int64_t n_pos, int32_t n_samples, uint64_t *counts, double *ms_kernel);
+int msnv_snvfreq_file(msnv_ctx *ctx, const char *freq_path, const char *species, const char *out_dir, const msnv_snvfreq_opts *opts, int64_t result[8],
+                      double *ms_kernel);
+
 /* subpopr's writeGenotypeFreqs -> computeUniquePosPerCluster (src/subpopr/R/writeGenotypeFreqs.R:2-112, :195-277): which SNVs tell one
  * subspecies from every other.  Restated from reading the R code; no R was run (unpinned).
  *

@@ -89,6 +89,10 @@ class MembStabOpts(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("boot_iters", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SnvFreqOpts(C.Structure):
+    _fields_ = [("max_prop_reads_non_homog", C.c_double), ("min_prop_homog_snv", C.c_double), ("reserved", C.c_int32 * 2)]
+
+
 class RefDesc(C.Structure):
     _fields_ = [("n_contigs", C.c_int32), ("names", C.POINTER(C.c_char_p)), ("lengths", C.POINTER(C.c_int64)),
                 ("seqs", C.POINTER(C.c_char_p)), ("seq_lens", C.POINTER(C.c_int64))]
@@ -256,6 +260,11 @@ SYMBOLS = [
                                     P(C.c_double)]),
     ("msnv_heatmap_order", C.c_int, [C.c_int32, P(C.c_int32), P(C.c_double), P(C.c_int32)]),
     ("msnv_heatmap_file", C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_char_p, P(C.c_int64), P(C.c_double)]),
+    ("msnv_snvfreq_opts_default", None, [P(SnvFreqOpts)]),
+    ("msnv_freq_curves_geometry", None, [P(C.c_int32), P(C.c_int32)]),
+    ("msnv_freq_curves", C.c_int, [_vp, P(C.c_double), C.c_int64, C.c_int32, C.c_double, C.c_double, P(C.c_uint64), P(C.c_double)]),
+    ("msnv_freq_bands", C.c_int, [_vp, P(C.c_double), C.c_int64, C.c_int32, P(C.c_uint64), P(C.c_double)]),
+    ("msnv_snvfreq_file", C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_char_p, P(SnvFreqOpts), P(C.c_int64), P(C.c_double)]),
     ("msnv_genotype_rows", C.c_int, [_vp, C.c_uint64, C.c_int32, P(C.c_double), P(C.c_int32), C.c_int32, C.c_double, P(C.c_uint32), P(C.c_uint32), P(C.c_uint64),
                                      P(C.c_double)]),
     ("msnv_genotype_file", C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_double, P(C.c_int64), P(C.c_double)]),

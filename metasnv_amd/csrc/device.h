@@ -286,6 +286,11 @@ int dev_cluster_boot(const ClusterDev &c, uint64_t n_sets, const uint32_t *m, ui
                      int32_t *clus0, int32_t *best, double *ms_kernel);
 int dev_pred_strength(const ClusterDev &c, uint64_t n_splits, const uint32_t *len, const uint32_t *k, const int32_t *idx, void *stream, double *prederr, double *ms_kernel);
 int dev_freq_bands(const double *rows, uint64_t n_pos, uint32_t n_samples, void *stream, uint64_t *counts, double *ms_kernel);   // counts[sample][4]
+// snvfreq.cpp + snvfreq_k.hip: subpopr's snvFreqPlot.  A block of msnv_freq_curves_k is one wavefront of FREQ_CURVE_LANES sample columns over
+// FREQ_CURVE_ROWS rows.  counts[sample][102] as msnv_freq_curves lays them out; *outside = 1 when a cell is neither NaN nor within [0, 100]
+constexpr uint32_t FREQ_CURVE_LANES = 64, FREQ_CURVE_ROWS = 1024;
+int dev_freq_curves(const double *rows, uint64_t n_pos, uint32_t n_samples, double strict_lo, double strict_hi, void *stream, uint64_t *counts, uint32_t *outside,
+                    double *ms_kernel);
 // cluster.cpp, shared with pcoa.cpp: the checks of a distance matrix (include/msnv.h), the reader of <species>.filtered.mann.dist (r_form: the
 // header as write.table prints it), and removeOutliersFromDistMatrixMinDissim(3 sd, at most 5): the samples that stay, in matrix order
 int check_matrix(const char *who, int64_t n, const double *d);

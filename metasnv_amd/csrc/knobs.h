@@ -202,8 +202,8 @@ inline uint64_t mptext_batch_bytes() { return (uint64_t)std::max<long long>(1, i
 inline int mptext_round_samples() { return std::max(1, int_or("MSNV_MPTEXT_ROUND", 64)); }
 
 // ---------------------------------------------------------------------------------- the file stages' row slabs (stagedev.h)
-// MSNV_STAGE_SLAB_ROWS=n (0: no cap; a negative value is 0): a row slab of dev_genotype_rows, dev_freq_bands and dev_gene_corr holds at
-// most n rows, so that a table of a few rows walks several slabs.  Per call (tests/test_gpu_stage_slabs.py).
+// MSNV_STAGE_SLAB_ROWS=n (0: no cap; a negative value is 0): a row slab of dev_genotype_rows, dev_freq_bands, dev_freq_curves and dev_gene_corr
+// holds at most n rows, so that a table of a few rows walks several slabs.  Per call (tests/test_gpu_stage_slabs.py, tests/test_gpu_snvfreq.py).
 inline uint64_t stage_slab_rows() { return (uint64_t)std::max<long long>(0, i64_or("MSNV_STAGE_SLAB_ROWS", 0)); }
 
 // ---------------------------------------------------------------------------------- the hclust batches (hclust.cpp)

@@ -25,6 +25,10 @@
       <species>.filtered.mann.dist (+ <dir>/<species>_mann_distMatrixUsedForClustMedoidDefns.txt, _clustering.tab)  ->  our own files
       <dir>/<species>_mann_{hclust,heatmap}_{all,discovery}.tab
 
+  snvFreqSubpops.py <freq_file> <outDir> [--species S] [--fix-read-threshold X] [--fix-snv-threshold Y]
+      (src/subpopr/R/snvFreqPlot.R snvFreqPlot, the first step of defineSubpopulations, with computeClusters' strict band beside it)
+      <species>.filtered.freq  ->  our own files <outDir>/snvFreqPlots/<species>_snvFreq_{cutoffs,fixed}.tab
+
   clusterMembStability.py <species> <dir> [--k N] [--ps-cut X] [--seed N] [--boot N]
       (src/subpopr/R/clusteringStability.R getClusMembStability and getClusMembStabScore; <dir> = clusterSubpops.py's outDir or its noClustering/)
       <dir>/<species>_mann_distMatrixUsedForClustMedoidDefns.txt (+ _PS_values.tab, _clusNumStability.tab)  ->  <dir>/<species>_mann_{clusMembStability.tab,
@@ -52,9 +56,9 @@
 getGenotypingSNVSubset.py and writeSubpopAbund.py are text filters (native, no device work) and summariseClustering.py reads and writes small
 tables in Python; the frequencies of convertSNVtoAlleleFreq.py, the correlations, every PAM run of clusterSubpops.py and clusterMembStability.py
 with the matching of the re-clustered subsets, pcoaSubpops.py's centring and eigendecomposition, heatmapSubpops.py's agglomerations,
-writeGenotypeFreqs.py's walk over the frequency table and profileSubpops.py's counts and medians per sample are computed on the GPU
-(msnv_snv_allele_freq, msnv_gene_corr, msnv_corr_stats, msnv_pam_tasks, msnv_pred_strength, msnv_cluster_boot, msnv_pcoa, msnv_hclust_tasks,
-msnv_genotype_rows, msnv_subpop_profile_columns) and there is no CPU fallback for them."""
+snvFreqSubpops.py's class counts per sample, writeGenotypeFreqs.py's walk over the frequency table and profileSubpops.py's counts and medians per
+sample are computed on the GPU (msnv_snv_allele_freq, msnv_gene_corr, msnv_corr_stats, msnv_pam_tasks, msnv_pred_strength, msnv_cluster_boot,
+msnv_pcoa, msnv_hclust_tasks, msnv_freq_curves, msnv_genotype_rows, msnv_subpop_profile_columns) and there is no CPU fallback for them."""
 import ctypes as C
 import glob
 import os
@@ -460,6 +464,93 @@ def heatmap_subpops_main(argv=None):                           # detailedSpecies
         ctx.close()
     print("Species " + species + ": " + str(res["n_samples"]) + " samples ordered (average linkage)"
           + ("; no discovery subset" if res["status"] == core._lib.HEATMAP_NO_DISCOVERY else "; " + str(res["n_discovery"]) + " of the discovery subset (complete linkage)"))
+    return res
+
+
+def freq_curves_geometry():
+    """(rows, sample columns) that one block of msnv_freq_curves_k covers."""
+    from ._lib import lib
+    rows, cols = C.c_int32(), C.c_int32()
+    lib.msnv_freq_curves_geometry(C.byref(rows), C.byref(cols))
+    return rows.value, cols.value
+
+
+def freq_curves(ctx, rows, strict_lo=10.0, strict_hi=90.0):
+    """The cumulative counts behind snvFreqPlot of rows [n_pos x S] on the percent scale, NaN for no coverage (msnv_freq_curves).  Returns a dict:
+    low [S, 50] (cells <= k), high [S, 50] (cells >= 100 - k), covered [S], strict [S] (cells < strict_lo or > strict_hi), all uint64, and ms_kernel."""
+    import numpy as np
+    from ._lib import lib, check
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    if rows.ndim != 2:
+        raise ValueError("freq_curves: rows must be a positions x samples table")
+    n_pos, S = rows.shape
+    counts = np.zeros((max(S, 1), 102), dtype=np.uint64)
+    ms = C.c_double()
+    check(lib.msnv_freq_curves(ctx._h, _dptr(rows) if rows.size else None, n_pos, S, float(strict_lo), float(strict_hi), counts.ctypes.data_as(C.POINTER(C.c_uint64)),
+                               C.byref(ms)))
+    counts = counts[:S]
+    return {"low": counts[:, :50].copy(), "high": counts[:, 50:100].copy(), "covered": counts[:, 100].copy(), "strict": counts[:, 101].copy(), "ms_kernel": ms.value}
+
+
+def freq_bands(ctx, rows):
+    """computeSnvFreqStats' three fixed bands of the same table (msnv_freq_bands): uint64 [S, 4] = cells outside 20/80, 10/90, 5/95 and covered
+    cells; and the kernel's ms."""
+    import numpy as np
+    from ._lib import lib, check
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    if rows.ndim != 2:
+        raise ValueError("freq_bands: rows must be a positions x samples table")
+    n_pos, S = rows.shape
+    counts = np.zeros((max(S, 1), 4), dtype=np.uint64)
+    ms = C.c_double()
+    check(lib.msnv_freq_bands(ctx._h, _dptr(rows) if rows.size else None, n_pos, S, counts.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(ms)))
+    return counts[:S], ms.value
+
+
+def snv_freq_file(ctx, freq_path, out_dir, species=None, max_prop_reads_non_homog=0.1, min_prop_homog_snv=0.8, reserved=(0, 0)):
+    """The stage on files (msnv_snvfreq_file): writes <species>_snvFreq_cutoffs.tab and <species>_snvFreq_fixed.tab into out_dir/snvFreqPlots/.
+    Returns a dict: n_samples, n_rows, cutoff_index (0: no cutoff matches -x), n_used_for_medoid_defn (the plot's rule), n_selected (the
+    clustering's rule), n_uncovered, ms_kernel."""
+    from ._lib import lib, check, SnvFreqOpts
+    if species is None:
+        species = os.path.basename(freq_path).split(".")[0]
+    opts = SnvFreqOpts()
+    lib.msnv_snvfreq_opts_default(C.byref(opts))
+    opts.max_prop_reads_non_homog, opts.min_prop_homog_snv = float(max_prop_reads_non_homog), float(min_prop_homog_snv)
+    opts.reserved[0], opts.reserved[1] = int(reserved[0]), int(reserved[1])
+    res = (C.c_int64 * 8)()
+    ms = C.c_double()
+    check(lib.msnv_snvfreq_file(ctx._h, freq_path.encode(), species.encode(), out_dir.encode(), C.byref(opts), res, C.byref(ms)))
+    return {"n_samples": res[0], "n_rows": res[1], "cutoff_index": res[2], "n_used_for_medoid_defn": res[3], "n_selected": res[4], "n_uncovered": res[5],
+            "ms_kernel": ms.value}
+
+
+def snv_freq_subpops_main(argv=None):                          # snvFreqPlot.R:1-113; profileSubpops.R:152-158
+    import argparse
+    ap = argparse.ArgumentParser(prog="snvFreqSubpops.py", description="Write the numbers behind subpopr's SNV-frequency plots (snvFreqPlot) on the GPU.")
+    ap.add_argument("freq_file", metavar="FREQ_FILE", help="<species>.filtered.freq of metaSNV_Filtering.py")
+    ap.add_argument("out_dir", metavar="OUTDIR", help="the files go to OUTDIR/snvFreqPlots/")
+    ap.add_argument("--species", default=None, metavar="S", help="default: the freq file's name up to its first '.'")
+    ap.add_argument("--fix-read-threshold", type=float, default=0.1, metavar="X", help="subpopr -x: how far from 0 or 100 %% of reads an allele may be and count as fixed (0.1)")
+    ap.add_argument("--fix-snv-threshold", type=float, default=0.8, metavar="Y", help="subpopr -y: the share of a sample's SNV positions that must be fixed (0.8)")
+    a = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    species = a.species if a.species is not None else os.path.basename(a.freq_file).split(".")[0]
+    if not os.path.exists(a.freq_file):
+        sys.exit("ERROR: missing input file: " + a.freq_file)
+    from . import core
+    try:
+        ctx = core.Context(0)
+    except core._lib.MsnvError as e:
+        sys.exit("\nERROR:  {}\n\nSOLUTION: run on a node with an AMD Instinct GPU (there is no CPU fallback)\n".format(e))
+    try:
+        res = snv_freq_file(ctx, a.freq_file, a.out_dir, species=species, max_prop_reads_non_homog=a.fix_read_threshold, min_prop_homog_snv=a.fix_snv_threshold)
+    except core._lib.MsnvError as e:
+        sys.exit("ERROR: {}".format(e))
+    finally:
+        ctx.close()
+    print("Species " + species + ": " + str(res["n_samples"]) + " samples, " + str(res["n_rows"]) + " rows; " + str(res["n_used_for_medoid_defn"]) + " pass the plot's rule ("
+          + ("cutoffIndex " + str(res["cutoff_index"]) if res["cutoff_index"] else "no cutoffIndex matches " + repr(a.fix_read_threshold)) + "), "
+          + str(res["n_selected"]) + " pass the selection rule")
     return res
 
 
