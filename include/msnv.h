@@ -759,8 +759,9 @@ int  msnv_dataset_info_get(const msnv_dataset *ds, msnv_dataset_info *out);
  * launched and the careful route took over (a sample that needs the sequential edits, more far-reaching reads than the list holds), [16] samples
  * whose depth cap / token limit ran as kernels (round 6; [11] counts the ones the host pre-pass still takes: MSNV_PREPASS=host, a template with
  * more alignments than the overlap kernel's slots, far-reaching reads), [17] 1 when finalize adopted a single round's column buffer as the
- * dataset's columns instead of copying it (devpack_place_columns; MSNV_NO_ADOPT=1 copies). */
-#define MSNV_PACK_STATS 18
+ * dataset's columns instead of copying it (devpack_place_columns; MSNV_NO_ADOPT=1 copies), [18] blocks of 64 records that msnv_emit_block
+ * handed to msnv_emit_block_slow (every block under MSNV_EMIT=slow). */
+#define MSNV_PACK_STATS 19
 int  msnv_dataset_pack_stats(const msnv_dataset *ds, double *out, int32_t n);
 /* Inspection hook: the bytes of one device column / index table of a finalized dataset ("hdr", "hdr4", "hdr8m", "blk", "seq", "qual",
  * "s_read_base", "s_seq_base", "ref4", "pairs", "work", "chunks", "cov_iv", "cov_pairs", "cov_work"; the other tables of the tile index:

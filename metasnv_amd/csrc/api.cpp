@@ -538,7 +538,7 @@ extern "C" int msnv_dataset_pack_stats(const msnv_dataset *ds, double *out, int3
     const DevPackTables &t = ds->dp;
     const double v[MSNV_PACK_STATS] = {t.ms_scan, t.ms_measure, t.ms_depth, t.ms_emit, t.ms_sort, t.wall_upload_s, t.wall_download_s, t.wall_prepass_s,
                                        (double)t.raw_bytes, (double)t.n_records, (double)t.n_pieces, (double)t.n_prepass_samples, (double)t.n_scan_redone, (double)t.n_deep_runs_split, (double)t.n_dense_samples, (double)t.n_quick_redone, (double)t.n_device_edit_samples,
-                                       (double)t.n_columns_adopted};
+                                       (double)t.n_columns_adopted, (double)t.n_emit_slow_blocks};
     for (int i = 0; i < n; ++i) out[i] = i < MSNV_PACK_STATS ? v[i] : 0.0;
     return MSNV_OK;
 }

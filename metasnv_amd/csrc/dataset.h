@@ -179,6 +179,7 @@ struct DevPackTables {
     uint64_t  raw_bytes = 0, n_records = 0, n_pieces = 0, n_prepass_samples = 0, n_scan_redone = 0, n_deep_runs_split = 0, n_dense_samples = 0;
     uint64_t  n_device_edit_samples = 0;     // samples whose depth cap / token limit ran as kernels (msnv_cap_reads, msnv_token_cut) instead of the host pre-pass
     uint64_t  n_quick_redone = 0;    // rounds the quick route handed to the careful one though their walk stood: launched and taken back (a sample needs the host pre-pass, far-reaching reads), or left at the totals (a place beyond its slot field, two contigs overhanging in one sub-segment)
+    uint64_t  n_emit_slow_blocks = 0; // blocks of 64 records msnv_emit_block handed to msnv_emit_block_slow, over the rounds (read with a round's accumulators: devpack_sync_pending)
     uint64_t  n_columns_adopted = 0; // finalize took a single round's column buffer as the dataset's columns (devpack_place_columns)
 };
 

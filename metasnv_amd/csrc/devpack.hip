@@ -1781,6 +1781,9 @@ int devpack_sync_pending(msnv_dataset &ds) {
         SampleCols &sc = ds.samples[T.pending.first + s];
         sc.mm_sampled_bases = a[s].mm_bases; sc.mm_sampled = a[s].mm;
     }
+    uint32_t n_slow = 0;
+    memcpy(&n_slow, a + T.pending.n, 4);                           // (behind the round's accumulators: launch_emit)
+    T.n_emit_slow_blocks += n_slow;
     return MSNV_OK;
 }
 void devpack_ctx_release(msnv_ctx *ctx) {
@@ -2394,7 +2397,7 @@ struct Round {
         auto up8 = [](uint64_t v) { return (v + 15) & ~15ull; };
         o_acc = up8(((uint64_t)ds.samples.size() + 16) * 4); o_sum = o_acc + up8(b_acc); o_pb = o_sum + up8(b_sum); o_rb = o_pb + up8(b_pb); o_misc = o_rb + up8(b_rb); o_runs = o_misc + 16; o_grp = o_runs + up8(b_runs);
         const uint64_t o_end = o_grp + up8(b_grp);
-        if (int rc = pin_ensure(ds, std::max<uint64_t>(o_end, S * sizeof(DpAcc)))) return rc;
+        if (int rc = pin_ensure(ds, std::max<uint64_t>(o_end, S * sizeof(DpAcc) + 16))) return rc;      // (+ 16: the emit kernels' count of slow blocks behind the accumulators)
         pinb = static_cast<uint8_t *>(T.pin) + T.pin_cap / 2;
         if (quick) {
             const bool depth_on_main = knob::depth_on_main();
@@ -2436,6 +2439,7 @@ struct Round {
         // and little of what finalize does first needs the bases or the headers.  What they leave for the host (the mismatch sample of every
         // sample, their time) comes through pinned memory and is taken by devpack_sync_pending.
         HIP_TRY(hipMemcpy2DAsync(T.pin, sizeof(DpAcc), d_acc, sizeof(DpAcc) * ACC_COPIES, sizeof(DpAcc), S, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(static_cast<uint8_t *>(T.pin) + S * sizeof(DpAcc), d_slow, 4, hipMemcpyDeviceToHost, st));      // (how many blocks msnv_emit_block left to msnv_emit_block_slow: same event, no wait of its own)
         HIP_TRY(hipEventRecord((hipEvent_t)T.pending.ev1, st));
         T.pending.active = true; T.pending.first = first; T.pending.n = S;
         return MSNV_OK;
