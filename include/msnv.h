@@ -322,6 +322,19 @@ int msnv_pred_strength(msnv_ctx *ctx, int32_t n, const double *dist, int32_t k_m
                        double *prederr, double *mean_pred, int32_t *optimalk, double *ms_kernel);
 int msnv_cluster_file(msnv_ctx *ctx, const char *dist_path, const char *freq_path, const char *species, const char *out_dir,
                       const msnv_cluster_opts *opts, int64_t result[8], double *ms_kernel);
+/* msnv_cluster_file_ex -- msnv_cluster_file with subpopr's -x / -y (clustering.R:43-51, computeSnvFreqStats.R:31-46).  In double, as R computes
+ * them: h = x > 0.5 ? 1 - x : x; t = h * 100; hi = max(100 - t, t); lo = min(100 - t, t).  A sample is kept when #(cell < lo | cell > hi) / #covered
+ * >= y on the table's cells as they are read (the kernel and strict count of msnv_freq_curves; 0 / 0 is not kept; a cell that is neither -1 nor
+ * within [0, 100] is MSNV_EDOMAIN).  y <= 0 disables the filter: every sample left after outlier removal is used.  <species>_freq_composition.tab
+ * keeps its three fixed columns.  x or y outside [0, 1], or NaN, is MSNV_EINVAL before any file is read.  filter NULL = the defaults, 0.1 and 0.8:
+ * msnv_cluster_file is this call with filter NULL. */
+typedef struct {
+    double max_prop_reads_non_homog;   /* subpopr -x, 0.1 */
+    double min_prop_homog_snv;         /* subpopr -y, 0.8 */
+} msnv_cluster_filter;
+void msnv_cluster_filter_default(msnv_cluster_filter *f);
+int msnv_cluster_file_ex(msnv_ctx *ctx, const char *dist_path, const char *freq_path, const char *species, const char *out_dir,
+                         const msnv_cluster_opts *opts, const msnv_cluster_filter *filter, int64_t result[8], double *ms_kernel);
 
 /* The stability of each cluster's membership: getClusMembStability -> clusterAssignSubsample -> getClusMembStabScore
  * (src/subpopr/R/clusteringStability.R:129-148, :170-176, :224-237), i.e. fpc::clusterboot(bootmethod = "subset", clustermethod = claraCBI,

@@ -85,6 +85,10 @@ class ClusterOpts(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("ps_cut", C.c_double), ("stability_iters", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ClusterFilter(C.Structure):
+    _fields_ = [("max_prop_reads_non_homog", C.c_double), ("min_prop_homog_snv", C.c_double)]
+
+
 class MembStabOpts(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("boot_iters", C.c_int32), ("reserved", C.c_int32)]
 
@@ -250,6 +254,8 @@ SYMBOLS = [
     ("msnv_pred_strength", C.c_int, [_vp, C.c_int32, P(C.c_double), C.c_int32, C.c_int32, P(C.c_int32), C.c_double, P(C.c_double), P(C.c_double), P(C.c_int32),
                                      P(C.c_double)]),
     ("msnv_cluster_file", C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, P(ClusterOpts), P(C.c_int64), P(C.c_double)]),
+    ("msnv_cluster_filter_default", None, [P(ClusterFilter)]),
+    ("msnv_cluster_file_ex", C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, P(ClusterOpts), P(ClusterFilter), P(C.c_int64), P(C.c_double)]),
     ("msnv_membstab_opts_default", None, [P(MembStabOpts)]),
     ("msnv_cluster_boot", C.c_int, [_vp, C.c_int32, P(C.c_double), C.c_int32, P(C.c_int32), C.c_int32, C.c_int64, P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_int32),
                                     P(C.c_int32), P(C.c_int32), P(C.c_double)]),

@@ -3,7 +3,7 @@
 //
 //   msnv_pam_tasks       cluster::pam of many index subsets of one distance matrix
 //   msnv_pred_strength   predStrengthCustom (:152-216) for given permutations, with mean.pred and optimalk
-//   msnv_cluster_file    the stage: outliers (filterSamples.R:42-72), SNV frequency composition (computeSnvFreqStats.R:1-24, :139-147), Gmax
+//   msnv_cluster_file(_ex)  the stage: outliers (filterSamples.R:42-72), SNV frequency composition (computeSnvFreqStats.R:1-24, :139-147), Gmax
 //                        (:218-236), prediction strength, PAM, the stability of the cluster number (:359-381, clusteringStability.R:6-24,
 //                        :201-221), small clusters (:383-400), the files
 //   msnv_cluster_boot    fpc::clusterboot(bootmethod = "subset") on given subsets: PAM of the members and of every subset, each original cluster's
@@ -12,8 +12,9 @@
 //                        matrix msnv_cluster_file wrote: the two stability files (at the end of this file)
 // What is on the host: reading and writing, the outlier rule (n numbers), the draws (include/msnv.h), R's mean() of each k's M values and the
 // stability score.  Every PAM run, classification and pair count is on the device; there is no CPU fallback.
-// Divergences: rmNAfromDistMatrix is not built (an NA cell is MSNV_EFORMAT); R's generator is not reproduced; when Gmax <= 1
-// no _PS_values.tab is written (the reference hands write.table a NULL there); a stability group that holds an NA does not count as constant.
+// Divergences: an NA cell is MSNV_EFORMAT here (rmNAfromDistMatrix is the driver's, metasnv_amd/subpopr_run.py); R's generator
+// is not reproduced; when Gmax <= 1 no _PS_values.tab is written (the reference hands write.table a NULL there); a stability group that holds an NA
+// does not count as constant.
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -67,7 +68,7 @@ int read_dist(const char *path, std::vector<std::string> &names, std::vector<dou
         for (size_t c = 1; c < f.size(); ++c) {
             char *e = nullptr;
             const double v = f[c].empty() || f[c] == "NA" ? 0.0 : strtod(f[c].c_str(), &e);
-            if (!e || e != f[c].c_str() + f[c].size()) { rc = fail(MSNV_EFORMAT, "%s:%llu: cell '%s' is not a number (NA and empty cells are refused: rmNAfromDistMatrix is not built)", path, (unsigned long long)lineno, f[c].c_str()); break; }
+            if (!e || e != f[c].c_str() + f[c].size()) { rc = fail(MSNV_EFORMAT, "%s:%llu: cell '%s' is not a number (NA and empty cells are refused: metaSNV_subpopr.py removes them before the stages, rmNAfromDistMatrix)", path, (unsigned long long)lineno, f[c].c_str()); break; }
             d.push_back(v);
         }
         ++n_rows;
@@ -246,8 +247,15 @@ extern "C" int msnv_pred_strength(msnv_ctx *ctx, int32_t n, const double *dist, 
     return MSNV_OK;
 }
 
+extern "C" void msnv_cluster_filter_default(msnv_cluster_filter *f) { if (f) *f = msnv_cluster_filter{0.1, 0.8}; }
+
 extern "C" int msnv_cluster_file(msnv_ctx *ctx, const char *dist_path, const char *freq_path, const char *species, const char *out_dir, const msnv_cluster_opts *opts,
                                  int64_t result[8], double *ms_kernel) {
+    return msnv_cluster_file_ex(ctx, dist_path, freq_path, species, out_dir, opts, nullptr, result, ms_kernel);
+}
+
+extern "C" int msnv_cluster_file_ex(msnv_ctx *ctx, const char *dist_path, const char *freq_path, const char *species, const char *out_dir, const msnv_cluster_opts *opts,
+                                    const msnv_cluster_filter *filter, int64_t result[8], double *ms_kernel) {
     clear_error();
     if (!ctx || !dist_path || !species || !out_dir) return fail(MSNV_EINVAL, "msnv_cluster_file: NULL argument");
     msnv_cluster_opts o;
@@ -255,6 +263,12 @@ extern "C" int msnv_cluster_file(msnv_ctx *ctx, const char *dist_path, const cha
     if (opts) o = *opts;
     if (o.reserved != 0 || o.stability_iters < 1 || o.stability_iters > 1024 || !(o.ps_cut >= 0.0 && o.ps_cut < 1.0))
         return fail(MSNV_EINVAL, "msnv_cluster_file: ps_cut = %g, stability_iters = %d, reserved = %d (0 <= ps_cut < 1, 1..1024 iterations, reserved 0)", o.ps_cut, o.stability_iters, o.reserved);
+    msnv_cluster_filter flt;
+    msnv_cluster_filter_default(&flt);
+    if (filter) flt = *filter;
+    if (!(flt.max_prop_reads_non_homog >= 0.0 && flt.max_prop_reads_non_homog <= 1.0) || !(flt.min_prop_homog_snv >= 0.0 && flt.min_prop_homog_snv <= 1.0))
+        return fail(MSNV_EINVAL, "msnv_cluster_file_ex: max_prop_reads_non_homog = %g, min_prop_homog_snv = %g (0 <= proportion <= 1)", flt.max_prop_reads_non_homog,
+                    flt.min_prop_homog_snv);
     if (result) for (int i = 0; i < 8; ++i) result[i] = 0;
     if (ms_kernel) *ms_kernel = 0;
     double ms = 0;
@@ -274,7 +288,7 @@ extern "C" int msnv_cluster_file(msnv_ctx *ctx, const char *dist_path, const cha
     if (result) result[3] = (int64_t)(n_all - qc.size());
     if (qc.size() < 2) return fail(MSNV_EDOMAIN, "%s: %zu samples left after outlier removal", dist_path, qc.size());
 
-    // ---- computeSnvFreqStats + onlyKeepSamplesWithDistinctFreqs(minPropHomogSnvAllelesPerSample = 0.8)
+    // ---- computeSnvFreqStats, computeSnvFreqStatsThreshold(-x) + onlyKeepSamplesWithDistinctFreqs(-y) (clustering.R:41-79)
     std::vector<int32_t> used = qc;                                    // distForMedoids
     std::string composition;
     if (freq_path) {
@@ -284,23 +298,38 @@ extern "C" int msnv_cluster_file(msnv_ctx *ctx, const char *dist_path, const cha
         if (int rc = read_freq(freq_path, fnames, nullptr, rows, n_pos)) return rc;
         const size_t S = fnames.size();
         if (S == 0) return fail(MSNV_EFORMAT, "%s: no sample column", freq_path);
+        if (S > 0x7fffffffull) return fail(MSNV_EDOMAIN, "%s: %zu sample columns", freq_path, S);
         std::vector<uint64_t> cnt(S * 4, 0);
         if (int rc = dev_freq_bands(rows.data(), n_pos, (uint32_t)S, ctx->stream, cnt.data(), &ms)) return rc;
-        std::unordered_map<std::string, int32_t> in_qc;
-        for (int32_t i : qc) in_qc.emplace(names[i], i);
         composition = "freq_data_sample_20_80\tfreq_data_sample_10_90\tfreq_data_sample_5_95\n";
-        used.clear();
         for (size_t s = 0; s < S; ++s) {
             const double valid = (double)cnt[s * 4 + 3];
             composition += fnames[s];
             for (int b = 0; b < 3; ++b) { composition.push_back('\t'); r_double((double)cnt[s * 4 + b] / valid, composition); }
             composition.push_back('\n');
-            auto it = in_qc.find(fnames[s]);
-            if ((double)cnt[s * 4 + 1] / valid >= 0.8 && it != in_qc.end()) { used.push_back(it->second); in_qc.erase(it); }
+        }
+        // computeSnvFreqStatsThreshold's band of -x: the strict count of msnv_freq_curves_k ([101] of a sample's 102, covered cells in [100])
+        const bool filtering = flt.min_prop_homog_snv > 0.0;           // clustering.R:47: doFilterSamplesByAlleleDist & minPropHomogSnvAllelesPerSample > 0
+        if (filtering) {
+            double lo = 0, hi = 0;
+            strict_band(flt.max_prop_reads_non_homog, lo, hi);
+            std::vector<uint64_t> curves(S * 102, 0);
+            if (n_pos) {
+                uint32_t outside = 0;
+                if (int rc = dev_freq_curves(rows.data(), n_pos, (uint32_t)S, lo, hi, ctx->stream, curves.data(), &outside, &ms)) return rc;
+                if (outside) return fail(MSNV_EDOMAIN, "%s: a cell is neither -1 nor within [0, 100]", freq_path);
+            }
+            std::unordered_map<std::string, int32_t> in_qc;
+            for (int32_t i : qc) in_qc.emplace(names[i], i);
+            used.clear();
+            for (size_t s = 0; s < S; ++s) {
+                auto it = in_qc.find(fnames[s]);
+                if ((double)curves[s * 102 + 101] / (double)curves[s * 102 + 100] >= flt.min_prop_homog_snv && it != in_qc.end()) { used.push_back(it->second); in_qc.erase(it); }
+            }
         }
         int status = -1;
-        if (used.size() < 6) status = MSNV_CLUSTER_TOO_FEW;
-        else {
+        if (filtering && used.size() < 6) status = MSNV_CLUSTER_TOO_FEW;
+        else if (filtering) {
             bool all_equal = true;
             const double v0 = d[(size_t)used[1] * n_all + used[0]];
             for (size_t a = 1; a < used.size() && all_equal; ++a)

@@ -291,6 +291,8 @@ int dev_freq_bands(const double *rows, uint64_t n_pos, uint32_t n_samples, void 
 constexpr uint32_t FREQ_CURVE_LANES = 64, FREQ_CURVE_ROWS = 1024;
 int dev_freq_curves(const double *rows, uint64_t n_pos, uint32_t n_samples, double strict_lo, double strict_hi, void *stream, uint64_t *counts, uint32_t *outside,
                     double *ms_kernel);
+// snvfreq.cpp, shared with cluster.cpp: the strict band (lo, hi) on the percent scale of subpopr's -x, folded at 0.5
+void strict_band(double max_prop_reads_non_homog, double &lo, double &hi);
 // cluster.cpp, shared with pcoa.cpp: the checks of a distance matrix (include/msnv.h), the reader of <species>.filtered.mann.dist (r_form: the
 // header as write.table prints it), and removeOutliersFromDistMatrixMinDissim(3 sd, at most 5): the samples that stay, in matrix order
 int check_matrix(const char *who, int64_t n, const double *d);

@@ -18,6 +18,14 @@
 
 namespace msnv {
 
+// computeSnvFreqStatsThreshold's band of maxPropReadsNonHomog (clustering.R:43-51, computeSnvFreqStats.R:31-46), in double as R computes it; shared
+// with msnv_cluster_file_ex (device.h)
+void strict_band(double max_prop_reads_non_homog, double &lo, double &hi) {
+    const double h = max_prop_reads_non_homog > 0.5 ? 1.0 - max_prop_reads_non_homog : max_prop_reads_non_homog;      // clustering.R:43-44
+    const double c = h * 100.0;
+    hi = std::max(100.0 - c, c); lo = std::min(100.0 - c, c);
+}
+
 namespace {
 
 struct Thresholds {
@@ -30,9 +38,7 @@ Thresholds thresholds(double max_prop_reads_non_homog) {
     const double index = max_prop_reads_non_homog * 100.0 + 1.0;      // snvFreqPlot.R:6, :13: two roundings
     for (int32_t k = 1; k <= 50; ++k)
         if ((double)k == index) t.match = k;
-    const double h = max_prop_reads_non_homog > 0.5 ? 1.0 - max_prop_reads_non_homog : max_prop_reads_non_homog;      // clustering.R:43-44
-    const double c = h * 100.0;
-    t.hi = std::max(100.0 - c, c); t.lo = std::min(100.0 - c, c);
+    strict_band(max_prop_reads_non_homog, t.lo, t.hi);
     return t;
 }
 

@@ -270,10 +270,12 @@ CLUSTER_REASONS = {                                            # what computeClu
 }
 
 
-def cluster_file(ctx, dist_path, out_dir, species=None, freq_path=None, seed=None, ps_cut=None, stability_iters=None):
-    """The stage on files (msnv_cluster_file).  Returns a dict: status (_lib.CLUSTER_*), n_clusters, n_samples, n_outliers, stability_score
-    (1 Low, 2 Medium, 3 High, 0 not rated), optimalk, n_pam_tasks, ms_kernel."""
-    from ._lib import lib, check, ClusterOpts
+def cluster_file(ctx, dist_path, out_dir, species=None, freq_path=None, seed=None, ps_cut=None, stability_iters=None, max_prop_reads_non_homog=None,
+                 min_prop_homog_snv=None):
+    """The stage on files (msnv_cluster_file_ex; subpopr's -x / -y as max_prop_reads_non_homog / min_prop_homog_snv, None: 0.1 / 0.8).  Returns a
+    dict: status (_lib.CLUSTER_*), n_clusters, n_samples, n_outliers, stability_score (1 Low, 2 Medium, 3 High, 0 not rated), optimalk,
+    n_pam_tasks, ms_kernel."""
+    from ._lib import lib, check, ClusterOpts, ClusterFilter
     if species is None:
         species = os.path.basename(dist_path).split(".")[0]
     o = ClusterOpts()
@@ -286,8 +288,16 @@ def cluster_file(ctx, dist_path, out_dir, species=None, freq_path=None, seed=Non
         o.stability_iters = int(stability_iters)
     res = (C.c_int64 * 8)()
     ms = C.c_double()
-    check(lib.msnv_cluster_file(ctx._h, dist_path.encode(), None if freq_path is None else freq_path.encode(), species.encode(), out_dir.encode(),
-                                C.byref(o), res, C.byref(ms)))
+    flt = None
+    if max_prop_reads_non_homog is not None or min_prop_homog_snv is not None:
+        flt = ClusterFilter()
+        lib.msnv_cluster_filter_default(C.byref(flt))
+        if max_prop_reads_non_homog is not None:
+            flt.max_prop_reads_non_homog = float(max_prop_reads_non_homog)
+        if min_prop_homog_snv is not None:
+            flt.min_prop_homog_snv = float(min_prop_homog_snv)
+    check(lib.msnv_cluster_file_ex(ctx._h, dist_path.encode(), None if freq_path is None else freq_path.encode(), species.encode(), out_dir.encode(),
+                                   C.byref(o), None if flt is None else C.byref(flt), res, C.byref(ms)))
     return {"status": res[0], "n_clusters": res[1], "n_samples": res[2], "n_outliers": res[3], "stability_score": res[4], "optimalk": res[5],
             "n_pam_tasks": res[6], "ms_kernel": ms.value}
 
