@@ -873,6 +873,9 @@ typedef struct {
     const char *out_specific_path;  /* OUT.specific; needed with -x        */
 } msnv_cov_ex_args;
 int  msnv_coverage_ex(msnv_ctx *ctx, const msnv_cov_ex_args *args);
+/* ... over the reads that `qaCompute -a` keeps (the subsampler below: word from msnv_subsample_seed_word, frac of -a's argument); frac <= 0:
+ * msnv_coverage_ex, or msnv_coverage when none of -m -p -x is asked for. */
+int  msnv_coverage_sub(msnv_ctx *ctx, const msnv_cov_ex_args *args, uint32_t word, double frac);
 
 /* Formats the last run as called_SNPs / indiv_called (call_vC.cpp:641-667).
  * ann_path / fasta_path feed the codon annotation (call_vC.cpp:604-633) and may be NULL. */
@@ -947,6 +950,39 @@ int  msnv_records_deal_device(msnv_ctx *ctx, const uint8_t *const *streams, cons
  * the weight of the reference's split rule, genome length x coverage = aligned bases (src/createOptimumSplit.py:46-50), which
  * the N-rank driver takes from its first round of decoded BAMs before it fixes the contig owners. */
 int  msnv_records_contig_bases(const uint8_t *records, uint64_t n_bytes, int32_t n_contigs, uint64_t *bases);
+
+/* ------------------------------------------------------------------------------------
+ * Reads subsampled by the hash of their name: `qaCompute -a SEED.FRAC` (qaCompute.cpp:319-325, :454-458), the rule of
+ * `samtools view -s`.  A read is kept iff (wang(x31(name) ^ word) & 0xffffff) < ceil(frac * 2^24); mates share a name and so a
+ * fate; a dropped read exists nowhere behind this stage (no statistic, no coverage, no pileup); the kept ones keep order and bytes.
+ * x31 / wang are khash.h's string and integer hashes as restated in csrc/devsub.h (unpinned against a real qaCompute: DESIGN.md
+ * section 7).  The name is the record's read_name up to its first NUL, at most l_read_name bytes.
+ * frac <= 0 everywhere below means NO subsampling: nothing is launched, read or copied; frac >= 1 keeps every read.
+ * ------------------------------------------------------------------------------------ */
+/* word = 0 for seed 0, else libc's srand(seed); rand() (1 -> 1804289383 with glibc).  seed < 0 or > 4294967295: MSNV_EINVAL (the
+ * reference truncates such a seed). */
+int  msnv_subsample_seed_word(int64_t seed, uint32_t *word);
+/* The rule for ONE name (NUL-terminated): 1 = kept, 0 = dropped (no error code; NULL is dropped).  frac <= 0 drops every name here --
+ * the callers below never ask then. */
+int  msnv_subsample_keep(const char *name, uint32_t word, double frac);
+/* One stream on a host thread: the kept records to out (room for n_bytes bytes), *out_bytes of them; counts = {kept, dropped}.
+ * frac <= 0: out is not touched, *out_bytes = n_bytes, counts = {0, 0}.  A malformed chain of records is MSNV_EFORMAT. */
+int  msnv_records_subsample(const uint8_t *records, uint64_t n_bytes, uint32_t word, double frac, uint8_t *out, uint64_t *out_bytes, uint64_t counts[2]);
+/* n streams (n <= 2048; host memory, or device memory when on_device != 0) ON THE DEVICE (csrc/devsub.hip): the kept records of stream i
+ * go to out + out_off[i], out_bytes[i] of them; counts[2 * i] = kept, counts[2 * i + 1] = dropped.  out: DEVICE memory of `capacity`
+ * bytes; stream i is given ((n_bytes[i] + 31) & ~15) bytes of it, whatever is kept -- it starts on 16 bytes and at least 16 readable bytes
+ * lie behind it -- and a capacity below the sum of these is MSNV_EINVAL before anything is launched.  ms_kernel (may be NULL): kernel
+ * milliseconds of the record scan and the stage.  frac <= 0: out is not touched, out_off[i] = UINT64_MAX (the stream is its own output),
+ * out_bytes[i] = n_bytes[i], counts 0, *ms_kernel = 0.  A malformed chain of records is MSNV_EFORMAT. */
+int  msnv_records_subsample_device(msnv_ctx *ctx, const uint8_t *const *streams, const uint64_t *n_bytes, int32_t n, int32_t on_device, uint32_t word, double frac,
+                                   uint8_t *out, uint64_t capacity, uint64_t *out_off, uint64_t *out_bytes, uint64_t *counts, double *ms_kernel);
+/* Every stream handed to the dataset from now on passes through the subsampler before it is packed: msnv_dataset_add_sample_records[_many],
+ * msnv_dataset_add_sample_bam[s], msnv_dataset_add_sample_records_device, the staged and the synthetic samples -- on the device, into a buffer
+ * of the round's own, unless the dataset packs on host threads (MSNV_PACK=host, no context).  msnv_dataset_sample_stats counts the kept reads.
+ * Set BEFORE the first sample is added (later: MSNV_EINVAL); frac <= 0 switches it off.  While it is set,
+ * msnv_dataset_add_sample_records_resident, msnv_dataset_deal_bams_device and msnv_dataset_inflate_bams_device refuse with MSNV_EINVAL and
+ * leave the dataset as it was. */
+int  msnv_dataset_set_subsample(msnv_dataset *ds, uint32_t word, double frac);
 /* Statistics of sample `sample_idx` as counted while it was packed (only over the records this dataset was given). */
 int  msnv_dataset_sample_stats(const msnv_dataset *ds, int32_t sample_idx, msnv_sample_stats *out);
 /* Accumulators of the last msnv_coverage_run: acc[n_samples][n_contigs][MSNV_COV_WORDS], zeros for contigs outside the shard. */

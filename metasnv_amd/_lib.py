@@ -207,6 +207,13 @@ SYMBOLS = [
     ("msnv_dataset_inflate_bams_device", C.c_int, [_vp, P(C.c_char_p), C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, P(C.c_uint64), P(C.c_uint64), P(SampleStats), P(C.c_uint64)]),
     ("msnv_records_deal_device", C.c_int, [_vp, P(C.c_void_p), P(C.c_uint64), C.c_int32, C.c_int32, P(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64,
                                            P(C.c_uint64), P(SampleStats), P(C.c_uint64)]),
+    ("msnv_subsample_seed_word", C.c_int, [C.c_int64, P(C.c_uint32)]),
+    ("msnv_subsample_keep", C.c_int, [C.c_char_p, C.c_uint32, C.c_double]),
+    ("msnv_records_subsample", C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_double, _vp, P(C.c_uint64), P(C.c_uint64)]),
+    ("msnv_records_subsample_device", C.c_int, [_vp, P(C.c_void_p), P(C.c_uint64), C.c_int32, C.c_int32, C.c_uint32, C.c_double, C.c_void_p, C.c_uint64,
+                                                P(C.c_uint64), P(C.c_uint64), P(C.c_uint64), P(C.c_double)]),
+    ("msnv_dataset_set_subsample", C.c_int, [_vp, C.c_uint32, C.c_double]),
+    ("msnv_coverage_sub", C.c_int, [_vp, P(CovExArgs), C.c_uint32, C.c_double]),
     ("msnv_coverage_run", C.c_int, [_vp, P(RunStats)]),
     ("msnv_fused_run", C.c_int, [_vp, P(RunStats), P(RunStats)]),
     ("msnv_write_coverage", C.c_int, [_vp, C.c_int32, C.c_char_p, C.c_char_p]),

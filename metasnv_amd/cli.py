@@ -170,7 +170,8 @@ def resident_run(args, ctx, rank, world):
     try:
         res = parallel.resident_project_run(ctx, bams[0], args.ref_db, bams, params, batch=max(1, args.threads),
                                             want_coverage=not args.use_prev_cov, ann_path=args.db_ann or None, after_coverage=between_passes,
-                                            species_weight=species_weight, inflate_after_context=getattr(args, "inflate_after_context", False))
+                                            species_weight=species_weight, inflate_after_context=getattr(args, "inflate_after_context", False),
+                                            subsample=args.subsample_parsed)
     except core._lib.MsnvError as e:
         sys.stderr.write(str(e) + "\n")
         sys.stderr.write("SNV calling failed")
@@ -216,6 +217,10 @@ def build_parser():                                             # metaSNV.py:225
                    help='Use "cov/" and "outputs.all_cov.tab" and "outputs.all_perc.tab" data produced by previous metaSNV run')
     p.add_argument('--min_pos_cov', metavar='INT', default=4, type=int, help='minimum coverage (mapped reads) per position for snpCall.')
     p.add_argument('--min_pos_snvs', metavar='INT', default=4, type=int, help='minimum number of non-reference nucleotides per position for snpCall.')
+    # ours, not the reference's: what `samtools view -s` on every BAM would do first, without the second copy of the cohort
+    p.add_argument('--subsample', metavar='SEED.FRAC', default=None,
+                   help='Subsample the reads of every BAM by the hash of their name before coverage and calling, as `qaCompute -a` / `samtools view -s` '
+                        'do: integer part = seed, fraction = share of the reads kept (42.25: seed 42, a quarter). One rank only.')
     return p
 
 
@@ -232,8 +237,23 @@ def main(argv=None):
     if args.threads > 1 and args.n_splits == 1:                 # metaSNV.py:275-276
         args.n_splits = args.threads
 
+    args.subsample_parsed = None
+    if args.subsample is not None:
+        from . import core
+        try:
+            seed, frac = core.parse_subsample(args.subsample)
+            core.subsample_seed_word(seed)
+        except (ValueError, core._lib.MsnvError) as e:
+            sys.stderr.write("\nERROR:	--subsample {}: {}\n\n".format(args.subsample, e))
+            sys.exit(1)
+        if frac > 0:                                             # (a fraction of 0 -- `--subsample 1` -- subsamples nothing, as in qaCompute)
+            args.subsample_parsed = (seed, frac)
+
     from . import parallel
     rank, world, local = parallel.init_from_env()
+    if args.subsample_parsed is not None and world > 1:
+        sys.stderr.write("\nERROR:	--subsample is not built for more than one rank\n\n")
+        parallel.abort(1)
     if rank == 0 and os.path.exists(args.project_dir) and not args.print_commands and not args.use_prev_cov:
         sys.stderr.write("Project directory '{}' already exists\n\n\n".format(args.project_dir))
         parallel.abort(1)

@@ -138,6 +138,7 @@ def _cstr_array(strings):
 
 class Dataset:
     """Packed read columns of one shard, resident in HBM after finalize()."""
+    subsample = None                                           # (seed, frac) once set_subsample has switched the read subsampler on
 
     def __init__(self, ctx, names, lengths, seqs=None, params=None):
         self.ctx = ctx
@@ -194,6 +195,12 @@ class Dataset:
     def set_contig_mask(self, mask):
         m = (C.c_uint8 * len(mask))(*[1 if x else 0 for x in mask])
         check(lib.msnv_dataset_set_contig_mask(self._h, m, len(mask)))
+
+    def set_subsample(self, seed, frac):
+        """Every stream added from now on loses the reads `qaCompute -a SEED.FRAC` drops before it is packed (msnv_dataset_set_subsample):
+        before the first sample; frac <= 0 switches it off.  `subsample` = (seed, frac) while it is on, else None."""
+        check(lib.msnv_dataset_set_subsample(self._h, subsample_seed_word(seed), float(frac)))
+        self.subsample = (int(seed), float(frac)) if frac > 0 else None
 
     def add_sample_records(self, records):
         """records: bytes / numpy uint8 array of raw BAM alignment records."""
@@ -559,6 +566,84 @@ def deal_records_device(ctx, streams, contig_owner, n_parts, out_ptr, capacity, 
     parts = np.array(list(pb)[:n * n_parts], dtype=np.int64).reshape(n, n_parts) if n else np.zeros((0, n_parts), np.int64)
     stats = np.array([[getattr(st[i], k) for k in STATS_FIELDS] for i in range(n)], dtype=np.uint32).reshape(n, len(STATS_FIELDS))
     return parts, stats
+
+
+def subsample_seed_word(seed):
+    """The word the read names' hashes are mixed with (msnv_subsample_seed_word): 0 for seed 0, else libc's srand(seed); rand()."""
+    w = C.c_uint32()
+    check(lib.msnv_subsample_seed_word(int(seed), C.byref(w)))
+    return w.value
+
+
+def parse_subsample(text):
+    """`-a` / `--subsample` SEED.FRAC as qaCompute.cpp:319-325 reads it -- strtol, then strtod of what is left: '42.25' -> (42, .25),
+    '.5' and '0.5' -> (0, .5), '1' -> (1, 0.0).  A seed outside 0 .. 2^32 - 1 is a ValueError (the reference truncates it)."""
+    import re
+    m = re.match(r"\s*([+-]?\d+)?", text)
+    seed = int(m.group(1)) if m.group(1) else 0
+    rest = text[m.end():] if m.group(1) else text
+    f = re.match(r"\s*[+-]?(?:\d+\.?\d*|\.\d+)(?:[eE][+-]?\d+)?", rest)
+    frac = float(f.group(0)) if f else 0.0
+    if seed < 0 or seed > 0xffffffff:
+        raise ValueError("subsampling seed %d is outside 0 .. 4294967295" % seed)
+    return seed, frac
+
+
+_hip = None
+
+
+def _hip_runtime():
+    """The HIP runtime libmsnv.so is bound to, for the device buffer subsample_records hands the library."""
+    global _hip
+    if _hip is None:
+        _hip = C.CDLL("libamdhip64.so")
+        _hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        _hip.hipFree.argtypes = [C.c_void_p]
+        _hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    return _hip
+
+
+def subsample_records(ctx, streams, seed, frac, on_device=False, sizes=None):
+    """The reads of several record streams that `qaCompute -a SEED.FRAC` keeps, on the device (msnv_records_subsample_device): streams = uint8
+    arrays (or device addresses with sizes= and on_device=True).  Returns (kept streams as bytes, counts[n][2] = kept, dropped as int64
+    array, kernel milliseconds).  frac <= 0: nothing is launched -- host streams come back as they are (device ones as None), counts are 0."""
+    n = len(streams)
+    if on_device:
+        keep, ptrs, nb = None, [int(p) for p in streams], [int(x) for x in sizes]
+    else:
+        keep = [np.ascontiguousarray(r, dtype=np.uint8) for r in streams]
+        ptrs, nb = [b.ctypes.data for b in keep], [b.size for b in keep]
+    pa = (C.c_void_p * max(1, n))(*ptrs)
+    sa = (C.c_uint64 * max(1, n))(*nb)
+    oo = (C.c_uint64 * max(1, n))(); ob = (C.c_uint64 * max(1, n))(); cn = (C.c_uint64 * max(1, 2 * n))()
+    ms = C.c_double()
+    word = subsample_seed_word(seed)
+    cap = sum((x + 31) & ~15 for x in nb)
+    if not frac > 0:
+        check(lib.msnv_records_subsample_device(ctx._h, pa, sa, n, 1 if on_device else 0, word, float(frac), None, 0, oo, ob, cn, C.byref(ms)))
+        return [None if on_device else b.tobytes() for b in (keep or [None] * n)], np.zeros((n, 2), np.int64), ms.value
+    hip = _hip_runtime()
+    p = C.c_void_p()
+    if hip.hipMalloc(C.byref(p), max(16, cap)) != 0:
+        raise MemoryError("hipMalloc of %d bytes failed" % cap)
+    try:
+        check(lib.msnv_records_subsample_device(ctx._h, pa, sa, n, 1 if on_device else 0, word, float(frac), p, cap, oo, ob, cn, C.byref(ms)))
+        got = np.zeros(max(16, cap), np.uint8)
+        if hip.hipMemcpy(got.ctypes.data, p, max(16, cap), 2) != 0:
+            raise RuntimeError("hipMemcpy of the kept records failed")
+    finally:
+        hip.hipFree(p)
+    out = [got[oo[i]:oo[i] + ob[i]].tobytes() for i in range(n)]
+    return out, np.array(list(cn)[:2 * n], dtype=np.int64).reshape(n, 2), ms.value
+
+
+def subsample_records_host(records, seed, frac):
+    """One stream on a host thread (msnv_records_subsample): (kept bytes, (kept, dropped))."""
+    rec = np.ascontiguousarray(records, dtype=np.uint8)
+    out = np.empty(max(1, rec.size), dtype=np.uint8)
+    ob = C.c_uint64(); cn = (C.c_uint64 * 2)()
+    check(lib.msnv_records_subsample(rec.ctypes.data, rec.size, subsample_seed_word(seed), float(frac), out.ctypes.data, C.byref(ob), cn))
+    return (out[:ob.value].tobytes() if frac > 0 else rec.tobytes()), (int(cn[0]), int(cn[1]))
 
 
 def contig_bases(records, n_contigs, into=None):

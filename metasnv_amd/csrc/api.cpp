@@ -185,6 +185,30 @@ static bool pack_on_device(const msnv_dataset *ds) {
     if (!ds->ctx) return false;
     return !knob::pack_on_host();                        // (per call: tests switch it)
 }
+// The read subsampler of a dataset (devsub.h).  On the device route the seam is add_streams_device (bamfeed.cpp); where the dataset packs on
+// host threads it is pack_one_sample below, which every such call site goes through.  The entry points that cannot subsample refuse.
+extern "C" int msnv_dataset_set_subsample(msnv_dataset *ds, uint32_t word, double frac) {
+    clear_error();
+    if (!ds) return fail(MSNV_EINVAL, "msnv_dataset_set_subsample: NULL dataset");
+    if (int rc = check_open(ds, true)) return rc;
+    if (!ds->samples.empty() || !ds->staged.empty()) return fail(MSNV_EINVAL, "msnv_dataset_set_subsample: the dataset already holds samples (set it before the first one is added)");
+    if (frac != frac) return fail(MSNV_EINVAL, "msnv_dataset_set_subsample: the fraction is not a number");
+    ds->sub = Subsample{};
+    if (frac > 0) { ds->sub.on = true; ds->sub.word = word; ds->sub.frac = frac; ds->sub.threshold = sub_threshold(frac); }
+    return MSNV_OK;
+}
+static int refuse_subsampled(const msnv_dataset *ds, const char *who) {
+    if (!ds->sub.on) return MSNV_OK;
+    return fail(MSNV_EINVAL, "%s: the dataset subsamples its reads (msnv_dataset_set_subsample), which this entry point does not do", who);
+}
+static int pack_one_sample(const msnv_dataset &ds, const uint8_t *rec, uint64_t n_bytes, SampleCols &sc) {
+    if (!ds.sub.on) return pack_sample(ds, rec, n_bytes, sc);
+    std::vector<uint8_t> kept((size_t)n_bytes);
+    uint64_t kept_bytes = 0, counts[2];
+    if (int rc = records_subsample(rec, n_bytes, ds.sub.word, ds.sub.threshold, kept.data(), &kept_bytes, counts)) return rc;
+    return pack_sample(ds, kept.data(), kept_bytes, sc);
+}
+
 extern "C" int msnv_dataset_add_sample_records_device(msnv_dataset *ds, const void *const *dev_records, const uint64_t *n_bytes, int32_t n) {
     clear_error();
     if (!ds || n < 0 || (n && (!dev_records || !n_bytes))) return fail(MSNV_EINVAL, "msnv_dataset_add_sample_records_device: bad argument");
@@ -198,6 +222,7 @@ extern "C" int msnv_dataset_add_sample_records_resident(msnv_dataset *ds, void *
     clear_error();
     if (!ds || n < 0 || (n && (!dev_buffer || !offsets || !n_bytes))) return fail(MSNV_EINVAL, "msnv_dataset_add_sample_records_resident: bad argument");
     if (int rc = check_open(ds)) return rc;
+    if (int rc = refuse_subsampled(ds, "msnv_dataset_add_sample_records_resident")) return rc;
     if (!ds->ctx) return fail(MSNV_ENODEV, "msnv_dataset_add_sample_records_resident: the dataset has no device context");
     if (reinterpret_cast<uintptr_t>(dev_buffer) & 15u) return fail(MSNV_EINVAL, "msnv_dataset_add_sample_records_resident: the buffer must start on 16 bytes");
     uint64_t prev_end = 0;
@@ -218,7 +243,7 @@ extern "C" int msnv_dataset_add_sample_records(msnv_dataset *ds, const uint8_t *
     if (pack_on_device(ds)) return add_streams_device(ds, &records, &n_bytes, 1, false);
     ds->samples.emplace_back();
     int rc;
-    try { rc = pack_sample(*ds, records, n_bytes, ds->samples.back()); }
+    try { rc = pack_one_sample(*ds, records, n_bytes, ds->samples.back()); }
     catch (const std::exception &e) { rc = fail(MSNV_ENOMEM, "packing a sample failed: %s", e.what()); }      // nothing is thrown across the C ABI
     if (rc) ds->samples.pop_back();
     return rc;
@@ -233,7 +258,7 @@ extern "C" int msnv_dataset_add_sample_records_many(msnv_dataset *ds, const uint
     const size_t first = ds->samples.size();
     ds->samples.resize(first + (size_t)n);
     const int rc = for_each_index(0, (size_t)n, pool_threads(host_threads, n), 1,
-                                  [&](size_t i) { return pack_sample(*ds, records[i], n_bytes[i], ds->samples[first + i]); },
+                                  [&](size_t i) { return pack_one_sample(*ds, records[i], n_bytes[i], ds->samples[first + i]); },
                                   [](size_t i) { return "packing sample " + std::to_string(i) + " failed"; });
     if (rc) ds->samples.resize(first);
     return rc;
@@ -323,6 +348,7 @@ extern "C" int msnv_dataset_deal_bams_device(msnv_dataset *ds, const char *const
                                              int32_t cov_min_mapq, uint8_t *out, uint64_t capacity, uint64_t gap, uint64_t *part_bytes, msnv_sample_stats *stats, uint64_t *record_bytes) {
     clear_error();
     if (!ds || n < 0 || (n && (!bam_paths || !part_bytes || !stats || !record_bytes)) || !contig_owner) return fail(MSNV_EINVAL, "msnv_dataset_deal_bams_device: bad argument");
+    if (int rc = refuse_subsampled(ds, "msnv_dataset_deal_bams_device")) return rc;
     if (!ds->ctx) return fail(MSNV_ENODEV, "msnv_dataset_deal_bams_device needs a dataset with a device context");
     if (n == 0) return MSNV_OK;
     msnv_ctx *const fc = ds->feed_ctx ? ds->feed_ctx : ds->ctx;      // (msnv_dataset_set_feed_ctx: a round ahead of the dataset's own context)
@@ -352,6 +378,7 @@ extern "C" int msnv_dataset_inflate_bams_device(msnv_dataset *ds, const char *co
                                                 uint64_t *rec_off, uint64_t *rec_bytes, msnv_sample_stats *stats, uint64_t *contig_bases) {
     clear_error();
     if (!ds || n < 0 || (n && (!bam_paths || !rec_off || !rec_bytes || !stats || !out))) return fail(MSNV_EINVAL, "msnv_dataset_inflate_bams_device: bad argument");
+    if (int rc = refuse_subsampled(ds, "msnv_dataset_inflate_bams_device")) return rc;
     if (!ds->ctx) return fail(MSNV_ENODEV, "msnv_dataset_inflate_bams_device needs a dataset with a device context");
     if (n == 0) return MSNV_OK;
     msnv_ctx *const fc = ds->feed_ctx ? ds->feed_ctx : ds->ctx;
@@ -395,7 +422,7 @@ extern "C" int msnv_dataset_add_sample_bams(msnv_dataset *ds, const char *const 
     auto name_of = [&](size_t i) { return std::string(bam_paths[i]); };
     auto pack_one = [&](size_t i, const uint8_t *data, uint64_t size, const BamHeader &h, uint64_t rec_off) -> int {
         if (int rc = check_header(*ds, h, bam_paths[i])) return rc;
-        return pack_sample(*ds, data + rec_off, size - rec_off, ds->samples[first + i]);
+        return pack_one_sample(*ds, data + rec_off, size - rec_off, ds->samples[first + i]);
     };
     int rc;
     if (want_device_inflate(ds->ctx, bam_paths, n, nthreads)) {
@@ -480,7 +507,7 @@ extern "C" int msnv_dataset_add_synth_samples(msnv_dataset *ds, const msnv_synth
     const int rc = for_each_index(0, (size_t)count, nthreads, 1, [&](size_t i) -> int {
         thread_local std::vector<uint8_t> rec;                       // (a worker's buffer, reused from sample to sample)
         synth_sample_records(*p, first + (int)i, contigs, rec);
-        return pack_sample(*ds, rec.data(), rec.size(), ds->samples[base + i]);
+        return pack_one_sample(*ds, rec.data(), rec.size(), ds->samples[base + i]);
     }, name_of);
     if (rc) { ds->samples.resize(base); return fail(rc, "packing a synthetic sample failed"); }
     return MSNV_OK;
@@ -1088,6 +1115,21 @@ extern "C" int msnv_records_deal_device(msnv_ctx *ctx, const uint8_t *const *str
     catch (const std::exception &e) { return fail(MSNV_ENOMEM, "msnv_records_deal_device: %s", e.what()); }
 }
 
+extern "C" int msnv_records_subsample_device(msnv_ctx *ctx, const uint8_t *const *streams, const uint64_t *n_bytes, int32_t n, int32_t on_device, uint32_t word, double frac,
+                                             uint8_t *out, uint64_t capacity, uint64_t *out_off, uint64_t *out_bytes, uint64_t *counts, double *ms_kernel) {
+    clear_error();
+    if (ms_kernel) *ms_kernel = 0;
+    if (!ctx || n < 0 || (n && (!streams || !n_bytes || !out_off || !out_bytes || !counts))) return fail(MSNV_EINVAL, "msnv_records_subsample_device: bad argument");
+    for (int i = 0; i < n; ++i) if (n_bytes[i] && !streams[i]) return fail(MSNV_EINVAL, "msnv_records_subsample_device: stream %d is NULL", i);
+    if (!(frac > 0)) {                                              // no subsampling: every stream is its own output -- nothing is launched, read or copied
+        for (int i = 0; i < n; ++i) { out_off[i] = ~0ull; out_bytes[i] = n_bytes[i]; counts[2 * i] = counts[2 * i + 1] = 0; }
+        return MSNV_OK;
+    }
+    if (n && !out) return fail(MSNV_EINVAL, "msnv_records_subsample_device: NULL output");
+    try { return records_subsample_device(ctx, streams, n_bytes, n, on_device != 0, INT32_MAX, word, sub_threshold(frac), out, capacity, out_off, out_bytes, counts, ms_kernel); }
+    catch (const std::exception &e) { return fail(MSNV_ENOMEM, "msnv_records_subsample_device: %s", e.what()); }
+}
+
 extern "C" int msnv_records_contig_bases(const uint8_t *records, uint64_t n_bytes, int32_t n_contigs, uint64_t *bases) {
     clear_error();
     if ((n_bytes && !records) || n_contigs < 0 || (n_contigs && !bases)) return fail(MSNV_EINVAL, "msnv_records_contig_bases: bad argument");
@@ -1275,8 +1317,8 @@ extern "C" int msnv_call(msnv_ctx *ctx, const msnv_call_args *a) {
     return rc;
 }
 
-extern "C" int msnv_coverage_ex(msnv_ctx *ctx, const msnv_cov_ex_args *a) {
-    clear_error();
+// qaCompute's one-BAM run with its extras; `frac` > 0: of the reads the subsampler keeps (msnv_coverage_sub)
+static int coverage_ex_run(msnv_ctx *ctx, const msnv_cov_ex_args *a, uint32_t word, double frac) {
     if (!ctx || !a || !a->bam_path || !a->out_cov_path || !a->out_detail_path) return fail(MSNV_EINVAL, "msnv_coverage_ex: NULL argument");
     if (a->window < 0 || (a->window > 0 && !a->out_profile_path) || (a->regions_path && !a->out_specific_path)) return fail(MSNV_EINVAL, "msnv_coverage_ex: bad argument");
     msnv_params p;
@@ -1302,7 +1344,8 @@ extern "C" int msnv_coverage_ex(msnv_ctx *ctx, const msnv_cov_ex_args *a) {
         msnv_cov_extras what{};
         what.want_median = a->want_median; what.window = a->window; what.n_regions = (uint32_t)rc_contig.size();
         what.region_contig = rc_contig.data(); what.region_start = rc_start.data(); what.region_end = rc_end.data();
-        rc = msnv_dataset_add_sample_bam(ds, a->bam_path);
+        rc = msnv_dataset_set_subsample(ds, word, frac);
+        if (!rc) rc = msnv_dataset_add_sample_bam(ds, a->bam_path);
         if (!rc) rc = msnv_dataset_finalize(ds);
         if (!rc) rc = msnv_coverage_run(ds, nullptr);
         if (!rc) rc = msnv_coverage_extras_run(ds, &what);
@@ -1312,9 +1355,12 @@ extern "C" int msnv_coverage_ex(msnv_ctx *ctx, const msnv_cov_ex_args *a) {
         return rc;
     } catch (const std::exception &e) { return fail(MSNV_ENOMEM, "msnv_coverage_ex: %s", e.what()); }
 }
-
-extern "C" int msnv_coverage(msnv_ctx *ctx, const msnv_cov_args *a) {
+extern "C" int msnv_coverage_ex(msnv_ctx *ctx, const msnv_cov_ex_args *a) {
     clear_error();
+    return coverage_ex_run(ctx, a, 0u, 0.0);
+}
+
+static int coverage_plain_run(msnv_ctx *ctx, const msnv_cov_args *a, uint32_t word, double frac) {
     if (!ctx || !a || !a->bam_path || !a->out_cov_path || !a->out_detail_path) return fail(MSNV_EINVAL, "msnv_coverage: NULL argument");
     msnv_params p;
     msnv_params_default(&p);
@@ -1323,10 +1369,27 @@ extern "C" int msnv_coverage(msnv_ctx *ctx, const msnv_cov_args *a) {
     msnv_dataset *ds = nullptr;
     int rc = msnv_dataset_create_from_files(ctx, a->bam_path, nullptr, &p, &ds);
     if (rc) return rc;
-    rc = msnv_dataset_add_sample_bam(ds, a->bam_path);
+    rc = msnv_dataset_set_subsample(ds, word, frac);
+    if (!rc) rc = msnv_dataset_add_sample_bam(ds, a->bam_path);
     if (!rc) rc = msnv_dataset_finalize(ds);
     if (!rc) rc = msnv_coverage_run(ds, nullptr);
     if (!rc) rc = msnv_write_coverage(ds, 0, a->out_cov_path, a->out_detail_path);
     msnv_dataset_destroy(ds);
     return rc;
+}
+extern "C" int msnv_coverage(msnv_ctx *ctx, const msnv_cov_args *a) {
+    clear_error();
+    return coverage_plain_run(ctx, a, 0u, 0.0);
+}
+
+// `qaCompute -a`: msnv_coverage_ex over the reads the subsampler keeps (devsub.h); without -m / -p / -x the run of msnv_coverage, as the tool
+// has always taken it.  frac <= 0: no subsampling -- the same run as without this entry.
+extern "C" int msnv_coverage_sub(msnv_ctx *ctx, const msnv_cov_ex_args *a, uint32_t word, double frac) {
+    clear_error();
+    if (!a) return fail(MSNV_EINVAL, "msnv_coverage_sub: NULL argument");
+    if (frac != frac) return fail(MSNV_EINVAL, "msnv_coverage_sub: the fraction is not a number");
+    if (a->want_median || a->window || a->regions_path) return coverage_ex_run(ctx, a, word, frac);
+    msnv_cov_args p{};
+    p.bam_path = a->bam_path; p.max_cov = a->max_cov; p.min_mapq = a->min_mapq; p.out_cov_path = a->out_cov_path; p.out_detail_path = a->out_detail_path;
+    return coverage_plain_run(ctx, &p, word, frac);
 }

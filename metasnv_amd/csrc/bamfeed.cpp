@@ -78,6 +78,22 @@ int check_header(const msnv_dataset &ds, const BamHeader &h, const char *path) {
 }
 
 // ---------------------------------------------------------------------------------- into the device pack
+// A round's streams through the subsampler (msnv_dataset_set_subsample; devsub.hip) into a device buffer of the round's own: the round then
+// packs `kept` / `kept_bytes`, device-resident streams.  The buffer lives until the round has staged them (devpack_add_round copies and waits).
+struct SubRound { void *buf = nullptr; std::vector<const uint8_t *> kept; std::vector<uint64_t> kept_bytes; ~SubRound() { if (buf) dev_free(buf); } };
+static int subsample_round(msnv_dataset *ds, const uint8_t *const *records, const uint64_t *n_bytes, int n, bool streams_on_device, SubRound &sr) {
+    std::vector<uint64_t> off((size_t)n), counts(2 * (size_t)n);
+    sr.kept.assign((size_t)n, nullptr); sr.kept_bytes.assign((size_t)n, 0);
+    uint64_t need = 0;
+    sub_layout(n_bytes, n, nullptr, &need);
+    if (int rc = dev_set_device(ds->ctx->device)) return rc;
+    if (int rc = dev_alloc(&sr.buf, need + 256, nullptr)) return rc;
+    if (int rc = records_subsample_device(ds->ctx, records, n_bytes, n, streams_on_device, (int)ds->names.size(), ds->sub.word, ds->sub.threshold, static_cast<uint8_t *>(sr.buf), need,
+                                          off.data(), sr.kept_bytes.data(), counts.data(), nullptr)) return rc;
+    for (int i = 0; i < n; ++i) sr.kept[(size_t)i] = static_cast<const uint8_t *>(sr.buf) + off[(size_t)i];
+    return MSNV_OK;
+}
+
 int add_streams_device(msnv_dataset *ds, const uint8_t *const *records, const uint64_t *n_bytes, int n, bool streams_on_device, const uint8_t *in_place_base, uint64_t in_place_capacity) {
     HostTimerScope ts(HT_PACK_DEVICE_WALL);
     fin_trace_reset();
@@ -91,7 +107,11 @@ int add_streams_device(msnv_dataset *ds, const uint8_t *const *records, const ui
         for (int i0 = 0; i0 < n && !rc;) {
             int i1 = i0; uint64_t b = 0;
             while (i1 < n && i1 - i0 < 2048 && (i1 == i0 || b + n_bytes[i1] <= round_bytes)) { b += n_bytes[i1]; ++i1; }
-            rc = devpack_add_round(*ds, first + (size_t)i0, records + i0, n_bytes + i0, i1 - i0, streams_on_device, in_place_base, in_place_capacity);
+            if (ds->sub.on) {                                     // (the one flag test of a dataset that does not subsample)
+                SubRound sr;
+                rc = subsample_round(ds, records + i0, n_bytes + i0, i1 - i0, streams_on_device, sr);
+                if (!rc) rc = devpack_add_round(*ds, first + (size_t)i0, sr.kept.data(), sr.kept_bytes.data(), i1 - i0, true);
+            } else rc = devpack_add_round(*ds, first + (size_t)i0, records + i0, n_bytes + i0, i1 - i0, streams_on_device, in_place_base, in_place_capacity);
             i0 = i1;
         }
     } catch (const std::exception &e) { rc = fail(MSNV_ENOMEM, "packing on the device failed: %s", e.what()); }

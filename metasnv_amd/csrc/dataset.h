@@ -18,6 +18,7 @@
 #include <utility>
 #include <vector>
 
+#include "devsub.h"
 #include "msnv_internal.h"
 
 namespace msnv {
@@ -246,6 +247,7 @@ struct msnv_dataset {
     // samples
     std::vector<msnv::SampleCols> samples;
     bool finalized = false;
+    msnv::Subsample sub;            // msnv_dataset_set_subsample: every stream handed to the dataset loses the reads the rule drops before it is packed (devsub.h)
     bool poisoned = false;          // an add_* call failed AFTER rounds of the device pack had been appended (bamfeed.cpp: add_streams_device): nothing more is added or finalized
     // layout
     std::vector<uint32_t> tile_base;       // per contig (selected only; others = UINT32_MAX)

@@ -1,5 +1,6 @@
 // metasnv_amd/csrc/devrec.h -- a BAM record on the device and the sub-segment walk over a stream's records: what more than one of devscan.hip (the
-// record scan), devdeal.hip (the dealer) and devpack.hip (the round of the per-read stage) inlines or declares (HIP only; no kernel lives here).
+// record scan), devdeal.hip (the dealer), devsub.hip (the read subsampler) and devpack.hip (the round of the per-read stage) inlines or declares
+// (HIP only; no kernel lives here).
 //   Rec, rec_load .. cg_match     the fixed part of an alignment record read from HBM, the CIGAR operations' classes
 //   SubStream .. guess_entry      a stream's sub-segments: which bytes one holds, where the chain of records enters them (a guess)
 //   scan_sub_body<Walk>, scan_fix_body<Walk>, chain_before     the bodies of the walk and the fix kernels over a Walk: WalkPlain (devscan.hip: offsets) or

@@ -179,7 +179,8 @@ struct Prim {
     // order in which the compiler meets their first use; the templates above are instantiated wherever they are called, so devfin.hip's own
     // exclusive scan of uint32_t (the chunk cut) is in both objects.  Forms with one owner: the running maximum of the walks' ends
     // (SubWalk::scan_stops, behind which both routes reach it) and scan_sub_walk's exclusive scan over uint32_t * in devscan.hip; the sort of
-    // uint32_t pairs and the scan of uint32_t into unsigned long long in devdeal.hip; the scans of RecCnt and SubCnt in devpack.hip.
+    // uint32_t pairs in devdeal.hip; the scans of RecCnt and SubCnt in devpack.hip.  The scan of uint32_t into unsigned long long has two
+    // users, devdeal.hip and devsub.hip (the sizes of the records a call keeps), and is in both objects.
     int scan32(const uint32_t *in, uint32_t *out, size_t n, bool inclusive_);
     int sort64(unsigned long long *kin, unsigned long long *kout, uint32_t *vin, uint32_t *vout, size_t n, unsigned end_bit);
     int scan64(const uint32_t *in, unsigned long long *out, size_t n);

@@ -763,6 +763,9 @@ def feed_sharded(ds, bam_paths, owner, cov_min_mapq=1, batch=1, read_records=Non
     its contig mask and metrics["owner"] the assignment."""
     if _dist is None and read_records is None:
         return _feed_one_process(ds, bam_paths, owner, batch, metrics, plan, ctx_when_ready)
+    if getattr(ds, "subsample", None):
+        # the dealt records enter the datasets through entry points that do not subsample (core.Dataset.set_subsample): refused, never ignored
+        raise ValueError("the N-rank feed does not subsample reads (Dataset.set_subsample is set): run on one rank")
     feed = Feed(ds, bam_paths, owner, cov_min_mapq, batch, read_records, metrics, pack_threads, feed_overlap)
     if owner is None:
         feed.plan_owners(plan)
@@ -882,7 +885,8 @@ def gather_coverage_root(acc, stats=None, rows=None, shape=None):
 
 
 def resident_project_run(ctx, first_bam, fasta_path, bam_paths, params, batch=1, want_coverage=True, ann_path=None,
-                         after_coverage=None, species_weight=None, make_dataset=None, read_records=None, run_passes=None, inflate_after_context=False, feed_overlap=None):
+                         after_coverage=None, species_weight=None, make_dataset=None, read_records=None, run_passes=None, inflate_after_context=False, feed_overlap=None,
+                         subsample=None):
     """ONE resident dataset per rank for a whole metaSNV.py run, whatever the number of ranks and splits (the reference forks
     one qaCompute process per BAM, metaSNV.py:55-78, and one `mpileup | snpCall` process per split, :196-221, each of which
     inflates every BAM again): contigs are sharded over the ranks by species (LPT on length x coverage), the BAMs are dealt to
@@ -893,6 +897,8 @@ def resident_project_run(ctx, first_bam, fasta_path, bam_paths, params, batch=1,
     it they are fixed after the first decode round (feed_sharded).  make_dataset() / read_records(path) replace the BAM-file
     dataset and reader (bench.py's strong-scaling mode feeds synthetic record streams through this very function);
     run_passes(ds) -> stats replaces the single ds.run() (bench.py times K passes there).
+
+    subsample = (seed, frac): the reads of every BAM that `qaCompute -a seed.frac` keeps, for coverage and calls alike (one rank only).
 
     after_coverage(result) is called on every rank between the two passes -- the driver writes cov/, the tables and the
     split plan there -- and must contain its own barriers.  Returns a dict:
@@ -906,6 +912,11 @@ def resident_project_run(ctx, first_bam, fasta_path, bam_paths, params, batch=1,
     t_open = time.perf_counter()
     ds = make_dataset() if make_dataset else core.Dataset.from_files(None if lazy_ctx else ctx, first_bam, fasta_path, params)
     t_open = time.perf_counter() - t_open
+    if subsample is not None:
+        if _world > 1:
+            ds.close()
+            raise ValueError("subsampling reads is not built for more than one rank")
+        ds.set_subsample(*subsample)
     names, lengths = ds.names, ds.lengths
     owner = None
     if species_weight is not None or _dist is None:
